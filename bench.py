@@ -12,7 +12,11 @@ reconstruction of their own samples (`config.parity`) -- and measures the same c
 (`config.c_abi_fps`, PCIe inclusive, minimum of three runs, never `value`).  Several steps are in flight in the timed region (`--depth`, a HIP-stream frame
 queue of batch objects: cfhd_amd_batch_submit / _wait) on the runtime's default hardware queues; the same with GPU_MAX_HW_QUEUES=16 is a side figure.
 
-  python bench.py --gpus 1 --steps 20 --warmup 3 [--workload 1080p|2160p]
+A plain run does only what `value` and `ms_per_step` need: set-up, warm-up, the timed steps, the outputs of the last step (--dump-outputs DIR) and the line.
+Everything else named above -- parity check, `roofline` (its launch times come from passes run one at a time behind the timed region), the other workloads,
+the 16-queue side figure, host-fed and C-ABI figures, cpu_baseline -- runs with --full.
+
+  python bench.py --gpus 1 --steps 20 --warmup 3 [--workload 1080p|2160p] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
 import argparse, ctypes, hashlib, json, os, struct, sys, threading, time
@@ -287,11 +291,59 @@ def batch_api():
     return L
 
 
-def measure(workload, steps, warmup, batch, unique, threads, rank, world, barrier, reduce_max, depth=1, geometry=None, all_gather=None):
+DUMP_FRAMES = 3                 # --dump-outputs: the sample and the decoded picture of three frames of the last step (first, middle, last of its batch) ...
+DUMP_SAMPLE_BYTES = 1 << 20     # ... a sample whole up to 1 Mi bytes (4 MiB as float32), beyond that a fixed, seeded selection of its bytes
+DUMP_PICTURE_WORDS = 4 << 20    # ... a picture whole up to 4 Mi words (16 MiB as float32: a 1080p YUY2 picture is whole), beyond that a fixed, seeded selection
+
+
+def _fixed_selection(a, n, seed):
+    """`a` flattened, whole when it has at most n elements, else n of them at positions a generator seeded with `seed` draws (sorted): the same
+    positions in every run for the same length."""
+    a = a.reshape(-1)
+    if a.size <= n:
+        return a
+    import numpy as np
+    return a[np.sort(np.random.default_rng(seed).choice(a.size, n, replace=False))]
+
+
+def dump_outputs(L, b, wl, W, H, batch, out_dir):
+    """What the caller of the timed path receives from its last step, as float32 / float64 .npy files in out_dir (60 MiB at most): the length of every
+    sample; the sample of DUMP_FRAMES frames, with the clock-dependent metadata payloads (GUID / DATE / TIME / TIMC) and the per-call frame counters zeroed
+    as the parity check compares them; and, for the encode+decode workloads, those frames' decoded pictures (bytes for 8-bit YUY2, 16-bit words otherwise).
+    Returns the file names."""
+    import numpy as np
+    import cfhd_testlib as T
+    os.makedirs(out_dir, exist_ok=True)
+    names = []
+    def save(name, arr):
+        np.save(os.path.join(out_dir, name + ".npy"), arr); names.append(name + ".npy")
+    sizes = []
+    for i in range(batch):
+        p = ctypes.c_void_p(); sz = ctypes.c_size_t()
+        assert L.cfhd_amd_batch_get_sample(b, i, ctypes.byref(p), ctypes.byref(sz)) == 0
+        sizes.append(sz.value)
+    save("sample_sizes", np.array(sizes, dtype=np.float64))
+    bpp = wl["bpp"]
+    for i in sorted({0, batch // 2, batch - 1})[:DUMP_FRAMES]:
+        p = ctypes.c_void_p(); sz = ctypes.c_size_t()
+        assert L.cfhd_amd_batch_get_sample(b, i, ctypes.byref(p), ctypes.byref(sz)) == 0
+        sample = np.frombuffer(T.mask_volatile_metadata(normalise_counters(ctypes.string_at(p, sz.value))), dtype=np.uint8)
+        save("sample_%04d" % i, _fixed_selection(sample, DUMP_SAMPLE_BYTES, i).astype(np.float32))
+        if wl["mode"] != 0: continue
+        img = np.zeros(H * W * bpp, dtype=np.uint8)
+        assert L.cfhd_amd_batch_download_output(b, i, img.ctypes.data_as(ctypes.c_void_p), W * bpp) == 0
+        words = img if wl["fmt"] == "YUY2" else img.view(np.uint16)
+        save("decoded_%04d" % i, _fixed_selection(words, DUMP_PICTURE_WORDS, i).astype(np.float32))
+    return names
+
+
+def measure(workload, steps, warmup, batch, unique, threads, rank, world, barrier, reduce_max, depth=1, geometry=None, all_gather=None, full=True, dump_dir=None):
     """One workload through the batched device-resident path: frames generated and uploaded, `warmup` untimed steps, `steps` timed ones between
     barriers, parity check of what was timed on rank 0.  Returns (line fields of this workload, frames, pitch).
     depth: batches in flight (the frame queue, cfhd_amd_batch_submit / _wait): step k + 1 is submitted while step k is still on the GPU; every step is still one
-    complete pass over one batch of `batch` frames, and all `steps` of them start and finish inside the timed region."""
+    complete pass over one batch of `batch` frames, and all `steps` of them start and finish inside the timed region.
+    full=False (a plain bench run): no parity check and no passes one at a time behind the timed region, so no `roofline`.  dump_dir: rank 0 writes the outputs
+    of the last timed step there (dump_outputs) before anything else runs on its batch."""
     import numpy as np
     import cfhd_testlib as T
     wl = dict(WORKLOADS[workload])
@@ -364,9 +416,10 @@ def measure(workload, steps, warmup, batch, unique, threads, rank, world, barrie
     # times: config.kernel_ms_per_step).  The roofline of a kernel is a statement about the kernel: right behind the timed region the same pass runs ALONE_STEPS more
     # times one at a time on the batch of the last step, with the same events -- those launch times feed `roofline` (and agree with a rocprofv3 trace of --depth 1).
     # What was timed is what gets checked: the parity check reads the samples and pictures the LAST TIMED pass of every batch in flight left behind, before
-    # anything runs again on them (a solo pass afterwards could hide corruption between concurrent passes).
+    # anything runs again on them (a solo pass afterwards could hide corruption between concurrent passes).  The outputs of the last step are written first.
+    dumped = dump_outputs(L, b, wl, W, H, batch, dump_dir) if dump_dir and rank == 0 else None
     parity = None
-    if rank == 0 and not probing and not os.environ.get("CFHD_BENCH_NO_PARITY"):      # (CFHD_BENCH_NO_PARITY: timing probes of builds that produce no valid output, tools/gpu_r05_f.sh; the line then says parity_checked false)
+    if full and rank == 0 and not probing and not os.environ.get("CFHD_BENCH_NO_PARITY"):      # (CFHD_BENCH_NO_PARITY: timing probes of builds that produce no valid output, tools/gpu_r05_f.sh; the line then says parity_checked false)
         last = (steps - 1) % depth
         ref_cache = {}
         parity = parity_check(L, slots[last], frames, pitch, W, H, rank, wl, batch, nuniq, ref_cache=ref_cache)
@@ -376,7 +429,7 @@ def measure(workload, steps, warmup, batch, unique, threads, rank, world, barrie
             parity.setdefault("other_batches_in_flight", []).append(other["frames_checked"])
             parity["samples_checked"] += other["samples_checked"]
     kms_alone = None
-    if depth > 1:
+    if full and depth > 1:
         ALONE_STEPS = 8      # (three until round 6: the four longest kernels of a 1080p step are within 4 % of each other, and the longest one names the roofline)
         alone = {name: [] for name, _ in KERNELS}
         for _ in range(ALONE_STEPS):
@@ -466,6 +519,10 @@ def measure(workload, steps, warmup, batch, unique, threads, rank, world, barrie
                          "algorithmic_bytes_per_launch": int(algo[dom] * batch),
                          "other_kernels_gbs": {k: round(algo[k] * batch / (kms[k] * 1e-3) / 1e9, 1) for k in algo if kms[k] > 0 and k != dom}},
         }
+        if not full:                                     # a plain run times no pass by itself: the roofline is a --full figure
+            del line["roofline"]
+        if dumped:
+            line["config"]["outputs_of_the_last_step"] = {"dir": os.path.abspath(dump_dir), "files": dumped}
     for q in slots: L.cfhd_amd_batch_destroy(q)
     return line, frames, pitch
 
@@ -570,6 +627,9 @@ def main():
     ap.add_argument("--no-c-abi", action="store_true")
     ap.add_argument("--no-other-workloads", action="store_true", help="skip the short runs of the other BASELINE configs behind the timed region")
     ap.add_argument("--depth", type=int, default=DEFAULT_DEPTH, help="steps in flight (frame queue of batch objects: cfhd_amd_batch_submit / _wait); 1 = one synchronous pass after the other")
+    ap.add_argument("--full", action="store_true", help="everything beyond value and ms_per_step: parity check, roofline, the other workloads, the 16-queue, "
+                    "host-fed and C-ABI figures, cpu_baseline (the --no-* options leave parts of it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (float32 / float64; see dump_outputs)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -619,8 +679,9 @@ def main():
 
     cores = os.cpu_count() or 1
     threads = args.threads or max(1, cores // world)
-    line, frames, pitch = measure(args.workload, args.steps, args.warmup, batch, args.unique, threads, rank, world, barrier, reduce_max, depth=args.depth, all_gather=all_gather)
-    if rank == 0:
+    line, frames, pitch = measure(args.workload, args.steps, args.warmup, batch, args.unique, threads, rank, world, barrier, reduce_max, depth=args.depth, all_gather=all_gather,
+                                  full=args.full, dump_dir=args.dump_outputs)
+    if rank == 0 and args.full:
         if world == 1 and args.workload == "1080p" and not args.no_other_workloads:
             # the other BASELINE configs (and north_star's 3840x2160 frames) through the same path, a few steps each, behind the timed region of the
             # headline: their own fps, dominant kernel against the roofline and parity check in the driver-run record (never part of `value`)
@@ -640,7 +701,7 @@ def main():
             import subprocess
             try:
                 out = subprocess.run([sys.executable, os.path.abspath(__file__), "--steps", str(min(args.steps, 40)), "--warmup", str(args.warmup), "--depth", str(args.depth), "--batch", str(batch),
-                                      "--no-cpu-baseline", "--no-c-abi", "--no-other-workloads"], capture_output=True, text=True, timeout=600, env=dict(os.environ, GPU_MAX_HW_QUEUES="16"))
+                                      "--full", "--no-cpu-baseline", "--no-c-abi", "--no-other-workloads"], capture_output=True, text=True, timeout=600, env=dict(os.environ, GPU_MAX_HW_QUEUES="16"))
                 side = json.loads(out.stdout.strip().splitlines()[-1])
                 line["config"]["with_16_hardware_queues"] = {"value": side["value"], "unit": "fps", "ms_per_step": side["ms_per_step"], "steps": side["steps"], "parity_checked": side["config"]["parity_checked"],
                                                              "environment": "GPU_MAX_HW_QUEUES=16 (read by the ROCm runtime when the process starts; the library then gives a pass three streams instead of two)"}
@@ -673,6 +734,7 @@ def main():
         if world == 1 and not args.no_cpu_baseline:
             fmt = getattr(T, "PIX_" + wl["fmt"].upper())
             line["cpu_baseline"] = cpu_baseline(frames[:8], pitch, W, H, fmt=fmt, enc=wl["enc"], flags=wl["flags"], decode=wl["mode"] == 0, bpp=wl["bpp"], label=wl["fmt"])
+    if rank == 0:
         print(json.dumps(line), flush=True)
     if dist is not None:
         dist.destroy_process_group()

@@ -304,3 +304,46 @@ def test_c_abi_leg_of_the_bench_spreads_over_two_devices():
         del os.environ["CFHD_CABI_BENCH"]; del os.environ["HIPEMU_DEVICES"]
     assert "error" not in r, r
     assert r["sync_encode_fps"] > 0 and r["sync_decode_fps"] > 0 and r["decode_fps_4_handles"] > 0 and r["pool_encode_fps_4_workers"] > 0 and r["round_trip_fps_pool4_plus_4_decoders"] >= 0, r      # (the round trip's window opens with warm decoders: it can stay empty at the emulator's pace)
+
+
+def _worker_plain_bench(out_dir, q):
+    """bench.py's plain run of one rank -- measure() without --full, --dump-outputs given -- on one emulated device."""
+    os.environ.update({"HIPEMU_DEVICES": "1", "CFHD_AMD_DEVICE": "0"})
+    sys.path.insert(0, ROOT)
+    import bench
+    import cfhd_testlib as T
+    with T.emulated_product():
+        line, _, _ = bench.measure("1080p", 3, 1, 5, 2, 1, 0, 1, lambda: None, lambda elapsed: elapsed, depth=2, geometry=(192, 96), full=False, dump_dir=out_dir)
+    q.put(line)
+
+
+def test_bench_plain_run_dumps_the_outputs_of_its_last_step(tmp_path):
+    """`python bench.py --dump-outputs DIR` without --full: the line has no parity check and no roofline, and DIR holds the last step's outputs as float32 / float64
+    .npy files -- every sample's length, the samples (clock fields and counters zeroed) and decoded pictures of the first, middle and last frame -- the same values
+    from two runs with the same arguments."""
+    import multiprocessing as mp
+    import cfhd_testlib as T
+    if not T.have_ref(): pytest.skip("reference .so not built (Qbist frames, the emulated product build)")
+    T.product_emulated()
+    ctx = mp.get_context("spawn")
+    dirs, lines = [str(tmp_path / "a"), str(tmp_path / "b")], []
+    for d in dirs:
+        q = ctx.Queue()
+        p = ctx.Process(target=_worker_plain_bench, args=(d, q)); p.start()
+        lines.append(q.get(timeout=600))
+        p.join(120); assert p.exitcode == 0
+    want = ["decoded_0000.npy", "decoded_0002.npy", "decoded_0004.npy", "sample_0000.npy", "sample_0002.npy", "sample_0004.npy", "sample_sizes.npy"]
+    for line, d in zip(lines, dirs):
+        assert "roofline" not in line and line["config"]["parity_checked"] is False and line["steps"] == 3 and line["ms_per_step"] > 0
+        assert sorted(line["config"]["outputs_of_the_last_step"]["files"]) == want and sorted(os.listdir(d)) == want
+        assert sum(os.path.getsize(os.path.join(d, f)) for f in want) <= 64e6
+    a = {f: np.load(os.path.join(dirs[0], f)) for f in want}
+    for f in want:
+        assert a[f].dtype in (np.float32, np.float64)
+        assert np.array_equal(a[f], np.load(os.path.join(dirs[1], f))), f
+    sizes = a["sample_sizes.npy"]
+    assert sizes.shape == (5,) and (sizes > 0).all()
+    for i in (0, 2, 4):
+        s = a["sample_%04d.npy" % i]
+        assert s.size == sizes[i] and s.min() >= 0 and s.max() <= 255 and (s == np.round(s)).all()
+        assert a["decoded_%04d.npy" % i].size == 192 * 96 * 2

@@ -1,4 +1,4 @@
-"""Fills the tables of DESIGN.md (the blocks between <!--RESULTS_TABLE--> ... markers, the HOSTFED / CABI / CPU lines) from a bench line and the PMC traffic file:
+"""Fills the tables of DESIGN.md (the blocks between <!--RESULTS_TABLE--> ... markers, the HOSTFED / CABI / CPU lines) from a `bench.py --full` line and the PMC traffic file:
    python tools/fill_design_tables.py profiles/r06_v_default_bench_line.json profiles/pmc_traffic.json
 The VALU column is SQ_INSTS_VALU / (8 x SQ_BUSY_CYCLES) of profiles/r06_u_1080p_batch512_sq_counters.txt (tools/profile_sq.sh)."""
 import json, sys

@@ -1,5 +1,5 @@
 #!/bin/bash
-# On the GPU box: a selection of the GPU tests, then the default bench without the CPU baseline / C-ABI legs; prints the kernel times.
+# On the GPU box: a selection of the GPU tests, then a plain bench line; prints the kernel times (--full among the bench.py arguments adds parity and roofline).
 #   tools/gpu_quick.sh <tag> "<pytest -k expression or empty>" [bench.py arguments]
 TAG=$1; KEXPR=$2; shift 2
 cd ${GRAFT_REPO_ROOT:-/root/repo}
@@ -15,7 +15,7 @@ try:
     d = json.loads(open("gpurun_out/${TAG}_bench.json").read().strip().splitlines()[-1])
     print("fps", d["value"], "ms/step", d["ms_per_step"], "parity", d["config"]["parity"])
     print(d["config"]["kernel_ms_per_step"])
-    print("roofline", d["roofline"]["kernel"], d["roofline"]["frac"])
+    if "roofline" in d: print("roofline", d["roofline"]["kernel"], d["roofline"]["frac"])
 except Exception as e:
     print("bench failed:", e); print(open("gpurun_out/${TAG}_bench.err").read()[-1500:])
 PY
