@@ -81,7 +81,7 @@ private:
 	bool group_ = false; GopPlan gplan_;
 	FramePlan plan_; int n_ = 0, active_ = 0, device_ = 0 /* the GPU prepare() ran on */; size_t cap_ = 0; void *stream_ = nullptr;
 	int active_frames() const { return active_ > 0 && active_ < n_ ? active_ : n_; }
-	int nbands_ = 0, total_segs_ = 0;
+	int nbands_ = 0, total_segs_ = 0; size_t tok_per_frame_ = 0;
 	std::vector<SampleTemplate> tmpl_;
 	uint8_t *d_samples_ = nullptr, *h_samples_ = nullptr;
 	uint32_t *d_sizes_ = nullptr, *h_sizes_ = nullptr;

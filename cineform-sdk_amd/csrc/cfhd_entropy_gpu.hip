@@ -77,19 +77,24 @@ int GpuEntropyEncoder::prepare_units(int nframes, int16_t *d_coeffs, size_t stri
 	build_template(hdr0, &tmpl_[0]);
 	EntHostJobs &jobs = host_->jobs;
 	host_->geom = group_ ? ent_hole_geometry(gplan_, tmpl_[0]) : ent_hole_geometry(plan, tmpl_[0]);
-	if (!ent_build_band_jobs(host_->geom, tmpl_[0], n_, d_coeffs, stride, &jobs)) return -3;
-	nbands_ = jobs.nbands; total_segs_ = (int)jobs.segjobs.size();
+	// block lists of the level-1 bands, for the geometries k_fwd_yuv422_strip_blocks serves (EncodeBatch::strip_forward): one 16-byte slot per block of the
+	// pyramid (only the slots of listed blocks are ever touched), one mask per chunk
+	const bool lists = !group_ && !plan.interlaced && plan.encoded_format == ENC_YUV422 && (plan.pixel_kind == PIX_YUY2 || plan.pixel_kind == PIX_2VUY) && plan.width % 32 == 0;
+	// Those bands are sparse (a level-1 segment of 1024 coefficients codes ~400 bits): segments of dev::ENT_SEG_L1 coefficients there, so that the fixed cost of a wave in
+	// k_ent_count_blocks / k_ent_emit is paid a quarter as often.  CFHD_AMD_L1_SEG=1024 .. 8192 (multiples of 1024): another length, for A/B runs and the sweep.
+	static const int l1_seg_env = [] { const char *e = getenv("CFHD_AMD_L1_SEG"); const int v = e ? atoi(e) : 0;
+	                                   return v >= dev::ENT_SEG && v <= dev::ENT_SEG_MAX && v % dev::ENT_SEG == 0 ? v : (int)dev::ENT_SEG_L1; }();
+	if (!ent_build_band_jobs(host_->geom, tmpl_[0], n_, d_coeffs, stride, &jobs, lists ? l1_seg_env : (int)dev::ENT_SEG)) return -3;
+	nbands_ = jobs.nbands; total_segs_ = (int)jobs.segjobs.size(); tok_per_frame_ = jobs.tok_per_frame;
 	HIPCHK(hipMalloc(&d_bands_, jobs.bands.size() * sizeof(dev::EntBandJob)));
 	HIPCHK(hipMemcpy(d_bands_, jobs.bands.data(), jobs.bands.size() * sizeof(dev::EntBandJob), hipMemcpyHostToDevice));
 	HIPCHK(hipMalloc(&d_segband_, jobs.segjobs.size() * sizeof(dev::EntSegJob)));
 	HIPCHK(hipMemcpy(d_segband_, jobs.segjobs.data(), jobs.segjobs.size() * sizeof(dev::EntSegJob), hipMemcpyHostToDevice));
 	HIPCHK(hipMalloc(&d_segs_, jobs.segjobs.size() * sizeof(dev::EntSegState)));
-	HIPCHK(hipMalloc(&d_tokens_, jobs.segjobs.size() * (size_t)dev::ENT_TOK_STRIDE * sizeof(uint32_t)));      // token lists and finished bit strings: worst case one per coefficient, only the used part is ever touched
+	HIPCHK(hipMalloc(&d_tokens_, jobs.tok_per_frame * (size_t)n_ * sizeof(uint32_t)));      // token lists and finished bit strings: worst case one per coefficient, only the used part is ever touched
 	HIPCHK(hipMalloc(&d_bandstate_, jobs.bands.size() * sizeof(dev::EntBandState)));
-	// block lists of the level-1 bands, for the geometries k_fwd_yuv422_strip_blocks serves (EncodeBatch::strip_forward): one 16-byte slot per block of the
-	// pyramid (only the slots of listed blocks are ever touched), one mask per chunk
 	static_assert((int)kBlockChunkCols == (int)dev::FWD_CHUNK_COLS_ENT, "one chunk geometry");
-	if (!group_ && !plan.interlaced && plan.encoded_format == ENC_YUV422 && (plan.pixel_kind == PIX_YUY2 || plan.pixel_kind == PIX_2VUY) && plan.width % 32 == 0) {
+	if (lists) {
 		int mask_base[kMaxChannels][kNumBands];
 		masks_per_frame_ = (size_t)block_list_layout(plan, mask_base);
 		HIPCHK(hipMalloc(&d_blocks_, stride * 2 * (size_t)n_));
@@ -140,7 +145,7 @@ int GpuEntropyEncoder::launch()
 		dirty_ = false;
 	}
 	const dev::EntTables *T = (const dev::EntTables *)d_tables_;
-	const dev::EntBatchGeom geom = { total_segs_ / n_, nbands_, coeff_stride_ };
+	const dev::EntBatchGeom geom = { total_segs_ / n_, nbands_, coeff_stride_, tok_per_frame_ };
 	const int act = active_frames(), total_segs = total_segs_ / n_ * act;      // frames 0 .. act-1 (set_active)
 	(void)hipGetLastError();
 	HIPCHK(hipEventRecord((hipEvent_t)ev_[0], st));

@@ -215,6 +215,10 @@ inline bool build_dec_index_tables(int codebook, dev::DecIdxTables *T)
 	return true;
 }
 
+// k_ent_count_blocks packs a block's slot, counted from the first band row of its span, with its 9-bit number in the span into one word: the rows a span of
+// ENT_BLK_SPAN coefficients touches hold fewer than 2^23 blocks for every level-1 band a FramePlan accepts (rows of at most kMaxFrameDim coefficients).
+static_assert(((size_t)dev::ENT_BLK_SPAN + 2u * (size_t)kMaxFrameDim) / 8u < ((size_t)1 << 23) && dev::ENT_BLK_SPAN / 8 <= 512, "block slot << 9 | block number fits 32 bits");
+
 struct EntHostJobs {
 	std::vector<dev::EntBandJob> bands;
 	std::vector<dev::EntSegJob> segjobs;
@@ -222,6 +226,7 @@ struct EntHostJobs {
 	int nbands = 0;                     // coded bands per frame
 	// segment ranges [first, count) inside one frame's table: the level-1 bands (final once the level-1 transform has run) and everything else
 	std::vector<std::pair<int, int>> ranges_l1, ranges_rest;
+	size_t tok_per_frame = 0;           // token slots of one frame's segments (EntBatchGeom::tok_per_frame)
 };
 
 // Where the holes of a template find their coefficients: the band of the pyramid behind every hole, in template order (the same for every frame of a batch).
@@ -250,20 +255,27 @@ inline std::vector<EntHoleGeom> ent_hole_geometry(const GopPlan &plan, const Sam
 	return g;
 }
 
-inline bool ent_build_band_jobs(const std::vector<EntHoleGeom> &geom, const SampleTemplate &t0, int nframes, int16_t *coeffs, size_t stride, EntHostJobs *out)
+// l1_seg: segment length of the level-1 bands that are coded with table 0 from block lists (k_ent_count_blocks; the caller opts in when it has allocated them):
+// a multiple of dev::ENT_SEG up to dev::ENT_SEG_MAX.  Every other band -- and every band by default -- has segments of dev::ENT_SEG.
+inline bool ent_build_band_jobs(const std::vector<EntHoleGeom> &geom, const SampleTemplate &t0, int nframes, int16_t *coeffs, size_t stride, EntHostJobs *out,
+                                int l1_seg = dev::ENT_SEG)
 {
 	if ((int)t0.holes.size() > dev::ENT_MAX_HOLES || (int)t0.patches.size() > kEntMaxPatches || geom.size() != t0.holes.size()) return false;
+	if (l1_seg < dev::ENT_SEG || l1_seg > dev::ENT_SEG_MAX || l1_seg % dev::ENT_SEG) return false;
 	out->bands.clear(); out->segjobs.clear(); out->ranges_l1.clear(); out->ranges_rest.clear();
+	out->tok_per_frame = 0;
 	out->band_of_hole.assign(t0.holes.size(), -1);
 	for (int f = 0; f < nframes; f++) {
 		int16_t *base = coeffs + (size_t)f * stride;
+		size_t tok_at = 0;                  // token slots of the frame's segments in front
 		for (size_t h = 0; h < t0.holes.size(); h++) {
 			const SampleTemplate::Hole &hole = t0.holes[h];
 			if (hole.kind != 1) continue;
 			const EntHoleGeom &bd = geom[h];
 			dev::EntBandJob j;
 			j.coeffs = base + bd.offset; j.n = bd.height * bd.pitch;
-			j.nseg = (j.n + dev::ENT_SEG - 1) / dev::ENT_SEG; j.seg_base = (int)out->segjobs.size();
+			const int len = bd.level1 && bd.table == 0 && bd.mask_base >= 0 ? l1_seg : (int)dev::ENT_SEG;      // (table 1 keeps ENT_SEG: EntSegState::peaks)
+			j.nseg = (j.n + len - 1) / len; j.seg_base = (int)out->segjobs.size();
 			j.frame = f; j.hole = (int)h;
 			j.table = bd.table;
 			if (f == 0) {
@@ -271,16 +283,23 @@ inline bool ent_build_band_jobs(const std::vector<EntHoleGeom> &geom, const Samp
 				std::vector<std::pair<int, int>> &r = bd.level1 ? out->ranges_l1 : out->ranges_rest;
 				if (!r.empty() && r.back().first + r.back().second == j.seg_base) r.back().second += j.nseg; else r.push_back({ j.seg_base, j.nseg });
 			}
-			for (int s = 0; s < j.nseg; s++) out->segjobs.push_back(dev::EntSegJob{ j.coeffs, j.n, s * dev::ENT_SEG, (int)out->bands.size(), j.table, bd.pitch, bd.mask_base });
+			for (int s = 0; s < j.nseg; s++) {
+				// token slots: the segment's coefficients up to the band's end, in whole ENT_TOK_STRIDE (every coefficient may be a token); frame 0's table holds them
+				const int first = s * len, slots = ((j.n - first < len ? j.n - first : len) + dev::ENT_TOK_STRIDE - 1) / dev::ENT_TOK_STRIDE * dev::ENT_TOK_STRIDE;
+				out->segjobs.push_back(dev::EntSegJob{ j.coeffs, j.n, first, (int)out->bands.size(), j.table, bd.pitch, bd.mask_base, len, (int)tok_at });
+				tok_at += (size_t)slots;
+			}
 			out->bands.push_back(j);
 		}
+		if (tok_at > (size_t)INT32_MAX) return false;
+		out->tok_per_frame = tok_at;
 	}
 	out->nbands = (int)out->bands.size() / nframes;
 	return true;
 }
-inline bool ent_build_band_jobs(const FramePlan &plan, const SampleTemplate &t0, int nframes, int16_t *coeffs, size_t stride, EntHostJobs *out)
+inline bool ent_build_band_jobs(const FramePlan &plan, const SampleTemplate &t0, int nframes, int16_t *coeffs, size_t stride, EntHostJobs *out, int l1_seg = dev::ENT_SEG)
 {
-	return ent_build_band_jobs(ent_hole_geometry(plan, t0), t0, nframes, coeffs, stride, out);
+	return ent_build_band_jobs(ent_hole_geometry(plan, t0), t0, nframes, coeffs, stride, out, l1_seg);
 }
 
 // Serialises frame f's template into one kEntTmplStride block: bytes | holes-in-front-of-word | EntHole[] | EntPatch[].

@@ -26,8 +26,8 @@
 namespace cfhd {
 namespace dev {
 
-// A segment = 1024 consecutive raster coefficients of a band = the work of one wave (16 coefficients per lane; 512 was measured
-// slower: the per-wave descriptor loads dominate); four waves per
+// A segment = ENT_SEG = 1024 consecutive raster coefficients of a band = the work of one wave (16 coefficients per lane; 512 was measured
+// slower: the per-wave descriptor loads dominate) -- ENT_SEG_L1 on the sparse level-1 bands counted from block lists (below); four waves per
 // workgroup, no workgroup barriers in k_ent_count / k_ent_emit: all exchanges are wave-level (ballot / bpermute / shuffles).
 #ifndef CFHD_ENT_FILL
 #define CFHD_ENT_FILL 16384      // (the emulated tests build with a few words, so that trailers span many pieces)
@@ -40,15 +40,24 @@ namespace dev {
 #endif
 enum { FWD_CHUNK_COLS_ENT = 496 };      // = FWD_CHUNK_COLS of cfhd_kernels.h (static_assert in cfhd_device.hip, which sees both headers)
 enum { ENT_THREADS = 256, ENT_LANES = 64, ENT_WAVES = ENT_THREADS / ENT_LANES, ENT_PER_THREAD = CFHD_ENT_PER_THREAD, ENT_SEG = ENT_LANES * ENT_PER_THREAD,
-       ENT_LDS_WORDS = 256, ENT_TOK_CAP = CFHD_ENT_TOK_CAP, ENT_MAX_HOLES = 60 /* an intra sample has up to 40, a two-frame group 51; k_ent_layout sums them in one wave */,
+       ENT_LDS_WORDS = 1024, ENT_TOK_CAP = CFHD_ENT_TOK_CAP, ENT_MAX_HOLES = 60 /* an intra sample has up to 40, a two-frame group 51; k_ent_layout sums them in one wave */,
        ENT_FILL = CFHD_ENT_FILL /* bytes of a sample one workgroup of k_ent_layout fills at a time */,
        // what k_ent_count leaves per segment for k_ent_emit: one 32-bit word per token -- its finished bit string (run code + value code, left aligned in
        // the upper 26 bits) and its length in the low 6 bits; a token whose run takes several run codes or whose string is longer than 26 bits carries
        // run << 22 | value << 6 | ENT_CODE_COMPLEX instead and k_ent_emit walks the tables for it (rare: long codes belong to large values)
        ENT_TOK_STRIDE = ENT_SEG, ENT_STR_BITS = 26, ENT_CODE_COMPLEX = 63 /* length field: the token's run takes several run codes -- k_ent_emit walks the tables for it */,
-       ENT_RUN_COMPLEX = 0xff /* EntSegState::run_size: the run in front of the segment's first token takes several run codes */ };
-// ENT_LDS_WORDS: 32-bit words of the per-wave bit window in LDS (a segment of ordinary pictures codes into 10-40 words; beyond the window
-// the code words go to the payload with global atomics).  ENT_TOK_CAP: tokens (nonzero coefficients) of a segment held in LDS at a
+       ENT_RUN_COMPLEX = 0xff /* EntSegState::run_size: the run in front of the segment's first token takes several run codes */,
+       // Segments of the sparse level-1 bands (table 0, counted from block lists) are longer: ENT_SEG_L1 coefficients by default, any multiple of ENT_SEG up to
+       // ENT_SEG_MAX (EntSegJob::len; GpuEntropyEncoder::prepare_units, CFHD_AMD_L1_SEG).  The count kernels work a segment in windows of ENT_SEG token slots
+       // (their LDS stays 4 x ENT_SEG words), k_ent_count_blocks deals out the listed blocks of ENT_BLK_SPAN coefficients at a time (8 blocks per lane).
+       ENT_SEG_L1 = 4096, ENT_SEG_MAX = 8192, ENT_BLK_SPAN = 4096,
+       // a complex token: run << ENT_REC_RUN_SHIFT | (value clamped to +-1023, 11 bits) << 6 | ENT_CODE_COMPLEX
+       ENT_REC_RUN_SHIFT = 17 };
+static_assert(ENT_SEG_MAX - 1 < (1 << (32 - ENT_REC_RUN_SHIFT)), "the longest run inside a segment fits the token record's run field");
+static_assert(ENT_SEG_L1 % ENT_SEG == 0 && ENT_SEG_MAX % ENT_SEG == 0 && ENT_BLK_SPAN % ENT_SEG == 0 && ENT_BLK_SPAN / 8 <= 8 * ENT_LANES, "segments are whole token windows; a span is 8 blocks per lane");
+// ENT_LDS_WORDS: 32-bit words of the per-wave bit window in LDS (a segment of 1024 coefficients of ordinary pictures codes into 10-40 words, one of the
+// level-1 segments of ENT_SEG_L1 into 20-200; beyond the window the code words go to the payload with global atomics).  1024 words = 8 bits per coefficient
+// of a level-1 segment: 16.4 KB per workgroup of k_ent_emit, which still lets 8 workgroups (its register limit: 8 waves per SIMD) share a CU's 160 KB.  ENT_TOK_CAP: tokens (nonzero coefficients) of a segment held in LDS at a
 // time (ordinary: ~80 of 1024; a denser segment is worked off in passes).  Both are sized for occupancy, not for the worst case:
 // with worst-case windows (4 KB + 4 KB per wave) LDS capped k_ent_emit at 4 waves per SIMD and the kernel, a chain of dependent
 // lookups, ran latency-bound.
@@ -79,6 +88,8 @@ struct EntSegJob {                 // static per segment: everything k_ent_count
 	int table;                     // entropy table of the band (EntBandJob::table); such a band is also the one that may need a peak table
 	int pitch;                     // coefficients per band row (k_ent_count_blocks: a level-1 band's chunks are cut row by row)
 	int mask_base;                 // the band's first chunk in a frame's mask array (FwdBlockLists::mask_base); -1: the band has no block lists
+	int len;                       // coefficients of the segment (ENT_SEG, or ENT_SEG_L1 on level-1 bands coded from block lists); the band's last one may end early
+	int tok_base;                  // its first token slot in frame 0's part of `tokens` (a prefix of the segments' token slots: len rounded to whole ENT_TOK_STRIDE)
 };
 
 struct EntSegState {               // per segment, written by k_ent_count / k_ent_scan
@@ -93,6 +104,7 @@ struct EntSegState {               // per segment, written by k_ent_count / k_en
 	// token strings, k_ent_scan puts the first run's code in front.  The segment in FRONT writes the payload word the two share, with these
 	// bits merged in, as a plain store: no atomic on the payload for ordinary segments (ent_neighbours_merge()).
 	uint32_t lead32, lead_valid;
+	uint32_t tok_blk;              // k_ent_count: where its token strings are: tokens + tok_blk * ENT_TOK_STRIDE (frame offset included)
 	// What k_ent_emit would otherwise have to fetch through two more tables, one load behind the other (segment job -> band state): where the band's
 	// payload lies (k_ent_layout; null while the sample is not placed or overflowed its buffer) and bit 0: a segment of the same band precedes,
 	// bit 1: one follows, bits 8..: the band's entropy table (k_ent_count).  One 64-byte record per segment, three scalar loads per emitting wave.
@@ -176,13 +188,15 @@ __device__ __forceinline__ uint32_t value_entry(const EntTables *T, int v)
 // The segment table describes frame 0 only (every frame of a batch has the same geometry): frame f's segment s uses entry s with the
 // coefficient base moved by f pyramids and the band index by f * bands_per_frame, so the table (96 KB at 1080p) stays in L2 instead
 // of being streamed once per frame.
-struct EntBatchGeom { int segs_per_frame, bands_per_frame; size_t coeff_stride; };
-__device__ __forceinline__ EntSegJob ent_seg_job(const EntSegJob *seg_jobs, const EntBatchGeom &g, int seg, int *frame = nullptr)
+// tok_per_frame: token slots of one frame (0: segs_per_frame x ENT_TOK_STRIDE, every segment ENT_SEG long).
+struct EntBatchGeom { int segs_per_frame, bands_per_frame; size_t coeff_stride; size_t tok_per_frame; };
+__device__ __forceinline__ EntSegJob ent_seg_job(const EntSegJob *seg_jobs, const EntBatchGeom &g, int seg, int *frame = nullptr, size_t *tok_base = nullptr)
 {
 	const int f = seg / g.segs_per_frame, s = seg - f * g.segs_per_frame;
 	if (frame) *frame = f;
 	EntSegJob job = seg_jobs[s];
 	job.coeffs += (size_t)f * g.coeff_stride; job.band += f * g.bands_per_frame;
+	if (tok_base) *tok_base = (size_t)f * (g.tok_per_frame ? g.tok_per_frame : (size_t)g.segs_per_frame * ENT_TOK_STRIDE) + (size_t)job.tok_base;
 	return job;
 }
 
@@ -196,14 +210,16 @@ enum { ENT_PEAK_THRESHOLD = 250, ENT_PEAK_OFF_BITS = 21, ENT_PEAK_MAX = (1 << EN
        ENT_PEAK_TABLE_MAX = 2 * 0xffff };
 static_assert(ENT_PEAK_TABLE_MAX <= ENT_PEAK_MAX, "every table that is written has positions for all its peaks");
 static_assert(ENT_SEG < (1 << (32 - ENT_PEAK_OFF_BITS)), "a segment's peak count and its position in the band's table share a word");
-// The finished bit string of every token (nonzero coefficient) of every segment is kept in `tokens` (ENT_TOK_STRIDE words per segment, the first
-// 2 * ntok used): k_ent_emit places those -- a third of the bytes -- instead of reading, compacting and coding the coefficients a second time.
-// The coefficients of one segment as lane L of the wave holds them: dwords j * 64 + L (coalesced 4-byte loads), zero beyond the band.
-__device__ __forceinline__ void ent_load_segment(const EntSegJob &job, int lane, uint32_t *w)
+// The finished bit string of every token (nonzero coefficient) of every segment is kept in `tokens` (a segment's token slots start at EntSegState::tok_blk x
+// ENT_TOK_STRIDE, the first ntok are used): k_ent_emit places those -- a third of the bytes -- instead of reading, compacting and coding the coefficients a second time.
+// The coefficients of the window of ENT_SEG that starts `off` into the segment, as lane L of the wave holds them: dwords j * 64 + L (coalesced 4-byte loads), zero
+// beyond the segment and the band.
+__device__ __forceinline__ void ent_load_segment(const EntSegJob &job, int lane, uint32_t *w, int off = 0)
 {
-	const int rem = job.n - job.first;                   // coefficients from the segment's start to the end of the band (>= 1)
-	const uint32_t *src = (const uint32_t *)(job.coeffs + job.first);
-	if (rem >= ENT_SEG) {                                // wave-uniform: every segment of a band but its last
+	const int span = job.n - job.first < job.len ? job.n - job.first : job.len;
+	const int rem = span - off;                          // coefficients from the window's start to the end of the segment (>= 1)
+	const uint32_t *src = (const uint32_t *)(job.coeffs + job.first + off);
+	if (rem >= ENT_SEG) {                                // wave-uniform: every window but the last of a band
 #pragma unroll
 		for (int j = 0; j < ENT_SEG / 128; j++) w[j] = CFHD_LDG32(src + j * ENT_LANES + lane);
 	} else {
@@ -217,75 +233,53 @@ __device__ __forceinline__ void ent_load_segment(const EntSegJob &job, int lane,
 	}
 }
 
-__device__ __forceinline__ void ent_count_tokens(int seg, const EntSegJob &job, int frame, int ntok, int lane, uint32_t *s_tok, EntSegState *segs, const EntTables *tables,
-                                                 uint32_t *peak_flags, uint32_t *tokens, int probe);
+// What the token coder carries from one window of a segment to the next: tokens coded so far, the raster index (within the segment) of the first and of the
+// last of them, the peaks, the segment's first bits (from its first round of tokens) -- wave-uniform -- and the bits (per lane, summed at the end).
+struct EntTokCarry { int ntok, first_idx, last_idx; uint32_t bits, npeaks, lead32, lead_valid; };
+__device__ __forceinline__ EntTokCarry ent_tok_carry() { EntTokCarry c; c.ntok = 0; c.first_idx = -1; c.last_idx = -1; c.bits = 0; c.npeaks = 0; c.lead32 = 0; c.lead_valid = 0; return c; }
 
-// One segment of k_ent_count: the wave's loaded coefficients -> token strings in `tokens`, the segment's state in segs[seg].
-// The picture is sparse (about one coefficient in twelve is nonzero), so the code lookups run over a compacted token list, one token per lane
-// and round.  Compaction is what this kernel's instructions went into while every lane held 16 consecutive coefficients (a count, a wave scan and
-// 16 predicated LDS stores per lane: VALU-bound at 1.7 ms).  With lane L holding the dwords j * 64 + L raster order is j-major, lane, low / high
-// half, which is the order of a ballot -- a token's position is the number of nonzero halves in the rounds before (scalar popcounts) plus those in
-// the lanes below (v_mbcnt): no scan, no per-lane count.
-__device__ __forceinline__ void ent_count_segment(int seg, const EntSegJob &job, int frame, const uint32_t *w, int lane, uint32_t *s_tok, EntSegState *segs, const EntTables *tables,
-                                                  uint32_t *peak_flags, uint32_t *tokens, int probe)
+// One window of a segment's compacted token list, s_tok[0 .. nwin) (raster index within the segment << 16 | value, raster order), behind the c.ntok tokens of the
+// earlier windows: the tokens' finished bit strings into seg_out[c.ntok ..], their bits and peaks into c.  Shared by k_ent_count (tokens compacted from the dense band)
+// and k_ent_count_blocks (from the block lists).
+__device__ __forceinline__ void ent_count_window(const EntSegJob &job, const EntTables *T, int nwin, int lane, const uint32_t *s_tok, uint32_t *seg_out, EntTokCarry &c, int probe)
 {
-	if (CFHD_PROBE(probe) == 1) { uint32_t o = 0; for (int j = 0; j < ENT_SEG / 128; j++) o |= w[j]; const unsigned long long q = __ballot(o == 0x12345u); if (lane == 0) { EntSegState &z = segs[seg]; z.first_nz = -1; z.last_nz = -1; z.bits = q == 0x123456789ull; z.ntok = 0; z.lead32 = 0; z.lead_valid = 0; } return; }
-	int ntok = 0;                                        // wave-uniform
-#pragma unroll
-	for (int j = 0; j < ENT_SEG / 128; j++) {
-		const uint32_t vl = w[j] & 0xffffu, vh = w[j] >> 16;
-		const unsigned long long ml = __ballot(vl != 0u), mh = __ballot(vh != 0u);
-		const int pl = ntok + (int)wave_mbcnt(ml) + (int)wave_mbcnt(mh);
-		const uint32_t idx = (uint32_t)(j * 128 + 2 * lane) << 16;
-		if (vl) s_tok[pl] = idx | vl;
-		if (vh) s_tok[pl + (vl != 0u)] = (idx + 0x10000u) | vh;
-		ntok += __popcll(ml) + __popcll(mh);
-	}
-	CFHD_WAVE_SYNC();
-	ent_count_tokens(seg, job, frame, ntok, lane, s_tok, segs, tables, peak_flags, tokens, probe);
-}
-
-// The second half of a segment's count, from its compacted token list s_tok[0 .. ntok) (local raster index << 16 | value): the tokens' finished bit strings into
-// `tokens`, the segment's state into segs[seg].  Shared by k_ent_count (tokens compacted from the dense band) and k_ent_count_blocks (from the block lists).
-__device__ __forceinline__ void ent_count_tokens(int seg, const EntSegJob &job, int frame, int ntok, int lane, uint32_t *s_tok, EntSegState *segs, const EntTables *tables,
-                                                 uint32_t *peak_flags, uint32_t *tokens, int probe)
-{
-	const EntTables *T = tables + job.table;
-	uint32_t bits = 0, lead32 = 0, lead_valid = 0;
-	if (CFHD_PROBE(probe) == 2) { const unsigned long long q = __ballot(s_tok[lane] == 0x12345u); if (lane == 0) { EntSegState &z = segs[seg]; z.first_nz = -1; z.last_nz = -1; z.bits = q == 0x123456789ull && ntok == 0x12345; z.ntok = 0; z.lead32 = 0; z.lead_valid = 0; } return; }
-	uint32_t npeaks = 0;                                 // wave-uniform
-	for (int t0 = 0; t0 < ntok; t0 += ENT_LANES) {       // wave-uniform
+	for (int t0 = 0; t0 < nwin; t0 += ENT_LANES) {       // wave-uniform
 		const int t = t0 + lane;
-		const bool have = t < ntok;
+		const bool have = t < nwin;
 		const uint32_t tok = have ? s_tok[t] : 0u;
-		const uint32_t before = (have && t > 0) ? s_tok[t - 1] : 0u;
-		// zero run in front of the token, inside the segment (< 1024); the run in front of the segment's first token reaches into
+		// zero run in front of the token, inside the segment (< ENT_SEG_MAX); the run in front of the segment's first token reaches into
 		// the earlier segments and is added by k_ent_scan
-		const uint32_t run = (have && t > 0) ? (tok >> 16) - (before >> 16) - 1u : 0u;
+		const bool follows = have && (t > 0 || c.ntok > 0);
+		const uint32_t before = follows ? (t > 0 ? s_tok[t - 1] >> 16 : (uint32_t)c.last_idx) : 0u;
+		const uint32_t run = follows ? (tok >> 16) - before - 1u : 0u;
+		// a run past the ends of the run tables (segments longer than 3072 coefficients only): the token takes the table walk in k_ent_emit
+		const bool long_run = run >= 3072u;
+		const uint32_t ri = long_run ? 0u : run;
 		int value = (int)(int16_t)(tok & 0xffffu);
 		const bool is_peak = job.table && (value > ENT_PEAK_THRESHOLD || value < -ENT_PEAK_THRESHOLD);
 		if (is_peak) value = value > 0 ? ENT_PEAK_THRESHOLD + 1 : -ENT_PEAK_THRESHOLD - 1;
-		npeaks += (uint32_t)__popcll(__ballot(is_peak));
+		c.npeaks += (uint32_t)__popcll(__ballot(is_peak));
 		const uint32_t ve = value_entry(T, value);
-		const uint32_t rt = T->run_total[run];
-		const uint2 rp = T->run_pack[run];
+		uint32_t rt = T->run_total[ri];
+		if (__ballot(long_run)) { if (long_run) rt = run_bits_any(T, run); }      // (rare: kept out of the common path, its division included)
+		const uint2 rp = T->run_pack[ri];
 		uint32_t my_top = 0, my_len = 0;
 		if (have) {
-			bits += rt + (ve >> 27);
-			uint32_t *seg_out = tokens + (size_t)seg * ENT_TOK_STRIDE;
+			c.bits += rt + (ve >> 27);
 			// the token's finished bit string for k_ent_emit: run code (when one code covers the run: nearly always) + value code, left aligned;
 			// the first token of the segment carries its value code only (its run reaches into the earlier segments: k_ent_scan works that one out)
 			const uint32_t vs = ve >> 27, vc = ve & 0x7FFFFFFu, rs = run ? rp.y & 0xffu : 0u;
-			const bool simple = (run == 0u || (rp.y >> 8) == run) && rs + vs <= (uint32_t)ENT_STR_BITS;
+			const bool simple = !long_run && (run == 0u || (rp.y >> 8) == run) && rs + vs <= (uint32_t)ENT_STR_BITS;
 			const uint32_t str = simple ? (((run ? rp.x : 0u) << vs) | vc) << (32u - rs - vs) : 0u;      // (rs + vs >= 2: a value code has at least its sign)
 			const uint32_t len = simple ? rs + vs : (uint32_t)ENT_CODE_COMPLEX;
-			const uint32_t rec = simple ? str | len : (run << 22) | (((uint32_t)value & 0xffffu) << 6) | len;
-			if (CFHD_PROBE(probe) != 4) seg_out[t] = rec;
+			const int v11 = value < -1023 ? -1023 : (value > 1023 ? 1023 : value);      // (what value_entry() codes)
+			const uint32_t rec = simple ? str | len : (run << ENT_REC_RUN_SHIFT) | (((uint32_t)v11 & 0x7ffu) << 6) | len;
+			if (CFHD_PROBE(probe) != 4) seg_out[c.ntok + t] = rec;
 			my_top = str; my_len = len;
 		}
-		if (t0 == 0) {
-			// the first 32 bits of the strings of this round, as far as they are plain strings (up to the first token that needs the table walk)
-			const int hi = ntok < ENT_LANES ? ntok : ENT_LANES;
+		if (t0 == 0 && c.ntok == 0) {
+			// the first 32 bits of the strings of the segment's first round, as far as they are plain strings (up to the first token that needs the table walk)
+			const int hi = nwin < ENT_LANES ? nwin : ENT_LANES;
 			const unsigned long long cx = __ballot(have && my_len == (uint32_t)ENT_CODE_COMPLEX);
 			const uint32_t l = (have && my_len != (uint32_t)ENT_CODE_COMPLEX) ? my_len : 0u;
 			const uint32_t sc = wave_incl_scan(l), ex = sc - l;
@@ -293,24 +287,70 @@ __device__ __forceinline__ void ent_count_tokens(int seg, const EntSegJob &job, 
 			uint32_t part = (lane < stop_lane && ex < 32u) ? my_top >> ex : 0u;
 #pragma unroll
 			for (int d = 1; d < ENT_LANES; d <<= 1) part |= __shfl_xor(part, d);
-			lead32 = part;
+			c.lead32 = part;
 			const uint32_t known = stop_lane > 0 ? wave_get(sc, stop_lane - 1) : 0u;
-			lead_valid = known < 32u ? known : 32u;
+			c.lead_valid = known < 32u ? known : 32u;
 		}
 	}
-	if (npeaks && lane == 0) atomic_or_u32(&peak_flags[frame], 1u);
-	bits = wave_get(wave_incl_scan(bits), ENT_LANES - 1);
+	if (nwin) {
+		if (!c.ntok) c.first_idx = (int)(s_tok[0] >> 16);
+		c.last_idx = (int)(s_tok[nwin - 1] >> 16);
+		c.ntok += nwin;
+	}
+}
+
+// The segment's state into segs[seg] once all its windows are coded.  tok_base: its first token slot in `tokens`.
+__device__ __forceinline__ void ent_count_finish(int seg, const EntSegJob &job, int frame, size_t tok_base, int lane, const EntTokCarry &c, EntSegState *segs, uint32_t *peak_flags)
+{
+	if (c.npeaks && lane == 0) atomic_or_u32(&peak_flags[frame], 1u);
+	const uint32_t bits = wave_get(wave_incl_scan(c.bits), ENT_LANES - 1);
 	if (lane == 0) {
 		EntSegState &s = segs[seg];
-		s.first_nz = ntok ? job.first + (int)(s_tok[0] >> 16) : -1;
-		s.last_nz = ntok ? job.first + (int)(s_tok[ntok - 1] >> 16) : -1;
+		s.first_nz = c.ntok ? job.first + c.first_idx : -1;
+		s.last_nz = c.ntok ? job.first + c.last_idx : -1;
 		s.bits = bits;
-		s.ntok = (uint32_t)ntok;
-		s.lead32 = lead32; s.lead_valid = lead_valid;
+		s.ntok = (uint32_t)c.ntok;
+		s.lead32 = c.lead32; s.lead_valid = c.lead_valid;
+		s.tok_blk = (uint32_t)(tok_base / ENT_TOK_STRIDE);
 		s.out = nullptr;
-		s.info = (job.first != 0 ? 1u : 0u) | (job.first + ENT_SEG < job.n ? 2u : 0u) | ((uint32_t)job.table << 8);
-		s.peaks = npeaks;
+		s.info = (job.first != 0 ? 1u : 0u) | (job.first + job.len < job.n ? 2u : 0u) | ((uint32_t)job.table << 8);
+		s.peaks = c.npeaks;
 	}
+}
+
+// One segment of k_ent_count: the wave's loaded coefficients (the segment's first window) -> token strings in `tokens`, the segment's state in segs[seg]; a segment
+// longer than ENT_SEG is loaded, compacted and coded one window of ENT_SEG coefficients after the other.
+// The picture is sparse (about one coefficient in twelve is nonzero), so the code lookups run over a compacted token list, one token per lane
+// and round.  Compaction is what this kernel's instructions went into while every lane held 16 consecutive coefficients (a count, a wave scan and
+// 16 predicated LDS stores per lane: VALU-bound at 1.7 ms).  With lane L holding the dwords j * 64 + L raster order is j-major, lane, low / high
+// half, which is the order of a ballot -- a token's position is the number of nonzero halves in the rounds before (scalar popcounts) plus those in
+// the lanes below (v_mbcnt): no scan, no per-lane count.
+__device__ __forceinline__ void ent_count_segment(int seg, const EntSegJob &job, int frame, size_t tok_base, uint32_t *w, int lane, uint32_t *s_tok, EntSegState *segs, const EntTables *tables,
+                                                  uint32_t *peak_flags, uint32_t *tokens, int probe)
+{
+	if (CFHD_PROBE(probe) == 1) { uint32_t o = 0; for (int j = 0; j < ENT_SEG / 128; j++) o |= w[j]; const unsigned long long q = __ballot(o == 0x12345u); if (lane == 0) { EntSegState &z = segs[seg]; z.first_nz = -1; z.last_nz = -1; z.bits = q == 0x123456789ull; z.ntok = 0; z.lead32 = 0; z.lead_valid = 0; } return; }
+	const EntTables *T = tables + job.table;
+	EntTokCarry c = ent_tok_carry();
+	const int span = job.n - job.first < job.len ? job.n - job.first : job.len;
+	for (int off = 0; off < span; off += ENT_SEG) {      // wave-uniform
+		if (off) ent_load_segment(job, lane, w, off);
+		int nwin = 0;                                    // wave-uniform
+#pragma unroll
+		for (int j = 0; j < ENT_SEG / 128; j++) {
+			const uint32_t vl = w[j] & 0xffffu, vh = w[j] >> 16;
+			const unsigned long long ml = __ballot(vl != 0u), mh = __ballot(vh != 0u);
+			const int pl = nwin + (int)wave_mbcnt(ml) + (int)wave_mbcnt(mh);
+			const uint32_t idx = (uint32_t)(off + j * 128 + 2 * lane) << 16;
+			if (vl) s_tok[pl] = idx | vl;
+			if (vh) s_tok[pl + (vl != 0u)] = (idx + 0x10000u) | vh;
+			nwin += __popcll(ml) + __popcll(mh);
+		}
+		CFHD_WAVE_SYNC();
+		if (CFHD_PROBE(probe) == 2) { const unsigned long long q = __ballot(s_tok[lane] == 0x12345u); if (lane == 0) { EntSegState &z = segs[seg]; z.first_nz = -1; z.last_nz = -1; z.bits = q == 0x123456789ull && nwin == 0x12345; z.ntok = 0; z.lead32 = 0; z.lead_valid = 0; } return; }
+		ent_count_window(job, T, nwin, lane, s_tok, tokens + tok_base, c, probe);
+		CFHD_WAVE_SYNC();                                // the next window reuses s_tok
+	}
+	ent_count_finish(seg, job, frame, tok_base, lane, c, segs, peak_flags);
 }
 
 // ENT_COUNT_SEGS consecutive segments per wave, the loads of all of them issued before the first is worked on.  Measured with 2 (round 3): no change
@@ -324,101 +364,132 @@ __global__ void __launch_bounds__(ENT_THREADS) k_ent_count(const EntSegJob *seg_
                                                             uint32_t *peak_flags, uint32_t *tokens, int range_lo, int range_n,
                                                             int probe = 0 /* timing experiments: 1 behind the loads, 2 behind the compaction, 4 no token stores */)
 {
-	__shared__ uint32_t s_tok_all[ENT_WAVES][ENT_SEG];       // the segment's tokens: local raster index << 16 | value (16 bits); every coefficient may be one
+	__shared__ uint32_t s_tok_all[ENT_WAVES][ENT_SEG];       // a window's tokens: raster index in the segment << 16 | value (16 bits); every coefficient may be one
 	const int lane = wave_lane();
 	const int wave = wave_uniform((int)(threadIdx.x >> 6));
 	const int idx0 = wave_uniform(((int)blockIdx.x * ENT_WAVES + wave) * ENT_COUNT_SEGS);
 	if (idx0 >= total_segs) return;                      // whole wave
 	const int seg0 = (idx0 / range_n) * geom.segs_per_frame + range_lo + idx0 % range_n;      // (ENT_COUNT_SEGS == 1: one index, one segment)
 	static_assert(ENT_COUNT_SEGS == 1, "the range mapping takes one segment per wave");
-	EntSegJob job[ENT_COUNT_SEGS]; int frame[ENT_COUNT_SEGS];
+	EntSegJob job[ENT_COUNT_SEGS]; int frame[ENT_COUNT_SEGS]; size_t tok_base[ENT_COUNT_SEGS];
 	uint32_t w[ENT_COUNT_SEGS][ENT_SEG / 128];
 #pragma unroll
 	for (int k = 0; k < ENT_COUNT_SEGS; k++)
-		if (idx0 + k < total_segs) { job[k] = ent_seg_job(seg_jobs, geom, seg0 + k, &frame[k]); ent_load_segment(job[k], lane, w[k]); }
+		if (idx0 + k < total_segs) { job[k] = ent_seg_job(seg_jobs, geom, seg0 + k, &frame[k], &tok_base[k]); ent_load_segment(job[k], lane, w[k]); }
 #pragma unroll
 	for (int k = 0; k < ENT_COUNT_SEGS; k++)
 		if (idx0 + k < total_segs) {
-			ent_count_segment(seg0 + k, job[k], frame[k], w[k], lane, s_tok_all[wave], segs, tables, peak_flags, tokens, probe);
+			ent_count_segment(seg0 + k, job[k], frame[k], tok_base[k], w[k], lane, s_tok_all[wave], segs, tables, peak_flags, tokens, probe);
 			CFHD_WAVE_SYNC();                                 // the next segment reuses the token window
 		}
 }
 
-// k_ent_count over the block lists k_fwd_yuv422_strip_blocks leaves of the level-1 bands (cfhd_kernels.h FwdBlockLists) instead of the dense bands.  A segment's
-// 1024 raster coefficients are 128 blocks of 8: lane L takes blocks L and L + 64.  For each it works out the chunk the block lies in (band row, position in the
-// row), loads that chunk's occupancy mask and works out the slot its rank in the mask gives a listed block; the listed blocks are then dealt to the lanes in raster
-// order (round 6: a pass of 64 lanes takes 64 *listed* blocks) and fetched.  All lanes do this at
-// once: two dependent memory round trips per segment (masks, blocks), whatever the number of chunks a segment touches (the first version walked the chunks one
-// after the other, five dependent rounds: 1.9 ms per 512 frames where the dense k_ent_count takes 1.6).  The nonzero coefficients then go to the token list in
-// raster order (lanes in block order: a scan of the lanes' counts, first half of the segment, then the second).  What the kernel reads are the listed blocks -- a
-// third of the band on ordinary pictures -- and 8 bytes per chunk.  Same segment states and token strings as k_ent_count, by construction (the same second half).
+// k_ent_count over the block lists k_fwd_yuv422_strip_blocks leaves of the level-1 bands (cfhd_kernels.h FwdBlockLists) instead of the dense bands.  A segment is
+// worked in spans of up to ENT_BLK_SPAN raster coefficients, 512 blocks of 8: lane L takes blocks L + 64 h, h = 0 .. 7.  For each it works out the chunk the block
+// lies in (band row, position in the row), loads that chunk's occupancy mask and works out the slot its rank in the mask gives a listed block; the listed blocks are
+// then dealt to the lanes in raster order (round 6: a pass of 64 lanes takes 64 *listed* blocks) and fetched.  All lanes do this at once: two dependent memory round
+// trips per span (masks, blocks), whatever the number of chunks it touches (the first version walked the chunks one after the other, five dependent rounds: 1.9 ms
+// per 512 frames where the dense k_ent_count takes 1.6).  The nonzero coefficients then go to the token list in raster order (lanes in block order: a scan of the
+// lanes' counts per pass), which is coded whenever the next pass might overflow its ENT_SEG slots.  What the kernel reads are the listed blocks -- a third of the
+// band on ordinary pictures -- and 8 bytes per chunk.  Same segment states and token strings as k_ent_count, by construction (the same token coder).
 struct EntBlockLists { const uint4 *blocks; const unsigned long long *masks; const int16_t *coeff0; size_t masks_per_frame; };
 __global__ void __launch_bounds__(ENT_THREADS) k_ent_count_blocks(const EntSegJob *seg_jobs, EntBatchGeom geom, int total_segs, EntSegState *segs, const EntTables *tables,
                                                                    uint32_t *peak_flags, uint32_t *tokens, int range_lo, int range_n, EntBlockLists lists)
 {
 	__shared__ uint32_t s_tok_all[ENT_WAVES][ENT_SEG];
+	enum { SPAN_BLOCKS = ENT_BLK_SPAN / 8, HMAX = SPAN_BLOCKS / ENT_LANES };
 	const int lane = wave_lane();
 	const int wave = wave_uniform((int)(threadIdx.x >> 6));
 	const int idx0 = wave_uniform((int)blockIdx.x * ENT_WAVES + wave);
 	if (idx0 >= total_segs) return;                      // whole wave
 	const int seg = (idx0 / range_n) * geom.segs_per_frame + range_lo + idx0 % range_n;
-	int frame;
-	const EntSegJob job = ent_seg_job(seg_jobs, geom, seg, &frame);
-	uint32_t *s_tok = s_tok_all[wave];
+	int frame; size_t tok_base;
+	const EntSegJob job = ent_seg_job(seg_jobs, geom, seg, &frame, &tok_base);
+	const EntTables *T = tables + job.table;
+	uint32_t *s_tok = s_tok_all[wave], *seg_out = tokens + tok_base;
 	const int pitch = job.pitch, cpr = (pitch + FWD_CHUNK_COLS_ENT - 1) / FWD_CHUNK_COLS_ENT;
-	const int end = job.first + ENT_SEG < job.n ? job.first + ENT_SEG : job.n;
-	const uint4 *blocks = wave_uniform_ptr(lists.blocks + (size_t)(job.coeffs - lists.coeff0) / 8);      // first block slot of the band (bands start on 128-byte boundaries)
+	const int seg_end = job.first + job.len, end = seg_end < job.n ? seg_end : job.n;
+	const uint4 *band_blocks = lists.blocks + (size_t)(job.coeffs - lists.coeff0) / 8;      // first block slot of the band (bands start on 128-byte boundaries)
 	const unsigned long long *masks = wave_uniform_ptr(lists.masks + (size_t)frame * lists.masks_per_frame + job.mask_base);
-	const int row0 = job.first / pitch, col0 = job.first - row0 * pitch;      // wave-uniform: where the segment starts
-	// 1. which of the segment's 128 blocks are listed, and where each lies: lane L looks at blocks L and L + 64 (two chunk masks per lane, the loads side by side)
-	uint32_t entry[2]; bool listed[2];
+	EntTokCarry c = ent_tok_carry();
+	for (int s0 = job.first; s0 < end; s0 += ENT_BLK_SPAN) {      // wave-uniform: the spans of the segment
+		const int nq = (seg_end - s0 < ENT_BLK_SPAN ? seg_end - s0 : ENT_BLK_SPAN) / 8;      // blocks of the span (those beyond the band are never listed)
+		const int row0 = s0 / pitch, col0 = s0 - row0 * pitch;      // wave-uniform: where the span starts
+		// slots below are counted from the span's first band row: below 2^23 for any row a FramePlan accepts (static_assert in cfhd_entropy_jobs.h)
+		const uint4 *blocks = wave_uniform_ptr(band_blocks + (size_t)row0 * (size_t)(pitch >> 3));
+		// 1. which of the span's blocks are listed, and where each lies: lane L looks at blocks L + 64 h (the mask loads side by side)
+		uint32_t entry[HMAX]; bool listed[HMAX];
+		int row = 0, col = col0 + 8 * lane;              // (row: relative to row0)
+		while (col >= pitch) { col -= pitch; row++; }   // (a span covers one to a few dozen rows of the bands this kernel sees; any number works)
 #pragma unroll
-	for (int h = 0; h < 2; h++) {
-		const int q = lane + 64 * h, pos = job.first + 8 * q;
-		int row = row0, col = col0 + 8 * q;
-		while (col >= pitch) { col -= pitch; row++; }       // (a segment covers one to three rows of the bands this kernel sees; any number works)
-		// chunk k of the row and block i of the chunk: block c8 of the row / 62 as a multiply and a shift (exact below 1092 blocks = rows of 8736 coefficients; the widest level-1 row a FramePlan accepts has 8192: kMaxFrameDim), and
-		// every product on the full-rate 24-bit multiplier (the plain forms compile to v_mul_hi / v_mad_u64_u32 at a quarter of the rate: measured 6 % of this kernel)
-		static_assert(FWD_CHUNK_COLS_ENT == 62 * 8, "the division below is by 62 blocks");
-		const uint32_t c8 = (uint32_t)col >> 3, k = mul_u24(c8, 1058u) >> 16, i = c8 - mul_u24(k, 62u);
-		unsigned long long m = 0ull;
-		if (pos < end) m = masks[mul_u24((uint32_t)row, (uint32_t)cpr) + k];
-		listed[h] = ((m >> i) & 1ull) != 0ull;
-		// the slot of the block among the band's blocks (below 2^25: a band of 268 M coefficients) and its number in the segment, one word
-		entry[h] = ((mul_u24((uint32_t)row, (uint32_t)pitch >> 3) + mul_u24(k, 62u) + (uint32_t)__popcll(m & ((1ull << i) - 1ull))) << 7) | (uint32_t)q;
-	}
-	// 2. the listed blocks (a third of them on ordinary pictures), in raster order, dealt to the lanes: a listed block's rank among the listed ones (ballot + v_mbcnt) is the
-	//    lane that takes it.  Round 6: before, every lane fetched and compacted its two raster blocks whether listed or not -- two passes of count, scan and eight predicated
-	//    stores per segment where one does (the kernel runs at 89 % of the VALU issue rate).  The ranks travel through the head of the wave's token area.
-	const unsigned long long b0 = __ballot(listed[0]), b1 = __ballot(listed[1]);
-	const int n0 = __popcll(b0), nlisted = n0 + __popcll(b1);             // wave-uniform
-	if (listed[0]) s_tok[wave_mbcnt(b0)] = entry[0];
-	if (listed[1]) s_tok[n0 + (int)wave_mbcnt(b1)] = entry[1];
-	CFHD_WAVE_SYNC();
-	const uint32_t mine[2] = { lane < nlisted ? s_tok[lane] : 0u, lane + 64 < nlisted ? s_tok[lane + 64] : 0u };      // (both read before the first token is written over them)
-	CFHD_WAVE_SYNC();
-	int ntok = 0;                                        // wave-uniform
-#pragma unroll
-	for (int h = 0; h < 2; h++) {
-		if (64 * h >= nlisted) break;                    // wave-uniform: the second pass only for segments with more than 64 listed blocks
-		uint32_t w[4] = { 0u, 0u, 0u, 0u };
-		if (lane + 64 * h < nlisted) { const cfhd_u4 v = CFHD_LDG128(&blocks[mine[h] >> 7]); w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w; }
-		uint32_t cnt = 0;
-#pragma unroll
-		for (int d = 0; d < 4; d++) cnt += ((w[d] & 0xffffu) != 0u) + ((w[d] >> 16) != 0u);
-		const uint32_t incl = wave_incl_scan(cnt);
-		uint32_t p = (uint32_t)ntok + incl - cnt;
-		const uint32_t local = 8u * (mine[h] & 127u);       // raster index of the block's first coefficient within the segment
-#pragma unroll
-		for (int d = 0; d < 4; d++) {
-			const uint32_t vl = w[d] & 0xffffu, vh = w[d] >> 16;
-			if (vl) s_tok[p++] = ((local + 2u * d) << 16) | vl;
-			if (vh) s_tok[p++] = ((local + 2u * d + 1u) << 16) | vh;
+		for (int h = 0; h < HMAX; h++) {
+			listed[h] = false; entry[h] = 0u;
+			if (ENT_LANES * h >= nq) continue;           // wave-uniform
+			if (h) { col += 8 * ENT_LANES; while (col >= pitch) { col -= pitch; row++; } }
+			const int q = lane + ENT_LANES * h, pos = s0 + 8 * q;
+			// chunk k of the row and block i of the chunk: block c8 of the row / 62 as a multiply and a shift (exact below 1092 blocks = rows of 8736 coefficients; the widest level-1 row a FramePlan accepts has 8192: kMaxFrameDim), and
+			// every product on the full-rate 24-bit multiplier (the plain forms compile to v_mul_hi / v_mad_u64_u32 at a quarter of the rate: measured 6 % of this kernel)
+			static_assert(FWD_CHUNK_COLS_ENT == 62 * 8, "the division below is by 62 blocks");
+			const uint32_t c8 = (uint32_t)col >> 3, k = mul_u24(c8, 1058u) >> 16, i = c8 - mul_u24(k, 62u);
+			unsigned long long m = 0ull;
+			if (pos < end) m = masks[mul_u24((uint32_t)(row0 + row), (uint32_t)cpr) + k];
+			listed[h] = ((m >> i) & 1ull) != 0ull;
+			// the slot of the block among the span's rows and its number in the span, one word
+			entry[h] = ((mul_u24((uint32_t)row, (uint32_t)pitch >> 3) + mul_u24(k, 62u) + (uint32_t)__popcll(m & ((1ull << i) - 1ull))) << 9) | (uint32_t)q;
 		}
-		ntok += (int)wave_get(incl, ENT_LANES - 1);
+		// 2. the listed blocks (a third of them on ordinary pictures), in raster order, dealt to the lanes: a listed block's rank among the listed ones (ballot + v_mbcnt) is the
+		//    lane that takes it.  Round 6: before, every lane fetched and compacted its own raster blocks whether listed or not -- passes of count, scan and eight predicated
+		//    stores for blocks that are not there (the kernel runs at 89 % of the VALU issue rate).  The ranks travel through the head of the wave's token area.
+		int nlisted = 0;                                 // wave-uniform
+#pragma unroll
+		for (int h = 0; h < HMAX; h++) {
+			if (ENT_LANES * h >= nq) break;              // wave-uniform
+			const unsigned long long b = __ballot(listed[h]);
+			if (listed[h]) s_tok[nlisted + (int)wave_mbcnt(b)] = entry[h];
+			nlisted += __popcll(b);
+		}
+		CFHD_WAVE_SYNC();
+		uint32_t mine[HMAX];
+#pragma unroll
+		for (int h = 0; h < HMAX; h++) mine[h] = lane + ENT_LANES * h < nlisted ? s_tok[lane + ENT_LANES * h] : 0u;      // (all read before the first token is written over them)
+		CFHD_WAVE_SYNC();
+		int nwin = 0;                                    // wave-uniform: tokens in s_tok not yet coded
+		// the blocks of pass h + 1 are fetched before pass h is worked on (its loads would otherwise wait behind the token coder between passes)
+		cfhd_u4 next = { 0u, 0u, 0u, 0u };
+		if (lane < nlisted) next = CFHD_LDG128(&blocks[mine[0] >> 9]);
+#pragma unroll
+		for (int h = 0; h < HMAX; h++) {
+			if (ENT_LANES * h >= nlisted) break;         // wave-uniform: as many passes as 64 listed blocks
+			const uint32_t w[4] = { next.x, next.y, next.z, next.w };
+			if (h + 1 < HMAX) {
+				next.x = next.y = next.z = next.w = 0u;
+				if (lane + ENT_LANES * (h + 1) < nlisted) next = CFHD_LDG128(&blocks[mine[h + 1 < HMAX ? h + 1 : h] >> 9]);
+			}
+			uint32_t cnt = 0;
+#pragma unroll
+			for (int d = 0; d < 4; d++) cnt += ((w[d] & 0xffffu) != 0u) + ((w[d] >> 16) != 0u);
+			const uint32_t incl = wave_incl_scan(cnt), total = wave_get(incl, ENT_LANES - 1);
+			if (nwin + (int)total > ENT_SEG) {           // wave-uniform: the pass might not fit behind the tokens in the window -- code those first
+				CFHD_WAVE_SYNC();
+				ent_count_window(job, T, nwin, lane, s_tok, seg_out, c, 0);
+				CFHD_WAVE_SYNC();
+				nwin = 0;
+			}
+			uint32_t p = (uint32_t)nwin + incl - cnt;
+			const uint32_t local = (uint32_t)(s0 - job.first) + 8u * (mine[h] & 511u);      // raster index of the block's first coefficient within the segment
+#pragma unroll
+			for (int d = 0; d < 4; d++) {
+				const uint32_t vl = w[d] & 0xffffu, vh = w[d] >> 16;
+				if (vl) s_tok[p++] = ((local + 2u * d) << 16) | vl;
+				if (vh) s_tok[p++] = ((local + 2u * d + 1u) << 16) | vh;
+			}
+			nwin += (int)total;
+		}
+		CFHD_WAVE_SYNC();
+		ent_count_window(job, T, nwin, lane, s_tok, seg_out, c, 0);
+		CFHD_WAVE_SYNC();                                // the next span's ranks go where these tokens were
 	}
-	CFHD_WAVE_SYNC();
-	ent_count_tokens(seg, job, frame, ntok, lane, s_tok, segs, tables, peak_flags, tokens, 0);
+	ent_count_finish(seg, job, frame, tok_base, lane, c, segs, peak_flags);
 }
 
 // =============================================================================================
@@ -759,9 +830,9 @@ __device__ __forceinline__ void ent_emit_segment(const EntSegState &st, const En
 		if (__ballot(complex)) {
 			// rare: a run inside the segment that one composite code does not cover -- this lane walks the tables for its token
 			if (complex) {
-				run = rec >> 22;                                               // (zero for the first token: its run is k_ent_scan's)
-				ve = value_entry(T, (int)(int16_t)((rec >> 6) & 0xffffu));
-				len = (uint32_t)T->run_total[run] + (ve >> 27);
+				run = rec >> ENT_REC_RUN_SHIFT;                                // (zero for the first token: its run is k_ent_scan's)
+				ve = value_entry(T, (int)(rec << (32 - ENT_REC_RUN_SHIFT)) >> 21);      // (the value: 11 bits from bit 6 on, sign extended)
+				len = run_bits_any(T, run) + (ve >> 27);
 			}
 		}
 		const uint32_t sc = wave_incl_scan(len);
@@ -770,8 +841,8 @@ __device__ __forceinline__ void ent_emit_segment(const EntSegState &st, const En
 		if (have && !complex) ent_put_string32(s_words, out, use_lds, first_word, pos, rec & ~63u);
 		if (complex) {
 			uint32_t left = run;
-			while (left > 0u) {
-				const uint2 rc = T->run_pack[left];
+			while (left > 0u) {                                            // (the greedy loop: the longest code while 3072 zeros or more are left)
+				const uint2 rc = T->run_pack[left < 3072u ? left : 3071u];
 				const uint32_t size = rc.y & 0xffu;
 				ent_put_string(s_words, out, use_lds, first_word, pos, (uint64_t)rc.x << (64u - size));
 				pos += size; left -= rc.y >> 8;
@@ -816,20 +887,18 @@ __global__ void __launch_bounds__(ENT_THREADS) k_ent_emit(int total_segs, const 
 	uint32_t first_rec[ENT_EMIT_SEGS];
 	EntSegState st[ENT_EMIT_SEGS + 2];                   // st[k + 1] = segment seg0 + k
 #pragma unroll
-	for (int k = 0; k < ENT_EMIT_SEGS; k++) {            // (issued before anything is known about the segments: at worst 512 bytes each read for nothing)
-		const int sg = seg0 + k < total_segs ? seg0 + k : seg0;
-		first_rec[k] = tokens[(size_t)sg * ENT_TOK_STRIDE + lane];
-	}
-#pragma unroll
 	for (int k = 0; k < ENT_EMIT_SEGS + 2; k++) {
 		int sg = seg0 - 1 + k;
 		sg = sg < 0 ? 0 : (sg < total_segs ? sg : total_segs - 1);      // (the records say themselves whether a neighbour belongs to their band)
 		st[k] = segs[sg];
 	}
 #pragma unroll
+	for (int k = 0; k < ENT_EMIT_SEGS; k++)              // (issued before anything else is known about the segment: at worst 256 bytes read for nothing)
+		first_rec[k] = tokens[(size_t)st[k + 1].tok_blk * ENT_TOK_STRIDE + lane];
+#pragma unroll
 	for (int k = 0; k < ENT_EMIT_SEGS; k++)
 		if (seg0 + k < total_segs) {
-			ent_emit_segment(st[k + 1], st[k], st[k + 2], first_rec[k], tokens + (size_t)(seg0 + k) * ENT_TOK_STRIDE, lane, s_words_all[wave], tables, probe);
+			ent_emit_segment(st[k + 1], st[k], st[k + 2], first_rec[k], tokens + (size_t)st[k + 1].tok_blk * ENT_TOK_STRIDE, lane, s_words_all[wave], tables, probe);
 			CFHD_WAVE_SYNC();                                 // the next segment reuses the window
 		}
 }
