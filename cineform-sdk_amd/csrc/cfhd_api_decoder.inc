@@ -297,12 +297,16 @@ CFHD_Error CFHD_DecodeSample(CFHD_DecoderRef ref, void *sample, size_t size, voi
 	// interlaced samples (known only now: the SAMPLE_FLAGS tag lies behind the 512 bytes CFHD_PrepareToDecode sees): 4:2:2, full resolution through the
 	// inverse frame transform, half resolution from the level-1 lowpass planes like any other sample (the reference's output is the same model)
 	const bool interlaced = !ps.progressive;
+	// (RG48 / b64a / BGRA / BGRa of an interlaced sample at full resolution: the reference's 16-bit rows of the inverse frame transform, decoder.c:26488 -> :22027
+	// TransformInverseFrameToRow16u, then its RGB conversion of those rows, bayer.c:13186 -- k_inv_frame_yuv422_rows16 + k_yu64_to_rgb16 -- at the widths of the
+	// progressive RG48-of-4:2:2 route; at half resolution the level-1 lowpass planes, as for progressive samples)
 	// (YU64 / v210 output of interlaced samples: at half resolution only -- the level-1 lowpass planes, as for progressive samples; RG24 takes another route there: not built)
-	// (likewise the 8-bit / 16-bit RGB(A) pictures and the 10-bit RGB words of an interlaced sample: half resolution only -- at full resolution DecodeBatch::launch_inverse has no
-	// inverse frame transform into planes for them, and refusing here keeps the contract of every other unsupported combination: BADFORMAT, zeroed picture, nothing queued)
-	const bool planes_out = d->out_kind == PIX_YU64 || d->out_kind == PIX_V210 || d->out_kind == PIX_BGRA || d->out_kind == PIX_BGRa || d->out_kind == PIX_RG48 || d->out_kind == PIX_B64A ||
-	                        (d->out_kind >= PIX_R210 && d->out_kind <= PIX_AR10);
+	// (likewise the 10-bit RGB words of an interlaced sample: half resolution only; refusing here keeps the contract of every other unsupported combination:
+	// BADFORMAT, zeroed picture, nothing queued)
+	const bool rows16_out = d->out_kind == PIX_BGRA || d->out_kind == PIX_BGRa || d->out_kind == PIX_RG48 || d->out_kind == PIX_B64A;
+	const bool planes_out = d->out_kind == PIX_YU64 || d->out_kind == PIX_V210 || (d->out_kind >= PIX_R210 && d->out_kind <= PIX_AR10);
 	if (interlaced && (ps.encoded_format != ENC_YUV422 || (planes_out && !d->half) || d->out_kind == PIX_RG24)) return fail_zero(ERR_BADFORMAT);
+	if (interlaced && rows16_out && !d->half && ps.width < 128) return fail_zero(ERR_BADFORMAT);
 	if (interlaced && !d->half && ps.width > 8192) return fail_zero(ERR_BADFORMAT);        // k_dec_undiff serves rows of up to 4096 coefficients (cfhd_dec_kernels.h DXU_MAX): an unsupported size, not a bad sample
 	// another call of this geometry in flight right now: decode together with it (see DecodeService)
 	if (decode_gather_slots() > 1 && gpu_entropy_enabled() && size <= (size_t)d->plan.width * d->plan.height * pixel_bytes_of(d->out_kind) + 65536) {

@@ -99,7 +99,8 @@ public:
 	~DecodeBatch();
 	// half: CFHD_DECODED_RESOLUTION_HALF of 4:2:2 samples -- the last wavelet level is not run, the level-1 lowpass planes are the picture
 	int prepare(const FramePlan &plan, int nframes, int out_pixel_kind, bool own_output, bool half = false);
-	// interlaced 4:2:2 samples: the last level is the inverse frame transform (k_inv_frame_yuv422); 8-bit 4:2:2 output, full resolution
+	// interlaced 4:2:2 samples: the last level is the inverse frame transform (k_inv_frame_yuv422; 8-bit 4:2:2 output, full resolution), or into 16-bit rows
+	// (k_inv_frame_yuv422_rows16) for RG48 / b64a / BGRA / BGRa; set before prepare()
 	void set_interlaced(bool on) { interlaced_ = on; ent_.set_interlaced(on); }
 	bool interlaced() const { return interlaced_; }
 	// the next launches (entropy decoder with host-parsed samples, inverse transform) cover frames 0 .. k-1 only (0 = all)
@@ -147,6 +148,7 @@ private:
 	bool byr4_ = false; uint16_t *d_restore_ = nullptr;   // BYR4 output of Bayer samples: the four planes as 16-bit words per quad first, turned into the mosaic by k_bayer_to_byr4 (linear-restore table in HBM)
 	bool rgb16_of_422_ = false, rgb16_b64a_ = false;   // RG48 / b64a output of 4:2:2 samples: YU64 rows first, converted by k_yu64_to_rgb16 (bayer.c:11916 + RGB2YUV.c:1760)
 	bool rgb32_of_422_ = false;        // BGRA / BGRa output of 4:2:2 samples: the last level as k_inv_yuv422_rgb32 (spatial.c:29577)
+	bool rgb32_rows16_ = false, rgb32_bottom_up_ = false;   // BGRA / BGRa of interlaced 4:2:2 samples: the 16-bit rows, then k_yu64_to_rgb16's 8-bit mode (rgb16_of_422_ is set too)
 	bool rgb24_of_422_ = false;        // RG24 output of 4:2:2 samples: YU64 rows first, converted by k_yu64_to_rgb24 (the reference's route: 16-bit rows, then colour conversion)
 	std::vector<char> direct_;                      // frame i went straight to the caller's (registered) buffer: finish_frame has nothing to copy
 	enum { kMaxOutPieces = 8 };

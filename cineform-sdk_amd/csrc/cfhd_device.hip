@@ -846,7 +846,10 @@ int DecodeBatch::prepare(const FramePlan &plan, int nframes, int out_kind, bool 
 	if (rgb24_half) rgb24_of_422_ = false;
 	// RG48 / b64a output of 4:2:2 samples (bayer.c:11916 Row16uFull2OutputFormat: the 16-bit rows through RGB2YUV.c:1308 / :1760): the YU64 route into the scratch frame,
 	// then k_yu64_to_rgb16.  BGRA / BGRa output of 4:2:2 samples: the last level with the reference's fused colour conversion (k_inv_yuv422_rgb32).
-	rgb16_of_422_ = (out_kind == PIX_RG48 || out_kind == PIX_B64A) && plan.encoded_format == ENC_YUV422; rgb16_b64a_ = out_kind == PIX_B64A;
+	// Interlaced samples (full resolution): all four through the 16-bit rows of the inverse frame transform (decoder.c:26488 -> :22027 TransformInverseFrameToRow16u,
+	// k_inv_frame_yuv422_rows16) into the scratch frame, then k_yu64_to_rgb16 -- BGRA / BGRa in its 8-bit mode (bayer.c:825), not the fused k_inv_yuv422_rgb32.
+	rgb32_rows16_ = interlaced_ && !half && (out_kind == PIX_BGRA || out_kind == PIX_BGRa) && plan.encoded_format == ENC_YUV422; rgb32_bottom_up_ = out_kind == PIX_BGRA;
+	rgb16_of_422_ = ((out_kind == PIX_RG48 || out_kind == PIX_B64A) && plan.encoded_format == ENC_YUV422) || rgb32_rows16_; rgb16_b64a_ = out_kind == PIX_B64A;
 	const int final_kind = out_kind;
 	if (rgb16_of_422_) { if (!own_output) { g_err = "RG48 / b64a output of 4:2:2 samples: into the library's own output frames"; return -2; } if (!half) out_kind = PIX_YU64; }
 	rgb32_of_422_ = (out_kind == PIX_BGRA || out_kind == PIX_BGRa) && plan.encoded_format == ENC_YUV422;
@@ -964,7 +967,7 @@ int DecodeBatch::prepare(const FramePlan &plan, int nframes, int out_kind, bool 
 			hj.out = own_output ? job_out + job_frame_bytes * i : nullptr; hj.out_pitch = job_pitch;      // (v210 output: the scratch frame k_yu64_to_v210 reads)
 			continue;
 		}
-		if (dec_planes16(out_kind) && !rgb32_of_422_) {
+		if (dec_planes16(out_kind) && !rgb32_of_422_ && !(interlaced_ && rgb16_of_422_)) {
 			for (int c = 0; c < onch; c++) {
 				dev::InvPlaneJob &p = j.l1[(size_t)i * onch + c];
 				for (int b = 0; b < 4; b++) p.band[b] = base + plan.ch[c].band[0][b].offset;
@@ -992,6 +995,7 @@ int DecodeBatch::prepare(const FramePlan &plan, int nframes, int out_kind, bool 
 		y.width = plan.ch[0].band[0][0].width; y.height = plan.ch[0].band[0][0].height; y.display_height = plan.display_height;
 		y.uyvy = out_kind == PIX_2VUY; y.shift = plan.precision - 8; y.dither_seed = 0x9E3779B9u * (uint32_t)(i + 1);
 		y.out = own_output ? d_out_ + frame_bytes_ * i : nullptr; y.out_pitch = out_pitch_;
+		if (interlaced_ && rgb16_of_422_) { y.out = job_out + job_frame_bytes * i; y.out_pitch = job_pitch; }      // (k_inv_frame_yuv422_rows16: the YU64 scratch frame)
 		y.bottom_up = out_kind == PIX_BGRA; y.matrix_601 = plan.color_matrix >= 2;       // (k_inv_yuv422_rgb32)
 		y.masks = nullptr;                               // (block lists: prepare_entropy() knows the mask buffer)
 		{ int mb[kMaxChannels][kNumBands]; dec_block_list_layout(plan, mb); for (int c = 0; c < 3; c++) for (int b = 0; b < 4; b++) y.mask_base[c][b] = mb[c][b]; }
@@ -1109,7 +1113,7 @@ bool DecodeBatch::frame_inverse_strips() const
 }
 
 // k_inv_frame_yuv422_quad: four band columns per thread with 8-byte loads and 16-byte stores (CFHD_AMD_INVERSE=tile: the one-column kernel)
-bool DecodeBatch::frame_inverse_quads() const
+bool DecodeBatch::frame_inverse_quads() const      // (also k_inv_frame_yuv422_rows16 against k_inv_frame_yuv422_rows16_col)
 {
 	const int forced = shape_override("CFHD_AMD_INVERSE");
 	const BandDesc &b = plan_.ch[0].band[0][0];
@@ -1126,6 +1130,7 @@ const char *DecodeBatch::level_kernel(int level) const
 	if (level > 0) return planes_as_strips(plan_, level, act) ? "k_inv_plane_strip" : "k_inv_plane";
 	if (half_) return is_packed16(out_kind_) ? "k_half_packed16" : "k_half_yuv422";
 	if (dec_rgb10(out_kind_)) return "k_inv_rgb10";
+	if (interlaced_ && rgb16_of_422_) return frame_inverse_quads() ? "k_inv_frame_yuv422_rows16" : "k_inv_frame_yuv422_rows16_col";
 	if (dec_planes16(out_kind_)) return strip_inverse_packed16() ? "k_inv_packed16_strip" : "k_inv_packed16";
 	if (interlaced_) return frame_inverse_strips() ? (block_lists_inverse() ? "k_inv_frame_yuv422_strip_blocks" : "k_inv_frame_yuv422_strip") : (frame_inverse_quads() ? "k_inv_frame_yuv422_quad" : "k_inv_frame_yuv422");
 	return strip_inverse() ? (block_lists_inverse() ? "k_inv_yuv422_strip_blocks" : "k_inv_yuv422_strip") : "k_inv_yuv422";
@@ -1172,8 +1177,13 @@ int DecodeBatch::launch_inverse(uint32_t dither_seed)
 		HIPCHK(hipStreamWaitEvent(st, (hipEvent_t)ev2_[2], 0));
 		HIPCHK(hipEventRecord((hipEvent_t)evl_[1], st));
 	}
-	if (interlaced_ && !half_ && dec_planes16(out_kind_)) return -1;
-	if (half_ && plan_.encoded_format == ENC_YUV422 && (dec_rgb8(out_kind_) || out_kind_ == PIX_RG48 || out_kind_ == PIX_B64A)) {
+	// (interlaced samples at full resolution: the 16-bit rows serve RG48 / b64a / BGRA / BGRa only -- YU64, v210 and the 10-bit RGB words are refused at the C ABI)
+	if (interlaced_ && !half_ && dec_planes16(out_kind_) && !rgb16_of_422_) return -1;
+	if (interlaced_ && !half_ && rgb16_of_422_) {
+		const BandDesc &b = plan_.ch[0].band[0][0];
+		if (frame_inverse_quads()) dev::k_inv_frame_yuv422_rows16<<<dim3((b.width / 4 + dev::NTHREADS - 1) / dev::NTHREADS, b.height, act), dev::NTHREADS, 0, st>>>(j.yuv);
+		else dev::k_inv_frame_yuv422_rows16_col<<<dim3((b.width / 2 + dev::NTHREADS - 1) / dev::NTHREADS, b.height, act), dev::NTHREADS, 0, st>>>(j.yuv);
+	} else if (half_ && plan_.encoded_format == ENC_YUV422 && (dec_rgb8(out_kind_) || out_kind_ == PIX_RG48 || out_kind_ == PIX_B64A)) {
 		const BandDesc &b = plan_.ch[0].band[0][0];
 		dev::k_half_rgb24<<<dim3((b.width / 2 + dev::NTHREADS - 1) / dev::NTHREADS, out_rows_, act), dev::NTHREADS, 0, st>>>(j.half);
 	} else if (half_ && (dec_rgb8(out_kind_) || dec_rgb10(out_kind_) || (out_kind_ == PIX_B64A && nch == 3))) {
@@ -1228,7 +1238,7 @@ int DecodeBatch::launch_inverse(uint32_t dither_seed)
 	if (rgb16_of_422_) {
 		const int pairs = plan_.width / 2;
 		dev::k_yu64_to_rgb16<<<dim3((unsigned)((pairs + dev::NTHREADS - 1) / dev::NTHREADS), (unsigned)out_rows_, (unsigned)act), dev::NTHREADS, 0, st>>>(
-			(const uint16_t *)d_tmp_, tmp_pitch_ / 2, tmp_frame_bytes_ / 2, (uint16_t *)d_out_, out_pitch_ / 2, frame_bytes_ / 2, pairs, plan_.color_matrix >= 2, rgb16_b64a_ ? 1 : 0);
+			(const uint16_t *)d_tmp_, tmp_pitch_ / 2, tmp_frame_bytes_ / 2, (uint16_t *)d_out_, out_pitch_ / 2, frame_bytes_ / 2, pairs, plan_.color_matrix >= 2, rgb32_rows16_ ? (rgb32_bottom_up_ ? 3 : 2) : (rgb16_b64a_ ? 1 : 0));
 	}
 	if (byr4_) {
 		const int quads = plan_.width;

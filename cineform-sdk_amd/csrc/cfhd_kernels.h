@@ -2645,17 +2645,12 @@ __device__ __forceinline__ void frame_synth_run(const Quad16 &lo, const Quad16 &
 		out[2 * k] = sat16(e >> 1); out[2 * k + 1] = sat16(o >> 1);
 	}
 }
-__global__ void __launch_bounds__(NTHREADS) k_inv_frame_yuv422_quad(const InvYuvJob *jobs, uint32_t launch_seed)
+// temporal low / high samples of band row r, luma band columns 4t .. 4t + 3 and chroma band columns 2t, 2t + 1: tl / th[0..7] luma (even, odd of each column),
+// [8..11] V, [12..15] U.  Every lane of the wave calls it (the neighbour columns come by lane exchange); `have` says whether the lane's columns exist.
+__device__ __forceinline__ void frame_quad_samples(const InvYuvJob &job, int t, int r, bool have, int lane, int *tl, int *th)
 {
-	const InvYuvJob &job = jobs[blockIdx.z];
 	const int w = job.width, cw = w >> 1;
-	const int t = (int)(blockIdx.x * NTHREADS + threadIdx.x), r = blockIdx.y;
 	const int c = 4 * t, cc = 2 * t;                          // first luma / chroma band column of this thread
-	const bool have = c < w && r < job.height;
-	const int lane = (int)(threadIdx.x & 63u);
-	const uint32_t seed = job.dither_seed ^ launch_seed;
-	const int sh = job.shift;
-	int tl[16], th[16];                                       // temporal low / high samples: 8 luma, 4 V, 4 U
 	// one (lowpass, highpass) band pair at a time: luma (LL, LH) -> temporal low, (HL, HH) -> temporal high, then the same for V and U
 #pragma unroll
 	for (int pair = 0; pair < 2; pair++) {
@@ -2697,6 +2692,19 @@ __global__ void __launch_bounds__(NTHREADS) k_inv_frame_yuv422_quad(const InvYuv
 			}
 		}
 	}
+}
+__global__ void __launch_bounds__(NTHREADS) k_inv_frame_yuv422_quad(const InvYuvJob *jobs, uint32_t launch_seed)
+{
+	const InvYuvJob &job = jobs[blockIdx.z];
+	const int w = job.width;
+	const int t = (int)(blockIdx.x * NTHREADS + threadIdx.x), r = blockIdx.y;
+	const int cc = 2 * t;                                     // first chroma band column of this thread
+	const bool have = 4 * t < w && r < job.height;
+	const int lane = (int)(threadIdx.x & 63u);
+	const uint32_t seed = job.dither_seed ^ launch_seed;
+	const int sh = job.shift;
+	int tl[16], th[16];                                       // temporal low / high samples: 8 luma, 4 V, 4 U
+	frame_quad_samples(job, t, r, have, lane, tl, th);
 	if (!have) return;
 #pragma unroll
 	for (int par = 0; par < 2; par++) {
@@ -2721,6 +2729,107 @@ __global__ void __launch_bounds__(NTHREADS) k_inv_frame_yuv422_quad(const InvYuv
 		}
 		uint4 o4; o4.x = words[0]; o4.y = words[1]; o4.z = words[2]; o4.w = words[3];
 		*(uint4 *)(job.out + (size_t)orow * job.out_pitch + 16 * (size_t)t) = o4;
+	}
+}
+
+// =============================================================================================
+// Interlaced last level into 16-bit rows: RG48 / b64a / BGRA / BGRa output of interlaced 4:2:2 samples (Codec/decoder.c:26488 -> :22027
+// TransformInverseFrameToRow16u).  The temporal low / high rows are the ones k_inv_frame_yuv422 builds (spatial.c:19803 InvertHorizontalRow16s: the same
+// 2/6 synthesis, >> 1, saturated); temporal.c:7087 InvertInterlacedRow16sToRow16u then gives row 2r = low - high, row 2r + 1 = low + high as 16-bit words:
+// the output columns below output_width - output_width % 8 of a channel take the vector body (saturating difference / sum, clamped by the adds / subs_epu16
+// pair with protect 2047 -- 511 at 8-bit precision --, >> 1, << 6 -- << 8 --), the rest the scalar tail ((low -+ high) / 2, clamped to [0, 1023] -- [0, 255] --,
+// << 6 -- << 8 --).  Written as YU64 words Y0 C1 Y1 C2 (channel 1 = V, channel 2 = U) into the scratch frame that k_yu64_to_rgb16 converts; no dither.
+// Restated in tests/interlaced_rgb_model.py, pinned on the reference decoder.  Dense bands only (no block lists); the first display_height rows only.
+// =============================================================================================
+__device__ __forceinline__ uint32_t row16u_word(int l, int h, int odd_row, bool tail, int sh)
+{
+	const int protect = sh ? 2047 : 511, scale = sh ? 6 : 8, top = sh ? 1023 : 255;
+	if (tail) {
+		int v = (odd_row ? l + h : l - h) / 2;                // (C division: towards zero)
+		v = v < 0 ? 0 : (v > top ? top : v);
+		return (uint32_t)(v << scale);
+	}
+	int x = adds16(odd_row ? adds16(l, h) : subs16(l, h), 0x7fff - protect) & 0xffff;      // adds_epi16
+	x = x >= 0x7fff - protect ? x - (0x7fff - protect) : 0;                                  // subs_epu16
+	x = (int)(int16_t)x >> 1;                                                                 // srai_epi16
+	return (uint32_t)(x << scale) & 0xffffu;                                                  // slli_epi16
+}
+
+// four luma band columns (eight pixels, four YU64 pixel pairs) per thread: the loads and lane exchanges of k_inv_frame_yuv422_quad, two 16-byte stores per
+// picture row (32 bytes of YU64 words)
+__global__ void __launch_bounds__(NTHREADS) k_inv_frame_yuv422_rows16(const InvYuvJob *jobs)
+{
+	const InvYuvJob &job = jobs[blockIdx.z];
+	const int w = job.width;
+	const int t = (int)(blockIdx.x * NTHREADS + threadIdx.x), r = blockIdx.y;
+	const bool have = 4 * t < w && r < job.height;
+	const int lane = (int)(threadIdx.x & 63u);
+	const int sh = job.shift;
+	int tl[16], th[16];
+	frame_quad_samples(job, t, r, have, lane, tl, th);
+	if (!have) return;
+	const int ypost = 2 * w - (2 * w) % 8, cpost = w - w % 8;   // first tail column of the luma / chroma output rows (2w luma, w chroma samples)
+	const int x0 = 8 * t, p0 = 4 * t;                          // first luma sample, first chroma sample (= pixel pair) of this thread
+#pragma unroll
+	for (int par = 0; par < 2; par++) {
+		const int orow = 2 * r + par;
+		if (orow >= job.display_height) continue;
+		uint32_t words[8];
+#pragma unroll
+		for (int k = 0; k < 4; k++) {                          // pixel pair p0 + k: Y (2k), V, Y (2k + 1), U
+			const uint32_t y0 = row16u_word(tl[2 * k], th[2 * k], par, x0 + 2 * k >= ypost, sh);
+			const uint32_t y1 = row16u_word(tl[2 * k + 1], th[2 * k + 1], par, x0 + 2 * k + 1 >= ypost, sh);
+			const uint32_t v = row16u_word(tl[8 + k], th[8 + k], par, p0 + k >= cpost, sh);
+			const uint32_t u = row16u_word(tl[12 + k], th[12 + k], par, p0 + k >= cpost, sh);
+			words[2 * k] = y0 | (v << 16); words[2 * k + 1] = y1 | (u << 16);
+		}
+		uint4 *o = (uint4 *)(job.out + (size_t)orow * job.out_pitch + 32 * (size_t)t);
+		uint4 a; a.x = words[0]; a.y = words[1]; a.z = words[2]; a.w = words[3];
+		uint4 b; b.x = words[4]; b.y = words[5]; b.z = words[6]; b.w = words[7];
+		o[0] = a; o[1] = b;
+	}
+}
+
+// one chroma band column (two luma band columns, two YU64 pixel pairs) per thread, any width: the geometries the four-column shape does not serve and
+// CFHD_AMD_INVERSE=tile
+__global__ void __launch_bounds__(NTHREADS) k_inv_frame_yuv422_rows16_col(const InvYuvJob *jobs)
+{
+	const InvYuvJob &job = jobs[blockIdx.z];
+	const int w = job.width, cw = w >> 1;
+	const int cc = (int)(blockIdx.x * NTHREADS + threadIdx.x), r = blockIdx.y;
+	if (cc >= cw || r >= job.height) return;
+	const int sh = job.shift;
+	int tl[8], th[8];                                          // 4 luma (columns 2cc, 2cc + 1: even, odd each), 2 V, 2 U
+	{
+		const size_t o = (size_t)r * job.band_pitch[0];
+		frame_synth(job.band[0][0] + o, job.band[0][1] + o, 2 * cc, w, tl[0], tl[1]);
+		frame_synth(job.band[0][0] + o, job.band[0][1] + o, 2 * cc + 1, w, tl[2], tl[3]);
+		frame_synth(job.band[0][2] + o, job.band[0][3] + o, 2 * cc, w, th[0], th[1]);
+		frame_synth(job.band[0][2] + o, job.band[0][3] + o, 2 * cc + 1, w, th[2], th[3]);
+	}
+#pragma unroll
+	for (int x = 0; x < 2; x++) {
+		const size_t o = (size_t)r * job.band_pitch[1 + x];
+		frame_synth(job.band[1 + x][0] + o, job.band[1 + x][1] + o, cc, cw, tl[4 + 2 * x], tl[5 + 2 * x]);
+		frame_synth(job.band[1 + x][2] + o, job.band[1 + x][3] + o, cc, cw, th[4 + 2 * x], th[5 + 2 * x]);
+	}
+	const int ypost = 2 * w - (2 * w) % 8, cpost = w - w % 8;
+	const int x0 = 4 * cc, p0 = 2 * cc;
+#pragma unroll
+	for (int par = 0; par < 2; par++) {
+		const int orow = 2 * r + par;
+		if (orow >= job.display_height) continue;
+		uint32_t words[4];
+#pragma unroll
+		for (int k = 0; k < 2; k++) {
+			const uint32_t y0 = row16u_word(tl[2 * k], th[2 * k], par, x0 + 2 * k >= ypost, sh);
+			const uint32_t y1 = row16u_word(tl[2 * k + 1], th[2 * k + 1], par, x0 + 2 * k + 1 >= ypost, sh);
+			const uint32_t v = row16u_word(tl[4 + k], th[4 + k], par, p0 + k >= cpost, sh);
+			const uint32_t u = row16u_word(tl[6 + k], th[6 + k], par, p0 + k >= cpost, sh);
+			words[2 * k] = y0 | (v << 16); words[2 * k + 1] = y1 | (u << 16);
+		}
+		uint4 o4; o4.x = words[0]; o4.y = words[1]; o4.z = words[2]; o4.w = words[3];
+		*(uint4 *)(job.out + (size_t)orow * job.out_pitch + 16 * (size_t)cc) = o4;
 	}
 }
 
@@ -2843,9 +2952,12 @@ __global__ void __launch_bounds__(NTHREADS) k_yu64_to_v210(const uint16_t *yu64,
 // ChannelYUYV16toPlanarYUV16 (every chroma word serves its pixel pair) + :1760 PlanarYUV16toPlanarRGB16 (vector body: 15-bit samples, 13-bit coefficients, mulhi
 // products, saturating sums, the clamp to 14 bits) + bayer.c:478 ConvertLinesToOutput at white point 16 (the words as they are; b64a: 0xffff in front).  Restated in
 // oracle/cfhd_oracle_inv.c orc_yu64_to_rgb16, pinned on the reference decoder.  One thread per pixel pair: 8 bytes in, 12 or 16 out.
+// mode 0: RG48, 1: b64a, 2 / 3: RGB32 (the output of interlaced samples, Codec/bayer.c:825 at white point 16 without dither, :477 NEWDITHER 0): every RG48 word >> 8,
+// bytes B, G, R, 0xff; 3: bottom row first (BGRA, decoder.c:26395) -- `out` is then a byte frame of out_pitch_words * 2 bytes per row.
 __global__ void __launch_bounds__(NTHREADS) k_yu64_to_rgb16(const uint16_t *yu64, int in_pitch_words, size_t in_frame_words, uint16_t *out, int out_pitch_words, size_t out_frame_words,
-                                                            int pairs, int matrix_601, int b64a)
+                                                            int pairs, int matrix_601, int mode)
 {
+	const int b64a = mode == 1;
 	const int p = (int)(blockIdx.x * blockDim.x + threadIdx.x), row = (int)blockIdx.y;
 	if (p >= pairs) return;
 	const cfhd_u2 in = CFHD_LDG64(yu64 + blockIdx.z * in_frame_words + (size_t)row * in_pitch_words + 4 * (size_t)p);      // Y0 C1 | Y1 C2: channel 1 = V, channel 2 = U
@@ -2856,6 +2968,7 @@ __global__ void __launch_bounds__(NTHREADS) k_yu64_to_rgb16(const uint16_t *yu64
 	const int uu = sat16((U >> 1) - c_offset), vv = sat16((V >> 1) - c_offset);
 	const int rv = (vv * r_vmult) >> 16, gu = (uu * -g_umult) >> 16, gv = (vv * -g_vmult) >> 16, bu = (uu * b_umult) >> 16;
 	uint16_t *o = out + blockIdx.z * out_frame_words + (size_t)row * out_pitch_words + (size_t)p * (b64a ? 8 : 6);
+	uint32_t px[2];                                          // (RGB32: the two pixels' bytes)
 #pragma unroll
 	for (int k = 0; k < 2; k++) {
 		const int yy = (sat16((Y[k] >> 1) - y_offset) * ymult) >> 16;
@@ -2867,8 +2980,14 @@ __global__ void __launch_bounds__(NTHREADS) k_yu64_to_rgb16(const uint16_t *yu64
 			v = (v & 0xffff) - (0x7fff - 0x3fff); v = v < 0 ? 0 : v;
 			comp[c] = (v << 2) & 0xffff;
 		}
-		if (b64a) { o[4 * k] = 0xffff; o[4 * k + 1] = (uint16_t)comp[0]; o[4 * k + 2] = (uint16_t)comp[1]; o[4 * k + 3] = (uint16_t)comp[2]; }
+		if (mode >= 2) px[k] = ((uint32_t)comp[2] >> 8) | (((uint32_t)comp[1] >> 8) << 8) | (((uint32_t)comp[0] >> 8) << 16) | 0xff000000u;
+		else if (b64a) { o[4 * k] = 0xffff; o[4 * k + 1] = (uint16_t)comp[0]; o[4 * k + 2] = (uint16_t)comp[1]; o[4 * k + 3] = (uint16_t)comp[2]; }
 		else { o[3 * k] = (uint16_t)comp[0]; o[3 * k + 1] = (uint16_t)comp[1]; o[3 * k + 2] = (uint16_t)comp[2]; }
+	}
+	if (mode >= 2) {
+		const int orow = mode == 3 ? (int)gridDim.y - 1 - row : row;
+		uint2 v; v.x = px[0]; v.y = px[1];
+		*(uint2 *)((uint8_t *)out + 2 * (blockIdx.z * out_frame_words + (size_t)orow * out_pitch_words) + 8 * (size_t)p) = v;
 	}
 }
 
