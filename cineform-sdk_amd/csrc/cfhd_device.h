@@ -32,6 +32,7 @@ const char *device_last_error();
 
 // N frames that travel through the forward path together: one launch per wavelet level covers every channel of
 // every frame (blockIdx.z walks the job table).  N = 1 is the synchronous CFHD_EncodeSample path.
+struct ForwardRoute; struct InverseRoute;      // (cfhd_device.hip: the kernels a launch picks)
 class EncodeBatch {
 public:
 	EncodeBatch();
@@ -56,12 +57,8 @@ public:
 	GpuEntropyEncoder &entropy() { return ent_; }
 	void set_stage_pieces(int k) { stage_pieces_ = k < 1 ? 1 : (k > 16 ? 16 : k); }      // plain input frames staged in k pieces (upload_frame)
 	bool has_entropy() const { return ent_ready_; }
-	bool strip_forward() const;                     // level 1 of 4:2:2 runs as k_fwd_yuv422_strip (else k_fwd_yuv422)
-	bool block_lists_forward() const;               // ... and leaves the quantized level-1 bands as block lists for k_ent_count_blocks (k_fwd_yuv422_strip_blocks)
-	bool strip_forward_packed16() const;
-	bool strip_forward_bayer() const;
-	bool strip_forward_frame() const;            // level 1 of RG48 / b64a runs as k_fwd_packed16_strip (else k_fwd_packed16)
-	const char *level_kernel(int level) const;      // name of the kernel the next launch_forward() uses for level 0 / 1 / 2 (as a profiler shows it)
+	// name of the kernel the next launch_forward(coeffs_needed) uses for level 0 / 1 / 2 (as a profiler shows it; two launches: "a+b")
+	const char *level_kernel(int level, bool coeffs_needed = false) const;
 	int download_coeffs();                             // async: final (entropy coded) region of every frame -> pinned host
 	int wait();
 	const int16_t *host_coeffs(int i) const { return h_coeff_ + (size_t)i * plan_.final_elems; }
@@ -75,6 +72,7 @@ private:
 	int sync_jobs();
 	void fill_jobs();
 	void fill_block_lists();
+	ForwardRoute forward_route(bool coeffs_needed) const;      // which kernels the next launch_forward() runs: launch_forward() and level_kernel() both read this
 	FramePlan plan_;
 	int n_ = 0, active_ = 0, device_ = 0; bool own_input_ = false, jobs_dirty_ = true;
 	void *stream_ = nullptr, *ev0_ = nullptr, *ev1_ = nullptr, *evl_[2] = {nullptr, nullptr};
@@ -114,14 +112,9 @@ public:
 	// GPU entropy decoder (k_dec_bands): samples in, dequantized pyramid built in HBM (replaces host_coeffs()/upload_coeffs()).
 	int prepare_entropy(size_t sample_cap);
 	GpuEntropyDecoder &entropy() { return ent_; }
-	int launch_entropy();                            // entropy().launch() with the level-1 bands as block lists where the inverse gathers them (block_lists_inverse())
+	int launch_entropy();                            // entropy().launch() with the level-1 bands as block lists where the inverse gathers them
 	bool has_entropy() const { return ent_ready_; }
-	bool strip_inverse() const;                     // the last level of 4:2:2 runs as k_inv_yuv422_strip (else k_inv_yuv422)
-	bool strip_inverse_packed16() const;            // the last level of RG48 / b64a output runs as k_inv_packed16_strip (else k_inv_packed16)
-	bool frame_inverse_quads() const;
-	bool frame_inverse_strips() const;
-	bool block_lists_inverse() const;               // interlaced samples: k_inv_frame_yuv422_quad (else k_inv_frame_yuv422)
-	const char *level_kernel(int level) const;      // name of the kernel the next launch_inverse() uses for level 0 / 1 / 2
+	const char *level_kernel(int level) const;      // name of the kernel the next launch_entropy() + launch_inverse() use for level 0 / 1 / 2 (as a profiler shows it)
 	int set_device_output(int i, void *d_out, int pitch_bytes);
 	int launch_inverse(uint32_t dither_seed);          // async
 	int download_frame(int i, void *out, int pitch_bytes);   // async D2H into pinned staging, then row copy after wait
@@ -135,6 +128,7 @@ public:
 	void release();                                    // frees every device / pinned buffer of the batch (the destructor's work; prepare() starts with it)
 private:
 	int sync_jobs();
+	InverseRoute inverse_route() const;             // which kernels the next launch_entropy() + launch_inverse() run: both and level_kernel() read this
 	FramePlan plan_;
 	int n_ = 0, out_kind_ = 0, device_ = 0; bool own_output_ = false, jobs_dirty_ = true, half_ = false, interlaced_ = false; int active_ = 0;
 	void *stream_ = nullptr, *ev0_ = nullptr, *ev1_ = nullptr, *evl_[2] = {nullptr, nullptr};

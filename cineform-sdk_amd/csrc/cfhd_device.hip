@@ -592,6 +592,7 @@ static int shape_override(const char *name)           // 0: by size, 1: tile, 2:
 	const char *e = getenv(name);
 	return !e ? 0 : (strcmp(e, "tile") == 0 ? 1 : (strcmp(e, "strip") == 0 ? 2 : 0));
 }
+static int active_frames(int active, int n) { return active > 0 && active < n ? active : n; }      // frames 0 .. this-1 of a batch of n take part in a launch (set_active(); 0 = all)
 static bool planes_as_strips(const FramePlan &plan, int lv /* wavelet index whose bands are produced / consumed */, int frames)
 {
 	const int forced = shape_override("CFHD_AMD_PLANES");
@@ -622,141 +623,119 @@ template <typename F> static void for_channel_runs(const FramePlan &plan, int lv
 	}
 }
 
-// k_fwd_yuv422_strip serves progressive 4:2:2 frames of whole 32-pixel blocks whose rows are 16-byte aligned;
-// everything else (and CFHD_AMD_FORWARD=tile, for A/B runs) takes the LDS-tiled k_fwd_yuv422.  Both produce the same coefficients.
-bool EncodeBatch::strip_forward() const
+// Level 1 of the forward transform: every kernel launch_forward() can pick, and the name a profiler shows it under (level_kernel()).  The strip kernels and
+// the LDS-tiled ones produce the same coefficients.
+enum class FwdL1 { Yuv422, Yuv422Strip, Yuv422StripBlocks, Yuv422StripBlocksDense, FrameYuv422, FrameYuv422Strip, Packed16, Packed16Strip, BayerStrip, BayerUnpack };
+static const char *const kFwdL1Name[] = {"k_fwd_yuv422", "k_fwd_yuv422_strip", "k_fwd_yuv422_strip_blocks", "k_fwd_yuv422_strip_blocks_dense", "k_fwd_frame_yuv422",
+                                         "k_fwd_frame_yuv422_strip", "k_fwd_packed16", "k_fwd_packed16_strip", "k_fwd_bayer_strip", "k_unpack_byr4+k_fwd_plane"};
+static const char *const kFwdPlaneName[2] = {"k_fwd_plane", "k_fwd_plane_strip"};      // levels 2 and 3: [planes_as_strips()]
+static_assert(sizeof(kFwdL1Name) / sizeof(*kFwdL1Name) == (size_t)FwdL1::BayerUnpack + 1, "one name per level-1 kernel");
+struct ForwardRoute {
+	FwdL1 l1; bool strip_planes[2];                     // [lv - 1]: level lv + 1 runs as k_fwd_plane_strip
+	bool block_lists() const { return l1 == FwdL1::Yuv422StripBlocks || l1 == FwdL1::Yuv422StripBlocksDense; }      // the quantized level-1 bands leave as block lists for k_ent_count_blocks
+};
+template <typename F> static bool every_frame(int n, F ok) { for (int i = 0; i < n; i++) if (!ok(i)) return false; return true; }
+
+// The kernels of the next launch_forward(), from the prepared batch alone: the environment switches, the active frame count and the job table are read here and nowhere else.
+ForwardRoute EncodeBatch::forward_route(bool coeffs_needed) const
 {
-	const int forced = shape_override("CFHD_AMD_FORWARD");
-	const int act = active_ > 0 && active_ < n_ ? active_ : n_;
-	if (forced == 1 || (forced == 0 && frames_1080p_equivalent(plan_, act) < 32.0)) return false;
-	if (plan_.interlaced || plan_.encoded_format != ENC_YUV422 || plan_.width % 32) return false;
-	EncJobs j = enc_jobs_at(h_jobs_, n_, plan_.num_channels);
-	for (int i = 0; i < n_; i++) if (((uintptr_t)j.yuv[i].in & 15) || (j.yuv[i].in_pitch & 15)) return false;
-	return true;
+	static const int blocks_env = [] { const char *e = getenv("CFHD_AMD_BLOCKS"); return e ? atoi(e) : 1; }();      // 0: dense bands and k_ent_count (A/B runs)
+	const int act = active_frames(active_, n_), forced = shape_override("CFHD_AMD_FORWARD"), kind = plan_.pixel_kind, nch = plan_.num_channels;
+	const EncJobs j = enc_jobs_at(h_jobs_, n_, nch);
+	ForwardRoute r;
+	for (int lv = 1; lv < 3; lv++) r.strip_planes[lv - 1] = planes_as_strips(plan_, lv, act);
+	// the register-strip kernels pay from 32 frames of 1080p on (CFHD_AMD_FORWARD=tile / strip, for A/B runs: never / wherever the geometry allows)
+	const bool strips = forced != 1 && (forced != 0 || frames_1080p_equivalent(plan_, act) >= 32.0);
+	const bool yuy2 = kind == PIX_YUY2 || kind == PIX_2VUY, bayer = kind == PIX_BYR4 || kind == PIX_BYR5;
+	// 4:2:2 frames of whole 32-pixel blocks whose rows are 16-byte aligned (k_fwd_yuv422_strip, k_fwd_frame_yuv422_strip)
+	const bool yuv_strips = strips && plan_.encoded_format == ENC_YUV422 && plan_.width % 32 == 0 &&
+	                        every_frame(n_, [&](int i) { return !((uintptr_t)j.yuv[i].in & 15) && !(j.yuv[i].in_pitch & 15); });
+	if (bayer && bayer_fused_) r.l1 = FwdL1::Packed16;
+	else if (bayer) {
+		// BYR4 mosaics whose component planes are whole 8-column blocks wide and whose rows are 16-byte aligned; BYR5 and small launches unpack the planes first
+		const bool ok = strips && kind == PIX_BYR4 && plan_.width % 8 == 0 && nch == 4 &&
+		                every_frame(n_, [&](int i) { return !((uintptr_t)j.bayer[i].in & 15) && !((j.bayer[i].in_pitch * 2) & 15) && j.bayer[i].order == j.bayer[0].order; });
+		r.l1 = ok ? FwdL1::BayerStrip : FwdL1::BayerUnpack;
+	} else if (strips && is_packed16(kind) && plan_.encoded_format != ENC_YUV422 && plan_.width % 8 == 0 && nch >= 3 && every_frame(n_, [&](int i) {
+		// RG48 / b64a frames of whole 8-pixel blocks whose rows are 16-byte aligned
+		const dev::FwdPlaneJob &p = j.l1[(size_t)i * nch];
+		const uintptr_t frame = (uintptr_t)((const uint16_t *)p.in - packed_word_of_channel(kind, 0));
+		return !(frame & 15) && !((p.in_pitch * 2) & 15) && p.layout == 0 && p.width % 8 == 0; })) r.l1 = FwdL1::Packed16Strip;
+	else if (enc_packed16(kind)) r.l1 = FwdL1::Packed16;
+	else if (plan_.interlaced) r.l1 = yuv_strips && yuy2 ? FwdL1::FrameYuv422Strip : FwdL1::FrameYuv422;
+	else if (!yuv_strips) r.l1 = FwdL1::Yuv422;
+	// block lists wherever the 4:2:2 strip kernel runs in front of the GPU entropy stage; their dense rows are written too when something else reads the coefficients
+	else if (blocks_env && ent_ready_ && ent_.block_slots() && yuy2) r.l1 = coeffs_needed ? FwdL1::Yuv422StripBlocksDense : FwdL1::Yuv422StripBlocks;
+	else r.l1 = FwdL1::Yuv422Strip;
+	return r;
 }
 
-// k_fwd_frame_yuv422_strip: the same geometry rule for interlaced 4:2:2 frames (else the LDS-tiled k_fwd_frame_yuv422)
-bool EncodeBatch::strip_forward_frame() const
+const char *EncodeBatch::level_kernel(int level, bool coeffs_needed) const
 {
-	const int forced = shape_override("CFHD_AMD_FORWARD");
-	const int act = active_ > 0 && active_ < n_ ? active_ : n_;
-	if (forced == 1 || (forced == 0 && frames_1080p_equivalent(plan_, act) < 32.0)) return false;
-	if (!plan_.interlaced || plan_.encoded_format != ENC_YUV422 || plan_.width % 32 || !(plan_.pixel_kind == PIX_YUY2 || plan_.pixel_kind == PIX_2VUY)) return false;
-	EncJobs j = enc_jobs_at(h_jobs_, n_, plan_.num_channels);
-	for (int i = 0; i < n_; i++) if (((uintptr_t)j.yuv[i].in & 15) || (j.yuv[i].in_pitch & 15)) return false;
-	return true;
-}
-
-// k_fwd_packed16_strip serves RG48 / b64a frames of whole 8-pixel blocks whose rows are 16-byte aligned, from the launch size on at which
-// the strip kernels pay (as strip_forward()); everything else takes the LDS-tiled k_fwd_packed16.
-bool EncodeBatch::strip_forward_packed16() const
-{
-	const int forced = shape_override("CFHD_AMD_FORWARD");
-	const int act = active_ > 0 && active_ < n_ ? active_ : n_;
-	if (forced == 1 || (forced == 0 && frames_1080p_equivalent(plan_, act) < 32.0)) return false;
-	if (!is_packed16(plan_.pixel_kind) || plan_.encoded_format == ENC_YUV422 || plan_.width % 8 || plan_.num_channels < 3) return false;
-	EncJobs j = enc_jobs_at(h_jobs_, n_, plan_.num_channels);
-	for (int i = 0; i < n_; i++) {
-		const dev::FwdPlaneJob &p = j.l1[(size_t)i * plan_.num_channels];
-		const uintptr_t frame = (uintptr_t)((const uint16_t *)p.in - packed_word_of_channel(plan_.pixel_kind, 0));
-		if ((frame & 15) || ((p.in_pitch * 2) & 15) || p.layout != 0 || p.width % 8) return false;
-	}
-	return true;
-}
-
-// k_fwd_bayer_strip serves BYR4 mosaics whose component planes are whole 8-column blocks wide and whose rows are 16-byte aligned, from the launch size on at which
-// the strip kernels pay; BYR5, small launches and CFHD_AMD_FORWARD=tile take k_unpack_byr4 + k_fwd_plane.
-bool EncodeBatch::strip_forward_bayer() const
-{
-	const int forced = shape_override("CFHD_AMD_FORWARD");
-	const int act = active_ > 0 && active_ < n_ ? active_ : n_;
-	if (forced == 1 || (forced == 0 && frames_1080p_equivalent(plan_, act) < 32.0)) return false;
-	if (plan_.pixel_kind != PIX_BYR4 || bayer_fused_ || plan_.width % 8 || plan_.num_channels != 4) return false;
-	EncJobs j = enc_jobs_at(h_jobs_, n_, plan_.num_channels);
-	for (int i = 0; i < n_; i++) if (((uintptr_t)j.bayer[i].in & 15) || ((j.bayer[i].in_pitch * 2) & 15) || j.bayer[i].order != j.bayer[0].order) return false;
-	return true;
-}
-
-const char *EncodeBatch::level_kernel(int level) const
-{
-	const int act = active_ > 0 && active_ < n_ ? active_ : n_;
-	if (level > 0) return planes_as_strips(plan_, level, act) ? "k_fwd_plane_strip" : "k_fwd_plane";
-	if (strip_forward_bayer()) return "k_fwd_bayer_strip";
-	if (plan_.pixel_kind == PIX_BYR4 || plan_.pixel_kind == PIX_BYR5) return bayer_fused_ ? "k_fwd_packed16" : "k_unpack_byr4+k_fwd_plane";
-	if (strip_forward_packed16()) return "k_fwd_packed16_strip";
-	if (enc_packed16(plan_.pixel_kind)) return "k_fwd_packed16";
-	if (plan_.interlaced) return strip_forward_frame() ? "k_fwd_frame_yuv422_strip" : "k_fwd_frame_yuv422";
-	return strip_forward() ? (block_lists_forward() ? "k_fwd_yuv422_strip_blocks" : "k_fwd_yuv422_strip") : "k_fwd_yuv422";
-}
-
-// Level-1 bands as block lists for the GPU entropy stage (k_fwd_yuv422_strip_blocks -> k_ent_count_blocks): wherever the 4:2:2 strip kernel runs in front of the
-// GPU entropy stage.  CFHD_AMD_BLOCKS=0: dense bands and k_ent_count (A/B runs).
-bool EncodeBatch::block_lists_forward() const
-{
-	static const int blocks_env = [] { const char *e = getenv("CFHD_AMD_BLOCKS"); return e ? atoi(e) : 1; }();
-	return blocks_env && ent_ready_ && ent_.block_slots() && (plan_.pixel_kind == PIX_YUY2 || plan_.pixel_kind == PIX_2VUY) && strip_forward();
+	const ForwardRoute r = forward_route(coeffs_needed);
+	return level > 0 ? kFwdPlaneName[r.strip_planes[level - 1]] : kFwdL1Name[(int)r.l1];
 }
 
 int EncodeBatch::launch_forward(bool coeffs_needed)
 {
 	(void)hipSetDevice(device_);
-	const int dense_env = 0;
-	const bool blocks = block_lists_forward();
-	if (ent_ready_) ent_.set_block_lists(blocks);
+	const ForwardRoute r = forward_route(coeffs_needed);
+	if (ent_ready_) ent_.set_block_lists(r.block_lists());
 	int rc = sync_jobs();
 	if (rc) return rc;
 	hipStream_t st = (hipStream_t)stream_;
 	const int nch = plan_.num_channels;
-	const int act = active_ > 0 && active_ < n_ ? active_ : n_;      // frames 0 .. act-1 of the batch hold frames (set_active)
+	const int act = active_frames(active_, n_);                    // frames 0 .. act-1 of the batch hold frames (set_active)
 	EncJobs j = enc_jobs_at(d_jobs_, n_, nch);
+	static_assert(sizeof(dev::FwdFrameJob) == sizeof(dev::FwdYuvJob) && offsetof(dev::FwdFrameJob, q) == offsetof(dev::FwdYuvJob, q), "the two level-1 jobs share one table");
 	(void)hipGetLastError();                            // drop stale sticky errors: the check below is for these launches only
 	timed_ = true;
 	HIPCHK(hipEventRecord((hipEvent_t)ev0_, st));
-	if ((plan_.pixel_kind == PIX_BYR4 || plan_.pixel_kind == PIX_BYR5) && bayer_fused_) {
-		// level 1 straight from the mosaic: every component plane's loader computes its samples from the photosite quads (the planes k_unpack_byr4 would
-		// write -- 8 bytes per quad out, 8 back in -- never exist)
-		dim3 grid(((plan_.width / 2 + dev::TW - 1) / dev::TW) * nch, (plan_.height / 2 + dev::TH - 1) / dev::TH, act);
-		dev::k_fwd_packed16<<<grid, dev::NTHREADS, 0, st>>>(j.l1, nch);
-	} else if (strip_forward_bayer()) {
+	const dim3 tiles((plan_.width / 2 + dev::TW - 1) / dev::TW, (plan_.height / 2 + dev::TH - 1) / dev::TH, act);      // the LDS-tiled kernels: one workgroup per tile of a half-size plane
+	const int nseg16 = (plan_.width / 16 + dev::SSEG - 1) / dev::SSEG;      // 4:2:2 strips: segments of 124 luma blocks (1984 pixels)
+	const int nseg = (plan_.width / 8 + dev::PSTEP - 1) / dev::PSTEP, nstrips = (plan_.height / 2 + dev::PSR - 1) / dev::PSR, waves = act * nseg * nstrips;      // RG48 / b64a / Bayer strips
+	switch (r.l1) {
+	case FwdL1::Packed16:
+		// (a fused Bayer batch too: every component plane's loader computes its samples from the photosite quads, the planes k_unpack_byr4 would write never exist)
+		dev::k_fwd_packed16<<<dim3(tiles.x * nch, tiles.y, act), dev::NTHREADS, 0, st>>>(j.l1, nch);
+		break;
+	case FwdL1::BayerStrip:
 		// level 1 straight from the mosaic, every photosite read and curved once, all four component planes from one pass (cfhd_kernels.h k_fwd_bayer_strip)
-		const int nseg = (plan_.width / 8 + dev::PSTEP - 1) / dev::PSTEP, nstrips = (plan_.height / 2 + dev::PSR - 1) / dev::PSR, waves = act * nseg * nstrips;
 		dev::k_fwd_bayer_strip<<<(waves + 3) / 4, dev::NTHREADS, 0, st>>>(j.l1, j.bayer, act, nseg, nstrips);
-	} else if (plan_.pixel_kind == PIX_BYR4 || plan_.pixel_kind == PIX_BYR5) {
+		break;
+	case FwdL1::BayerUnpack:
 		dev::k_unpack_byr4<<<dim3((plan_.width / 2 + dev::NTHREADS - 1) / dev::NTHREADS, plan_.height, act), dev::NTHREADS, 0, st>>>(j.bayer);      // two quads per thread
-		dim3 grid((plan_.width / 2 + dev::TW - 1) / dev::TW, (plan_.height / 2 + dev::TH - 1) / dev::TH, act * nch);
-		dev::k_fwd_plane<<<grid, dev::NTHREADS, 0, st>>>(j.l1);
-	} else if (strip_forward_packed16()) {
-		const int nseg = (plan_.width / 8 + dev::PSTEP - 1) / dev::PSTEP, nstrips = (plan_.height / 2 + dev::PSR - 1) / dev::PSR, waves = act * nseg * nstrips;
-		const dim3 grid((waves + 3) / 4);
-		if (plan_.pixel_kind == PIX_RG48) dev::k_fwd_packed16_strip<3, 3><<<grid, dev::NTHREADS, 0, st>>>(j.l1, act, nseg, nstrips);
-		else if (nch == 4) dev::k_fwd_packed16_strip<4, 4><<<grid, dev::NTHREADS, 0, st>>>(j.l1, act, nseg, nstrips);
-		else dev::k_fwd_packed16_strip<4, 3><<<grid, dev::NTHREADS, 0, st>>>(j.l1, act, nseg, nstrips);
-	} else if (enc_packed16(plan_.pixel_kind)) {
-		dim3 grid(((plan_.width / 2 + dev::TW - 1) / dev::TW) * nch, (plan_.height / 2 + dev::TH - 1) / dev::TH, act);
-		dev::k_fwd_packed16<<<grid, dev::NTHREADS, 0, st>>>(j.l1, nch);
-	} else if (strip_forward_frame()) {
-		static_assert(sizeof(dev::FwdFrameJob) == sizeof(dev::FwdYuvJob) && offsetof(dev::FwdFrameJob, q) == offsetof(dev::FwdYuvJob, q), "the two level-1 jobs share one table");
-		const int nseg = (plan_.width / 16 + dev::SSEG - 1) / dev::SSEG;      // segments of 124 luma blocks (1984 pixels)
-		dev::k_fwd_frame_yuv422_strip<<<dim3(nseg, (plan_.height / 2 + dev::SRI - 1) / dev::SRI, act), dev::NTHREADS, 0, st>>>((const dev::FwdFrameJob *)j.yuv);
-	} else if (plan_.interlaced) {
-		static_assert(sizeof(dev::FwdFrameJob) == sizeof(dev::FwdYuvJob) && offsetof(dev::FwdFrameJob, q) == offsetof(dev::FwdYuvJob, q), "the two level-1 jobs share one table");
-		dim3 grid((plan_.width / 2 + dev::FTW - 1) / dev::FTW, (plan_.height / 2 + dev::FRW - 1) / dev::FRW, act);
-		dev::k_fwd_frame_yuv422<<<grid, dev::NTHREADS, 0, st>>>((const dev::FwdFrameJob *)j.yuv);
-	} else if (strip_forward()) {
-		const int nseg = (plan_.width / 16 + dev::SSEG - 1) / dev::SSEG;      // segments of 124 luma blocks (1984 pixels)
-		const dim3 grid(nseg, (plan_.height / 2 + dev::SRF - 1) / dev::SRF, act);
-		if (blocks && (coeffs_needed || dense_env)) dev::k_fwd_yuv422_strip_blocks_dense<<<grid, dev::NTHREADS, 0, st>>>(j.yuv);
-		else if (blocks) dev::k_fwd_yuv422_strip_blocks<<<grid, dev::NTHREADS, 0, st>>>(j.yuv);
-		else dev::k_fwd_yuv422_strip<<<grid, dev::NTHREADS, 0, st>>>(j.yuv);
-	} else {
-		dim3 grid((plan_.width / 2 + dev::TW - 1) / dev::TW, (plan_.height / 2 + dev::TH - 1) / dev::TH, act);
-		dev::k_fwd_yuv422<<<grid, dev::NTHREADS, 0, st>>>(j.yuv);
+		dev::k_fwd_plane<<<dim3(tiles.x, tiles.y, act * nch), dev::NTHREADS, 0, st>>>(j.l1);
+		break;
+	case FwdL1::Packed16Strip:
+		if (plan_.pixel_kind == PIX_RG48) dev::k_fwd_packed16_strip<3, 3><<<dim3((waves + 3) / 4), dev::NTHREADS, 0, st>>>(j.l1, act, nseg, nstrips);
+		else if (nch == 4) dev::k_fwd_packed16_strip<4, 4><<<dim3((waves + 3) / 4), dev::NTHREADS, 0, st>>>(j.l1, act, nseg, nstrips);
+		else dev::k_fwd_packed16_strip<4, 3><<<dim3((waves + 3) / 4), dev::NTHREADS, 0, st>>>(j.l1, act, nseg, nstrips);
+		break;
+	case FwdL1::FrameYuv422Strip:
+		dev::k_fwd_frame_yuv422_strip<<<dim3(nseg16, (plan_.height / 2 + dev::SRI - 1) / dev::SRI, act), dev::NTHREADS, 0, st>>>((const dev::FwdFrameJob *)j.yuv);
+		break;
+	case FwdL1::FrameYuv422:
+		dev::k_fwd_frame_yuv422<<<dim3((plan_.width / 2 + dev::FTW - 1) / dev::FTW, (plan_.height / 2 + dev::FRW - 1) / dev::FRW, act), dev::NTHREADS, 0, st>>>((const dev::FwdFrameJob *)j.yuv);
+		break;
+	case FwdL1::Yuv422StripBlocksDense:
+		dev::k_fwd_yuv422_strip_blocks_dense<<<dim3(nseg16, (plan_.height / 2 + dev::SRF - 1) / dev::SRF, act), dev::NTHREADS, 0, st>>>(j.yuv);
+		break;
+	case FwdL1::Yuv422StripBlocks:
+		dev::k_fwd_yuv422_strip_blocks<<<dim3(nseg16, (plan_.height / 2 + dev::SRF - 1) / dev::SRF, act), dev::NTHREADS, 0, st>>>(j.yuv);
+		break;
+	case FwdL1::Yuv422Strip:
+		dev::k_fwd_yuv422_strip<<<dim3(nseg16, (plan_.height / 2 + dev::SRF - 1) / dev::SRF, act), dev::NTHREADS, 0, st>>>(j.yuv);
+		break;
+	case FwdL1::Yuv422:
+		dev::k_fwd_yuv422<<<tiles, dev::NTHREADS, 0, st>>>(j.yuv);
+		break;
 	}
 	for (int lv = 1; lv < 3; lv++) {
 		HIPCHK(hipEventRecord((hipEvent_t)evl_[lv - 1], st));
 		const BandDesc &src = plan_.ch[0].band[lv - 1][0];     // luma is the widest plane of the level
 		const dev::FwdPlaneJob *jobs = lv == 1 ? j.l2 : j.l3;
-		if (planes_as_strips(plan_, lv, act)) {
+		if (r.strip_planes[lv - 1]) {
 			const int n = act;
 			for_channel_runs(plan_, lv, [&](int c0, int nc, int glog, const BandDesc &b, int nseg) {
 				const int nstrips = (b.height + dev::SRP - 1) / dev::SRP, per_wave = nseg > 1 ? 1 : 64 >> glog, waves = ((n * nc + per_wave - 1) / per_wave) * nstrips * nseg;
@@ -1017,23 +996,6 @@ int DecodeBatch::prepare_entropy(size_t sample_cap)
 	return rc;
 }
 
-// The level-1 highpass bands as block lists between the entropy decoder's tile pass and k_inv_yuv422_strip_blocks (cfhd_core.h dec_block_list_layout): wherever the
-// progressive 4:2:2 strip kernel writes 8-bit 4:2:2 pictures behind the GPU entropy stage.  CFHD_AMD_DEC_BLOCKS=0: dense bands (A/B runs).
-bool DecodeBatch::block_lists_inverse() const
-{
-	const int blocks_env = [] { const char *e = getenv("CFHD_AMD_DEC_BLOCKS"); return e ? atoi(e) : 1; }();      // (read at every launch: tests switch within one process)
-	if (!blocks_env || !ent_ready_ || !ent_.block_masks(0) || !ent_.chunk_indexed()) return false;
-	if (half_ || dec_planes16(out_kind_) || rgb32_of_422_ || rgb16_of_422_ || rgb24_of_422_ || v210_ || byr4_) return false;
-	if (!(out_kind_ == PIX_YUY2 || out_kind_ == PIX_2VUY) || plan_.encoded_format != ENC_YUV422) return false;
-	return interlaced_ ? frame_inverse_strips() : strip_inverse();      // (interlaced: LH and HH as lists, the difference-coded HL dense)
-}
-
-int DecodeBatch::launch_entropy()
-{
-	ent_.set_block_lists(block_lists_inverse());
-	return ent_.launch();
-}
-
 int DecodeBatch::sync_jobs()
 {
 	(void)hipSetDevice(device_);
@@ -1072,81 +1034,89 @@ int DecodeBatch::set_device_output(int i, void *d_out, int pitch)
 	return 0;
 }
 
-// k_inv_yuv422_strip serves luma bands of whole 16-column blocks and writes 16-byte words; everything else (and
-// CFHD_AMD_INVERSE=tile, for A/B runs) takes the LDS-tiled k_inv_yuv422.  Both produce the same bytes.
-bool DecodeBatch::strip_inverse() const
-{
-	const int forced = shape_override("CFHD_AMD_INVERSE");
-	const int bw = plan_.ch[0].band[0][0].width;
-	const int act = active_ > 0 && active_ < n_ ? active_ : n_;
-	if (forced == 1 || (forced == 0 && frames_1080p_equivalent(plan_, act) < 12.0)) return false;
-	if (dec_planes16(out_kind_) || bw % 16) return false;
-	DecJobs j = dec_jobs_at(h_jobs_, n_, plan_.num_channels);
-	for (int i = 0; i < n_; i++) if (((uintptr_t)j.yuv[i].out & 15) || (j.yuv[i].out_pitch & 15)) return false;
-	return true;
-}
+// The last level of the inverse transform: every kernel launch_inverse() can pick, and the name a profiler shows it under (level_kernel()).  Where a strip kernel and
+// an LDS-tiled one serve the same output they produce the same bytes.
+enum class InvL1 { Refused, HalfRgb24, HalfRgb, HalfYu64, HalfPacked16, HalfYuv422, FrameRows16, FrameRows16Col, Packed16Strip, Yuv422Rgb32, Rgb10, Packed16,
+                   FrameYuv422StripBlocks, FrameYuv422Strip, FrameYuv422Quad, FrameYuv422, Yuv422StripBlocks, Yuv422Strip, Yuv422 };
+static const char *const kInvL1Name[] = {"refused", "k_half_rgb24", "k_half_rgb", "k_half_yu64", "k_half_packed16", "k_half_yuv422", "k_inv_frame_yuv422_rows16", "k_inv_frame_yuv422_rows16_col",
+                                         "k_inv_packed16_strip", "k_inv_yuv422_rgb32", "k_inv_rgb10", "k_inv_packed16", "k_inv_frame_yuv422_strip_blocks", "k_inv_frame_yuv422_strip",
+                                         "k_inv_frame_yuv422_quad", "k_inv_frame_yuv422", "k_inv_yuv422_strip_blocks", "k_inv_yuv422_strip", "k_inv_yuv422"};
+static const char *const kInvPlaneName[2] = {"k_inv_plane", "k_inv_plane_strip"};      // levels 3 and 2: [planes_as_strips()]
+static_assert(sizeof(kInvL1Name) / sizeof(*kInvL1Name) == (size_t)InvL1::Yuv422 + 1, "one name per last-level kernel");
+struct InverseRoute {
+	InvL1 l1; bool strip_planes[2];                     // [lv - 1]: level lv + 1 runs as k_inv_plane_strip
+	// the level-1 highpass bands travel as block lists between the entropy decoder's tile pass and the kernel that gathers them (cfhd_core.h dec_block_list_layout;
+	// interlaced: LH and HH as lists, the difference-coded HL dense)
+	bool block_lists() const { return l1 == InvL1::Yuv422StripBlocks || l1 == InvL1::FrameYuv422StripBlocks; }
+};
 
-// k_inv_packed16_strip serves RG48 / b64a output of whole 8-pixel blocks whose rows are 16-byte aligned, from the launch size on at which the
-// strip kernels pay; everything else takes the LDS-tiled k_inv_packed16.
-bool DecodeBatch::strip_inverse_packed16() const
+// The kernels of the next launch_entropy() + launch_inverse(), from the prepared batch alone: the environment switches, the active frame count and the job table are read
+// here and nowhere else.
+InverseRoute DecodeBatch::inverse_route() const
 {
-	const int forced = shape_override("CFHD_AMD_INVERSE");
-	const int act = active_ > 0 && active_ < n_ ? active_ : n_;
-	if (forced == 1 || (forced == 0 && frames_1080p_equivalent(plan_, act) < 12.0)) return false;
-	if (!is_packed16(out_kind_) || half_ || plan_.ch[0].band[0][0].width % 4 || (out_kind_ == PIX_B64A && plan_.num_channels == 3) || byr4_) return false;      // (the strip kernel knows the RG48 and b64a pixels only)
-	DecJobs j = dec_jobs_at(h_jobs_, n_, plan_.num_channels);
-	const int onch = dec_out_channels(out_kind_, plan_);
-	for (int i = 0; i < n_; i++) {
-		const dev::InvPlaneJob &p = j.l1[(size_t)i * onch];
-		const uintptr_t frame = (uintptr_t)((const uint16_t *)p.out - packed_word_of_channel(out_kind_, 0));
-		if ((frame & 15) || ((p.out_pitch * 2) & 15) || (p.band_pitch & 3)) return false;
-	}
-	return true;
-}
-
-// k_inv_frame_yuv422_strip: the interlaced last level in the shape of k_inv_yuv422_strip, under the same conditions
-bool DecodeBatch::frame_inverse_strips() const
-{
-	if (!interlaced_ || half_) return false;
-	for (int c = 0; c < 3; c++) if (plan_.ch[c].band[0][0].pitch % 8) return false;
-	return strip_inverse();
-}
-
-// k_inv_frame_yuv422_quad: four band columns per thread with 8-byte loads and 16-byte stores (CFHD_AMD_INVERSE=tile: the one-column kernel)
-bool DecodeBatch::frame_inverse_quads() const      // (also k_inv_frame_yuv422_rows16 against k_inv_frame_yuv422_rows16_col)
-{
-	const int forced = shape_override("CFHD_AMD_INVERSE");
+	const int blocks_env = [] { const char *e = getenv("CFHD_AMD_DEC_BLOCKS"); return e ? atoi(e) : 1; }();      // 0: dense bands (A/B runs; read at every launch: tests switch within one process)
+	const int act = active_frames(active_, n_), forced = shape_override("CFHD_AMD_INVERSE"), nch = plan_.num_channels;
 	const BandDesc &b = plan_.ch[0].band[0][0];
-	if (forced == 1 || b.width % 4 || b.width < 8) return false;
-	for (int c = 0; c < 3; c++) if (plan_.ch[c].band[0][0].pitch % 4) return false;
-	DecJobs j = dec_jobs_at(h_jobs_, n_, plan_.num_channels);
-	for (int i = 0; i < n_; i++) if (((uintptr_t)j.yuv[i].out & 15) || (j.yuv[i].out_pitch & 15)) return false;
-	return true;
+	const DecJobs j = dec_jobs_at(h_jobs_, n_, nch);
+	InverseRoute r;
+	for (int lv = 1; lv < 3; lv++) r.strip_planes[lv - 1] = planes_as_strips(plan_, lv, act);
+	// the register-strip kernels pay from 12 frames of 1080p on (CFHD_AMD_INVERSE=tile / strip, for A/B runs: never / wherever the geometry allows)
+	const bool strips = forced != 1 && (forced != 0 || frames_1080p_equivalent(plan_, act) >= 12.0);
+	auto pitches_divide = [&](int m) { for (int c = 0; c < 3; c++) if (plan_.ch[c].band[0][0].pitch % m) return false; return true; };
+	auto rows_aligned = [&] { return every_frame(n_, [&](int i) { return !((uintptr_t)j.yuv[i].out & 15) && !(j.yuv[i].out_pitch & 15); }); };      // 16-byte stores
+	// interlaced: four band columns per thread with 8-byte loads and 16-byte stores, else the one-column kernel
+	auto quads = [&] { return forced != 1 && b.width % 4 == 0 && b.width >= 8 && pitches_divide(4) && rows_aligned(); };
+	// 8-bit 4:2:2 pictures behind the chunk-indexed GPU entropy decoder take the level-1 bands as block lists wherever a 4:2:2 strip kernel runs
+	const bool lists = blocks_env && ent_ready_ && ent_.block_masks(0) && ent_.chunk_indexed() && (out_kind_ == PIX_YUY2 || out_kind_ == PIX_2VUY) && plan_.encoded_format == ENC_YUV422;
+	// (interlaced samples at full resolution: the 16-bit rows serve RG48 / b64a / BGRA / BGRa only -- YU64, v210 and the 10-bit RGB words are refused at the C ABI)
+	if (interlaced_ && !half_ && dec_planes16(out_kind_)) r.l1 = !rgb16_of_422_ ? InvL1::Refused : (quads() ? InvL1::FrameRows16 : InvL1::FrameRows16Col);
+	// half resolution: the last level is not run, the level-1 lowpass planes are the picture
+	else if (half_ && plan_.encoded_format == ENC_YUV422 && (dec_rgb8(out_kind_) || out_kind_ == PIX_RG48 || out_kind_ == PIX_B64A)) r.l1 = InvL1::HalfRgb24;
+	else if (half_ && (dec_rgb8(out_kind_) || dec_rgb10(out_kind_) || (out_kind_ == PIX_B64A && nch == 3))) r.l1 = InvL1::HalfRgb;
+	else if (half_) r.l1 = out_kind_ == PIX_YU64 ? InvL1::HalfYu64 : (is_packed16(out_kind_) ? InvL1::HalfPacked16 : InvL1::HalfYuv422);
+	// RG48 / b64a output of whole 8-pixel blocks whose rows are 16-byte aligned (the strip kernel knows the RG48 and b64a pixels only)
+	else if (strips && is_packed16(out_kind_) && b.width % 4 == 0 && !(out_kind_ == PIX_B64A && nch == 3) && !byr4_ && every_frame(n_, [&](int i) {
+		const dev::InvPlaneJob &p = j.l1[(size_t)i * dec_out_channels(out_kind_, plan_)];
+		const uintptr_t frame = (uintptr_t)((const uint16_t *)p.out - packed_word_of_channel(out_kind_, 0));
+		return !(frame & 15) && !((p.out_pitch * 2) & 15) && !(p.band_pitch & 3); })) r.l1 = InvL1::Packed16Strip;
+	else if (rgb32_of_422_) r.l1 = InvL1::Yuv422Rgb32;
+	else if (dec_planes16(out_kind_)) r.l1 = dec_rgb10(out_kind_) ? InvL1::Rgb10 : InvL1::Packed16;
+	// 4:2:2 pictures: luma bands of whole 16-column blocks, written in 16-byte words (interlaced: band rows of whole 8-coefficient words too)
+	else if (strips && b.width % 16 == 0 && rows_aligned() && (!interlaced_ || pitches_divide(8)))
+		r.l1 = interlaced_ ? (lists ? InvL1::FrameYuv422StripBlocks : InvL1::FrameYuv422Strip) : (lists ? InvL1::Yuv422StripBlocks : InvL1::Yuv422Strip);
+	else if (interlaced_) r.l1 = quads() ? InvL1::FrameYuv422Quad : InvL1::FrameYuv422;
+	else r.l1 = InvL1::Yuv422;
+	return r;
 }
 
 const char *DecodeBatch::level_kernel(int level) const
 {
-	const int act = active_ > 0 && active_ < n_ ? active_ : n_;
-	if (level > 0) return planes_as_strips(plan_, level, act) ? "k_inv_plane_strip" : "k_inv_plane";
-	if (half_) return is_packed16(out_kind_) ? "k_half_packed16" : "k_half_yuv422";
-	if (dec_rgb10(out_kind_)) return "k_inv_rgb10";
-	if (interlaced_ && rgb16_of_422_) return frame_inverse_quads() ? "k_inv_frame_yuv422_rows16" : "k_inv_frame_yuv422_rows16_col";
-	if (dec_planes16(out_kind_)) return strip_inverse_packed16() ? "k_inv_packed16_strip" : "k_inv_packed16";
-	if (interlaced_) return frame_inverse_strips() ? (block_lists_inverse() ? "k_inv_frame_yuv422_strip_blocks" : "k_inv_frame_yuv422_strip") : (frame_inverse_quads() ? "k_inv_frame_yuv422_quad" : "k_inv_frame_yuv422");
-	return strip_inverse() ? (block_lists_inverse() ? "k_inv_yuv422_strip_blocks" : "k_inv_yuv422_strip") : "k_inv_yuv422";
+	const InverseRoute r = inverse_route();
+	return level > 0 ? kInvPlaneName[r.strip_planes[level - 1]] : kInvL1Name[(int)r.l1];
+}
+
+int DecodeBatch::launch_entropy()
+{
+	ent_.set_block_lists(inverse_route().block_lists());
+	return ent_.launch();
 }
 
 int DecodeBatch::launch_inverse(uint32_t dither_seed)
 {
+	InverseRoute r = inverse_route();
 	// (the level-1 bands of the last entropy pass are block lists: only the kernel that gathers them may run behind it)
-	if (ent_ready_ && ent_.level1_as_block_lists() && !block_lists_inverse()) { g_err = "the level-1 bands are block lists but the inverse would read them as dense rows"; return -1; }
+	const bool lists = ent_ready_ && ent_.level1_as_block_lists();
+	if (lists && !r.block_lists()) { g_err = "the level-1 bands are block lists but the inverse would read them as dense rows"; return -1; }
+	if (r.l1 == InvL1::Refused) return -1;
+	// (the route is what the next entropy pass would leave; bands that came as dense rows -- upload_coeffs() -- go through the same strip kernel's dense form)
+	if (!lists && r.block_lists()) r.l1 = interlaced_ ? InvL1::FrameYuv422Strip : InvL1::Yuv422Strip;
 	(void)hipSetDevice(device_);
 	const bool jobs_uploaded_now = jobs_dirty_;          // (the upload is queued on `st`: a second stream must not read the tables before it)
 	int rc = sync_jobs();
 	if (rc) return rc;
 	hipStream_t st = (hipStream_t)stream_;
 	const int nch = plan_.num_channels;
-	const int act = active_ > 0 && active_ < n_ ? active_ : n_;      // frames 0 .. act-1 carry pyramids (set_active)
+	const int act = active_frames(active_, n_);                    // frames 0 .. act-1 carry pyramids (set_active)
 	DecJobs j = dec_jobs_at(d_jobs_, n_, nch);
 	(void)hipGetLastError();
 	timed_ = true;
@@ -1158,9 +1128,9 @@ int DecodeBatch::launch_inverse(uint32_t dither_seed)
 	if (inv_split_) { HIPCHK(hipStreamWaitEvent(sl, (hipEvent_t)l23, 0)); HIPCHK(hipEventRecord((hipEvent_t)ev2_[0], sl)); }
 	HIPCHK(hipEventRecord((hipEvent_t)ev0_, st));
 	for (int lv = 2; lv >= 1; lv--) {
-		const BandDesc &b = plan_.ch[0].band[lv][0];
+		const BandDesc &lb = plan_.ch[0].band[lv][0];
 		const dev::InvPlaneJob *jobs = lv == 2 ? j.l3 : j.l2;
-		if (planes_as_strips(plan_, lv, act)) {
+		if (r.strip_planes[lv - 1]) {
 			const int n = act;
 			for_channel_runs(plan_, lv, [&](int c0, int nc, int glog, const BandDesc &cb, int nseg) {
 				const int nstrips = (cb.height + dev::SRP - 1) / dev::SRP, per_wave = nseg > 1 ? 1 : 64 >> glog, waves = ((n * nc + per_wave - 1) / per_wave) * nstrips * nseg;
@@ -1169,7 +1139,7 @@ int DecodeBatch::launch_inverse(uint32_t dither_seed)
 			HIPCHK(hipEventRecord((hipEvent_t)(inv_split_ ? ev2_[3 - lv] : evl_[2 - lv]), sl));
 			continue;
 		}
-		dim3 grid((b.width + dev::ITW - 1) / dev::ITW, (b.height + dev::ITH - 1) / dev::ITH, act * nch);
+		dim3 grid((lb.width + dev::ITW - 1) / dev::ITW, (lb.height + dev::ITH - 1) / dev::ITH, act * nch);
 		dev::k_inv_plane<<<grid, dev::NTHREADS, 0, sl>>>(jobs);
 		HIPCHK(hipEventRecord((hipEvent_t)(inv_split_ ? ev2_[3 - lv] : evl_[2 - lv]), sl));
 	}
@@ -1177,58 +1147,41 @@ int DecodeBatch::launch_inverse(uint32_t dither_seed)
 		HIPCHK(hipStreamWaitEvent(st, (hipEvent_t)ev2_[2], 0));
 		HIPCHK(hipEventRecord((hipEvent_t)evl_[1], st));
 	}
-	// (interlaced samples at full resolution: the 16-bit rows serve RG48 / b64a / BGRA / BGRa only -- YU64, v210 and the 10-bit RGB words are refused at the C ABI)
-	if (interlaced_ && !half_ && dec_planes16(out_kind_) && !rgb16_of_422_) return -1;
-	if (interlaced_ && !half_ && rgb16_of_422_) {
-		const BandDesc &b = plan_.ch[0].band[0][0];
-		if (frame_inverse_quads()) dev::k_inv_frame_yuv422_rows16<<<dim3((b.width / 4 + dev::NTHREADS - 1) / dev::NTHREADS, b.height, act), dev::NTHREADS, 0, st>>>(j.yuv);
-		else dev::k_inv_frame_yuv422_rows16_col<<<dim3((b.width / 2 + dev::NTHREADS - 1) / dev::NTHREADS, b.height, act), dev::NTHREADS, 0, st>>>(j.yuv);
-	} else if (half_ && plan_.encoded_format == ENC_YUV422 && (dec_rgb8(out_kind_) || out_kind_ == PIX_RG48 || out_kind_ == PIX_B64A)) {
-		const BandDesc &b = plan_.ch[0].band[0][0];
-		dev::k_half_rgb24<<<dim3((b.width / 2 + dev::NTHREADS - 1) / dev::NTHREADS, out_rows_, act), dev::NTHREADS, 0, st>>>(j.half);
-	} else if (half_ && (dec_rgb8(out_kind_) || dec_rgb10(out_kind_) || (out_kind_ == PIX_B64A && nch == 3))) {
-		const BandDesc &b = plan_.ch[0].band[0][0];
-		dev::k_half_rgb<<<dim3((b.width + dev::NTHREADS - 1) / dev::NTHREADS, out_rows_, act), dev::NTHREADS, 0, st>>>(j.halfp, dither_seed);
-	} else if (half_ && out_kind_ == PIX_YU64) {
-		const BandDesc &b = plan_.ch[0].band[0][0];
-		dev::k_half_yu64<<<dim3((b.width / 2 + dev::NTHREADS - 1) / dev::NTHREADS, out_rows_, act), dev::NTHREADS, 0, st>>>(j.half);
-	} else if (half_ && is_packed16(out_kind_)) {
-		const BandDesc &b = plan_.ch[0].band[0][0];
-		dev::k_half_packed16<<<dim3((b.width / 8 + dev::NTHREADS - 1) / dev::NTHREADS, out_rows_, act), dev::NTHREADS, 0, st>>>(j.halfp);
-	} else if (half_) {
-		const BandDesc &b = plan_.ch[0].band[0][0];
-		dev::k_half_yuv422<<<dim3((b.width / 8 + dev::NTHREADS - 1) / dev::NTHREADS, out_rows_, act), dev::NTHREADS, 0, st>>>(j.half);
-	} else if (strip_inverse_packed16()) {
-		const BandDesc &b = plan_.ch[0].band[0][0];
+	const BandDesc &b = plan_.ch[0].band[0][0];
+	const dim3 tiles((b.width + dev::ITW - 1) / dev::ITW, (b.height + dev::ITH - 1) / dev::ITH, act);      // the LDS-tiled kernels: one workgroup per tile, all components
+	const int sr = interlaced_ ? dev::SRI : dev::SR;
+	const dim3 strips((b.width / dev::SBLK + dev::SSEG - 1) / dev::SSEG, (b.height + sr - 1) / sr, act);      // the 4:2:2 strip kernels: segments of 124 luma blocks, sr band rows
+	auto rows = [&](int cols_per_thread, int nrows) { return dim3((b.width / cols_per_thread + dev::NTHREADS - 1) / dev::NTHREADS, nrows, act); };      // the row kernels: one thread per group of band columns
+	switch (r.l1) {
+	case InvL1::Refused: break;                         // (left above)
+	case InvL1::FrameRows16: dev::k_inv_frame_yuv422_rows16<<<rows(4, b.height), dev::NTHREADS, 0, st>>>(j.yuv); break;
+	case InvL1::FrameRows16Col: dev::k_inv_frame_yuv422_rows16_col<<<rows(2, b.height), dev::NTHREADS, 0, st>>>(j.yuv); break;
+	case InvL1::HalfRgb24: dev::k_half_rgb24<<<rows(2, out_rows_), dev::NTHREADS, 0, st>>>(j.half); break;
+	case InvL1::HalfRgb: dev::k_half_rgb<<<rows(1, out_rows_), dev::NTHREADS, 0, st>>>(j.halfp, dither_seed); break;
+	case InvL1::HalfYu64: dev::k_half_yu64<<<rows(2, out_rows_), dev::NTHREADS, 0, st>>>(j.half); break;
+	case InvL1::HalfPacked16: dev::k_half_packed16<<<rows(8, out_rows_), dev::NTHREADS, 0, st>>>(j.halfp); break;
+	case InvL1::HalfYuv422: dev::k_half_yuv422<<<rows(8, out_rows_), dev::NTHREADS, 0, st>>>(j.half); break;
+	case InvL1::Packed16Strip: {
 		const int nseg = (b.width / 4 + dev::PSTEP - 1) / dev::PSTEP, nstrips = (b.height + dev::QSR - 1) / dev::QSR, waves = act * nseg * nstrips;
 		if (dec_out_channels(out_kind_, plan_) == 4) dev::k_inv_packed16_strip<4><<<(waves + 3) / 4, dev::NTHREADS, 0, st>>>(j.l1, act, nseg, nstrips);
 		else dev::k_inv_packed16_strip<3><<<(waves + 3) / 4, dev::NTHREADS, 0, st>>>(j.l1, act, nseg, nstrips);
-	} else if (rgb32_of_422_) {
-		const BandDesc &b = plan_.ch[0].band[0][0];
-		dim3 grid((b.width + dev::ITW - 1) / dev::ITW, (b.height + dev::ITH - 1) / dev::ITH, act);
-		dev::k_inv_yuv422_rgb32<<<grid, dev::NTHREADS, 0, st>>>(j.yuv);
-	} else if (dec_planes16(out_kind_)) {
-		const BandDesc &b = plan_.ch[0].band[0][0];
-		dim3 grid((b.width + dev::ITW - 1) / dev::ITW, (b.height + dev::ITH - 1) / dev::ITH, act);      // one workgroup per tile, all components
-		if (dec_rgb10(out_kind_)) dev::k_inv_rgb10<<<grid, dev::NTHREADS, 0, st>>>(j.l1);
-		else { const int onch = dec_out_channels(out_kind_, plan_); dev::k_inv_packed16<<<grid, dev::NTHREADS, 0, st>>>(j.l1, onch, dec_words_per_position(out_kind_, onch), dither_seed); }
-	} else if (interlaced_) {                           // (half resolution was served above: the level-1 lowpass planes need no inverse frame transform)
-		const BandDesc &b = plan_.ch[0].band[0][0];
-		if (frame_inverse_strips()) {
-			const int nseg = (b.width / dev::SBLK + dev::SSEG - 1) / dev::SSEG;
-			if (ent_ready_ && ent_.level1_as_block_lists()) dev::k_inv_frame_yuv422_strip_blocks<<<dim3(nseg, (b.height + dev::SRI - 1) / dev::SRI, act), dev::NTHREADS, 0, st>>>(j.yuv, dither_seed);
-			else dev::k_inv_frame_yuv422_strip<<<dim3(nseg, (b.height + dev::SRI - 1) / dev::SRI, act), dev::NTHREADS, 0, st>>>(j.yuv, dither_seed);
-		} else if (frame_inverse_quads()) dev::k_inv_frame_yuv422_quad<<<dim3((b.width / 4 + dev::NTHREADS - 1) / dev::NTHREADS, b.height, act), dev::NTHREADS, 0, st>>>(j.yuv, dither_seed);
-		else dev::k_inv_frame_yuv422<<<dim3((b.width / 2 + dev::NTHREADS - 1) / dev::NTHREADS, b.height, act), dev::NTHREADS, 0, st>>>(j.yuv, dither_seed);
-	} else if (strip_inverse()) {
-		const BandDesc &b = plan_.ch[0].band[0][0];
-		const int nseg = (b.width / dev::SBLK + dev::SSEG - 1) / dev::SSEG;
-		if (ent_ready_ && ent_.level1_as_block_lists()) dev::k_inv_yuv422_strip_blocks<<<dim3(nseg, (b.height + dev::SR - 1) / dev::SR, act), dev::NTHREADS, 0, st>>>(j.yuv, dither_seed);
-		else dev::k_inv_yuv422_strip<<<dim3(nseg, (b.height + dev::SR - 1) / dev::SR, act), dev::NTHREADS, 0, st>>>(j.yuv, dither_seed);
-	} else {
-		const BandDesc &b = plan_.ch[0].band[0][0];
-		dim3 grid((b.width + dev::ITW - 1) / dev::ITW, (b.height + dev::ITH - 1) / dev::ITH, act);
-		dev::k_inv_yuv422<<<grid, dev::NTHREADS, 0, st>>>(j.yuv, dither_seed);
+		break;
+	}
+	case InvL1::Yuv422Rgb32: dev::k_inv_yuv422_rgb32<<<tiles, dev::NTHREADS, 0, st>>>(j.yuv); break;
+	case InvL1::Rgb10: dev::k_inv_rgb10<<<tiles, dev::NTHREADS, 0, st>>>(j.l1); break;
+	case InvL1::Packed16: {
+		const int onch = dec_out_channels(out_kind_, plan_);
+		dev::k_inv_packed16<<<tiles, dev::NTHREADS, 0, st>>>(j.l1, onch, dec_words_per_position(out_kind_, onch), dither_seed);
+		break;
+	}
+	// (interlaced, half resolution was served above: the level-1 lowpass planes need no inverse frame transform)
+	case InvL1::FrameYuv422StripBlocks: dev::k_inv_frame_yuv422_strip_blocks<<<strips, dev::NTHREADS, 0, st>>>(j.yuv, dither_seed); break;
+	case InvL1::FrameYuv422Strip: dev::k_inv_frame_yuv422_strip<<<strips, dev::NTHREADS, 0, st>>>(j.yuv, dither_seed); break;
+	case InvL1::FrameYuv422Quad: dev::k_inv_frame_yuv422_quad<<<rows(4, b.height), dev::NTHREADS, 0, st>>>(j.yuv, dither_seed); break;
+	case InvL1::FrameYuv422: dev::k_inv_frame_yuv422<<<rows(2, b.height), dev::NTHREADS, 0, st>>>(j.yuv, dither_seed); break;
+	case InvL1::Yuv422StripBlocks: dev::k_inv_yuv422_strip_blocks<<<strips, dev::NTHREADS, 0, st>>>(j.yuv, dither_seed); break;
+	case InvL1::Yuv422Strip: dev::k_inv_yuv422_strip<<<strips, dev::NTHREADS, 0, st>>>(j.yuv, dither_seed); break;
+	case InvL1::Yuv422: dev::k_inv_yuv422<<<tiles, dev::NTHREADS, 0, st>>>(j.yuv, dither_seed); break;
 	}
 	if (rgb24_of_422_) {
 		const int pairs = plan_.width / 2;

@@ -77,7 +77,7 @@ int GpuEntropyEncoder::prepare_units(int nframes, int16_t *d_coeffs, size_t stri
 	build_template(hdr0, &tmpl_[0]);
 	EntHostJobs &jobs = host_->jobs;
 	host_->geom = group_ ? ent_hole_geometry(gplan_, tmpl_[0]) : ent_hole_geometry(plan, tmpl_[0]);
-	// block lists of the level-1 bands, for the geometries k_fwd_yuv422_strip_blocks serves (EncodeBatch::strip_forward): one 16-byte slot per block of the
+	// block lists of the level-1 bands, for the geometries k_fwd_yuv422_strip_blocks serves (EncodeBatch::forward_route): one 16-byte slot per block of the
 	// pyramid (only the slots of listed blocks are ever touched), one mask per chunk
 	const bool lists = !group_ && !plan.interlaced && plan.encoded_format == ENC_YUV422 && (plan.pixel_kind == PIX_YUY2 || plan.pixel_kind == PIX_2VUY) && plan.width % 32 == 0;
 	// Those bands are sparse (a level-1 segment of 1024 coefficients codes ~400 bits): segments of dev::ENT_SEG_L1 coefficients there, so that the fixed cost of a wave in
