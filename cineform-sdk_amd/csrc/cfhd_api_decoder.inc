@@ -55,6 +55,30 @@ CFHD_Error CFHD_GetSampleInfo(CFHD_DecoderRef ref, void *sample, size_t size, CF
 	return ERR_OKAY;
 }
 
+// What a 4:2:2 sample `width` pixels wide decodes to -- intra samples and two-frame groups alike (CFHD_PrepareToDecode; the interlaced-only refusals follow at
+// CFHD_DecodeSample, where the scan is known):
+//   YUY2 / 2vuy: always;
+//   YU64 (16-bit words Y0 C1 Y1 C2; the reference's planar 16-bit row route; half resolution: frame.c:11146 ConvertLowpass16sToYUV64, k_half_yu64): the tail-column
+//     rule of the 16-bit rows is restated for chroma bands of 16 columns and more;
+//   v210 (the YU64 words >> 6, three to a 32-bit word: k_yu64_to_v210; half resolution: frame.c:12139 ConvertLowpass16s10bitToV210 = the half-resolution YU64 words
+//     >> 6): widths of whole six-pixel groups;
+//   RG24 (the YU64 rows through the reference's scalar colour conversion with its 15-bit dither, k_yu64_to_rgb24; half resolution: frame.c:8504, k_half_rgb24);
+//   BGRA / BGRa (the reference's fused horizontal pass + 8-bit colour conversion, spatial.c:29577: k_inv_yuv422_rgb32) and RG48 / b64a (its 16-bit rows +
+//     RGB2YUV.c:1760: k_yu64_to_rgb16) -- the last four rows of TestCFHD's table; half resolution: the level-1 lowpass planes through frame.c:8504's RGB32 branch
+//     -- its SSE2 loop, so half widths that are multiples of 16 -- and frame.c:9567 ConvertLowpass16sYUVtoRGB48: k_half_rgb24's other modes.
+// Not the 10-bit RGB words, BYR4 or the encoder-only inputs.
+static bool yuv422_output_served(int kind, int width, bool half)
+{
+	switch (kind) {
+	case PIX_YUY2: case PIX_2VUY: return true;
+	case PIX_YU64: case PIX_RG24: return width >= 128;
+	case PIX_V210: return width >= 128 && (half ? width / 2 : width) % 6 == 0;
+	case PIX_BGRA: case PIX_BGRa: return width >= 32 && (!half || (width / 2) % 16 == 0);
+	case PIX_RG48: case PIX_B64A: return width >= (half ? 32 : 128);
+	default: return false;
+	}
+}
+
 CFHD_Error CFHD_PrepareToDecode(CFHD_DecoderRef ref, int, int, CFHD_PixelFormat fmt, CFHD_DecodedResolution resolution, CFHD_DecodingFlags,
                                 void *sample, size_t size, int *aw, int *ah, CFHD_PixelFormat *af)
 {
@@ -71,15 +95,18 @@ CFHD_Error CFHD_PrepareToDecode(CFHD_DecoderRef ref, int, int, CFHD_PixelFormat 
 			// (only the header tags matter here: the caller may pass the first 512 bytes of the sample)
 			(void)parse_group_sample(s8, size < 160 ? size : 160, &pg);
 			if (pg.width <= 0 || pg.height <= 0) return ERR_BADSAMPLE;
+			// every output an intra 4:2:2 sample of this width decodes to, full and half resolution: each frame's level-1 wavelet goes through the intra route of the output
+			if (resolution != 1 && resolution != 0 && resolution != 2) return ERR_BAD_RESOLUTION;
+			const bool half = resolution == 2;
 			const int kind = pixel_kind_of(fmt);
-			if ((kind != PIX_YUY2 && kind != PIX_2VUY) || (resolution != 1 && resolution != 0)) return ERR_BADFORMAT;      // packed 8-bit 4:2:2 at full resolution
+			if (!yuv422_output_served(kind, pg.width, half)) return ERR_BADFORMAT;
 			const int display = pg.display_height ? pg.display_height : pg.height;
-			if (!build_gop_plan(&d->gplan, pg.width, display, kind)) return ERR_BADFORMAT;
+			if (!build_gop_plan(&d->gplan, pg.width, display, kind == PIX_2VUY ? PIX_2VUY : PIX_YUY2)) return ERR_BADFORMAT;      // (the plan's pixel kind is the encoder's input)
 			d->gop = true; d->gop_ready = false; d->gop_second = false;
-			d->out_format = fmt; d->out_kind = kind; d->half = false; d->prepared = true;
+			d->out_format = fmt; d->out_kind = kind; d->half = half; d->prepared = true;
 			d->plan = FramePlan(); d->plan.width = pg.width; d->plan.height = d->gplan.height; d->plan.display_height = display;
-			if (aw) *aw = pg.width;
-			if (ah) *ah = display;
+			if (aw) *aw = half ? pg.width / 2 : pg.width;
+			if (ah) *ah = half ? display / 2 : display;
 			if (af) *af = fmt;
 			return ERR_OKAY;
 		}
@@ -95,44 +122,34 @@ CFHD_Error CFHD_PrepareToDecode(CFHD_DecoderRef ref, int, int, CFHD_PixelFormat 
 	if ((encf != ENC_YUV422 && encf != ENC_RGB444 && encf != ENC_RGBA4444 && encf != ENC_BAYER) || d->header.transform_type != 0) return ERR_BADFORMAT;
 	int kind = pixel_kind_of(fmt);
 	if (kind == PIX_NONE) return ERR_BADFORMAT;
-	// 4:2:2 samples decode to the packed 4:2:2 formats, RGB 4:4:4 samples to RG48 (wavelet.c:4947), RGBA 4:4:4:4 samples to b64a
-	// (bayer.c:11916 Row16uFull2OutputFormat); colour conversions between the families (ConvertLib / the colour part of the
-	// active-metadata pipeline in the reference) are not built
-	// ... and to YU64 (16-bit words Y0 C1 Y1 C2; the reference's planar 16-bit row route, full resolution, progressive samples)
-	if (kind == PIX_YU64 && encf != ENC_YUV422) return ERR_BADFORMAT;      // (half resolution: frame.c:11146 ConvertLowpass16sToYUV64, k_half_yu64)
-	// ... and RGB 4:4:4 samples to the 8-bit pixels RG24 / BGRA / BGRa (the RG48 reconstruction reduced with the reference's four-bit dither; full resolution)
-	const bool rgb8 = kind == PIX_RG24 || kind == PIX_BGRA || kind == PIX_BGRa;
-	// ... and RGBA 4:4:4:4 samples to BGRA / BGRa (no dither there: (12-bit component + 2) >> 4, the alpha expanded from that rounded value)
-	const bool rgba8 = (kind == PIX_BGRA || kind == PIX_BGRa) && encf == ENC_RGBA4444;
-	// ... and 4:2:2 samples to RG24: the YU64 rows through the reference's scalar colour conversion with its 15-bit dither (DecodeBatch / k_yu64_to_rgb24)
-	const bool rgb24_of_422 = kind == PIX_RG24 && encf == ENC_YUV422 && d->header.width >= 128;      // (half resolution: frame.c:8504, k_half_rgb24)
-	// ... and 4:2:2 samples to BGRA / BGRa (the reference's fused horizontal pass + 8-bit colour conversion, spatial.c:29577: k_inv_yuv422_rgb32) and to RG48 / b64a (its
-	// 16-bit rows + RGB2YUV.c:1760: k_yu64_to_rgb16) -- the last four rows of TestCFHD's table; full resolution, progressive
-	// (half resolution: the level-1 lowpass planes through frame.c:8504's RGB32 branch -- its SSE2 loop, so half widths that are multiples of 16 -- and frame.c:9567
-	// ConvertLowpass16sYUVtoRGB48: k_half_rgb24's other modes)
-	const bool rgb32_of_422 = (kind == PIX_BGRA || kind == PIX_BGRa) && encf == ENC_YUV422 && d->header.width >= 32 && (!half || (d->header.width / 2) % 16 == 0);
-	const bool rgb16_of_422 = (kind == PIX_RG48 || kind == PIX_B64A) && encf == ENC_YUV422 && d->header.width >= (half ? 32 : 128);
-	// (half resolution -- frame.c:7150 ConvertLowpassRGB444ToRGB -- for the outputs of RGB 4:4:4 samples: 8-bit, 10-bit, b64a; k_half_rgb)
-	if (rgb8 && ((encf != ENC_RGB444 && !rgba8 && !rgb24_of_422 && !rgb32_of_422) || (half && encf != ENC_RGB444 && !rgba8 && !rgb24_of_422 && !rgb32_of_422) || d->header.width < 32)) return ERR_BADFORMAT;
-	// ... and to the 10-bit RGB words r210 / DPX0 / AB10 / AR10 ((value before the final >> 1, + 3) >> 3 per component: a model fitted on the reference
-	// decoder and pinned word for word on the CPU, equal to the reference decoder on the GPU)
-	const bool rgb10 = kind >= PIX_R210 && kind <= PIX_AR10;
-	if (rgb10 && (encf != ENC_RGB444 || d->header.width < 32)) return ERR_BADFORMAT;
-	// ... and 4:2:2 samples to v210 (the YU64 words >> 6, three to a 32-bit word: DecodeBatch / k_yu64_to_v210; widths of whole six-pixel groups)
-	if (kind == PIX_V210 && (encf != ENC_YUV422 || (half ? d->header.width / 2 : d->header.width) % 6 || d->header.width < 128)) return ERR_BADFORMAT;      // (half resolution: frame.c:12139 ConvertLowpass16s10bitToV210 = the half-resolution YU64 words >> 6)
-	// ... and Bayer samples to BYR4: the raw mosaic, no demosaic (the four planes as 16-bit rows, recombined per quad and sent through the reference's linear-restore
-	// table: DecodeBatch / k_bayer_to_byr4; full resolution)
-	const bool byr4_of_bayer = kind == PIX_BYR4 && encf == ENC_BAYER && !half && d->header.width >= 32;
-	if ((encf == ENC_BAYER) != byr4_of_bayer) return ERR_BADFORMAT;
-	if ((kind == PIX_BYR4 && !byr4_of_bayer) || kind == PIX_BYR5 || kind == PIX_RG64 || (kind >= PIX_R210 && kind <= PIX_AR10 && !rgb10)) return ERR_BADFORMAT;     // encoder inputs only
-	// ... and RGB 4:4:4 samples to b64a (the RG48 words behind a constant alpha word 0xfff0, full resolution: what TestCFHD's b64a -> RGB 4:4:4 row decodes to)
-	const bool b64a_of_444 = kind == PIX_B64A && encf == ENC_RGB444;
-	// ... and RGBA 4:4:4:4 samples to RG48 (the RG48 route on planes G, R, B, the alpha plane left behind; full and half resolution)
-	const bool rg48_of_4444 = kind == PIX_RG48 && encf == ENC_RGBA4444;
-	if ((kind == PIX_RG48 || kind == PIX_B64A) && encf == ENC_YUV422 && !rgb16_of_422) return ERR_BADFORMAT;
-	if ((encf == ENC_RGB444) != ((kind == PIX_RG48 && !rg48_of_4444 && !rgb16_of_422) || (rgb8 && !rgba8 && !rgb24_of_422 && !rgb32_of_422) || rgb10 || b64a_of_444) ||
-	    (encf == ENC_RGBA4444) != ((kind == PIX_B64A && !b64a_of_444 && !rgb16_of_422) || rgba8 || rg48_of_4444)) return ERR_BADFORMAT;
-	if (kind == PIX_YU64 && d->header.width < 128) return ERR_BADFORMAT;      // (the tail-column rule of the 16-bit rows is restated for chroma bands of 16 columns and more)
+	// 4:2:2 samples decode to the packed 4:2:2 formats, YU64, v210 and the RGB outputs of yuv422_output_served (the same gate as two-frame groups)
+	if (encf == ENC_YUV422) { if (!yuv422_output_served(kind, d->header.width, half)) return ERR_BADFORMAT; }
+	else {
+		// RGB 4:4:4 samples decode to RG48 (wavelet.c:4947), RGBA 4:4:4:4 samples to b64a (bayer.c:11916 Row16uFull2OutputFormat); colour conversions between the
+		// families (ConvertLib / the colour part of the active-metadata pipeline in the reference) are not built; YU64 and v210 are 4:2:2 samples' only
+		if (kind == PIX_YU64 || kind == PIX_V210) return ERR_BADFORMAT;
+		// ... and RGB 4:4:4 samples to the 8-bit pixels RG24 / BGRA / BGRa (the RG48 reconstruction reduced with the reference's four-bit dither; full resolution)
+		const bool rgb8 = kind == PIX_RG24 || kind == PIX_BGRA || kind == PIX_BGRa;
+		// ... and RGBA 4:4:4:4 samples to BGRA / BGRa (no dither there: (12-bit component + 2) >> 4, the alpha expanded from that rounded value)
+		const bool rgba8 = (kind == PIX_BGRA || kind == PIX_BGRa) && encf == ENC_RGBA4444;
+		// (half resolution -- frame.c:7150 ConvertLowpassRGB444ToRGB -- for the outputs of RGB 4:4:4 samples: 8-bit, 10-bit, b64a; k_half_rgb)
+		if (rgb8 && ((encf != ENC_RGB444 && !rgba8) || d->header.width < 32)) return ERR_BADFORMAT;
+		// ... and to the 10-bit RGB words r210 / DPX0 / AB10 / AR10 ((value before the final >> 1, + 3) >> 3 per component: a model fitted on the reference
+		// decoder and pinned word for word on the CPU, equal to the reference decoder on the GPU)
+		const bool rgb10 = kind >= PIX_R210 && kind <= PIX_AR10;
+		if (rgb10 && (encf != ENC_RGB444 || d->header.width < 32)) return ERR_BADFORMAT;
+		// ... and Bayer samples to BYR4: the raw mosaic, no demosaic (the four planes as 16-bit rows, recombined per quad and sent through the reference's linear-restore
+		// table: DecodeBatch / k_bayer_to_byr4; full resolution)
+		const bool byr4_of_bayer = kind == PIX_BYR4 && encf == ENC_BAYER && !half && d->header.width >= 32;
+		if ((encf == ENC_BAYER) != byr4_of_bayer) return ERR_BADFORMAT;
+		if ((kind == PIX_BYR4 && !byr4_of_bayer) || kind == PIX_BYR5 || kind == PIX_RG64 || (kind >= PIX_R210 && kind <= PIX_AR10 && !rgb10)) return ERR_BADFORMAT;     // encoder inputs only
+		// ... and RGB 4:4:4 samples to b64a (the RG48 words behind a constant alpha word 0xfff0, full resolution: what TestCFHD's b64a -> RGB 4:4:4 row decodes to)
+		const bool b64a_of_444 = kind == PIX_B64A && encf == ENC_RGB444;
+		// ... and RGBA 4:4:4:4 samples to RG48 (the RG48 route on planes G, R, B, the alpha plane left behind; full and half resolution)
+		const bool rg48_of_4444 = kind == PIX_RG48 && encf == ENC_RGBA4444;
+		if ((encf == ENC_RGB444) != ((kind == PIX_RG48 && !rg48_of_4444) || (rgb8 && !rgba8) || rgb10 || b64a_of_444) ||
+		    (encf == ENC_RGBA4444) != ((kind == PIX_B64A && !b64a_of_444) || rgba8 || rg48_of_4444)) return ERR_BADFORMAT;
+	}
 	bool ok;
 	plan_from_sample(d->header, kind, &d->plan, &ok);
 	if (!ok) return ERR_BADSAMPLE;
@@ -192,9 +209,9 @@ static CFHD_Error decode_on_handle(Decoder *d, const ParsedSample &ps, const uin
 static CFHD_Error decode_group_sample(Decoder *d, const uint8_t *s, size_t size, void *out, int32_t pitch)
 {
 	const GopPlan &gp = d->gplan;
-	auto fail_zero = [&](int err) {
-		const int rowbytes = packed_frame_pitch(d->out_kind, gp.width);
-		for (int r = 0; r < gp.display_height; r++) memset((uint8_t *)out + (ptrdiff_t)r * pitch, 0, (size_t)rowbytes);
+	auto fail_zero = [&](int err) {                                       // (the output's own row size and row count: half size at half resolution)
+		const int rowbytes = packed_frame_pitch(d->out_kind, d->half ? gp.width / 2 : gp.width), rows = d->half ? gp.display_height / 2 : gp.display_height;
+		for (int r = 0; r < rows; r++) memset((uint8_t *)out + (ptrdiff_t)r * pitch, 0, (size_t)rowbytes);
 		return err;
 	};
 	ParsedGroup pg;
@@ -213,15 +230,24 @@ static CFHD_Error decode_group_sample(Decoder *d, const uint8_t *s, size_t size,
 	const bool interlaced = !pg.progressive;
 	for (int c = 0; c < 3; c++) for (int k = 0; k < kGopWavelets; k++) for (int b = 0; b < 4; b++)
 		if (pg.band[c][k][b].present && pg.band[c][k][b].difference != (interlaced && k < 2 && b == 2)) return fail_zero(ERR_BADSAMPLE);
+	// (as decode_on_handle refuses them for intra samples: YU64 and v210 of an interlaced group at full resolution, RG24 at either, and the 16-bit-row outputs RG48 / b64a /
+	// BGRA / BGRa at full resolution below 128 pixels -- BADFORMAT, zeroed picture, nothing queued; the P-frame sample behind it has no picture either)
+	const bool rows16_out = d->out_kind == PIX_BGRA || d->out_kind == PIX_BGRa || d->out_kind == PIX_RG48 || d->out_kind == PIX_B64A;
+	if (interlaced && ((!d->half && (d->out_kind == PIX_YU64 || d->out_kind == PIX_V210 || (rows16_out && pg.width < 128))) || d->out_kind == PIX_RG24)) {
+		d->gop_second = false;
+		return fail_zero(ERR_BADFORMAT);
+	}
 	if (d->gop_ready && d->gplan.interlaced != interlaced) d->gop_ready = false;
 	d->gplan.interlaced = interlaced;
 	if (!d->gop_ready) {
 		device_select(d->device);
-		const int prc = d->gop_batch.prepare(gp, true, d->out_kind);
+		const int prc = d->gop_batch.prepare(gp, true, d->out_kind, d->half);
 		device_select(-1);
 		if (prc) return ERR_INTERNAL;
 		d->gop_ready = true;
 	}
+	// for outputs that convert YUV to RGB: 601 or 709 by the group's colour space tag, the computer-systems range (plan_from_sample)
+	d->gop_batch.set_color_matrix((pg.color_space & 3) == 1 ? 2 : 0);
 	const uint32_t dither_seed = 0x2545F491u * ++d->frames_decoded;
 	// GPU entropy stage (the default): the sample goes to HBM, every coded band to one workgroup; a sample the device stage does not serve (launch < 0: geometry
 	// the kernels do not take, a raw band with a divisor) is decoded below by the host coder instead
@@ -241,8 +267,8 @@ static CFHD_Error decode_group_sample(Decoder *d, const uint8_t *s, size_t size,
 		const ParsedBand &lp = pg.lowpass[c];
 		const GopWavelet &top = ch.w[5];
 		if (!lp.present || lp.width != top.width || lp.height != top.height) return fail_zero(ERR_BADSAMPLE);
-		// the bias the reference adds to the lowpass band while unpacking it: twice the intra frame's for a group (decoder.c:12265 `num_frames == 2 ? 48 : 24`)
-		const int bias = 2 * lowpass_bias(10, top.width, d->out_kind);
+		// the bias the reference adds to the lowpass band while unpacking it: the group's of the requested output (group_lowpass_bias; decoder.c:12265 `num_frames == 2 ? 48 : 24`)
+		const int bias = group_lowpass_bias(top.width, d->out_kind, c);
 		for (int r = 0; r < top.height; r++) {
 			const uint8_t *p = s + lp.offset + (size_t)r * top.width * 2;
 			int16_t *dst = coeffs + top.offset[0] + (size_t)r * top.pitch;

@@ -455,6 +455,14 @@ int lowpass_bias(int precision, int lowpass_width, int out_pixel_kind, int chann
 	return 0;
 }
 
+int group_lowpass_bias(int lowpass_width, int out_pixel_kind, int channel)
+{
+	// decoder.c:12273-12278 `codec->num_frames == 2 ? 14 : 4` for YU64 / YR16 / V210, `? 48 : 24` for every other output
+	if ((lowpass_width & 1) == 0) return out_pixel_kind == PIX_YU64 || out_pixel_kind == PIX_V210 ? 14 : 48;
+	// odd widths (:12486 `? 10 : 5`), then the same -8 / -4 YUV -> RGB correction as for intra frames for RGB24 / RGB32 (RG24, BGRA; :12504-12510)
+	return 10 + (out_pixel_kind == PIX_RG24 || out_pixel_kind == PIX_BGRA ? (channel == 0 ? -8 : -4) : 0);
+}
+
 // ------------------------------------------------------------------------------------------
 // Host VLC decode
 // ------------------------------------------------------------------------------------------

@@ -160,6 +160,9 @@ int parse_sample(const uint8_t *data, size_t size, ParsedSample *out);
 // Bias the reference decoder adds to every lowpass coefficient while unpacking it (Codec/decoder.c:12240-12290 fast path for
 // even widths, :12468-12545 bit-serial path for odd widths): depends on the sample precision and the output pixel format.
 int lowpass_bias(int precision, int lowpass_width, int out_pixel_kind, int channel = 0);
+// The same for the lowpass band of a two-frame group (10-bit; num_frames == 2 in the same code): twice the intra bias except for the 10-bit and 16-bit 4:2:2
+// outputs of even widths (14, not 8) and the bottom-up RGB outputs of odd widths (the correction is not doubled).
+int group_lowpass_bias(int lowpass_width, int out_pixel_kind, int channel);
 // Host VLC decode of one band into a zeroed band. Returns 0 on success.
 int vlc_decode_band(const uint8_t *data, size_t bytes, int width, int height, int pitch, int quant, int codebook, int16_t *band);
 // What the reference does to a decoded difference band (DecodeBandFSM16sNoGapWithPeaks decoder.c:19809 + :20822): coefficients beyond the peak

@@ -32,7 +32,7 @@ const char *device_last_error();
 
 // N frames that travel through the forward path together: one launch per wavelet level covers every channel of
 // every frame (blockIdx.z walks the job table).  N = 1 is the synchronous CFHD_EncodeSample path.
-struct ForwardRoute; struct InverseRoute;      // (cfhd_device.hip: the kernels a launch picks)
+struct ForwardRoute; struct InverseRoute; struct GopRoute;      // (cfhd_device.hip: the kernels a launch picks)
 class EncodeBatch {
 public:
 	EncodeBatch();
@@ -167,8 +167,11 @@ class GopBatch {
 public:
 	GopBatch();
 	~GopBatch();
-	int prepare(const GopPlan &plan, bool decode, int out_pixel_kind);
+	// decode: out_pixel_kind is any output a 4:2:2 sample decodes to (the last level of both frames is the intra path's kernel of that output); half: the
+	// level-1 lowpass planes the temporal inverse leaves are the picture (CFHD_DECODED_RESOLUTION_HALF), the last level is not run
+	int prepare(const GopPlan &plan, bool decode, int out_pixel_kind, bool half = false);
 	const GopPlan &plan() const { return plan_; }
+	void set_color_matrix(int m);                    // decoder: the matrix of the outputs that convert to RGB (FramePlan::color_matrix), from the group sample's colour space tag
 	void set_plan(const GopPlan &plan);              // same geometry, new quantizer tables
 	// encoder
 	int upload_frame(int f, const void *frame, int pitch_bytes);      // f = 0, 1: stage one frame of the pair and start its H2D copy
@@ -192,9 +195,12 @@ public:
 	void release();
 private:
 	void fill_jobs();
-	GopPlan plan_; bool decode_ = false; int out_kind_ = 0, device_ = 0;
+	GopRoute route() const;                          // decoder: the last-level kernel and the conversion behind it, from the output kind, half and interlaced alone
+	GopPlan plan_; bool decode_ = false, half_ = false; int out_kind_ = 0, device_ = 0, matrix_ = 0;
 	void *stream_ = nullptr;
 	uint8_t *d_frames_ = nullptr, *h_frames_ = nullptr; size_t frame_bytes_ = 0; int pitch_ = 0, rows_ = 0;
+	// decoder outputs converted from 16-bit rows (RG24, RG48, b64a, v210; RG48 / b64a / BGRA / BGRa of interlaced groups): the YU64 rows of both frames first
+	uint8_t *d_tmp_ = nullptr; size_t tmp_frame_bytes_ = 0; int tmp_pitch_ = 0;
 	int16_t *d_coeff_ = nullptr, *h_coeff_ = nullptr;
 	void *d_jobs_ = nullptr, *h_jobs_ = nullptr; size_t jobs_bytes_ = 0; bool jobs_dirty_ = true;
 	GpuEntropyEncoder ent_; bool ent_ready_ = false;

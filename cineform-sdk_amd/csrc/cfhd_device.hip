@@ -1328,16 +1328,55 @@ struct GopJobs {            // layout of a GopBatch's job table
 	dev::FwdPlaneJob *top;      // [3]      w[5]
 	dev::InvPlaneJob *itop;     // [3]      w[5] -> lowpass band of w[4]
 	dev::InvPlaneJob *imid;     // [6]      w[4] -> temporal lowpass, w[3] -> temporal highpass
-	dev::InvYuvJob *iyuv;       // [2]
+	dev::InvYuvJob *iyuv;       // [2]      last level of the two frames: k_inv_yuv422 / k_inv_frame_yuv422 / k_inv_yuv422_rgb32 / k_inv_frame_yuv422_rows16(_col)
+	dev::InvPlaneJob *l1;       // [2 * 3]  the same as YU64 rows (k_inv_packed16), frame f channel c at 3 f + c
+	dev::HalfYuvJob *half;      // [2]      half resolution: the level-1 lowpass plane of each frame (k_half_yuv422 / k_half_yu64 / k_half_rgb24)
 };
 GopJobs gop_jobs_at(void *base)
 {
 	GopJobs j;
 	j.yuv = (dev::FwdYuvJob *)base; j.temp = (dev::GopTemporalJob *)(j.yuv + 2); j.mid = (dev::FwdPlaneJob *)(j.temp + 3); j.top = j.mid + 6;
 	j.itop = (dev::InvPlaneJob *)(j.top + 3); j.imid = j.itop + 3; j.iyuv = (dev::InvYuvJob *)(j.imid + 6);
+	j.l1 = (dev::InvPlaneJob *)(j.iyuv + 2); j.half = (dev::HalfYuvJob *)(j.l1 + 6);
 	return j;
 }
-size_t gop_jobs_bytes() { return 2 * sizeof(dev::FwdYuvJob) + 3 * sizeof(dev::GopTemporalJob) + 9 * sizeof(dev::FwdPlaneJob) + 9 * sizeof(dev::InvPlaneJob) + 2 * sizeof(dev::InvYuvJob); }
+size_t gop_jobs_bytes() { return 2 * sizeof(dev::FwdYuvJob) + 3 * sizeof(dev::GopTemporalJob) + 9 * sizeof(dev::FwdPlaneJob) + 15 * sizeof(dev::InvPlaneJob) + 2 * sizeof(dev::InvYuvJob) + 2 * sizeof(dev::HalfYuvJob); }
+}
+
+// The last level of a group's two frames: the intra path's kernel of the output (InvL1, one launch over both frames), then -- outputs made from 16-bit rows --
+// the conversion of both frames' YU64 rows.
+enum class GopConvert { None, Rgb24, Rgb16, V210 };
+struct GopRoute { InvL1 l1; GopConvert convert; };
+
+// What a 4:2:2 sample decodes to (DecodeBatch::prepare and inverse_route(), the C ABI's yuv422_output_served) restated for the group pyramid: the output kind, half and
+// interlaced are read here and nowhere else.
+GopRoute GopBatch::route() const
+{
+	const int k = out_kind_;
+	const bool rgb32 = k == PIX_BGRA || k == PIX_BGRa, rgb16 = is_packed16(k), yuv8 = k == PIX_YUY2 || k == PIX_2VUY;
+	if (half_) {
+		if (yuv8) return { InvL1::HalfYuv422, GopConvert::None };
+		if (k == PIX_YU64 || k == PIX_V210) return { InvL1::HalfYu64, k == PIX_V210 ? GopConvert::V210 : GopConvert::None };
+		if (k == PIX_RG24 || rgb32 || rgb16) return { InvL1::HalfRgb24, GopConvert::None };
+		return { InvL1::Refused, GopConvert::None };
+	}
+	if (plan_.interlaced) {
+		// (the inverse frame transform: 8-bit 4:2:2, or the 16-bit rows of RG48 / b64a / BGRA / BGRa; YU64, v210 and RG24 are refused at the C ABI)
+		if (yuv8) return { InvL1::FrameYuv422, GopConvert::None };
+		if (!rgb32 && !rgb16) return { InvL1::Refused, GopConvert::None };
+		const int w = plan_.ch[0].w[0].width;
+		// (the scratch rows are 16-byte aligned: 4 * width bytes, the width a multiple of 16: build_gop_plan)
+		bool quads = shape_override("CFHD_AMD_INVERSE") != 1 && w % 4 == 0 && w >= 8;
+		for (int c = 0; c < 3; c++) quads = quads && plan_.ch[c].w[0].pitch % 4 == 0;
+		return { quads ? InvL1::FrameRows16 : InvL1::FrameRows16Col, GopConvert::Rgb16 };
+	}
+	if (yuv8) return { InvL1::Yuv422, GopConvert::None };
+	if (rgb32) return { InvL1::Yuv422Rgb32, GopConvert::None };
+	if (k == PIX_YU64) return { InvL1::Packed16, GopConvert::None };
+	if (k == PIX_V210) return { InvL1::Packed16, GopConvert::V210 };
+	if (k == PIX_RG24) return { InvL1::Packed16, GopConvert::Rgb24 };
+	if (rgb16) return { InvL1::Packed16, GopConvert::Rgb16 };
+	return { InvL1::Refused, GopConvert::None };
 }
 
 GopBatch::GopBatch() {}
@@ -1351,26 +1390,36 @@ void GopBatch::release()
 	if (dec_ready_) { dec_.release(); dec_ready_ = false; }
 	if (d_frames_) hipFree(d_frames_);
 	if (h_frames_) hipHostFree(h_frames_);
+	if (d_tmp_) hipFree(d_tmp_);
 	if (d_coeff_) hipFree(d_coeff_);
 	if (h_coeff_) hipHostFree(h_coeff_);
 	if (d_jobs_) hipFree(d_jobs_);
 	if (h_jobs_) hipHostFree(h_jobs_);
 	if (stream_) device_stream_destroy(stream_);
-	d_frames_ = h_frames_ = nullptr; d_coeff_ = h_coeff_ = nullptr; d_jobs_ = h_jobs_ = nullptr; stream_ = nullptr;
+	d_frames_ = h_frames_ = d_tmp_ = nullptr; d_coeff_ = h_coeff_ = nullptr; d_jobs_ = h_jobs_ = nullptr; stream_ = nullptr;
 }
 
-int GopBatch::prepare(const GopPlan &plan, bool decode, int out_pixel_kind)
+int GopBatch::prepare(const GopPlan &plan, bool decode, int out_pixel_kind, bool half)
 {
 	int rc = device_init();
 	if (rc) return rc;
 	release();
 	device_ = device_current(); (void)hipSetDevice(device_);
-	plan_ = plan; decode_ = decode; out_kind_ = out_pixel_kind;
+	plan_ = plan; decode_ = decode; out_kind_ = out_pixel_kind; half_ = decode && half;
+	const GopRoute r = route();
+	if (decode && r.l1 == InvL1::Refused) { g_err = "two-frame groups: output not served"; return -2; }
 	HIPCHK((hipError_t)device_stream_create(&stream_));
-	pitch_ = packed_frame_pitch(decode ? out_pixel_kind : plan.pixel_kind, plan.width); rows_ = plan.display_height;
+	const int out_width = half_ ? plan.width / 2 : plan.width;      // (the output's own row size and row count, which may be half size)
+	pitch_ = packed_frame_pitch(decode ? out_pixel_kind : plan.pixel_kind, out_width); rows_ = half_ ? plan.display_height / 2 : plan.display_height;
 	frame_bytes_ = (size_t)pitch_ * rows_;
 	HIPCHK(hipMalloc((void **)&d_frames_, 2 * frame_bytes_));
 	HIPCHK(hipHostMalloc((void **)&h_frames_, 2 * frame_bytes_, hipHostMallocPortable));
+	if (decode && out_pixel_kind == PIX_V210) HIPCHK(hipMemsetAsync(d_frames_, 0, 2 * frame_bytes_, (hipStream_t)stream_));      // (row padding beyond the last whole group of 48 pixels stays zero)
+	tmp_pitch_ = 0; tmp_frame_bytes_ = 0;
+	if (decode && r.convert != GopConvert::None) {
+		tmp_pitch_ = packed_frame_pitch(PIX_YU64, out_width); tmp_frame_bytes_ = (size_t)tmp_pitch_ * rows_;
+		HIPCHK(hipMalloc((void **)&d_tmp_, 2 * tmp_frame_bytes_));
+	}
 	HIPCHK(hipMalloc((void **)&d_coeff_, plan.coeff_elems * 2));
 	HIPCHK(hipMemsetAsync(d_coeff_, 0, plan.coeff_elems * 2, (hipStream_t)stream_));      // pad columns stay zero forever
 	HIPCHK(hipHostMalloc((void **)&h_coeff_, plan.coeff_elems * 2, hipHostMallocPortable));
@@ -1381,6 +1430,14 @@ int GopBatch::prepare(const GopPlan &plan, bool decode, int out_pixel_kind)
 	memset(h_jobs_, 0, jobs_bytes_);
 	fill_jobs();
 	return 0;
+}
+
+void GopBatch::set_color_matrix(int m)
+{
+	if (m == matrix_) return;
+	if (stream_) (void)hipStreamSynchronize((hipStream_t)stream_);
+	matrix_ = m;
+	if (h_jobs_) fill_jobs();
 }
 
 void GopBatch::set_plan(const GopPlan &plan)
@@ -1434,6 +1491,28 @@ void GopBatch::fill_jobs()
 		iy.width = plan.ch[0].w[f].width; iy.height = plan.ch[0].w[f].height; iy.display_height = plan.display_height;
 		iy.uyvy = out_kind_ == PIX_2VUY; iy.shift = plan.precision - 8; iy.dither_seed = 0x9E3779B9u * (uint32_t)(f + 1);
 		iy.out = d_frames_ + frame_bytes_ * f; iy.out_pitch = pitch_;
+		// (the matrix of frame 1 is the default one: the P-frame sample that hands it out carries no colour space tag, and the reference converts it with 709 -- pinned)
+		const int matrix = f == 0 ? matrix_ : 0;
+		iy.bottom_up = out_kind_ == PIX_BGRA; iy.matrix_601 = matrix >= 2; iy.masks = nullptr;      // (k_inv_yuv422_rgb32)
+		if (!decode_) continue;
+		// the outputs made from 16-bit rows: the YU64 rows of frame f go to the scratch frame (k_inv_frame_yuv422_rows16(_col) / k_inv_packed16 / k_half_yu64 of v210)
+		uint8_t *rows16 = d_tmp_ ? d_tmp_ + tmp_frame_bytes_ * f : d_frames_ + frame_bytes_ * f;
+		const int rows16_pitch = d_tmp_ ? tmp_pitch_ : pitch_;
+		if (plan.interlaced && d_tmp_) { iy.out = rows16; iy.out_pitch = rows16_pitch; }
+		for (int c = 0; c < 3; c++) {                    // k_inv_packed16: the YU64 words of the three planes (DecodeBatch's job for a 4:2:2 sample, on the group's w[f])
+			const GopWavelet &w = plan.ch[c].w[f];
+			dev::InvPlaneJob &p = j.l1[3 * f + c];
+			memset(&p, 0, sizeof(p));
+			for (int b = 0; b < 4; b++) p.band[b] = base + w.offset[b];
+			p.band_pitch = w.pitch; p.width = w.width; p.height = w.height; p.descale = 0;
+			p.out = dec_plane_out(rows16, PIX_YU64, c); p.out_pitch = rows16_pitch / 2;
+			p.xstride = dec_stride_of_channel(PIX_YU64, c, 3); p.precision = plan.precision; p.display_height = plan.display_height;
+		}
+		dev::HalfYuvJob &hj = j.half[f];                 // half resolution: the level-1 lowpass plane the temporal inverse left in w[f]
+		for (int c = 0; c < 3; c++) { hj.ll[c] = base + plan.ch[c].w[f].offset[0]; hj.pitch[c] = plan.ch[c].w[f].pitch; }
+		hj.width = plan.ch[0].w[f].width; hj.rows = rows_; hj.uyvy = out_kind_ == PIX_2VUY; hj.matrix = matrix;
+		hj.mode = out_kind_ == PIX_RG24 ? 0 : (out_kind_ == PIX_RG48 ? 2 : (out_kind_ == PIX_B64A ? 3 : 1)); hj.bottom_up = out_kind_ == PIX_BGRA;
+		hj.out = rows16; hj.out_pitch = rows16_pitch;
 	}
 	auto fwd = [&](dev::FwdPlaneJob &p, const int16_t *in, const GopWavelet &src, const GopWavelet &dst) {
 		p.in = in; p.in_pitch = src.pitch; p.width = src.width; p.height = src.height; p.prescale = dst.prescale;
@@ -1518,8 +1597,52 @@ int GopBatch::launch_inverse(uint32_t dither_seed, bool coeffs_on_device)
 	dev::k_inv_plane<<<dim3((top.width + dev::ITW - 1) / dev::ITW, (top.height + dev::ITH - 1) / dev::ITH, 3), dev::NTHREADS, 0, st>>>(j.itop);
 	dev::k_inv_plane<<<dim3((mid.width + dev::ITW - 1) / dev::ITW, (mid.height + dev::ITH - 1) / dev::ITH, 6), dev::NTHREADS, 0, st>>>(j.imid);
 	dev::k_gop_temporal_inv<<<dim3((unsigned)((t.pitch * t.height / 2 + dev::NTHREADS - 1) / dev::NTHREADS), 3), dev::NTHREADS, 0, st>>>(j.temp);
-	if (plan_.interlaced) dev::k_inv_frame_yuv422<<<dim3((l1.width / 2 + dev::NTHREADS - 1) / dev::NTHREADS, l1.height, 2), dev::NTHREADS, 0, st>>>(j.iyuv, dither_seed);
-	else dev::k_inv_yuv422<<<dim3((l1.width + dev::ITW - 1) / dev::ITW, (l1.height + dev::ITH - 1) / dev::ITH, 2), dev::NTHREADS, 0, st>>>(j.iyuv, dither_seed);
+	// the last level of both frames (grid z = 2), as DecodeBatch::launch_inverse launches the same kernels for one frame each
+	const GopRoute r = route();
+	const dim3 tiles((l1.width + dev::ITW - 1) / dev::ITW, (l1.height + dev::ITH - 1) / dev::ITH, 2);
+	auto rows = [&](int cols_per_thread, int nrows) { return dim3((l1.width / cols_per_thread + dev::NTHREADS - 1) / dev::NTHREADS, nrows, 2); };
+	switch (r.l1) {
+	case InvL1::Yuv422: dev::k_inv_yuv422<<<tiles, dev::NTHREADS, 0, st>>>(j.iyuv, dither_seed); break;
+	case InvL1::FrameYuv422: dev::k_inv_frame_yuv422<<<rows(2, l1.height), dev::NTHREADS, 0, st>>>(j.iyuv, dither_seed); break;
+	case InvL1::Yuv422Rgb32: dev::k_inv_yuv422_rgb32<<<tiles, dev::NTHREADS, 0, st>>>(j.iyuv); break;
+	case InvL1::Packed16: dev::k_inv_packed16<<<tiles, dev::NTHREADS, 0, st>>>(j.l1, 3, dec_words_per_position(PIX_YU64, 3), dither_seed); break;
+	case InvL1::FrameRows16: dev::k_inv_frame_yuv422_rows16<<<rows(4, l1.height), dev::NTHREADS, 0, st>>>(j.iyuv); break;
+	case InvL1::FrameRows16Col: dev::k_inv_frame_yuv422_rows16_col<<<rows(2, l1.height), dev::NTHREADS, 0, st>>>(j.iyuv); break;
+	// (half resolution: the level-1 lowpass planes of both frames, no last level)
+	case InvL1::HalfYuv422: dev::k_half_yuv422<<<rows(8, rows_), dev::NTHREADS, 0, st>>>(j.half); break;
+	case InvL1::HalfYu64: dev::k_half_yu64<<<rows(2, rows_), dev::NTHREADS, 0, st>>>(j.half); break;
+	case InvL1::HalfRgb24: dev::k_half_rgb24<<<rows(2, rows_), dev::NTHREADS, 0, st>>>(j.half); break;
+	default: g_err = "two-frame groups: output not served"; return -1;
+	}
+	const int pairs = (half_ ? plan_.width / 2 : plan_.width) / 2;
+	// the colour conversions run over both frames in one launch -- two when frame 0 takes another matrix than frame 1 (fill_jobs); frame 1 alone then runs as z = 0
+	// with the seed that gives it the dither of z = 1
+	auto by_matrix = [&](auto launch) { if (matrix_ == 0) launch(0, 2, 0); else { launch(0, 1, matrix_); launch(1, 1, 0); } };
+	switch (r.convert) {
+	case GopConvert::None: break;
+	case GopConvert::Rgb24:
+		by_matrix([&](int f, int nf, int m) {
+			dev::k_yu64_to_rgb24<<<dim3((unsigned)((pairs + dev::NTHREADS - 1) / dev::NTHREADS), (unsigned)rows_, (unsigned)nf), dev::NTHREADS, 0, st>>>(
+				(const uint16_t *)(d_tmp_ + tmp_frame_bytes_ * f), tmp_pitch_ / 2, tmp_frame_bytes_ / 2, d_frames_ + frame_bytes_ * f, pitch_, frame_bytes_, pairs, rows_, m,
+				dither_seed + 0x9E3779B9u * (uint32_t)f);
+		});
+		break;
+	case GopConvert::Rgb16: {
+		const int mode = out_kind_ == PIX_BGRA ? 3 : (out_kind_ == PIX_BGRa ? 2 : (out_kind_ == PIX_B64A ? 1 : 0));
+		by_matrix([&](int f, int nf, int m) {
+			dev::k_yu64_to_rgb16<<<dim3((unsigned)((pairs + dev::NTHREADS - 1) / dev::NTHREADS), (unsigned)rows_, (unsigned)nf), dev::NTHREADS, 0, st>>>(
+				(const uint16_t *)(d_tmp_ + tmp_frame_bytes_ * f), tmp_pitch_ / 2, tmp_frame_bytes_ / 2, (uint16_t *)(d_frames_ + frame_bytes_ * f), pitch_ / 2, frame_bytes_ / 2,
+				pairs, m >= 2, mode);
+		});
+		break;
+	}
+	case GopConvert::V210: {
+		const int groups = (half_ ? plan_.width / 2 : plan_.width) / 6;
+		dev::k_yu64_to_v210<<<dim3((unsigned)((groups + dev::NTHREADS - 1) / dev::NTHREADS), (unsigned)rows_, 2u), dev::NTHREADS, 0, st>>>(
+			(const uint16_t *)d_tmp_, tmp_pitch_ / 2, tmp_frame_bytes_ / 2, (uint32_t *)d_frames_, pitch_ / 4, frame_bytes_ / 4, groups);
+		break;
+	}
+	}
 	HIPCHK(hipGetLastError());
 	return 0;
 }

@@ -709,8 +709,8 @@ int GpuGroupEntropyDecoder::launch(const uint8_t *sample, size_t size, const Par
 		const ParsedBand &lp = pg.lowpass[c];
 		const GopWavelet &top = ch.w[5];
 		if (!lp.present || lp.width != top.width || lp.height != top.height || (size_t)lp.offset + (size_t)top.width * top.height * 2 > size) return -2;
-		// the bias the reference adds to the lowpass band while unpacking it: twice the intra frame's for a group (decoder.c:12265 `num_frames == 2 ? 48 : 24`)
-		lj[nl++] = dev::DecLowpassJob{ d_sample_ + lp.offset, d_coeffs_ + top.offset[0], top.width, top.height, top.pitch, 2 * lowpass_bias(10, top.width, out_kind_) };
+		// the bias the reference adds to the lowpass band while unpacking it: the group's of the requested output (group_lowpass_bias; decoder.c:12265 `num_frames == 2 ? 48 : 24`)
+		lj[nl++] = dev::DecLowpassJob{ d_sample_ + lp.offset, d_coeffs_ + top.offset[0], top.width, top.height, top.pitch, group_lowpass_bias(top.width, out_kind_, c) };
 		static const int coded[5] = { 5, 4, 3, 1, 0 };
 		for (int k : coded) {
 			const GopWavelet &wv = ch.w[k];

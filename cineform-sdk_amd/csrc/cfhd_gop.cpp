@@ -406,6 +406,7 @@ int parse_group_sample(const uint8_t *d, size_t size, ParsedGroup *pg)
 		case TAG_CHANNEL: channel = value; if (channel < 0 || channel >= 3) return -3; break;
 		case TAG_NUM_CHANNELS: pg->num_channels = value; break;
 		case TAG_INPUT_FORMAT: pg->input_format = value; break;
+		case TAG_ENCODED_COLORSPACE: pg->color_space = value; break;
 		case TAG_FRAME_WIDTH: pg->width = value; break;
 		case TAG_FRAME_HEIGHT: pg->height = value; break;
 		case TAG_FRAME_DISPLAY_HEIGHT: pg->display_height = value; break;
