@@ -282,7 +282,9 @@ static CFHD_Error decode_group_sample(Decoder *d, const uint8_t *s, size_t size,
 				const ParsedBand &pb = pg.band[c][k][b];
 				if (!pb.present || pb.width != wv.width || pb.height != wv.height) return fail_zero(ERR_BADSAMPLE);
 				int16_t *dst = coeffs + wv.offset[b];
-				if (pb.codebook < 0) {                                       // raw 16-bit words (the lowpass band of the temporal highpass wavelet)
+				if (pb.codebook == -2) {                                     // the same band divided and coded in two passes (groups from 8-bit RGB sources: cfhd_gop.h)
+					if (k != 3 || b != 0 || vlc_decode_band_two_pass(s + pb.offset, pb.bytes, wv.width, wv.height, wv.pitch, pb.quant, dst)) return fail_zero(ERR_BADSAMPLE);
+				} else if (pb.codebook < 0) {                                // raw 16-bit words (the lowpass band of the temporal highpass wavelet)
 					if ((size_t)pb.bytes < (size_t)wv.width * wv.height * 2) return fail_zero(ERR_BADSAMPLE);
 					for (int r = 0; r < wv.height; r++) {
 						const uint8_t *p = s + pb.offset + (size_t)r * wv.width * 2;

@@ -49,6 +49,19 @@ CFHD_Error CFHD_PrepareToEncode(CFHD_EncoderRef ref, int w, int h, CFHD_PixelFor
 	return ERR_OKAY;
 }
 
+// The group encoder's device side, on the first call that needs it: the group batch, a sample buffer for two frames, the GPU entropy stage.
+static int prepare_group_encoder(Encoder *e)
+{
+	if (e->gop_ready) return 0;
+	if (e->gop_batch.prepare(e->params.gplan, false, e->params.pixel_kind)) return -1;
+	e->gop_ready = true;
+	e->sample.assign(2 * sample_capacity(e->params), 0);
+	// (a group whose w[3] lowpass band is divided and coded in two passes -- the 8-bit RGB inputs, cfhd_gop.h gop_temporal_lowpass_is_coded -- is written by the host
+	// writer from the GPU's coefficients: the device entropy stage codes that band as raw words only)
+	if (gpu_entropy_enabled() && !gop_temporal_lowpass_is_coded(e->params.gplan) && e->gop_batch.prepare_entropy(e->sample.size())) return -1;
+	return 0;
+}
+
 CFHD_Error CFHD_SetEncodeLicense(CFHD_EncoderRef ref, unsigned char *) { return ref ? ERR_OKAY : ERR_INVALID_ARGUMENT; }
 CFHD_Error CFHD_SetEncodeLicense2(CFHD_EncoderRef ref, unsigned char *, uint32_t *level) { if (level) *level = 31; return ref ? ERR_OKAY : ERR_INVALID_ARGUMENT; }
 
@@ -63,12 +76,7 @@ CFHD_Error CFHD_EncodeSample(CFHD_EncoderRef ref, void *frame, int pitch)
 		// Two frames per sample (encoder.c:3282-3380): the first call of a sequence answers with the sequence header, the call that completes a
 		// pair with the group, the calls in between with the header of the group's second frame.  Frame numbers: group g carries 2 g + 1,
 		// and so does the P-frame header behind it (pinned on the reference's samples).
-		if (!e->gop_ready) {
-			if (e->gop_batch.prepare(e->params.gplan, false, e->params.pixel_kind)) return ERR_INTERNAL;
-			e->gop_ready = true;
-			e->sample.assign(2 * sample_capacity(e->params), 0);
-			if (gpu_entropy_enabled() && e->gop_batch.prepare_entropy(e->sample.size())) return ERR_INTERNAL;
-		}
+		if (prepare_group_encoder(e)) return ERR_INTERNAL;
 		const uint32_t n = e->gop_calls++;
 		// Rate feedback (encoder.c:2880-2905): every call re-derives the subband tables from the size of the last key sample (the FILMSCAN2/3 limiter moves), the
 		// call that opens a group also runs the bit-rate limiter and deals the divisors to the group's wavelets -- both frames of the group are quantized with them
@@ -84,7 +92,7 @@ CFHD_Error CFHD_EncodeSample(CFHD_EncoderRef ref, void *frame, int pitch)
 		size_t bytes;
 		if (!(n & 1u)) {
 			if (e->gop_batch.wait()) return ERR_INTERNAL;              // the caller's frame is borrowed for the call only: it is in pinned memory now
-			bytes = n == 0 ? write_sequence_header(e->params.gplan, color_format_of(e->params.pixel_kind), e->sample.data(), e->sample.size())
+			bytes = n == 0 ? write_sequence_header(e->params.gplan, gop_sequence_input_format(e->params.pixel_kind, color_format_of(e->params.pixel_kind)), e->sample.data(), e->sample.size())
 			               : write_pframe_sample(e->params.gplan, n - 1, e->sample.data(), e->sample.size());
 		} else {
 			MetaBlock global = e->meta.global, local = e->meta.local;
@@ -124,6 +132,26 @@ CFHD_Error CFHD_EncodeSample(CFHD_EncoderRef ref, void *frame, int pitch)
 	e->prof.mark(0); e->prof.calls++;
 	e->meta.local.clear();                                                // FreeLocalMetadata (CFHDEncoder.cpp:351)
 	return rc;
+}
+
+// Extension: the level-1 transform kernel behind the handle's next CFHD_EncodeSample (as a profiler shows it), "" before CFHD_PrepareToEncode.  A group encoder answers
+// from GopBatch::forward_route(), an intra encoder from EncodeBatch::forward_route(): the routes the launches themselves read.
+const char *cfhd_amd_encoder_kernel_name(CFHD_EncoderRef ref)
+{
+	CallerDevice caller_device;
+	if (!ref || *(const uint32_t *)ref != kEncoderMagic) return "";
+	Encoder *e = (Encoder *)ref;
+	if (!e->params.valid) return "";
+	if (e->params.gop) {
+		if (prepare_group_encoder(e)) return "";
+		return e->gop_batch.level1_kernel();
+	}
+	if (!e->batch_ready) {
+		e->batch.set_stage_pieces(sync_stage_pieces());
+		if (prepare_batch(e->batch, e->params)) return "";
+		e->batch_ready = true;
+	}
+	return e->batch.level_kernel(0, true);      // (encode_one launches with the coefficients kept)
 }
 
 CFHD_Error CFHD_GetSampleData(CFHD_EncoderRef ref, void **data, size_t *size)

@@ -106,14 +106,18 @@ int make_params(EncodeParams &p, int w, int h, uint32_t fmt, int encoded, uint32
 	const bool deep_rgb_as_422 = ((kind == PIX_RG48 || kind == PIX_B64A || rg64) && encoded == 0) || rgb8_as_422;
 	// BGRA / BGRa encoded as RGBA 4:4:4:4 (frame.c:6415 ConvertRGBAtoRGBA64): the alpha byte joins as the fourth plane, curved as b64a's
 	const bool rgba8_as_4444 = (kind == PIX_BGRA || kind == PIX_BGRa) && encoded == 2;
-	if (!deep_rgb_as_422 && !rgba8_as_4444 && !((kind == PIX_B64A || rg64) && (encoded == 1 || encoded == 2)) && encoded != (kind == PIX_RG48 || rgb8 || rgb10 ? 1 : (kind == PIX_B64A ? 2 : (kind == PIX_BYR4 || kind == PIX_BYR5 ? 3 : 0)))) return ERR_BADFORMAT;
 	// CFHD_ENCODING_FLAGS_YUV_INTERLACED: field-based level 1 (encoder.c:2093), built for the packed 4:2:2 formats
 	const bool interlaced = (flags & (1u << 0)) != 0;
-	if (interlaced && !(kind == PIX_YUY2 || kind == PIX_2VUY)) return ERR_BADFORMAT;
-	// CFHD_ENCODING_FLAGS_YUV_2FRAME_GOP (CFHDTypes.h:254, "YUV 4:2:2 only"): two frames per sample through the temporal transform (cfhd_gop.h).
-	// With CFHD_ENCODING_FLAGS_YUV_INTERLACED on top, level 1 of both frames is the frame transform (GopPlan::interlaced).
+	// (encoded as 4:2:2: the inputs of yuv422_input_served, the one list the intra frames and the two-frame groups share)
+	if (encoded == 0 ? !yuv422_input_served(kind, false)
+	                 : (!rgba8_as_4444 && !((kind == PIX_B64A || rg64) && (encoded == 1 || encoded == 2)) && encoded != (kind == PIX_RG48 || rgb8 || rgb10 ? 1 : (kind == PIX_B64A ? 2 : (kind == PIX_BYR4 || kind == PIX_BYR5 ? 3 : 0))))) return ERR_BADFORMAT;
+	if (interlaced && !(encoded == 0 && yuv422_input_served(kind, true))) return ERR_BADFORMAT;
+	// CFHD_ENCODING_FLAGS_YUV_2FRAME_GOP (CFHDTypes.h:254, "YUV 4:2:2 only"): two frames per sample through the temporal transform (cfhd_gop.h), from every input that
+	// encodes to 4:2:2 -- the reference converts the frame to planes before it asks whether it is an intra frame or half of a group (encoder.c:2336-2865), so the
+	// conversions, the 601 / 709 choice and the marks in the quality word are those of the intra encoder.  The other encoded formats stay refused.
+	// With CFHD_ENCODING_FLAGS_YUV_INTERLACED on top, level 1 of both frames is the frame transform (GopPlan::interlaced): YUY2 / 2vuy, as for interlaced intra frames.
 	const bool gop = (flags & (1u << 1)) != 0;
-	if (gop && !(kind == PIX_YUY2 || kind == PIX_2VUY)) return ERR_BADFORMAT;
+	if (gop && encoded != 0) return ERR_BADFORMAT;
 	const int enc = kind == PIX_BYR4 || kind == PIX_BYR5 ? ENC_BAYER : (((kind == PIX_B64A || rg64) && encoded == 2) || rgba8_as_4444 ? ENC_RGBA4444 : (rgb && !deep_rgb_as_422 ? ENC_RGB444 : ENC_YUV422));
 	// an encoded format other than the default of the input format marks the quality word (SampleEncoder.cpp:216-219; QUALITY_H 0x0800 in the header)
 	if (deep_rgb_as_422 && !rgb8_as_422) quality |= 0x08000000;
@@ -134,7 +138,11 @@ int make_params(EncodeParams &p, int w, int h, uint32_t fmt, int encoded, uint32
 	derive_quantization(&p.plan, quality, p.progressive, 0.0f, &p.qstate);
 	p.gop = gop;
 	p.gstate = {0, -1, 0};
-	if (gop && (!build_gop_plan(&p.gplan, w, h, kind, interlaced) || !derive_gop_quantization(&p.gplan, quality, &p.gstate))) return ERR_BADFORMAT;
+	if (gop) {
+		if (!build_gop_plan(&p.gplan, w, h, kind, interlaced)) return ERR_BADFORMAT;
+		p.gplan.color_matrix = p.plan.color_matrix;
+		if (!derive_gop_quantization(&p.gplan, quality, &p.gstate)) return ERR_BADFORMAT;
+	}
 	p.valid = true;
 	return ERR_OKAY;
 }

@@ -466,7 +466,7 @@ int group_lowpass_bias(int lowpass_width, int out_pixel_kind, int channel)
 // ------------------------------------------------------------------------------------------
 // Host VLC decode
 // ------------------------------------------------------------------------------------------
-int vlc_decode_band(const uint8_t *data, size_t bytes, int width, int height, int pitch, int quant, int codebook, int16_t *band)
+int vlc_decode_band(const uint8_t *data, size_t bytes, int width, int height, int pitch, int quant, int codebook, int16_t *band, size_t *used)
 {
 	(void)width;
 	const EntropyTables *t = entropy_tables(codebook ? codebook : 1);
@@ -484,7 +484,7 @@ int vlc_decode_band(const uint8_t *data, size_t bytes, int width, int height, in
 		if (size == 0) {
 			bool end;
 			if (slow_decode_symbol(codebook ? codebook : 1, (uint32_t)(acc >> 32), &size, &run, &mag, &end) < 0) return -3;
-			if (end) return 0;
+			if (end) { if (used) *used = (pos * 8 - (size_t)have + (size_t)size + 7) / 8; return 0; }
 		}
 		acc <<= size; have -= size;
 		if (mag) {

@@ -164,7 +164,8 @@ int lowpass_bias(int precision, int lowpass_width, int out_pixel_kind, int chann
 // outputs of even widths (14, not 8) and the bottom-up RGB outputs of odd widths (the correction is not doubled).
 int group_lowpass_bias(int lowpass_width, int out_pixel_kind, int channel);
 // Host VLC decode of one band into a zeroed band. Returns 0 on success.
-int vlc_decode_band(const uint8_t *data, size_t bytes, int width, int height, int pitch, int quant, int codebook, int16_t *band);
+// used (optional): the bytes read up to and including the band end code
+int vlc_decode_band(const uint8_t *data, size_t bytes, int width, int height, int pitch, int quant, int codebook, int16_t *band, size_t *used = nullptr);
 // What the reference does to a decoded difference band (DecodeBandFSM16sNoGapWithPeaks decoder.c:19809 + :20822): coefficients beyond the peak
 // level take their values from the peak table, then every row becomes its running sum.  peaks may be NULL (level 0).
 void finish_difference_band(int16_t *band, int width, int height, int pitch, const uint8_t *peaks, size_t peak_bytes, int peak_level);

@@ -108,6 +108,18 @@ void derive_quantization(FramePlan *plan, int quality, bool progressive, float f
 // Builds the pyramid geometry for the given encoded dimensions.
 bool build_frame_plan(FramePlan *plan, int width, int height, int pixel_kind, int encoded_format);
 
+// The inputs that encode to YUV 4:2:2 (CFHD_ENCODED_FORMAT_YUV_422), as intra frames and as two-frame groups alike: make_params and build_gop_plan both ask here (the
+// encode twin of the decoder's yuv422_output_served).  The packed 8-bit formats go through the fused level-1 kernels, the others through the loaders of the packed-16
+// kernel, RGB converted with the reference's integer matrices on the way in.  interlaced (CFHD_ENCODING_FLAGS_YUV_INTERLACED): the frame transform reads YUY2 / 2vuy only.
+static inline bool yuv422_input_served(int pixel_kind, bool interlaced)
+{
+	switch (pixel_kind) {
+	case PIX_YUY2: case PIX_2VUY: return true;
+	case PIX_YU64: case PIX_V210: case PIX_RG24: case PIX_BGRA: case PIX_BGRa: case PIX_RG48: case PIX_B64A: case PIX_RG64: return !interlaced;
+	default: return false;
+	}
+}
+
 // Which GPU serves unit i (worker i of an encoder pool, the i-th decoder handle of the process) on a node with `ndevices` GPUs.
 //   pinned (CFHD_AMD_DEVICE or LOCAL_RANK is set: one process per GPU, the launcher dealt the devices) -> -1 for everybody: the process default
 //   list   (CFHD_AMD_POOL_DEVICES, e.g. "0,1,2,3" or "0,0": devices may repeat)                      -> list[i % length], each taken modulo ndevices

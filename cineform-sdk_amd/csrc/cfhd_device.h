@@ -32,7 +32,7 @@ const char *device_last_error();
 
 // N frames that travel through the forward path together: one launch per wavelet level covers every channel of
 // every frame (blockIdx.z walks the job table).  N = 1 is the synchronous CFHD_EncodeSample path.
-struct ForwardRoute; struct InverseRoute; struct GopRoute;      // (cfhd_device.hip: the kernels a launch picks)
+struct ForwardRoute; struct InverseRoute; struct GopRoute; struct GopForwardRoute;      // (cfhd_device.hip: the kernels a launch picks)
 class EncodeBatch {
 public:
 	EncodeBatch();
@@ -160,8 +160,8 @@ private:
 	GpuEntropyDecoder ent_; bool ent_ready_ = false;
 };
 
-// One two-frame group on the GPU (cfhd_gop.h): the kernels of the intra path (level 1 of both frames, the plane transforms of the three spatial
-// wavelets) around the temporal step, forward for the encoder and inverse for the decoder.  The run-length / VLC stage of a group stays on the
+// One two-frame group on the GPU (cfhd_gop.h): the kernels of the intra path (level 1 of both frames -- from every input that encodes to 4:2:2 --, the plane
+// transforms of the three spatial wavelets) around the temporal step, forward for the encoder and inverse for the decoder.  The run-length / VLC stage of a group stays on the
 // host (write_group_sample / vlc_decode_band): the coefficient pyramid crosses PCIe, as BASELINE.json's north_star arranges the codec.
 class GopBatch {
 public:
@@ -176,6 +176,7 @@ public:
 	// encoder
 	int upload_frame(int f, const void *frame, int pitch_bytes);      // f = 0, 1: stage one frame of the pair and start its H2D copy
 	int launch_forward();                            // async: level 1 of both frames, temporal step, three spatial transforms per channel
+	const char *level1_kernel() const;               // name of the kernel the next launch_forward() runs for level 1 of both frames (as a profiler shows it)
 	int download_coeffs();                           // async: the group pyramid -> pinned host
 	// GPU entropy stage for the group sample (GpuEntropyEncoder::prepare_group): entropy().set_frame_header(0, hdr), launch_forward(), entropy().launch(),
 	// entropy().download(), wait() -> entropy().host_sample(0)
@@ -196,6 +197,7 @@ public:
 private:
 	void fill_jobs();
 	GopRoute route() const;                          // decoder: the last-level kernel and the conversion behind it, from the output kind, half and interlaced alone
+	GopForwardRoute forward_route() const;           // encoder: the level-1 kernel of both frames, from the input kind and interlaced alone
 	GopPlan plan_; bool decode_ = false, half_ = false; int out_kind_ = 0, device_ = 0, matrix_ = 0;
 	void *stream_ = nullptr;
 	uint8_t *d_frames_ = nullptr, *h_frames_ = nullptr; size_t frame_bytes_ = 0; int pitch_ = 0, rows_ = 0;

@@ -119,6 +119,24 @@ static int rgb10_shift(int pixel_kind, int c) { const int r = pixel_kind == PIX_
 static bool enc_rgb_as_422(const FramePlan &plan) { return (is_packed16(plan.pixel_kind) || plan.pixel_kind == PIX_RG64) && plan.encoded_format == ENC_YUV422; }
 static int enc_word_of_channel(int pixel_kind, int c) { return pixel_kind == PIX_V210 || enc_bytes8(pixel_kind) || enc_rgb10(pixel_kind) ? 0 : (pixel_kind == PIX_YU64 ? (c == 0 ? 0 : (c == 1 ? 1 : 3)) : packed_word_of_channel(pixel_kind, c)); }
 static int enc_stride_of_channel(int pixel_kind, int c, int nch) { return pixel_kind == PIX_YU64 ? (c == 0 ? 2 : 4) : (pixel_kind == PIX_B64A || pixel_kind == PIX_RG64 ? 4 : nch); }     // (b64a / RG64 to RGB 4:4:4 have three planes of four-word pixels)
+// The loader of k_fwd_packed16 / k_fwd_gop_packed16 for plane c of one packed frame (FwdPlaneJob: in, in_pitch, xstride, shift, display_height, compand, layout,
+// tail_from), written in one place for the intra batches and the two-frame groups; `frame` may be null (frames supplied later as device pointers).
+static void fill_packed16_loader(dev::FwdPlaneJob &p, const uint8_t *frame8, int in_pitch, int pixel_kind, int encoded_format, int color_matrix, int width, int precision,
+                                 int display_height, int nch, int c)
+{
+	const uint16_t *frame = (const uint16_t *)frame8;
+	p.in = frame ? (const int16_t *)(frame + enc_word_of_channel(pixel_kind, c)) : nullptr; p.in_pitch = in_pitch / 2;
+	p.xstride = enc_stride_of_channel(pixel_kind, c, nch); p.shift = 16 - precision; p.display_height = display_height;
+	p.compand = (pixel_kind == PIX_B64A || pixel_kind == PIX_RG64) && c == 3;
+	p.layout = pixel_kind == PIX_V210 ? c + 1 : 0; p.tail_from = (width - width % 48) / 2;
+	if (enc_bytes8(pixel_kind)) { p.layout = pixel_kind == PIX_BGRa ? 5 : 4; p.in_pitch = in_pitch; p.xstride = pixel_kind == PIX_RG24 ? 3 : 4; p.tail_from = c == 0 ? 1 : (c == 1 ? 2 : (c == 2 ? 0 : 3)); p.compand = c == 3; }     // planes G, R, B(, A) of bytes B, G, R(, A)
+	if (enc_rgb10(pixel_kind)) { p.layout = 6; p.in_pitch = in_pitch / 4; p.xstride = pixel_kind == PIX_R210 || pixel_kind == PIX_DPX0; p.tail_from = rgb10_shift(pixel_kind, c); }
+	if ((is_packed16(pixel_kind) || pixel_kind == PIX_RG64) && encoded_format == ENC_YUV422) {      // (enc_rgb_as_422)
+		p.in = frame ? (const int16_t *)(frame + (pixel_kind == PIX_B64A ? 1 : 0)) : nullptr;
+		p.layout = 7; p.xstride = pixel_kind == PIX_RG48 ? 3 : 4; p.tail_from = c; p.shift = color_matrix; p.compand = 0;
+	}
+	if (enc_bytes8(pixel_kind) && encoded_format == ENC_YUV422) { p.layout = pixel_kind == PIX_BGRa ? 9 : 8; p.tail_from = c; p.shift = color_matrix; }
+}
 } // namespace
 
 const char *device_last_error() { std::lock_guard<std::mutex> l(g_err_mutex); t_err_copy = g_err_text; return t_err_copy.c_str(); }
@@ -392,19 +410,9 @@ void EncodeBatch::fill_jobs()
 		if (enc_packed16(plan.pixel_kind))
 			for (int c = 0; c < nch; c++) {
 				dev::FwdPlaneJob &p = j.l1[(size_t)i * nch + c];
-				const uint16_t *frame = own_input ? (const uint16_t *)(d_in_ + frame_bytes_ * i) : nullptr;
-				p.in = frame ? (const int16_t *)(frame + enc_word_of_channel(plan.pixel_kind, c)) : nullptr; p.in_pitch = in_pitch_ / 2;
+				fill_packed16_loader(p, own_input ? d_in_ + frame_bytes_ * i : nullptr, in_pitch_, plan.pixel_kind, plan.encoded_format, plan.color_matrix, plan.width, plan.precision,
+				                     plan.display_height, nch, c);
 				p.width = plan.ch[c].width; p.height = plan.ch[c].height; p.prescale = plan.prescale[0];
-				p.xstride = enc_stride_of_channel(plan.pixel_kind, c, nch); p.shift = 16 - plan.precision; p.display_height = plan.display_height;
-				p.compand = (plan.pixel_kind == PIX_B64A || plan.pixel_kind == PIX_RG64) && c == 3;
-				p.layout = plan.pixel_kind == PIX_V210 ? c + 1 : 0; p.tail_from = (plan.width - plan.width % 48) / 2;
-				if (enc_bytes8(plan.pixel_kind)) { p.layout = plan.pixel_kind == PIX_BGRa ? 5 : 4; p.in_pitch = in_pitch_; p.xstride = plan.pixel_kind == PIX_RG24 ? 3 : 4; p.tail_from = c == 0 ? 1 : (c == 1 ? 2 : (c == 2 ? 0 : 3)); p.compand = c == 3; }     // planes G, R, B(, A) of bytes B, G, R(, A)
-				if (enc_rgb10(plan.pixel_kind)) { p.layout = 6; p.in_pitch = in_pitch_ / 4; p.xstride = plan.pixel_kind == PIX_R210 || plan.pixel_kind == PIX_DPX0; p.tail_from = rgb10_shift(plan.pixel_kind, c); }
-				if (enc_rgb_as_422(plan)) {
-					p.in = frame ? (const int16_t *)(frame + (plan.pixel_kind == PIX_B64A ? 1 : 0)) : nullptr;
-					p.layout = 7; p.xstride = plan.pixel_kind == PIX_RG48 ? 3 : 4; p.tail_from = c; p.shift = plan.color_matrix; p.compand = 0;
-				}
-				if (enc_bytes8(plan.pixel_kind) && plan.encoded_format == ENC_YUV422) { p.layout = plan.pixel_kind == PIX_BGRa ? 9 : 8; p.tail_from = c; p.shift = plan.color_matrix; }
 				p.out_pitch = plan.ch[c].band[0][0].pitch;
 				for (int b = 0; b < 4; b++) { p.out[b] = base + plan.ch[c].band[0][b].offset; p.q[b] = make_q(plan.ch[c].band[0][b].quant, mpq); }
 			}
@@ -1331,17 +1339,35 @@ struct GopJobs {            // layout of a GopBatch's job table
 	dev::InvYuvJob *iyuv;       // [2]      last level of the two frames: k_inv_yuv422 / k_inv_frame_yuv422 / k_inv_yuv422_rgb32 / k_inv_frame_yuv422_rows16(_col)
 	dev::InvPlaneJob *l1;       // [2 * 3]  the same as YU64 rows (k_inv_packed16), frame f channel c at 3 f + c
 	dev::HalfYuvJob *half;      // [2]      half resolution: the level-1 lowpass plane of each frame (k_half_yuv422 / k_half_yu64 / k_half_rgb24)
+	dev::FwdPlaneJob *fl1;      // [2 * 3]  level 1 of the two frames from the inputs of the packed-16 loaders (k_fwd_gop_packed16), frame f plane c at 3 f + c
+	dev::GopQuantJob *tq;       // [3]      the lowpass band of w[3] where it is divided and coded (k_gop_quant_lowpass)
 };
 GopJobs gop_jobs_at(void *base)
 {
 	GopJobs j;
 	j.yuv = (dev::FwdYuvJob *)base; j.temp = (dev::GopTemporalJob *)(j.yuv + 2); j.mid = (dev::FwdPlaneJob *)(j.temp + 3); j.top = j.mid + 6;
 	j.itop = (dev::InvPlaneJob *)(j.top + 3); j.imid = j.itop + 3; j.iyuv = (dev::InvYuvJob *)(j.imid + 6);
-	j.l1 = (dev::InvPlaneJob *)(j.iyuv + 2); j.half = (dev::HalfYuvJob *)(j.l1 + 6);
+	j.l1 = (dev::InvPlaneJob *)(j.iyuv + 2); j.half = (dev::HalfYuvJob *)(j.l1 + 6); j.fl1 = (dev::FwdPlaneJob *)(j.half + 2); j.tq = (dev::GopQuantJob *)(j.fl1 + 6);
 	return j;
 }
-size_t gop_jobs_bytes() { return 2 * sizeof(dev::FwdYuvJob) + 3 * sizeof(dev::GopTemporalJob) + 9 * sizeof(dev::FwdPlaneJob) + 15 * sizeof(dev::InvPlaneJob) + 2 * sizeof(dev::InvYuvJob) + 2 * sizeof(dev::HalfYuvJob); }
+size_t gop_jobs_bytes() { return 2 * sizeof(dev::FwdYuvJob) + 3 * sizeof(dev::GopTemporalJob) + 15 * sizeof(dev::FwdPlaneJob) + 15 * sizeof(dev::InvPlaneJob) + 2 * sizeof(dev::InvYuvJob) + 2 * sizeof(dev::HalfYuvJob) + 3 * sizeof(dev::GopQuantJob); }
 }
+
+// Level 1 of a group's two frames on the way in: one launch over both frames (gridDim.z = 2), and the name a profiler shows it under.
+enum class GopFwdL1 { Yuv422, FrameYuv422, Packed16 };
+static const char *const kGopFwdL1Name[] = {"k_fwd_yuv422", "k_fwd_frame_yuv422", "k_fwd_gop_packed16"};
+static_assert(sizeof(kGopFwdL1Name) / sizeof(*kGopFwdL1Name) == (size_t)GopFwdL1::Packed16 + 1, "one name per level-1 kernel of a group");
+struct GopForwardRoute { GopFwdL1 l1; };
+
+// The forward twin of route(): which kernel transforms the two input frames, from the plan's input kind and interlaced alone; launch_forward(), fill_jobs() and
+// level1_kernel() read this and nothing else.  (Interlaced groups exist for YUY2 / 2vuy only: yuv422_input_served.)
+GopForwardRoute GopBatch::forward_route() const
+{
+	if (enc_packed16(plan_.pixel_kind)) return { GopFwdL1::Packed16 };
+	return { plan_.interlaced ? GopFwdL1::FrameYuv422 : GopFwdL1::Yuv422 };
+}
+const char *GopBatch::level1_kernel() const { return decode_ ? "" : kGopFwdL1Name[(int)forward_route().l1]; }
+
 
 // The last level of a group's two frames: the intra path's kernel of the output (InvL1, one launch over both frames), then -- outputs made from 16-bit rows --
 // the conversion of both frames' YU64 rows.
@@ -1514,6 +1540,17 @@ void GopBatch::fill_jobs()
 		hj.mode = out_kind_ == PIX_RG24 ? 0 : (out_kind_ == PIX_RG48 ? 2 : (out_kind_ == PIX_B64A ? 3 : 1)); hj.bottom_up = out_kind_ == PIX_BGRA;
 		hj.out = rows16; hj.out_pitch = rows16_pitch;
 	}
+	if (!decode_ && forward_route().l1 == GopFwdL1::Packed16)
+		for (int f = 0; f < 2; f++)
+			for (int c = 0; c < 3; c++) {                  // the intra path's loader of this input (EncodeBatch::fill_jobs), the bands and quantizers of the group's w[f]
+				const GopWavelet &w = plan.ch[c].w[f];
+				dev::FwdPlaneJob &p = j.fl1[3 * f + c];
+				memset(&p, 0, sizeof(p));
+				fill_packed16_loader(p, d_frames_ + frame_bytes_ * f, pitch_, plan.pixel_kind, ENC_YUV422, plan.color_matrix, plan.width, plan.precision, plan.display_height, 3, c);
+				p.width = plan.ch[c].width; p.height = plan.ch[c].height; p.prescale = w.prescale;
+				p.out_pitch = w.pitch;
+				for (int b = 0; b < 4; b++) { p.out[b] = base + w.offset[b]; p.q[b] = make_q(w.quant[b], mpq); }
+			}
 	auto fwd = [&](dev::FwdPlaneJob &p, const int16_t *in, const GopWavelet &src, const GopWavelet &dst) {
 		p.in = in; p.in_pitch = src.pitch; p.width = src.width; p.height = src.height; p.prescale = dst.prescale;
 		p.xstride = 1; p.shift = 0; p.display_height = src.height; p.compand = 0; p.layout = 0; p.tail_from = 0;
@@ -1537,6 +1574,12 @@ void GopBatch::fill_jobs()
 		if (!decode_) { t.a = base + ch.w[0].offset[0]; t.b = base + ch.w[1].offset[0]; t.x = base + ch.w[2].offset[0]; t.y = base + ch.w[2].offset[1]; }
 		else { t.a = base + ch.w[2].offset[0]; t.b = base + ch.w[2].offset[1]; t.x = base + ch.w[0].offset[0]; t.y = base + ch.w[1].offset[0]; }
 		fwd(j.mid[2 * c], base + ch.w[2].offset[1], ch.w[2], ch.w[3]);      // the temporal highpass band
+		{                                                                    // ... whose lowpass band is divided behind the transform where the source asks for it
+			const GopWavelet &w3 = ch.w[3];
+			j.mid[2 * c].q[0] = make_q(1, mpq);
+			j.tq[c].band = base + w3.offset[0]; j.tq[c].pairs = w3.pitch * w3.height / 2;
+			j.tq[c].q.divisor = w3.quant[0]; j.tq[c].q.mid = 0; j.tq[c].q.mult = w3.quant[0] > 1 ? ((1u << 16) / (unsigned)w3.quant[0]) & 0xffffu : 0;
+		}
 		fwd(j.mid[2 * c + 1], base + ch.w[2].offset[0], ch.w[2], ch.w[4]);  // the temporal lowpass band
 		fwd(j.top[c], base + ch.w[4].offset[0], ch.w[4], ch.w[5]);
 		inv(j.itop[c], ch.w[5], base + ch.w[4].offset[0], ch.w[4].pitch);
@@ -1567,11 +1610,26 @@ int GopBatch::launch_forward()
 	GopJobs j = gop_jobs_at(d_jobs_);
 	(void)hipGetLastError();
 	// level 1 of both frames: the spatial transform, or -- interlaced groups -- the frame transform of interlaced intra frames (the two kernels share the job table)
-	if (plan_.interlaced) dev::k_fwd_frame_yuv422<<<dim3((plan_.width / 2 + dev::FTW - 1) / dev::FTW, (plan_.height / 2 + dev::FRW - 1) / dev::FRW, 2), dev::NTHREADS, 0, st>>>((const dev::FwdFrameJob *)j.yuv);
-	else dev::k_fwd_yuv422<<<dim3((plan_.width / 2 + dev::TW - 1) / dev::TW, (plan_.height / 2 + dev::TH - 1) / dev::TH, 2), dev::NTHREADS, 0, st>>>(j.yuv);
+	// (the 10-bit, 16-bit and RGB inputs: the packed-16 loaders, the planes of a tile row side by side in gridDim.x)
+	const int luma_tiles = (plan_.ch[0].width / 2 + dev::TW - 1) / dev::TW, chroma_tiles = (plan_.ch[1].width / 2 + dev::TW - 1) / dev::TW;
+	switch (forward_route().l1) {
+	case GopFwdL1::FrameYuv422:
+		dev::k_fwd_frame_yuv422<<<dim3((plan_.width / 2 + dev::FTW - 1) / dev::FTW, (plan_.height / 2 + dev::FRW - 1) / dev::FRW, 2), dev::NTHREADS, 0, st>>>((const dev::FwdFrameJob *)j.yuv);
+		break;
+	case GopFwdL1::Yuv422:
+		dev::k_fwd_yuv422<<<dim3((plan_.width / 2 + dev::TW - 1) / dev::TW, (plan_.height / 2 + dev::TH - 1) / dev::TH, 2), dev::NTHREADS, 0, st>>>(j.yuv);
+		break;
+	case GopFwdL1::Packed16:
+		dev::k_fwd_gop_packed16<<<dim3(luma_tiles + 2 * chroma_tiles, (plan_.height / 2 + dev::TH - 1) / dev::TH, 2), dev::NTHREADS, 0, st>>>(j.fl1, luma_tiles);
+		break;
+	}
 	const GopWavelet &t = plan_.ch[0].w[2];
 	dev::k_gop_temporal_fwd<<<dim3((unsigned)((t.pitch * t.height / 2 + dev::NTHREADS - 1) / dev::NTHREADS), 3), dev::NTHREADS, 0, st>>>(j.temp);
 	dev::k_fwd_plane<<<dim3((t.width / 2 + dev::TW - 1) / dev::TW, (t.height / 2 + dev::TH - 1) / dev::TH, 6), dev::NTHREADS, 0, st>>>(j.mid);
+	if (!decode_ && gop_temporal_lowpass_is_coded(plan_)) {
+		const GopWavelet &w3 = plan_.ch[0].w[3];                         // (luma is the largest of the three bands)
+		dev::k_gop_quant_lowpass<<<dim3((unsigned)((w3.pitch * w3.height / 2 + dev::NTHREADS - 1) / dev::NTHREADS), 3), dev::NTHREADS, 0, st>>>(j.tq);
+	}
 	const GopWavelet &m = plan_.ch[0].w[4];
 	dev::k_fwd_plane<<<dim3((m.width / 2 + dev::TW - 1) / dev::TW, (m.height / 2 + dev::TH - 1) / dev::TH, 3), dev::NTHREADS, 0, st>>>(j.top);
 	HIPCHK(hipGetLastError());

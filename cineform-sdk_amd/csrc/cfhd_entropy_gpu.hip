@@ -717,6 +717,7 @@ int GpuGroupEntropyDecoder::launch(const uint8_t *sample, size_t size, const Par
 			for (int b = (k == 3 ? 0 : 1); b < 4; b++) {
 				const ParsedBand &pb = pg.band[c][k][b];
 				if (!pb.present || pb.width != wv.width || pb.height != wv.height || (pb.offset & 3) || (size_t)pb.offset + pb.bytes > size) return -2;
+				if (pb.codebook == -2) return -3;                            // (coded in two passes, cfhd_gop.h: the host coder's)
 				if (pb.codebook < 0) {                                       // raw 16-bit words (the lowpass band of the temporal highpass wavelet): signed, no bias
 					if ((size_t)pb.bytes < (size_t)wv.width * wv.height * 2 || pb.quant != 1 || (wv.width & 1)) return -3;
 					lj[nl++] = dev::DecLowpassJob{ d_sample_ + pb.offset, d_coeffs_ + wv.offset[0], wv.width, wv.height, wv.pitch, 0 };

@@ -10,7 +10,7 @@ bool build_gop_plan(GopPlan *plan, int width, int height, int pixel_kind, bool i
 {
 	plan->interlaced = interlaced;
 	if (width <= 0 || height <= 0 || width > kMaxFrameDim || height > kMaxFrameDim) return false;
-	if (pixel_kind != PIX_YUY2 && pixel_kind != PIX_2VUY) return false;              // CFHD_ENCODING_FLAGS_YUV_2FRAME_GOP: "YUV 4:2:2 only" (CFHDTypes.h:254)
+	if (!yuv422_input_served(pixel_kind, interlaced)) return false;                  // CFHD_ENCODING_FLAGS_YUV_2FRAME_GOP: "YUV 4:2:2 only" (CFHDTypes.h:254) -- the inputs of the intra 4:2:2 encoder
 	const int enc_height = (height + 7) & ~7;                                        // encoder.c:1569-1571
 	// the chroma planes halve once per level on whole pairs: level 1, the two levels on the temporal lowpass band
 	if ((width / 2) % 8 || width % 16) return false;
@@ -45,7 +45,15 @@ bool build_gop_plan(GopPlan *plan, int width, int height, int pixel_kind, bool i
 		spatial(ch.w[5], ch.w[4].scale[0]);
 	}
 	plan->coeff_elems = at;
-	plan->sample_buffer_bytes = (size_t)width * height * 4 + 65536;      // SampleEncoder.cpp:387 (PixelSize of YUY2 / 2vuy: 4, :1232)
+	// SampleEncoder.cpp:387 with the reference's own PixelSize (:1221-1267: YUY2 / 2vuy and BGRA / BGRa 4, RG24 and v210 3, RG48 6, everything else -- YU64, b64a, RG64 -- 8)
+	int pixel_size = 8;
+	switch (pixel_kind) {
+	case PIX_YUY2: case PIX_2VUY: case PIX_BGRA: case PIX_BGRa: pixel_size = 4; break;
+	case PIX_RG24: case PIX_V210: pixel_size = 3; break;
+	case PIX_RG48: pixel_size = 6; break;
+	default: break;
+	}
+	plan->sample_buffer_bytes = (size_t)width * height * pixel_size + 65536;
 	return true;
 }
 
@@ -73,7 +81,7 @@ bool derive_gop_quantization(GopPlan *plan, int quality, QuantState *st, float f
 			}
 		}
 		subband++;                                                                    // subband 7: the lowpass band of w[3], kept at 1 for 10-bit sources (encoder.c:8538)
-		ch.w[3].quant[0] = 1;
+		ch.w[3].quant[0] = (quality & 0x1000000) ? 1 << ((quality & 0x0e00000) >> 21) : 1;      // CFEncode_Temporal_Quality_On / _Mask (encoder.c:8203): gop_temporal_lowpass_is_coded()
 		for (int b = 1; b < 4; b++, subband++) {
 			int q = ((quant[subband] * 256 * ch.w[3].scale[b]) >> 8) >> 2;
 			if (!(quality & 0x10000000)) q = midpoint(q);
@@ -86,6 +94,42 @@ bool derive_gop_quantization(GopPlan *plan, int quality, QuantState *st, float f
 		}
 	}
 	return true;
+}
+
+// ------------------------------------------------------------------------------------------
+// The two-pass coding of a divided w[3] lowpass band (cfhd_gop.h)
+// ------------------------------------------------------------------------------------------
+void vlc_encode_band_two_pass(BitWriter &w, const int16_t *band, int width, int height, int pitch)
+{
+	// pass 1 leaves behind what pass 2 codes (encoder.c:5185-5238): the high byte as 0 .. 255, nothing for the values that pass 1 coded whole
+	std::vector<int16_t> low((size_t)pitch * height, 0), high((size_t)pitch * height, 0);
+	for (int r = 0; r < height; r++)
+		for (int x = 0; x < width; x++) {
+			const size_t i = (size_t)r * pitch + x;
+			const int v = band[i];
+			if ((v & 0xff) != 0 && v < 0 && v >= -255) low[i] = (int16_t)v;
+			else { low[i] = (int16_t)(v & 0xff); high[i] = (int16_t)((v >> 8) & 0xff); }
+		}
+	vlc_encode_band(w, low.data(), width, height, pitch, 2, 1);          // (code set 18; ends with its band end code, padded to a whole word)
+	w.put_tag(82, 0);                                                    // CODEC_TAG_BAND_SECONDPASS (codec.c:1909)
+	vlc_encode_band(w, high.data(), width, height, pitch, 2, 1);
+}
+
+int vlc_decode_band_two_pass(const uint8_t *data, size_t bytes, int width, int height, int pitch, int quant, int16_t *band)
+{
+	std::vector<int16_t> high((size_t)pitch * height, 0);
+	size_t used = 0;
+	for (size_t i = 0; i < (size_t)pitch * height; i++) band[i] = 0;
+	if (vlc_decode_band(data, bytes, width, height, pitch, 1, 2, band, &used)) return -1;
+	used = (used + 3) & ~(size_t)3;
+	if (used + 4 > bytes || data[used] != 0 || data[used + 1] != 82) return -2;      // the BAND_SECONDPASS tag behind the padded first pass
+	if (vlc_decode_band(data + used + 4, bytes - used - 4, width, height, pitch, 1, 2, high.data())) return -3;
+	for (int r = 0; r < height; r++)
+		for (int x = 0; x < width; x++) {
+			const size_t i = (size_t)r * pitch + x;
+			band[i] = (int16_t)((int16_t)(band[i] + (high[i] << 8)) * quant);
+		}
+	return 0;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -120,6 +164,7 @@ struct GroupHostSink {
 	void band(int c, int k, int b)
 	{
 		const GopWavelet &wv = plan.ch[c].w[k];
+		if (k == 3 && b == 0) { vlc_encode_band_two_pass(w, coeffs + wv.offset[0], wv.width, wv.height, wv.pitch); return; }      // (arrives here only where it is coded)
 		const int codebook = gop_band_is_difference_coded(plan, k, b) ? 2 : 1;
 		// "only compress up to 80% of the frame size" (encoder.c:8332): once the sample fills more than that of the caller's sample buffer, the remaining
 		// bands of the frame wavelets are coded as zeros (EncodeZeroBand encoder.c:6220: the same header, one run over the whole band)
@@ -162,7 +207,7 @@ template <typename Sink> void put_band_header(Sink &w, int band, const GopWavele
 {
 	w.tag(TAG_MARKER, MARK_BAND_START);
 	w.tag(TAG_BAND_NUMBER, band);
-	w.tag(TAG_BAND_CODING_FLAGS, difference ? 2 + 16 : 1);      // code set 17, no difference coding (encoder.c:6120 SetCodingFlags for a progressive group); interlaced: subbands 12 / 15 in code set 18, difference coded
+	w.tag(TAG_BAND_CODING_FLAGS, difference ? 2 + 16 : (encoding == 5 ? 2 : 1));      // code set 17, no difference coding (encoder.c:6120 SetCodingFlags for a progressive group); interlaced: subbands 12 / 15 in code set 18, difference coded; BAND_ENCODING_LOSSLESS (5): code set 18 (encoder.c:6856)
 	w.tag(TAG_BAND_WIDTH, wv.width);
 	w.tag(TAG_BAND_HEIGHT, wv.height);
 	w.tag(TAG_BAND_SUBBAND, subband);
@@ -199,7 +244,8 @@ template <typename Sink> void walk_group_sample(Sink &w, const GopPlan &plan, co
 	w.tag(TAG_TRANSFORM_TYPE, 2);                        // TRANSFORM_TYPE_FIELDPLUS
 	w.tag(TAG_NUM_FRAMES, 2);
 	w.tag(TAG_NUM_CHANNELS, nch);
-	w.tag_opt(TAG_INPUT_FORMAT, hdr.input_format);
+	if (hdr.input_format >= 100) w.tag(TAG_INPUT_FORMAT, hdr.input_format);      // COLOR_FORMAT_INPUT_FORMAT_TAG_REQUIRED (codec.c:895): RG48, RG64
+	else w.tag_opt(TAG_INPUT_FORMAT, hdr.input_format);
 	{ const int cs = hdr.color_space & ~4; if (cs) w.tag_opt(TAG_ENCODED_COLORSPACE, cs); }
 	w.tag(TAG_NUM_WAVELETS, kGopWavelets);
 	w.tag(TAG_NUM_SUBBANDS, kGopSubbands);
@@ -282,8 +328,9 @@ template <typename Sink> void walk_group_sample(Sink &w, const GopPlan &plan, co
 			const GopWavelet &wv = ch.w[3];
 			put_wavelet_header(w, wv, 4);
 			for (int b = 0; b < 4; b++, subband++) {
-				put_band_header(w, b, wv, subband, b == 0 ? 4 : 3);      // BAND_ENCODING_16BIT for the lowpass band (encoder.c:8219, precision >= 10)
-				if (b == 0) { w.raw16(c, 3); w.bytes(band_end, band_end_bytes); }
+				const bool coded = gop_temporal_lowpass_is_coded(plan);
+				put_band_header(w, b, wv, subband, b == 0 ? (coded ? 5 : 4) : 3);      // BAND_ENCODING_16BIT for the lowpass band (encoder.c:8219, precision >= 10), _LOSSLESS where it is divided and coded
+				if (b == 0 && !coded) { w.raw16(c, 3); w.bytes(band_end, band_end_bytes); }
 				else w.band(c, 3, b);
 				w.tag(TAG_BAND_TRAILER, 0);
 				w.pop();
@@ -444,7 +491,7 @@ int parse_group_sample(const uint8_t *d, size_t size, ParsedGroup *pg)
 			if (end < pos + 4 || end > size) return -7;
 			pb.offset = (uint32_t)pos; pb.bytes = (uint32_t)(end - 4 - pos);
 			pb.width = bw; pb.height = bh; pb.quant = bq; pb.subband = bsub; pb.present = true;
-			pb.codebook = benc == 4 ? -1 : (bflags & 0xf);      // -1: raw 16-bit words (BAND_ENCODING_16BIT)
+			pb.codebook = benc == 4 ? -1 : (benc == 5 ? -2 : (bflags & 0xf));      // -1: raw 16-bit words (BAND_ENCODING_16BIT); -2: two passes of code set 18 (BAND_ENCODING_LOSSLESS)
 			pb.difference = (bflags & 0x10) != 0; pb.peak_level = peak_level; pb.peak_offset = peak_level ? (uint32_t)(peak_base + peak_offset) : 0u;      // (difference-coded bands: interlaced groups)
 			if (pb.peak_level && (size_t)pb.peak_offset + 2 > size) return -8;
 			peak_level = 0;

@@ -29,7 +29,8 @@ struct GopChannel { int width, height; GopWavelet w[kGopWavelets]; };
 struct GopPlan {
 	int width = 0, height = 0, display_height = 0;      // height rounded up to a multiple of 8 (encoder.c:1569)
 	int num_channels = 3, precision = 10, midpoint_prequant = 2;
-	int pixel_kind = PIX_YUY2;
+	int pixel_kind = PIX_YUY2;                  // the encoder's input: any of yuv422_input_served (cfhd_core.h); the decoder's plans say YUY2 / 2vuy
+	int color_matrix = 0;                       // RGB inputs: the matrix of the conversion in the level-1 loader (FramePlan::color_matrix)
 	// CFHD_ENCODING_FLAGS_YUV_INTERLACED on top of the group flag: level 1 of both frames is the frame transform of interlaced intra frames (Codec/encoder.c:2950-2979
 	// TransformForwardFrameYUV into w[0] / w[1]); everything above it is the same.  The horizontal-lowpass / temporal-highpass band of both frame wavelets (band 2:
 	// subbands 12 and 15) is difference coded in code set 18 with a peak table (encoder.c:6143-6154 SetCodingFlags), as subband 8 of an interlaced intra frame.
@@ -42,6 +43,16 @@ struct GopPlan {
 
 // the band of a frame wavelet that an interlaced group codes as differences along the row, in code set 18, with a peak table (subbands 12 and 15)
 inline bool gop_band_is_difference_coded(const GopPlan &plan, int wavelet, int band) { return plan.interlaced && wavelet < 2 && band == 2; }
+// The lowpass band of w[3] (subband 7) of a source the reference marks CFEncode_Temporal_Quality_On in the quality word -- the 8-bit RGB inputs, 0x01a00000 -- is not
+// stored as raw 16-bit words: it is divided by 1 << factor (32) without a midpoint (quantize.c:928 QuantizeRow16s) and coded in two passes of code set 18, the low
+// bytes and then the high bytes (BAND_ENCODING_LOSSLESS: encoder.c:8203-8209, :6832 EncodeBand16sLossless, :5112 EncodeQuantLongRuns2Pass).  The divisor is the band's
+// quant[0]; 1 means raw words.
+inline bool gop_temporal_lowpass_is_coded(const GopPlan &plan) { return plan.ch[0].w[3].quant[0] > 1; }
+// The two passes of such a band (host code; the band is already divided).  Pass 1 codes, per coefficient, the value itself where it lies in -255 .. -1 and its low
+// byte otherwise (zero low bytes join the runs); pass 2 codes the high bytes of the others as 0 .. 255; a band end code and the BAND_SECONDPASS tag lie between them.
+void vlc_encode_band_two_pass(BitWriter &w, const int16_t *band, int width, int height, int pitch);
+// ... and back: value = pass 1 + (pass 2 << 8) in 16 bits, times quant (decoder.c:12862 DecodeBand16sLossless).  0, or < 0 for a malformed band.
+int vlc_decode_band_two_pass(const uint8_t *data, size_t bytes, int width, int height, int pitch, int quant, int16_t *band);
 // false: geometry the group transform does not serve (the same rule as build_frame_plan: chroma must halve on whole pairs four times here)
 bool build_gop_plan(GopPlan *plan, int width, int height, int pixel_kind, bool interlaced = false);
 // Quantizer tables of the group (QuantizationSetQuality quantize.c:186 + SetTransformQuantization :2865, :3480 + SetTransformScale wavelet.c:7142).
@@ -57,8 +68,16 @@ size_t write_group_sample(const GopPlan &plan, const SampleHeaderInfo &hdr, cons
 void build_group_template(const GopPlan &plan, const SampleHeaderInfo &hdr, SampleTemplate *t);
 bool gop_sample_may_zero_bands(const GopPlan &plan, size_t bytes);
 // The 40-byte sequence header a sequence starts with (codec.c:736) and the 24-byte sample of a group's second frame (codec.c:1258).
+// input_format: the COLOR_FORMAT_* code of the frame as the transform sees it, i.e. behind the conversion -- gop_sequence_input_format().
 size_t write_sequence_header(const GopPlan &plan, int input_format, uint8_t *out, size_t cap);
 size_t write_pframe_sample(const GopPlan &plan, uint32_t frame_number, uint8_t *out, size_t cap);
+
+// The input format of the sequence header: the reference writes it from the frame it has converted (encoder.c:3228 passes `format`, which the RGB conversions
+// of :2339-2785 have set to COLOR_FORMAT_YU64 = 12), the group header from the caller's format (encoder.c:7525 encoder->input.format).  Pinned on the reference's samples.
+inline int gop_sequence_input_format(int pixel_kind, int color_format)
+{
+	switch (pixel_kind) { case PIX_RG24: case PIX_BGRA: case PIX_BGRa: case PIX_RG48: case PIX_B64A: case PIX_RG64: return 12; default: return color_format; }
+}
 
 // ---- decoder side ----
 struct ParsedGroup {

@@ -425,12 +425,18 @@ __device__ __forceinline__ uint32_t v210_sample(const uint32_t *row, int layout,
 	return (row[4 * g + word] >> shift) & 0x3ffu;
 }
 
-template <bool PACKED>
+// GROUP422 (k_fwd_gop_packed16): the three planes of a 4:2:2 frame are of two widths, so gridDim.x = luma tiles + 2 x chroma tiles of a tile row -- `nch` carries the
+// luma tile count -- and no workgroup starts on the half of a chroma plane that is not there; frame tile.z reads jobs[3 z + plane].
+template <bool PACKED, bool GROUP422 = false>
 __device__ __forceinline__ void fwd_plane_tile(const FwdPlaneJob *jobs, int nch)
 {
 	TileId tile = xcd_tile();
 	int comp = 0;
-	if (PACKED) { comp = tile.x % nch; tile.x /= nch; }
+	if (GROUP422) {
+		const int luma_tiles = nch, chroma_tiles = ((int)gridDim.x - luma_tiles) >> 1;
+		if (tile.x >= luma_tiles) { tile.x -= luma_tiles; comp = tile.x < chroma_tiles ? 1 : 2; if (comp == 2) tile.x -= chroma_tiles; }
+		nch = 3;
+	} else if (PACKED) { comp = tile.x % nch; tile.x /= nch; }
 	__shared__ FwdPlaneJob s_job;
 	stage_job(&s_job, &jobs[PACKED ? tile.z * nch + comp : tile.z]);
 	const FwdPlaneJob &job = s_job;
@@ -535,6 +541,9 @@ __device__ __forceinline__ void fwd_plane_tile(const FwdPlaneJob *jobs, int nch)
 
 __global__ void __launch_bounds__(NTHREADS) k_fwd_plane(const FwdPlaneJob *jobs) { fwd_plane_tile<false>(jobs, 1); }
 __global__ void __launch_bounds__(NTHREADS) k_fwd_packed16(const FwdPlaneJob *jobs, int nch) { fwd_plane_tile<true>(jobs, nch); }
+// Level 1 of both frames of a two-frame group from the inputs the packed-16 loaders read (YU64, v210, RG24 / BGRA / BGRa / RG48 / b64a converted to 4:2:2 on the way
+// in): one launch, gridDim = (luma_tiles + 2 * chroma tiles, tile rows, 2 frames), jobs[3 f + plane] (GopBatch::fill_jobs).
+__global__ void __launch_bounds__(NTHREADS) k_fwd_gop_packed16(const FwdPlaneJob *jobs, int luma_tiles) { fwd_plane_tile<true, true>(jobs, luma_tiles); }
 
 // =============================================================================================
 // Forward level 1, packed 8-bit 4:2:2 source (all three channels of a tile in one workgroup)
@@ -2905,6 +2914,19 @@ __global__ void __launch_bounds__(NTHREADS) k_gop_temporal_fwd(const GopTemporal
 		hi[i] = pk_subs(vb, va);
 	}
 }
+// The lowpass band of w[3] of a group whose source is marked for it (cfhd_gop.h gop_temporal_lowpass_is_coded): divided in place, |x| * (65536 / divisor) >> 16 with the
+// sign put back and no midpoint (quantize.c:928 QuantizeRow16s), pad columns included (they are zero).  gridDim.y = channel; pairs of coefficients per thread.
+struct GopQuantJob { int16_t *band; int pairs; QuantParam q; };
+__global__ void __launch_bounds__(NTHREADS) k_gop_quant_lowpass(const GopQuantJob *jobs)
+{
+	const GopQuantJob job = jobs[blockIdx.y];
+	const int i = blockIdx.x * NTHREADS + threadIdx.x;
+	if (i >= job.pairs) return;
+	uint32_t *p = (uint32_t *)job.band + i;
+	const uint32_t v = *p;
+	*p = pack16(quantize(lo16(v), job.q), quantize(hi16(v), job.q));
+}
+
 __global__ void __launch_bounds__(NTHREADS) k_gop_temporal_inv(const GopTemporalJob *jobs)
 {
 	const GopTemporalJob job = jobs[blockIdx.y];

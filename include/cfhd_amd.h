@@ -6,7 +6,8 @@
  * cites the reference interface it replaces.  Handles are opaque; every function returns a
  * CFHD error code (0 = CFHD_ERROR_OKAY, Common/CFHDError.h:25-82).
  *
- * Scope: intra-frame encode of YUY2 / 2vuy (progressive and interlaced), YU64 and v210 -> YUV 4:2:2 10-bit, RG48 / RG24 / BGRA / BGRa /
+ * Scope: intra-frame encode of YUY2 / 2vuy (progressive and interlaced), YU64 and v210 -> YUV 4:2:2 10-bit; two-frame groups (CFHD_ENCODING_FLAGS_YUV_2FRAME_GOP)
+ * from YUY2 / 2vuy (progressive and interlaced) and from YU64 / v210 / RG24 / BGRA / BGRa / RG48 / b64a / RG64 encoded as YUV 4:2:2 (progressive); RG48 / RG24 / BGRA / BGRa /
  * r210 / DPX0 / AB10 / AR10 / b64a -> RGB 4:4:4 12-bit, b64a -> RGBA 4:4:4:4 12-bit, BYR4 -> Bayer 12-bit; decode of 4:2:2 samples to
  * YUY2 / 2vuy (full and half resolution, interlaced samples too), RG48 / b64a / BGRA / BGRa (full and half resolution, interlaced samples too)
  * and YU64 (full resolution, progressive samples), RGB 4:4:4 samples to RG48 (and RG24 / BGRA / BGRa
@@ -162,6 +163,8 @@ int  cfhd_amd_batch_download_output(cfhd_amd_batch *batch, int frame, void *out,
 float cfhd_amd_batch_kernel_ms(cfhd_amd_batch *batch, int which);                              /* HIP-event time of the kernels of the last pass */
 const char *cfhd_amd_batch_kernel_name(cfhd_amd_batch *batch, int which);                      /* which 0..5: the transform kernel behind that time */
 double cfhd_amd_batch_stage_seconds(cfhd_amd_batch *batch, int which);
+/* The level-1 transform kernel of a prepared encoder handle's next CFHD_EncodeSample, intra frame or two-frame group ("" when the handle is not prepared). */
+const char *cfhd_amd_encoder_kernel_name(CFHD_EncoderRef encoderRef);
 int  cfhd_amd_batch_dx_stats(cfhd_amd_batch *batch, uint32_t *out16);
 int  cfhd_amd_device_count(void);
 /* Text of the last HIP / device failure behind a CFHD_ERROR_INTERNAL (the library has no CPU fallback: without a gfx950 device every
