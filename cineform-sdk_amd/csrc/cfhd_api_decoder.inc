@@ -140,9 +140,9 @@ CFHD_Error CFHD_PrepareToDecode(CFHD_DecoderRef ref, int, int, CFHD_PixelFormat 
 		if (rgb10 && (encf != ENC_RGB444 || d->header.width < 32)) return ERR_BADFORMAT;
 		// ... and Bayer samples to BYR4: the raw mosaic, no demosaic (the four planes as 16-bit rows, recombined per quad and sent through the reference's linear-restore
 		// table: DecodeBatch / k_bayer_to_byr4; full resolution)
-		const bool byr4_of_bayer = kind == PIX_BYR4 && encf == ENC_BAYER && !half && d->header.width >= 32;
-		if ((encf == ENC_BAYER) != byr4_of_bayer) return ERR_BADFORMAT;
-		if ((kind == PIX_BYR4 && !byr4_of_bayer) || kind == PIX_BYR5 || kind == PIX_RG64 || (kind >= PIX_R210 && kind <= PIX_AR10 && !rgb10)) return ERR_BADFORMAT;     // encoder inputs only
+		const bool bayer_as_byr4 = kind == PIX_BYR4 && encf == ENC_BAYER && !half && d->header.width >= 32;
+		if ((encf == ENC_BAYER) != bayer_as_byr4) return ERR_BADFORMAT;
+		if ((kind == PIX_BYR4 && !bayer_as_byr4) || kind == PIX_BYR5 || kind == PIX_RG64 || (kind >= PIX_R210 && kind <= PIX_AR10 && !rgb10)) return ERR_BADFORMAT;     // encoder inputs only
 		// ... and RGB 4:4:4 samples to b64a (the RG48 words behind a constant alpha word 0xfff0, full resolution: what TestCFHD's b64a -> RGB 4:4:4 row decodes to)
 		const bool b64a_of_444 = kind == PIX_B64A && encf == ENC_RGB444;
 		// ... and RGBA 4:4:4:4 samples to RG48 (the RG48 route on planes G, R, B, the alpha plane left behind; full and half resolution)
@@ -377,7 +377,7 @@ static CFHD_Error decode_on_handle(Decoder *d, const ParsedSample &ps, const uin
 		d->batch.set_interlaced(interlaced);
 		device_select(d->device);                      // the handle's GPU (the batch remembers it: later calls may come from any thread)
 		d->batch.set_stage_pieces(sync_stage_pieces());
-		int prc = d->batch.prepare(d->plan, 1, d->out_kind, true, d->half);
+		int prc = d->batch.prepare(d->plan, 1, d->out_kind, d->half);
 		if (!prc && gpu_entropy_enabled()) prc = d->batch.prepare_entropy((size_t)d->plan.width * d->plan.height * pixel_bytes_of(d->out_kind) + 65536);
 		device_select(-1);
 		if (prc) return ERR_INTERNAL;

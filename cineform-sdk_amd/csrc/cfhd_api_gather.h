@@ -89,7 +89,7 @@ struct EncodeService : Gatherer<EncodeBatch> {
 		slots = nslots;
 		device = key.device;
 		struct OnDevice { OnDevice(int d) { device_select(d); } ~OnDevice() { device_select(-1); } } on(device);      // the shared batches live on the GPU of the workers they serve
-		for (Pass &x : g) if (x.batch.prepare(p.plan, slots, true) || x.batch.prepare_entropy(sample_capacity(p))) { for (Pass &y : g) y.batch.release(); return false; }   // (a service that cannot be set up holds no HBM)
+		for (Pass &x : g) if (x.batch.prepare(p.plan, slots) || x.batch.prepare_entropy(sample_capacity(p))) { for (Pass &y : g) y.batch.release(); return false; }   // (a service that cannot be set up holds no HBM)
 		run_pass = [](Pass &x, int n, uint32_t) {
 			x.batch.set_active(n);
 			int rc = x.batch.launch_forward();

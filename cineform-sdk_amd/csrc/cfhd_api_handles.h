@@ -123,7 +123,7 @@ struct DecodeService : Gatherer<DecodeBatch> {
 		struct OnDevice { OnDevice(int d) { device_select(d); } ~OnDevice() { device_select(-1); } } on(device);      // the batches are prepared on the service's GPU
 		for (Pass &x : g) {
 			x.batch.set_interlaced(interlaced);
-			if (x.batch.prepare(plan, slots, out_kind, true, half) || x.batch.prepare_entropy(cap) || !x.batch.entropy().chunk_indexed()) { for (Pass &y : g) y.batch.release(); return false; }
+			if (x.batch.prepare(plan, slots, out_kind, half) || x.batch.prepare_entropy(cap) || !x.batch.entropy().chunk_indexed()) { for (Pass &y : g) y.batch.release(); return false; }
 		}
 		run_pass = [](Pass &x, int n, uint32_t launch) {
 			x.batch.set_active(n);

@@ -160,7 +160,7 @@ int sync_stage_pieces() { return 4; }      // (measured with 1 / 2 / 4 / 8 piece
 
 int prepare_batch(EncodeBatch &batch, const EncodeParams &p)
 {
-	if (batch.prepare(p.plan, 1, true)) return ERR_INTERNAL;
+	if (batch.prepare(p.plan, 1)) return ERR_INTERNAL;
 	if (gpu_entropy_enabled() && batch.prepare_entropy(sample_capacity(p))) return ERR_INTERNAL;
 	return ERR_OKAY;
 }

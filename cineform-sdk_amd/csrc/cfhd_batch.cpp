@@ -180,8 +180,8 @@ cfhd_amd_batch *cfhd_amd_batch_create_ex(int width, int height, uint32_t pixel_f
 		std::unique_ptr<cfhd_amd_chunk> c(new cfhd_amd_chunk);
 		c->first = first; c->n = nframes - first < chunk ? nframes - first : chunk;
 		bool ok = true;
-		auto encoder = [&] { return !c->enc.prepare(b->plan, c->n, true) && !(b->gpu_entropy && c->enc.prepare_entropy(cap)); };
-		auto decoder = [&] { if (!b->decode) return true; c->dec.set_interlaced(!b->progressive); return !c->dec.prepare(b->plan, c->n, kind, true) && !(b->gpu_entropy && c->dec.prepare_entropy(cap)); };
+		auto encoder = [&] { return !c->enc.prepare(b->plan, c->n) && !(b->gpu_entropy && c->enc.prepare_entropy(cap)); };
+		auto decoder = [&] { if (!b->decode) return true; c->dec.set_interlaced(!b->progressive); return !c->dec.prepare(b->plan, c->n, kind) && !(b->gpu_entropy && c->dec.prepare_entropy(cap)); };
 		if (streams == 1) { StreamScope scope; ok = encoder() && decoder(); if (scope.stream()) b->shared_streams.push_back(scope.stream()); }
 		else if (streams == 2) {
 			// (CFHD_AMD_STREAM_ORDER=alt, A/B: every second batch of the process creates its decoder's stream first -- with four queues dealt in creation order the encoder of

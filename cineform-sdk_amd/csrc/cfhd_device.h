@@ -37,15 +37,12 @@ class EncodeBatch {
 public:
 	EncodeBatch();
 	~EncodeBatch();
-	// own_input: allocate HBM (and pinned host staging) for the packed frames; otherwise frames are supplied as device pointers.
-	int prepare(const FramePlan &plan, int nframes, bool own_input);
+	int prepare(const FramePlan &plan, int nframes);      // allocates HBM and pinned host staging for the packed frames, the pyramids and the job tables
 	int nframes() const { return n_; }
 	const FramePlan &plan() const { return plan_; }
 	// Stage one host frame (any pitch, negative allowed as in Codec/encoder.c:1957) and start its H2D copy.
 	int upload_frame(int i, const void *frame, int pitch_bytes);
 	int upload_frames(const void *frames, size_t frame_stride, int pitch_bytes);      // all n frames, asynchronous on the batch's stream; ONE copy when the frames lie back to back in a registered buffer
-	// Use frames that already live in HBM (bench / device-resident callers).
-	int set_device_frame(int i, const void *d_frame, int pitch_bytes);
 	// the next launches (forward transform, entropy coder, sample download) cover frames 0 .. k-1 only (0 = all)
 	void set_active(int k) { active_ = k; ent_.set_active(k); }
 	// async: all levels, all frames.  coeffs_needed = false: nothing but the GPU entropy stage will read this launch's coefficients -- where the level-1 bands
@@ -74,21 +71,35 @@ private:
 	void fill_block_lists();
 	ForwardRoute forward_route(bool coeffs_needed) const;      // which kernels the next launch_forward() runs: launch_forward() and level_kernel() both read this
 	FramePlan plan_;
-	int n_ = 0, active_ = 0, device_ = 0; bool own_input_ = false, jobs_dirty_ = true;
+	int n_ = 0, active_ = 0, device_ = 0; bool jobs_dirty_ = true;
 	void *stream_ = nullptr, *ev0_ = nullptr, *ev1_ = nullptr, *evl_[2] = {nullptr, nullptr};
 	float level_ms_[3] = {0, 0, 0};
 	uint8_t *d_in_ = nullptr, *h_in_ = nullptr; size_t frame_bytes_ = 0; int in_pitch_ = 0, in_rows_ = 0;
 	int16_t *d_coeff_ = nullptr, *h_coeff_ = nullptr;
 	void *d_jobs_ = nullptr, *h_jobs_ = nullptr; size_t jobs_bytes_ = 0;
 	int16_t *d_planes_ = nullptr; uint16_t *d_curve_ = nullptr; size_t plane_elems_ = 0;   // Bayer input: component planes + encode curve LUT
-	// Bayer: k_unpack_byr4 writes the component planes and k_fwd_plane transforms them (small launches; large ones take k_fwd_bayer_strip).  bayer_fused_ (tests only, no
-	// switch since round 5): level 1 computes the planes in its loader (k_fwd_packed16 layout 10 / 11) and never writes them -- same bytes, but 5.1 ms instead of 2.2 for
-	// 96 4K frames (round 3): every plane's loader pays the four curve gathers of a photosite quad again, and the tile's halo columns on top.
-	bool bayer_fused_ = false;
+	// Bayer: k_unpack_byr4 writes the component planes and k_fwd_plane transforms them (small launches; large ones take k_fwd_bayer_strip, level 1 straight from the mosaic)
 	float kernel_ms_ = 0;
 	bool timed_ = false;
 	GpuEntropyEncoder ent_; bool ent_ready_ = false;
 	int stage_pieces_ = 1;
+};
+
+// What a decoder output needs, computed once from (the sample's encoded format, the requested output, half, interlaced) by output_route() in cfhd_device.hip -- the one
+// place that knows what an output means.  DecodeBatch keeps it from prepare() on and sizes its buffers, builds its one last-level job table, names its kernel and runs
+// its conversion from it; GopBatch asks the same function for the outputs of 4:2:2 samples.  A new output format is a new answer of output_route(), at most one job
+// helper and at most one case of launch_convert().  (Which widths a caller may ask for is the C ABI's gate: cfhd_api_decoder.inc yuv422_output_served.)
+enum class OutJobs { Yuv, Planes16, HalfYuv, HalfPacked };      // the table the last launch reads: InvYuvJob | InvPlaneJob per output plane | HalfYuvJob | HalfPackedJob
+enum class OutConvert { None, V210, Rgb24, Rgb16, Byr4 };       // the pass behind the last level (k_yu64_to_v210 / _rgb24 / _rgb16, k_bayer_to_byr4); any but None: the last level writes a scratch frame
+struct OutputRoute {
+	const char *refusal = nullptr;                  // not served: the text device_last_error() gives, prepare() answers -2
+	int width_multiple = 1; const char *width_refusal = nullptr;      // the output's width in pixels is a multiple of this, or the same answer with this text
+	OutJobs jobs = OutJobs::Yuv;
+	int work = 0;                                   // the pixel kind the last-level kernel writes: the output itself, YU64 rows in front of a conversion, RG48 words of four planes for BYR4
+	OutConvert convert = OutConvert::None; int rgb16_mode = 0;       // k_yu64_to_rgb16: 0 RG48, 1 b64a, 2 BGRa, 3 BGRA
+	// half resolution: HalfYuvJob::mode and bottom_up (k_half_rgb24); HalfPackedJob::mode (0: k_half_packed16, else k_half_rgb), bytes, bottom_up and big_endian
+	int half_mode = 0, half_bytes = 0; bool bottom_up = false, big_endian = false;
+	int lowpass_kind = 0;                           // the output as the lowpass bias rule sees it (lowpass_bias()): the requested kind
 };
 
 class DecodeBatch {
@@ -96,7 +107,7 @@ public:
 	DecodeBatch();
 	~DecodeBatch();
 	// half: CFHD_DECODED_RESOLUTION_HALF of 4:2:2 samples -- the last wavelet level is not run, the level-1 lowpass planes are the picture
-	int prepare(const FramePlan &plan, int nframes, int out_pixel_kind, bool own_output, bool half = false);
+	int prepare(const FramePlan &plan, int nframes, int out_pixel_kind, bool half = false);
 	// interlaced 4:2:2 samples: the last level is the inverse frame transform (k_inv_frame_yuv422; 8-bit 4:2:2 output, full resolution), or into 16-bit rows
 	// (k_inv_frame_yuv422_rows16) for RG48 / b64a / BGRA / BGRa; set before prepare()
 	void set_interlaced(bool on) { interlaced_ = on; ent_.set_interlaced(on); }
@@ -115,7 +126,6 @@ public:
 	int launch_entropy();                            // entropy().launch() with the level-1 bands as block lists where the inverse gathers them
 	bool has_entropy() const { return ent_ready_; }
 	const char *level_kernel(int level) const;      // name of the kernel the next launch_entropy() + launch_inverse() use for level 0 / 1 / 2 (as a profiler shows it)
-	int set_device_output(int i, void *d_out, int pitch_bytes);
 	int launch_inverse(uint32_t dither_seed);          // async
 	int download_frame(int i, void *out, int pitch_bytes);   // async D2H into pinned staging, then row copy after wait
 	int download_frames(void *out, size_t frame_stride, int pitch_bytes);      // all n frames (finish_frame() for each behind wait()); ONE copy into a registered buffer that takes them back to back
@@ -130,20 +140,16 @@ private:
 	int sync_jobs();
 	InverseRoute inverse_route() const;             // which kernels the next launch_entropy() + launch_inverse() run: both and level_kernel() read this
 	FramePlan plan_;
-	int n_ = 0, out_kind_ = 0, device_ = 0; bool own_output_ = false, jobs_dirty_ = true, half_ = false, interlaced_ = false; int active_ = 0;
+	int n_ = 0, device_ = 0; bool jobs_dirty_ = true, half_ = false, interlaced_ = false; int active_ = 0;
+	int out_kind_ = 0; OutputRoute route_;          // the REQUESTED output kind, never rewritten, and what it needs (the kind the kernels write is route_.work)
 	void *stream_ = nullptr, *ev0_ = nullptr, *ev1_ = nullptr, *evl_[2] = {nullptr, nullptr};
 	float level_ms_[3] = {0, 0, 0};
 	int16_t *d_coeff_ = nullptr, *h_coeff_ = nullptr;
 	uint8_t *d_out_ = nullptr, *h_out_ = nullptr; size_t frame_bytes_ = 0; int out_pitch_ = 0, out_rows_ = 0;
-	bool v210_ = false; uint8_t *d_tmp_ = nullptr; int tmp_pitch_ = 0; size_t tmp_frame_bytes_ = 0;      // v210 output: YU64 rows first, packed by k_yu64_to_v210
+	uint8_t *d_tmp_ = nullptr; int tmp_pitch_ = 0; size_t tmp_frame_bytes_ = 0;      // outputs behind a conversion (route_.convert): the scratch frames the last level writes
 	// levels 3 and 2 of the inverse transform on a stream of their own when the entropy decoder finished their bands ahead of the level-1 bands (GpuEntropyDecoder::levels23_event)
 	void *stream2_ = nullptr, *ev2_[3] = {nullptr, nullptr, nullptr}; bool inv_split_ = false;
-	int lowpass_kind_ = 0;             // the output format as the lowpass bias rule sees it (lowpass_bias(): RG24 of a 4:2:2 sample is not YU64 there)
-	bool byr4_ = false; uint16_t *d_restore_ = nullptr;   // BYR4 output of Bayer samples: the four planes as 16-bit words per quad first, turned into the mosaic by k_bayer_to_byr4 (linear-restore table in HBM)
-	bool rgb16_of_422_ = false, rgb16_b64a_ = false;   // RG48 / b64a output of 4:2:2 samples: YU64 rows first, converted by k_yu64_to_rgb16 (bayer.c:11916 + RGB2YUV.c:1760)
-	bool rgb32_of_422_ = false;        // BGRA / BGRa output of 4:2:2 samples: the last level as k_inv_yuv422_rgb32 (spatial.c:29577)
-	bool rgb32_rows16_ = false, rgb32_bottom_up_ = false;   // BGRA / BGRa of interlaced 4:2:2 samples: the 16-bit rows, then k_yu64_to_rgb16's 8-bit mode (rgb16_of_422_ is set too)
-	bool rgb24_of_422_ = false;        // RG24 output of 4:2:2 samples: YU64 rows first, converted by k_yu64_to_rgb24 (the reference's route: 16-bit rows, then colour conversion)
+	uint16_t *d_restore_ = nullptr;                 // BYR4 output: the linear-restore table of k_bayer_to_byr4 in HBM
 	std::vector<char> direct_;                      // frame i went straight to the caller's (registered) buffer: finish_frame has nothing to copy
 	enum { kMaxOutPieces = 8 };
 	int stage_pieces_ = 1;
@@ -167,7 +173,7 @@ class GopBatch {
 public:
 	GopBatch();
 	~GopBatch();
-	// decode: out_pixel_kind is any output a 4:2:2 sample decodes to (the last level of both frames is the intra path's kernel of that output); half: the
+	// decode: out_pixel_kind is any output a 4:2:2 sample decodes to (OutputRoute: the last level of both frames is the intra path's job and kernel of that output); half: the
 	// level-1 lowpass planes the temporal inverse leaves are the picture (CFHD_DECODED_RESOLUTION_HALF), the last level is not run
 	int prepare(const GopPlan &plan, bool decode, int out_pixel_kind, bool half = false);
 	const GopPlan &plan() const { return plan_; }
@@ -196,12 +202,12 @@ public:
 	void release();
 private:
 	void fill_jobs();
-	GopRoute route() const;                          // decoder: the last-level kernel and the conversion behind it, from the output kind, half and interlaced alone
+	GopRoute route() const;                          // decoder: output_route() of a 4:2:2 sample for the output kind, half and interlaced, and the kernel that serves its family
 	GopForwardRoute forward_route() const;           // encoder: the level-1 kernel of both frames, from the input kind and interlaced alone
 	GopPlan plan_; bool decode_ = false, half_ = false; int out_kind_ = 0, device_ = 0, matrix_ = 0;
 	void *stream_ = nullptr;
 	uint8_t *d_frames_ = nullptr, *h_frames_ = nullptr; size_t frame_bytes_ = 0; int pitch_ = 0, rows_ = 0;
-	// decoder outputs converted from 16-bit rows (RG24, RG48, b64a, v210; RG48 / b64a / BGRA / BGRa of interlaced groups): the YU64 rows of both frames first
+	// decoder outputs behind a conversion (OutputRoute::convert): the YU64 rows of both frames first
 	uint8_t *d_tmp_ = nullptr; size_t tmp_frame_bytes_ = 0; int tmp_pitch_ = 0;
 	int16_t *d_coeff_ = nullptr, *h_coeff_ = nullptr;
 	void *d_jobs_ = nullptr, *h_jobs_ = nullptr; size_t jobs_bytes_ = 0; bool jobs_dirty_ = true;

@@ -100,7 +100,6 @@ static bool dec_rgb10(int out_kind) { return out_kind >= PIX_R210 && out_kind <=
 // planes of the sample that reach the output pixel: an RGBA 4:4:4:4 sample decoded to RG48 leaves its alpha plane behind (the reference's RG48 route on planes G, R, B;
 // pinned on eight geometries, tests/test_oracle_vs_ref.py)
 static int dec_out_channels(int out_kind, const FramePlan &plan) { return out_kind == PIX_RG48 && plan.encoded_format == ENC_RGBA4444 ? 3 : plan.num_channels; }
-static bool dec_planes16(int out_kind) { return is_packed16(out_kind) || out_kind == PIX_YU64 || dec_rgb8(out_kind) || dec_rgb10(out_kind); }
 // position of plane c inside the pixel: 16-bit word, or byte for the 8-bit formats (planes G, R, B(, A) -> bytes 1, 2, 0(, 3))
 static int dec_word_of_channel(int out_kind, int c) { return dec_rgb10(out_kind) ? 0 : out_kind == PIX_YU64 ? (c == 0 ? 0 : (c == 1 ? 1 : 3)) : (dec_rgb8(out_kind) ? (c == 0 ? 1 : (c == 1 ? 2 : (c == 2 ? 0 : 3))) : packed_word_of_channel(out_kind, c)); }
 static int dec_stride_of_channel(int out_kind, int c, int nch) { return out_kind == PIX_YU64 ? (c == 0 ? 2 : 4) : (dec_rgb8(out_kind) ? rgb8_bytes(out_kind) : (dec_rgb10(out_kind) ? 3 : (out_kind == PIX_B64A ? 4 : nch))); }     // (b64a from RGB 4:4:4: three planes, four words)
@@ -120,19 +119,19 @@ static bool enc_rgb_as_422(const FramePlan &plan) { return (is_packed16(plan.pix
 static int enc_word_of_channel(int pixel_kind, int c) { return pixel_kind == PIX_V210 || enc_bytes8(pixel_kind) || enc_rgb10(pixel_kind) ? 0 : (pixel_kind == PIX_YU64 ? (c == 0 ? 0 : (c == 1 ? 1 : 3)) : packed_word_of_channel(pixel_kind, c)); }
 static int enc_stride_of_channel(int pixel_kind, int c, int nch) { return pixel_kind == PIX_YU64 ? (c == 0 ? 2 : 4) : (pixel_kind == PIX_B64A || pixel_kind == PIX_RG64 ? 4 : nch); }     // (b64a / RG64 to RGB 4:4:4 have three planes of four-word pixels)
 // The loader of k_fwd_packed16 / k_fwd_gop_packed16 for plane c of one packed frame (FwdPlaneJob: in, in_pitch, xstride, shift, display_height, compand, layout,
-// tail_from), written in one place for the intra batches and the two-frame groups; `frame` may be null (frames supplied later as device pointers).
+// tail_from), written in one place for the intra batches and the two-frame groups.
 static void fill_packed16_loader(dev::FwdPlaneJob &p, const uint8_t *frame8, int in_pitch, int pixel_kind, int encoded_format, int color_matrix, int width, int precision,
                                  int display_height, int nch, int c)
 {
 	const uint16_t *frame = (const uint16_t *)frame8;
-	p.in = frame ? (const int16_t *)(frame + enc_word_of_channel(pixel_kind, c)) : nullptr; p.in_pitch = in_pitch / 2;
+	p.in = (const int16_t *)(frame + enc_word_of_channel(pixel_kind, c)); p.in_pitch = in_pitch / 2;
 	p.xstride = enc_stride_of_channel(pixel_kind, c, nch); p.shift = 16 - precision; p.display_height = display_height;
 	p.compand = (pixel_kind == PIX_B64A || pixel_kind == PIX_RG64) && c == 3;
 	p.layout = pixel_kind == PIX_V210 ? c + 1 : 0; p.tail_from = (width - width % 48) / 2;
 	if (enc_bytes8(pixel_kind)) { p.layout = pixel_kind == PIX_BGRa ? 5 : 4; p.in_pitch = in_pitch; p.xstride = pixel_kind == PIX_RG24 ? 3 : 4; p.tail_from = c == 0 ? 1 : (c == 1 ? 2 : (c == 2 ? 0 : 3)); p.compand = c == 3; }     // planes G, R, B(, A) of bytes B, G, R(, A)
 	if (enc_rgb10(pixel_kind)) { p.layout = 6; p.in_pitch = in_pitch / 4; p.xstride = pixel_kind == PIX_R210 || pixel_kind == PIX_DPX0; p.tail_from = rgb10_shift(pixel_kind, c); }
 	if ((is_packed16(pixel_kind) || pixel_kind == PIX_RG64) && encoded_format == ENC_YUV422) {      // (enc_rgb_as_422)
-		p.in = frame ? (const int16_t *)(frame + (pixel_kind == PIX_B64A ? 1 : 0)) : nullptr;
+		p.in = (const int16_t *)(frame + (pixel_kind == PIX_B64A ? 1 : 0));
 		p.layout = 7; p.xstride = pixel_kind == PIX_RG48 ? 3 : 4; p.tail_from = c; p.shift = color_matrix; p.compand = 0;
 	}
 	if (enc_bytes8(pixel_kind) && encoded_format == ENC_YUV422) { p.layout = pixel_kind == PIX_BGRa ? 9 : 8; p.tail_from = c; p.shift = color_matrix; }
@@ -324,7 +323,7 @@ void EncodeBatch::release()
 	d_in_ = h_in_ = nullptr; d_coeff_ = h_coeff_ = nullptr; d_jobs_ = h_jobs_ = nullptr; stream_ = ev0_ = ev1_ = nullptr; n_ = 0;
 }
 
-int EncodeBatch::prepare(const FramePlan &plan, int nframes, bool own_input)
+int EncodeBatch::prepare(const FramePlan &plan, int nframes)
 {
 	int rc = device_init();
 	if (rc) return rc;
@@ -332,8 +331,7 @@ int EncodeBatch::prepare(const FramePlan &plan, int nframes, bool own_input)
 	device_ = device_current(); (void)hipSetDevice(device_);      // (release() went to the device of the buffers it freed)
 	const bool bayer = plan.pixel_kind == PIX_BYR4 || plan.pixel_kind == PIX_BYR5;
 	if (plan.pixel_kind != PIX_YUY2 && plan.pixel_kind != PIX_2VUY && !enc_packed16(plan.pixel_kind) && !bayer) { g_err = "pixel format not supported by the GPU path yet"; return -2; }
-	plan_ = plan; n_ = nframes; own_input_ = own_input;
-	bayer_fused_ = false;      // (level 1 straight from the mosaic through the tiled kernel: measured 5.1 ms against 2.2 for 96 4K frames in round 3; k_fwd_bayer_strip is the fused kernel that pays)
+	plan_ = plan; n_ = nframes;
 	HIPCHK((hipError_t)device_stream_create(&stream_));
 	HIPCHK(hipEventCreate((hipEvent_t *)&ev0_));
 	HIPCHK(hipEventCreate((hipEvent_t *)&ev1_));
@@ -350,10 +348,8 @@ int EncodeBatch::prepare(const FramePlan &plan, int nframes, bool own_input)
 		HIPCHK(hipMalloc((void **)&d_curve_, curve.size() * 2));
 		HIPCHK(hipMemcpy(d_curve_, curve.data(), curve.size() * 2, hipMemcpyHostToDevice));
 	}
-	if (own_input) {
-		HIPCHK(hipMalloc((void **)&d_in_, frame_bytes_ * n_));
-		HIPCHK(hipHostMalloc((void **)&h_in_, frame_bytes_ * n_, hipHostMallocPortable));
-	}
+	HIPCHK(hipMalloc((void **)&d_in_, frame_bytes_ * n_));
+	HIPCHK(hipHostMalloc((void **)&h_in_, frame_bytes_ * n_, hipHostMallocPortable));
 	HIPCHK(hipMalloc((void **)&d_coeff_, (size_t)plan.coeff_elems * 2 * n_));
 	HIPCHK(hipMemsetAsync(d_coeff_, 0, (size_t)plan.coeff_elems * 2 * n_, (hipStream_t)stream_));   // pad columns stay zero forever
 	HIPCHK(hipHostMalloc((void **)&h_coeff_, (size_t)plan.final_elems * 2 * n_, hipHostMallocPortable));
@@ -366,19 +362,17 @@ int EncodeBatch::prepare(const FramePlan &plan, int nframes, bool own_input)
 	return 0;
 }
 
-// (Re)writes the job tables from plan_: geometry, band addresses and quantizer parameters.  Input frame pointers set with
-// set_device_frame() are kept.
+// (Re)writes the job tables from plan_: geometry, band addresses and quantizer parameters.
 void EncodeBatch::fill_jobs()
 {
 	const FramePlan &plan = plan_;
-	const bool own_input = own_input_;
 	const bool bayer = plan.pixel_kind == PIX_BYR4 || plan.pixel_kind == PIX_BYR5;
 	const int nch = plan.num_channels, mpq = plan.midpoint_prequant;
 	EncJobs j = enc_jobs_at(h_jobs_, n_, nch);
 	for (int i = 0; i < n_; i++) {
 		int16_t *base = d_coeff_ + (size_t)i * plan.coeff_elems;
 		dev::FwdYuvJob &y = j.yuv[i];
-		y.in = own_input ? d_in_ + frame_bytes_ * i : nullptr; y.in_pitch = in_pitch_;
+		y.in = d_in_ + frame_bytes_ * i; y.in_pitch = in_pitch_;
 		y.width = plan.width; y.height = plan.height; y.display_height = plan.display_height;
 		y.uyvy = plan.pixel_kind == PIX_2VUY; y.shift = plan.precision - 8;
 		for (int c = 0; c < 3; c++) {
@@ -391,7 +385,7 @@ void EncodeBatch::fill_jobs()
 		if (bayer) {
 			const int ppitch = plan.ch[0].band[0][0].pitch * 2;
 			dev::BayerJob &bj = j.bayer[i];
-			bj.in = own_input ? (const uint16_t *)(d_in_ + frame_bytes_ * i) : nullptr; bj.in_pitch = in_pitch_ / 2;
+			bj.in = (const uint16_t *)(d_in_ + frame_bytes_ * i); bj.in_pitch = in_pitch_ / 2;
 			bj.width = plan.width; bj.height = plan.height; bj.display_height = plan.display_height;
 			bj.out_pitch = ppitch; bj.curve = d_curve_; bj.order = 0; bj.precision = plan.precision; bj.packed12 = plan.pixel_kind == PIX_BYR5;
 			for (int c = 0; c < 4; c++) {
@@ -399,10 +393,6 @@ void EncodeBatch::fill_jobs()
 				dev::FwdPlaneJob &p = j.l1[(size_t)i * nch + c];
 				p.in = bj.out[c]; p.in_pitch = ppitch; p.width = plan.ch[c].width; p.height = plan.ch[c].height; p.prescale = plan.prescale[0];
 				p.xstride = 1; p.shift = 0; p.display_height = plan.ch[c].height; p.compand = 0;
-				if (bayer_fused_) {                          // the planes are never written: level 1 reads the mosaic
-					p.in = (const int16_t *)bj.in; p.in_pitch = bj.in_pitch; p.layout = plan.pixel_kind == PIX_BYR5 ? 11 : 10; p.tail_from = c; p.xstride = bj.order;
-					p.shift = plan.precision; p.display_height = plan.display_height; p.curve = d_curve_;
-				}
 				p.out_pitch = plan.ch[c].band[0][0].pitch;
 				for (int b = 0; b < 4; b++) { p.out[b] = base + plan.ch[c].band[0][b].offset; p.q[b] = make_q(plan.ch[c].band[0][b].quant, mpq); }
 			}
@@ -410,7 +400,7 @@ void EncodeBatch::fill_jobs()
 		if (enc_packed16(plan.pixel_kind))
 			for (int c = 0; c < nch; c++) {
 				dev::FwdPlaneJob &p = j.l1[(size_t)i * nch + c];
-				fill_packed16_loader(p, own_input ? d_in_ + frame_bytes_ * i : nullptr, in_pitch_, plan.pixel_kind, plan.encoded_format, plan.color_matrix, plan.width, plan.precision,
+				fill_packed16_loader(p, d_in_ + frame_bytes_ * i, in_pitch_, plan.pixel_kind, plan.encoded_format, plan.color_matrix, plan.width, plan.precision,
 				                     plan.display_height, nch, c);
 				p.width = plan.ch[c].width; p.height = plan.ch[c].height; p.prescale = plan.prescale[0];
 				p.out_pitch = plan.ch[c].band[0][0].pitch;
@@ -436,23 +426,8 @@ int EncodeBatch::update_quant(const FramePlan &plan)
 	(void)hipSetDevice(device_);
 	if (plan.coeff_elems != plan_.coeff_elems || plan.num_channels != plan_.num_channels) return -1;
 	if (stream_) HIPCHK(hipStreamSynchronize((hipStream_t)stream_));      // the pinned job table may still be in flight
-	EncJobs j = enc_jobs_at(h_jobs_, n_, plan_.num_channels);
-	std::vector<const void *> keep_yuv(n_), keep_bayer(n_), keep_l1((size_t)n_ * plan_.num_channels);
-	std::vector<int> keep_pitch(n_), keep_bpitch(n_), keep_l1pitch((size_t)n_ * plan_.num_channels);
-	for (int i = 0; i < n_; i++) {
-		keep_yuv[i] = j.yuv[i].in; keep_pitch[i] = j.yuv[i].in_pitch; keep_bayer[i] = j.bayer[i].in; keep_bpitch[i] = j.bayer[i].in_pitch;
-		for (int c = 0; c < plan_.num_channels; c++) { keep_l1[(size_t)i * plan_.num_channels + c] = j.l1[(size_t)i * plan_.num_channels + c].in; keep_l1pitch[(size_t)i * plan_.num_channels + c] = j.l1[(size_t)i * plan_.num_channels + c].in_pitch; }
-	}
 	plan_ = plan;
 	fill_jobs();
-	if (!own_input_) for (int i = 0; i < n_; i++) {
-		j.yuv[i].in = (const uint8_t *)keep_yuv[i]; j.yuv[i].in_pitch = keep_pitch[i];
-		if (plan_.pixel_kind == PIX_BYR4 || plan_.pixel_kind == PIX_BYR5) {
-			j.bayer[i].in = (const uint16_t *)keep_bayer[i]; j.bayer[i].in_pitch = keep_bpitch[i];
-			if (bayer_fused_) for (int c = 0; c < 4; c++) { j.l1[(size_t)i * 4 + c].in = (const int16_t *)keep_bayer[i]; j.l1[(size_t)i * 4 + c].in_pitch = keep_bpitch[i]; }
-		}
-		if (enc_packed16(plan_.pixel_kind)) for (int c = 0; c < plan_.num_channels; c++) { j.l1[(size_t)i * plan_.num_channels + c].in = (const int16_t *)keep_l1[(size_t)i * plan_.num_channels + c]; j.l1[(size_t)i * plan_.num_channels + c].in_pitch = keep_l1pitch[(size_t)i * plan_.num_channels + c]; }
-	}
 	if (ent_ready_) ent_.set_plan(plan);
 	return 0;
 }
@@ -500,7 +475,7 @@ static size_t stage_piece_min_bytes() { static const size_t v = [] { const char 
 int EncodeBatch::upload_frame(int i, const void *frame, int pitch)
 {
 	(void)hipSetDevice(device_);
-	if (!own_input_ || i < 0 || i >= n_) return -1;
+	if (i < 0 || i >= n_) return -1;
 	const uint8_t *src = (const uint8_t *)frame;
 	if (plan_.pixel_kind == PIX_BYR4) {
 		// The reference reads a BYR4 frame as tightly packed rows whatever pitch it was given (frame.c:5376-5377: line1 = data + row * width * 4,
@@ -537,7 +512,7 @@ int EncodeBatch::upload_frame(int i, const void *frame, int pitch)
 int EncodeBatch::upload_frames(const void *frames, size_t frame_stride, int pitch)
 {
 	(void)hipSetDevice(device_);
-	if (!own_input_ || !frames) return -1;
+	if (!frames) return -1;
 	if (pitch == in_pitch_ && frame_stride == frame_bytes_ && plan_.pixel_kind != PIX_BYR4 && plan_.pixel_kind != PIX_BYR5 && host_buffer_is_registered(frames, frame_bytes_ * (size_t)n_)) {
 		HIPCHK(hipMemcpyAsync(d_in_, frames, frame_bytes_ * (size_t)n_, hipMemcpyHostToDevice, (hipStream_t)stream_));
 		return 0;
@@ -562,28 +537,6 @@ int EncodeBatch::upload_frames(const void *frames, size_t frame_stride, int pitc
 		return 0;
 	}
 	for (int i = 0; i < n_; i++) { const int rc = upload_frame(i, (const uint8_t *)frames + frame_stride * (size_t)i, pitch); if (rc) return rc; }
-	return 0;
-}
-
-int EncodeBatch::set_device_frame(int i, const void *d_frame, int pitch)
-{
-	if (i < 0 || i >= n_) return -1;
-	EncJobs j = enc_jobs_at(h_jobs_, n_, plan_.num_channels);
-	if (plan_.pixel_kind == PIX_BYR4 || plan_.pixel_kind == PIX_BYR5) {
-		j.bayer[i].in = (const uint16_t *)d_frame; j.bayer[i].in_pitch = pitch / 2;
-		if (bayer_fused_) for (int c = 0; c < 4; c++) { j.l1[(size_t)i * 4 + c].in = (const int16_t *)d_frame; j.l1[(size_t)i * 4 + c].in_pitch = pitch / 2; }
-		jobs_dirty_ = true; return 0;
-	}
-	if (enc_packed16(plan_.pixel_kind)) {
-		for (int c = 0; c < plan_.num_channels; c++) {
-			dev::FwdPlaneJob &p = j.l1[(size_t)i * plan_.num_channels + c];
-			p.in = (const int16_t *)((const uint16_t *)d_frame + enc_word_of_channel(plan_.pixel_kind, c)); p.in_pitch = enc_bytes8(plan_.pixel_kind) ? pitch : (enc_rgb10(plan_.pixel_kind) ? pitch / 4 : pitch / 2);
-			if (enc_rgb_as_422(plan_)) p.in = (const int16_t *)((const uint16_t *)d_frame + (plan_.pixel_kind == PIX_B64A ? 1 : 0));
-		}
-		jobs_dirty_ = true;
-		return 0;
-	}
-	if (j.yuv[i].in != d_frame || j.yuv[i].in_pitch != pitch) { j.yuv[i].in = (const uint8_t *)d_frame; j.yuv[i].in_pitch = pitch; jobs_dirty_ = true; }
 	return 0;
 }
 
@@ -658,8 +611,7 @@ ForwardRoute EncodeBatch::forward_route(bool coeffs_needed) const
 	// 4:2:2 frames of whole 32-pixel blocks whose rows are 16-byte aligned (k_fwd_yuv422_strip, k_fwd_frame_yuv422_strip)
 	const bool yuv_strips = strips && plan_.encoded_format == ENC_YUV422 && plan_.width % 32 == 0 &&
 	                        every_frame(n_, [&](int i) { return !((uintptr_t)j.yuv[i].in & 15) && !(j.yuv[i].in_pitch & 15); });
-	if (bayer && bayer_fused_) r.l1 = FwdL1::Packed16;
-	else if (bayer) {
+	if (bayer) {
 		// BYR4 mosaics whose component planes are whole 8-column blocks wide and whose rows are 16-byte aligned; BYR5 and small launches unpack the planes first
 		const bool ok = strips && kind == PIX_BYR4 && plan_.width % 8 == 0 && nch == 4 &&
 		                every_frame(n_, [&](int i) { return !((uintptr_t)j.bayer[i].in & 15) && !((j.bayer[i].in_pitch * 2) & 15) && j.bayer[i].order == j.bayer[0].order; });
@@ -704,7 +656,6 @@ int EncodeBatch::launch_forward(bool coeffs_needed)
 	const int nseg = (plan_.width / 8 + dev::PSTEP - 1) / dev::PSTEP, nstrips = (plan_.height / 2 + dev::PSR - 1) / dev::PSR, waves = act * nseg * nstrips;      // RG48 / b64a / Bayer strips
 	switch (r.l1) {
 	case FwdL1::Packed16:
-		// (a fused Bayer batch too: every component plane's loader computes its samples from the photosite quads, the planes k_unpack_byr4 would write never exist)
 		dev::k_fwd_packed16<<<dim3(tiles.x * nch, tiles.y, act), dev::NTHREADS, 0, st>>>(j.l1, nch);
 		break;
 	case FwdL1::BayerStrip:
@@ -782,6 +733,149 @@ int EncodeBatch::wait()
 }
 
 // =============================================================================================
+// Decoder outputs: what an output needs (cfhd_device.h OutputRoute), the job of each family, the conversion pass
+// =============================================================================================
+// The one place that knows what a requested output of a sample means; DecodeBatch (prepare, inverse_route, launch_inverse) and GopBatch (route, fill_jobs,
+// launch_inverse; always ENC_YUV422) read the answer and decide nothing about outputs themselves.  Pure: no environment, no batch state, no geometry -- the band-width
+// rules of the 16-bit rows are DecodeBatch::prepare's, the widths a caller may ask for are the C ABI's (cfhd_api_decoder.inc yuv422_output_served).
+static OutputRoute output_route(int encoded_format, int kind, bool half, bool interlaced)
+{
+	OutputRoute r; r.work = kind; r.lowpass_kind = kind;
+	const bool yuv8 = kind == PIX_YUY2 || kind == PIX_2VUY, rgb32 = kind == PIX_BGRA || kind == PIX_BGRa, rgb16 = is_packed16(kind), rgb8 = dec_rgb8(kind), rgb10 = dec_rgb10(kind);
+	auto refuse = [&r](const char *text) { r.refusal = text; return r; };
+	static const char *const not_served = "output format not supported by the GPU path yet";
+	// BYR4 output of Bayer samples (decoder.c:14738 + bayer.c:13233 GenerateBYR2): the four component planes as 16-bit rows -- the RG48 route with four planes,
+	// four words per photosite quad -- then k_bayer_to_byr4
+	if (kind == PIX_BYR4) {
+		if (encoded_format != ENC_BAYER || half) return refuse("BYR4 output: Bayer samples, full resolution");
+		r.jobs = OutJobs::Planes16; r.work = PIX_RG48; r.convert = OutConvert::Byr4;
+		return r;
+	}
+	if (encoded_format == ENC_YUV422) {
+		if (!yuv8 && kind != PIX_YU64 && kind != PIX_V210 && !rgb8 && !rgb16) return refuse(not_served);
+		// v210 (10-bit 4:2:2, three samples per 32-bit word): the reference's samples are its YU64 words >> 6 (oracle/cfhd_oracle_inv.c orc_inv_spatial_to_v210, pinned on
+		// the reference decoder for widths that are multiples of six) -- YU64 rows into the scratch frame (half resolution: by k_half_yu64), packed by k_yu64_to_v210
+		if (kind == PIX_V210) { r.work = PIX_YU64; r.convert = OutConvert::V210; r.width_multiple = 6; r.width_refusal = "v210 output: widths that are multiples of 6"; }
+		if (half) {
+			// the level-1 lowpass planes are the picture: 8-bit 4:2:2 (k_half_yuv422), YU64 words (k_half_yu64), or -- RG24, BGRA / BGRa, RG48, b64a -- k_half_rgb24's modes
+			// straight from the planes (frame.c:8504 and its RGB32 branch, an SSE2 loop of 16 pixels; frame.c:9567): no scratch frame, no last level
+			r.jobs = OutJobs::HalfYuv;
+			if (rgb8 || rgb16) { r.half_mode = kind == PIX_RG24 ? 0 : (kind == PIX_RG48 ? 2 : (kind == PIX_B64A ? 3 : 1)); r.bottom_up = kind == PIX_BGRA; }
+			if (rgb32) { r.width_multiple = 16; r.width_refusal = "BGRA / BGRa output of 4:2:2 samples: half widths that are multiples of 16"; }
+			return r;
+		}
+		if (yuv8) return r;                              // (OutJobs::Yuv: the 4:2:2 kernels, interlaced: the inverse frame transform)
+		// BGRA / BGRa of progressive samples: the last level with the reference's fused colour conversion (spatial.c:29577, k_inv_yuv422_rgb32)
+		if (rgb32 && !interlaced) return r;
+		// Everything else is made from 16-bit rows in the scratch frame.  Progressive: the three planes as YU64 words (k_inv_packed16), then RG24 by the reference's scalar
+		// conversion (convert.c:11392 ConvertRow16uToDitheredRGB: k_yu64_to_rgb24), RG48 / b64a by bayer.c:11916 Row16uFull2OutputFormat + RGB2YUV.c:1760 (k_yu64_to_rgb16).
+		// Interlaced: RG48 / b64a / BGRA / BGRa from the 16-bit rows of the inverse frame transform (decoder.c:26488 -> :22027 TransformInverseFrameToRow16u,
+		// k_inv_frame_yuv422_rows16) -- BGRA / BGRa in k_yu64_to_rgb16's 8-bit mode (bayer.c:825), not the fused kernel; YU64, v210 and RG24 have no such rows (the C ABI
+		// refuses them, the planes' route does not run on an interlaced sample: inverse_route)
+		r.work = PIX_YU64;
+		r.jobs = interlaced && (rgb16 || rgb32) ? OutJobs::Yuv : OutJobs::Planes16;
+		if (kind == PIX_RG24) r.convert = OutConvert::Rgb24;
+		if (rgb16 || rgb32) { r.convert = OutConvert::Rgb16; r.rgb16_mode = kind == PIX_BGRA ? 3 : (kind == PIX_BGRa ? 2 : (kind == PIX_B64A ? 1 : 0)); }
+		return r;
+	}
+	// RGB 4:4:4 and RGBA 4:4:4:4 samples: RG48 and b64a of either (b64a of RGB 4:4:4: a constant alpha word; RG48 of RGBA: the alpha plane left behind), the 8-bit
+	// pixels (not RG24 of RGBA), the 10-bit words of RGB 4:4:4
+	const bool rgb = encoded_format == ENC_RGB444, rgba = encoded_format == ENC_RGBA4444;
+	if (!((rgb16 && (rgb || rgba)) || (rgb8 && (rgb || (rgba && kind != PIX_RG24))) || (rgb10 && rgb))) return refuse(not_served);
+	if (!half) { r.jobs = OutJobs::Planes16; return r; }
+	r.jobs = OutJobs::HalfPacked;                        // (half_mode 0: k_half_packed16 -- RG48, b64a of RGBA)
+	if (rgb8 || rgb10 || (kind == PIX_B64A && rgb)) {    // k_half_rgb (frame.c:7150 ConvertLowpassRGB444ToRGB)
+		r.half_mode = rgb8 ? 1 : (rgb10 ? 2 : 3); r.half_bytes = rgb8 ? rgb8_bytes(kind) : 0;
+		r.bottom_up = kind == PIX_RG24 || kind == PIX_BGRA; r.big_endian = kind == PIX_R210 || kind == PIX_DPX0;
+	}
+	return r;
+}
+
+// The level-1 wavelet of one frame as the last launch sees it: a frame of an intra batch, or frame f of a two-frame group (the temporal inverse leaves it in w[f])
+struct Level1 { int16_t *band[kMaxChannels][4]; int pitch[kMaxChannels], width[kMaxChannels], height[kMaxChannels]; };
+static Level1 level1_of(const FramePlan &plan, int16_t *base)
+{
+	Level1 l;
+	for (int c = 0; c < plan.num_channels; c++) { const BandDesc *b = plan.ch[c].band[0]; l.pitch[c] = b[0].pitch; l.width[c] = b[0].width; l.height[c] = b[0].height; for (int k = 0; k < 4; k++) l.band[c][k] = base + b[k].offset; }
+	return l;
+}
+static Level1 level1_of(const GopPlan &plan, int f, int16_t *base)
+{
+	Level1 l;
+	for (int c = 0; c < 3; c++) { const GopWavelet &w = plan.ch[c].w[f]; l.pitch[c] = w.pitch; l.width[c] = w.width; l.height[c] = w.height; for (int k = 0; k < 4; k++) l.band[c][k] = base + w.offset[k]; }
+	return l;
+}
+
+// One job of each family (OutJobs) for frame i, into tables that were zeroed: `out` is where the last launch writes the frame -- the output, or the scratch frame of a conversion
+static void fill_half_yuv_job(dev::HalfYuvJob &hj, const Level1 &l, const OutputRoute &r, int rows, int matrix, uint8_t *out, int out_pitch)
+{
+	for (int c = 0; c < 3; c++) { hj.ll[c] = l.band[c][0]; hj.pitch[c] = l.pitch[c]; }
+	hj.width = l.width[0]; hj.rows = rows; hj.uyvy = r.work == PIX_2VUY; hj.matrix = matrix;
+	hj.mode = r.half_mode; hj.bottom_up = r.bottom_up;
+	hj.out = out; hj.out_pitch = out_pitch;
+}
+static void fill_half_packed_job(dev::HalfPackedJob &hp, const Level1 &l, const OutputRoute &r, int onch, int precision, int rows, int i, uint8_t *out, int out_pitch)
+{
+	for (int c = 0; c < onch; c++) { hp.ll[c] = l.band[c][0]; hp.word[c] = dec_rgb10(r.work) ? rgb10_shift(r.work, c) : (r.half_mode ? 0 : packed_word_of_channel(r.work, c)); }
+	hp.pitch = l.pitch[0]; hp.width = l.width[0]; hp.rows = rows; hp.nch = onch;
+	if (r.half_mode) { hp.mode = r.half_mode; hp.bytes = r.half_bytes; hp.bottom_up = r.bottom_up; hp.big_endian = r.big_endian; hp.dither_seed = 0x9E3779B9u * (uint32_t)(i + 1); }      // k_half_rgb
+	else { hp.shift = 16 - precision - 2; hp.alpha = r.work == PIX_B64A; }                                                                                                        // k_half_packed16
+	hp.out = (uint16_t *)out; hp.out_pitch = out_pitch;
+}
+// (nch: the planes of the sample, onch: those that reach the pixel -- dec_out_channels)
+static void fill_planes16_jobs(dev::InvPlaneJob *jobs, const Level1 &l, const OutputRoute &r, int nch, int onch, int precision, int display_height, int i, uint8_t *out, int out_pitch)
+{
+	const int k = r.work;
+	for (int c = 0; c < onch; c++) {
+		dev::InvPlaneJob &p = jobs[c];
+		for (int b = 0; b < 4; b++) p.band[b] = l.band[c][b];
+		p.band_pitch = l.pitch[c]; p.width = l.width[c]; p.height = l.height[c]; p.descale = 0;
+		p.out = dec_plane_out(out, k, c); p.out_pitch = dec_rgb8(k) ? out_pitch : out_pitch / 2;
+		p.xstride = dec_stride_of_channel(k, c, onch); p.precision = precision; p.display_height = display_height;
+		p.alpha = (k == PIX_B64A || dec_rgb8(k)) && c == 3;
+		p.alpha_const = k == PIX_B64A && nch == 3 ? 0xfff0 : 0;
+		p.bytes8 = dec_rgb8(k) ? (nch == 4 ? 2 : 1) : 0;        // 2: BGRA / BGRa of an RGBA 4:4:4:4 sample (alpha from the fourth plane, no dither)
+		p.bottom_up = k == PIX_RG24 || k == PIX_BGRA; p.dither_seed = 0x9E3779B9u * (uint32_t)(i + 1);
+		if (dec_rgb10(k)) { p.out = (int16_t *)out; p.out_pitch = out_pitch / 4; p.bit_shift = rgb10_shift(k, c); p.big_endian = k == PIX_R210 || k == PIX_DPX0; }
+	}
+}
+// (masks / mask_base, the block lists of an intra batch behind its entropy decoder, are DecodeBatch's to add)
+static void fill_inv_yuv_job(dev::InvYuvJob &y, const Level1 &l, const OutputRoute &r, int precision, int display_height, int matrix, int i, uint8_t *out, int out_pitch)
+{
+	for (int c = 0; c < 3; c++) { y.band_pitch[c] = l.pitch[c]; for (int b = 0; b < 4; b++) y.band[c][b] = l.band[c][b]; }
+	y.width = l.width[0]; y.height = l.height[0]; y.display_height = display_height;
+	y.uyvy = r.work == PIX_2VUY; y.shift = precision - 8; y.dither_seed = 0x9E3779B9u * (uint32_t)(i + 1);
+	y.out = out; y.out_pitch = out_pitch;
+	y.bottom_up = r.work == PIX_BGRA; y.matrix_601 = matrix >= 2;       // (k_inv_yuv422_rgb32)
+	y.masks = nullptr;
+}
+
+// The pass behind the last level of `frames` frames from `first` on: the scratch frames (16-bit rows, `width` pixels -- BYR4: photosite quads -- by `rows` rows) into
+// the output frames.  Pitches and frame strides in bytes.  matrix: FramePlan::color_matrix; restore: the linear-restore table of BYR4.
+static void launch_convert(const OutputRoute &r, const uint8_t *src8, int src_pitch, size_t src_stride, uint8_t *dst, int dst_pitch, size_t dst_stride, int width, int rows,
+                           int first, int frames, int matrix, uint32_t seed, const uint16_t *restore, hipStream_t st)
+{
+	const uint16_t *src = (const uint16_t *)(src8 + src_stride * first);
+	dst += dst_stride * first;
+	auto grid = [&](int columns) { return dim3((unsigned)((columns + dev::NTHREADS - 1) / dev::NTHREADS), (unsigned)rows, (unsigned)frames); };
+	switch (r.convert) {
+	case OutConvert::None: break;
+	case OutConvert::V210:                               // six pixels per thread
+		dev::k_yu64_to_v210<<<grid(width / 6), dev::NTHREADS, 0, st>>>(src, src_pitch / 2, src_stride / 2, (uint32_t *)dst, dst_pitch / 4, dst_stride / 4, width / 6);
+		break;
+	case OutConvert::Rgb24:                              // a pixel pair per thread
+		dev::k_yu64_to_rgb24<<<grid(width / 2), dev::NTHREADS, 0, st>>>(src, src_pitch / 2, src_stride / 2, dst, dst_pitch, dst_stride, width / 2, rows, matrix, seed);
+		break;
+	case OutConvert::Rgb16:
+		dev::k_yu64_to_rgb16<<<grid(width / 2), dev::NTHREADS, 0, st>>>(src, src_pitch / 2, src_stride / 2, (uint16_t *)dst, dst_pitch / 2, dst_stride / 2, width / 2, matrix >= 2, r.rgb16_mode);
+		break;
+	case OutConvert::Byr4:                               // a photosite quad per thread
+		dev::k_bayer_to_byr4<<<grid(width), dev::NTHREADS, 0, st>>>(src, src_pitch / 2, src_stride / 2, (uint16_t *)dst, dst_pitch / 2, dst_stride / 2, width, restore);
+		break;
+	}
+}
+
+// =============================================================================================
 // DecodeBatch
 // =============================================================================================
 DecodeBatch::DecodeBatch() {}
@@ -812,54 +906,20 @@ void DecodeBatch::release()
 	d_out_ = h_out_ = nullptr; d_coeff_ = h_coeff_ = nullptr; d_jobs_ = h_jobs_ = nullptr; stream_ = ev0_ = ev1_ = nullptr; n_ = 0;
 }
 
-int DecodeBatch::prepare(const FramePlan &plan, int nframes, int out_kind, bool own_output, bool half)
+int DecodeBatch::prepare(const FramePlan &plan, int nframes, int out_kind, bool half)
 {
 	int rc = device_init();
 	if (rc) return rc;
 	release();
 	device_ = device_current(); (void)hipSetDevice(device_);      // (release() went to the device of the buffers it freed)
-	half_ = half;
-	// v210 output (10-bit 4:2:2, three samples per 32-bit word): the reference's samples are its YU64 words >> 6 (oracle/cfhd_oracle_inv.c
-	// orc_inv_spatial_to_v210, pinned on the reference decoder for widths that are multiples of six) -- the frames are computed as YU64 rows into a
-	// scratch buffer and k_yu64_to_v210 packs them into the output
-	v210_ = out_kind == PIX_V210;
-	if (v210_) { if ((half ? plan.width / 2 : plan.width) % 6 || !own_output) { g_err = "v210 output: widths that are multiples of 6"; return -2; } out_kind = PIX_YU64; }      // (half resolution: k_half_yu64 feeds the same repack)
-	// RG24 output of 4:2:2 samples: the reference computes the three planes as 16-bit rows (the YU64 route) and converts them pixel by pixel
-	// (convert.c:11392 ConvertRow16uToDitheredRGB, oracle orc_inv_spatial_to_rgb24_of_yuv422): the same two steps here
-	lowpass_kind_ = out_kind;
-	rgb24_of_422_ = out_kind == PIX_RG24 && plan.encoded_format == ENC_YUV422;
-	if (rgb24_of_422_) { if (!own_output) { g_err = "RG24 output of 4:2:2 samples: into the library's own output frames"; return -2; } if (!half) out_kind = PIX_YU64; }
-	const bool rgb24_half = rgb24_of_422_ && half;      // (half resolution: k_half_rgb24 straight from the lowpass planes, no scratch frame)
-	if (rgb24_half) rgb24_of_422_ = false;
-	// RG48 / b64a output of 4:2:2 samples (bayer.c:11916 Row16uFull2OutputFormat: the 16-bit rows through RGB2YUV.c:1308 / :1760): the YU64 route into the scratch frame,
-	// then k_yu64_to_rgb16.  BGRA / BGRa output of 4:2:2 samples: the last level with the reference's fused colour conversion (k_inv_yuv422_rgb32).
-	// Interlaced samples (full resolution): all four through the 16-bit rows of the inverse frame transform (decoder.c:26488 -> :22027 TransformInverseFrameToRow16u,
-	// k_inv_frame_yuv422_rows16) into the scratch frame, then k_yu64_to_rgb16 -- BGRA / BGRa in its 8-bit mode (bayer.c:825), not the fused k_inv_yuv422_rgb32.
-	rgb32_rows16_ = interlaced_ && !half && (out_kind == PIX_BGRA || out_kind == PIX_BGRa) && plan.encoded_format == ENC_YUV422; rgb32_bottom_up_ = out_kind == PIX_BGRA;
-	rgb16_of_422_ = ((out_kind == PIX_RG48 || out_kind == PIX_B64A) && plan.encoded_format == ENC_YUV422) || rgb32_rows16_; rgb16_b64a_ = out_kind == PIX_B64A;
-	const int final_kind = out_kind;
-	if (rgb16_of_422_) { if (!own_output) { g_err = "RG48 / b64a output of 4:2:2 samples: into the library's own output frames"; return -2; } if (!half) out_kind = PIX_YU64; }
-	rgb32_of_422_ = (out_kind == PIX_BGRA || out_kind == PIX_BGRa) && plan.encoded_format == ENC_YUV422;
-	if (rgb32_of_422_ && (!own_output || (half && (plan.width / 2) % 16))) { g_err = "BGRA / BGRa output of 4:2:2 samples: into the library's own output frames; half widths that are multiples of 16"; return -2; }
-	// (half resolution of the four: k_half_rgb24's other modes straight from the lowpass planes -- frame.c:8504 RGB32 branch, frame.c:9567 -- no scratch frame, no last level)
-	const bool rgb_half_of_422 = half && (rgb16_of_422_ || rgb32_of_422_);
-	if (rgb_half_of_422) { rgb16_of_422_ = false; rgb32_of_422_ = false; }
-	// BYR4 output of Bayer samples (decoder.c:14738 + bayer.c:13233 GenerateBYR2): the four component planes as 16-bit rows -- the RG48 route with four planes,
-	// four words per photosite quad -- then k_bayer_to_byr4
-	byr4_ = out_kind == PIX_BYR4;
-	if (byr4_) { if (plan.encoded_format != ENC_BAYER || !own_output || half) { g_err = "BYR4 output: Bayer samples, full resolution"; return -2; } out_kind = PIX_RG48; }
-	const bool repack = v210_ || rgb24_of_422_ || byr4_ || rgb16_of_422_;
-
-	const bool yuv_ok = (out_kind == PIX_YUY2 || out_kind == PIX_2VUY || rgb32_of_422_) && plan.encoded_format == ENC_YUV422;
-	// (b64a from an RGB 4:4:4 sample: the three colour planes and a constant alpha word, full resolution)
-	const bool rgb_ok = ((out_kind == PIX_RG48 && plan.encoded_format == ENC_RGB444) || (out_kind == PIX_B64A && plan.encoded_format == ENC_RGBA4444) ||
-	                     (out_kind == PIX_B64A && plan.encoded_format == ENC_RGB444) || (out_kind == PIX_RG48 && plan.encoded_format == ENC_RGBA4444) || byr4_) &&
-	                    plan.ch[0].band[0][0].width >= 16;   // k_inv_packed16's tail-column rule assumes the reference's vector path
-	const bool yu64_ok = out_kind == PIX_YU64 && plan.encoded_format == ENC_YUV422 && plan.ch[1].band[0][0].width >= 16;
-	const bool rgb8_ok = dec_rgb8(out_kind) && (plan.encoded_format == ENC_RGB444 || (plan.encoded_format == ENC_RGBA4444 && out_kind != PIX_RG24)) && plan.ch[0].band[0][0].width >= 16 && plan.ch[0].band[0][0].width % 2 == 0;
-	const bool rgb10_ok = dec_rgb10(out_kind) && plan.encoded_format == ENC_RGB444 && plan.ch[0].band[0][0].width >= 16;
-	if (!yuv_ok && !rgb_ok && !yu64_ok && !rgb8_ok && !rgb10_ok && !rgb24_half && !rgb_half_of_422) { g_err = "output format not supported by the GPU path yet"; return -2; }
-	plan_ = plan; n_ = nframes; out_kind_ = out_kind; own_output_ = own_output;
+	const OutputRoute r = output_route(plan.encoded_format, out_kind, half, interlaced_);
+	const int out_width = half ? plan.width / 2 : plan.width, work_rows = half ? plan.display_height / 2 : plan.display_height;
+	if (r.refusal || out_width % r.width_multiple) { g_err = r.refusal ? r.refusal : r.width_refusal; return -2; }
+	// the tail-column rule of the 16-bit rows (k_inv_packed16, the half-resolution kernels of the same outputs) assumes the reference's vector path: bands of 16 columns
+	// and more -- the chroma bands where the rows are YU64 words --, the 8-bit pixels of RGB samples in pairs
+	const BandDesc &narrowest = plan.ch[r.work == PIX_YU64 ? 1 : 0].band[0][0];
+	if ((r.work == PIX_YU64 || plan.encoded_format != ENC_YUV422) && (narrowest.width < 16 || (dec_rgb8(r.work) && narrowest.width % 2))) { g_err = "output format not supported by the GPU path yet"; return -2; }
+	plan_ = plan; n_ = nframes; out_kind_ = out_kind; half_ = half; route_ = r;
 	HIPCHK((hipError_t)device_stream_create(&stream_));
 	HIPCHK(hipEventCreate((hipEvent_t *)&ev0_));
 	HIPCHK(hipEventCreate((hipEvent_t *)&ev1_));
@@ -868,29 +928,25 @@ int DecodeBatch::prepare(const FramePlan &plan, int nframes, int out_kind, bool 
 	// (a batch of the frame queue creates its second stream only for the arrangement that uses it -- CFHD_AMD_TILES_SPLIT=1, launch_inverse --: a stream that is never used
 	// still takes its turn when the runtime deals its 4 hardware queues to the streams in creation order)
 	{ const char *se = getenv("CFHD_AMD_TILES_SPLIT"); if ((se && se[0] == '1') || !device_streams_are_lean()) HIPCHK((hipError_t)device_stream_create(&stream2_)); }      // (not lean: the C ABI's handles, cfhd_entropy_gpu.h device_streams_lean)
-	out_rows_ = half ? plan.display_height / 2 : plan.display_height;
-	out_pitch_ = byr4_ ? plan.width * 8 : packed_frame_pitch(out_kind, half ? plan.width / 2 : plan.width);      // (BYR4: the scratch rows hold four words per quad)
+	// The output frames, in the requested kind; behind a conversion the last level writes scratch frames of the working kind instead.  (BYR4: the plan counts photosite
+	// quads -- scratch rows of four words per quad, twice as many mosaic rows.)
+	const bool convert = r.convert != OutConvert::None, byr4 = r.convert == OutConvert::Byr4;
+	out_rows_ = byr4 ? 2 * work_rows : work_rows;
+	out_pitch_ = packed_frame_pitch(out_kind, byr4 ? 2 * plan.width : out_width);
 	frame_bytes_ = (size_t)out_pitch_ * out_rows_;
-	uint8_t *job_out = nullptr; size_t job_frame_bytes = frame_bytes_;      // where the last-level kernel writes frame i: the output, or the YU64 scratch of v210 output
-	if (repack) {
-		HIPCHK(hipMalloc((void **)&d_tmp_, frame_bytes_ * n_));
-		job_out = d_tmp_; tmp_pitch_ = out_pitch_; tmp_frame_bytes_ = frame_bytes_;
-		if (byr4_) {
-			out_rows_ = 2 * plan.display_height; out_pitch_ = packed_frame_pitch(PIX_BYR4, 2 * plan.width);      // (the plan counts quads)
-			std::vector<uint16_t> curve((size_t)1 << kBayerCurveBits);
-			build_bayer_linear_restore_curve(curve.data());
-			HIPCHK(hipMalloc((void **)&d_restore_, curve.size() * 2));
-			HIPCHK(hipMemcpy(d_restore_, curve.data(), curve.size() * 2, hipMemcpyHostToDevice));
-		} else out_pitch_ = packed_frame_pitch(v210_ ? PIX_V210 : (rgb16_of_422_ ? final_kind : PIX_RG24), half ? plan.width / 2 : plan.width);
-		frame_bytes_ = (size_t)out_pitch_ * out_rows_;
+	tmp_pitch_ = !convert ? 0 : (byr4 ? plan.width * 8 : packed_frame_pitch(r.work, out_width)); tmp_frame_bytes_ = (size_t)tmp_pitch_ * work_rows;
+	if (convert) HIPCHK(hipMalloc((void **)&d_tmp_, tmp_frame_bytes_ * n_));
+	if (byr4) {
+		std::vector<uint16_t> curve((size_t)1 << kBayerCurveBits);
+		build_bayer_linear_restore_curve(curve.data());
+		HIPCHK(hipMalloc((void **)&d_restore_, curve.size() * 2));
+		HIPCHK(hipMemcpy(d_restore_, curve.data(), curve.size() * 2, hipMemcpyHostToDevice));
 	}
-	if (own_output) {
-		HIPCHK(hipMalloc((void **)&d_out_, frame_bytes_ * n_));
-		HIPCHK(hipHostMalloc((void **)&h_out_, frame_bytes_ * n_, hipHostMallocPortable));
-		if (v210_) HIPCHK(hipMemsetAsync(d_out_, 0, frame_bytes_ * n_, (hipStream_t)stream_));      // (row padding beyond the last whole group of 48 pixels stays zero)
-	}
-	if (!repack) job_out = d_out_;
-	const int job_pitch = repack ? tmp_pitch_ : out_pitch_;
+	HIPCHK(hipMalloc((void **)&d_out_, frame_bytes_ * n_));
+	HIPCHK(hipHostMalloc((void **)&h_out_, frame_bytes_ * n_, hipHostMallocPortable));
+	if (r.convert == OutConvert::V210) HIPCHK(hipMemsetAsync(d_out_, 0, frame_bytes_ * n_, (hipStream_t)stream_));      // (row padding beyond the last whole group of 48 pixels stays zero)
+	uint8_t *job_out = convert ? d_tmp_ : d_out_;        // where the last-level kernel writes frame i
+	const size_t job_frame_bytes = convert ? tmp_frame_bytes_ : frame_bytes_; const int job_pitch = convert ? tmp_pitch_ : out_pitch_;
 	HIPCHK(hipMalloc((void **)&d_coeff_, (size_t)plan.coeff_elems * 2 * n_));
 	HIPCHK(hipMemsetAsync(d_coeff_, 0, (size_t)plan.coeff_elems * 2 * n_, (hipStream_t)stream_));
 	HIPCHK(hipHostMalloc((void **)&h_coeff_, (size_t)plan.final_elems * 2 * n_, hipHostMallocPortable));
@@ -900,7 +956,7 @@ int DecodeBatch::prepare(const FramePlan &plan, int nframes, int out_kind, bool 
 	HIPCHK(hipHostMalloc(&h_jobs_, jobs_bytes_, hipHostMallocPortable));
 	memset(h_jobs_, 0, jobs_bytes_);
 
-	const int nch = plan.num_channels, onch = dec_out_channels(out_kind, plan);
+	const int nch = plan.num_channels, onch = dec_out_channels(r.work, plan);
 	DecJobs j = dec_jobs_at(h_jobs_, n_, nch);
 	for (int i = 0; i < n_; i++) {
 		int16_t *base = d_coeff_ + (size_t)i * plan.coeff_elems;
@@ -914,78 +970,19 @@ int DecodeBatch::prepare(const FramePlan &plan, int nframes, int out_kind, bool 
 				p.out = base + plan.ch[c].band[lv - 1][0].offset; p.out_pitch = plan.ch[c].band[lv - 1][0].pitch;
 				p.xstride = 1; p.precision = 0; p.display_height = 2 * p.height;
 			}
-		if (half && plan.encoded_format == ENC_YUV422 && (dec_rgb8(out_kind) || out_kind == PIX_RG48 || out_kind == PIX_B64A)) {      // k_half_rgb24: RG24, BGRA / BGRa, RG48, b64a of a 4:2:2 sample
-			dev::HalfYuvJob &hj = j.half[i];
-			for (int c = 0; c < 3; c++) { hj.ll[c] = base + plan.ch[c].band[0][0].offset; hj.pitch[c] = plan.ch[c].band[0][0].pitch; }
-			hj.width = plan.ch[0].band[0][0].width; hj.rows = out_rows_; hj.uyvy = 0; hj.matrix = plan.color_matrix;
-			hj.mode = out_kind == PIX_RG24 ? 0 : (out_kind == PIX_RG48 ? 2 : (out_kind == PIX_B64A ? 3 : 1)); hj.bottom_up = out_kind == PIX_BGRA;
-			hj.out = own_output ? d_out_ + frame_bytes_ * i : nullptr; hj.out_pitch = out_pitch_;
-			continue;
+		const Level1 l1 = level1_of(plan, base);
+		uint8_t *out = job_out + job_frame_bytes * i;
+		switch (r.jobs) {                                // the one table the last launch reads
+		case OutJobs::HalfYuv: fill_half_yuv_job(j.half[i], l1, r, out_rows_, plan.color_matrix, out, job_pitch); break;
+		case OutJobs::HalfPacked: fill_half_packed_job(j.halfp[i], l1, r, onch, plan.precision, out_rows_, i, out, job_pitch); break;
+		case OutJobs::Planes16: fill_planes16_jobs(&j.l1[(size_t)i * onch], l1, r, nch, onch, plan.precision, plan.display_height, i, out, job_pitch); break;
+		case OutJobs::Yuv: {
+			fill_inv_yuv_job(j.yuv[i], l1, r, plan.precision, plan.display_height, plan.color_matrix, i, out, job_pitch);
+			// (block lists: prepare_entropy() knows the mask buffer)
+			int mb[kMaxChannels][kNumBands]; dec_block_list_layout(plan, mb); for (int c = 0; c < 3; c++) for (int b = 0; b < 4; b++) j.yuv[i].mask_base[c][b] = mb[c][b];
+			break;
 		}
-		if (half && plan.encoded_format != ENC_YUV422 && (dec_rgb8(out_kind) || dec_rgb10(out_kind) || (out_kind == PIX_B64A && nch == 3))) {      // k_half_rgb
-			dev::HalfPackedJob &hp = j.halfp[i];
-			for (int c = 0; c < 3; c++) { hp.ll[c] = base + plan.ch[c].band[0][0].offset; hp.word[c] = dec_rgb10(out_kind) ? rgb10_shift(out_kind, c) : 0; }
-			hp.pitch = plan.ch[0].band[0][0].pitch; hp.width = plan.ch[0].band[0][0].width; hp.rows = out_rows_; hp.nch = dec_rgb8(out_kind) && nch == 4 ? 4 : 3;
-			if (hp.nch == 4) hp.ll[3] = base + plan.ch[3].band[0][0].offset;
-			hp.mode = dec_rgb8(out_kind) ? 1 : (dec_rgb10(out_kind) ? 2 : 3);
-			hp.bytes = dec_rgb8(out_kind) ? rgb8_bytes(out_kind) : 0; hp.bottom_up = out_kind == PIX_RG24 || out_kind == PIX_BGRA;
-			hp.big_endian = out_kind == PIX_R210 || out_kind == PIX_DPX0; hp.dither_seed = 0x9E3779B9u * (uint32_t)(i + 1);
-			hp.out = own_output ? (uint16_t *)(d_out_ + frame_bytes_ * i) : nullptr; hp.out_pitch = out_pitch_;
-			continue;
 		}
-		if (half && is_packed16(out_kind)) {
-			dev::HalfPackedJob &hp = j.halfp[i];
-			for (int c = 0; c < onch; c++) { hp.ll[c] = base + plan.ch[c].band[0][0].offset; hp.word[c] = packed_word_of_channel(out_kind, c); }
-			hp.pitch = plan.ch[0].band[0][0].pitch; hp.width = plan.ch[0].band[0][0].width; hp.rows = out_rows_; hp.nch = onch;
-			hp.shift = 16 - plan.precision - 2; hp.alpha = out_kind == PIX_B64A;
-			hp.out = own_output ? (uint16_t *)(d_out_ + frame_bytes_ * i) : nullptr; hp.out_pitch = out_pitch_;
-		}
-		if (half && out_kind == PIX_RG24 && plan.encoded_format == ENC_YUV422) {      // k_half_rgb24
-			dev::HalfYuvJob &hj = j.half[i];
-			for (int c = 0; c < 3; c++) { hj.ll[c] = base + plan.ch[c].band[0][0].offset; hj.pitch[c] = plan.ch[c].band[0][0].pitch; }
-			hj.width = plan.ch[0].band[0][0].width; hj.rows = out_rows_; hj.uyvy = 0; hj.matrix = plan.color_matrix;
-			hj.out = own_output ? d_out_ + frame_bytes_ * i : nullptr; hj.out_pitch = out_pitch_;
-			continue;
-		}
-		if (half && out_kind == PIX_YU64) {                 // k_half_yu64
-			dev::HalfYuvJob &hj = j.half[i];
-			for (int c = 0; c < 3; c++) { hj.ll[c] = base + plan.ch[c].band[0][0].offset; hj.pitch[c] = plan.ch[c].band[0][0].pitch; }
-			hj.width = plan.ch[0].band[0][0].width; hj.rows = out_rows_; hj.uyvy = 0;
-			hj.out = own_output ? job_out + job_frame_bytes * i : nullptr; hj.out_pitch = job_pitch;      // (v210 output: the scratch frame k_yu64_to_v210 reads)
-			continue;
-		}
-		if (dec_planes16(out_kind) && !rgb32_of_422_ && !(interlaced_ && rgb16_of_422_)) {
-			for (int c = 0; c < onch; c++) {
-				dev::InvPlaneJob &p = j.l1[(size_t)i * onch + c];
-				for (int b = 0; b < 4; b++) p.band[b] = base + plan.ch[c].band[0][b].offset;
-				p.band_pitch = plan.ch[c].band[0][0].pitch;
-				p.width = plan.ch[c].band[0][0].width; p.height = plan.ch[c].band[0][0].height; p.descale = 0;
-				uint16_t *frame = own_output ? (uint16_t *)(job_out + job_frame_bytes * i) : nullptr;
-				p.out = frame ? dec_plane_out(frame, out_kind, c) : nullptr; p.out_pitch = dec_rgb8(out_kind) ? job_pitch : job_pitch / 2;
-				p.xstride = dec_stride_of_channel(out_kind, c, onch); p.precision = plan.precision; p.display_height = plan.display_height;
-				p.alpha = (out_kind == PIX_B64A || dec_rgb8(out_kind)) && c == 3;
-				p.alpha_const = out_kind == PIX_B64A && nch == 3 ? 0xfff0 : 0;
-				p.bytes8 = dec_rgb8(out_kind) ? (nch == 4 ? 2 : 1) : 0;        // 2: BGRA / BGRa of an RGBA 4:4:4:4 sample (alpha from the fourth plane, no dither)
-				p.bottom_up = out_kind == PIX_RG24 || out_kind == PIX_BGRA; p.dither_seed = 0x9E3779B9u * (uint32_t)(i + 1);
-				if (dec_rgb10(out_kind)) { p.out = (int16_t *)frame; p.out_pitch = job_pitch / 4; p.bit_shift = rgb10_shift(out_kind, c); p.big_endian = out_kind == PIX_R210 || out_kind == PIX_DPX0; }
-			}
-			continue;
-		}
-		if (half && !is_packed16(out_kind)) {
-			dev::HalfYuvJob &hj = j.half[i];
-			for (int c = 0; c < 3; c++) { hj.ll[c] = base + plan.ch[c].band[0][0].offset; hj.pitch[c] = plan.ch[c].band[0][0].pitch; }
-			hj.width = plan.ch[0].band[0][0].width; hj.rows = out_rows_; hj.uyvy = out_kind == PIX_2VUY;
-			hj.out = own_output ? d_out_ + frame_bytes_ * i : nullptr; hj.out_pitch = out_pitch_;
-		}
-		dev::InvYuvJob &y = j.yuv[i];
-		for (int c = 0; c < 3; c++) { y.band_pitch[c] = plan.ch[c].band[0][0].pitch; for (int b = 0; b < 4; b++) y.band[c][b] = base + plan.ch[c].band[0][b].offset; }
-		y.width = plan.ch[0].band[0][0].width; y.height = plan.ch[0].band[0][0].height; y.display_height = plan.display_height;
-		y.uyvy = out_kind == PIX_2VUY; y.shift = plan.precision - 8; y.dither_seed = 0x9E3779B9u * (uint32_t)(i + 1);
-		y.out = own_output ? d_out_ + frame_bytes_ * i : nullptr; y.out_pitch = out_pitch_;
-		if (interlaced_ && rgb16_of_422_) { y.out = job_out + job_frame_bytes * i; y.out_pitch = job_pitch; }      // (k_inv_frame_yuv422_rows16: the YU64 scratch frame)
-		y.bottom_up = out_kind == PIX_BGRA; y.matrix_601 = plan.color_matrix >= 2;       // (k_inv_yuv422_rgb32)
-		y.masks = nullptr;                               // (block lists: prepare_entropy() knows the mask buffer)
-		{ int mb[kMaxChannels][kNumBands]; dec_block_list_layout(plan, mb); for (int c = 0; c < 3; c++) for (int b = 0; b < 4; b++) y.mask_base[c][b] = mb[c][b]; }
 	}
 	jobs_dirty_ = true;
 	return 0;
@@ -994,7 +991,7 @@ int DecodeBatch::prepare(const FramePlan &plan, int nframes, int out_kind, bool 
 int DecodeBatch::prepare_entropy(size_t sample_cap)
 {
 	ent_.set_skip_level1(half_);                         // half resolution never looks at the level-1 highpass bands
-	int rc = ent_.prepare(plan_, n_, d_coeff_, plan_.coeff_elems, sample_cap, lowpass_kind_, stream_);
+	int rc = ent_.prepare(plan_, n_, d_coeff_, plan_.coeff_elems, sample_cap, route_.lowpass_kind, stream_);
 	ent_ready_ = rc == 0;
 	if (ent_ready_ && h_jobs_) {
 		DecJobs j = dec_jobs_at(h_jobs_, n_, plan_.num_channels);
@@ -1024,24 +1021,6 @@ int DecodeBatch::upload_coeffs()
 	return 0;
 }
 
-int DecodeBatch::set_device_output(int i, void *d_out, int pitch)
-{
-	if (i < 0 || i >= n_) return -1;
-	DecJobs j = dec_jobs_at(h_jobs_, n_, plan_.num_channels);
-	if (half_ && is_packed16(out_kind_)) { j.halfp[i].out = (uint16_t *)d_out; j.halfp[i].out_pitch = pitch; jobs_dirty_ = true; return 0; }
-	if (dec_planes16(out_kind_)) {
-		for (int c = 0; c < plan_.num_channels; c++) {
-			dev::InvPlaneJob &p = j.l1[(size_t)i * plan_.num_channels + c];
-			p.out = dec_plane_out(d_out, out_kind_, c); p.out_pitch = dec_rgb8(out_kind_) ? pitch : (dec_rgb10(out_kind_) ? pitch / 4 : pitch / 2);
-		}
-		jobs_dirty_ = true;
-		return 0;
-	}
-	if (half_) { j.half[i].out = (uint8_t *)d_out; j.half[i].out_pitch = pitch; jobs_dirty_ = true; return 0; }
-	if (j.yuv[i].out != d_out || j.yuv[i].out_pitch != pitch) { j.yuv[i].out = (uint8_t *)d_out; j.yuv[i].out_pitch = pitch; jobs_dirty_ = true; }
-	return 0;
-}
-
 // The last level of the inverse transform: every kernel launch_inverse() can pick, and the name a profiler shows it under (level_kernel()).  Where a strip kernel and
 // an LDS-tiled one serve the same output they produce the same bytes.
 enum class InvL1 { Refused, HalfRgb24, HalfRgb, HalfYu64, HalfPacked16, HalfYuv422, FrameRows16, FrameRows16Col, Packed16Strip, Yuv422Rgb32, Rgb10, Packed16,
@@ -1058,8 +1037,11 @@ struct InverseRoute {
 	bool block_lists() const { return l1 == InvL1::Yuv422StripBlocks || l1 == InvL1::FrameYuv422StripBlocks; }
 };
 
-// The kernels of the next launch_entropy() + launch_inverse(), from the prepared batch alone: the environment switches, the active frame count and the job table are read
-// here and nowhere else.
+// The half-resolution kernel of a 4:2:2 sample's outputs (OutJobs::HalfYuv), for intra batches and two-frame groups
+static InvL1 half_yuv_kernel(const OutputRoute &o) { return o.work == PIX_YU64 ? InvL1::HalfYu64 : (o.work == PIX_YUY2 || o.work == PIX_2VUY ? InvL1::HalfYuv422 : InvL1::HalfRgb24); }
+
+// The kernels of the next launch_entropy() + launch_inverse(), from the prepared batch alone.  What the output needs is route_'s (output_route); which shape serves it --
+// strips against tiles, block lists, quads -- is decided here: the environment switches, the active frame count and the job table are read here and nowhere else.
 InverseRoute DecodeBatch::inverse_route() const
 {
 	const int blocks_env = [] { const char *e = getenv("CFHD_AMD_DEC_BLOCKS"); return e ? atoi(e) : 1; }();      // 0: dense bands (A/B runs; read at every launch: tests switch within one process)
@@ -1072,28 +1054,35 @@ InverseRoute DecodeBatch::inverse_route() const
 	const bool strips = forced != 1 && (forced != 0 || frames_1080p_equivalent(plan_, act) >= 12.0);
 	auto pitches_divide = [&](int m) { for (int c = 0; c < 3; c++) if (plan_.ch[c].band[0][0].pitch % m) return false; return true; };
 	auto rows_aligned = [&] { return every_frame(n_, [&](int i) { return !((uintptr_t)j.yuv[i].out & 15) && !(j.yuv[i].out_pitch & 15); }); };      // 16-byte stores
-	// interlaced: four band columns per thread with 8-byte loads and 16-byte stores, else the one-column kernel
 	auto quads = [&] { return forced != 1 && b.width % 4 == 0 && b.width >= 8 && pitches_divide(4) && rows_aligned(); };
 	// 8-bit 4:2:2 pictures behind the chunk-indexed GPU entropy decoder take the level-1 bands as block lists wherever a 4:2:2 strip kernel runs
 	const bool lists = blocks_env && ent_ready_ && ent_.block_masks(0) && ent_.chunk_indexed() && (out_kind_ == PIX_YUY2 || out_kind_ == PIX_2VUY) && plan_.encoded_format == ENC_YUV422;
-	// (interlaced samples at full resolution: the 16-bit rows serve RG48 / b64a / BGRA / BGRa only -- YU64, v210 and the 10-bit RGB words are refused at the C ABI)
-	if (interlaced_ && !half_ && dec_planes16(out_kind_)) r.l1 = !rgb16_of_422_ ? InvL1::Refused : (quads() ? InvL1::FrameRows16 : InvL1::FrameRows16Col);
+	const int work = route_.work;
+	switch (route_.jobs) {
 	// half resolution: the last level is not run, the level-1 lowpass planes are the picture
-	else if (half_ && plan_.encoded_format == ENC_YUV422 && (dec_rgb8(out_kind_) || out_kind_ == PIX_RG48 || out_kind_ == PIX_B64A)) r.l1 = InvL1::HalfRgb24;
-	else if (half_ && (dec_rgb8(out_kind_) || dec_rgb10(out_kind_) || (out_kind_ == PIX_B64A && nch == 3))) r.l1 = InvL1::HalfRgb;
-	else if (half_) r.l1 = out_kind_ == PIX_YU64 ? InvL1::HalfYu64 : (is_packed16(out_kind_) ? InvL1::HalfPacked16 : InvL1::HalfYuv422);
-	// RG48 / b64a output of whole 8-pixel blocks whose rows are 16-byte aligned (the strip kernel knows the RG48 and b64a pixels only)
-	else if (strips && is_packed16(out_kind_) && b.width % 4 == 0 && !(out_kind_ == PIX_B64A && nch == 3) && !byr4_ && every_frame(n_, [&](int i) {
-		const dev::InvPlaneJob &p = j.l1[(size_t)i * dec_out_channels(out_kind_, plan_)];
-		const uintptr_t frame = (uintptr_t)((const uint16_t *)p.out - packed_word_of_channel(out_kind_, 0));
-		return !(frame & 15) && !((p.out_pitch * 2) & 15) && !(p.band_pitch & 3); })) r.l1 = InvL1::Packed16Strip;
-	else if (rgb32_of_422_) r.l1 = InvL1::Yuv422Rgb32;
-	else if (dec_planes16(out_kind_)) r.l1 = dec_rgb10(out_kind_) ? InvL1::Rgb10 : InvL1::Packed16;
-	// 4:2:2 pictures: luma bands of whole 16-column blocks, written in 16-byte words (interlaced: band rows of whole 8-coefficient words too)
-	else if (strips && b.width % 16 == 0 && rows_aligned() && (!interlaced_ || pitches_divide(8)))
-		r.l1 = interlaced_ ? (lists ? InvL1::FrameYuv422StripBlocks : InvL1::FrameYuv422Strip) : (lists ? InvL1::Yuv422StripBlocks : InvL1::Yuv422Strip);
-	else if (interlaced_) r.l1 = quads() ? InvL1::FrameYuv422Quad : InvL1::FrameYuv422;
-	else r.l1 = InvL1::Yuv422;
+	case OutJobs::HalfYuv: r.l1 = half_yuv_kernel(route_); break;
+	case OutJobs::HalfPacked: r.l1 = route_.half_mode ? InvL1::HalfRgb : InvL1::HalfPacked16; break;
+	case OutJobs::Planes16:
+		// (interlaced samples at full resolution have no planes' route: YU64, v210, RG24 and the 10-bit RGB words are refused at the C ABI)
+		if (interlaced_) r.l1 = InvL1::Refused;
+		// RG48 / b64a output of whole 8-pixel blocks whose rows are 16-byte aligned (the strip kernel knows the RG48 and b64a pixels only)
+		else if (strips && is_packed16(work) && b.width % 4 == 0 && !(work == PIX_B64A && nch == 3) && route_.convert != OutConvert::Byr4 && every_frame(n_, [&](int i) {
+			const dev::InvPlaneJob &p = j.l1[(size_t)i * dec_out_channels(work, plan_)];
+			const uintptr_t frame = (uintptr_t)((const uint16_t *)p.out - packed_word_of_channel(work, 0));
+			return !(frame & 15) && !((p.out_pitch * 2) & 15) && !(p.band_pitch & 3); })) r.l1 = InvL1::Packed16Strip;
+		else r.l1 = dec_rgb10(work) ? InvL1::Rgb10 : InvL1::Packed16;
+		break;
+	case OutJobs::Yuv:
+		// interlaced: four band columns per thread with 8-byte loads and 16-byte stores, else the one-column kernel
+		if (route_.convert == OutConvert::Rgb16) r.l1 = quads() ? InvL1::FrameRows16 : InvL1::FrameRows16Col;
+		else if (dec_rgb8(work)) r.l1 = InvL1::Yuv422Rgb32;
+		// 4:2:2 pictures: luma bands of whole 16-column blocks, written in 16-byte words (interlaced: band rows of whole 8-coefficient words too)
+		else if (strips && b.width % 16 == 0 && rows_aligned() && (!interlaced_ || pitches_divide(8)))
+			r.l1 = interlaced_ ? (lists ? InvL1::FrameYuv422StripBlocks : InvL1::FrameYuv422Strip) : (lists ? InvL1::Yuv422StripBlocks : InvL1::Yuv422Strip);
+		else if (interlaced_) r.l1 = quads() ? InvL1::FrameYuv422Quad : InvL1::FrameYuv422;
+		else r.l1 = InvL1::Yuv422;
+		break;
+	}
 	return r;
 }
 
@@ -1171,15 +1160,15 @@ int DecodeBatch::launch_inverse(uint32_t dither_seed)
 	case InvL1::HalfYuv422: dev::k_half_yuv422<<<rows(8, out_rows_), dev::NTHREADS, 0, st>>>(j.half); break;
 	case InvL1::Packed16Strip: {
 		const int nseg = (b.width / 4 + dev::PSTEP - 1) / dev::PSTEP, nstrips = (b.height + dev::QSR - 1) / dev::QSR, waves = act * nseg * nstrips;
-		if (dec_out_channels(out_kind_, plan_) == 4) dev::k_inv_packed16_strip<4><<<(waves + 3) / 4, dev::NTHREADS, 0, st>>>(j.l1, act, nseg, nstrips);
+		if (dec_out_channels(route_.work, plan_) == 4) dev::k_inv_packed16_strip<4><<<(waves + 3) / 4, dev::NTHREADS, 0, st>>>(j.l1, act, nseg, nstrips);
 		else dev::k_inv_packed16_strip<3><<<(waves + 3) / 4, dev::NTHREADS, 0, st>>>(j.l1, act, nseg, nstrips);
 		break;
 	}
 	case InvL1::Yuv422Rgb32: dev::k_inv_yuv422_rgb32<<<tiles, dev::NTHREADS, 0, st>>>(j.yuv); break;
 	case InvL1::Rgb10: dev::k_inv_rgb10<<<tiles, dev::NTHREADS, 0, st>>>(j.l1); break;
 	case InvL1::Packed16: {
-		const int onch = dec_out_channels(out_kind_, plan_);
-		dev::k_inv_packed16<<<tiles, dev::NTHREADS, 0, st>>>(j.l1, onch, dec_words_per_position(out_kind_, onch), dither_seed);
+		const int onch = dec_out_channels(route_.work, plan_);
+		dev::k_inv_packed16<<<tiles, dev::NTHREADS, 0, st>>>(j.l1, onch, dec_words_per_position(route_.work, onch), dither_seed);
 		break;
 	}
 	// (interlaced, half resolution was served above: the level-1 lowpass planes need no inverse frame transform)
@@ -1191,26 +1180,8 @@ int DecodeBatch::launch_inverse(uint32_t dither_seed)
 	case InvL1::Yuv422Strip: dev::k_inv_yuv422_strip<<<strips, dev::NTHREADS, 0, st>>>(j.yuv, dither_seed); break;
 	case InvL1::Yuv422: dev::k_inv_yuv422<<<tiles, dev::NTHREADS, 0, st>>>(j.yuv, dither_seed); break;
 	}
-	if (rgb24_of_422_) {
-		const int pairs = plan_.width / 2;
-		dev::k_yu64_to_rgb24<<<dim3((unsigned)((pairs + dev::NTHREADS - 1) / dev::NTHREADS), (unsigned)out_rows_, (unsigned)act), dev::NTHREADS, 0, st>>>(
-			(const uint16_t *)d_tmp_, tmp_pitch_ / 2, tmp_frame_bytes_ / 2, d_out_, out_pitch_, frame_bytes_, pairs, out_rows_, plan_.color_matrix, dither_seed);
-	}
-	if (rgb16_of_422_) {
-		const int pairs = plan_.width / 2;
-		dev::k_yu64_to_rgb16<<<dim3((unsigned)((pairs + dev::NTHREADS - 1) / dev::NTHREADS), (unsigned)out_rows_, (unsigned)act), dev::NTHREADS, 0, st>>>(
-			(const uint16_t *)d_tmp_, tmp_pitch_ / 2, tmp_frame_bytes_ / 2, (uint16_t *)d_out_, out_pitch_ / 2, frame_bytes_ / 2, pairs, plan_.color_matrix >= 2, rgb32_rows16_ ? (rgb32_bottom_up_ ? 3 : 2) : (rgb16_b64a_ ? 1 : 0));
-	}
-	if (byr4_) {
-		const int quads = plan_.width;
-		dev::k_bayer_to_byr4<<<dim3((unsigned)((quads + dev::NTHREADS - 1) / dev::NTHREADS), (unsigned)plan_.display_height, (unsigned)act), dev::NTHREADS, 0, st>>>(
-			(const uint16_t *)d_tmp_, tmp_pitch_ / 2, tmp_frame_bytes_ / 2, (uint16_t *)d_out_, out_pitch_ / 2, frame_bytes_ / 2, quads, d_restore_);
-	}
-	if (v210_) {
-		const int groups = (half_ ? plan_.width / 2 : plan_.width) / 6;
-		dev::k_yu64_to_v210<<<dim3((unsigned)((groups + dev::NTHREADS - 1) / dev::NTHREADS), (unsigned)out_rows_, (unsigned)act), dev::NTHREADS, 0, st>>>(
-			(const uint16_t *)d_tmp_, tmp_pitch_ / 2, tmp_frame_bytes_ / 2, (uint32_t *)d_out_, out_pitch_ / 4, frame_bytes_ / 4, groups);
-	}
+	launch_convert(route_, d_tmp_, tmp_pitch_, tmp_frame_bytes_, d_out_, out_pitch_, frame_bytes_, half_ ? plan_.width / 2 : plan_.width, half_ ? plan_.display_height / 2 : plan_.display_height,
+	               0, act, plan_.color_matrix, dither_seed, d_restore_, st);
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipEventRecord((hipEvent_t)ev1_, st));
 	return 0;
@@ -1219,7 +1190,7 @@ int DecodeBatch::launch_inverse(uint32_t dither_seed)
 int DecodeBatch::download_frame(int i, void *out, int pitch)
 {
 	(void)hipSetDevice(device_);
-	if (!own_output_ || i < 0 || i >= n_) return -1;
+	if (i < 0 || i >= n_) return -1;
 	if (direct_.size() != (size_t)n_) direct_.assign((size_t)n_, 0);
 	direct_[i] = 0;
 	if (out && pitch >= out_pitch_ && host_buffer_is_registered(out, (size_t)pitch * (out_rows_ - 1) + out_pitch_)) {
@@ -1255,7 +1226,7 @@ int DecodeBatch::download_frame(int i, void *out, int pitch)
 int DecodeBatch::download_frames(void *out, size_t frame_stride, int pitch)
 {
 	(void)hipSetDevice(device_);
-	if (!own_output_ || !out) return -1;
+	if (!out) return -1;
 	if (pitch == out_pitch_ && frame_stride == frame_bytes_ && host_buffer_is_registered(out, frame_bytes_ * (size_t)n_)) {
 		HIPCHK(hipMemcpyAsync(out, d_out_, frame_bytes_ * (size_t)n_, hipMemcpyDeviceToHost, (hipStream_t)stream_));
 		direct_.assign((size_t)n_, 1);
@@ -1303,7 +1274,7 @@ int DecodeBatch::wait()
 
 int DecodeBatch::finish_frame(int i, void *out, int pitch)
 {
-	if (!own_output_ || i < 0 || i >= n_) return -1;
+	if (i < 0 || i >= n_) return -1;
 	if (direct_.size() == (size_t)n_ && direct_[i]) return 0;            // already in the caller's buffer
 	const uint8_t *src = h_out_ + frame_bytes_ * i;
 	uint8_t *dst = (uint8_t *)out;
@@ -1371,38 +1342,27 @@ const char *GopBatch::level1_kernel() const { return decode_ ? "" : kGopFwdL1Nam
 
 // The last level of a group's two frames: the intra path's kernel of the output (InvL1, one launch over both frames), then -- outputs made from 16-bit rows --
 // the conversion of both frames' YU64 rows.
-enum class GopConvert { None, Rgb24, Rgb16, V210 };
-struct GopRoute { InvL1 l1; GopConvert convert; };
+struct GopRoute { InvL1 l1; OutputRoute out; };
 
-// What a 4:2:2 sample decodes to (DecodeBatch::prepare and inverse_route(), the C ABI's yuv422_output_served) restated for the group pyramid: the output kind, half and
-// interlaced are read here and nowhere else.
+// What the output needs is output_route()'s answer for a 4:2:2 sample; here the family becomes the tile / row kernel the group launches (no strips, no block lists).
 GopRoute GopBatch::route() const
 {
-	const int k = out_kind_;
-	const bool rgb32 = k == PIX_BGRA || k == PIX_BGRa, rgb16 = is_packed16(k), yuv8 = k == PIX_YUY2 || k == PIX_2VUY;
-	if (half_) {
-		if (yuv8) return { InvL1::HalfYuv422, GopConvert::None };
-		if (k == PIX_YU64 || k == PIX_V210) return { InvL1::HalfYu64, k == PIX_V210 ? GopConvert::V210 : GopConvert::None };
-		if (k == PIX_RG24 || rgb32 || rgb16) return { InvL1::HalfRgb24, GopConvert::None };
-		return { InvL1::Refused, GopConvert::None };
-	}
-	if (plan_.interlaced) {
-		// (the inverse frame transform: 8-bit 4:2:2, or the 16-bit rows of RG48 / b64a / BGRA / BGRa; YU64, v210 and RG24 are refused at the C ABI)
-		if (yuv8) return { InvL1::FrameYuv422, GopConvert::None };
-		if (!rgb32 && !rgb16) return { InvL1::Refused, GopConvert::None };
+	const OutputRoute o = output_route(ENC_YUV422, out_kind_, half_, plan_.interlaced);
+	if (o.refusal) return { InvL1::Refused, o };
+	switch (o.jobs) {
+	case OutJobs::HalfYuv: return { half_yuv_kernel(o), o };
+	case OutJobs::Planes16: return { plan_.interlaced ? InvL1::Refused : InvL1::Packed16, o };      // (YU64, v210 and RG24 of interlaced groups are refused at the C ABI)
+	case OutJobs::Yuv: {
+		if (o.convert != OutConvert::Rgb16) return { dec_rgb8(o.work) ? InvL1::Yuv422Rgb32 : (plan_.interlaced ? InvL1::FrameYuv422 : InvL1::Yuv422), o };
 		const int w = plan_.ch[0].w[0].width;
 		// (the scratch rows are 16-byte aligned: 4 * width bytes, the width a multiple of 16: build_gop_plan)
 		bool quads = shape_override("CFHD_AMD_INVERSE") != 1 && w % 4 == 0 && w >= 8;
 		for (int c = 0; c < 3; c++) quads = quads && plan_.ch[c].w[0].pitch % 4 == 0;
-		return { quads ? InvL1::FrameRows16 : InvL1::FrameRows16Col, GopConvert::Rgb16 };
+		return { quads ? InvL1::FrameRows16 : InvL1::FrameRows16Col, o };
 	}
-	if (yuv8) return { InvL1::Yuv422, GopConvert::None };
-	if (rgb32) return { InvL1::Yuv422Rgb32, GopConvert::None };
-	if (k == PIX_YU64) return { InvL1::Packed16, GopConvert::None };
-	if (k == PIX_V210) return { InvL1::Packed16, GopConvert::V210 };
-	if (k == PIX_RG24) return { InvL1::Packed16, GopConvert::Rgb24 };
-	if (rgb16) return { InvL1::Packed16, GopConvert::Rgb16 };
-	return { InvL1::Refused, GopConvert::None };
+	case OutJobs::HalfPacked: break;                     // (no output of a 4:2:2 sample)
+	}
+	return { InvL1::Refused, o };
 }
 
 GopBatch::GopBatch() {}
@@ -1442,7 +1402,7 @@ int GopBatch::prepare(const GopPlan &plan, bool decode, int out_pixel_kind, bool
 	HIPCHK(hipHostMalloc((void **)&h_frames_, 2 * frame_bytes_, hipHostMallocPortable));
 	if (decode && out_pixel_kind == PIX_V210) HIPCHK(hipMemsetAsync(d_frames_, 0, 2 * frame_bytes_, (hipStream_t)stream_));      // (row padding beyond the last whole group of 48 pixels stays zero)
 	tmp_pitch_ = 0; tmp_frame_bytes_ = 0;
-	if (decode && r.convert != GopConvert::None) {
+	if (decode && r.out.convert != OutConvert::None) {
 		tmp_pitch_ = packed_frame_pitch(PIX_YU64, out_width); tmp_frame_bytes_ = (size_t)tmp_pitch_ * rows_;
 		HIPCHK(hipMalloc((void **)&d_tmp_, 2 * tmp_frame_bytes_));
 	}
@@ -1501,44 +1461,33 @@ void GopBatch::fill_jobs()
 	GopJobs j = gop_jobs_at(h_jobs_);
 	const int mpq = plan.midpoint_prequant;
 	int16_t *base = d_coeff_;
+	const OutputRoute o = decode_ ? route().out : OutputRoute();
 	for (int f = 0; f < 2; f++) {
 		dev::FwdYuvJob &y = j.yuv[f];
 		y.in = d_frames_ + frame_bytes_ * f; y.in_pitch = pitch_;
 		y.width = plan.width; y.height = plan.height; y.display_height = plan.display_height;
 		y.uyvy = plan.pixel_kind == PIX_2VUY; y.shift = plan.precision - 8;
-		dev::InvYuvJob &iy = j.iyuv[f];
 		for (int c = 0; c < 3; c++) {
 			const GopWavelet &w = plan.ch[c].w[f];
-			y.out_pitch[c] = w.pitch; iy.band_pitch[c] = w.pitch;
-			for (int b = 0; b < 4; b++) { y.out[c][b] = base + w.offset[b]; y.q[c][b] = make_q(w.quant[b], mpq); iy.band[c][b] = base + w.offset[b]; }
+			y.out_pitch[c] = w.pitch;
+			for (int b = 0; b < 4; b++) { y.out[c][b] = base + w.offset[b]; y.q[c][b] = make_q(w.quant[b], mpq); }
 			// interlaced groups: the difference-coded band is quantized inside the horizontal filter, midpoint = divisor / prequant without the decrement (spatial.c:5360-5363)
 			if (plan.interlaced && w.quant[2] > 1 && mpq >= 2 && mpq < 9) y.q[c][2].mid = w.quant[2] / mpq;
 		}
-		iy.width = plan.ch[0].w[f].width; iy.height = plan.ch[0].w[f].height; iy.display_height = plan.display_height;
-		iy.uyvy = out_kind_ == PIX_2VUY; iy.shift = plan.precision - 8; iy.dither_seed = 0x9E3779B9u * (uint32_t)(f + 1);
-		iy.out = d_frames_ + frame_bytes_ * f; iy.out_pitch = pitch_;
+		if (!decode_) continue;
+		// the last level of frame f: the intra path's job of the output's family (DecodeBatch::prepare) on the group's w[f].  Outputs made from 16-bit rows: the YU64
+		// rows of frame f go to the scratch frame
+		const Level1 l1 = level1_of(plan, f, base);
+		uint8_t *out = d_tmp_ ? d_tmp_ + tmp_frame_bytes_ * f : d_frames_ + frame_bytes_ * f;
+		const int out_pitch = d_tmp_ ? tmp_pitch_ : pitch_;
 		// (the matrix of frame 1 is the default one: the P-frame sample that hands it out carries no colour space tag, and the reference converts it with 709 -- pinned)
 		const int matrix = f == 0 ? matrix_ : 0;
-		iy.bottom_up = out_kind_ == PIX_BGRA; iy.matrix_601 = matrix >= 2; iy.masks = nullptr;      // (k_inv_yuv422_rgb32)
-		if (!decode_) continue;
-		// the outputs made from 16-bit rows: the YU64 rows of frame f go to the scratch frame (k_inv_frame_yuv422_rows16(_col) / k_inv_packed16 / k_half_yu64 of v210)
-		uint8_t *rows16 = d_tmp_ ? d_tmp_ + tmp_frame_bytes_ * f : d_frames_ + frame_bytes_ * f;
-		const int rows16_pitch = d_tmp_ ? tmp_pitch_ : pitch_;
-		if (plan.interlaced && d_tmp_) { iy.out = rows16; iy.out_pitch = rows16_pitch; }
-		for (int c = 0; c < 3; c++) {                    // k_inv_packed16: the YU64 words of the three planes (DecodeBatch's job for a 4:2:2 sample, on the group's w[f])
-			const GopWavelet &w = plan.ch[c].w[f];
-			dev::InvPlaneJob &p = j.l1[3 * f + c];
-			memset(&p, 0, sizeof(p));
-			for (int b = 0; b < 4; b++) p.band[b] = base + w.offset[b];
-			p.band_pitch = w.pitch; p.width = w.width; p.height = w.height; p.descale = 0;
-			p.out = dec_plane_out(rows16, PIX_YU64, c); p.out_pitch = rows16_pitch / 2;
-			p.xstride = dec_stride_of_channel(PIX_YU64, c, 3); p.precision = plan.precision; p.display_height = plan.display_height;
+		switch (o.jobs) {
+		case OutJobs::HalfYuv: fill_half_yuv_job(j.half[f], l1, o, rows_, matrix, out, out_pitch); break;
+		case OutJobs::Planes16: fill_planes16_jobs(&j.l1[3 * f], l1, o, 3, 3, plan.precision, plan.display_height, f, out, out_pitch); break;
+		case OutJobs::Yuv: fill_inv_yuv_job(j.iyuv[f], l1, o, plan.precision, plan.display_height, matrix, f, out, out_pitch); break;
+		case OutJobs::HalfPacked: break;                 // (no output of a 4:2:2 sample)
 		}
-		dev::HalfYuvJob &hj = j.half[f];                 // half resolution: the level-1 lowpass plane the temporal inverse left in w[f]
-		for (int c = 0; c < 3; c++) { hj.ll[c] = base + plan.ch[c].w[f].offset[0]; hj.pitch[c] = plan.ch[c].w[f].pitch; }
-		hj.width = plan.ch[0].w[f].width; hj.rows = rows_; hj.uyvy = out_kind_ == PIX_2VUY; hj.matrix = matrix;
-		hj.mode = out_kind_ == PIX_RG24 ? 0 : (out_kind_ == PIX_RG48 ? 2 : (out_kind_ == PIX_B64A ? 3 : 1)); hj.bottom_up = out_kind_ == PIX_BGRA;
-		hj.out = rows16; hj.out_pitch = rows16_pitch;
 	}
 	if (!decode_ && forward_route().l1 == GopFwdL1::Packed16)
 		for (int f = 0; f < 2; f++)
@@ -1672,35 +1621,13 @@ int GopBatch::launch_inverse(uint32_t dither_seed, bool coeffs_on_device)
 	case InvL1::HalfRgb24: dev::k_half_rgb24<<<rows(2, rows_), dev::NTHREADS, 0, st>>>(j.half); break;
 	default: g_err = "two-frame groups: output not served"; return -1;
 	}
-	const int pairs = (half_ ? plan_.width / 2 : plan_.width) / 2;
-	// the colour conversions run over both frames in one launch -- two when frame 0 takes another matrix than frame 1 (fill_jobs); frame 1 alone then runs as z = 0
-	// with the seed that gives it the dither of z = 1
-	auto by_matrix = [&](auto launch) { if (matrix_ == 0) launch(0, 2, 0); else { launch(0, 1, matrix_); launch(1, 1, 0); } };
-	switch (r.convert) {
-	case GopConvert::None: break;
-	case GopConvert::Rgb24:
-		by_matrix([&](int f, int nf, int m) {
-			dev::k_yu64_to_rgb24<<<dim3((unsigned)((pairs + dev::NTHREADS - 1) / dev::NTHREADS), (unsigned)rows_, (unsigned)nf), dev::NTHREADS, 0, st>>>(
-				(const uint16_t *)(d_tmp_ + tmp_frame_bytes_ * f), tmp_pitch_ / 2, tmp_frame_bytes_ / 2, d_frames_ + frame_bytes_ * f, pitch_, frame_bytes_, pairs, rows_, m,
-				dither_seed + 0x9E3779B9u * (uint32_t)f);
-		});
-		break;
-	case GopConvert::Rgb16: {
-		const int mode = out_kind_ == PIX_BGRA ? 3 : (out_kind_ == PIX_BGRa ? 2 : (out_kind_ == PIX_B64A ? 1 : 0));
-		by_matrix([&](int f, int nf, int m) {
-			dev::k_yu64_to_rgb16<<<dim3((unsigned)((pairs + dev::NTHREADS - 1) / dev::NTHREADS), (unsigned)rows_, (unsigned)nf), dev::NTHREADS, 0, st>>>(
-				(const uint16_t *)(d_tmp_ + tmp_frame_bytes_ * f), tmp_pitch_ / 2, tmp_frame_bytes_ / 2, (uint16_t *)(d_frames_ + frame_bytes_ * f), pitch_ / 2, frame_bytes_ / 2,
-				pairs, m >= 2, mode);
-		});
-		break;
-	}
-	case GopConvert::V210: {
-		const int groups = (half_ ? plan_.width / 2 : plan_.width) / 6;
-		dev::k_yu64_to_v210<<<dim3((unsigned)((groups + dev::NTHREADS - 1) / dev::NTHREADS), (unsigned)rows_, 2u), dev::NTHREADS, 0, st>>>(
-			(const uint16_t *)d_tmp_, tmp_pitch_ / 2, tmp_frame_bytes_ / 2, (uint32_t *)d_frames_, pitch_ / 4, frame_bytes_ / 4, groups);
-		break;
-	}
-	}
+	// the conversion runs over both frames in one launch -- two when frame 0 takes another matrix than frame 1 (fill_jobs; v210 takes none); frame 1 alone then runs
+	// as z = 0 with the seed that gives it the dither of z = 1
+	auto convert = [&](int f, int nf, int m) {
+		launch_convert(r.out, d_tmp_, tmp_pitch_, tmp_frame_bytes_, d_frames_, pitch_, frame_bytes_, half_ ? plan_.width / 2 : plan_.width, rows_, f, nf, m,
+		               dither_seed + 0x9E3779B9u * (uint32_t)f, nullptr, st);
+	};
+	if (matrix_ == 0 || r.out.convert == OutConvert::V210) convert(0, 2, 0); else { convert(0, 1, matrix_); convert(1, 1, 0); }
 	HIPCHK(hipGetLastError());
 	return 0;
 }
