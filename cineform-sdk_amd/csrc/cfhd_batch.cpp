@@ -115,12 +115,19 @@ long long batch_finish(cfhd_amd_batch *b)
 {
 	cfhd_amd_chunk *c = b->chunks[0].get();
 	if (c->enc.entropy().download_finish() || c->enc.wait()) return -2;
+	// A frame whose sample does not fit its buffer has size 0 (k_ent_layout) and fails the pass with -3 -- behind the loop: the samples of the other frames are complete
+	// and keep their sizes for cfhd_amd_batch_get_sample, and the decoder's stream, which is parsing these buffers, has drained before the caller gets the batch back.
+	bool overflow = false, peaks = false;
 	for (int l = 0; l < c->n; l++) {
-		size_t n = c->enc.entropy().sample_bytes(l); if (!n) return -3; b->sample_size[c->first + l] = n;
-		if (c->enc.entropy().needs_peak_table(l)) return -8;      // a band with more peak values than the entropy stage's positions hold (two million): only CFHD_EncodeSample writes such a sample (host writer)
+		size_t n = c->enc.entropy().sample_bytes(l); b->sample_size[c->first + l] = n;
+		if (!n) { overflow = true; continue; }
+		if (c->enc.entropy().needs_peak_table(l)) peaks = true;   // a band with more peak values than the entropy stage's positions hold (two million): only CFHD_EncodeSample writes such a sample (host writer)
 	}
 	const double t_enc = now();
-	if (b->decode) { if (c->dec.wait()) return -5; if (c->dec.entropy().check()) return -7; }
+	if (b->decode && c->dec.wait()) return -5;
+	if (overflow) return -3;
+	if (peaks) return -8;
+	if (b->decode && c->dec.entropy().check()) return -7;
 	if (b->decode && b->host_out) {                  // (pictures staged through pinned memory -- a plain buffer -- leave it on a few threads side by side; nothing to do for a registered one)
 		std::atomic<int> bad(0);
 		parallel_for(c->n, c->n > 8 ? 8 : 1, [&](int l) { if (c->dec.finish_frame(l, b->host_out + b->host_out_stride * (size_t)l, b->host_out_pitch)) bad.store(1); });
@@ -271,8 +278,8 @@ static long long cfhd_amd_batch_roundtrip_locked(cfhd_amd_batch *b)
 			t_sub[k] = now();
 			if (c->enc.entropy().download() || c->enc.wait()) return fail(-2);
 			for (int l = 0; l < c->n; l++) {
-				size_t n = c->enc.entropy().sample_bytes(l); if (!n) return fail(-3); b->sample_size[c->first + l] = n;
-				if (c->enc.entropy().needs_peak_table(l)) return fail(-8);      // a band with more peak values than the entropy stage's positions hold (two million): only CFHD_EncodeSample writes such a sample (host writer)
+				size_t n = c->enc.entropy().sample_bytes(l); b->sample_size[c->first + l] = n; if (!n) { fail(-3); continue; }      // (the other frames keep their samples and sizes)
+				if (c->enc.entropy().needs_peak_table(l)) fail(-8);             // a band with more peak values than the entropy stage's positions hold (two million): only CFHD_EncodeSample writes such a sample (host writer)
 			}
 			t_enc[k] = now();
 			if (b->decode) { if (c->dec.wait()) return fail(-5); if (c->dec.entropy().check()) return fail(-7); }
@@ -292,15 +299,20 @@ static long long cfhd_amd_batch_roundtrip_locked(cfhd_amd_batch *b)
 		t1 = now();
 		// 2. as each chunk's samples arrive on the host (the encoder's product), hand them to the decoder and queue its work
 		double wait_s = 0, stage_s = 0;
+		int pass_err = 0;
 		for (auto &c : b->chunks) {
 			double a = now();
 			if (c->enc.entropy().download() || c->enc.wait()) return -2;
+			// (an oversize frame, -3, or one that needs the host writer's peak table, -8, fails the pass behind the loops, as in batch_finish: every frame's size is recorded,
+			// the chunk's pictures are not decoded, the decoders already at work drain)
+			bool undecodable = false;
 			for (int l = 0; l < c->n; l++) {
-				size_t n = c->enc.entropy().sample_bytes(l); if (!n) return -3; b->sample_size[c->first + l] = n;
-				if (c->enc.entropy().needs_peak_table(l)) return -8;
+				size_t n = c->enc.entropy().sample_bytes(l); b->sample_size[c->first + l] = n;
+				if (!n) { if (!pass_err) pass_err = -3; undecodable = true; continue; }
+				if (c->enc.entropy().needs_peak_table(l)) { if (!pass_err) pass_err = -8; undecodable = true; }
 			}
 			double m = now();
-			if (!b->decode) { wait_s += m - a; continue; }
+			if (!b->decode || undecodable) { wait_s += m - a; continue; }
 			cfhd_amd_chunk *cp = c.get();
 			parallel_for(c->n, b->nthreads < 16 ? b->nthreads : 16, [&, cp](int l) {
 				if (cp->dec.entropy().set_sample_host(l, cp->enc.entropy().host_sample(l), b->sample_size[cp->first + l])) bad++; });
@@ -310,7 +322,8 @@ static long long cfhd_amd_batch_roundtrip_locked(cfhd_amd_batch *b)
 		}
 		t2 = t1 + wait_s; t3 = t2 + stage_s;
 		// 3. drain
-		if (b->decode) for (auto &c : b->chunks) { if (c->dec.wait()) return -5; if (c->dec.entropy().check()) return -7; }
+		if (b->decode) for (auto &c : b->chunks) { if (c->dec.wait()) return -5; if (!pass_err && c->dec.entropy().check()) return -7; }
+		if (pass_err) return pass_err;
 	} else {
 		cfhd_amd_chunk &c = *b->chunks[0];
 		prepare_meta();

@@ -69,13 +69,14 @@ __device__ __forceinline__ uint32_t pk_to8(uint32_t v, int shift, uint32_t dithe
 }
 __device__ __forceinline__ uint32_t byte_perm(uint32_t s0, uint32_t s1, uint32_t sel) { return __builtin_amdgcn_perm(s0, s1, sel); }
 // 10 -> 8 bits of four neighbouring samples: e = (s0, s2), o = (s1, s3) as 16-bit lanes before the last >> 1, d2e / d2o = twice the dither bit of each lane (bit 1, bit 17),
-// shift1 = shift + 1 (<= 7).  Equal to pk_to8 on both words, bytes in sample order: ((v >> 1) + d) >> shift = (v + 2 d) >> (shift + 1) for v >= 0, a negative v stays <= 0
-// through the saturating add and the arithmetic shift, and v_sat_pk_u8_i16 clamps each lane to 0 .. 255 while packing -- three instructions a word instead of five, one v_perm
-// instead of a shift and an or.
+// shift1 = shift + 1 (<= 7).  Equal to pk_to8 on both words, bytes in sample order: ((v >> 1) + d) >> shift = (v + 2 d) >> (shift + 1) for v >= 0, the saturating add
+// keeps v + 2 d at 32767 (>= 255 after any shift1 <= 7), and v_sat_pk_u8_i16 clamps each lane to 0 .. 255 while packing -- four instructions a word instead of five,
+// one v_perm instead of a shift and an or.  The clamp at zero comes first, as in pk_to8: without it a negative v with its dither bit set gives (v + 2) >> 1 <= 0 at
+// shift1 = 1 (8-bit precision samples) where pk_to8 gives (0 + 1) >> 0 = 1 (tests/test_gpu_primitives.py runs both over the whole int16 range).
 __device__ __forceinline__ uint32_t sat_pk_u8(uint32_t v) { uint32_t r; asm("v_sat_pk_u8_i16 %0, %1" : "=v"(r) : "v"(v)); return r; }
 __device__ __forceinline__ uint32_t pk_to8_bytes(uint32_t e, uint32_t o, int shift1, uint32_t d2e, uint32_t d2o)
 {
-	e = pk_sra(pk_adds(e, d2e), shift1); o = pk_sra(pk_adds(o, d2o), shift1);
+	e = pk_sra(pk_adds(pk_maxs(e, 0u), d2e), shift1); o = pk_sra(pk_adds(pk_maxs(o, 0u), d2o), shift1);
 	return __builtin_amdgcn_perm(sat_pk_u8(o), sat_pk_u8(e), 0x05010400u);
 }
 __device__ __forceinline__ uint32_t rotr32(uint32_t w, uint32_t n) { return __builtin_amdgcn_alignbit(w, w, n); }   // n < 32

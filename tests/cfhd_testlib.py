@@ -462,6 +462,46 @@ def hooks():
     return _hooks
 
 
+PRIMS_SRC = os.path.join(ROOT, "tests", "gpu_prims", "prims.hip")
+PRIMS_SO = os.path.join(ROOT, "tests", "_build", "libcfhd_prims.so")
+PRIMS_EMU_SO = os.path.join(ROOT, "tests", "_build", "libcfhd_prims_hipemu.so")
+_prims = {}
+
+
+def gfx950_prims_build():
+    """Test-only library: tests/gpu_prims/prims.hip (one C entry per primitive of cfhd_gfx950.h) compiled by hipcc for gfx950 over the product's own header.
+    Not part of libcfhd_amd.so.  Compiles without a GPU; __graft_entry__.build() calls this so that the library travels with the tree."""
+    csrc = os.path.join(PRODUCT_DIR, "csrc")
+    deps = [PRIMS_SRC, os.path.join(csrc, "cfhd_gfx950.h")]
+    if not os.path.exists(PRIMS_SO) or any(os.path.getmtime(d) > os.path.getmtime(PRIMS_SO) for d in deps):
+        os.makedirs(os.path.dirname(PRIMS_SO), exist_ok=True)
+        _build_once(PRIMS_SO, ["hipcc", "--offload-arch=gfx950", "-O2", "-std=c++17", "-fPIC", "-shared", "-I" + csrc, PRIMS_SRC], deps)
+    return PRIMS_SO
+
+
+def gfx950_prims(emulated=False):
+    """The primitives' test library: the hardware build (needs a GPU to run) or, emulated=True, the same source compiled by g++ over tests/hipemu (the scalar twin header,
+    launches rewritten by translate_launches.py, as product_emulated does)."""
+    if emulated not in _prims:
+        if emulated:
+            hipemu = os.path.join(ROOT, "tests", "hipemu")
+            deps = [PRIMS_SRC] + [os.path.join(hipemu, f) for f in ("hip_emu.h", "cfhd_gfx950.h", "emu_runtime.cpp", "translate_launches.py")] + [os.path.join(hipemu, "hip", "hip_runtime.h")]
+            if not os.path.exists(PRIMS_EMU_SO) or any(os.path.getmtime(d) > os.path.getmtime(PRIMS_EMU_SO) for d in deps):
+                gen = os.path.join(ROOT, "tests", "_build", "hipemu_prims"); os.makedirs(gen, exist_ok=True)
+                sys.path.insert(0, hipemu)
+                from translate_launches import translate
+                sys.path.pop(0)
+                out = os.path.join(gen, "prims.%d.cpp" % os.getpid())
+                with open(out, "w") as fh: fh.write("// generated from tests/gpu_prims/prims.hip by tests/hipemu/translate_launches.py -- test infrastructure\n" + translate(open(PRIMS_SRC).read()))
+                _build_once(PRIMS_EMU_SO, ["g++", "-O1", "-w", "-std=c++17", "-fPIC", "-shared", "-pthread", "-I" + hipemu, os.path.join(hipemu, "emu_runtime.cpp"), out], deps)
+                os.replace(out, os.path.join(gen, "prims.cpp"))
+            os.environ.setdefault("HIPEMU_DEVICES", "4")
+            _prims[emulated] = ctypes.CDLL(PRIMS_EMU_SO)
+        else:
+            _prims[emulated] = ctypes.CDLL(gfx950_prims_build())
+    return _prims[emulated]
+
+
 class Plan:
     """Python view of cfhd::FramePlan (geometry + quantizer) as the product derives it."""
 

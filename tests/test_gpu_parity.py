@@ -73,7 +73,10 @@ def test_encode_matches_golden_small_fixture():
     assert mask_volatile_metadata(mine) == mask_volatile_metadata(want)
 
 
-def _check_decode(sample, source, w, h, pixfmt=PIX_YUY2, interlaced=False, decoder=None):
+def _check_decode(sample, source, w, h, pixfmt=PIX_YUY2, interlaced=False, decoder=None, reference_psnr=True):
+    """reference_psnr=False drops one thing only, the comparison of the product's PSNR with that of ONE run of the reference's rand() dither (for pictures in which the
+    dither can move so few bytes that two runs of the reference differ by more than the 0.1 dB themselves: tests/hostile_pictures.py PSNR_WITNESS_MIN_MOVABLE); the
+    reference's picture must still lie in the interval."""
     out, pitch, aw, ah = amd_decode_sample(sample, pixfmt, decoder=decoder)
     assert (aw, ah) == (w, h)
     img = out.reshape(ah, pitch)[:, : w * 2]
@@ -96,7 +99,7 @@ def _check_decode(sample, source, w, h, pixfmt=PIX_YUY2, interlaced=False, decod
         rimg = rout.reshape(h, rpitch)[:, : w * 2]
         if not ((rimg == lo) | (rimg == hi)).all(): return "the reference's own output leaves the dither interval"
         d = abs(mine_db - psnr_yuy2(rimg, src))
-        return d < 0.1 or "PSNR differs by %.2f dB" % d
+        return d < 0.1 or not reference_psnr or "PSNR differs by %.2f dB" % d
     reference_leg(leg, 3, "4:2:2 -> 8-bit 4:2:2")
     return img
 

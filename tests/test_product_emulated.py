@@ -10,7 +10,7 @@ Test infrastructure only: nothing here is a product path (the product has no CPU
 import itertools, os
 import pytest
 from cfhd_testlib import *
-import test_gpu_parity, test_gpu_gop
+import test_gpu_parity, test_gpu_gop, test_gpu_hostile
 
 pytestmark = pytest.mark.skipif(not have_ref(), reason="oracle/_ref/libcfhd_ref.so is not built")
 
@@ -44,7 +44,7 @@ def _cases(module):
     return out
 
 
-@pytest.mark.parametrize("module,name,kw", _cases(test_gpu_parity) + _cases(test_gpu_gop))
+@pytest.mark.parametrize("module,name,kw", _cases(test_gpu_parity) + _cases(test_gpu_gop) + _cases(test_gpu_hostile))
 def test_on_the_emulated_product(module, name, kw):
     with emulated_product():
         getattr(module, name)(**kw)
