@@ -101,7 +101,7 @@ int batch_launch(cfhd_amd_batch *b)
 		if (ordered_decode && stage_order_wait(c->enc.device(), 1, c->dec.stream())) return -5;
 		// the parser only needs the headers and size fields (k_ent_layout): it runs beside k_ent_emit, the band decoder waits for the payloads
 		c->dec.entropy().set_producer_events(c->enc.entropy().headers_event(), c->enc.entropy().samples_event());
-		if (c->dec.entropy().set_samples_device(c->enc.entropy().device_sample(0), c->enc.entropy().sample_cap(), c->enc.entropy().device_sizes())) return -4;
+		if (c->dec.entropy().set_samples_device(c->enc.entropy().device_samples(), 0, c->enc.entropy().device_sizes(), c->enc.entropy().device_offsets())) return -4;
 		if (c->dec.launch_entropy() || c->dec.launch_inverse(seed + (uint32_t)c->first)) return -5;
 		if (ordered_decode && stage_order_done(c->enc.device(), 1, c->dec.stream())) return -5;
 		if (b->host_out && c->dec.download_frames(b->host_out, b->host_out_stride, b->host_out_pitch)) return -5;      // the pictures' copies behind the inverse transform, on the decoder's stream
@@ -272,7 +272,7 @@ static long long cfhd_amd_batch_roundtrip_locked(cfhd_amd_batch *b)
 			if (b->decode) {
 				// the parser only needs the headers and size fields (k_ent_layout): it runs beside k_ent_emit, the band decoder waits for the payloads
 				c->dec.entropy().set_producer_events(c->enc.entropy().headers_event(), c->enc.entropy().samples_event());
-				if (c->dec.entropy().set_samples_device(c->enc.entropy().device_sample(0), c->enc.entropy().sample_cap(), c->enc.entropy().device_sizes())) return fail(-4);
+				if (c->dec.entropy().set_samples_device(c->enc.entropy().device_samples(), 0, c->enc.entropy().device_sizes(), c->enc.entropy().device_offsets())) return fail(-4);
 				if (c->dec.launch_entropy() || c->dec.launch_inverse(seed + (uint32_t)c->first)) return fail(-5);
 			}
 			t_sub[k] = now();

@@ -37,14 +37,16 @@ public:
 	// A sample beyond gop_sample_may_zero_bands() is not valid (the reference zeroes bands there, encoder.c:8332): the caller writes it on the host.
 	int prepare_group(const GopPlan &plan, int ngroups, int16_t *d_coeffs, size_t coeff_stride_elems, size_t sample_cap, void *stream);
 	void set_group_plan(const GopPlan &plan) { gplan_ = plan; }
-	int launch();                                                    // async: templates H2D + 4 kernels
-	int download();                                                  // sizes + packed offsets -> sync -> one async copy of all sample bytes (wait on the stream afterwards)
+	int launch();                                                    // async: templates H2D + the kernels; leaves the samples densely in HBM
+	int download();                                                  // sizes + offsets -> sync -> one async copy of all sample bytes (wait on the stream afterwards)
 	int download_queue();                                            // the two halves of download(): what can be queued behind launch() without the host ...
 	int download_finish();                                           // ... and what needs the sizes on the host (synchronises the stream, queues the copy of the sample bytes)
 	int fetch_sizes();                                               // sizes only (device-resident consumers); synchronises the stream
 	const uint32_t *device_sizes() const { return d_sizes_; }
 	const uint8_t *host_sample(int i) const { return h_samples_ + h_offsets_[i]; }   // after download() + stream wait
-	uint8_t *device_sample(int i) { return d_samples_ + (size_t)i * cap_; }
+	// the samples in HBM after launch(): sample i at device_samples() + device_offsets()[i] (64-byte aligned, dense, in frame order), device_sizes()[i] bytes
+	const uint8_t *device_samples() const { return d_packed_; }
+	const uint32_t *device_offsets() const { return d_offsets_; }
 	uint32_t sample_bytes(int i) const { return h_sizes_[i]; }
 	// the next launch() / download() cover frames 0 .. k-1 of the batch (0 = all)
 	void set_active(int k) { active_ = k; }
@@ -58,7 +60,7 @@ public:
 	size_t sample_cap() const { return cap_; }
 	int total_segments() const { return total_segs_; }
 	// HIP-event time of kernel k of the last launch() (0 k_ent_count -- when the level-1 bands are counted on the second stream: the launches on the main stream
-	// only --, 1 k_ent_scan, 2 k_ent_layout, 3 k_ent_emit, 4 the level-1 part of k_ent_count on the second stream, 0 when there is none); valid once the stream was synchronised
+	// only --, 1 k_ent_scan, 2 k_ent_sizes + k_ent_pack_offsets + k_ent_layout, 3 k_ent_emit, 4 the level-1 part of k_ent_count on the second stream, 0 when there is none); valid once the stream was synchronised
 	float kernel_ms(int k);
 	// Events of the last launch() on the encoder's stream: every sample's header, size fields and raw lowpass bands are in place
 	// (k_ent_layout done) / the samples are complete (k_ent_emit done).  A consumer on another stream can parse behind the first.
@@ -83,9 +85,9 @@ private:
 	int active_frames() const { return active_ > 0 && active_ < n_ ? active_ : n_; }
 	int nbands_ = 0, total_segs_ = 0; size_t tok_per_frame_ = 0;
 	std::vector<SampleTemplate> tmpl_;
-	uint8_t *d_samples_ = nullptr, *h_samples_ = nullptr;
+	uint8_t *h_samples_ = nullptr;
 	uint32_t *d_sizes_ = nullptr, *h_sizes_ = nullptr;
-	uint8_t *d_packed_ = nullptr; uint32_t *d_offsets_ = nullptr, *h_offsets_ = nullptr;   // dense copy of the samples for the D2H transfer
+	uint8_t *d_packed_ = nullptr; uint32_t *d_offsets_ = nullptr, *h_offsets_ = nullptr;   // the samples, dense: written there by k_ent_layout / k_ent_emit, read by the D2H transfer and the decoder
 	size_t expect_bytes_ = 0, copied_ahead_ = 0; int expect_frames_ = 0; bool speculative_download_ = false;      // download_queue(): the copy sized by the last pass (set_speculative_download)
 	void *d_tables_ = nullptr, *d_bands_ = nullptr, *d_segband_ = nullptr, *d_segs_ = nullptr, *d_bandstate_ = nullptr, *d_frames_ = nullptr, *d_tokens_ = nullptr;
 	uint8_t *d_tmpl_ = nullptr, *h_tmpl_ = nullptr;
@@ -113,9 +115,10 @@ public:
 	int set_sample_host(int i, const uint8_t *sample, size_t size);
 	// Sample bytes already in HBM at d_sample; host_copy (same bytes) is only parsed for the band offsets.
 	int set_sample_device(int i, const uint8_t *d_sample, const uint8_t *host_copy, size_t size);
-	// All n samples already in HBM (sample i at d_samples + i * stride_bytes, its size in d_sizes[i]): nothing touches the host,
-	// k_dec_parse walks the tag streams on the GPU.  Stays in force until a set_sample_host()/set_sample_device() call.
-	int set_samples_device(const uint8_t *d_samples, size_t stride_bytes, const uint32_t *d_sizes);
+	// All n samples already in HBM (sample i at d_samples + i * stride_bytes -- or, with d_offsets (device memory, multiples of 4, read when the parser runs), at
+	// d_samples + d_offsets[i]: GpuEntropyEncoder's dense buffer --, its size in d_sizes[i]): nothing touches the host, k_dec_parse walks the tag streams on the GPU.
+	// Stays in force until a set_sample_host()/set_sample_device() call.
+	int set_samples_device(const uint8_t *d_samples, size_t stride_bytes, const uint32_t *d_sizes, const uint32_t *d_offsets = nullptr);
 	// Optional, for device-resident samples still being written by another stream: the next launch() lets k_dec_parse wait for
 	// `headers` only (it reads the tag stream, not the coded payloads) and the band decoder for `payloads`.
 	void set_producer_events(void *headers, void *payloads) { ev_headers_ = headers; ev_payloads_ = payloads; }
@@ -145,7 +148,7 @@ private:
 	bool skip_level1_ = false, interlaced_ = false; void *d_diffjobs_ = nullptr;
 	int active_ = 0;
 	int active_frames() const { return active_ > 0 && active_ < n_ ? active_ : n_; }
-	const uint8_t *ext_samples_ = nullptr; size_t ext_stride_ = 0; const uint32_t *ext_sizes_ = nullptr;   // set_samples_device()
+	const uint8_t *ext_samples_ = nullptr; size_t ext_stride_ = 0; const uint32_t *ext_sizes_ = nullptr, *ext_offsets_ = nullptr;   // set_samples_device()
 	int *d_errors_ = nullptr, *h_errors_ = nullptr;
 	bool lane_kernel_ = false;
 	// cfhd_dec_kernels.h (default): chunk index + tile decode.  CFHD_AMD_DEC=par / lane select the round-1 kernels for A/B runs.

@@ -22,7 +22,7 @@ GpuEntropyEncoder::~GpuEntropyEncoder() { release(); delete host_; }
 void GpuEntropyEncoder::release()
 {
 	(void)hipSetDevice(device_);
-	void *dev[] = { d_samples_, d_sizes_, d_tables_, d_bands_, d_segband_, d_segs_, d_bandstate_, d_frames_, d_tmpl_, d_packed_, d_offsets_, d_tokens_, d_blocks_, d_masks_ };
+	void *dev[] = { d_sizes_, d_tables_, d_bands_, d_segband_, d_segs_, d_bandstate_, d_frames_, d_tmpl_, d_packed_, d_offsets_, d_tokens_, d_blocks_, d_masks_ };
 	for (void *p : dev) if (p) (void)hipFree(p);
 	if (h_samples_) (void)hipHostFree(h_samples_);
 	if (h_sizes_) (void)hipHostFree(h_sizes_);
@@ -34,7 +34,7 @@ void GpuEntropyEncoder::release()
 	for (void *&e : ev2_) if (e) { (void)hipEventDestroy((hipEvent_t)e); e = nullptr; }
 	if (stream2_) { device_stream_destroy(stream2_); stream2_ = nullptr; }
 	timed_ = false;
-	d_samples_ = h_samples_ = nullptr; d_sizes_ = h_sizes_ = nullptr; d_tables_ = d_bands_ = d_segband_ = d_segs_ = d_bandstate_ = d_frames_ = d_tokens_ = nullptr;
+	h_samples_ = nullptr; d_sizes_ = h_sizes_ = nullptr; d_tables_ = d_bands_ = d_segband_ = d_segs_ = d_bandstate_ = d_frames_ = d_tokens_ = nullptr;
 	d_tmpl_ = h_tmpl_ = nullptr; n_ = 0;
 	d_blocks_ = nullptr; d_masks_ = nullptr; masks_per_frame_ = 0; use_blocks_ = false;
 }
@@ -101,12 +101,13 @@ int GpuEntropyEncoder::prepare_units(int nframes, int16_t *d_coeffs, size_t stri
 		HIPCHK(hipMalloc((void **)&d_masks_, masks_per_frame_ * 8 * (size_t)n_ + 64));      // (+ spare entries: the inverse kernel fetches the masks of two chunks at a time)
 		HIPCHK(hipMemset(d_masks_, 0, masks_per_frame_ * 8 * (size_t)n_ + 64));
 	}
-	HIPCHK(hipMalloc((void **)&d_samples_, cap_ * n_));
 	HIPCHK(hipHostMalloc((void **)&h_samples_, cap_ * n_, hipHostMallocPortable));
 	HIPCHK(hipMalloc((void **)&d_sizes_, sizeof(uint32_t) * 2 * n_));                   // [n] sample sizes, [n] peak flags
 	HIPCHK(hipHostMalloc((void **)&h_sizes_, sizeof(uint32_t) * 2 * n_, hipHostMallocPortable));
 	memset(h_sizes_, 0, sizeof(uint32_t) * 2 * n_);
-	HIPCHK(hipMalloc((void **)&d_packed_, cap_ * n_));
+	// the samples, densely: every one at its 64-byte aligned offset (none is longer than cap_, a multiple of 256) + the rest of the last 256-byte window a parser of the
+	// last sample's tags may fetch (k_dec_parse)
+	HIPCHK(hipMalloc((void **)&d_packed_, cap_ * n_ + 256));
 	HIPCHK(hipMalloc((void **)&d_offsets_, sizeof(uint32_t) * (n_ + 1)));
 	HIPCHK(hipHostMalloc((void **)&h_offsets_, sizeof(uint32_t) * (n_ + 1), hipHostMallocPortable));
 	memset(h_offsets_, 0, sizeof(uint32_t) * (n_ + 1));
@@ -130,7 +131,7 @@ int GpuEntropyEncoder::set_frame_header(int f, const SampleHeaderInfo &hdr)
 	SampleTemplate &t = tmpl_[f];
 	build_template(hdr, &t);
 	if (!ent_fill_frame_block(host_->geom, t, f, host_->jobs, d_coeffs_ + (size_t)f * coeff_stride_, h_tmpl_ + (size_t)kEntTmplStride * f)) return -4;
-	host_->frames[f] = ent_frame_job(t, d_tmpl_ + (size_t)kEntTmplStride * f, d_samples_ + cap_ * f, (uint32_t)cap_, d_sizes_ + f, d_sizes_ + n_ + f);
+	host_->frames[f] = ent_frame_job(t, d_tmpl_ + (size_t)kEntTmplStride * f, d_packed_, (uint32_t)cap_, d_sizes_ + f, d_sizes_ + n_ + f, d_offsets_ + f);
 	dirty_ = true;
 	return 0;
 }
@@ -195,6 +196,9 @@ int GpuEntropyEncoder::launch()
 	HIPCHK(hipEventRecord((hipEvent_t)ev_[1], st));
 	dev::k_ent_scan<<<nbands_ * act, dev::ENT_THREADS, 0, st>>>((const dev::EntBandJob *)d_bands_, (dev::EntSegState *)d_segs_, (dev::EntBandState *)d_bandstate_, T);
 	HIPCHK(hipEventRecord((hipEvent_t)ev_[2], st));
+	// every sample's size and its place in the dense buffer follow from what the scan left: nothing is written anywhere else, nothing is copied afterwards
+	dev::k_ent_sizes<<<(act + dev::ENT_WAVES - 1) / dev::ENT_WAVES, dev::ENT_THREADS, 0, st>>>((const dev::EntFrameJob *)d_frames_, act, (const dev::EntBandState *)d_bandstate_);
+	dev::k_ent_pack_offsets<<<1, dev::ENT_THREADS, 0, st>>>(d_sizes_, act, d_offsets_);
 	// workgroups per frame: enough to fill the chip for short batches of large frames, at least the 8 that 512 1080p frames were tuned with
 	const unsigned layout_parts = act >= 256 ? 8u : (unsigned)((2048 + act - 1) / act > 256 ? 256 : (2048 + act - 1) / act);
 	dev::k_ent_layout<<<dim3((unsigned)act, layout_parts), dev::ENT_THREADS, 0, st>>>((const dev::EntFrameJob *)d_frames_, (const dev::EntBandJob *)d_bands_, (dev::EntSegState *)d_segs_,
@@ -245,18 +249,15 @@ int GpuEntropyEncoder::fetch_sizes()
 
 int GpuEntropyEncoder::download() { const int rc = download_queue(); return rc ? rc : download_finish(); }
 
-// The part of download() that can be queued behind the kernels without the host: the dense copy of the samples in HBM, sizes and offsets on their way to the host.
+// The part of download() that can be queued behind the kernels without the host: sizes and offsets on their way to the host, the samples -- written densely in HBM by
+// launch() -- behind them.
 int GpuEntropyEncoder::download_queue()
 {
 	(void)hipSetDevice(device_);
 	hipStream_t st = (hipStream_t)stream_;
-	// pack in HBM, then one copy (SDMA engine when the runtime has it enabled)
-	const bool direct = false;      // (k_ent_pack storing straight into the pinned host buffer: measured slower than pack + one SDMA copy in round 2)
-	(void)hipGetLastError();
+	// one copy out of HBM (SDMA engine when the runtime has it enabled)
+	const bool direct = false;      // (the kernels storing straight into the pinned host buffer: measured slower than dense samples in HBM + one SDMA copy in round 2)
 	const int act = active_frames();
-	dev::k_ent_pack_offsets<<<1, dev::ENT_THREADS, 0, st>>>(d_sizes_, act, d_offsets_);
-	dev::k_ent_pack<<<dim3(direct ? 2 : 8, (unsigned)act), dev::ENT_THREADS, 0, st>>>(d_samples_, cap_, d_sizes_, d_offsets_, direct ? h_samples_ : d_packed_);
-	HIPCHK(hipGetLastError());
 	HIPCHK(hipMemcpyAsync(h_sizes_, d_sizes_, sizeof(uint32_t) * 2 * n_, hipMemcpyDeviceToHost, st));
 	HIPCHK(hipMemcpyAsync(h_offsets_, d_offsets_, sizeof(uint32_t) * (act + 1), hipMemcpyDeviceToHost, st));
 	// The copy of the sample bytes needs their number, which the host learns when the sizes arrive (download_finish()).  A pass that is queued as a whole
@@ -397,10 +398,12 @@ int GpuEntropyDecoder::prepare(const FramePlan &plan, int nframes, int16_t *d_co
 	return 0;
 }
 
-int GpuEntropyDecoder::set_samples_device(const uint8_t *d_samples, size_t stride_bytes, const uint32_t *d_sizes)
+int GpuEntropyDecoder::set_samples_device(const uint8_t *d_samples, size_t stride_bytes, const uint32_t *d_sizes, const uint32_t *d_offsets)
 {
-	if (!d_samples || !d_sizes || (stride_bytes & 255) || ((uintptr_t)d_samples & 255)) return -1;   // k_dec_parse reads aligned 256-byte windows (a slot must extend to the window that holds its last tag)
-	ext_samples_ = d_samples; ext_stride_ = stride_bytes; ext_sizes_ = d_sizes;
+	// k_dec_parse reads windows of 256 bytes counted from the sample's start, longword by longword: a slot must extend to the window that holds its last tag, the buffer
+	// behind dense samples to the last sample's (every other window ends inside the next sample)
+	if (!d_samples || !d_sizes || ((uintptr_t)d_samples & 255) || (!d_offsets && (stride_bytes & 255))) return -1;
+	ext_samples_ = d_samples; ext_stride_ = stride_bytes; ext_sizes_ = d_sizes; ext_offsets_ = d_offsets;
 	return 0;
 }
 
@@ -455,7 +458,7 @@ int GpuEntropyDecoder::launch()
 		HIPCHK(hipEventRecord((hipEvent_t)ev_[0], st));
 		dev::k_dec_parse<<<n_, dev::DEC_PARSE_THREADS, 0, st>>>(ext_samples_, ext_stride_, ext_sizes_, n_,
 			(const dev::DecPlan *)d_plan_, d_coeffs_, coeff_stride_, (dev::DecBandJob *)d_bandjobs_, (dev::DecLowpassJob *)d_lowjobs_, d_errors_,
-			interlaced_ && dx_ ? (dev::DecDiffJob *)d_diffjobs_ : nullptr);
+			interlaced_ && dx_ ? (dev::DecDiffJob *)d_diffjobs_ : nullptr, ext_offsets_);
 		parse_end_ = ev_payloads_ != nullptr;
 		if (parse_end_) { HIPCHK(hipEventRecord((hipEvent_t)ev_[4], st)); HIPCHK(hipStreamWaitEvent(st, (hipEvent_t)ev_payloads_, 0)); }
 		ev_headers_ = ev_payloads_ = nullptr;

@@ -339,11 +339,12 @@ inline bool ent_fill_frame_block(const FramePlan &plan, const SampleTemplate &t,
 	return ent_fill_frame_block(ent_hole_geometry(plan, t), t, f, jobs, coeffs_f, block);
 }
 
-// Frame job whose pointers refer to `block_addr` (the device -- or, under emulation, host -- address of the serialised block).
-inline dev::EntFrameJob ent_frame_job(const SampleTemplate &t, uint8_t *block_addr, uint8_t *out, uint32_t out_cap, uint32_t *size_out, uint32_t *peak_flag)
+// Frame job whose pointers refer to `block_addr` (the device -- or, under emulation, host -- address of the serialised block).  dense_off: where the device finds the
+// sample's offset behind `out` (the dense buffer of a batch: k_ent_pack_offsets); null: the sample starts at `out`.
+inline dev::EntFrameJob ent_frame_job(const SampleTemplate &t, uint8_t *block_addr, uint8_t *out, uint32_t out_cap, uint32_t *size_out, uint32_t *peak_flag, const uint32_t *dense_off = nullptr)
 {
 	dev::EntFrameJob fj;
-	fj.out = out; fj.out_cap = out_cap;
+	fj.out = out; fj.out_cap = out_cap; fj.dense_off = dense_off;
 	fj.tmpl = block_addr; fj.tmpl_bytes = (int)t.bytes.size();
 	fj.word_holes = block_addr + kEntTmplBytes;
 	fj.holes = (const dev::EntHole *)(block_addr + kEntTmplBytes + kEntWordHolesBytes); fj.nholes = (int)t.holes.size();

@@ -4,8 +4,9 @@
 //
 //   k_ent_count   one workgroup per 2048-coefficient segment: zero-run structure + bits of the tokens that start in it
 //   k_ent_scan    one workgroup per band: previous-nonzero max-scan and bit-offset sum-scan over its segments, band size
+//   k_ent_sizes   one wave per frame: the sample's size from the bands' sizes; k_ent_pack_offsets: the samples' 64-byte aligned places in one dense buffer
 //   k_ent_layout  one workgroup per frame: payload offsets, header template copy, size-field patches, raw lowpass words,
-//                 payload zeroing, trailing zero run + band end marker
+//                 payload zeroing, trailing zero run + band end marker -- at the sample's place in the dense buffer
 //   k_ent_emit    one workgroup per segment: code words assembled in LDS (atomic OR), whole words stored big-endian
 //
 // A token = the zero run in front of a nonzero coefficient (greedy composite run codes, encoder.c:5488-5545) followed by
@@ -128,6 +129,7 @@ struct EntFrameJob {
 	const EntPatch *patches; int npatches;
 	uint32_t *sample_bytes;                    // out: size of the finished sample (0 on overflow)
 	uint32_t *peak_flag;                       // the frame's word of peak_flags[] (see ENT_PEAK_THRESHOLD)
+	const uint32_t *dense_off;                 // null: the sample starts at out; else at out + *dense_off (k_ent_pack_offsets: the samples of a batch lie densely behind `out`)
 };
 
 __device__ __forceinline__ uint32_t bswap32(uint32_t v) { return (v >> 24) | ((v >> 8) & 0xff00u) | ((v << 8) & 0xff0000u) | (v << 24); }
@@ -586,6 +588,40 @@ __device__ __forceinline__ void put_code_plain(uint32_t *words, uint64_t pos, ui
 }
 
 // =============================================================================================
+// The size of a frame's sample, known once k_ent_scan has left every band's payload_bytes and npeaks -- before a sample byte is written.  One wave: lane h fetches
+// the size of hole h (the loads overlap), a prefix sum over the lanes.  Returns the sample's bytes to every lane; *hole_bytes: this lane's hole, *cum_incl: the holes
+// up to and including it.
+__device__ __forceinline__ uint32_t ent_sample_size(const EntFrameJob &f, const EntBandState *band_state, int lane, uint32_t *hole_bytes, uint32_t *cum_incl)
+{
+	uint32_t bytes = 0;
+	if (lane < f.nholes) {
+		const EntHole &hole = f.holes[lane];
+		if (hole.kind == 0) bytes = (uint32_t)hole.fixed_bytes;
+		else if (hole.kind == 1) bytes = band_state[hole.band_job].payload_bytes;
+		else {
+			// the peak table of the band in front: chunk header + 16-bit values padded to a whole longword (encoder.c:6543-6585); nothing without peaks
+			const uint32_t np = band_state[hole.band_job].npeaks;
+			bytes = (np && np <= (uint32_t)ENT_PEAK_TABLE_MAX) ? 4u + 4u * ((np + 1u) >> 1) : 0u;      // (more than the chunk header can count: no table, as the reference)
+		}
+	}
+	const uint32_t cum = wave_incl_scan(bytes);
+	*hole_bytes = bytes; *cum_incl = cum;
+	return (uint32_t)f.tmpl_bytes + wave_get(cum, 63);
+}
+
+// One wave per frame, behind k_ent_scan: the sample sizes (0: the sample does not fit its buffer and takes no room).  k_ent_pack_offsets turns them into the
+// samples' places in the dense buffer, where k_ent_layout and k_ent_emit write them.
+__global__ void __launch_bounds__(ENT_THREADS) k_ent_sizes(const EntFrameJob *frames, int nframes, const EntBandState *band_state)
+{
+	const int fr = wave_uniform((int)(blockIdx.x * ENT_WAVES + (threadIdx.x >> 6)));
+	if (fr >= nframes) return;
+	const EntFrameJob &f = frames[fr];
+	uint32_t bytes, cum;
+	const uint32_t total = ent_sample_size(f, band_state, wave_lane(), &bytes, &cum);
+	if (wave_lane() == 0) *f.sample_bytes = total <= f.out_cap ? total : 0u;
+}
+
+// =============================================================================================
 __global__ void __launch_bounds__(ENT_THREADS) k_ent_layout(const EntFrameJob *frames, const EntBandJob *bands, EntSegState *segs,
                                                              EntBandState *band_state, const EntTables *tables)
 {
@@ -599,27 +635,17 @@ __global__ void __launch_bounds__(ENT_THREADS) k_ent_layout(const EntFrameJob *f
 	__shared__ int s_ok;
 	const int tid = threadIdx.x;
 	if (tid < 64) {
-		// one wave: every lane fetches the size of one hole (the loads overlap), two prefix sums over the lanes
-		uint32_t bytes = 0;
-		if (tid < f.nholes) {
-			const EntHole &hole = f.holes[tid];
-			if (hole.kind == 0) bytes = (uint32_t)hole.fixed_bytes;
-			else if (hole.kind == 1) bytes = band_state[hole.band_job].payload_bytes;
-			else {
-				// the peak table of the band in front: chunk header + 16-bit values padded to a whole longword (encoder.c:6543-6585); nothing without peaks
-				const uint32_t np = band_state[hole.band_job].npeaks;
-				bytes = (np && np <= (uint32_t)ENT_PEAK_TABLE_MAX) ? 4u + 4u * ((np + 1u) >> 1) : 0u;      // (more than the chunk header can count: no table, as the reference)
-			}
-		}
+		uint32_t bytes, cum;
+		const uint32_t total = ent_sample_size(f, band_state, tid, &bytes, &cum);
 		const uint32_t pieces = tid < f.nholes ? (bytes / ENT_FILL ? bytes / ENT_FILL : 1u) : 0u;
-		const uint32_t cum = wave_incl_scan(bytes), pc = wave_incl_scan(pieces);
+		const uint32_t pc = wave_incl_scan(pieces);
 		if (tid <= f.nholes && tid <= ENT_MAX_HOLES) { s_cum[tid] = cum - bytes; s_piece[tid] = pc - pieces; }
-		const uint32_t total = (uint32_t)f.tmpl_bytes + wave_get(cum, 63);
 		if (tid == 0) { s_ok = total <= f.out_cap; if (part == 0) *f.sample_bytes = total <= f.out_cap ? total : 0u; }
 	}
 	__syncthreads();
 	if (!s_ok) return;                                   // uniform: the whole workgroup leaves
-	uint32_t *out = (uint32_t *)f.out;
+	uint8_t *const fout = f.out + (f.dense_off ? *f.dense_off : 0u);      // (k_ent_pack_offsets ran in front: every frame's place follows from the sizes alone)
+	uint32_t *out = (uint32_t *)fout;
 	// 1. fixed words of the template
 	const uint32_t *tw = (const uint32_t *)f.tmpl;
 	if (part == 0) for (int i = tid; i < f.tmpl_bytes / 4; i += ENT_THREADS) out[i + (s_cum[f.word_holes[i]] >> 2)] = tw[i];
@@ -677,7 +703,7 @@ __global__ void __launch_bounds__(ENT_THREADS) k_ent_layout(const EntFrameJob *f
 			// peak table: the chunk header (optional tag 0x4001 with the number of longwords that follow), zeros where k_ent_peaks puts the values
 			const uint32_t np = band_state[hole.band_job].npeaks;      // (<= ENT_PEAK_TABLE_MAX here: the hole of a larger table has no bytes)
 			for (uint32_t i = w0 + tid; i < w1; i += ENT_THREADS) out[(base >> 2) + i] = i == 0 ? bswap32(((uint32_t)(uint16_t)(-0x4001) << 16) | ((np + 1u) >> 1)) : 0u;
-			if (k == 0 && tid == 0) band_state[hole.band_job].peak_out = bytes ? f.out + base + 4 : nullptr;
+			if (k == 0 && tid == 0) band_state[hole.band_job].peak_out = bytes ? fout + base + 4 : nullptr;
 			continue;
 		}
 		// coded band: k_ent_emit ORs its code words into zeroed words.  Everything from the word that holds the first bit of the trailer
@@ -707,10 +733,10 @@ __global__ void __launch_bounds__(ENT_THREADS) k_ent_layout(const EntFrameJob *f
 			words[i] = bswap32(w);
 		}
 		__syncthreads();                                  // (uniform: k, last are) the words of the trailer are in place
-		for (int i = tid; i < bands[hole.band_job].nseg; i += ENT_THREADS) segs[bands[hole.band_job].seg_base + i].out = f.out + base;      // (k_ent_emit reads it there)
+		for (int i = tid; i < bands[hole.band_job].nseg; i += ENT_THREADS) segs[bands[hole.band_job].seg_base + i].out = fout + base;      // (k_ent_emit reads it there)
 		if (tid == 0) {
 			EntBandState &b = band_state[hole.band_job];
-			b.base_byte = base; b.out = f.out + base;
+			b.base_byte = base; b.out = fout + base;
 			uint64_t pos = p1;
 			uint32_t run = bs.tail_run - copies * maxc;
 			while (run > 0) {
@@ -943,9 +969,9 @@ __global__ void __launch_bounds__(ENT_THREADS) k_ent_peaks(const EntFrameJob *fr
 }
 
 // =============================================================================================
-// The finished samples sit in fixed-stride slots (sized for the worst case); the host wants them as bytes.  k_ent_pack_offsets
-// turns the sample sizes into 64-byte aligned offsets of a dense buffer, k_ent_pack copies every sample there, and one D2H
-// copy of offsets[n] bytes replaces one copy per frame.
+// The host wants the samples as bytes, with one D2H copy of offsets[n] bytes instead of one per frame.  k_ent_pack_offsets turns the
+// sample sizes (k_ent_sizes) into 64-byte aligned offsets of a dense buffer; k_ent_layout and k_ent_emit write every sample there.
+// (Until round 8 the samples were written into fixed-stride slots and copied here by a pack kernel: two more crossings of HBM per byte.)
 // =============================================================================================
 __global__ void __launch_bounds__(ENT_THREADS) k_ent_pack_offsets(const uint32_t *sizes, int n, uint32_t *offsets)
 {
@@ -960,15 +986,6 @@ __global__ void __launch_bounds__(ENT_THREADS) k_ent_pack_offsets(const uint32_t
 		carry += (uint32_t)total;
 	}
 	if (threadIdx.x == 0) offsets[n] = carry;
-}
-
-__global__ void __launch_bounds__(ENT_THREADS) k_ent_pack(const uint8_t *samples, size_t stride, const uint32_t *sizes, const uint32_t *offsets, uint8_t *packed)
-{
-	const int f = blockIdx.y;
-	const uint4 *src = (const uint4 *)(samples + stride * (size_t)f);
-	uint4 *dst = (uint4 *)(packed + offsets[f]);
-	const uint32_t n16 = (sizes[f] + 15u) >> 4;
-	for (uint32_t i = blockIdx.x * ENT_THREADS + threadIdx.x; i < n16; i += gridDim.x * ENT_THREADS) dst[i] = src[i];
 }
 
 // =============================================================================================
@@ -1241,12 +1258,13 @@ struct DecTagReader {
 
 __global__ void __launch_bounds__(DEC_PARSE_THREADS) k_dec_parse(const uint8_t *samples, size_t sample_stride, const uint32_t *sizes, int nframes, const DecPlan *P,
                                                                  int16_t *coeffs, size_t coeff_stride, DecBandJob *bandjobs, DecLowpassJob *lowjobs, int *errors,
-                                                                 DecDiffJob *diffjobs /* [nframes * channels], may be null: progressive samples only */)
+                                                                 DecDiffJob *diffjobs /* [nframes * channels], may be null: progressive samples only */,
+                                                                 const uint32_t *offsets = nullptr /* sample f at samples + offsets[f] (the encoder's dense buffer); null: at samples + f * sample_stride */)
 {
 	const int f = blockIdx.x;                            // every lane walks the same tags; lane 0 writes the jobs
 	const int lane = wave_lane();
 	const bool writer = lane == 0;
-	const uint8_t *d = samples + sample_stride * (size_t)f;
+	const uint8_t *d = offsets ? samples + offsets[f] : samples + sample_stride * (size_t)f;
 	int16_t *cbase = coeffs + coeff_stride * (size_t)f;
 	const uint64_t size = sizes[f];
 	const int nch = P->num_channels;
