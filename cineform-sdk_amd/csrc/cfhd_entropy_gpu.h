@@ -99,8 +99,10 @@ private:
 };
 
 
-// Decoder counterpart: parses each sample on the host (tag walk only), ships the sample bytes to HBM (unless they already live
-// there) and lets one GPU lane per coded band rebuild the dequantized coefficient pyramid.
+// Decoder counterpart: rebuilds the dequantized coefficient pyramids of a batch of samples.  The samples either lie in HBM already and are parsed there (k_dec_parse:
+// set_samples_device) or are parsed on the host (tag walk only) and shipped to HBM with their job tables.  The bands are decoded by the chunk-indexed decoder
+// (cfhd_dec_kernels.h: chunk index + tile decode) unless CFHD_AMD_DEC=par / lane selects the round-1 kernels (a workgroup / a lane per coded band) for A/B runs.
+enum class DecBackend { ChunkIndexed, Par, ParLowLatency, Lane };      // chosen once, in prepare()
 class GpuEntropyDecoder {
 public:
 	GpuEntropyDecoder();
@@ -122,10 +124,10 @@ public:
 	// Optional, for device-resident samples still being written by another stream: the next launch() lets k_dec_parse wait for
 	// `headers` only (it reads the tag stream, not the coded payloads) and the band decoder for `payloads`.
 	void set_producer_events(void *headers, void *payloads) { ev_headers_ = headers; ev_payloads_ = payloads; }
-	int launch();                        // async: (H2D samples, job tables | k_dec_parse), k_dec_bands_par + k_dec_lowpass
+	int launch();                        // async: (H2D samples, job tables | k_dec_parse), the band decoder (k_dec_index .. k_dec_tiles by default) + k_dec_lowpass
 	int check();                         // after the stream was synchronised: 0 when every band decoded cleanly
 	float kernel_ms(int k);              // last launch(): 0 k_dec_parse (device-resident samples only), 1 band decoder (all its kernels), 2 k_dec_lowpass, 3 k_dec_plan + k_dec_index, 4 k_dec_chain + k_dec_tile_index, 5 k_dec_tiles
-	bool chunk_indexed() const { return dx_; }
+	bool chunk_indexed() const { return backend_ == DecBackend::ChunkIndexed; }
 	// Set by launch() when it decoded the bands of levels 2 and 3 (and the lowpass bands) first and recorded this event behind them: the inverse transforms of
 	// those levels may start there, beside the tile pass over the level-1 bands that is still queued on the decoder's stream.  Null otherwise.
 	void *levels23_event() const { return l23_split_ ? ev_l23_ : nullptr; }
@@ -150,16 +152,21 @@ private:
 	int active_frames() const { return active_ > 0 && active_ < n_ ? active_ : n_; }
 	const uint8_t *ext_samples_ = nullptr; size_t ext_stride_ = 0; const uint32_t *ext_sizes_ = nullptr, *ext_offsets_ = nullptr;   // set_samples_device()
 	int *d_errors_ = nullptr, *h_errors_ = nullptr;
-	bool lane_kernel_ = false;
-	// cfhd_dec_kernels.h (default): chunk index + tile decode.  CFHD_AMD_DEC=par / lane select the round-1 kernels for A/B runs.
-	bool dx_ = true;
+	DecBackend backend_ = DecBackend::ChunkIndexed;
 	void *d_tile_start_ = nullptr, *d_stats_ = nullptr, *d_repair_ = nullptr, *d_alts_ = nullptr, *d_reindex_ = nullptr, *d_alt_entries_ = nullptr; uint32_t alt_slots_ = 0;
 	void *d_idx_tables_ = nullptr, *d_entries_ = nullptr, *d_recs_ = nullptr, *d_chunk_base_ = nullptr, *d_chunk_job_ = nullptr, *d_sums_ = nullptr, *d_counters_ = nullptr;
 	uint32_t max_chunks_ = 0, *h_counters_ = nullptr; void *h_chunk_job_ = nullptr;
 	int grid_index_ = 0, grid_tiles_ = 0;
 	int device_ = 0;                       // the GPU prepare() ran on: every launch selects it for the calling thread
-	int launch_dx(bool device_jobs, int njobs, uint32_t host_chunks, int lowpass_jobs);
-	void *ev_l23_ = nullptr, *ev_low_ = nullptr; bool l23_split_ = false;      // ev_low_: in front of k_dec_lowpass when it runs between the two tile passes      // recorded behind the tiles of the level-2 / level-3 bands and the lowpass bands when the tile pass is split
+	// what one launch() decodes: jobs written by k_dec_parse or flattened from the host's tables, the frames taking part, the band and lowpass jobs, and the chunks
+	// (host tables: their number; device jobs: the bound, the device numbers them)
+	struct Pass { bool device_jobs; int frames, band_jobs, lowpass_jobs; uint32_t chunks; };
+	int flatten_host_jobs(Pass *p);
+	int launch_dx(const Pass &p);
+	void launch_round1(DecBackend backend, int band_jobs);
+	// the split tile pass: ev_low_ in front of k_dec_lowpass, which then runs between the two tile passes; ev_l23_ behind it, that is behind the tiles of the
+	// level-2 / level-3 bands and the lowpass bands
+	void *ev_l23_ = nullptr, *ev_low_ = nullptr; bool l23_split_ = false;
 	void *ev_[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; bool timed_ = false;    // [4]: end of k_dec_parse when the band decoder waits for a second event behind it; [5], [6]: behind k_dec_index / k_dec_chain; [7]: behind k_dec_plan (in front of k_dec_index)
 	bool parse_end_ = false;
 	unsigned long long *d_masks_ = nullptr; size_t masks_per_frame_ = 0; bool use_blocks_ = false, blocks_written_ = false;

@@ -168,27 +168,19 @@ int GpuEntropyEncoder::launch()
 	// CFHD_AMD_COUNT_SPLIT=0: (A/B) the level-1 bands counted on the main stream behind the level-2 / level-3 transforms instead of beside them
 	static const bool split_on = [] { const char *e = getenv("CFHD_AMD_COUNT_SPLIT"); return !(e && atoi(e) == 0); }();
 	split_ = split_on && ev_level1_ && stream2_ && !host_->jobs.ranges_l1.empty() && act >= 8;      // (a single frame gains nothing from six launches instead of one)
-	// the peak flags are raised by the difference-coded band only, a level-1 band: cleared on the stream that counts it
-	if (peak_flags_in_use() && !split_) HIPCHK(hipMemsetAsync(d_sizes_ + n_, 0, sizeof(uint32_t) * n_, st));
 	serial_split_ = split_ && stream2_ == stream_;      // (a pass whose streams are one, cfhd_batch.cpp StreamScope: the same launches in a row, timed apart)
-	if (serial_split_) {
-		if (peak_flags_in_use()) HIPCHK(hipMemsetAsync(d_sizes_ + n_, 0, sizeof(uint32_t) * n_, st));
-		HIPCHK(hipEventRecord((hipEvent_t)ev2_[0], st));
-		for (const auto &r : host_->jobs.ranges_l1) count_range(st, r.first, r.second, true);
-		HIPCHK(hipEventRecord((hipEvent_t)ev2_[1], st));
+	// the level-1 bands on the second stream as soon as the level-1 transform is done; the bands of levels 2 and 3 on the main stream, behind their transforms; the scan waits for both
+	hipStream_t s1 = split_ ? (hipStream_t)stream2_ : st;
+	if (s1 != st) HIPCHK(hipStreamWaitEvent(s1, (hipEvent_t)ev_level1_, 0));
+	// the peak flags are raised by the difference-coded band only, a level-1 band: cleared on the stream that counts it
+	if (peak_flags_in_use()) HIPCHK(hipMemsetAsync(d_sizes_ + n_, 0, sizeof(uint32_t) * n_, s1));
+	if (split_) {
+		HIPCHK(hipEventRecord((hipEvent_t)ev2_[0], s1));
+		for (const auto &r : host_->jobs.ranges_l1) count_range(s1, r.first, r.second, true);
+		HIPCHK(hipEventRecord((hipEvent_t)ev2_[1], s1));
 		for (const auto &r : host_->jobs.ranges_rest) count_range(st, r.first, r.second);
 		HIPCHK(hipEventRecord((hipEvent_t)ev2_[2], st));
-	} else if (split_) {
-		// the level-1 bands on the second stream as soon as the level-1 transform is done; the bands of levels 2 and 3 here, behind their transforms; the scan waits for both
-		hipStream_t s2 = (hipStream_t)stream2_;
-		HIPCHK(hipStreamWaitEvent(s2, (hipEvent_t)ev_level1_, 0));
-		if (peak_flags_in_use()) HIPCHK(hipMemsetAsync(d_sizes_ + n_, 0, sizeof(uint32_t) * n_, s2));
-		HIPCHK(hipEventRecord((hipEvent_t)ev2_[0], s2));
-		for (const auto &r : host_->jobs.ranges_l1) count_range(s2, r.first, r.second, true);
-		HIPCHK(hipEventRecord((hipEvent_t)ev2_[1], s2));
-		for (const auto &r : host_->jobs.ranges_rest) count_range(st, r.first, r.second);
-		HIPCHK(hipEventRecord((hipEvent_t)ev2_[2], st));
-		HIPCHK(hipStreamWaitEvent(st, (hipEvent_t)ev2_[1], 0));
+		if (s1 != st) HIPCHK(hipStreamWaitEvent(st, (hipEvent_t)ev2_[1], 0));
 	} else if (use_blocks_) {
 		for (const auto &r : host_->jobs.ranges_l1) count_range(st, r.first, r.second, true);
 		for (const auto &r : host_->jobs.ranges_rest) count_range(st, r.first, r.second);
@@ -255,8 +247,7 @@ int GpuEntropyEncoder::download_queue()
 {
 	(void)hipSetDevice(device_);
 	hipStream_t st = (hipStream_t)stream_;
-	// one copy out of HBM (SDMA engine when the runtime has it enabled)
-	const bool direct = false;      // (the kernels storing straight into the pinned host buffer: measured slower than dense samples in HBM + one SDMA copy in round 2)
+	// one copy out of HBM (SDMA engine when the runtime has it enabled; the kernels storing straight into the pinned host buffer measured slower in round 2)
 	const int act = active_frames();
 	HIPCHK(hipMemcpyAsync(h_sizes_, d_sizes_, sizeof(uint32_t) * 2 * n_, hipMemcpyDeviceToHost, st));
 	HIPCHK(hipMemcpyAsync(h_offsets_, d_offsets_, sizeof(uint32_t) * (act + 1), hipMemcpyDeviceToHost, st));
@@ -264,7 +255,7 @@ int GpuEntropyEncoder::download_queue()
 	// (cfhd_amd_batch_submit) would start that copy only when its result is collected, a step or two later; so the copy goes out now, sized by what the last pass of this
 	// many frames produced plus a margin, and download_finish() adds the remainder if this pass turned out larger (consecutive passes of a sequence differ by a few percent).
 	copied_ahead_ = 0;
-	if (!direct && expect_bytes_ && expect_frames_ == act) {
+	if (expect_bytes_ && expect_frames_ == act) {
 		copied_ahead_ = expect_bytes_ < cap_ * (size_t)act ? expect_bytes_ : cap_ * (size_t)act;
 		HIPCHK(hipMemcpyAsync(h_samples_, d_packed_, copied_ahead_, hipMemcpyDeviceToHost, st));
 	}
@@ -276,11 +267,10 @@ int GpuEntropyEncoder::download_finish()
 {
 	(void)hipSetDevice(device_);
 	hipStream_t st = (hipStream_t)stream_;
-	const bool direct = false;
 	const int act = active_frames();
 	HIPCHK(hipStreamSynchronize(st));
 	const size_t total = h_offsets_[act];
-	if (!direct && total > copied_ahead_) HIPCHK(hipMemcpyAsync(h_samples_ + copied_ahead_, d_packed_ + copied_ahead_, total - copied_ahead_, hipMemcpyDeviceToHost, st));
+	if (total > copied_ahead_) HIPCHK(hipMemcpyAsync(h_samples_ + copied_ahead_, d_packed_ + copied_ahead_, total - copied_ahead_, hipMemcpyDeviceToHost, st));
 	expect_bytes_ = speculative_download_ ? ((total + total / 32 + 4095) & ~(size_t)4095) : 0; expect_frames_ = act;
 	return 0;
 }
@@ -291,7 +281,11 @@ struct GpuEntropyDecoder::Host {
 	std::vector<size_t> host_bytes;                       // bytes to copy H2D per frame (0: sample already in HBM)
 	std::vector<std::vector<dev::DecDiffJob>> diffs;     // per frame: the difference-coded band of every channel (interlaced samples)
 	dev::DecBandJob *flat_bands = nullptr; dev::DecLowpassJob *flat_lows = nullptr; dev::DecDiffJob *flat_diffs = nullptr;   // pinned
+	dev::DecPlan plan;                                    // the slots of the job tables (dec_build_plan): fixed by prepare()
 };
+
+enum { kLowLatencyFrames = 32 };     // up to here k_dec_bands_par_ll: measured 0.22 vs 0.37 ms for one 1080p frame, break-even near 64 frames
+static DecBackend par_backend(int nframes) { return nframes <= kLowLatencyFrames ? DecBackend::ParLowLatency : DecBackend::Par; }
 
 GpuEntropyDecoder::GpuEntropyDecoder() : host_(new Host) {}
 GpuEntropyDecoder::~GpuEntropyDecoder() { release(); delete host_; }
@@ -340,8 +334,13 @@ int GpuEntropyDecoder::prepare(const FramePlan &plan, int nframes, int16_t *d_co
 	HIPCHK(hipMalloc((void **)&d_errors_, sizeof(int)));
 	HIPCHK(hipHostMalloc((void **)&h_errors_, sizeof(int), hipHostMallocPortable));
 	*h_errors_ = 0;
-	{ const char *e = getenv("CFHD_AMD_DEC"); lane_kernel_ = e && strcmp(e, "lane") == 0; dx_ = !(e && (strcmp(e, "lane") == 0 || strcmp(e, "par") == 0)); }   // A/B switch: the round-1 kernels
-	if (dx_) {
+	// the band decoder, chosen here and nowhere else.  CFHD_AMD_DEC=lane / par: (A/B) the round-1 kernels -- par in its latency shape for few frames (the launch lasts as
+	// long as the longest band's serial steps), in its throughput shape for many
+	const char *be = getenv("CFHD_AMD_DEC");
+	backend_ = be && strcmp(be, "lane") == 0 ? DecBackend::Lane : be && strcmp(be, "par") == 0 ? par_backend(n_) : DecBackend::ChunkIndexed;
+	dev::DecPlan &dp = host_->plan;
+	dec_build_plan(plan, out_kind, &dp);
+	if (chunk_indexed()) {
 		dev::DecIdxTables *it = new dev::DecIdxTables;
 		const bool ok = build_dec_index_tables(1, it);
 		if (ok) { hipError_t e = hipMalloc(&d_idx_tables_, sizeof(*it)); if (e == hipSuccess) e = hipMemcpy(d_idx_tables_, it, sizeof(*it), hipMemcpyHostToDevice); if (e != hipSuccess) { delete it; return g_fail(e, "decoder tables"); } }
@@ -362,13 +361,9 @@ int GpuEntropyDecoder::prepare(const FramePlan &plan, int nframes, int16_t *d_co
 		HIPCHK(hipMalloc(&d_reindex_, (size_t)max_chunks_ * sizeof(dev::DxReindex)));
 		alt_slots_ = max_chunks_ / 8 > 64u ? max_chunks_ / 8 : 64u;          // entries of the extra candidates of chunks without a unique alignment (a few per cent of the chunks)
 		HIPCHK(hipMalloc(&d_alt_entries_, (size_t)alt_slots_ * dev::DX_ENTRY_STRIDE * 4));
-		{
-			dev::DecPlan dp0; dec_build_plan(plan, out_kind, &dp0);
-			const dev::DxTilePlan tp0 = dx_tile_plan(plan, dp0, n_, false);
-			HIPCHK(hipMalloc(&d_tile_start_, ((size_t)tp0.total + 1) * sizeof(dev::DxTileDesc)));      // one record per tile (k_dec_tile_index)
-			const char *se = getenv("CFHD_AMD_DX_STATS");
-			if (se && atoi(se)) { HIPCHK(hipMalloc(&d_stats_, 64)); HIPCHK(hipMemset(d_stats_, 0, 64)); }
-		}
+		HIPCHK(hipMalloc(&d_tile_start_, ((size_t)dx_tile_plan(plan, dp, n_, false).total + 1) * sizeof(dev::DxTileDesc)));      // one record per tile (k_dec_tile_index)
+		const char *se = getenv("CFHD_AMD_DX_STATS");
+		if (se && atoi(se)) { HIPCHK(hipMalloc(&d_stats_, 64)); HIPCHK(hipMemset(d_stats_, 0, 64)); }
 		HIPCHK(hipHostMalloc((void **)&h_chunk_job_, (size_t)max_chunks_ * sizeof(dev::DxChunkDesc), hipHostMallocPortable));
 		HIPCHK(hipHostMalloc((void **)&h_counters_, 32, hipHostMallocPortable));
 		int cus = 256;
@@ -379,14 +374,10 @@ int GpuEntropyDecoder::prepare(const FramePlan &plan, int nframes, int16_t *d_co
 		if (grid_index_ < 1) grid_index_ = 1;
 		if (grid_tiles_ < 1) grid_tiles_ = 1;
 	}
-	{
-		dev::DecPlan dp;
-		dec_build_plan(plan, out_kind, &dp);
-		HIPCHK(hipMalloc(&d_plan_, sizeof(dp)));
-		HIPCHK(hipMemcpy(d_plan_, &dp, sizeof(dp), hipMemcpyHostToDevice));
-	}
+	HIPCHK(hipMalloc(&d_plan_, sizeof(dp)));
+	HIPCHK(hipMemcpy(d_plan_, &dp, sizeof(dp), hipMemcpyHostToDevice));
 	// chunk masks of the level-1 bands as block lists (cfhd_core.h dec_block_list_layout): for 4:2:2 frames, whose last level has a strip kernel that gathers them
-	if (dx_ && plan.encoded_format == ENC_YUV422 && plan.num_channels == 3) {
+	if (chunk_indexed() && plan.encoded_format == ENC_YUV422 && plan.num_channels == 3) {
 		int mask_base[kMaxChannels][kNumBands];
 		masks_per_frame_ = (size_t)dec_block_list_layout(plan, mask_base);
 		HIPCHK(hipMalloc((void **)&d_masks_, masks_per_frame_ * 8 * (size_t)n_));
@@ -424,9 +415,9 @@ int GpuEntropyDecoder::set_sample_device(int i, const uint8_t *d_sample, const u
 	if (parse_sample(host_copy, size, &ps) != 0) return -2;
 	if (ps.width != plan_.width || ps.display_height != plan_.display_height || ps.encoded_format != plan_.encoded_format || ps.num_channels != plan_.num_channels) return -3;
 	host_->bands[i].clear(); host_->lows[i].clear(); host_->host_bytes[i] = 0;
-	if (dx_) {
+	if (chunk_indexed()) {
 		// rows of the [slot][frame] job table, by slot
-		dev::DecPlan dp; dec_build_plan(plan_, out_kind_, &dp);
+		const dev::DecPlan &dp = host_->plan;
 		host_->bands[i].assign((size_t)dp.bands_per_frame, dev::DecBandJob());
 		host_->lows[i].assign((size_t)plan_.num_channels, dev::DecLowpassJob());
 		host_->diffs[i].assign((size_t)plan_.num_channels, dev::DecDiffJob());
@@ -439,17 +430,67 @@ int GpuEntropyDecoder::set_sample_device(int i, const uint8_t *d_sample, const u
 	return 0;
 }
 
-enum { kLowLatencyFrames = 32 };     // up to here k_dec_bands_par_ll: measured 0.22 vs 0.37 ms for one 1080p frame, break-even near 64 frames
+// The host's job tables as the kernels read them.  Chunk-indexed decoder: [slot][frame] over the frames that carry samples (set_active), the chunks numbered here.
+// Round-1 kernels: band-type major over the whole batch -- the 64 lanes of a wave (lane kernel) decode bands of similar length, and the workgroups of the parallel
+// kernel start with the long bands (level-1 luma first) so that the short ones fill the tail of the launch.
+int GpuEntropyDecoder::flatten_host_jobs(Pass *p)
+{
+	const int nch = plan_.num_channels;
+	dev::DecBandJob *fb = host_->flat_bands; dev::DecLowpassJob *fl = host_->flat_lows;
+	if (chunk_indexed()) {
+		const int slots = host_->plan.bands_per_frame, act = active_frames();
+		for (int f = 0; f < act; f++) {
+			if ((int)host_->bands[f].size() != slots || (int)host_->lows[f].size() != nch) return -1;
+			for (int s = 0; s < slots; s++) fb[(size_t)s * act + f] = host_->bands[f][s];
+			for (int c = 0; c < nch; c++) fl[(size_t)f * nch + c] = host_->lows[f][c];
+			if (interlaced_) { if ((int)host_->diffs[f].size() != nch) return -1; for (int c = 0; c < nch; c++) host_->flat_diffs[(size_t)f * nch + c] = host_->diffs[f][c]; }
+		}
+		std::vector<dev::DxChunkDesc> cj;
+		const uint32_t nchunks = dx_number_chunks(fb, slots * act, &cj);
+		if (nchunks > max_chunks_) return -5;
+		memcpy(h_chunk_job_, cj.data(), cj.size() * sizeof(dev::DxChunkDesc));
+		h_counters_[0] = nchunks; h_counters_[1] = 0; h_counters_[2] = 0; h_counters_[3] = 0; h_counters_[4] = 0;
+		*p = Pass{ false, act, slots * act, act * nch, nchunks };
+		return 0;
+	}
+	size_t nfb = 0, nfl = 0, per_frame = 0;
+	for (int f = 0; f < n_; f++) per_frame = host_->bands[f].size() > per_frame ? host_->bands[f].size() : per_frame;
+	for (size_t k = 0; k < per_frame; k++) for (int f = 0; f < n_; f++) if (k < host_->bands[f].size()) fb[nfb++] = host_->bands[f][k];
+	for (int f = 0; f < n_; f++) for (const dev::DecLowpassJob &j : host_->lows[f]) fl[nfl++] = j;
+	if (!nfb) return -1;
+	if (backend_ != DecBackend::Lane) std::stable_sort(fb, fb + nfb, [](const dev::DecBandJob &a, const dev::DecBandJob &b) { return a.bytes > b.bytes; });
+	else HIPCHK(hipMemset2DAsync(d_coeffs_, coeff_stride_ * 2, 0, (size_t)plan_.final_elems * 2, n_, (hipStream_t)stream_));   // the parallel kernel clears its own bands
+	*p = Pass{ false, n_, (int)nfb, (int)nfl, 0u };
+	return 0;
+}
 
+// The round-1 band kernels (the only place that names them): a lane per band, or a workgroup per band in its latency or its throughput shape.
+void GpuEntropyDecoder::launch_round1(DecBackend backend, int nb)
+{
+	hipStream_t st = (hipStream_t)stream_;
+	const dev::DecBandJob *jobs = (const dev::DecBandJob *)d_bandjobs_; const dev::DecTables *T = (const dev::DecTables *)d_tables_;
+	if (backend == DecBackend::Lane) dev::k_dec_bands<<<(nb + dev::DEC_THREADS - 1) / dev::DEC_THREADS, dev::DEC_THREADS, 0, st>>>(jobs, nb, T, d_errors_);
+	else if (backend == DecBackend::ParLowLatency) dev::k_dec_bands_par_ll<<<nb, dev::DECP_LL_THREADS, 0, st>>>(jobs, T, d_errors_);
+	else dev::k_dec_bands_par<<<nb, dev::DECP_THREADS, 0, st>>>(jobs, T, d_errors_);
+}
+
+// One pass over the batch: the job tables (parsed on the GPU from device-resident samples, or uploaded with the host-parsed samples), the band decoder -- by default the
+// chunk-indexed one, launch_dx --, the lowpass bands, the error flag on its way to the host.
 int GpuEntropyDecoder::launch()
 {
 	(void)hipSetDevice(device_);
 	hipStream_t st = (hipStream_t)stream_;
+	const int nch = plan_.num_channels;
 	l23_split_ = false; blocks_written_ = false;
-	if (ext_samples_) {
-		// device-resident samples: parse on the GPU; the job tables have one row per band type (largest first), nframes wide
-		const int nch = plan_.num_channels, nb = n_ * nch * 9;
-		HIPCHK(hipMemsetAsync(d_errors_, 0, sizeof(int), st));
+	// device-resident samples: the job tables have one row per band type (largest first), nframes wide, and the device numbers the chunks
+	Pass p = { true, n_, n_ * nch * 9, n_ * nch, max_chunks_ };
+	if (!ext_samples_) {
+		if (chunk_indexed()) HIPCHK(hipStreamSynchronize(st));                    // the pinned tables of the previous launch may still be in flight
+		const int rc = flatten_host_jobs(&p);
+		if (rc) return rc;
+	}
+	HIPCHK(hipMemsetAsync(d_errors_, 0, sizeof(int), st));
+	if (p.device_jobs) {
 		(void)hipGetLastError();
 		// CFHD_AMD_PARSE_EARLY=0: (A/B) the parser behind the finished payloads instead of beside k_ent_emit
 		static const bool parse_early = [] { const char *e = getenv("CFHD_AMD_PARSE_EARLY"); return !(e && atoi(e) == 0); }();
@@ -458,88 +499,31 @@ int GpuEntropyDecoder::launch()
 		HIPCHK(hipEventRecord((hipEvent_t)ev_[0], st));
 		dev::k_dec_parse<<<n_, dev::DEC_PARSE_THREADS, 0, st>>>(ext_samples_, ext_stride_, ext_sizes_, n_,
 			(const dev::DecPlan *)d_plan_, d_coeffs_, coeff_stride_, (dev::DecBandJob *)d_bandjobs_, (dev::DecLowpassJob *)d_lowjobs_, d_errors_,
-			interlaced_ && dx_ ? (dev::DecDiffJob *)d_diffjobs_ : nullptr, ext_offsets_);
+			interlaced_ && chunk_indexed() ? (dev::DecDiffJob *)d_diffjobs_ : nullptr, ext_offsets_);
 		parse_end_ = ev_payloads_ != nullptr;
 		if (parse_end_) { HIPCHK(hipEventRecord((hipEvent_t)ev_[4], st)); HIPCHK(hipStreamWaitEvent(st, (hipEvent_t)ev_payloads_, 0)); }
 		ev_headers_ = ev_payloads_ = nullptr;
-		HIPCHK(hipEventRecord((hipEvent_t)ev_[1], st));
-		// few frames: the latency shape (the launch lasts as long as the longest band's serial steps); many: the throughput shape
-		l23_split_ = false;
-		if (dx_) { const int rc_dx = launch_dx(true, nb, 0u, n_ * nch); if (rc_dx) return rc_dx; }
-		else if (n_ <= kLowLatencyFrames) dev::k_dec_bands_par_ll<<<nb, dev::DECP_LL_THREADS, 0, st>>>((const dev::DecBandJob *)d_bandjobs_, (const dev::DecTables *)d_tables_, d_errors_);
-		else dev::k_dec_bands_par<<<nb, dev::DECP_THREADS, 0, st>>>((const dev::DecBandJob *)d_bandjobs_, (const dev::DecTables *)d_tables_, d_errors_);
-		HIPCHK(hipEventRecord((hipEvent_t)ev_[2], st));
-		if (!l23_split_) dev::k_dec_lowpass<<<dim3(8, (unsigned)(n_ * nch)), 256, 0, st>>>((const dev::DecLowpassJob *)d_lowjobs_);      // (split: launched between the two tile passes)
-		HIPCHK(hipGetLastError());
-		HIPCHK(hipEventRecord((hipEvent_t)ev_[3], st));
-		timed_ = true;
-		HIPCHK(hipMemcpyAsync(h_errors_, d_errors_, sizeof(int), hipMemcpyDeviceToHost, st));
-		return 0;
-	}
-	parse_end_ = false;
-	if (dx_) {
-		// host-parsed samples: the [slot][frame] job table and the chunk numbering come from the host
-		dev::DecPlan dp; dec_build_plan(plan_, out_kind_, &dp);
-		const int nch = plan_.num_channels, act = active_frames(), nb = dp.bands_per_frame * act;      // frames 0 .. act-1 of the batch carry samples
-		HIPCHK(hipStreamSynchronize(st));                                     // the pinned tables of the previous launch may still be in flight
-		for (int f = 0; f < act; f++) {
-			if ((int)host_->bands[f].size() != dp.bands_per_frame || (int)host_->lows[f].size() != nch) return -1;
-			for (int s = 0; s < dp.bands_per_frame; s++) host_->flat_bands[(size_t)s * act + f] = host_->bands[f][s];
-			for (int c = 0; c < nch; c++) host_->flat_lows[(size_t)f * nch + c] = host_->lows[f][c];
-			if (interlaced_) { if ((int)host_->diffs[f].size() != nch) return -1; for (int c = 0; c < nch; c++) host_->flat_diffs[(size_t)f * nch + c] = host_->diffs[f][c]; }
-		}
-		std::vector<dev::DxChunkDesc> cj;
-		const uint32_t nchunks = dx_number_chunks(host_->flat_bands, nb, &cj);
-		if (nchunks > max_chunks_) return -5;
-		memcpy(h_chunk_job_, cj.data(), cj.size() * sizeof(dev::DxChunkDesc));
-		h_counters_[0] = nchunks; h_counters_[1] = 0; h_counters_[2] = 0; h_counters_[3] = 0; h_counters_[4] = 0;
-		HIPCHK(hipMemsetAsync(d_errors_, 0, sizeof(int), st));
-		for (int f = 0; f < act; f++)
+	} else {
+		parse_end_ = false;
+		for (int f = 0; f < p.frames; f++)
 			if (host_->host_bytes[f]) HIPCHK(hipMemcpyAsync(d_samples_ + cap_ * f, h_samples_ + cap_ * f, host_->host_bytes[f], hipMemcpyHostToDevice, st));
-		HIPCHK(hipMemcpyAsync(d_bandjobs_, host_->flat_bands, (size_t)nb * sizeof(dev::DecBandJob), hipMemcpyHostToDevice, st));
-		HIPCHK(hipMemcpyAsync(d_lowjobs_, host_->flat_lows, (size_t)act * nch * sizeof(dev::DecLowpassJob), hipMemcpyHostToDevice, st));
-		if (interlaced_) HIPCHK(hipMemcpyAsync(d_diffjobs_, host_->flat_diffs, (size_t)act * nch * sizeof(dev::DecDiffJob), hipMemcpyHostToDevice, st));
-		HIPCHK(hipMemcpyAsync(d_chunk_job_, h_chunk_job_, (size_t)nchunks * sizeof(dev::DxChunkDesc), hipMemcpyHostToDevice, st));
-		HIPCHK(hipMemcpyAsync(d_counters_, h_counters_, 20, hipMemcpyHostToDevice, st));
+		HIPCHK(hipMemcpyAsync(d_bandjobs_, host_->flat_bands, (size_t)p.band_jobs * sizeof(dev::DecBandJob), hipMemcpyHostToDevice, st));
+		HIPCHK(hipMemcpyAsync(d_lowjobs_, host_->flat_lows, (size_t)p.lowpass_jobs * sizeof(dev::DecLowpassJob), hipMemcpyHostToDevice, st));
+		if (chunk_indexed()) {
+			if (interlaced_) HIPCHK(hipMemcpyAsync(d_diffjobs_, host_->flat_diffs, (size_t)p.lowpass_jobs * sizeof(dev::DecDiffJob), hipMemcpyHostToDevice, st));
+			HIPCHK(hipMemcpyAsync(d_chunk_job_, h_chunk_job_, (size_t)p.chunks * sizeof(dev::DxChunkDesc), hipMemcpyHostToDevice, st));
+			HIPCHK(hipMemcpyAsync(d_counters_, h_counters_, 20, hipMemcpyHostToDevice, st));
+		}
 		(void)hipGetLastError();
 		HIPCHK(hipEventRecord((hipEvent_t)ev_[0], st));
-		HIPCHK(hipEventRecord((hipEvent_t)ev_[1], st));
-		l23_split_ = false;
-		int rc = launch_dx(false, nb, nchunks, act * nch);
-		if (rc) return rc;
-		HIPCHK(hipEventRecord((hipEvent_t)ev_[2], st));
-		if (!l23_split_) dev::k_dec_lowpass<<<dim3(8, (unsigned)(act * nch)), 256, 0, st>>>((const dev::DecLowpassJob *)d_lowjobs_);
-		HIPCHK(hipGetLastError());
-		HIPCHK(hipEventRecord((hipEvent_t)ev_[3], st));
-		timed_ = true;
-		HIPCHK(hipMemcpyAsync(h_errors_, d_errors_, sizeof(int), hipMemcpyDeviceToHost, st));
-		return 0;
 	}
-	const bool lane_kernel = lane_kernel_;
-	dev::DecBandJob *fb = host_->flat_bands; dev::DecLowpassJob *fl = host_->flat_lows;
-	size_t nfb = 0, nfl = 0, per_frame = 0;
-	// band-type major: the 64 lanes of a wave (lane kernel) decode bands of similar length, and the workgroups of the parallel
-	// kernel start with the long bands (level-1 luma first) so that the short ones fill the tail of the launch
-	for (int f = 0; f < n_; f++) per_frame = host_->bands[f].size() > per_frame ? host_->bands[f].size() : per_frame;
-	for (size_t k = 0; k < per_frame; k++) for (int f = 0; f < n_; f++) if (k < host_->bands[f].size()) fb[nfb++] = host_->bands[f][k];
-	for (int f = 0; f < n_; f++) for (const dev::DecLowpassJob &j : host_->lows[f]) fl[nfl++] = j;
-	if (!nfb) return -1;
-	if (!lane_kernel) std::stable_sort(fb, fb + nfb, [](const dev::DecBandJob &a, const dev::DecBandJob &b) { return a.bytes > b.bytes; });
-	else HIPCHK(hipMemset2DAsync(d_coeffs_, coeff_stride_ * 2, 0, (size_t)plan_.final_elems * 2, n_, st));   // the parallel kernel clears its own bands
-	HIPCHK(hipMemsetAsync(d_errors_, 0, sizeof(int), st));
-	for (int f = 0; f < n_; f++)
-		if (host_->host_bytes[f]) HIPCHK(hipMemcpyAsync(d_samples_ + cap_ * f, h_samples_ + cap_ * f, host_->host_bytes[f], hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemcpyAsync(d_bandjobs_, fb, nfb * sizeof(dev::DecBandJob), hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemcpyAsync(d_lowjobs_, fl, nfl * sizeof(dev::DecLowpassJob), hipMemcpyHostToDevice, st));
-	(void)hipGetLastError();
-	const int nb = (int)nfb;
-	HIPCHK(hipEventRecord((hipEvent_t)ev_[0], st));
 	HIPCHK(hipEventRecord((hipEvent_t)ev_[1], st));
-	if (lane_kernel) dev::k_dec_bands<<<(nb + dev::DEC_THREADS - 1) / dev::DEC_THREADS, dev::DEC_THREADS, 0, st>>>((const dev::DecBandJob *)d_bandjobs_, nb, (const dev::DecTables *)d_tables_, d_errors_);
-	else if (n_ <= kLowLatencyFrames) dev::k_dec_bands_par_ll<<<nb, dev::DECP_LL_THREADS, 0, st>>>((const dev::DecBandJob *)d_bandjobs_, (const dev::DecTables *)d_tables_, d_errors_);
-	else dev::k_dec_bands_par<<<nb, dev::DECP_THREADS, 0, st>>>((const dev::DecBandJob *)d_bandjobs_, (const dev::DecTables *)d_tables_, d_errors_);
+	// (the lane kernel wants the pyramid cleared and its jobs from the host: device-resident samples go to the parallel one)
+	const DecBackend round1 = p.device_jobs && backend_ == DecBackend::Lane ? par_backend(n_) : backend_;
+	if (chunk_indexed()) { const int rc = launch_dx(p); if (rc) return rc; }
+	else launch_round1(round1, p.band_jobs);
 	HIPCHK(hipEventRecord((hipEvent_t)ev_[2], st));
-	dev::k_dec_lowpass<<<dim3(8, (unsigned)nfl), 256, 0, st>>>((const dev::DecLowpassJob *)d_lowjobs_);
+	if (!l23_split_) dev::k_dec_lowpass<<<dim3(8, (unsigned)p.lowpass_jobs), 256, 0, st>>>((const dev::DecLowpassJob *)d_lowjobs_);      // (split: launched between the two tile passes)
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipEventRecord((hipEvent_t)ev_[3], st));
 	timed_ = true;
@@ -547,31 +531,29 @@ int GpuEntropyDecoder::launch()
 	return 0;
 }
 
-// The chunk-indexed decoder on the batch's stream.  device_jobs: the job table was filled by k_dec_parse (chunks are numbered on the device).
-int GpuEntropyDecoder::launch_dx(bool device_jobs, int njobs, uint32_t host_chunks, int lowpass_jobs)
+// The chunk-indexed decoder on the batch's stream.
+int GpuEntropyDecoder::launch_dx(const Pass &p)
 {
 	hipStream_t st = (hipStream_t)stream_;
 	dev::DecBandJob *jobs = (dev::DecBandJob *)d_bandjobs_;
 	const dev::DecIdxTables *T = (const dev::DecIdxTables *)d_idx_tables_;
-	dev::DecPlan dp; dec_build_plan(plan_, out_kind_, &dp);
-	const int frames = device_jobs ? n_ : active_frames();
+	const int njobs = p.band_jobs;
 	const bool lists = use_blocks_ && d_masks_ && !skip_level1_;
-	const dev::DxTilePlan tp = dx_tile_plan(plan_, dp, frames, skip_level1_, lists, interlaced_);
+	const dev::DxTilePlan tp = dx_tile_plan(plan_, host_->plan, p.frames, skip_level1_, lists, interlaced_);
 	unsigned long long *const tmasks = lists ? d_masks_ : nullptr;
 	blocks_written_ = lists;
 	const char *spec_env = getenv("CFHD_AMD_DX_SPECULATE");
 	const bool speculate = !(spec_env && atoi(spec_env) == 0);            // 0: every chunk goes through the repair path (tests)
-	if (device_jobs) HIPCHK(hipMemsetAsync((uint32_t *)d_counters_ + 1, 0, 16, st));     // the repair and re-index lists, the alternate-entry slots and the chunk counter start at zero (the host path uploads zeroed counters)
-	if (device_jobs) {
+	if (p.device_jobs) {
+		// the repair and re-index lists, the alternate-entry slots and the chunk counter start at zero (the host path uploads zeroed counters); the chunks are numbered here
+		HIPCHK(hipMemsetAsync((uint32_t *)d_counters_ + 1, 0, 16, st));
 		dev::k_dec_plan<<<1, 1024, 0, st>>>(jobs, njobs, max_chunks_, (uint32_t *)d_counters_, d_errors_);
 		dev::k_dec_plan_fill<<<(njobs + dev::DX_WAVES - 1) / dev::DX_WAVES, dev::DX_THREADS, 0, st>>>(jobs, njobs, (dev::DxChunkDesc *)d_chunk_job_, (const uint32_t *)d_counters_);
 	}
 	HIPCHK(hipEventRecord((hipEvent_t)ev_[7], st));         // (k_dec_index is timed by itself: kernel_ms(3); the plan in front of it: kernel_ms(6))
-	// grid-stride kernels: as many workgroups as the chip holds at once, fewer when there is less work
-	const uint32_t chunk_bound = device_jobs ? max_chunks_ : host_chunks;
+	// grid-stride kernels: as many workgroups as the chip holds at once, fewer when there is less work (k_dec_tiles: a workgroup per tile)
 	int g1 = grid_index_, g3 = grid_tiles_;
-	if ((uint32_t)g1 * dev::DX_WAVES > chunk_bound) g1 = (int)((chunk_bound + dev::DX_WAVES - 1) / dev::DX_WAVES);
-	const uint32_t tile_waves = 1u;                       // (a workgroup per tile)
+	if ((uint32_t)g1 * dev::DX_WAVES > p.chunks) g1 = (int)((p.chunks + dev::DX_WAVES - 1) / dev::DX_WAVES);
 	if ((uint32_t)g3 > tp.total) g3 = (int)tp.total;
 	if (g1 < 1) g1 = 1;
 	if (g3 < 1) g3 = 1;
@@ -593,28 +575,24 @@ int GpuEntropyDecoder::launch_dx(bool device_jobs, int njobs, uint32_t host_chun
 	// measured in round 3 (1080p, 512 frames), the step does not get shorter (48.1 k fps either way) -- k_dec_tiles is bound by instruction issue and owns its CUs' LDS,
 	// the plane kernels beside it only stretch it from 1.67 to 2.25 ms.  (The same idea pays on the encoder side, where the kernel that shares the chip waits on memory.)
 	const char *split_env = getenv("CFHD_AMD_TILES_SPLIT");
-	l23_split_ = frames >= 8 && !skip_level1_ && tp.split > 0 && tp.split < tp.total && split_env && split_env[0] == '1';
-	auto tile_pass = [&](const dev::DxTilePlan &p, int g) {
-		dev::k_dec_tiles<dev::DX_TILE_THREADS><<<g < 1 ? 1 : g, dev::DX_TILE_THREADS, 0, st>>>((const dev::DxTileDesc *)d_tile_start_, p.first, p.total, T, (const uint32_t *)d_entries_, (const uint32_t *)d_chunk_base_);
+	l23_split_ = p.frames >= 8 && !skip_level1_ && tp.split > 0 && tp.split < tp.total && split_env && split_env[0] == '1';
+	auto tile_pass = [&](const dev::DxTilePlan &t, int g) {
+		dev::k_dec_tiles<dev::DX_TILE_THREADS><<<g < 1 ? 1 : g, dev::DX_TILE_THREADS, 0, st>>>((const dev::DxTileDesc *)d_tile_start_, t.first, t.total, T, (const uint32_t *)d_entries_, (const uint32_t *)d_chunk_base_);
 	};
 	if (l23_split_) {
 		dev::DxTilePlan ta = tp, tb = tp;
 		ta.total = tp.split; tb.first = tp.split;
-		int ga = g3, gb = g3;
-		if ((uint32_t)ga * tile_waves > ta.total) ga = (int)((ta.total + tile_waves - 1) / tile_waves);
-		if ((uint32_t)gb * tile_waves > tb.total - tb.first) gb = (int)((tb.total - tb.first + tile_waves - 1) / tile_waves);
-		tile_pass(ta, ga);
+		tile_pass(ta, (uint32_t)g3 > ta.total ? (int)ta.total : g3);
 		HIPCHK(hipEventRecord((hipEvent_t)ev_low_, st));
-		dev::k_dec_lowpass<<<dim3(8, (unsigned)lowpass_jobs), 256, 0, st>>>((const dev::DecLowpassJob *)d_lowjobs_);
+		dev::k_dec_lowpass<<<dim3(8, (unsigned)p.lowpass_jobs), 256, 0, st>>>((const dev::DecLowpassJob *)d_lowjobs_);
 		HIPCHK(hipEventRecord((hipEvent_t)ev_l23_, st));
-		tile_pass(tb, gb);
+		tile_pass(tb, (uint32_t)g3 > tb.total - tb.first ? (int)(tb.total - tb.first) : g3);
 	} else tile_pass(tp, g3);
 	if (interlaced_) {
 		// the difference-coded band of every channel back to coefficients: a wave per row for the bands without a peak table, the workgroup-per-band
 		// kernel of round 3 for the few that have one (measured against that kernel for all of them: profiles/r04_o_*)
-		const bool rows = true;
-		if (rows) dev::k_dec_undiff_rows<<<dim3((unsigned)(frames * plan_.num_channels), 32), 64 * dev::DXR_WAVES, 0, st>>>((const dev::DecDiffJob *)d_diffjobs_);
-		dev::k_dec_undiff<<<dim3((unsigned)(frames * plan_.num_channels), dev::DXU_SPLIT), dev::DXU_THREADS, 0, st>>>((const dev::DecDiffJob *)d_diffjobs_, d_errors_, rows ? 1 : 0);
+		dev::k_dec_undiff_rows<<<dim3((unsigned)(p.frames * plan_.num_channels), 32), 64 * dev::DXR_WAVES, 0, st>>>((const dev::DecDiffJob *)d_diffjobs_);
+		dev::k_dec_undiff<<<dim3((unsigned)(p.frames * plan_.num_channels), dev::DXU_SPLIT), dev::DXU_THREADS, 0, st>>>((const dev::DecDiffJob *)d_diffjobs_, d_errors_, 1);
 	}
 	HIPCHK(hipGetLastError());
 	return 0;
@@ -638,7 +616,7 @@ float GpuEntropyDecoder::kernel_ms(int k)
 {
 	float ms = 0;
 	if (k >= 3) {                                                // the chunk-indexed decoder's own kernels
-		if (!timed_ || !dx_ || k > 6) return 0;
+		if (!timed_ || !chunk_indexed() || k > 6) return 0;
 		// 3: k_dec_index, 4: k_dec_chain (+ repair, reindex, tile index), 5: k_dec_tiles, 6: k_dec_plan + k_dec_plan_fill (one workgroup that numbers the chunks: latency, not work)
 		void *a = k == 3 ? ev_[7] : (k == 4 ? ev_[5] : (k == 5 ? ev_[6] : ev_[1])), *b = k == 3 ? ev_[5] : (k == 4 ? ev_[6] : (k == 5 ? ev_[2] : ev_[7]));
 		if (hipEventElapsedTime(&ms, (hipEvent_t)a, (hipEvent_t)b) != hipSuccess) { (void)hipGetLastError(); return 0; }

@@ -352,15 +352,7 @@ def test_batched_device_resident_round_trip(handoff, decoder):
     product syntax, every decoded frame must lie in the oracle's dither interval of its own sample.  handoff=device: the decoder
     reads the samples in HBM and parses them with k_dec_parse; host: samples cross to the host parser and back.  decoder: the
     workgroup-per-band kernel or the lane-per-band one."""
-    L = product()
-    L.cfhd_amd_batch_create.restype = ctypes.c_void_p
-    L.cfhd_amd_batch_create.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int, ctypes.c_int, ctypes.c_int]
-    L.cfhd_amd_batch_upload.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
-    L.cfhd_amd_batch_roundtrip.restype = ctypes.c_longlong
-    L.cfhd_amd_batch_roundtrip.argtypes = [ctypes.c_void_p]
-    L.cfhd_amd_batch_get_sample.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
-    L.cfhd_amd_batch_download_output.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
-    L.cfhd_amd_batch_destroy.argtypes = [ctypes.c_void_p]
+    L = _batch_prototypes(product())
     w, h, n = 640, 360, 5
     frames = [synth_yuy2(w, h, 70 + i)[0] for i in range(n)]
     os.environ["CFHD_AMD_CHUNK"] = "2"
@@ -372,6 +364,33 @@ def test_batched_device_resident_round_trip(handoff, decoder):
     finally:
         del os.environ["CFHD_AMD_CHUNK"], os.environ["CFHD_AMD_HANDOFF"], os.environ["CFHD_AMD_DEC"]
         os.environ.pop("CFHD_AMD_DX_SPECULATE", None)
+
+
+@pytest.mark.parametrize("handoff", ["device", "host"])
+def test_batched_round_trip_par_decoder_many_frames(handoff):
+    """33 frames in one chunk, one more than the workgroup-per-band decoder's latency shape serves: CFHD_AMD_DEC=par runs k_dec_bands_par itself (the five frames in
+    chunks of two above only reach k_dec_bands_par_ll).  Same checks: every sample, every decoded picture."""
+    L = _batch_prototypes(product())
+    w, h, n = 320, 192, 33
+    frames = [synth_yuy2(w, h, 70 + i)[0] for i in range(n)]
+    os.environ["CFHD_AMD_HANDOFF"] = handoff
+    os.environ["CFHD_AMD_DEC"] = "par"
+    try:
+        _batched_round_trip_body(L, w, h, n, frames)
+    finally:
+        del os.environ["CFHD_AMD_HANDOFF"], os.environ["CFHD_AMD_DEC"]
+
+
+def _batch_prototypes(L):
+    L.cfhd_amd_batch_create.restype = ctypes.c_void_p
+    L.cfhd_amd_batch_create.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    L.cfhd_amd_batch_upload.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
+    L.cfhd_amd_batch_roundtrip.restype = ctypes.c_longlong
+    L.cfhd_amd_batch_roundtrip.argtypes = [ctypes.c_void_p]
+    L.cfhd_amd_batch_get_sample.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
+    L.cfhd_amd_batch_download_output.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
+    L.cfhd_amd_batch_destroy.argtypes = [ctypes.c_void_p]
+    return L
 
 
 def _batched_round_trip_body(L, w, h, n, frames):
