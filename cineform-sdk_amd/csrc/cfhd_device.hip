@@ -1040,6 +1040,9 @@ struct InverseRoute {
 // The half-resolution kernel of a 4:2:2 sample's outputs (OutJobs::HalfYuv), for intra batches and two-frame groups
 static InvL1 half_yuv_kernel(const OutputRoute &o) { return o.work == PIX_YU64 ? InvL1::HalfYu64 : (o.work == PIX_YUY2 || o.work == PIX_2VUY ? InvL1::HalfYuv422 : InvL1::HalfRgb24); }
 
+// The interlaced row kernels' four-column shape: whole groups of four luma band columns, band rows of whole 8-byte words (the caller answers for 16-byte output rows)
+static bool frame_quads_fit(int forced, int band_w, const int pitch[3]) { return forced != 1 && band_w % 4 == 0 && band_w >= 8 && pitch[0] % 4 == 0 && pitch[1] % 4 == 0 && pitch[2] % 4 == 0; }
+
 // The kernels of the next launch_entropy() + launch_inverse(), from the prepared batch alone.  What the output needs is route_'s (output_route); which shape serves it --
 // strips against tiles, block lists, quads -- is decided here: the environment switches, the active frame count and the job table are read here and nowhere else.
 InverseRoute DecodeBatch::inverse_route() const
@@ -1052,9 +1055,9 @@ InverseRoute DecodeBatch::inverse_route() const
 	for (int lv = 1; lv < 3; lv++) r.strip_planes[lv - 1] = planes_as_strips(plan_, lv, act);
 	// the register-strip kernels pay from 12 frames of 1080p on (CFHD_AMD_INVERSE=tile / strip, for A/B runs: never / wherever the geometry allows)
 	const bool strips = forced != 1 && (forced != 0 || frames_1080p_equivalent(plan_, act) >= 12.0);
-	auto pitches_divide = [&](int m) { for (int c = 0; c < 3; c++) if (plan_.ch[c].band[0][0].pitch % m) return false; return true; };
+	const int pitch[3] = { b.pitch, plan_.ch[1].band[0][0].pitch, plan_.ch[2].band[0][0].pitch };
 	auto rows_aligned = [&] { return every_frame(n_, [&](int i) { return !((uintptr_t)j.yuv[i].out & 15) && !(j.yuv[i].out_pitch & 15); }); };      // 16-byte stores
-	auto quads = [&] { return forced != 1 && b.width % 4 == 0 && b.width >= 8 && pitches_divide(4) && rows_aligned(); };
+	auto quads = [&] { return frame_quads_fit(forced, b.width, pitch) && rows_aligned(); };
 	// 8-bit 4:2:2 pictures behind the chunk-indexed GPU entropy decoder take the level-1 bands as block lists wherever a 4:2:2 strip kernel runs
 	const bool lists = blocks_env && ent_ready_ && ent_.block_masks(0) && ent_.chunk_indexed() && (out_kind_ == PIX_YUY2 || out_kind_ == PIX_2VUY) && plan_.encoded_format == ENC_YUV422;
 	const int work = route_.work;
@@ -1077,13 +1080,57 @@ InverseRoute DecodeBatch::inverse_route() const
 		if (route_.convert == OutConvert::Rgb16) r.l1 = quads() ? InvL1::FrameRows16 : InvL1::FrameRows16Col;
 		else if (dec_rgb8(work)) r.l1 = InvL1::Yuv422Rgb32;
 		// 4:2:2 pictures: luma bands of whole 16-column blocks, written in 16-byte words (interlaced: band rows of whole 8-coefficient words too)
-		else if (strips && b.width % 16 == 0 && rows_aligned() && (!interlaced_ || pitches_divide(8)))
+		else if (strips && b.width % 16 == 0 && rows_aligned() && (!interlaced_ || !(pitch[0] % 8 || pitch[1] % 8 || pitch[2] % 8)))
 			r.l1 = interlaced_ ? (lists ? InvL1::FrameYuv422StripBlocks : InvL1::FrameYuv422Strip) : (lists ? InvL1::Yuv422StripBlocks : InvL1::Yuv422Strip);
 		else if (interlaced_) r.l1 = quads() ? InvL1::FrameYuv422Quad : InvL1::FrameYuv422;
 		else r.l1 = InvL1::Yuv422;
 		break;
 	}
 	return r;
+}
+
+// The launch of the last level, for intra batches (`frames` active frames) and two-frame groups alike: every InvL1 kernel and every grid formula is here and nowhere else.
+struct LastLevel {
+	int band_w, band_h, out_rows, frames; bool interlaced;      // the luma band of level 1; the rows of a half-resolution output; grid z
+	const dev::InvYuvJob *yuv; const dev::InvPlaneJob *l1; const dev::HalfYuvJob *half; const dev::HalfPackedJob *halfp;      // job tables (null: the caller has none)
+	int out_channels, words_per_position;                       // of the packed 16-bit outputs
+};
+static int launch_last_level(InvL1 k, const LastLevel &g, uint32_t dither_seed, hipStream_t st)
+{
+	const dim3 tiles((g.band_w + dev::ITW - 1) / dev::ITW, (g.band_h + dev::ITH - 1) / dev::ITH, g.frames);      // the LDS-tiled kernels: one workgroup per tile, all components
+	const int sr = g.interlaced ? dev::SRI : dev::SR;
+	const dim3 strips((g.band_w / dev::SBLK + dev::SSEG - 1) / dev::SSEG, (g.band_h + sr - 1) / sr, g.frames);      // the 4:2:2 strip kernels: segments of 124 luma blocks, sr band rows
+	auto rows = [&](int cols_per_thread, int nrows) { return dim3((g.band_w / cols_per_thread + dev::NTHREADS - 1) / dev::NTHREADS, nrows, g.frames); };      // the row kernels: one thread per group of band columns
+	auto unserved = [] { g_err = "two-frame groups: output not served"; return -1; };      // (a kernel without its job table: GopBatch::route() yields none)
+	switch (k) {
+	case InvL1::Refused: break;                         // (left by the callers)
+	case InvL1::FrameRows16: if (!g.yuv) return unserved(); dev::k_inv_frame_yuv422_rows16<<<rows(4, g.band_h), dev::NTHREADS, 0, st>>>(g.yuv); break;
+	case InvL1::FrameRows16Col: if (!g.yuv) return unserved(); dev::k_inv_frame_yuv422_rows16_col<<<rows(2, g.band_h), dev::NTHREADS, 0, st>>>(g.yuv); break;
+	// half resolution: the level-1 lowpass planes are the picture, no last level
+	case InvL1::HalfRgb24: if (!g.half) return unserved(); dev::k_half_rgb24<<<rows(2, g.out_rows), dev::NTHREADS, 0, st>>>(g.half); break;
+	case InvL1::HalfRgb: if (!g.halfp) return unserved(); dev::k_half_rgb<<<rows(1, g.out_rows), dev::NTHREADS, 0, st>>>(g.halfp, dither_seed); break;
+	case InvL1::HalfYu64: if (!g.half) return unserved(); dev::k_half_yu64<<<rows(2, g.out_rows), dev::NTHREADS, 0, st>>>(g.half); break;
+	case InvL1::HalfPacked16: if (!g.halfp) return unserved(); dev::k_half_packed16<<<rows(8, g.out_rows), dev::NTHREADS, 0, st>>>(g.halfp); break;
+	case InvL1::HalfYuv422: if (!g.half) return unserved(); dev::k_half_yuv422<<<rows(8, g.out_rows), dev::NTHREADS, 0, st>>>(g.half); break;
+	case InvL1::Packed16Strip: {
+		if (!g.l1) return unserved();
+		const int nseg = (g.band_w / 4 + dev::PSTEP - 1) / dev::PSTEP, nstrips = (g.band_h + dev::QSR - 1) / dev::QSR, waves = g.frames * nseg * nstrips;
+		if (g.out_channels == 4) dev::k_inv_packed16_strip<4><<<(waves + 3) / 4, dev::NTHREADS, 0, st>>>(g.l1, g.frames, nseg, nstrips);
+		else dev::k_inv_packed16_strip<3><<<(waves + 3) / 4, dev::NTHREADS, 0, st>>>(g.l1, g.frames, nseg, nstrips);
+		break;
+	}
+	case InvL1::Yuv422Rgb32: if (!g.yuv) return unserved(); dev::k_inv_yuv422_rgb32<<<tiles, dev::NTHREADS, 0, st>>>(g.yuv); break;
+	case InvL1::Rgb10: if (!g.l1) return unserved(); dev::k_inv_rgb10<<<tiles, dev::NTHREADS, 0, st>>>(g.l1); break;
+	case InvL1::Packed16: if (!g.l1) return unserved(); dev::k_inv_packed16<<<tiles, dev::NTHREADS, 0, st>>>(g.l1, g.out_channels, g.words_per_position, dither_seed); break;
+	case InvL1::FrameYuv422StripBlocks: if (!g.yuv) return unserved(); dev::k_inv_frame_yuv422_strip_blocks<<<strips, dev::NTHREADS, 0, st>>>(g.yuv, dither_seed); break;
+	case InvL1::FrameYuv422Strip: if (!g.yuv) return unserved(); dev::k_inv_frame_yuv422_strip<<<strips, dev::NTHREADS, 0, st>>>(g.yuv, dither_seed); break;
+	case InvL1::FrameYuv422Quad: if (!g.yuv) return unserved(); dev::k_inv_frame_yuv422_quad<<<rows(4, g.band_h), dev::NTHREADS, 0, st>>>(g.yuv, dither_seed); break;
+	case InvL1::FrameYuv422: if (!g.yuv) return unserved(); dev::k_inv_frame_yuv422<<<rows(2, g.band_h), dev::NTHREADS, 0, st>>>(g.yuv, dither_seed); break;
+	case InvL1::Yuv422StripBlocks: if (!g.yuv) return unserved(); dev::k_inv_yuv422_strip_blocks<<<strips, dev::NTHREADS, 0, st>>>(g.yuv, dither_seed); break;
+	case InvL1::Yuv422Strip: if (!g.yuv) return unserved(); dev::k_inv_yuv422_strip<<<strips, dev::NTHREADS, 0, st>>>(g.yuv, dither_seed); break;
+	case InvL1::Yuv422: if (!g.yuv) return unserved(); dev::k_inv_yuv422<<<tiles, dev::NTHREADS, 0, st>>>(g.yuv, dither_seed); break;
+	}
+	return 0;
 }
 
 const char *DecodeBatch::level_kernel(int level) const
@@ -1145,41 +1192,9 @@ int DecodeBatch::launch_inverse(uint32_t dither_seed)
 		HIPCHK(hipEventRecord((hipEvent_t)evl_[1], st));
 	}
 	const BandDesc &b = plan_.ch[0].band[0][0];
-	const dim3 tiles((b.width + dev::ITW - 1) / dev::ITW, (b.height + dev::ITH - 1) / dev::ITH, act);      // the LDS-tiled kernels: one workgroup per tile, all components
-	const int sr = interlaced_ ? dev::SRI : dev::SR;
-	const dim3 strips((b.width / dev::SBLK + dev::SSEG - 1) / dev::SSEG, (b.height + sr - 1) / sr, act);      // the 4:2:2 strip kernels: segments of 124 luma blocks, sr band rows
-	auto rows = [&](int cols_per_thread, int nrows) { return dim3((b.width / cols_per_thread + dev::NTHREADS - 1) / dev::NTHREADS, nrows, act); };      // the row kernels: one thread per group of band columns
-	switch (r.l1) {
-	case InvL1::Refused: break;                         // (left above)
-	case InvL1::FrameRows16: dev::k_inv_frame_yuv422_rows16<<<rows(4, b.height), dev::NTHREADS, 0, st>>>(j.yuv); break;
-	case InvL1::FrameRows16Col: dev::k_inv_frame_yuv422_rows16_col<<<rows(2, b.height), dev::NTHREADS, 0, st>>>(j.yuv); break;
-	case InvL1::HalfRgb24: dev::k_half_rgb24<<<rows(2, out_rows_), dev::NTHREADS, 0, st>>>(j.half); break;
-	case InvL1::HalfRgb: dev::k_half_rgb<<<rows(1, out_rows_), dev::NTHREADS, 0, st>>>(j.halfp, dither_seed); break;
-	case InvL1::HalfYu64: dev::k_half_yu64<<<rows(2, out_rows_), dev::NTHREADS, 0, st>>>(j.half); break;
-	case InvL1::HalfPacked16: dev::k_half_packed16<<<rows(8, out_rows_), dev::NTHREADS, 0, st>>>(j.halfp); break;
-	case InvL1::HalfYuv422: dev::k_half_yuv422<<<rows(8, out_rows_), dev::NTHREADS, 0, st>>>(j.half); break;
-	case InvL1::Packed16Strip: {
-		const int nseg = (b.width / 4 + dev::PSTEP - 1) / dev::PSTEP, nstrips = (b.height + dev::QSR - 1) / dev::QSR, waves = act * nseg * nstrips;
-		if (dec_out_channels(route_.work, plan_) == 4) dev::k_inv_packed16_strip<4><<<(waves + 3) / 4, dev::NTHREADS, 0, st>>>(j.l1, act, nseg, nstrips);
-		else dev::k_inv_packed16_strip<3><<<(waves + 3) / 4, dev::NTHREADS, 0, st>>>(j.l1, act, nseg, nstrips);
-		break;
-	}
-	case InvL1::Yuv422Rgb32: dev::k_inv_yuv422_rgb32<<<tiles, dev::NTHREADS, 0, st>>>(j.yuv); break;
-	case InvL1::Rgb10: dev::k_inv_rgb10<<<tiles, dev::NTHREADS, 0, st>>>(j.l1); break;
-	case InvL1::Packed16: {
-		const int onch = dec_out_channels(route_.work, plan_);
-		dev::k_inv_packed16<<<tiles, dev::NTHREADS, 0, st>>>(j.l1, onch, dec_words_per_position(route_.work, onch), dither_seed);
-		break;
-	}
-	// (interlaced, half resolution was served above: the level-1 lowpass planes need no inverse frame transform)
-	case InvL1::FrameYuv422StripBlocks: dev::k_inv_frame_yuv422_strip_blocks<<<strips, dev::NTHREADS, 0, st>>>(j.yuv, dither_seed); break;
-	case InvL1::FrameYuv422Strip: dev::k_inv_frame_yuv422_strip<<<strips, dev::NTHREADS, 0, st>>>(j.yuv, dither_seed); break;
-	case InvL1::FrameYuv422Quad: dev::k_inv_frame_yuv422_quad<<<rows(4, b.height), dev::NTHREADS, 0, st>>>(j.yuv, dither_seed); break;
-	case InvL1::FrameYuv422: dev::k_inv_frame_yuv422<<<rows(2, b.height), dev::NTHREADS, 0, st>>>(j.yuv, dither_seed); break;
-	case InvL1::Yuv422StripBlocks: dev::k_inv_yuv422_strip_blocks<<<strips, dev::NTHREADS, 0, st>>>(j.yuv, dither_seed); break;
-	case InvL1::Yuv422Strip: dev::k_inv_yuv422_strip<<<strips, dev::NTHREADS, 0, st>>>(j.yuv, dither_seed); break;
-	case InvL1::Yuv422: dev::k_inv_yuv422<<<tiles, dev::NTHREADS, 0, st>>>(j.yuv, dither_seed); break;
-	}
+	const int onch = dec_out_channels(route_.work, plan_);
+	rc = launch_last_level(r.l1, { b.width, b.height, out_rows_, act, interlaced_, j.yuv, j.l1, j.half, j.halfp, onch, dec_words_per_position(route_.work, onch) }, dither_seed, st);
+	if (rc) return rc;
 	launch_convert(route_, d_tmp_, tmp_pitch_, tmp_frame_bytes_, d_out_, out_pitch_, frame_bytes_, half_ ? plan_.width / 2 : plan_.width, half_ ? plan_.display_height / 2 : plan_.display_height,
 	               0, act, plan_.color_matrix, dither_seed, d_restore_, st);
 	HIPCHK(hipGetLastError());
@@ -1354,11 +1369,9 @@ GopRoute GopBatch::route() const
 	case OutJobs::Planes16: return { plan_.interlaced ? InvL1::Refused : InvL1::Packed16, o };      // (YU64, v210 and RG24 of interlaced groups are refused at the C ABI)
 	case OutJobs::Yuv: {
 		if (o.convert != OutConvert::Rgb16) return { dec_rgb8(o.work) ? InvL1::Yuv422Rgb32 : (plan_.interlaced ? InvL1::FrameYuv422 : InvL1::Yuv422), o };
-		const int w = plan_.ch[0].w[0].width;
 		// (the scratch rows are 16-byte aligned: 4 * width bytes, the width a multiple of 16: build_gop_plan)
-		bool quads = shape_override("CFHD_AMD_INVERSE") != 1 && w % 4 == 0 && w >= 8;
-		for (int c = 0; c < 3; c++) quads = quads && plan_.ch[c].w[0].pitch % 4 == 0;
-		return { quads ? InvL1::FrameRows16 : InvL1::FrameRows16Col, o };
+		const int pitch[3] = { plan_.ch[0].w[0].pitch, plan_.ch[1].w[0].pitch, plan_.ch[2].w[0].pitch };
+		return { frame_quads_fit(shape_override("CFHD_AMD_INVERSE"), plan_.ch[0].w[0].width, pitch) ? InvL1::FrameRows16 : InvL1::FrameRows16Col, o };
 	}
 	case OutJobs::HalfPacked: break;                     // (no output of a 4:2:2 sample)
 	}
@@ -1604,23 +1617,10 @@ int GopBatch::launch_inverse(uint32_t dither_seed, bool coeffs_on_device)
 	dev::k_inv_plane<<<dim3((top.width + dev::ITW - 1) / dev::ITW, (top.height + dev::ITH - 1) / dev::ITH, 3), dev::NTHREADS, 0, st>>>(j.itop);
 	dev::k_inv_plane<<<dim3((mid.width + dev::ITW - 1) / dev::ITW, (mid.height + dev::ITH - 1) / dev::ITH, 6), dev::NTHREADS, 0, st>>>(j.imid);
 	dev::k_gop_temporal_inv<<<dim3((unsigned)((t.pitch * t.height / 2 + dev::NTHREADS - 1) / dev::NTHREADS), 3), dev::NTHREADS, 0, st>>>(j.temp);
-	// the last level of both frames (grid z = 2), as DecodeBatch::launch_inverse launches the same kernels for one frame each
+	// the last level of both frames (grid z = 2): the intra path's kernels through the intra path's launcher
 	const GopRoute r = route();
-	const dim3 tiles((l1.width + dev::ITW - 1) / dev::ITW, (l1.height + dev::ITH - 1) / dev::ITH, 2);
-	auto rows = [&](int cols_per_thread, int nrows) { return dim3((l1.width / cols_per_thread + dev::NTHREADS - 1) / dev::NTHREADS, nrows, 2); };
-	switch (r.l1) {
-	case InvL1::Yuv422: dev::k_inv_yuv422<<<tiles, dev::NTHREADS, 0, st>>>(j.iyuv, dither_seed); break;
-	case InvL1::FrameYuv422: dev::k_inv_frame_yuv422<<<rows(2, l1.height), dev::NTHREADS, 0, st>>>(j.iyuv, dither_seed); break;
-	case InvL1::Yuv422Rgb32: dev::k_inv_yuv422_rgb32<<<tiles, dev::NTHREADS, 0, st>>>(j.iyuv); break;
-	case InvL1::Packed16: dev::k_inv_packed16<<<tiles, dev::NTHREADS, 0, st>>>(j.l1, 3, dec_words_per_position(PIX_YU64, 3), dither_seed); break;
-	case InvL1::FrameRows16: dev::k_inv_frame_yuv422_rows16<<<rows(4, l1.height), dev::NTHREADS, 0, st>>>(j.iyuv); break;
-	case InvL1::FrameRows16Col: dev::k_inv_frame_yuv422_rows16_col<<<rows(2, l1.height), dev::NTHREADS, 0, st>>>(j.iyuv); break;
-	// (half resolution: the level-1 lowpass planes of both frames, no last level)
-	case InvL1::HalfYuv422: dev::k_half_yuv422<<<rows(8, rows_), dev::NTHREADS, 0, st>>>(j.half); break;
-	case InvL1::HalfYu64: dev::k_half_yu64<<<rows(2, rows_), dev::NTHREADS, 0, st>>>(j.half); break;
-	case InvL1::HalfRgb24: dev::k_half_rgb24<<<rows(2, rows_), dev::NTHREADS, 0, st>>>(j.half); break;
-	default: g_err = "two-frame groups: output not served"; return -1;
-	}
+	const int rc = launch_last_level(r.l1, { l1.width, l1.height, rows_, 2, plan_.interlaced, j.iyuv, j.l1, j.half, nullptr, 3, dec_words_per_position(PIX_YU64, 3) }, dither_seed, st);
+	if (rc) return rc;
 	// the conversion runs over both frames in one launch -- two when frame 0 takes another matrix than frame 1 (fill_jobs; v210 takes none); frame 1 alone then runs
 	// as z = 0 with the seed that gives it the dither of z = 1
 	auto convert = [&](int f, int nf, int m) {

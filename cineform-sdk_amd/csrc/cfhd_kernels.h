@@ -2573,12 +2573,21 @@ __global__ void __launch_bounds__(NTHREADS) k_fwd_frame_yuv422_strip(const FwdFr
 }
 
 // =============================================================================================
-// Interlaced last level: the inverse of k_fwd_frame_yuv422 (Codec/decoder.c:21493 TransformInverseFrameToYUV, :24304 threaded;
-// Codec/temporal.c:5961 InvertInterlacedRow16s10bitToYUV, :6498 ToUYVY).  Band row r of the level-1 wavelet gives two picture rows: the
-// horizontal synthesis of (LL, LH) is the temporal lowpass row, that of (HL, HH) -- HL un-differenced by k_dec_undiff -- the temporal
-// highpass row (spatial.c:19302 InvertHorizontalRow16s8sTo16sBuffered: the usual 2/6 synthesis, >> 1, saturated); row 2r = low - high,
-// row 2r + 1 = low + high (saturating), then 10 -> 8 bits like every other 4:2:2 output.  No vertical filter, hence no halo rows and no
-// LDS: one thread per chroma column (two luma columns: 4 + 2 + 2 samples = 8 bytes of each of the two rows), any width.
+// Interlaced last level as row kernels: the inverse of k_fwd_frame_yuv422 (Codec/decoder.c:21493 TransformInverseFrameToYUV, :24304 threaded;
+// Codec/temporal.c:5961 InvertInterlacedRow16s10bitToYUV, :6498 ToUYVY; 16-bit rows: decoder.c:26488 -> :22027 TransformInverseFrameToRow16u,
+// temporal.c:7087 InvertInterlacedRow16sToRow16u).  Band row r of the level-1 wavelet gives two picture rows: the horizontal synthesis of (LL, LH)
+// is the temporal lowpass row, that of (HL, HH) -- HL un-differenced by k_dec_undiff -- the temporal highpass row (spatial.c:19302
+// InvertHorizontalRow16s8sTo16sBuffered, :19803 InvertHorizontalRow16s: the usual 2/6 synthesis, >> 1, saturated); row 2r = low - high,
+// row 2r + 1 = low + high.  No vertical filter, hence no halo rows and no LDS.  One body (inv_frame_yuv422_rows) in two widths and two outputs:
+//   P = 1: one chroma band column (two luma columns) per thread, any width -- the geometries the wide shape does not serve and CFHD_AMD_INVERSE=tile;
+//   P = 2: two chroma (four luma) band columns per thread: the bands are read with 8-byte loads, the columns next to a thread's own come from its
+//          neighbours' registers (the first and last lane of a wave fetch theirs); needs the luma band width to be a multiple of 4 and 8-byte
+//          aligned band rows, which every frame the codec accepts has, and 16-byte aligned output rows;
+//   8-bit YUY2 / UYVY: saturating difference / sum, then 10 -> 8 bits like every other 4:2:2 output (8 P bytes of a picture row per thread, one store);
+//   ROWS16: the 16-bit rows of the RG48 / b64a / BGRA / BGRa outputs, as YU64 words Y0 C1 Y1 C2 (channel 1 = V, channel 2 = U) into the scratch
+//          frame that k_yu64_to_rgb16 converts; no dither; 16 P bytes per thread in 16-byte stores.  Restated in tests/interlaced_rgb_model.py, pinned on
+//          the reference decoder.
+// Both widths write the same bytes (same dither bit per sample).  Dense bands only (no block lists); the first display_height rows only.
 // =============================================================================================
 __device__ __forceinline__ void frame_synth(const int16_t *lo, const int16_t *hi, int c, int w, int &even, int &odd)
 {
@@ -2590,56 +2599,11 @@ __device__ __forceinline__ void frame_synth(const int16_t *lo, const int16_t *hi
 	even = sat16(e >> 1); odd = sat16(o >> 1);
 }
 
-__global__ void __launch_bounds__(NTHREADS) k_inv_frame_yuv422(const InvYuvJob *jobs, uint32_t launch_seed)
-{
-	const InvYuvJob &job = jobs[blockIdx.z];
-	const int w = job.width, cw = w >> 1;                // luma / chroma band columns
-	const int cc = (int)(blockIdx.x * NTHREADS + threadIdx.x), r = blockIdx.y;
-	if (cc >= cw || r >= job.height) return;
-	const uint32_t seed = job.dither_seed ^ launch_seed;
-	const int sh = job.shift;
-	// temporal low / high samples: 4 luma (columns 2cc, 2cc + 1: even, odd each), 2 V, 2 U
-	int tl[8], th[8];
-	{
-		const size_t o = (size_t)r * job.band_pitch[0];
-		frame_synth(job.band[0][0] + o, job.band[0][1] + o, 2 * cc, w, tl[0], tl[1]);
-		frame_synth(job.band[0][0] + o, job.band[0][1] + o, 2 * cc + 1, w, tl[2], tl[3]);
-		frame_synth(job.band[0][2] + o, job.band[0][3] + o, 2 * cc, w, th[0], th[1]);
-		frame_synth(job.band[0][2] + o, job.band[0][3] + o, 2 * cc + 1, w, th[2], th[3]);
-	}
-#pragma unroll
-	for (int x = 0; x < 2; x++) {                         // V, U
-		const size_t o = (size_t)r * job.band_pitch[1 + x];
-		frame_synth(job.band[1 + x][0] + o, job.band[1 + x][1] + o, cc, cw, tl[4 + 2 * x], tl[5 + 2 * x]);
-		frame_synth(job.band[1 + x][2] + o, job.band[1 + x][3] + o, cc, cw, th[4 + 2 * x], th[5 + 2 * x]);
-	}
-#pragma unroll
-	for (int par = 0; par < 2; par++) {
-		const int orow = 2 * r + par;
-		if (orow >= job.display_height) continue;
-		const uint32_t dz = sh >= 2 ? dither422_column(seed, orow, cc) : 0u;      // same bit assignment as the progressive kernels
-		uint32_t b[8];
-#pragma unroll
-		for (int i = 0; i < 8; i++) {
-			const int v = par ? adds16(tl[i], th[i]) : subs16(tl[i], th[i]);
-			b[i] = to8(v, sh, (int)((dz >> (i == 5 ? 6 : (i == 6 ? 5 : i))) & 1u));     // (b[] holds v0, v1, u0, u1 behind the luma samples, the dither byte v0, u0, v1, u1); the temporal lowpass is the sum of the two rows: clamp at zero, halve, dither, >> shift, saturate (temporal.c:6071-6120)
-		}
-		const uint32_t y0 = b[0], y1 = b[1], y2 = b[2], y3 = b[3], v0 = b[4], v1 = b[5], u0 = b[6], u1 = b[7];
-		uint2 o2;
-		if (job.uyvy) { o2.x = u0 | (y0 << 8) | (v0 << 16) | (y1 << 24); o2.y = u1 | (y2 << 8) | (v1 << 16) | (y3 << 24); }
-		else { o2.x = y0 | (u0 << 8) | (y1 << 16) | (v0 << 24); o2.y = y2 | (u1 << 8) | (y3 << 16) | (v1 << 24); }
-		*(uint2 *)(job.out + (size_t)orow * job.out_pitch + 8 * (size_t)cc) = o2;
-	}
-}
-
-// The same, four luma band columns (eight pixels of both picture rows) per thread: the bands are read with 8-byte loads, the columns next
-// to a thread's four come from its neighbours' registers (the first and last lane of a wave fetch theirs), and each picture row leaves as one
-// 16-byte store per thread.  Same bytes as k_inv_frame_yuv422 (same dither bit per sample); needs the luma band width to be a multiple of 4
-// and 8-byte aligned band rows, which every frame the codec accepts has.
 struct Quad16 { int v[4]; };
 __device__ __forceinline__ Quad16 quad_load(const int16_t *p) { const uint2 q = *(const uint2 *)p; Quad16 r; r.v[0] = lo16(q.x); r.v[1] = hi16(q.x); r.v[2] = lo16(q.y); r.v[3] = hi16(q.y); return r; }
 __device__ __forceinline__ Quad16 pair_load(const int16_t *p) { const uint32_t q = *(const uint32_t *)p; Quad16 r; r.v[0] = lo16(q); r.v[1] = hi16(q); r.v[2] = 0; r.v[3] = 0; return r; }
-// horizontal synthesis of n (4 or 2) adjacent columns starting at band column c: out[2k], out[2k + 1] = even, odd sample of column c + k
+// horizontal synthesis of N (4 or 2) adjacent columns starting at band column c: out[2k], out[2k + 1] = even, odd sample of column c + k.  The band's first
+// column is a thread's first, its last a thread's last (w % N == 0); their far taps lie outside a run of two: they are `right` / `left` then.
 template <int N>
 __device__ __forceinline__ void frame_synth_run(const Quad16 &lo, const Quad16 &hi, int left, int right, int c, int w, int *out)
 {
@@ -2648,108 +2612,73 @@ __device__ __forceinline__ void frame_synth_run(const Quad16 &lo, const Quad16 &
 		const int col = c + k;
 		const int lm1 = k ? lo.v[k - 1] : left, lp1 = k + 1 < N ? lo.v[k + 1] : right;
 		int e, o;
-		if (col == 0) inv_horiz(0, lo.v[k], lp1, k + 2 < N ? lo.v[k + 2] : right, hi.v[k], 0, e, o);      // (k + 2 < N: always, the first column is a thread's first)
-		else if (col == w - 1) inv_horiz(lm1, lo.v[k], 0, k >= 2 ? lo.v[k - 2] : left, hi.v[k], 2, e, o);
+		if (k == 0 && col == 0) inv_horiz(0, lo.v[k], lp1, k + 2 < N ? lo.v[k + 2] : right, hi.v[k], 0, e, o);
+		else if (k == N - 1 && col == w - 1) inv_horiz(lm1, lo.v[k], 0, k >= 2 ? lo.v[k - 2] : left, hi.v[k], 2, e, o);
 		else inv_horiz(lm1, lo.v[k], lp1, 0, hi.v[k], 1, e, o);
 		out[2 * k] = sat16(e >> 1); out[2 * k + 1] = sat16(o >> 1);
 	}
 }
-// temporal low / high samples of band row r, luma band columns 4t .. 4t + 3 and chroma band columns 2t, 2t + 1: tl / th[0..7] luma (even, odd of each column),
-// [8..11] V, [12..15] U.  Every lane of the wave calls it (the neighbour columns come by lane exchange); `have` says whether the lane's columns exist.
-__device__ __forceinline__ void frame_quad_samples(const InvYuvJob &job, int t, int r, bool have, int lane, int *tl, int *th)
+// N band columns from column c of one (lowpass, highpass) band pair of width bw: a thread's 2 P luma or P chroma columns.  P = 2: every lane of the wave
+// comes here (the neighbour columns come by lane exchange); `have` says whether the lane's columns exist.
+template <int P, int N>
+__device__ __forceinline__ void frame_synth_columns(const int16_t *lo, const int16_t *hi, int c, int bw, bool have, int *out)
+{
+	if (P == 1) {
+#pragma unroll
+		for (int k = 0; k < N; k++) if (have) frame_synth(lo, hi, c + k, bw, out[2 * k], out[2 * k + 1]);
+		return;
+	}
+	const int lane = (int)(threadIdx.x & 63u);
+	Quad16 L = { { 0, 0, 0, 0 } }, H = { { 0, 0, 0, 0 } };
+	if (have) { L = N == 4 ? quad_load(lo + c) : pair_load(lo + c); H = N == 4 ? quad_load(hi + c) : pair_load(hi + c); }
+	int left = __shfl_up(L.v[N - 1], 1u), right = __shfl_down(L.v[0], 1u);
+	if (have && lane == 0 && c > 0) left = lo[c - 1];
+	if (have && (lane == 63 || c + N >= bw) && c + N < bw) right = lo[c + N];
+	if (have) frame_synth_run<N>(L, H, left, right, c, bw, out);
+}
+// temporal low / high samples of band row r, chroma band columns P t .. P t + P - 1 and their luma columns: tl / th [0, 4P) luma (even, odd of each column),
+// [4P, 6P) V, [6P, 8P) U
+template <int P>
+__device__ __forceinline__ void frame_row_samples(const InvYuvJob &job, int t, int r, bool have, int *tl, int *th)
 {
 	const int w = job.width, cw = w >> 1;
-	const int c = 4 * t, cc = 2 * t;                          // first luma / chroma band column of this thread
 	// one (lowpass, highpass) band pair at a time: luma (LL, LH) -> temporal low, (HL, HH) -> temporal high, then the same for V and U
 #pragma unroll
 	for (int pair = 0; pair < 2; pair++) {
 		int *dst = pair ? th : tl;
-		{
-			const size_t o = (size_t)r * job.band_pitch[0];
-			const int16_t *lo = job.band[0][2 * pair] + o, *hi = job.band[0][2 * pair + 1] + o;
-			Quad16 L = { { 0, 0, 0, 0 } }, H = { { 0, 0, 0, 0 } };
-			if (have) { L = quad_load(lo + c); H = quad_load(hi + c); }
-			int left = __shfl_up(L.v[3], 1u), right = __shfl_down(L.v[0], 1u);
-			if (have && lane == 0 && c > 0) left = lo[c - 1];
-			if (have && (lane == 63 || c + 4 >= w) && c + 4 < w) right = lo[c + 4];
-			if (have) frame_synth_run<4>(L, H, left, right, c, w, dst);
-		}
+		const size_t o = (size_t)r * job.band_pitch[0];
+		frame_synth_columns<P, 2 * P>(job.band[0][2 * pair] + o, job.band[0][2 * pair + 1] + o, 2 * P * t, w, have, dst);
 #pragma unroll
 		for (int x = 0; x < 2; x++) {
-			const size_t o = (size_t)r * job.band_pitch[1 + x];
-			const int16_t *lo = job.band[1 + x][2 * pair] + o, *hi = job.band[1 + x][2 * pair + 1] + o;
-			Quad16 L = { { 0, 0, 0, 0 } }, H = { { 0, 0, 0, 0 } };
-			if (have) { L = pair_load(lo + cc); H = pair_load(hi + cc); }
-			int left = __shfl_up(L.v[1], 1u), right = __shfl_down(L.v[0], 1u);
-			if (have && lane == 0 && cc > 0) left = lo[cc - 1];
-			if (have && (lane == 63 || cc + 2 >= cw) && cc + 2 < cw) right = lo[cc + 2];
-			if (have) {
-				// two columns: the far taps of the first / last column of the band lie outside a pair
-				int out4[4];
-#pragma unroll
-				for (int k = 0; k < 2; k++) {
-					const int col = cc + k;
-					const int lm1 = k ? L.v[0] : left, lp1 = k ? right : L.v[1];
-					int e, od;
-					if (col == 0) inv_horiz(0, L.v[0], L.v[1], right, H.v[0], 0, e, od);
-					else if (col == cw - 1) inv_horiz(L.v[0], L.v[1], 0, left, H.v[1], 2, e, od);
-					else inv_horiz(lm1, L.v[k], lp1, 0, H.v[k], 1, e, od);
-					out4[2 * k] = sat16(e >> 1); out4[2 * k + 1] = sat16(od >> 1);
-				}
-#pragma unroll
-				for (int k = 0; k < 4; k++) dst[8 + 4 * x + k] = out4[k];
-			}
+			const size_t oc = (size_t)r * job.band_pitch[1 + x];
+			frame_synth_columns<P, P>(job.band[1 + x][2 * pair] + oc, job.band[1 + x][2 * pair + 1] + oc, P * t, cw, have, dst + 4 * P + 2 * P * x);
 		}
-	}
-}
-__global__ void __launch_bounds__(NTHREADS) k_inv_frame_yuv422_quad(const InvYuvJob *jobs, uint32_t launch_seed)
-{
-	const InvYuvJob &job = jobs[blockIdx.z];
-	const int w = job.width;
-	const int t = (int)(blockIdx.x * NTHREADS + threadIdx.x), r = blockIdx.y;
-	const int cc = 2 * t;                                     // first chroma band column of this thread
-	const bool have = 4 * t < w && r < job.height;
-	const int lane = (int)(threadIdx.x & 63u);
-	const uint32_t seed = job.dither_seed ^ launch_seed;
-	const int sh = job.shift;
-	int tl[16], th[16];                                       // temporal low / high samples: 8 luma, 4 V, 4 U
-	frame_quad_samples(job, t, r, have, lane, tl, th);
-	if (!have) return;
-#pragma unroll
-	for (int par = 0; par < 2; par++) {
-		const int orow = 2 * r + par;
-		if (orow >= job.display_height) continue;
-		uint32_t words[4];
-#pragma unroll
-		for (int half = 0; half < 2; half++) {                 // chroma column cc + half: the bits the one-column kernel uses for it
-			const int ccol = cc + half;
-			const uint32_t dz = sh >= 2 ? dither422_column(seed, orow, ccol) : 0u;
-			uint32_t b[8];
-#pragma unroll
-			for (int i = 0; i < 8; i++) {
-				// sample order of the one-column kernel: four luma (columns 2 ccol, 2 ccol + 1: even, odd each), two V, two U
-				const int idx = i < 4 ? 4 * half + i : (i < 6 ? 8 + 2 * half + (i - 4) : 12 + 2 * half + (i - 6));
-				const int v = par ? adds16(tl[idx], th[idx]) : subs16(tl[idx], th[idx]);
-				b[i] = to8(v, sh, (int)((dz >> (i == 5 ? 6 : (i == 6 ? 5 : i))) & 1u));
-			}
-			const uint32_t y0 = b[0], y1 = b[1], y2 = b[2], y3 = b[3], v0 = b[4], v1 = b[5], u0 = b[6], u1 = b[7];
-			if (job.uyvy) { words[2 * half] = u0 | (y0 << 8) | (v0 << 16) | (y1 << 24); words[2 * half + 1] = u1 | (y2 << 8) | (v1 << 16) | (y3 << 24); }
-			else { words[2 * half] = y0 | (u0 << 8) | (y1 << 16) | (v0 << 24); words[2 * half + 1] = y2 | (u1 << 8) | (y3 << 16) | (v1 << 24); }
-		}
-		uint4 o4; o4.x = words[0]; o4.y = words[1]; o4.z = words[2]; o4.w = words[3];
-		*(uint4 *)(job.out + (size_t)orow * job.out_pitch + 16 * (size_t)t) = o4;
 	}
 }
 
-// =============================================================================================
-// Interlaced last level into 16-bit rows: RG48 / b64a / BGRA / BGRa output of interlaced 4:2:2 samples (Codec/decoder.c:26488 -> :22027
-// TransformInverseFrameToRow16u).  The temporal low / high rows are the ones k_inv_frame_yuv422 builds (spatial.c:19803 InvertHorizontalRow16s: the same
-// 2/6 synthesis, >> 1, saturated); temporal.c:7087 InvertInterlacedRow16sToRow16u then gives row 2r = low - high, row 2r + 1 = low + high as 16-bit words:
-// the output columns below output_width - output_width % 8 of a channel take the vector body (saturating difference / sum, clamped by the adds / subs_epu16
-// pair with protect 2047 -- 511 at 8-bit precision --, >> 1, << 6 -- << 8 --), the rest the scalar tail ((low -+ high) / 2, clamped to [0, 1023] -- [0, 255] --,
-// << 6 -- << 8 --).  Written as YU64 words Y0 C1 Y1 C2 (channel 1 = V, channel 2 = U) into the scratch frame that k_yu64_to_rgb16 converts; no dither.
-// Restated in tests/interlaced_rgb_model.py, pinned on the reference decoder.  Dense bands only (no block lists); the first display_height rows only.
-// =============================================================================================
+// 8-bit finisher: the YUY2 / UYVY word pair of a thread's chroma band column `half` (band column ccol) in picture row orow of parity par
+template <int P>
+__device__ __forceinline__ void frame_column_yuv8(const int *tl, const int *th, int half, int ccol, int orow, int par, int sh, uint32_t seed, int uyvy, uint32_t *words)
+{
+	const uint32_t dz = sh >= 2 ? dither422_column(seed, orow, ccol) : 0u;      // same bit assignment as the progressive kernels
+	uint32_t b[8];
+#pragma unroll
+	for (int i = 0; i < 8; i++) {
+		// the column's four luma samples (columns 2 ccol, 2 ccol + 1: even, odd each), two V, two U
+		const int idx = i < 4 ? 4 * half + i : (i < 6 ? 4 * P + 2 * half + (i - 4) : 6 * P + 2 * half + (i - 6));
+		const int v = par ? adds16(tl[idx], th[idx]) : subs16(tl[idx], th[idx]);
+		// (b[] holds v0, v1, u0, u1 behind the luma samples, the dither byte v0, u0, v1, u1); the temporal lowpass is the sum of the two rows: clamp at zero, halve,
+		// dither, >> shift, saturate (temporal.c:6071-6120)
+		b[i] = to8(v, sh, (int)((dz >> (i == 5 ? 6 : (i == 6 ? 5 : i))) & 1u));
+	}
+	const uint32_t y0 = b[0], y1 = b[1], y2 = b[2], y3 = b[3], v0 = b[4], v1 = b[5], u0 = b[6], u1 = b[7];
+	if (uyvy) { words[0] = u0 | (y0 << 8) | (v0 << 16) | (y1 << 24); words[1] = u1 | (y2 << 8) | (v1 << 16) | (y3 << 24); }
+	else { words[0] = y0 | (u0 << 8) | (y1 << 16) | (v0 << 24); words[1] = y2 | (u1 << 8) | (y3 << 16) | (v1 << 24); }
+}
+
+// 16-bit word of a row: the output columns below output_width - output_width % 8 of a channel take the reference's vector body (saturating difference / sum,
+// clamped by the adds / subs_epu16 pair with protect 2047 -- 511 at 8-bit precision --, >> 1, << 6 -- << 8 --), the rest its scalar tail ((low -+ high) / 2,
+// clamped to [0, 1023] -- [0, 255] --, << 6 -- << 8 --)
 __device__ __forceinline__ uint32_t row16u_word(int l, int h, int odd_row, bool tail, int sh)
 {
 	const int protect = sh ? 2047 : 511, scale = sh ? 6 : 8, top = sh ? 1023 : 255;
@@ -2763,84 +2692,56 @@ __device__ __forceinline__ uint32_t row16u_word(int l, int h, int odd_row, bool 
 	x = (int)(int16_t)x >> 1;                                                                 // srai_epi16
 	return (uint32_t)(x << scale) & 0xffffu;                                                  // slli_epi16
 }
-
-// four luma band columns (eight pixels, four YU64 pixel pairs) per thread: the loads and lane exchanges of k_inv_frame_yuv422_quad, two 16-byte stores per
-// picture row (32 bytes of YU64 words)
-__global__ void __launch_bounds__(NTHREADS) k_inv_frame_yuv422_rows16(const InvYuvJob *jobs)
+// 16-bit finisher: the 2 P YU64 pixel pairs of thread t in a picture row of parity par
+template <int P>
+__device__ __forceinline__ void frame_pairs_yu64(const int *tl, const int *th, int t, int par, int w, int sh, uint32_t *words)
 {
-	const InvYuvJob &job = jobs[blockIdx.z];
-	const int w = job.width;
-	const int t = (int)(blockIdx.x * NTHREADS + threadIdx.x), r = blockIdx.y;
-	const bool have = 4 * t < w && r < job.height;
-	const int lane = (int)(threadIdx.x & 63u);
-	const int sh = job.shift;
-	int tl[16], th[16];
-	frame_quad_samples(job, t, r, have, lane, tl, th);
-	if (!have) return;
 	const int ypost = 2 * w - (2 * w) % 8, cpost = w - w % 8;   // first tail column of the luma / chroma output rows (2w luma, w chroma samples)
-	const int x0 = 8 * t, p0 = 4 * t;                          // first luma sample, first chroma sample (= pixel pair) of this thread
+	const int x0 = 4 * P * t, p0 = 2 * P * t;                   // first luma sample, first chroma sample (= pixel pair) of this thread
 #pragma unroll
-	for (int par = 0; par < 2; par++) {
-		const int orow = 2 * r + par;
-		if (orow >= job.display_height) continue;
-		uint32_t words[8];
-#pragma unroll
-		for (int k = 0; k < 4; k++) {                          // pixel pair p0 + k: Y (2k), V, Y (2k + 1), U
-			const uint32_t y0 = row16u_word(tl[2 * k], th[2 * k], par, x0 + 2 * k >= ypost, sh);
-			const uint32_t y1 = row16u_word(tl[2 * k + 1], th[2 * k + 1], par, x0 + 2 * k + 1 >= ypost, sh);
-			const uint32_t v = row16u_word(tl[8 + k], th[8 + k], par, p0 + k >= cpost, sh);
-			const uint32_t u = row16u_word(tl[12 + k], th[12 + k], par, p0 + k >= cpost, sh);
-			words[2 * k] = y0 | (v << 16); words[2 * k + 1] = y1 | (u << 16);
-		}
-		uint4 *o = (uint4 *)(job.out + (size_t)orow * job.out_pitch + 32 * (size_t)t);
-		uint4 a; a.x = words[0]; a.y = words[1]; a.z = words[2]; a.w = words[3];
-		uint4 b; b.x = words[4]; b.y = words[5]; b.z = words[6]; b.w = words[7];
-		o[0] = a; o[1] = b;
+	for (int k = 0; k < 2 * P; k++) {                          // pixel pair p0 + k: Y (2k), V, Y (2k + 1), U
+		const uint32_t y0 = row16u_word(tl[2 * k], th[2 * k], par, x0 + 2 * k >= ypost, sh);
+		const uint32_t y1 = row16u_word(tl[2 * k + 1], th[2 * k + 1], par, x0 + 2 * k + 1 >= ypost, sh);
+		const uint32_t v = row16u_word(tl[4 * P + k], th[4 * P + k], par, p0 + k >= cpost, sh);
+		const uint32_t u = row16u_word(tl[6 * P + k], th[6 * P + k], par, p0 + k >= cpost, sh);
+		words[2 * k] = y0 | (v << 16); words[2 * k + 1] = y1 | (u << 16);
 	}
 }
 
-// one chroma band column (two luma band columns, two YU64 pixel pairs) per thread, any width: the geometries the four-column shape does not serve and
-// CFHD_AMD_INVERSE=tile
-__global__ void __launch_bounds__(NTHREADS) k_inv_frame_yuv422_rows16_col(const InvYuvJob *jobs)
+template <int P /* chroma band columns per thread: 1 or 2 */, bool ROWS16>
+__device__ __forceinline__ void inv_frame_yuv422_rows(const InvYuvJob *jobs, uint32_t launch_seed)
 {
 	const InvYuvJob &job = jobs[blockIdx.z];
-	const int w = job.width, cw = w >> 1;
-	const int cc = (int)(blockIdx.x * NTHREADS + threadIdx.x), r = blockIdx.y;
-	if (cc >= cw || r >= job.height) return;
-	const int sh = job.shift;
-	int tl[8], th[8];                                          // 4 luma (columns 2cc, 2cc + 1: even, odd each), 2 V, 2 U
-	{
-		const size_t o = (size_t)r * job.band_pitch[0];
-		frame_synth(job.band[0][0] + o, job.band[0][1] + o, 2 * cc, w, tl[0], tl[1]);
-		frame_synth(job.band[0][0] + o, job.band[0][1] + o, 2 * cc + 1, w, tl[2], tl[3]);
-		frame_synth(job.band[0][2] + o, job.band[0][3] + o, 2 * cc, w, th[0], th[1]);
-		frame_synth(job.band[0][2] + o, job.band[0][3] + o, 2 * cc + 1, w, th[2], th[3]);
-	}
-#pragma unroll
-	for (int x = 0; x < 2; x++) {
-		const size_t o = (size_t)r * job.band_pitch[1 + x];
-		frame_synth(job.band[1 + x][0] + o, job.band[1 + x][1] + o, cc, cw, tl[4 + 2 * x], tl[5 + 2 * x]);
-		frame_synth(job.band[1 + x][2] + o, job.band[1 + x][3] + o, cc, cw, th[4 + 2 * x], th[5 + 2 * x]);
-	}
-	const int ypost = 2 * w - (2 * w) % 8, cpost = w - w % 8;
-	const int x0 = 4 * cc, p0 = 2 * cc;
+	const int t = (int)(blockIdx.x * NTHREADS + threadIdx.x), r = blockIdx.y;
+	const int w = job.width, sh = job.shift;
+	const bool have = P * t < (w >> 1) && r < job.height;
+	const uint32_t seed = job.dither_seed ^ launch_seed;
+	int tl[8 * P], th[8 * P];
+	frame_row_samples<P>(job, t, r, have, tl, th);
+	if (!have) return;
+	constexpr int NW = (ROWS16 ? 4 : 2) * P;                    // 32-bit words of a picture row per thread
 #pragma unroll
 	for (int par = 0; par < 2; par++) {
 		const int orow = 2 * r + par;
 		if (orow >= job.display_height) continue;
-		uint32_t words[4];
+		uint32_t words[NW];
+		if (ROWS16) frame_pairs_yu64<P>(tl, th, t, par, w, sh, words);
+		else {
 #pragma unroll
-		for (int k = 0; k < 2; k++) {
-			const uint32_t y0 = row16u_word(tl[2 * k], th[2 * k], par, x0 + 2 * k >= ypost, sh);
-			const uint32_t y1 = row16u_word(tl[2 * k + 1], th[2 * k + 1], par, x0 + 2 * k + 1 >= ypost, sh);
-			const uint32_t v = row16u_word(tl[4 + k], th[4 + k], par, p0 + k >= cpost, sh);
-			const uint32_t u = row16u_word(tl[6 + k], th[6 + k], par, p0 + k >= cpost, sh);
-			words[2 * k] = y0 | (v << 16); words[2 * k + 1] = y1 | (u << 16);
+			for (int half = 0; half < P; half++) frame_column_yuv8<P>(tl, th, half, P * t + half, orow, par, sh, seed, job.uyvy, words + 2 * half);
 		}
-		uint4 o4; o4.x = words[0]; o4.y = words[1]; o4.z = words[2]; o4.w = words[3];
-		*(uint4 *)(job.out + (size_t)orow * job.out_pitch + 16 * (size_t)cc) = o4;
+		uint8_t *o = job.out + (size_t)orow * job.out_pitch + 4 * NW * (size_t)t;
+		if (NW == 2) { uint2 o2; o2.x = words[0]; o2.y = words[1]; *(uint2 *)o = o2; }
+		else {
+#pragma unroll
+			for (int q = 0; q < NW / 4; q++) { uint4 o4; o4.x = words[4 * q]; o4.y = words[4 * q + 1]; o4.z = words[4 * q + 2]; o4.w = words[4 * q + 3]; ((uint4 *)o)[q] = o4; }
+		}
 	}
 }
+__global__ void __launch_bounds__(NTHREADS) k_inv_frame_yuv422(const InvYuvJob *jobs, uint32_t launch_seed) { inv_frame_yuv422_rows<1, false>(jobs, launch_seed); }
+__global__ void __launch_bounds__(NTHREADS) k_inv_frame_yuv422_quad(const InvYuvJob *jobs, uint32_t launch_seed) { inv_frame_yuv422_rows<2, false>(jobs, launch_seed); }
+__global__ void __launch_bounds__(NTHREADS) k_inv_frame_yuv422_rows16(const InvYuvJob *jobs) { inv_frame_yuv422_rows<2, true>(jobs, 0u); }
+__global__ void __launch_bounds__(NTHREADS) k_inv_frame_yuv422_rows16_col(const InvYuvJob *jobs) { inv_frame_yuv422_rows<1, true>(jobs, 0u); }
 
 // =============================================================================================
 // Bayer input (ConvertBYR4ToFrame16s, frame.c:4993, curve branch :5219-5393): every 2x2 quad of the mosaic gives one sample of the

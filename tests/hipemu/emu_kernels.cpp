@@ -443,6 +443,20 @@ int emu_inv_frame_yuv422_quad(int16_t **bands /*[3][4]*/, const int *band_pitch,
 	return 0;
 }
 
+// the same level into 16-bit YU64 rows (no dither): cols_per_thread 4 = k_inv_frame_yuv422_rows16 (luma band width a multiple of 4), 2 = k_inv_frame_yuv422_rows16_col (any width)
+int emu_inv_frame_yuv422_rows16(int16_t **bands /*[3][4]*/, const int *band_pitch, int w, int h, int display_height, int shift, uint8_t *out, int out_pitch, int cols_per_thread)
+{
+	if ((cols_per_thread != 2 && cols_per_thread != 4) || (cols_per_thread == 4 && w % 4)) return -1;
+	InvYuvJob job;
+	memset(&job, 0, sizeof(job));
+	for (int c = 0; c < 3; c++) { job.band_pitch[c] = band_pitch[c]; for (int b = 0; b < 4; b++) job.band[c][b] = bands[c * 4 + b]; }
+	job.width = w; job.height = h; job.display_height = display_height; job.shift = shift; job.out = out; job.out_pitch = out_pitch;
+	const dim3 grid((w / cols_per_thread + NTHREADS - 1) / NTHREADS, h, 1);
+	if (cols_per_thread == 4) hipemu::launch(grid, dim3(NTHREADS), [&] { k_inv_frame_yuv422_rows16(&job); });
+	else hipemu::launch(grid, dim3(NTHREADS), [&] { k_inv_frame_yuv422_rows16_col(&job); });
+	return 0;
+}
+
 // the register-strip variant of the same level (luma band width a multiple of 16; segments of 124 blocks of 8 columns)
 int emu_inv_yuv422_strip(int16_t **bands /*[3][4]*/, const int *band_pitch, int w, int h, int display_height, int uyvy, int shift,
                          unsigned dither_seed, uint8_t *out, int out_pitch)

@@ -1359,6 +1359,25 @@ def test_interlaced_decode_reference_samples(w, h, pixfmt):
     assert psnr_yuy2(a, frames[0].reshape(h, -1)[:, : w * 2]) > 38 and psnr_yuy2(b, frames[1].reshape(h, -1)[:, : w * 2]) > 38
 
 
+@pytest.mark.parametrize("w,h", [(320, 240), (2064, 48)])
+@pytest.mark.parametrize("pixfmt", [PIX_YUY2, PIX_2VUY])
+def test_interlaced_row_kernels_in_both_widths(w, h, pixfmt):
+    """The 8-bit interlaced row kernels: a single frame decodes through k_inv_frame_yuv422_quad (four band columns per thread), under CFHD_AMD_INVERSE=tile through
+    k_inv_frame_yuv422 (one chroma column per thread); both are one body (inv_frame_yuv422_rows) and both meet the bar of every 8-bit decode.  2064 wide: the
+    smallest luma band beyond 1024 columns (1032), so the four-column shape runs a second workgroup and wave borders inside a row."""
+    f = synth_yuy2(w, h, 5)[0]
+    v = f.reshape(h, 2 * w); v[1::2] = np.roll(v[1::2], 8, axis=1)
+    sample = ref_encode_frames([f], 2 * w, w, h, pixfmt, flags=1)[0]
+    _check_decode(sample, f, w, h, pixfmt, interlaced=True)
+    old = os.environ.get("CFHD_AMD_INVERSE")
+    os.environ["CFHD_AMD_INVERSE"] = "tile"
+    try:
+        _check_decode(sample, f, w, h, pixfmt, interlaced=True)
+    finally:
+        if old is None: os.environ.pop("CFHD_AMD_INVERSE")
+        else: os.environ["CFHD_AMD_INVERSE"] = old
+
+
 def test_interlaced_decode_peak_table_frames():
     """Field flicker: the difference band of the sample carries a peak table (values beyond +-250 quantization steps); k_dec_undiff
     takes them from the table in raster order."""

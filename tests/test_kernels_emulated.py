@@ -1049,6 +1049,42 @@ def test_inv_frame_yuv422(w, h, dh, uyvy):
     assert np.any(e != outs[0]) and np.any(e != outs[1])
 
 
+@pytest.mark.parametrize("w,h,dh", [(8, 4, 8), (132, 33, 66), (260, 19, 37), (1032, 4, 8), (360, 30, 58)])
+@pytest.mark.parametrize("shift", [0, 2])
+def test_inv_frame_yuv422_rows16(w, h, dh, shift):
+    """The interlaced last level into 16-bit YU64 rows (RG48 / b64a / BGRA / BGRa outputs), both precisions: k_inv_frame_yuv422_rows16 (four band columns per thread)
+    and k_inv_frame_yuv422_rows16_col (one chroma column per thread) write the same words, those of the model's rows16 stage (tests/interlaced_rgb_model.py, pinned on
+    the reference decoder); rows from the display height on and the bytes right of a row stay untouched.  Band sizes: the minimum; luma tail columns (2w % 8 != 0);
+    the second wave and the second workgroup of the four-column shape; a display height that is not twice the band height."""
+    import interlaced_rgb_model as M
+    rng = np.random.default_rng(w + h + shift)
+    bands, pitches = [], []
+    for ch in range(3):
+        cw = w if ch == 0 else w // 2
+        pitch = (cw + 7) // 8 * 8 + (8 if ch == 2 else 0); pitches.append(pitch)
+        bs = [rng.integers(-50, 50, size=(h, pitch)).astype(np.int16) for _ in range(4)]
+        bs[0][:, :cw] = rand_plane(rng, cw, h, 11)
+        for k in range(1, 4): bs[k][:, :cw] = rand_plane(rng, cw, h, 9, signed=True)
+        bs[2][:, :cw] *= 3                                      # temporal highpass beyond the lowpass: low - high below zero, low + high above the range
+        bands.append(bs)
+    ptrs = (c_i16p * 12)(*[p16(a) for ch in range(3) for a in bands[ch]])
+    want = np.zeros((2 * h, 4 * w), np.uint16)                  # YU64 words Y0 V Y1 U: 2w luma, w V, w U words in a row
+    for ch, sel in enumerate((slice(0, None, 2), slice(1, None, 4), slice(3, None, 4))):
+        cw = w if ch == 0 else w // 2
+        b = [a[:, :cw] for a in bands[ch]]
+        want[0::2, sel], want[1::2, sel] = M.interlaced_row16u(M.inv_horizontal_rows(b[0], b[1]), M.inv_horizontal_rows(b[2], b[3]), 10 if shift else 8)
+    E = emu()
+    E.emu_inv_frame_yuv422_rows16.argtypes = [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
+    got = []
+    for cols in (4, 2):
+        o = np.full((2 * h, 4 * w + 8), 0x0707, np.uint16)
+        assert E.emu_inv_frame_yuv422_rows16(ptrs, iarr(pitches), w, h, dh, shift, o.ctypes.data_as(ctypes.c_void_p), 2 * (4 * w + 8), cols) == 0
+        assert np.all(o[:, 4 * w:] == 0x0707) and np.all(o[dh:] == 0x0707), cols
+        got.append(o)
+    assert np.array_equal(got[0], got[1])
+    assert np.array_equal(got[0][:dh, :4 * w], want[:dh])
+
+
 def test_gpu_entropy_stage_emulated_long_trailers():
     """Empty bands of a larger frame: the trailer of a band is dozens of copies of the longest run code, more than one piece of k_ent_layout's
     fill (the emulated build uses pieces of 16 words), written in closed form by the lanes; a single value in the middle of one band splits
