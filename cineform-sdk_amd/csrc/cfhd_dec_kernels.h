@@ -17,8 +17,9 @@
 //   k_dec_chain   one wave per band: checks that every chunk started where its predecessor ended (a chunk that did not -- its run-in
 //                 lane never fell in step, rare -- is indexed again from the exact position), and turns the chunks' coefficient counts into
 //                 raster positions.
-//   k_dec_tiles   over the *output*: every wave owns 2048 consecutive coefficients of a band (4 KB), finds the 64-bit pieces of
-//                 payload whose code words land in it, decodes each piece on its own lane into an LDS image of the tile and streams the
+//   k_dec_tiles   over the *output*: every workgroup owns a tile, up to DX_TILE = 14848 consecutive coefficients of a band (29 KB; below), finds
+//                 the 64-bit pieces of payload whose code words land in it (k_dec_tile_index), decodes each piece on its own lane -- 64
+//                 consecutive pieces per wave and round -- into one LDS image of the tile that its eight waves share, and streams the
 //                 tile out with 16-byte stores.  The zero runs are never decoded into stores and never written twice: the band is written
 //                 exactly once, in full lines, whatever the picture looks like (the round-1 kernel cleared each band and then scattered 2-byte
 //                 stores into it: 1.24x the bytes, and its run time followed the longest band).

@@ -194,6 +194,32 @@ int cfhd_amd_decode_bands_host(const uint8_t *sample, size_t size, int pixel_kin
 	return 0;
 }
 
+// Where the host parser finds the coded bands of an intra-frame sample: per channel, level, band 1..3 (that order) offset, bytes, code set (1 / 2), peak level.
+// Returns the number of ints or < 0.  (tests/hand_made_samples.py: payload sizes against the decoder's 2016-byte chunks.)
+int cfhd_amd_band_payloads(const uint8_t *sample, size_t size, int *out)
+{
+	ParsedSample ps;
+	if (parse_sample(sample, size, &ps) != 0) return -1;
+	int n = 0;
+	for (int c = 0; c < ps.num_channels; c++)
+		for (int lv = 0; lv < kNumLevels; lv++)
+			for (int b = 1; b < kNumBands; b++) {
+				const ParsedBand &pb = ps.high[c][lv][b];
+				out[n++] = (int)pb.offset; out[n++] = (int)pb.bytes; out[n++] = pb.codebook; out[n++] = pb.peak_level;
+			}
+	return n;
+}
+
+// Bits of the host writer's code words: the composite run codes (size and zeros covered, 3072 each), the value codes by 11-bit two's complement value
+// (2048, sign bit included), the band end marker.  With them a test lays a band's code words out bit by bit as vlc_encode_band does.
+void cfhd_amd_code_sizes(int codebook, int *run_size, int *run_count, int *value_size, int *band_end_size)
+{
+	const EntropyTables *t = entropy_tables(codebook);
+	for (int i = 0; i < 3072; i++) { run_size[i] = t->run_size[i]; run_count[i] = t->run_count[i]; }
+	for (int i = 0; i < 2048; i++) value_size[i] = (int)(t->value_code[i] >> 27);
+	*band_end_size = t->band_end_size;
+}
+
 } // extern "C"
 
 // Test hook: the Bayer encode curve the device path uploads (must equal the oracle's restatement entry for entry).
