@@ -32,7 +32,7 @@ const char *device_last_error();
 
 // N frames that travel through the forward path together: one launch per wavelet level covers every channel of
 // every frame (blockIdx.z walks the job table).  N = 1 is the synchronous CFHD_EncodeSample path.
-struct ForwardRoute; struct InverseRoute; struct GopRoute; struct GopForwardRoute;      // (cfhd_device.hip: the kernels a launch picks)
+struct ForwardRoute; struct InverseRoute; struct GopRoute; enum class FwdL1;      // (cfhd_device.hip: the kernels a launch picks)
 class EncodeBatch {
 public:
 	EncodeBatch();
@@ -203,7 +203,7 @@ public:
 private:
 	void fill_jobs();
 	GopRoute route() const;                          // decoder: output_route() of a 4:2:2 sample for the output kind, half and interlaced, and the kernel that serves its family
-	GopForwardRoute forward_route() const;           // encoder: the level-1 kernel of both frames, from the input kind and interlaced alone
+	FwdL1 forward_route() const;                     // encoder: the level-1 kernel of both frames, from the input kind and interlaced alone
 	GopPlan plan_; bool decode_ = false, half_ = false; int out_kind_ = 0, device_ = 0, matrix_ = 0;
 	void *stream_ = nullptr;
 	uint8_t *d_frames_ = nullptr, *h_frames_ = nullptr; size_t frame_bytes_ = 0; int pitch_ = 0, rows_ = 0;

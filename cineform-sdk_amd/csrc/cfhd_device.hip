@@ -114,12 +114,12 @@ static bool enc_bytes8(int pixel_kind) { return pixel_kind == PIX_RG24 || pixel_
 static bool enc_rgb10(int pixel_kind) { return pixel_kind >= PIX_R210 && pixel_kind <= PIX_AR10; }
 // bit position of plane c (G, R, B) inside the pixel word of the 10-bit RGB formats
 static int rgb10_shift(int pixel_kind, int c) { const int r = pixel_kind == PIX_DPX0 ? 22 : (pixel_kind == PIX_AB10 ? 0 : 20), g = pixel_kind == PIX_DPX0 ? 12 : 10, b = pixel_kind == PIX_DPX0 ? 2 : (pixel_kind == PIX_AB10 ? 20 : 0); return c == 0 ? g : (c == 1 ? r : b); }
-// RG48 / b64a encoded as YUV 4:2:2: the loader of k_fwd_packed16 converts the pixels (FwdPlaneJob::layout 7); every plane reads from the R word
+// RG48 / b64a encoded as YUV 4:2:2: the loader of k_fwd_packed16 converts the pixels (FWD_RGB16_AS_422); every plane reads from the R word
 static bool enc_rgb_as_422(const FramePlan &plan) { return (is_packed16(plan.pixel_kind) || plan.pixel_kind == PIX_RG64) && plan.encoded_format == ENC_YUV422; }
 static int enc_word_of_channel(int pixel_kind, int c) { return pixel_kind == PIX_V210 || enc_bytes8(pixel_kind) || enc_rgb10(pixel_kind) ? 0 : (pixel_kind == PIX_YU64 ? (c == 0 ? 0 : (c == 1 ? 1 : 3)) : packed_word_of_channel(pixel_kind, c)); }
 static int enc_stride_of_channel(int pixel_kind, int c, int nch) { return pixel_kind == PIX_YU64 ? (c == 0 ? 2 : 4) : (pixel_kind == PIX_B64A || pixel_kind == PIX_RG64 ? 4 : nch); }     // (b64a / RG64 to RGB 4:4:4 have three planes of four-word pixels)
 // The loader of k_fwd_packed16 / k_fwd_gop_packed16 for plane c of one packed frame (FwdPlaneJob: in, in_pitch, xstride, shift, display_height, compand, layout,
-// tail_from), written in one place for the intra batches and the two-frame groups.
+// tail_from), written in one place for the intra batches and the two-frame groups: it reads the frame where fill_fwd_plane_job's job reads a plane.
 static void fill_packed16_loader(dev::FwdPlaneJob &p, const uint8_t *frame8, int in_pitch, int pixel_kind, int encoded_format, int color_matrix, int width, int precision,
                                  int display_height, int nch, int c)
 {
@@ -127,14 +127,60 @@ static void fill_packed16_loader(dev::FwdPlaneJob &p, const uint8_t *frame8, int
 	p.in = (const int16_t *)(frame + enc_word_of_channel(pixel_kind, c)); p.in_pitch = in_pitch / 2;
 	p.xstride = enc_stride_of_channel(pixel_kind, c, nch); p.shift = 16 - precision; p.display_height = display_height;
 	p.compand = (pixel_kind == PIX_B64A || pixel_kind == PIX_RG64) && c == 3;
-	p.layout = pixel_kind == PIX_V210 ? c + 1 : 0; p.tail_from = (width - width % 48) / 2;
-	if (enc_bytes8(pixel_kind)) { p.layout = pixel_kind == PIX_BGRa ? 5 : 4; p.in_pitch = in_pitch; p.xstride = pixel_kind == PIX_RG24 ? 3 : 4; p.tail_from = c == 0 ? 1 : (c == 1 ? 2 : (c == 2 ? 0 : 3)); p.compand = c == 3; }     // planes G, R, B(, A) of bytes B, G, R(, A)
-	if (enc_rgb10(pixel_kind)) { p.layout = 6; p.in_pitch = in_pitch / 4; p.xstride = pixel_kind == PIX_R210 || pixel_kind == PIX_DPX0; p.tail_from = rgb10_shift(pixel_kind, c); }
+	p.layout = pixel_kind == PIX_V210 ? dev::FWD_V210_Y + c : dev::FWD_WORDS16; p.tail_from = (width - width % 48) / 2;
+	if (enc_bytes8(pixel_kind)) { p.layout = pixel_kind == PIX_BGRa ? dev::FWD_BYTES8_TOP_DOWN : dev::FWD_BYTES8_BOTTOM_UP; p.in_pitch = in_pitch; p.xstride = pixel_kind == PIX_RG24 ? 3 : 4; p.tail_from = c == 0 ? 1 : (c == 1 ? 2 : (c == 2 ? 0 : 3)); p.compand = c == 3; }     // planes G, R, B(, A) of bytes B, G, R(, A)
+	if (enc_rgb10(pixel_kind)) { p.layout = dev::FWD_RGB10; p.in_pitch = in_pitch / 4; p.xstride = pixel_kind == PIX_R210 || pixel_kind == PIX_DPX0; p.tail_from = rgb10_shift(pixel_kind, c); }
 	if ((is_packed16(pixel_kind) || pixel_kind == PIX_RG64) && encoded_format == ENC_YUV422) {      // (enc_rgb_as_422)
 		p.in = (const int16_t *)(frame + (pixel_kind == PIX_B64A ? 1 : 0));
-		p.layout = 7; p.xstride = pixel_kind == PIX_RG48 ? 3 : 4; p.tail_from = c; p.shift = color_matrix; p.compand = 0;
+		p.layout = dev::FWD_RGB16_AS_422; p.xstride = pixel_kind == PIX_RG48 ? 3 : 4; p.tail_from = c; p.shift = color_matrix; p.compand = 0;
 	}
-	if (enc_bytes8(pixel_kind) && encoded_format == ENC_YUV422) { p.layout = pixel_kind == PIX_BGRa ? 9 : 8; p.tail_from = c; p.shift = color_matrix; }
+	if (enc_bytes8(pixel_kind) && encoded_format == ENC_YUV422) { p.layout = pixel_kind == PIX_BGRa ? dev::FWD_BYTES8_AS_422_TOP_DOWN : dev::FWD_BYTES8_AS_422_BOTTOM_UP; p.tail_from = c; p.shift = color_matrix; }
+}
+
+// The level-1 wavelet of one frame as its first (encoder) or last (decoder) launch sees it: a frame of an intra batch, or frame f of a two-frame group (w[f]: what the
+// temporal step reads, what the temporal inverse leaves).  The plan types stop here: the job fillers below read this.
+struct Level1 { int16_t *band[kMaxChannels][4]; int pitch[kMaxChannels], width[kMaxChannels], height[kMaxChannels], quant[kMaxChannels][4]; };
+Level1 level1_of(const FramePlan &plan, int16_t *base)
+{
+	Level1 l;
+	for (int c = 0; c < plan.num_channels; c++) { const BandDesc *b = plan.ch[c].band[0]; l.pitch[c] = b[0].pitch; l.width[c] = b[0].width; l.height[c] = b[0].height; for (int k = 0; k < 4; k++) { l.band[c][k] = base + b[k].offset; l.quant[c][k] = b[k].quant; } }
+	return l;
+}
+Level1 level1_of(const GopPlan &plan, int f, int16_t *base)
+{
+	Level1 l;
+	for (int c = 0; c < 3; c++) { const GopWavelet &w = plan.ch[c].w[f]; l.pitch[c] = w.pitch; l.width[c] = w.width; l.height[c] = w.height; for (int k = 0; k < 4; k++) { l.band[c][k] = base + w.offset[k]; l.quant[c][k] = w.quant[k]; } }
+	return l;
+}
+// The four bands a forward job writes, with their divisors: channel c of a level-1 wavelet, a wavelet of an intra pyramid, a wavelet of a group
+struct FwdBands { int16_t *out[4]; int pitch, quant[4]; };
+FwdBands fwd_bands(const Level1 &l, int c) { FwdBands d; d.pitch = l.pitch[c]; for (int b = 0; b < 4; b++) { d.out[b] = l.band[c][b]; d.quant[b] = l.quant[c][b]; } return d; }
+FwdBands fwd_bands(int16_t *base, const BandDesc *w) { FwdBands d; d.pitch = w[0].pitch; for (int b = 0; b < 4; b++) { d.out[b] = base + w[b].offset; d.quant[b] = w[b].quant; } return d; }
+FwdBands fwd_bands(int16_t *base, const GopWavelet &w) { FwdBands d; d.pitch = w.pitch; for (int b = 0; b < 4; b++) { d.out[b] = base + w.offset[b]; d.quant[b] = w.quant[b]; } return d; }
+
+// One job of each forward family, for the intra batches and the two-frame groups alike.  Level 1 of a packed 8-bit 4:2:2 frame (k_fwd_yuv422 and its strip forms;
+// interlaced: k_fwd_frame_yuv422, the same table read as FwdFrameJob); FwdYuvJob::lists is EncodeBatch::fill_block_lists's.
+void fill_fwd_yuv_job(dev::FwdYuvJob &y, const uint8_t *in, int in_pitch, int width, int height, int display_height, int pixel_kind, int precision, const Level1 &l, int mpq, bool interlaced)
+{
+	y.in = in; y.in_pitch = in_pitch;
+	y.width = width; y.height = height; y.display_height = display_height;
+	y.uyvy = pixel_kind == PIX_2VUY; y.shift = precision - 8;
+	for (int c = 0; c < 3; c++) {
+		y.out_pitch[c] = l.pitch[c];
+		for (int b = 0; b < 4; b++) { y.out[c][b] = l.band[c][b]; y.q[c][b] = make_q(l.quant[c][b], mpq); }
+		// interlaced: the difference-coded band is quantized inside the horizontal filter, midpoint = divisor / prequant without the decrement (spatial.c:5360-5363)
+		const int dq = l.quant[c][2];
+		if (interlaced && dq > 1 && mpq >= 2 && mpq < 9) y.q[c][2].mid = dq / mpq;
+	}
+}
+// One wavelet of a plane of 16-bit samples (k_fwd_plane, k_fwd_plane_strip): levels 2 and 3, the Bayer component planes, the group's spatial wavelets.  Sets every field a
+// kernel reads; a job of the packed-16 loaders passes no plane and lets fill_packed16_loader say how the frame is read instead.
+void fill_fwd_plane_job(dev::FwdPlaneJob &p, const int16_t *in, int in_pitch, int width, int height, int prescale, const FwdBands &d, int mpq)
+{
+	p.in = in; p.in_pitch = in_pitch; p.width = width; p.height = height; p.prescale = prescale;
+	p.xstride = 1; p.shift = 0; p.display_height = height; p.compand = 0; p.layout = dev::FWD_WORDS16; p.tail_from = 0; p.curve = nullptr;
+	p.out_pitch = d.pitch;
+	for (int b = 0; b < 4; b++) { p.out[b] = d.out[b]; p.q[b] = make_q(d.quant[b], mpq); }
 }
 } // namespace
 
@@ -371,49 +417,30 @@ void EncodeBatch::fill_jobs()
 	EncJobs j = enc_jobs_at(h_jobs_, n_, nch);
 	for (int i = 0; i < n_; i++) {
 		int16_t *base = d_coeff_ + (size_t)i * plan.coeff_elems;
-		dev::FwdYuvJob &y = j.yuv[i];
-		y.in = d_in_ + frame_bytes_ * i; y.in_pitch = in_pitch_;
-		y.width = plan.width; y.height = plan.height; y.display_height = plan.display_height;
-		y.uyvy = plan.pixel_kind == PIX_2VUY; y.shift = plan.precision - 8;
-		for (int c = 0; c < 3; c++) {
-			y.out_pitch[c] = plan.ch[c].band[0][0].pitch;
-			for (int b = 0; b < 4; b++) { y.out[c][b] = base + plan.ch[c].band[0][b].offset; y.q[c][b] = make_q(plan.ch[c].band[0][b].quant, mpq); }
-			// interlaced: the difference-coded band is quantized inside the horizontal filter, midpoint = divisor / prequant without the decrement
-			const int dq = plan.ch[c].band[0][2].quant;
-			if (plan.interlaced && dq > 1 && mpq >= 2 && mpq < 9) y.q[c][2].mid = dq / mpq;
-		}
+		const uint8_t *frame = d_in_ + frame_bytes_ * i;
+		const Level1 l1 = level1_of(plan, base);
+		fill_fwd_yuv_job(j.yuv[i], frame, in_pitch_, plan.width, plan.height, plan.display_height, plan.pixel_kind, plan.precision, l1, mpq, plan.interlaced);
 		if (bayer) {
 			const int ppitch = plan.ch[0].band[0][0].pitch * 2;
 			dev::BayerJob &bj = j.bayer[i];
-			bj.in = (const uint16_t *)(d_in_ + frame_bytes_ * i); bj.in_pitch = in_pitch_ / 2;
+			bj.in = (const uint16_t *)frame; bj.in_pitch = in_pitch_ / 2;
 			bj.width = plan.width; bj.height = plan.height; bj.display_height = plan.display_height;
 			bj.out_pitch = ppitch; bj.curve = d_curve_; bj.order = 0; bj.precision = plan.precision; bj.packed12 = plan.pixel_kind == PIX_BYR5;
 			for (int c = 0; c < 4; c++) {
 				bj.out[c] = d_planes_ + ((size_t)i * 4 + c) * plane_elems_;
-				dev::FwdPlaneJob &p = j.l1[(size_t)i * nch + c];
-				p.in = bj.out[c]; p.in_pitch = ppitch; p.width = plan.ch[c].width; p.height = plan.ch[c].height; p.prescale = plan.prescale[0];
-				p.xstride = 1; p.shift = 0; p.display_height = plan.ch[c].height; p.compand = 0;
-				p.out_pitch = plan.ch[c].band[0][0].pitch;
-				for (int b = 0; b < 4; b++) { p.out[b] = base + plan.ch[c].band[0][b].offset; p.q[b] = make_q(plan.ch[c].band[0][b].quant, mpq); }
+				fill_fwd_plane_job(j.l1[(size_t)i * nch + c], bj.out[c], ppitch, plan.ch[c].width, plan.ch[c].height, plan.prescale[0], fwd_bands(l1, c), mpq);
 			}
 		}
 		if (enc_packed16(plan.pixel_kind))
 			for (int c = 0; c < nch; c++) {
 				dev::FwdPlaneJob &p = j.l1[(size_t)i * nch + c];
-				fill_packed16_loader(p, d_in_ + frame_bytes_ * i, in_pitch_, plan.pixel_kind, plan.encoded_format, plan.color_matrix, plan.width, plan.precision,
-				                     plan.display_height, nch, c);
-				p.width = plan.ch[c].width; p.height = plan.ch[c].height; p.prescale = plan.prescale[0];
-				p.out_pitch = plan.ch[c].band[0][0].pitch;
-				for (int b = 0; b < 4; b++) { p.out[b] = base + plan.ch[c].band[0][b].offset; p.q[b] = make_q(plan.ch[c].band[0][b].quant, mpq); }
+				fill_fwd_plane_job(p, nullptr, 0, plan.ch[c].width, plan.ch[c].height, plan.prescale[0], fwd_bands(l1, c), mpq);
+				fill_packed16_loader(p, frame, in_pitch_, plan.pixel_kind, plan.encoded_format, plan.color_matrix, plan.width, plan.precision, plan.display_height, nch, c);
 			}
 		for (int lv = 1; lv < 3; lv++)
 			for (int c = 0; c < nch; c++) {
-				dev::FwdPlaneJob &p = (lv == 1 ? j.l2 : j.l3)[(size_t)i * nch + c];
 				const BandDesc &src = plan.ch[c].band[lv - 1][0];
-				p.in = base + src.offset; p.in_pitch = src.pitch; p.width = src.width; p.height = src.height; p.prescale = plan.prescale[lv];
-				p.xstride = 1; p.shift = 0; p.display_height = src.height; p.compand = 0;
-				p.out_pitch = plan.ch[c].band[lv][0].pitch;
-				for (int b = 0; b < 4; b++) { p.out[b] = base + plan.ch[c].band[lv][b].offset; p.q[b] = make_q(plan.ch[c].band[lv][b].quant, mpq); }
+				fill_fwd_plane_job((lv == 1 ? j.l2 : j.l3)[(size_t)i * nch + c], base + src.offset, src.pitch, src.width, src.height, plan.prescale[lv], fwd_bands(base, plan.ch[c].band[lv]), mpq);
 			}
 	}
 	jobs_dirty_ = true;
@@ -584,13 +611,24 @@ template <typename F> static void for_channel_runs(const FramePlan &plan, int lv
 	}
 }
 
-// Level 1 of the forward transform: every kernel launch_forward() can pick, and the name a profiler shows it under (level_kernel()).  The strip kernels and
-// the LDS-tiled ones produce the same coefficients.
-enum class FwdL1 { Yuv422, Yuv422Strip, Yuv422StripBlocks, Yuv422StripBlocksDense, FrameYuv422, FrameYuv422Strip, Packed16, Packed16Strip, BayerStrip, BayerUnpack };
+// The launch geometry of k_fwd_plane_strip and k_inv_plane_strip for one run of channels (for_channel_runs): strips of SRP band rows, 64 >> glog planes per wave, four waves per workgroup
+struct PlaneStrips { int nstrips; unsigned blocks; };
+static PlaneStrips plane_strips(int frames, int nc, int glog, int nseg, int band_height)
+{
+	const int nstrips = (band_height + dev::SRP - 1) / dev::SRP, per_wave = nseg > 1 ? 1 : 64 >> glog, waves = ((frames * nc + per_wave - 1) / per_wave) * nstrips * nseg;
+	return { nstrips, (unsigned)((waves + 3) / 4) };
+}
+// k_fwd_plane over `planes` source planes of width x height samples: one workgroup per tile of the half-size bands
+static void launch_fwd_plane_tiles(const dev::FwdPlaneJob *jobs, int width, int height, int planes, hipStream_t st) { dev::k_fwd_plane<<<dim3((width / 2 + dev::TW - 1) / dev::TW, (height / 2 + dev::TH - 1) / dev::TH, planes), dev::NTHREADS, 0, st>>>(jobs); }
+
+// Level 1 of the forward transform: every kernel launch_forward() can pick -- an intra batch's, and a two-frame group's (one launch over both frames: the tile kernels,
+// GopPacked16 for the packed-16 loaders) --, and the name a profiler shows it under (level_kernel(), level1_kernel()).  The strip kernels and the LDS-tiled ones produce
+// the same coefficients.
+enum class FwdL1 { Yuv422, Yuv422Strip, Yuv422StripBlocks, Yuv422StripBlocksDense, FrameYuv422, FrameYuv422Strip, Packed16, Packed16Strip, BayerStrip, BayerUnpack, GopPacked16 };
 static const char *const kFwdL1Name[] = {"k_fwd_yuv422", "k_fwd_yuv422_strip", "k_fwd_yuv422_strip_blocks", "k_fwd_yuv422_strip_blocks_dense", "k_fwd_frame_yuv422",
-                                         "k_fwd_frame_yuv422_strip", "k_fwd_packed16", "k_fwd_packed16_strip", "k_fwd_bayer_strip", "k_unpack_byr4+k_fwd_plane"};
+                                         "k_fwd_frame_yuv422_strip", "k_fwd_packed16", "k_fwd_packed16_strip", "k_fwd_bayer_strip", "k_unpack_byr4+k_fwd_plane", "k_fwd_gop_packed16"};
 static const char *const kFwdPlaneName[2] = {"k_fwd_plane", "k_fwd_plane_strip"};      // levels 2 and 3: [planes_as_strips()]
-static_assert(sizeof(kFwdL1Name) / sizeof(*kFwdL1Name) == (size_t)FwdL1::BayerUnpack + 1, "one name per level-1 kernel");
+static_assert(sizeof(kFwdL1Name) / sizeof(*kFwdL1Name) == (size_t)FwdL1::GopPacked16 + 1, "one name per level-1 kernel");
 struct ForwardRoute {
 	FwdL1 l1; bool strip_planes[2];                     // [lv - 1]: level lv + 1 runs as k_fwd_plane_strip
 	bool block_lists() const { return l1 == FwdL1::Yuv422StripBlocks || l1 == FwdL1::Yuv422StripBlocksDense; }      // the quantized level-1 bands leave as block lists for k_ent_count_blocks
@@ -620,7 +658,7 @@ ForwardRoute EncodeBatch::forward_route(bool coeffs_needed) const
 		// RG48 / b64a frames of whole 8-pixel blocks whose rows are 16-byte aligned
 		const dev::FwdPlaneJob &p = j.l1[(size_t)i * nch];
 		const uintptr_t frame = (uintptr_t)((const uint16_t *)p.in - packed_word_of_channel(kind, 0));
-		return !(frame & 15) && !((p.in_pitch * 2) & 15) && p.layout == 0 && p.width % 8 == 0; })) r.l1 = FwdL1::Packed16Strip;
+		return !(frame & 15) && !((p.in_pitch * 2) & 15) && p.layout == dev::FWD_WORDS16 && p.width % 8 == 0; })) r.l1 = FwdL1::Packed16Strip;
 	else if (enc_packed16(kind)) r.l1 = FwdL1::Packed16;
 	else if (plan_.interlaced) r.l1 = yuv_strips && yuy2 ? FwdL1::FrameYuv422Strip : FwdL1::FrameYuv422;
 	else if (!yuv_strips) r.l1 = FwdL1::Yuv422;
@@ -628,6 +666,48 @@ ForwardRoute EncodeBatch::forward_route(bool coeffs_needed) const
 	else if (blocks_env && ent_ready_ && ent_.block_slots() && yuy2) r.l1 = coeffs_needed ? FwdL1::Yuv422StripBlocksDense : FwdL1::Yuv422StripBlocks;
 	else r.l1 = FwdL1::Yuv422Strip;
 	return r;
+}
+
+// The launch of level 1, for intra batches (`frames` active frames) and two-frame groups (2) alike: every FwdL1 kernel and every grid formula is here and nowhere else.
+struct FirstLevel {
+	int width, height, frames;                                  // the picture (Bayer: its component planes); grid z
+	const dev::FwdYuvJob *yuv; const dev::FwdPlaneJob *l1; const dev::BayerJob *bayer;      // job tables (null: the caller has none)
+	int nch, pixel_kind;
+	int luma_tiles, chroma_tiles;                               // GopPacked16: tiles of a tile row, the planes side by side in gridDim.x
+};
+static int launch_first_level(FwdL1 k, const FirstLevel &g, hipStream_t st)
+{
+	static_assert(sizeof(dev::FwdFrameJob) == sizeof(dev::FwdYuvJob) && offsetof(dev::FwdFrameJob, q) == offsetof(dev::FwdYuvJob, q), "the two level-1 jobs share one table");
+	const int hw = g.width / 2, hh = g.height / 2, act = g.frames, nch = g.nch;
+	const dim3 tiles((hw + dev::TW - 1) / dev::TW, (hh + dev::TH - 1) / dev::TH, act);      // the LDS-tiled kernels: one workgroup per tile of a half-size plane
+	auto strips422 = [&](int rows) { return dim3((g.width / 16 + dev::SSEG - 1) / dev::SSEG, (hh + rows - 1) / rows, act); };      // 4:2:2 strips: segments of 124 luma blocks (1984 pixels)
+	const int nseg = (g.width / 8 + dev::PSTEP - 1) / dev::PSTEP, nstrips = (hh + dev::PSR - 1) / dev::PSR, waves = act * nseg * nstrips;      // RG48 / b64a / Bayer strips
+	const dev::FwdFrameJob *frame = (const dev::FwdFrameJob *)g.yuv;
+	// (a kernel without its job table: no route yields one)
+	const bool bayer = k == FwdL1::BayerStrip || k == FwdL1::BayerUnpack, planes = bayer || k == FwdL1::Packed16 || k == FwdL1::Packed16Strip || k == FwdL1::GopPacked16;
+	if ((planes ? !g.l1 : !g.yuv) || (bayer && !g.bayer)) { g_err = "forward level 1: no job table for the kernel"; return -1; }
+	switch (k) {
+	case FwdL1::Packed16: dev::k_fwd_packed16<<<dim3(tiles.x * nch, tiles.y, act), dev::NTHREADS, 0, st>>>(g.l1, nch); break;
+	case FwdL1::GopPacked16: dev::k_fwd_gop_packed16<<<dim3(g.luma_tiles + 2 * g.chroma_tiles, tiles.y, act), dev::NTHREADS, 0, st>>>(g.l1, g.luma_tiles); break;
+	// level 1 straight from the mosaic, every photosite read and curved once, all four component planes from one pass (cfhd_kernels.h k_fwd_bayer_strip)
+	case FwdL1::BayerStrip: dev::k_fwd_bayer_strip<<<(waves + 3) / 4, dev::NTHREADS, 0, st>>>(g.l1, g.bayer, act, nseg, nstrips); break;
+	case FwdL1::BayerUnpack:
+		dev::k_unpack_byr4<<<dim3((hw + dev::NTHREADS - 1) / dev::NTHREADS, g.height, act), dev::NTHREADS, 0, st>>>(g.bayer);      // two quads per thread
+		launch_fwd_plane_tiles(g.l1, g.width, g.height, act * nch, st);
+		break;
+	case FwdL1::Packed16Strip:
+		if (g.pixel_kind == PIX_RG48) dev::k_fwd_packed16_strip<3, 3><<<dim3((waves + 3) / 4), dev::NTHREADS, 0, st>>>(g.l1, act, nseg, nstrips);
+		else if (nch == 4) dev::k_fwd_packed16_strip<4, 4><<<dim3((waves + 3) / 4), dev::NTHREADS, 0, st>>>(g.l1, act, nseg, nstrips);
+		else dev::k_fwd_packed16_strip<4, 3><<<dim3((waves + 3) / 4), dev::NTHREADS, 0, st>>>(g.l1, act, nseg, nstrips);
+		break;
+	case FwdL1::FrameYuv422Strip: dev::k_fwd_frame_yuv422_strip<<<strips422(dev::SRI), dev::NTHREADS, 0, st>>>(frame); break;
+	case FwdL1::FrameYuv422: dev::k_fwd_frame_yuv422<<<dim3((hw + dev::FTW - 1) / dev::FTW, (hh + dev::FRW - 1) / dev::FRW, act), dev::NTHREADS, 0, st>>>(frame); break;
+	case FwdL1::Yuv422StripBlocksDense: dev::k_fwd_yuv422_strip_blocks_dense<<<strips422(dev::SRF), dev::NTHREADS, 0, st>>>(g.yuv); break;
+	case FwdL1::Yuv422StripBlocks: dev::k_fwd_yuv422_strip_blocks<<<strips422(dev::SRF), dev::NTHREADS, 0, st>>>(g.yuv); break;
+	case FwdL1::Yuv422Strip: dev::k_fwd_yuv422_strip<<<strips422(dev::SRF), dev::NTHREADS, 0, st>>>(g.yuv); break;
+	case FwdL1::Yuv422: dev::k_fwd_yuv422<<<tiles, dev::NTHREADS, 0, st>>>(g.yuv); break;
+	}
+	return 0;
 }
 
 const char *EncodeBatch::level_kernel(int level, bool coeffs_needed) const
@@ -647,63 +727,23 @@ int EncodeBatch::launch_forward(bool coeffs_needed)
 	const int nch = plan_.num_channels;
 	const int act = active_frames(active_, n_);                    // frames 0 .. act-1 of the batch hold frames (set_active)
 	EncJobs j = enc_jobs_at(d_jobs_, n_, nch);
-	static_assert(sizeof(dev::FwdFrameJob) == sizeof(dev::FwdYuvJob) && offsetof(dev::FwdFrameJob, q) == offsetof(dev::FwdYuvJob, q), "the two level-1 jobs share one table");
 	(void)hipGetLastError();                            // drop stale sticky errors: the check below is for these launches only
 	timed_ = true;
 	HIPCHK(hipEventRecord((hipEvent_t)ev0_, st));
-	const dim3 tiles((plan_.width / 2 + dev::TW - 1) / dev::TW, (plan_.height / 2 + dev::TH - 1) / dev::TH, act);      // the LDS-tiled kernels: one workgroup per tile of a half-size plane
-	const int nseg16 = (plan_.width / 16 + dev::SSEG - 1) / dev::SSEG;      // 4:2:2 strips: segments of 124 luma blocks (1984 pixels)
-	const int nseg = (plan_.width / 8 + dev::PSTEP - 1) / dev::PSTEP, nstrips = (plan_.height / 2 + dev::PSR - 1) / dev::PSR, waves = act * nseg * nstrips;      // RG48 / b64a / Bayer strips
-	switch (r.l1) {
-	case FwdL1::Packed16:
-		dev::k_fwd_packed16<<<dim3(tiles.x * nch, tiles.y, act), dev::NTHREADS, 0, st>>>(j.l1, nch);
-		break;
-	case FwdL1::BayerStrip:
-		// level 1 straight from the mosaic, every photosite read and curved once, all four component planes from one pass (cfhd_kernels.h k_fwd_bayer_strip)
-		dev::k_fwd_bayer_strip<<<(waves + 3) / 4, dev::NTHREADS, 0, st>>>(j.l1, j.bayer, act, nseg, nstrips);
-		break;
-	case FwdL1::BayerUnpack:
-		dev::k_unpack_byr4<<<dim3((plan_.width / 2 + dev::NTHREADS - 1) / dev::NTHREADS, plan_.height, act), dev::NTHREADS, 0, st>>>(j.bayer);      // two quads per thread
-		dev::k_fwd_plane<<<dim3(tiles.x, tiles.y, act * nch), dev::NTHREADS, 0, st>>>(j.l1);
-		break;
-	case FwdL1::Packed16Strip:
-		if (plan_.pixel_kind == PIX_RG48) dev::k_fwd_packed16_strip<3, 3><<<dim3((waves + 3) / 4), dev::NTHREADS, 0, st>>>(j.l1, act, nseg, nstrips);
-		else if (nch == 4) dev::k_fwd_packed16_strip<4, 4><<<dim3((waves + 3) / 4), dev::NTHREADS, 0, st>>>(j.l1, act, nseg, nstrips);
-		else dev::k_fwd_packed16_strip<4, 3><<<dim3((waves + 3) / 4), dev::NTHREADS, 0, st>>>(j.l1, act, nseg, nstrips);
-		break;
-	case FwdL1::FrameYuv422Strip:
-		dev::k_fwd_frame_yuv422_strip<<<dim3(nseg16, (plan_.height / 2 + dev::SRI - 1) / dev::SRI, act), dev::NTHREADS, 0, st>>>((const dev::FwdFrameJob *)j.yuv);
-		break;
-	case FwdL1::FrameYuv422:
-		dev::k_fwd_frame_yuv422<<<dim3((plan_.width / 2 + dev::FTW - 1) / dev::FTW, (plan_.height / 2 + dev::FRW - 1) / dev::FRW, act), dev::NTHREADS, 0, st>>>((const dev::FwdFrameJob *)j.yuv);
-		break;
-	case FwdL1::Yuv422StripBlocksDense:
-		dev::k_fwd_yuv422_strip_blocks_dense<<<dim3(nseg16, (plan_.height / 2 + dev::SRF - 1) / dev::SRF, act), dev::NTHREADS, 0, st>>>(j.yuv);
-		break;
-	case FwdL1::Yuv422StripBlocks:
-		dev::k_fwd_yuv422_strip_blocks<<<dim3(nseg16, (plan_.height / 2 + dev::SRF - 1) / dev::SRF, act), dev::NTHREADS, 0, st>>>(j.yuv);
-		break;
-	case FwdL1::Yuv422Strip:
-		dev::k_fwd_yuv422_strip<<<dim3(nseg16, (plan_.height / 2 + dev::SRF - 1) / dev::SRF, act), dev::NTHREADS, 0, st>>>(j.yuv);
-		break;
-	case FwdL1::Yuv422:
-		dev::k_fwd_yuv422<<<tiles, dev::NTHREADS, 0, st>>>(j.yuv);
-		break;
-	}
+	rc = launch_first_level(r.l1, { plan_.width, plan_.height, act, j.yuv, j.l1, j.bayer, nch, plan_.pixel_kind, 0, 0 }, st);
+	if (rc) return rc;
 	for (int lv = 1; lv < 3; lv++) {
 		HIPCHK(hipEventRecord((hipEvent_t)evl_[lv - 1], st));
 		const BandDesc &src = plan_.ch[0].band[lv - 1][0];     // luma is the widest plane of the level
 		const dev::FwdPlaneJob *jobs = lv == 1 ? j.l2 : j.l3;
 		if (r.strip_planes[lv - 1]) {
-			const int n = act;
 			for_channel_runs(plan_, lv, [&](int c0, int nc, int glog, const BandDesc &b, int nseg) {
-				const int nstrips = (b.height + dev::SRP - 1) / dev::SRP, per_wave = nseg > 1 ? 1 : 64 >> glog, waves = ((n * nc + per_wave - 1) / per_wave) * nstrips * nseg;
-				dev::k_fwd_plane_strip<<<(waves + 3) / 4, dev::NTHREADS, 0, st>>>(jobs, n, nch, c0, nc, glog, nstrips, 2 * b.width, 2 * b.height, nseg);
+				const PlaneStrips g = plane_strips(act, nc, glog, nseg, b.height);
+				dev::k_fwd_plane_strip<<<g.blocks, dev::NTHREADS, 0, st>>>(jobs, act, nch, c0, nc, glog, g.nstrips, 2 * b.width, 2 * b.height, nseg);
 			});
 			continue;
 		}
-		dim3 grid((src.width / 2 + dev::TW - 1) / dev::TW, (src.height / 2 + dev::TH - 1) / dev::TH, act * nch);
-		dev::k_fwd_plane<<<grid, dev::NTHREADS, 0, st>>>(jobs);
+		launch_fwd_plane_tiles(jobs, src.width, src.height, act * nch, st);
 	}
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipEventRecord((hipEvent_t)ev1_, st));
@@ -789,21 +829,6 @@ static OutputRoute output_route(int encoded_format, int kind, bool half, bool in
 		r.bottom_up = kind == PIX_RG24 || kind == PIX_BGRA; r.big_endian = kind == PIX_R210 || kind == PIX_DPX0;
 	}
 	return r;
-}
-
-// The level-1 wavelet of one frame as the last launch sees it: a frame of an intra batch, or frame f of a two-frame group (the temporal inverse leaves it in w[f])
-struct Level1 { int16_t *band[kMaxChannels][4]; int pitch[kMaxChannels], width[kMaxChannels], height[kMaxChannels]; };
-static Level1 level1_of(const FramePlan &plan, int16_t *base)
-{
-	Level1 l;
-	for (int c = 0; c < plan.num_channels; c++) { const BandDesc *b = plan.ch[c].band[0]; l.pitch[c] = b[0].pitch; l.width[c] = b[0].width; l.height[c] = b[0].height; for (int k = 0; k < 4; k++) l.band[c][k] = base + b[k].offset; }
-	return l;
-}
-static Level1 level1_of(const GopPlan &plan, int f, int16_t *base)
-{
-	Level1 l;
-	for (int c = 0; c < 3; c++) { const GopWavelet &w = plan.ch[c].w[f]; l.pitch[c] = w.pitch; l.width[c] = w.width; l.height[c] = w.height; for (int k = 0; k < 4; k++) l.band[c][k] = base + w.offset[k]; }
-	return l;
 }
 
 // One job of each family (OutJobs) for frame i, into tables that were zeroed: `out` is where the last launch writes the frame -- the output, or the scratch frame of a conversion
@@ -1175,10 +1200,9 @@ int DecodeBatch::launch_inverse(uint32_t dither_seed)
 		const BandDesc &lb = plan_.ch[0].band[lv][0];
 		const dev::InvPlaneJob *jobs = lv == 2 ? j.l3 : j.l2;
 		if (r.strip_planes[lv - 1]) {
-			const int n = act;
 			for_channel_runs(plan_, lv, [&](int c0, int nc, int glog, const BandDesc &cb, int nseg) {
-				const int nstrips = (cb.height + dev::SRP - 1) / dev::SRP, per_wave = nseg > 1 ? 1 : 64 >> glog, waves = ((n * nc + per_wave - 1) / per_wave) * nstrips * nseg;
-				dev::k_inv_plane_strip<<<(waves + 3) / 4, dev::NTHREADS, 0, sl>>>(jobs, n, nch, c0, nc, glog, nstrips, cb.width, cb.height, nseg);
+				const PlaneStrips g = plane_strips(act, nc, glog, nseg, cb.height);
+				dev::k_inv_plane_strip<<<g.blocks, dev::NTHREADS, 0, sl>>>(jobs, act, nch, c0, nc, glog, g.nstrips, cb.width, cb.height, nseg);
 			});
 			HIPCHK(hipEventRecord((hipEvent_t)(inv_split_ ? ev2_[3 - lv] : evl_[2 - lv]), sl));
 			continue;
@@ -1339,21 +1363,14 @@ GopJobs gop_jobs_at(void *base)
 size_t gop_jobs_bytes() { return 2 * sizeof(dev::FwdYuvJob) + 3 * sizeof(dev::GopTemporalJob) + 15 * sizeof(dev::FwdPlaneJob) + 15 * sizeof(dev::InvPlaneJob) + 2 * sizeof(dev::InvYuvJob) + 2 * sizeof(dev::HalfYuvJob) + 3 * sizeof(dev::GopQuantJob); }
 }
 
-// Level 1 of a group's two frames on the way in: one launch over both frames (gridDim.z = 2), and the name a profiler shows it under.
-enum class GopFwdL1 { Yuv422, FrameYuv422, Packed16 };
-static const char *const kGopFwdL1Name[] = {"k_fwd_yuv422", "k_fwd_frame_yuv422", "k_fwd_gop_packed16"};
-static_assert(sizeof(kGopFwdL1Name) / sizeof(*kGopFwdL1Name) == (size_t)GopFwdL1::Packed16 + 1, "one name per level-1 kernel of a group");
-struct GopForwardRoute { GopFwdL1 l1; };
-
-// The forward twin of route(): which kernel transforms the two input frames, from the plan's input kind and interlaced alone; launch_forward(), fill_jobs() and
-// level1_kernel() read this and nothing else.  (Interlaced groups exist for YUY2 / 2vuy only: yuv422_input_served.)
-GopForwardRoute GopBatch::forward_route() const
+// The forward twin of route(): which kernel transforms the two input frames in one launch (gridDim.z = 2), from the plan's input kind and interlaced alone -- tile
+// kernels only; launch_forward(), fill_jobs() and level1_kernel() read this and nothing else.  (Interlaced groups exist for YUY2 / 2vuy only: yuv422_input_served.)
+FwdL1 GopBatch::forward_route() const
 {
-	if (enc_packed16(plan_.pixel_kind)) return { GopFwdL1::Packed16 };
-	return { plan_.interlaced ? GopFwdL1::FrameYuv422 : GopFwdL1::Yuv422 };
+	if (enc_packed16(plan_.pixel_kind)) return FwdL1::GopPacked16;
+	return plan_.interlaced ? FwdL1::FrameYuv422 : FwdL1::Yuv422;
 }
-const char *GopBatch::level1_kernel() const { return decode_ ? "" : kGopFwdL1Name[(int)forward_route().l1]; }
-
+const char *GopBatch::level1_kernel() const { return decode_ ? "" : kFwdL1Name[(int)forward_route()]; }
 
 // The last level of a group's two frames: the intra path's kernel of the output (InvL1, one launch over both frames), then -- outputs made from 16-bit rows --
 // the conversion of both frames' YU64 rows.
@@ -1476,21 +1493,18 @@ void GopBatch::fill_jobs()
 	int16_t *base = d_coeff_;
 	const OutputRoute o = decode_ ? route().out : OutputRoute();
 	for (int f = 0; f < 2; f++) {
-		dev::FwdYuvJob &y = j.yuv[f];
-		y.in = d_frames_ + frame_bytes_ * f; y.in_pitch = pitch_;
-		y.width = plan.width; y.height = plan.height; y.display_height = plan.display_height;
-		y.uyvy = plan.pixel_kind == PIX_2VUY; y.shift = plan.precision - 8;
-		for (int c = 0; c < 3; c++) {
-			const GopWavelet &w = plan.ch[c].w[f];
-			y.out_pitch[c] = w.pitch;
-			for (int b = 0; b < 4; b++) { y.out[c][b] = base + w.offset[b]; y.q[c][b] = make_q(w.quant[b], mpq); }
-			// interlaced groups: the difference-coded band is quantized inside the horizontal filter, midpoint = divisor / prequant without the decrement (spatial.c:5360-5363)
-			if (plan.interlaced && w.quant[2] > 1 && mpq >= 2 && mpq < 9) y.q[c][2].mid = w.quant[2] / mpq;
-		}
+		const uint8_t *frame = d_frames_ + frame_bytes_ * f;
+		const Level1 l1 = level1_of(plan, f, base);
+		fill_fwd_yuv_job(j.yuv[f], frame, pitch_, plan.width, plan.height, plan.display_height, plan.pixel_kind, plan.precision, l1, mpq, plan.interlaced);
+		if (!decode_ && forward_route() == FwdL1::GopPacked16)
+			for (int c = 0; c < 3; c++) {                  // the intra path's loader of this input (EncodeBatch::fill_jobs), the bands and quantizers of the group's w[f]
+				dev::FwdPlaneJob &p = j.fl1[3 * f + c];
+				fill_fwd_plane_job(p, nullptr, 0, plan.ch[c].width, plan.ch[c].height, plan.ch[c].w[f].prescale, fwd_bands(l1, c), mpq);
+				fill_packed16_loader(p, frame, pitch_, plan.pixel_kind, ENC_YUV422, plan.color_matrix, plan.width, plan.precision, plan.display_height, 3, c);
+			}
 		if (!decode_) continue;
 		// the last level of frame f: the intra path's job of the output's family (DecodeBatch::prepare) on the group's w[f].  Outputs made from 16-bit rows: the YU64
 		// rows of frame f go to the scratch frame
-		const Level1 l1 = level1_of(plan, f, base);
 		uint8_t *out = d_tmp_ ? d_tmp_ + tmp_frame_bytes_ * f : d_frames_ + frame_bytes_ * f;
 		const int out_pitch = d_tmp_ ? tmp_pitch_ : pitch_;
 		// (the matrix of frame 1 is the default one: the P-frame sample that hands it out carries no colour space tag, and the reference converts it with 709 -- pinned)
@@ -1502,23 +1516,7 @@ void GopBatch::fill_jobs()
 		case OutJobs::HalfPacked: break;                 // (no output of a 4:2:2 sample)
 		}
 	}
-	if (!decode_ && forward_route().l1 == GopFwdL1::Packed16)
-		for (int f = 0; f < 2; f++)
-			for (int c = 0; c < 3; c++) {                  // the intra path's loader of this input (EncodeBatch::fill_jobs), the bands and quantizers of the group's w[f]
-				const GopWavelet &w = plan.ch[c].w[f];
-				dev::FwdPlaneJob &p = j.fl1[3 * f + c];
-				memset(&p, 0, sizeof(p));
-				fill_packed16_loader(p, d_frames_ + frame_bytes_ * f, pitch_, plan.pixel_kind, ENC_YUV422, plan.color_matrix, plan.width, plan.precision, plan.display_height, 3, c);
-				p.width = plan.ch[c].width; p.height = plan.ch[c].height; p.prescale = w.prescale;
-				p.out_pitch = w.pitch;
-				for (int b = 0; b < 4; b++) { p.out[b] = base + w.offset[b]; p.q[b] = make_q(w.quant[b], mpq); }
-			}
-	auto fwd = [&](dev::FwdPlaneJob &p, const int16_t *in, const GopWavelet &src, const GopWavelet &dst) {
-		p.in = in; p.in_pitch = src.pitch; p.width = src.width; p.height = src.height; p.prescale = dst.prescale;
-		p.xstride = 1; p.shift = 0; p.display_height = src.height; p.compand = 0; p.layout = 0; p.tail_from = 0;
-		p.out_pitch = dst.pitch;
-		for (int b = 0; b < 4; b++) { p.out[b] = base + dst.offset[b]; p.q[b] = make_q(dst.quant[b], mpq); }
-	};
+	auto fwd = [&](dev::FwdPlaneJob &p, const int16_t *in, const GopWavelet &src, const GopWavelet &dst) { fill_fwd_plane_job(p, in, src.pitch, src.width, src.height, dst.prescale, fwd_bands(base, dst), mpq); };
 	auto inv = [&](dev::InvPlaneJob &p, const GopWavelet &src, int16_t *out, int out_pitch) {
 		memset(&p, 0, sizeof(p));
 		for (int b = 0; b < 4; b++) p.band[b] = base + src.offset[b];
@@ -1571,29 +1569,20 @@ int GopBatch::launch_forward()
 	if (jobs_dirty_) { HIPCHK(hipMemcpyAsync(d_jobs_, h_jobs_, jobs_bytes_, hipMemcpyHostToDevice, st)); jobs_dirty_ = false; }
 	GopJobs j = gop_jobs_at(d_jobs_);
 	(void)hipGetLastError();
-	// level 1 of both frames: the spatial transform, or -- interlaced groups -- the frame transform of interlaced intra frames (the two kernels share the job table)
-	// (the 10-bit, 16-bit and RGB inputs: the packed-16 loaders, the planes of a tile row side by side in gridDim.x)
+	// level 1 of both frames (grid z = 2) through the intra path's launcher: the spatial transform, or -- interlaced groups -- the frame transform of interlaced intra
+	// frames (the two kernels share the job table), or -- the 10-bit, 16-bit and RGB inputs -- the packed-16 loaders, the planes of a tile row side by side in gridDim.x
 	const int luma_tiles = (plan_.ch[0].width / 2 + dev::TW - 1) / dev::TW, chroma_tiles = (plan_.ch[1].width / 2 + dev::TW - 1) / dev::TW;
-	switch (forward_route().l1) {
-	case GopFwdL1::FrameYuv422:
-		dev::k_fwd_frame_yuv422<<<dim3((plan_.width / 2 + dev::FTW - 1) / dev::FTW, (plan_.height / 2 + dev::FRW - 1) / dev::FRW, 2), dev::NTHREADS, 0, st>>>((const dev::FwdFrameJob *)j.yuv);
-		break;
-	case GopFwdL1::Yuv422:
-		dev::k_fwd_yuv422<<<dim3((plan_.width / 2 + dev::TW - 1) / dev::TW, (plan_.height / 2 + dev::TH - 1) / dev::TH, 2), dev::NTHREADS, 0, st>>>(j.yuv);
-		break;
-	case GopFwdL1::Packed16:
-		dev::k_fwd_gop_packed16<<<dim3(luma_tiles + 2 * chroma_tiles, (plan_.height / 2 + dev::TH - 1) / dev::TH, 2), dev::NTHREADS, 0, st>>>(j.fl1, luma_tiles);
-		break;
-	}
+	const int rc = launch_first_level(forward_route(), { plan_.width, plan_.height, 2, j.yuv, j.fl1, nullptr, 3, plan_.pixel_kind, luma_tiles, chroma_tiles }, st);
+	if (rc) return rc;
 	const GopWavelet &t = plan_.ch[0].w[2];
 	dev::k_gop_temporal_fwd<<<dim3((unsigned)((t.pitch * t.height / 2 + dev::NTHREADS - 1) / dev::NTHREADS), 3), dev::NTHREADS, 0, st>>>(j.temp);
-	dev::k_fwd_plane<<<dim3((t.width / 2 + dev::TW - 1) / dev::TW, (t.height / 2 + dev::TH - 1) / dev::TH, 6), dev::NTHREADS, 0, st>>>(j.mid);
+	launch_fwd_plane_tiles(j.mid, t.width, t.height, 6, st);
 	if (!decode_ && gop_temporal_lowpass_is_coded(plan_)) {
 		const GopWavelet &w3 = plan_.ch[0].w[3];                         // (luma is the largest of the three bands)
 		dev::k_gop_quant_lowpass<<<dim3((unsigned)((w3.pitch * w3.height / 2 + dev::NTHREADS - 1) / dev::NTHREADS), 3), dev::NTHREADS, 0, st>>>(j.tq);
 	}
 	const GopWavelet &m = plan_.ch[0].w[4];
-	dev::k_fwd_plane<<<dim3((m.width / 2 + dev::TW - 1) / dev::TW, (m.height / 2 + dev::TH - 1) / dev::TH, 3), dev::NTHREADS, 0, st>>>(j.top);
+	launch_fwd_plane_tiles(j.top, m.width, m.height, 3, st);
 	HIPCHK(hipGetLastError());
 	return 0;
 }

@@ -41,28 +41,35 @@ struct FwdPlaneJob {
 	// display_height repeat the last picture row (frame.c:6020-6024)
 	int xstride, shift, display_height;
 	int compand;                            // alpha plane of b64a: 0 < a < 4095 -> ((a * 223 + 128) >> 8) + 256 (frame.c:6696-6707)
-	// v210 (10-bit 4:2:2, three samples per 32-bit word; convert.c:3968 ConvertV210RowToPlanar16s): layout 1 = luma, 2 = channel 1 (Cr),
-	// 3 = channel 2 (Cb); `in` is the start of the frame, rows beyond display_height are zero (frame.c:1481 stops there), and from sample
+	// layout (FwdLayout, below), in the enum's order.  FWD_WORDS16: everything above.
+	// FWD_V210_Y / _CR / _CB: v210 (10-bit 4:2:2, three samples per 32-bit word; convert.c:3968 ConvertV210RowToPlanar16s): luma, channel 1 (Cr),
+	// channel 2 (Cb); `in` is the start of the frame, rows beyond display_height are zero (frame.c:1481 stops there), and from sample
 	// tail_from on -- what the reference's 48-pixel SIMD loop leaves to its scalar loop -- channel 1 repeats the first Cr of every group of
-	// three (the scalar loop stores `v` before it has read the next one, convert.c:4530-4535).  layout 0: everything above.
-	// layout 4 / 5: 8-bit interleaved pixels, bottom / top row first (RG24, BGRA / BGRa; frame.c:6173 ConvertRGBtoRGB48, :6286 ConvertRGBAtoRGB48):
+	// three (the scalar loop stores `v` before it has read the next one, convert.c:4530-4535).
+	// FWD_BYTES8_BOTTOM_UP / _TOP_DOWN: 8-bit interleaved pixels, bottom / top row first (RG24, BGRA / BGRa; frame.c:6173 ConvertRGBtoRGB48, :6286 ConvertRGBAtoRGB48):
 	// `in` is the start of the frame, in_pitch is in BYTES, xstride = bytes per pixel, tail_from = the component's byte inside the pixel;
 	// sample = byte << 4 (compand: the alpha byte of a 4:4:4:4 encode, curved as b64a's); rows beyond display_height zero.
-	// layout 6: 10-bit RGB in one 32-bit word per pixel (r210, DPX0: big-endian; AB10, AR10: little-endian; wavelet.c:3595): in_pitch in 32-bit
+	// FWD_RGB10: 10-bit RGB in one 32-bit word per pixel (r210, DPX0: big-endian; AB10, AR10: little-endian; wavelet.c:3595): in_pitch in 32-bit
 	// words, xstride = 1 for big-endian words, tail_from = bit position of the component; sample = field << 2; rows beyond display_height repeat
 	// the last row (a choice: the reference's fused row pipeline treats them its own way, parity is claimed for heights that are multiples of 8).
-	// layout 8 / 9: 8-bit interleaved pixels (bottom / top row first) converted to one plane of a 10-bit 4:2:2 frame on the way in (frame.c:378; RG24 /
-	// BGRA / BGRa encoded as YUV 4:2:2): xstride = bytes per pixel, tail_from = the plane (0 Y, 1 v, 2 u), shift = the matrix as for layout 7.
-	// layout 7: deep RGB converted to one plane of a 10-bit 4:2:2 frame on the way in (Codec/frame.c:6731 ConvertAnyDeep444to422; RG48 / b64a encoded
+	// FWD_RGB16_AS_422: deep RGB converted to one plane of a 10-bit 4:2:2 frame on the way in (Codec/frame.c:6731 ConvertAnyDeep444to422; RG48 / b64a encoded
 	// as YUV 4:2:2): `in` = the R word of the first pixel (G, B behind it), xstride = words per pixel, tail_from = the plane (0 Y, 1 channel 1 = v,
 	// 2 channel 2 = u), shift = colour space (0 computer-systems 709, 1 video 709, 2 computer 601, 3 video 601); a chroma sample is the mean of
 	// its pixel pair; rows beyond display_height repeat the last row.
-	// layout 10 / 11: one component plane of a Bayer mosaic computed on the way in (BYR4: 16-bit photosites through the encode curve; BYR5: the packed 12-bit
+	// FWD_BYTES8_AS_422_BOTTOM_UP / _TOP_DOWN: 8-bit interleaved pixels (bottom / top row first) converted to one plane of a 10-bit 4:2:2 frame on the way in
+	// (frame.c:378; RG24 / BGRA / BGRa encoded as YUV 4:2:2): xstride = bytes per pixel, tail_from = the plane (0 Y, 1 v, 2 u), shift = the matrix as for
+	// FWD_RGB16_AS_422.
+	// FWD_BAYER_BYR4 / _BYR5: one component plane of a Bayer mosaic computed on the way in (BYR4: 16-bit photosites through the encode curve; BYR5: the packed 12-bit
 	// rows, no curve -- what k_unpack_byr4 writes as planes, without the planes): `in` = the frame, in_pitch = words per mosaic row (BYR4), xstride = pixel order
 	// (BAYER_FORMAT_*), tail_from = the plane (0 G, 1 R-G, 2 B-G, 3 G1-G2), shift = precision, width / display_height those of the component planes.
 	int layout, tail_from;
-	const uint16_t *curve;                  // layout 10: encode curve over 14-bit linear input
+	const uint16_t *curve;                  // FWD_BAYER_BYR4: encode curve over 14-bit linear input
 };
+// FwdPlaneJob::layout: how the loader of k_fwd_packed16 / k_fwd_gop_packed16 reads one component plane out of a packed frame (the values travel in the job tables)
+enum FwdLayout { FWD_WORDS16 = 0, FWD_V210_Y = 1, FWD_V210_CR = 2, FWD_V210_CB = 3, FWD_BYTES8_BOTTOM_UP = 4, FWD_BYTES8_TOP_DOWN = 5, FWD_RGB10 = 6, FWD_RGB16_AS_422 = 7,
+                 FWD_BYTES8_AS_422_BOTTOM_UP = 8, FWD_BYTES8_AS_422_TOP_DOWN = 9, FWD_BAYER_BYR4 = 10, FWD_BAYER_BYR5 = 11 };
+static_assert(FWD_V210_CB < FWD_BYTES8_BOTTOM_UP && FWD_BYTES8_TOP_DOWN < FWD_RGB10 && FWD_RGB10 < FWD_RGB16_AS_422 && FWD_RGB16_AS_422 < FWD_BYTES8_AS_422_BOTTOM_UP &&
+              FWD_BYTES8_AS_422_TOP_DOWN < FWD_BAYER_BYR4 && FWD_BAYER_BYR5 == 11, "fwd_plane_tile's loader tests the pairs as ranges");
 
 // One sample of plane `which` (0 Y, 1 v, 2 u) from the deep RGB pixels at p (luma: pixel x; chroma: pixels 2x, 2x + 1): the reference's integer
 // matrices, arithmetic shifts of the signed sums, clamps to 10 bits (frame.c:6803-6870, :7040-7170).
@@ -106,11 +113,11 @@ __device__ __forceinline__ uint32_t rgb8_to_yuv_sample(const uint8_t *row, int b
 	return (uint32_t)v >> 4;
 }
 
-// One sample of component plane job.tail_from of a Bayer frame (FwdPlaneJob::layout 10 / 11), the arithmetic of k_unpack_byr4.
+// One sample of component plane job.tail_from of a Bayer frame (FWD_BAYER_BYR4 / _BYR5), the arithmetic of k_unpack_byr4.
 __device__ __forceinline__ uint32_t bayer_plane_sample(const FwdPlaneJob &job, int row, int x)
 {
 	int tl, tr, bl, br;
-	if (job.layout == 11) {
+	if (job.layout == FWD_BAYER_BYR5) {
 		const uint8_t *base = (const uint8_t *)job.in + (size_t)row * job.width * 6, *nib = base + (size_t)job.width * 4;
 		int v[4];
 #pragma unroll
@@ -414,12 +421,12 @@ __device__ __forceinline__ int tile_first_row(int r0, int height) { int s = 2 * 
 __device__ __forceinline__ uint32_t v210_sample(const uint32_t *row, int layout, int x, int tail_from)
 {
 	int g, word, shift;
-	if (layout == 1) {
+	if (layout == FWD_V210_Y) {
 		g = x / 6; const int r = x - 6 * g;
 		word = (0x332110 >> (4 * r)) & 15; shift = (0x2805500a >> (5 * r)) & 31;          // words 0 1 1 2 3 3, shifts 10 0 20 10 0 20
 	} else {
 		g = x / 3; int r = x - 3 * g;
-		if (layout == 2) { if (x >= tail_from && r) r--; word = (0x320 >> (4 * r)) & 15; shift = (0x2814 >> (5 * r)) & 31; }   // Cr: words 0 2 3, shifts 20 0 10
+		if (layout == FWD_V210_CR) { if (x >= tail_from && r) r--; word = (0x320 >> (4 * r)) & 15; shift = (0x2814 >> (5 * r)) & 31; }   // Cr: words 0 2 3, shifts 20 0 10
 		else { word = r; shift = 10 * r; }                                                                                  // Cb: words 0 1 2, shifts 0 10 20
 	}
 	return (row[4 * g + word] >> shift) & 0x3ffu;
@@ -458,27 +465,29 @@ __device__ __forceinline__ void fwd_plane_tile(const FwdPlaneJob *jobs, int nch)
 			const int y = row_start + j, dw = c0 - 2 + d;    // dword index within the plane row
 			va[k] = 0;
 			if (i < ROWS * (TW + 4) && y < H && dw >= 0 && dw < HW) {
-				if (PACKED && job.layout >= 10) {
+				// (FwdLayout by name.  The pairs are tested as ranges from the last layout down, the order the compiled kernels have: tested in the enum's order, or one name
+				// at a time, the same chain compiles to other instructions)
+				if (PACKED && job.layout >= FWD_BAYER_BYR4) {
 					const int yy = y < job.display_height ? y : job.display_height - 1;
 					va[k] = bayer_plane_sample(job, yy, 2 * dw) | (bayer_plane_sample(job, yy, 2 * dw + 1) << 16);
-				} else if (PACKED && job.layout == 7) {
+				} else if (PACKED && job.layout == FWD_RGB16_AS_422) {
 					const int yy = y < job.display_height ? y : job.display_height - 1;
 					const uint16_t *row = (const uint16_t *)job.in + (size_t)yy * job.in_pitch;
 					va[k] = rgb16_to_yuv_sample(row, job.xstride, job.tail_from, job.shift, 2 * dw) | (rgb16_to_yuv_sample(row, job.xstride, job.tail_from, job.shift, 2 * dw + 1) << 16);
-				} else if (PACKED && job.layout >= 8) {
+				} else if (PACKED && job.layout >= FWD_BYTES8_AS_422_BOTTOM_UP) {
 					if (y < job.display_height) {
-						const uint8_t *row = (const uint8_t *)job.in + (size_t)(job.layout == 8 ? job.display_height - 1 - y : y) * job.in_pitch;
+						const uint8_t *row = (const uint8_t *)job.in + (size_t)(job.layout == FWD_BYTES8_AS_422_BOTTOM_UP ? job.display_height - 1 - y : y) * job.in_pitch;
 						va[k] = rgb8_to_yuv_sample(row, job.xstride, job.tail_from, job.shift, 2 * dw) | (rgb8_to_yuv_sample(row, job.xstride, job.tail_from, job.shift, 2 * dw + 1) << 16);
 					} else va[k] = job.tail_from ? 0x02000200u : 0x00400040u;       // rows below the picture: Y 64, chroma 512 (frame.c:466-500)
-				} else if (PACKED && job.layout == 6) {
+				} else if (PACKED && job.layout == FWD_RGB10) {
 					const int yy = y < job.display_height ? y : job.display_height - 1;
 					const uint32_t *row = (const uint32_t *)job.in + (size_t)yy * job.in_pitch;
 					uint32_t p0 = row[2 * dw], p1 = row[2 * dw + 1];
 					if (job.xstride) { p0 = __builtin_bswap32(p0); p1 = __builtin_bswap32(p1); }
 					va[k] = (((p0 >> job.tail_from) & 0x3ffu) << 2) | (((p1 >> job.tail_from) & 0x3ffu) << 18);
-				} else if (PACKED && job.layout >= 4) {
+				} else if (PACKED && job.layout >= FWD_BYTES8_BOTTOM_UP) {
 					if (y < job.display_height) {
-						const uint8_t *row = (const uint8_t *)job.in + (size_t)(job.layout == 4 ? job.display_height - 1 - y : y) * job.in_pitch + job.tail_from;
+						const uint8_t *row = (const uint8_t *)job.in + (size_t)(job.layout == FWD_BYTES8_BOTTOM_UP ? job.display_height - 1 - y : y) * job.in_pitch + job.tail_from;
 						uint32_t s0 = (uint32_t)row[(size_t)(2 * dw) * job.xstride] << 4, s1 = (uint32_t)row[(size_t)(2 * dw + 1) * job.xstride] << 4;
 						if (job.compand) {           // alpha of BGRA / BGRa encoded as 4:4:4:4 (frame.c:6415 ConvertRGBAtoRGBA64: the open interval ends at 255 << 4)
 							if (s0 > 0 && s0 < 4080) s0 = ((s0 * 223 + 128) >> 8) + 256;
@@ -486,12 +495,12 @@ __device__ __forceinline__ void fwd_plane_tile(const FwdPlaneJob *jobs, int nch)
 						}
 						va[k] = s0 | (s1 << 16);
 					}
-				} else if (PACKED && job.layout) {
+				} else if (PACKED && job.layout != FWD_WORDS16) {      // FWD_V210_Y / _CR / _CB
 					if (y < job.display_height) {
 						const uint32_t *row = (const uint32_t *)((const uint16_t *)job.in + (size_t)y * job.in_pitch);
 						va[k] = v210_sample(row, job.layout, 2 * dw, job.tail_from) | (v210_sample(row, job.layout, 2 * dw + 1, job.tail_from) << 16);
 					}
-				} else if (PACKED) {
+				} else if (PACKED) {                     // FWD_WORDS16
 					const int yy = y < job.display_height ? y : job.display_height - 1;
 					const uint16_t *px = (const uint16_t *)job.in + (size_t)yy * job.in_pitch + (size_t)(2 * dw) * job.xstride;
 					uint32_t s0 = (uint32_t)px[0] >> job.shift, s1 = (uint32_t)px[job.xstride] >> job.shift;
@@ -1817,7 +1826,7 @@ __global__ void __launch_bounds__(NTHREADS) k_fwd_plane_strip(const FwdPlaneJob 
 }
 
 // =============================================================================================
-// k_fwd_packed16_strip: level 1 of RG48 / b64a (interleaved 16-bit pixels, FwdPlaneJob layout 0) in the register-strip organisation.
+// k_fwd_packed16_strip: level 1 of RG48 / b64a (interleaved 16-bit pixels, FWD_WORDS16) in the register-strip organisation.
 // One lane = 8 pixels of every picture row of its strip, ALL component planes: WPP 16-byte loads bring the pixels in once, the components
 // are cut out of the registers (constant word positions), and every plane runs the horizontal 2/6 analysis of its 4 sample pairs
 // (neighbour pairs from the adjacent lanes) into its own six-row window; every second row the vertical analysis + quantizer emits one row

@@ -77,7 +77,7 @@ void emu_fwd_packed16_shapes(int which, const uint16_t *in, int in_pitch_words, 
 }
 
 // Level 1 of a 4:2:2 frame from deep RGB pixels (RG48: wpp 3, r_word 0; b64a: wpp 4, r_word 1): the conversion happens in the loader of
-// k_fwd_packed16 (layout 7), as EncodeBatch::fill_jobs sets it up.  quant[c*4+b], out[c*4+b]; out_pitch[c].
+// k_fwd_packed16 (FWD_RGB16_AS_422), as EncodeBatch::fill_jobs sets it up.  quant[c*4+b], out[c*4+b]; out_pitch[c].
 void emu_fwd_rgb16_to_yuv422(const uint16_t *in, int in_pitch_words, int wpp, int r_word, int width, int height, int display_height, int color_space,
                              const int *quant, int mpq, int16_t **out, const int *out_pitch)
 {
@@ -86,7 +86,7 @@ void emu_fwd_rgb16_to_yuv422(const uint16_t *in, int in_pitch_words, int wpp, in
 		FwdPlaneJob &job = jobs[c];
 		memset(&job, 0, sizeof(job));
 		job.in = (const int16_t *)(in + r_word); job.in_pitch = in_pitch_words; job.width = c ? width / 2 : width; job.height = height; job.prescale = 0;
-		job.xstride = wpp; job.shift = color_space; job.display_height = display_height; job.layout = 7; job.tail_from = c;
+		job.xstride = wpp; job.shift = color_space; job.display_height = display_height; job.layout = FWD_RGB16_AS_422; job.tail_from = c;
 		for (int b = 0; b < 4; b++) { job.out[b] = out[c * 4 + b]; job.q[b] = make_q(quant[c * 4 + b], mpq); }
 		job.out_pitch = out_pitch[c];
 	}
@@ -94,7 +94,7 @@ void emu_fwd_rgb16_to_yuv422(const uint16_t *in, int in_pitch_words, int wpp, in
 	hipemu::launch(grid, dim3(NTHREADS), [&] { k_fwd_packed16(jobs.data(), 3); });
 }
 
-// Level 1 of a 4:2:2 frame from 8-bit pixels B, G, R(, A) (RG24 / BGRA: bottom row first, layout 8; BGRa: top row first, layout 9), as
+// Level 1 of a 4:2:2 frame from 8-bit pixels B, G, R(, A) (RG24 / BGRA: bottom row first, FWD_BYTES8_AS_422_BOTTOM_UP; BGRa: top row first, FWD_BYTES8_AS_422_TOP_DOWN), as
 // EncodeBatch::fill_jobs sets it up.
 void emu_fwd_rgb8_to_yuv422(const uint8_t *in, int in_pitch, int bpp, int top_down, int width, int height, int display_height, int color_space,
                             const int *quant, int mpq, int16_t **out, const int *out_pitch)
@@ -104,7 +104,7 @@ void emu_fwd_rgb8_to_yuv422(const uint8_t *in, int in_pitch, int bpp, int top_do
 		FwdPlaneJob &job = jobs[c];
 		memset(&job, 0, sizeof(job));
 		job.in = (const int16_t *)in; job.in_pitch = in_pitch; job.width = c ? width / 2 : width; job.height = height; job.prescale = 0;
-		job.xstride = bpp; job.shift = color_space; job.display_height = display_height; job.layout = top_down ? 9 : 8; job.tail_from = c;
+		job.xstride = bpp; job.shift = color_space; job.display_height = display_height; job.layout = top_down ? FWD_BYTES8_AS_422_TOP_DOWN : FWD_BYTES8_AS_422_BOTTOM_UP; job.tail_from = c;
 		for (int b = 0; b < 4; b++) { job.out[b] = out[c * 4 + b]; job.q[b] = make_q(quant[c * 4 + b], mpq); }
 		job.out_pitch = out_pitch[c];
 	}
@@ -136,7 +136,7 @@ void emu_fwd_v210(const uint32_t *in, int in_pitch_bytes, int width, int height,
 		FwdPlaneJob &job = jobs[c];
 		job.in = (const int16_t *)in; job.in_pitch = in_pitch_bytes / 2; job.width = c ? width / 2 : width; job.height = height; job.prescale = 0;
 		job.xstride = 3; job.shift = 6; job.display_height = display_height; job.compand = 0;
-		job.layout = c + 1; job.tail_from = (width - width % 48) / 2;
+		job.layout = FWD_V210_Y + c; job.tail_from = (width - width % 48) / 2;
 		for (int b = 0; b < 4; b++) { job.out[b] = out[c * 4 + b]; job.q[b] = make_q(quant[c * 4 + b], mpq); }
 		job.out_pitch = out_pitch[c];
 	}
@@ -144,7 +144,7 @@ void emu_fwd_v210(const uint32_t *in, int in_pitch_bytes, int width, int height,
 	hipemu::launch(grid, dim3(NTHREADS), [&] { k_fwd_packed16(jobs.data(), 3); });
 }
 
-// Level 1 of an RGB 4:4:4 frame from 8-bit B, G, R bytes, bottom row first (RG24): FwdPlaneJob::layout 4, as EncodeBatch::fill_jobs sets it up.
+// Level 1 of an RGB 4:4:4 frame from 8-bit B, G, R bytes, bottom row first (RG24): FWD_BYTES8_BOTTOM_UP, as EncodeBatch::fill_jobs sets it up.
 void emu_fwd_rg24(const uint8_t *in, int in_pitch_bytes, int width, int height, int display_height, const int *quant, int mpq, int16_t **out, int out_pitch)
 {
 	std::vector<FwdPlaneJob> jobs(3);
@@ -152,7 +152,7 @@ void emu_fwd_rg24(const uint8_t *in, int in_pitch_bytes, int width, int height, 
 		FwdPlaneJob &job = jobs[c];
 		job.in = (const int16_t *)in; job.in_pitch = in_pitch_bytes; job.width = width; job.height = height; job.prescale = 0;
 		job.xstride = 3; job.shift = 4; job.display_height = display_height; job.compand = 0;
-		job.layout = 4; job.tail_from = c == 0 ? 1 : (c == 1 ? 2 : 0);
+		job.layout = FWD_BYTES8_BOTTOM_UP; job.tail_from = c == 0 ? 1 : (c == 1 ? 2 : 0);
 		for (int b = 0; b < 4; b++) { job.out[b] = out[c * 4 + b]; job.q[b] = make_q(quant[c * 4 + b], mpq); }
 		job.out_pitch = out_pitch;
 	}
@@ -160,7 +160,7 @@ void emu_fwd_rg24(const uint8_t *in, int in_pitch_bytes, int width, int height, 
 	hipemu::launch(grid, dim3(NTHREADS), [&] { k_fwd_packed16(jobs.data(), 3); });
 }
 
-// Level 1 of an RGBA 4:4:4:4 frame from 8-bit B, G, R, A bytes (BGRA: bottom row first, layout 4; BGRa: top row first, layout 5); the alpha plane is curved.
+// Level 1 of an RGBA 4:4:4:4 frame from 8-bit B, G, R, A bytes (BGRA: bottom row first, FWD_BYTES8_BOTTOM_UP; BGRa: top row first, FWD_BYTES8_TOP_DOWN); the alpha plane is curved.
 void emu_fwd_rgba8(const uint8_t *in, int in_pitch_bytes, int top_down, int width, int height, int display_height, const int *quant, int mpq, int16_t **out, int out_pitch)
 {
 	std::vector<FwdPlaneJob> jobs(4);
@@ -169,7 +169,7 @@ void emu_fwd_rgba8(const uint8_t *in, int in_pitch_bytes, int top_down, int widt
 		memset(&job, 0, sizeof(job));
 		job.in = (const int16_t *)in; job.in_pitch = in_pitch_bytes; job.width = width; job.height = height; job.prescale = 0;
 		job.xstride = 4; job.shift = 4; job.display_height = display_height; job.compand = c == 3;
-		job.layout = top_down ? 5 : 4; job.tail_from = c == 0 ? 1 : (c == 1 ? 2 : (c == 2 ? 0 : 3));
+		job.layout = top_down ? FWD_BYTES8_TOP_DOWN : FWD_BYTES8_BOTTOM_UP; job.tail_from = c == 0 ? 1 : (c == 1 ? 2 : (c == 2 ? 0 : 3));
 		for (int b = 0; b < 4; b++) { job.out[b] = out[c * 4 + b]; job.q[b] = make_q(quant[c * 4 + b], mpq); }
 		job.out_pitch = out_pitch;
 	}
@@ -177,7 +177,7 @@ void emu_fwd_rgba8(const uint8_t *in, int in_pitch_bytes, int top_down, int widt
 	hipemu::launch(grid, dim3(NTHREADS), [&] { k_fwd_packed16(jobs.data(), 4); });
 }
 
-// Level 1 of an RGB 4:4:4 frame from 10-bit fields of one 32-bit word per pixel (r210 ...): FwdPlaneJob::layout 6.  shifts[c]: bit position of plane c.
+// Level 1 of an RGB 4:4:4 frame from 10-bit fields of one 32-bit word per pixel (r210 ...): FWD_RGB10.  shifts[c]: bit position of plane c.
 void emu_fwd_rgb10(const uint32_t *in, int in_pitch_bytes, int width, int height, int display_height, int big_endian, const int *shifts, const int *quant, int mpq,
                    int16_t **out, int out_pitch)
 {
@@ -186,7 +186,7 @@ void emu_fwd_rgb10(const uint32_t *in, int in_pitch_bytes, int width, int height
 		FwdPlaneJob &job = jobs[c];
 		job.in = (const int16_t *)in; job.in_pitch = in_pitch_bytes / 4; job.width = width; job.height = height; job.prescale = 0;
 		job.xstride = big_endian; job.shift = 0; job.display_height = display_height; job.compand = 0;
-		job.layout = 6; job.tail_from = shifts[c];
+		job.layout = FWD_RGB10; job.tail_from = shifts[c];
 		for (int b = 0; b < 4; b++) { job.out[b] = out[c * 4 + b]; job.q[b] = make_q(quant[c * 4 + b], mpq); }
 		job.out_pitch = out_pitch;
 	}
@@ -336,7 +336,7 @@ void emu_unpack_byr4(const uint16_t *in, int in_pitch_words, int width, int heig
 	hipemu::launch(dim3((width / 2 + NTHREADS - 1) / NTHREADS, height, 1), dim3(NTHREADS), [&] { k_unpack_byr4(&job); });
 }
 
-// Bayer level 1 without the planes: k_fwd_packed16 computing every component plane in its loader (FwdPlaneJob::layout 10 BYR4 / 11 BYR5), as
+// Bayer level 1 without the planes: k_fwd_packed16 computing every component plane in its loader (FWD_BAYER_BYR4 / FWD_BAYER_BYR5), as
 // EncodeBatch::fill_jobs sets it up.  width / height: the component planes (coded height); quant[c*4+b], out[c*4+b].
 void emu_fwd_bayer(const void *in, int in_pitch_words, int width, int height, int display_height, int packed12, const uint16_t *curve, int order,
                    const int *quant, int mpq, int16_t **out, int out_pitch)
@@ -346,7 +346,7 @@ void emu_fwd_bayer(const void *in, int in_pitch_words, int width, int height, in
 		FwdPlaneJob &job = jobs[c];
 		memset(&job, 0, sizeof(job));
 		job.in = (const int16_t *)in; job.in_pitch = in_pitch_words; job.width = width; job.height = height; job.prescale = 0;
-		job.layout = packed12 ? 11 : 10; job.tail_from = c; job.xstride = order; job.shift = 12; job.display_height = display_height; job.curve = curve;
+		job.layout = packed12 ? FWD_BAYER_BYR5 : FWD_BAYER_BYR4; job.tail_from = c; job.xstride = order; job.shift = 12; job.display_height = display_height; job.curve = curve;
 		for (int b = 0; b < 4; b++) { job.out[b] = out[c * 4 + b]; job.q[b] = make_q(quant[c * 4 + b], mpq); }
 		job.out_pitch = out_pitch;
 	}
