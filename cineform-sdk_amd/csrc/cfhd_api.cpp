@@ -42,7 +42,9 @@ enum {
 static const uint32_t FMT_YUY2 = FOURCC_BE('Y', 'U', 'Y', '2'), FMT_2VUY = FOURCC_BE('2', 'v', 'u', 'y'), FMT_YUYV = FOURCC_BE('y', 'u', 'y', 'v'),
                       FMT_RG48 = FOURCC_BE('R', 'G', '4', '8'), FMT_B64A = FOURCC_BE('b', '6', '4', 'a'), FMT_BYR4 = FOURCC_BE('B', 'Y', 'R', '4'), FMT_YU64 = FOURCC_BE('Y', 'U', '6', '4'), FMT_V210 = FOURCC_BE('v', '2', '1', '0'), FMT_RG24 = FOURCC_BE('R', 'G', '2', '4'), FMT_BGRA = FOURCC_BE('B', 'G', 'R', 'A'), FMT_BGRa = FOURCC_BE('B', 'G', 'R', 'a'),
                       FMT_R210 = FOURCC_BE('r', '2', '1', '0'), FMT_DPX0 = FOURCC_BE('D', 'P', 'X', '0'), FMT_AB10 = FOURCC_BE('A', 'B', '1', '0'), FMT_AR10 = FOURCC_BE('A', 'R', '1', '0'),
-                      FMT_RG30 = FOURCC_BE('R', 'G', '3', '0'), FMT_BYR5 = FOURCC_BE('B', 'Y', 'R', '5'), FMT_RG64 = FOURCC_BE('R', 'G', '6', '4');      // (AJA's name for the AB10 word layout: same pixels, its own colour format code in the sample header)
+                      FMT_RG30 = FOURCC_BE('R', 'G', '3', '0'), FMT_BYR5 = FOURCC_BE('B', 'Y', 'R', '5'), FMT_RG64 = FOURCC_BE('R', 'G', '6', '4'),      // (RG30: AJA's name for the AB10 word layout: same pixels, its own colour format code in the sample header)
+                      // the Avid 4:2:2 layouts (Common/CFHDTypes.h:150-154), encoder inputs
+                      FMT_AVU8 = FOURCC_BE('a', 'v', 'u', '8'), FMT_AV28 = FOURCC_BE('a', 'v', '2', '8'), FMT_A214 = FOURCC_BE('a', '2', '1', '4'), FMT_A106 = FOURCC_BE('a', '1', '0', '6'), FMT_AV16 = FOURCC_BE('a', 'v', '1', '6');
 
 namespace {
 #include "cfhd_api_params.h"

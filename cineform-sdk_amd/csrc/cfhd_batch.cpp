@@ -147,7 +147,7 @@ long long cfhd_amd_batch_wait(cfhd_amd_batch *b);
 
 // width x height frames of `pixel_format` encoded as `encoded_format` with `encoding_flags` (the CFHD_PrepareToEncode arguments: YUY2 / 2vuy ->
 // 4:2:2, optionally interlaced; RG48 -> RGB 4:4:4; b64a -> RGBA 4:4:4:4; BYR4 -> Bayer).  mode 0: encode + decode back to the same pixel
-// format; mode 1: encode only (the only mode for BYR4).
+// format; mode 1: encode only (the only mode for BYR4 / BYR5 and the Avid 4:2:2 layouts, which no decoder output has).
 cfhd_amd_batch *cfhd_amd_batch_create_ex(int width, int height, uint32_t pixel_format, int encoded_format, uint32_t encoding_flags, int quality, int nframes, int nthreads, int mode)
 {
 	CallerDevice caller_device;
@@ -165,7 +165,7 @@ cfhd_amd_batch *cfhd_amd_batch_create_ex(int width, int height, uint32_t pixel_f
 	b->color_format = fp.color_format; b->color_space = fp.color_space; b->progressive = fp.progressive;
 	b->decode = mode == 0;
 	b->plan = fp.plan;
-	if (b->decode && (kind == PIX_BYR4 || kind == PIX_BYR5)) { delete b; return nullptr; }
+	if (b->decode && (kind == PIX_BYR4 || kind == PIX_BYR5 || is_avid_422(kind))) { delete b; return nullptr; }      // (no decoder output of these layouts)
 	const char *e = getenv("CFHD_AMD_ENTROPY");
 	b->gpu_entropy = !(e && strcmp(e, "host") == 0);
 	if (!b->gpu_entropy && (!yuv || !b->progressive || !b->decode)) { delete b; return nullptr; }      // the host-entropy arrangement is kept for the headline workload only

@@ -38,6 +38,12 @@ enum PixelKind : int {
 	PIX_AR10,      // little-endian, R 20-29, G 10-19, B 0-9 (124)
 	PIX_RG64,      // 16-bit words R, G, B, A (COLOR_FORMAT_RG64 = 121; encoder input only: to RGBA 4:4:4:4, RGB 4:4:4 or YUV 4:2:2 like b64a, quantized like RG48)
 	PIX_BYR5,      // 12-bit Bayer, per row pair the four components as runs of high bytes, then their low nibbles (COLOR_FORMAT_BYR5 = 105; encoder input only)
+	// The Avid 4:2:2 layouts, Cb Y1 Cr Y2 per pixel pair (encoder inputs only, to YUV 4:2:2; Codec/frame.c:13144-13515)
+	PIX_AVU8,      // 'avu8' bytes, sample = byte << 2 (COLOR_FORMAT_CbYCrY_8bit = 65)
+	PIX_AV16,      // 'av16' 16-bit words, sample = word >> 6 (COLOR_FORMAT_CbYCrY_16bit = 66)
+	PIX_AV28,      // 'av28' two planes: the low two bits of four samples per byte, then the high eight bits as bytes (COLOR_FORMAT_CbYCrY_10bit_2_8 = 67)
+	PIX_A214,      // 'a214' signed 2.14 words, scaled to video range with C's division and clamped (COLOR_FORMAT_CbYCrY_16bit_2_14 = 68)
+	PIX_A106,      // 'a106' 10.6 words, sample = word >> 6 (COLOR_FORMAT_CbYCrY_16bit_10_6 = 69)
 };
 
 // ENCODED_FORMAT_* values as written into the bitstream (Codec/codec.h)
@@ -108,14 +114,17 @@ void derive_quantization(FramePlan *plan, int quality, bool progressive, float f
 // Builds the pyramid geometry for the given encoded dimensions.
 bool build_frame_plan(FramePlan *plan, int width, int height, int pixel_kind, int encoded_format);
 
+static inline bool is_avid_422(int pixel_kind) { return pixel_kind >= PIX_AVU8 && pixel_kind <= PIX_A106; }
 // The inputs that encode to YUV 4:2:2 (CFHD_ENCODED_FORMAT_YUV_422), as intra frames and as two-frame groups alike: make_params and build_gop_plan both ask here (the
 // encode twin of the decoder's yuv422_output_served).  The packed 8-bit formats go through the fused level-1 kernels, the others through the loaders of the packed-16
-// kernel, RGB converted with the reference's integer matrices on the way in.  interlaced (CFHD_ENCODING_FLAGS_YUV_INTERLACED): the frame transform reads YUY2 / 2vuy only.
+// kernel, RGB converted with the reference's integer matrices on the way in, the Avid layouts unpacked.  interlaced (CFHD_ENCODING_FLAGS_YUV_INTERLACED): the frame
+// transform reads YUY2 / 2vuy only.
 static inline bool yuv422_input_served(int pixel_kind, bool interlaced)
 {
 	switch (pixel_kind) {
 	case PIX_YUY2: case PIX_2VUY: return true;
 	case PIX_YU64: case PIX_V210: case PIX_RG24: case PIX_BGRA: case PIX_BGRa: case PIX_RG48: case PIX_B64A: case PIX_RG64: return !interlaced;
+	case PIX_AVU8: case PIX_AV16: case PIX_AV28: case PIX_A214: case PIX_A106: return !interlaced;
 	default: return false;
 	}
 }

@@ -109,7 +109,14 @@ static int16_t *dec_plane_out(void *frame, int out_kind, int c) { return dec_rgb
 // YU64 (Codec/frame.c:1556 ConvertYU64ToFrame16s + convert.c:3345, :14375): words Y0 C1 Y1 C2, every word >> 6 to 10 bits, channel 1 = C1, 2 = C2.
 // v210 (frame.c:1431 ConvertV210ToFrame16s): three 10-bit samples per 32-bit word, FwdPlaneJob::layout tells the loader which component to pick.
 // RG24 (frame.c:6173 ConvertRGBtoRGB48): bytes B, G, R, bottom row first, byte << 4; planes G, R, B.
-static bool enc_packed16(int pixel_kind) { return is_packed16(pixel_kind) || pixel_kind == PIX_RG64 || pixel_kind == PIX_YU64 || pixel_kind == PIX_V210 || pixel_kind == PIX_RG24 || pixel_kind == PIX_BGRA || pixel_kind == PIX_BGRa || (pixel_kind >= PIX_R210 && pixel_kind <= PIX_AR10); }
+// The Avid 4:2:2 layouts (frame.c:13144-13515): Cb Y1 Cr Y2 per pixel pair as bytes (avu8), 16-bit words (av16, a106: the same arithmetic), signed 2.14 words (a214)
+// or -- av28 -- a plane of two-bit fields and a plane of bytes; FwdPlaneJob::layout names the arithmetic (avid_layout).
+static bool enc_packed16(int pixel_kind) { return is_packed16(pixel_kind) || pixel_kind == PIX_RG64 || pixel_kind == PIX_YU64 || pixel_kind == PIX_V210 || pixel_kind == PIX_RG24 || pixel_kind == PIX_BGRA || pixel_kind == PIX_BGRa || (pixel_kind >= PIX_R210 && pixel_kind <= PIX_AR10) || is_avid_422(pixel_kind); }
+static int avid_layout(int pixel_kind) { return pixel_kind == PIX_AVU8 ? dev::FWD_AVID_BYTES8 : (pixel_kind == PIX_A214 ? dev::FWD_AVID_S214 : (pixel_kind == PIX_AV28 ? dev::FWD_AVID_2_8 : dev::FWD_AVID_WORDS16)); }
+// av28: the reference finds the lower plane width x height / 2 bytes into the frame, with the ENCODED height (frame.c:13180 takes the plane's, a multiple of 8), and
+// walks both planes as tightly packed rows whatever the pitch (:13185-13186).  The frame as it is copied: the upper plane up to there, display_height rows of the lower.
+static size_t av28_lower_plane_offset(int width, int height) { return (size_t)width * height / 2; }
+static size_t av28_frame_bytes(int width, int height, int display_height) { return av28_lower_plane_offset(width, height) + (size_t)width * 2 * display_height; }
 static bool enc_bytes8(int pixel_kind) { return pixel_kind == PIX_RG24 || pixel_kind == PIX_BGRA || pixel_kind == PIX_BGRa; }
 static bool enc_rgb10(int pixel_kind) { return pixel_kind >= PIX_R210 && pixel_kind <= PIX_AR10; }
 // bit position of plane c (G, R, B) inside the pixel word of the 10-bit RGB formats
@@ -120,9 +127,15 @@ static int enc_word_of_channel(int pixel_kind, int c) { return pixel_kind == PIX
 static int enc_stride_of_channel(int pixel_kind, int c, int nch) { return pixel_kind == PIX_YU64 ? (c == 0 ? 2 : 4) : (pixel_kind == PIX_B64A || pixel_kind == PIX_RG64 ? 4 : nch); }     // (b64a / RG64 to RGB 4:4:4 have three planes of four-word pixels)
 // The loader of k_fwd_packed16 / k_fwd_gop_packed16 for plane c of one packed frame (FwdPlaneJob: in, in_pitch, xstride, shift, display_height, compand, layout,
 // tail_from), written in one place for the intra batches and the two-frame groups: it reads the frame where fill_fwd_plane_job's job reads a plane.
-static void fill_packed16_loader(dev::FwdPlaneJob &p, const uint8_t *frame8, int in_pitch, int pixel_kind, int encoded_format, int color_matrix, int width, int precision,
+static void fill_packed16_loader(dev::FwdPlaneJob &p, const uint8_t *frame8, int in_pitch, int pixel_kind, int encoded_format, int color_matrix, int width, int height, int precision,
                                  int display_height, int nch, int c)
 {
+	if (is_avid_422(pixel_kind)) {           // planes Y, Cr, Cb of samples Cb Y1 Cr Y2
+		p.in = (const int16_t *)frame8; p.in_pitch = pixel_kind == PIX_AV28 ? 2 * width : in_pitch; p.display_height = display_height; p.compand = 0;
+		p.layout = avid_layout(pixel_kind); p.tail_from = c == 0 ? 1 : (c == 1 ? 2 : 0); p.xstride = c == 0 ? 2 : 4;
+		p.shift = pixel_kind == PIX_AV28 ? (int)av28_lower_plane_offset(width, height) : 0;
+		return;
+	}
 	const uint16_t *frame = (const uint16_t *)frame8;
 	p.in = (const int16_t *)(frame + enc_word_of_channel(pixel_kind, c)); p.in_pitch = in_pitch / 2;
 	p.xstride = enc_stride_of_channel(pixel_kind, c, nch); p.shift = 16 - precision; p.display_height = display_height;
@@ -334,7 +347,9 @@ int packed_frame_pitch(int pixel_kind, int width)
 	case PIX_B64A: case PIX_RG64: return width * 8;
 	case PIX_BYR4: return width * 2;
 	case PIX_BYR5: return width * 3;       // per row PAIR of the mosaic: 4 x width / 2 samples of 12 bits (the unit the frame is laid out in)
-	case PIX_YU64: return width * 4;
+	case PIX_YU64: case PIX_AV16: case PIX_A214: case PIX_A106: return width * 4;
+	case PIX_AVU8: return width * 2;
+	case PIX_AV28: return 0;               // two planes of different row sizes: one block of av28_frame_bytes (EncodeBatch::prepare, GopBatch::prepare)
 	case PIX_RG24: return width * 3;
 	case PIX_BGRA: case PIX_BGRa: case PIX_R210: case PIX_DPX0: case PIX_AB10: case PIX_AR10: return width * 4;
 	case PIX_V210: return (width + 47) / 48 * 128;      // six pixels in 16 bytes, rows padded to 48 pixels (Example/utils.cpp:84-90)
@@ -385,6 +400,7 @@ int EncodeBatch::prepare(const FramePlan &plan, int nframes)
 	// Bayer: the plan describes the component planes (half the mosaic in both directions)
 	in_pitch_ = packed_frame_pitch(plan.pixel_kind, bayer ? 2 * plan.width : plan.width);
 	in_rows_ = plan.pixel_kind == PIX_BYR4 ? 2 * plan.display_height : plan.display_height;      // (BYR5: one packed row per row pair)
+	if (plan.pixel_kind == PIX_AV28) { in_pitch_ = (int)av28_frame_bytes(plan.width, plan.height, plan.display_height); in_rows_ = 1; }      // the whole frame as one row
 	frame_bytes_ = (size_t)in_pitch_ * in_rows_;
 	if (bayer) {
 		plane_elems_ = (size_t)plan.ch[0].band[0][0].pitch * 2 * plan.height;           // plane pitch = 2 x the level-1 band pitch (multiple of 16)
@@ -435,7 +451,7 @@ void EncodeBatch::fill_jobs()
 			for (int c = 0; c < nch; c++) {
 				dev::FwdPlaneJob &p = j.l1[(size_t)i * nch + c];
 				fill_fwd_plane_job(p, nullptr, 0, plan.ch[c].width, plan.ch[c].height, plan.prescale[0], fwd_bands(l1, c), mpq);
-				fill_packed16_loader(p, frame, in_pitch_, plan.pixel_kind, plan.encoded_format, plan.color_matrix, plan.width, plan.precision, plan.display_height, nch, c);
+				fill_packed16_loader(p, frame, in_pitch_, plan.pixel_kind, plan.encoded_format, plan.color_matrix, plan.width, plan.height, plan.precision, plan.display_height, nch, c);
 			}
 		for (int lv = 1; lv < 3; lv++)
 			for (int c = 0; c < nch; c++) {
@@ -512,6 +528,10 @@ int EncodeBatch::upload_frame(int i, const void *frame, int pitch)
 		pitch = in_pitch_;
 	}
 	if (plan_.pixel_kind == PIX_BYR5) pitch = in_pitch_;      // frame.c:5515 walks the frame as tightly packed row pairs of width * 4 * 3 / 2 bytes, whatever the pitch
+	if (plan_.pixel_kind == PIX_AV28) {      // frame.c:13179-13186: likewise; a negative pitch still moves the start (encoder.c:1957)
+		if (pitch < 0) src += (ptrdiff_t)(plan_.display_height - 1) * pitch;
+		pitch = in_pitch_;
+	}
 	if (pitch < 0) { src += (ptrdiff_t)(in_rows_ - 1) * pitch; pitch = -pitch; }     // encoder.c:1957
 	if (pitch >= in_pitch_ && host_buffer_is_registered(src, (size_t)pitch * (in_rows_ - 1) + in_pitch_)) {
 		// a buffer the caller registered: DMA straight out of it (the frame is borrowed until the encode completes, as in the reference)
@@ -540,6 +560,7 @@ int EncodeBatch::upload_frames(const void *frames, size_t frame_stride, int pitc
 {
 	(void)hipSetDevice(device_);
 	if (!frames) return -1;
+	if (plan_.pixel_kind == PIX_AV28 && pitch >= 0) pitch = in_pitch_;      // (ignored: upload_frame)
 	if (pitch == in_pitch_ && frame_stride == frame_bytes_ && plan_.pixel_kind != PIX_BYR4 && plan_.pixel_kind != PIX_BYR5 && host_buffer_is_registered(frames, frame_bytes_ * (size_t)n_)) {
 		HIPCHK(hipMemcpyAsync(d_in_, frames, frame_bytes_ * (size_t)n_, hipMemcpyHostToDevice, (hipStream_t)stream_));
 		return 0;
@@ -1428,6 +1449,7 @@ int GopBatch::prepare(const GopPlan &plan, bool decode, int out_pixel_kind, bool
 	const int out_width = half_ ? plan.width / 2 : plan.width;      // (the output's own row size and row count, which may be half size)
 	pitch_ = packed_frame_pitch(decode ? out_pixel_kind : plan.pixel_kind, out_width); rows_ = half_ ? plan.display_height / 2 : plan.display_height;
 	frame_bytes_ = (size_t)pitch_ * rows_;
+	if (!decode && plan.pixel_kind == PIX_AV28) frame_bytes_ = av28_frame_bytes(plan.width, plan.height, plan.display_height);      // one block, its pitch ignored (upload_frame)
 	HIPCHK(hipMalloc((void **)&d_frames_, 2 * frame_bytes_));
 	HIPCHK(hipHostMalloc((void **)&h_frames_, 2 * frame_bytes_, hipHostMallocPortable));
 	if (decode && out_pixel_kind == PIX_V210) HIPCHK(hipMemsetAsync(d_frames_, 0, 2 * frame_bytes_, (hipStream_t)stream_));      // (row padding beyond the last whole group of 48 pixels stays zero)
@@ -1500,7 +1522,7 @@ void GopBatch::fill_jobs()
 			for (int c = 0; c < 3; c++) {                  // the intra path's loader of this input (EncodeBatch::fill_jobs), the bands and quantizers of the group's w[f]
 				dev::FwdPlaneJob &p = j.fl1[3 * f + c];
 				fill_fwd_plane_job(p, nullptr, 0, plan.ch[c].width, plan.ch[c].height, plan.ch[c].w[f].prescale, fwd_bands(l1, c), mpq);
-				fill_packed16_loader(p, frame, pitch_, plan.pixel_kind, ENC_YUV422, plan.color_matrix, plan.width, plan.precision, plan.display_height, 3, c);
+				fill_packed16_loader(p, frame, pitch_, plan.pixel_kind, ENC_YUV422, plan.color_matrix, plan.width, plan.height, plan.precision, plan.display_height, 3, c);
 			}
 		if (!decode_) continue;
 		// the last level of frame f: the intra path's job of the output's family (DecodeBatch::prepare) on the group's w[f].  Outputs made from 16-bit rows: the YU64
@@ -1554,9 +1576,10 @@ int GopBatch::upload_frame(int f, const void *frame, int pitch)
 	(void)hipSetDevice(device_);
 	if (decode_ || f < 0 || f > 1) return -1;
 	const uint8_t *src = (const uint8_t *)frame;
+	const bool av28 = plan_.pixel_kind == PIX_AV28;      // two planes walked as tightly packed rows whatever the pitch; its sign still moves the start (EncodeBatch::upload_frame)
 	if (pitch < 0) { src += (ptrdiff_t)(rows_ - 1) * pitch; pitch = -pitch; }     // encoder.c:1957
 	uint8_t *dst = h_frames_ + frame_bytes_ * f;
-	if (pitch == pitch_) memcpy(dst, src, frame_bytes_);
+	if (pitch == pitch_ || av28) memcpy(dst, src, frame_bytes_);
 	else for (int r = 0; r < rows_; r++) memcpy(dst + (size_t)r * pitch_, src + (size_t)r * pitch, (size_t)pitch_);
 	HIPCHK(hipMemcpyAsync(d_frames_ + frame_bytes_ * f, dst, frame_bytes_, hipMemcpyHostToDevice, (hipStream_t)stream_));
 	return 0;

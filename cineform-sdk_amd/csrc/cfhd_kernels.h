@@ -62,14 +62,21 @@ struct FwdPlaneJob {
 	// FWD_BAYER_BYR4 / _BYR5: one component plane of a Bayer mosaic computed on the way in (BYR4: 16-bit photosites through the encode curve; BYR5: the packed 12-bit
 	// rows, no curve -- what k_unpack_byr4 writes as planes, without the planes): `in` = the frame, in_pitch = words per mosaic row (BYR4), xstride = pixel order
 	// (BAYER_FORMAT_*), tail_from = the plane (0 G, 1 R-G, 2 B-G, 3 G1-G2), shift = precision, width / display_height those of the component planes.
+	// FWD_AVID_BYTES8 / _WORDS16 / _S214 / _2_8: one plane of an Avid 4:2:2 frame, Cb Y1 Cr Y2 per pixel pair (avu8; av16 and a106; a214; av28 -- frame.c:13386, :13453
+	// and :13319, :13234, :13144): `in` = the frame, in_pitch in BYTES, tail_from = the plane's first sample in a row (Y 1, Cr 2, Cb 0), xstride = samples from one to
+	// the next (2 / 4); sample = byte << 2, word >> 6, the signed 2.14 word scaled to video range (avid_sample), or -- _2_8 -- (byte of the lower plane << 2) | two bits
+	// of the upper plane: the upper plane at `in` with rows of width / 2 bytes, the lower one `shift` BYTES behind it with rows of in_pitch = 2 x width bytes.  Rows
+	// beyond display_height are zero and never read (the reference reads past the caller's frame there: parity for heights that are multiples of 8).
 	int layout, tail_from;
 	const uint16_t *curve;                  // FWD_BAYER_BYR4: encode curve over 14-bit linear input
 };
 // FwdPlaneJob::layout: how the loader of k_fwd_packed16 / k_fwd_gop_packed16 reads one component plane out of a packed frame (the values travel in the job tables)
 enum FwdLayout { FWD_WORDS16 = 0, FWD_V210_Y = 1, FWD_V210_CR = 2, FWD_V210_CB = 3, FWD_BYTES8_BOTTOM_UP = 4, FWD_BYTES8_TOP_DOWN = 5, FWD_RGB10 = 6, FWD_RGB16_AS_422 = 7,
-                 FWD_BYTES8_AS_422_BOTTOM_UP = 8, FWD_BYTES8_AS_422_TOP_DOWN = 9, FWD_BAYER_BYR4 = 10, FWD_BAYER_BYR5 = 11 };
+                 FWD_BYTES8_AS_422_BOTTOM_UP = 8, FWD_BYTES8_AS_422_TOP_DOWN = 9, FWD_BAYER_BYR4 = 10, FWD_BAYER_BYR5 = 11,
+                 FWD_AVID_BYTES8 = 12, FWD_AVID_WORDS16 = 13, FWD_AVID_S214 = 14, FWD_AVID_2_8 = 15 };
 static_assert(FWD_V210_CB < FWD_BYTES8_BOTTOM_UP && FWD_BYTES8_TOP_DOWN < FWD_RGB10 && FWD_RGB10 < FWD_RGB16_AS_422 && FWD_RGB16_AS_422 < FWD_BYTES8_AS_422_BOTTOM_UP &&
-              FWD_BYTES8_AS_422_TOP_DOWN < FWD_BAYER_BYR4 && FWD_BAYER_BYR5 == 11, "fwd_plane_tile's loader tests the pairs as ranges");
+              FWD_BYTES8_AS_422_TOP_DOWN < FWD_BAYER_BYR4 && FWD_BAYER_BYR5 == 11 && FWD_BAYER_BYR5 < FWD_AVID_BYTES8 && FWD_AVID_2_8 == 15,
+              "fwd_plane_tile's loader tests the pairs as ranges");
 
 // One sample of plane `which` (0 Y, 1 v, 2 u) from the deep RGB pixels at p (luma: pixel x; chroma: pixels 2x, 2x + 1): the reference's integer
 // matrices, arithmetic shifts of the signed sums, clamps to 10 bits (frame.c:6803-6870, :7040-7170).
@@ -138,6 +145,25 @@ __device__ __forceinline__ uint32_t bayer_plane_sample(const FwdPlaneJob &job, i
 	const int mid = 1 << (job.shift - 1), g = (g1 + g2) >> 1;
 	const int v = job.tail_from == 0 ? g : (job.tail_from == 1 ? ((r - g) >> 1) + mid : (job.tail_from == 2 ? ((bb - g) >> 1) + mid : (g1 - g2 + 2 * mid) >> 1));
 	return (uint32_t)(uint16_t)v;
+}
+
+// Sample s of row y of an Avid 4:2:2 frame (FWD_AVID_*: s counts Cb Y1 Cr Y2 Cb ... along the row) as its 10-bit plane value.
+// a214 (frame.c:13270-13292): luma ((219 y) / 16384 + 16) << 2, chroma ((224 (c + 8192)) / 16384 + 16) << 2, clamped to 0 .. 1023.  The division is C's, toward
+// zero -- -1 gives (0 + 16) << 2 = 64 where an arithmetic shift gives 60 --: 16383 added to a negative numerator in front of the shift.
+__device__ __forceinline__ uint32_t avid_sample(const FwdPlaneJob &job, int y, int s)
+{
+	const uint8_t *frame = (const uint8_t *)job.in;
+	if (job.layout == FWD_AVID_BYTES8) return (uint32_t)frame[(size_t)y * job.in_pitch + s] << 2;
+	if (job.layout == FWD_AVID_2_8) {
+		const uint32_t upper = frame[(size_t)y * (job.in_pitch >> 2) + (s >> 2)], lower = frame[(size_t)job.shift + (size_t)y * job.in_pitch + s];
+		return (lower << 2) | ((upper >> (6 - 2 * (s & 3))) & 3u);
+	}
+	const uint32_t w = *(const uint16_t *)(frame + (size_t)y * job.in_pitch + 2 * (size_t)s);
+	if (job.layout == FWD_AVID_WORDS16) return w >> 6;
+	const int v = (int)(int16_t)w;
+	const int n = job.tail_from == 1 ? 219 * v : 224 * (v + 8192);
+	const int q = (((n + ((n >> 31) & 16383)) >> 14) + 16) * 4;
+	return (uint32_t)(q < 0 ? 0 : (q > 1023 ? 1023 : q));
 }
 
 // Block lists (k_fwd_yuv422_strip_blocks -> k_ent_count_blocks, cfhd_entropy_kernels.h): the entropy coder wants the nonzero coefficients of the quantized
@@ -467,7 +493,12 @@ __device__ __forceinline__ void fwd_plane_tile(const FwdPlaneJob *jobs, int nch)
 			if (i < ROWS * (TW + 4) && y < H && dw >= 0 && dw < HW) {
 				// (FwdLayout by name.  The pairs are tested as ranges from the last layout down, the order the compiled kernels have: tested in the enum's order, or one name
 				// at a time, the same chain compiles to other instructions)
-				if (PACKED && job.layout >= FWD_BAYER_BYR4) {
+				if (PACKED && job.layout >= FWD_AVID_BYTES8) {
+					if (y < job.display_height) {
+						const int s = job.tail_from + 2 * dw * job.xstride;
+						va[k] = avid_sample(job, y, s) | (avid_sample(job, y, s + job.xstride) << 16);
+					}
+				} else if (PACKED && job.layout >= FWD_BAYER_BYR4) {
 					const int yy = y < job.display_height ? y : job.display_height - 1;
 					va[k] = bayer_plane_sample(job, yy, 2 * dw) | (bayer_plane_sample(job, yy, 2 * dw + 1) << 16);
 				} else if (PACKED && job.layout == FWD_RGB16_AS_422) {

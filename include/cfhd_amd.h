@@ -6,13 +6,15 @@
  * cites the reference interface it replaces.  Handles are opaque; every function returns a
  * CFHD error code (0 = CFHD_ERROR_OKAY, Common/CFHDError.h:25-82).
  *
- * Scope: intra-frame encode of YUY2 / 2vuy (progressive and interlaced), YU64 and v210 -> YUV 4:2:2 10-bit; two-frame groups (CFHD_ENCODING_FLAGS_YUV_2FRAME_GOP)
- * from YUY2 / 2vuy (progressive and interlaced) and from YU64 / v210 / RG24 / BGRA / BGRa / RG48 / b64a / RG64 encoded as YUV 4:2:2 (progressive); RG48 / RG24 / BGRA / BGRa /
+ * Scope: intra-frame encode of YUY2 / 2vuy (progressive and interlaced), YU64, v210 and the Avid 4:2:2 layouts avu8 / av16 / a106 / a214 / av28 (progressive)
+ * -> YUV 4:2:2 10-bit; two-frame groups (CFHD_ENCODING_FLAGS_YUV_2FRAME_GOP) from YUY2 / 2vuy (progressive and interlaced) and from YU64 / v210 / RG24 / BGRA / BGRa /
+ * RG48 / b64a / RG64 / avu8 / av16 / a106 / a214 / av28 encoded as YUV 4:2:2 (progressive); RG48 / RG24 / BGRA / BGRa /
  * r210 / DPX0 / AB10 / AR10 / b64a -> RGB 4:4:4 12-bit, b64a -> RGBA 4:4:4:4 12-bit, BYR4 -> Bayer 12-bit; decode of 4:2:2 samples to
  * YUY2 / 2vuy (full and half resolution, interlaced samples too), RG48 / b64a / BGRA / BGRa (full and half resolution, interlaced samples too)
  * and YU64 (full resolution, progressive samples), RGB 4:4:4 samples to RG48 (and RG24 / BGRA / BGRa
  * at full resolution) and RGBA 4:4:4:4
- * samples to b64a at full and half resolution (DESIGN.md section 1 lists what each round added).  Anything else
+ * samples to b64a at full and half resolution (DESIGN.md section 1 lists what each round added).  The Avid layouts are encoder inputs only: as decoder outputs
+ * they hang off the reference's active-metadata colour engine, which is out of scope ("Refused").  Anything else
  * returns CFHD_ERROR_BADFORMAT (3) / CFHD_ERROR_BAD_RESOLUTION (11).
  * There is no CPU fallback: without a HIP device the encode/decode calls return CFHD_ERROR_INTERNAL (6).
  */
