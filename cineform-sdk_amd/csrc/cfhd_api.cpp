@@ -53,6 +53,8 @@ namespace {
 
 } // namespace
 
+extern "C" { static bool yuv422_output_served(int kind, int width, bool half); }      // cfhd_api_decoder.inc
+
 namespace cfhd {
 int front_end_params(int width, int height, uint32_t pixel_format, int encoded_format, uint32_t encoding_flags, int quality, FrontEndParams *out)
 {
@@ -62,6 +64,13 @@ int front_end_params(int width, int height, uint32_t pixel_format, int encoded_f
 	out->pixel_kind = p.pixel_kind; out->encoded_format = p.encoded_format; out->pixel_bytes = pixel_bytes_of(p.pixel_kind);
 	out->color_format = p.pixel_format == FMT_RG30 ? 122 : color_format_of(p.pixel_kind); out->color_space = p.color_space; out->quality = p.quality; out->progressive = p.progressive;
 	out->plan = p.plan; out->static_quantizer = quantizer_is_static(p);
+	out->gop = p.gop;
+	if (p.gop) {
+		out->gplan = p.gplan; out->gop_static_quantizer = group_quantizer_is_static(p);
+		// (interlaced groups exist from YUY2 / 2vuy only, and those decode to themselves)
+		out->gop_output_served = yuv422_output_served(p.pixel_kind, width, false);
+		out->gop_sequence_format = gop_sequence_input_format(p.pixel_kind, out->color_format);
+	}
 	return 0;
 }
 }

@@ -155,6 +155,19 @@ bool quantizer_is_static(const EncodeParams &p)
 	return true;
 }
 
+// The group twin: the tables derive_gop_quantization deals on the call that opens a group, asked with an absurdly large previous key sample.
+bool group_quantizer_is_static(const EncodeParams &p)
+{
+	if (!p.gop) return true;
+	GopPlan probe = p.gplan; QuantState st = p.gstate;
+	st.lastgopbitcount = (int64_t)p.width * p.height * 128;              // (two frames)
+	if (!derive_gop_quantization(&probe, p.quality, &st, 0.0f, true)) return false;
+	if (probe.midpoint_prequant != p.gplan.midpoint_prequant) return false;
+	for (int c = 0; c < 3; c++)
+		for (int k = 0; k < kGopWavelets; k++) if (memcmp(probe.ch[c].w[k].quant, p.gplan.ch[c].w[k].quant, sizeof(probe.ch[c].w[k].quant)) != 0) return false;
+	return true;
+}
+
 // encode_one for a caller that may share its launches with others encoding the same geometry right now
 int encode_one_gathered(EncodeBatch &own, EncodeParams &p, const void *frame, int pitch, uint32_t frame_number,
                         MetaBlock global, MetaBlock local, uint8_t *out, size_t cap, size_t *size_out, EncodeService *svc)

@@ -6,12 +6,17 @@
 // host copy travels beside it.  CFHD_AMD_HANDOFF=host sends the samples through the host parser and back;
 // CFHD_AMD_ENTROPY=host keeps the run-length/VLC stage on host threads (the reference's own arrangement, Codec/encoder.c:5386 /
 // decoder.c:19534), fed by one D2H copy of the quantized bands and followed by one H2D copy of the dequantized bands.
+//
+// Two-frame groups (CFHD_ENCODING_FLAGS_YUV_2FRAME_GOP): a batch of nframes / 2 groups, frames 2 g and 2 g + 1 forming group g, through two GopBatch objects (encoder |
+// decoder) in the default arrangement only -- every stage on the GPU, the group samples parsed where the coder left them (k_dec_parse_group), one chunk, no host wait
+// between submit and wait.  The P-frame samples and the sequence header are host code.
 #include "../../include/cfhd_amd.h"
 #include "cfhd_core.h"
 #include "cfhd_bitstream.h"
 #include "cfhd_device.h"
 #include "cfhd_metadata.h"
 #include "cfhd_params.h"
+#include "cfhd_gop.h"
 #include <string.h>
 #include <stdlib.h>
 #include <vector>
@@ -23,6 +28,7 @@
 using namespace cfhd;
 
 struct cfhd_amd_chunk { EncodeBatch enc; DecodeBatch dec; int first = 0, n = 0; };
+enum { kPFrameSampleBytes = 24, kSequenceHeaderBytes = 40 };
 
 struct cfhd_amd_batch {
 	FramePlan plan;
@@ -51,7 +57,13 @@ struct cfhd_amd_batch {
 	uint8_t *host_out = nullptr; size_t host_out_stride = 0; int host_out_pitch = 0;
 	double t_launch0 = 0, t_launched = 0;
 	std::vector<void *> shared_streams;      // streams several objects of the batch share (StreamScope): released behind the objects
-	~cfhd_amd_batch() { if (worker.joinable()) worker.join(); chunks.clear(); for (void *s : shared_streams) device_stream_release(s); }
+	// two-frame groups: n / 2 groups on one encoder and (round trips) one decoder object; `chunks` stays empty.  Sample 2 g is group g, sample 2 g + 1 the 24-byte
+	// P-frame sample behind it; both carry frame number steps * n + 2 g + 1, as one CFHD_EncodeSample handle numbers them
+	bool gop = false; GopPlan gplan;
+	std::unique_ptr<GopBatch> genc, gdec;
+	std::vector<uint8_t> pframes; uint8_t sequence_header[64]; size_t sequence_header_size = 0;
+	int ngroups() const { return n / 2; }
+	~cfhd_amd_batch() { if (worker.joinable()) worker.join(); chunks.clear(); genc.reset(); gdec.reset(); for (void *s : shared_streams) device_stream_release(s); }
 };
 
 namespace {
@@ -140,6 +152,132 @@ long long batch_finish(cfhd_amd_batch *b)
 	for (int i = 0; i < b->n; i++) total += (long long)b->sample_size[i];
 	return total;
 }
+
+// The same two halves for a batch of two-frame groups.  gop_launch: (frames from the host,) level 1 of all frames, temporal step and the three spatial wavelets, the
+// entropy coder over the n / 2 group samples -- their headers serialised on the host while the transforms run --; on the decoder's stream the parser behind the coder's
+// headers, the band decoder behind its payloads, the inverse transforms, (the pictures to the host).  Nothing waits.
+int gop_launch(cfhd_amd_batch *b)
+{
+	GopBatch &enc = *b->genc;
+	const int ng = b->ngroups();
+	b->t_launch0 = now();
+	const uint32_t base_number = b->steps * (uint32_t)b->n;
+	// the metadata of the handle's call that completes group g: CFHD_EncodeSample advances it on every call, frame by frame
+	b->frame_meta.resize(b->n);
+	for (int i = 0; i < b->n; i++) { b->meta.handle(); b->frame_meta[i] = b->meta.global; meta_remove_hidden(b->frame_meta[i]); }
+	const uint32_t seed = 0xA511E9B3u * (b->steps + 1);
+	static const int forced = [] { const char *e = getenv("CFHD_AMD_QUEUE"); return e && strcmp(e, "ordered") == 0 ? 2 : (e && strcmp(e, "free") == 0 ? 0 : -1); }();
+	const int turns = forced >= 0 ? forced : (b->decode ? 0 : 1);      // (encode-only passes take turns, round trips run free: batch_launch says why)
+	const bool ordered = turns >= 1, ordered_decode = turns >= 2;
+	if (ordered && stage_order_wait(enc.device(), 0, enc.stream())) return -2;
+	if (b->host_in && enc.upload_frames(b->host_in, b->host_in_stride, b->host_in_pitch)) return -2;
+	if (enc.launch_forward()) return -2;
+	for (int g = 0; g < ng; g++) {
+		const MetaBlock &m = b->frame_meta[2 * g + 1];
+		const uint32_t number = base_number + 2u * (uint32_t)g + 1u;
+		SampleHeaderInfo h = { number, b->color_format, b->color_space, b->quality, b->progressive, m.data(), m.size(), nullptr, 0 };
+		if (enc.entropy().set_frame_header(g, h)) return -6;
+		if (write_pframe_sample(b->gplan, number, b->pframes.data() + (size_t)kPFrameSampleBytes * g, kPFrameSampleBytes) != kPFrameSampleBytes) return -6;
+	}
+	if (enc.entropy().launch()) return -2;
+	if (ordered && stage_order_done(enc.device(), 0, enc.stream())) return -2;
+	if (b->decode) {
+		GopBatch &dec = *b->gdec;
+		if (ordered_decode && stage_order_wait(enc.device(), 1, dec.stream())) return -5;
+		dec.batch_entropy().set_producer_events(enc.entropy().headers_event(), enc.entropy().samples_event());
+		if (dec.batch_entropy().set_samples_device(enc.entropy().device_samples(), enc.entropy().device_sizes(), enc.entropy().device_offsets())) return -4;
+		if (dec.batch_entropy().launch() || dec.launch_inverse(seed, true)) return -5;
+		if (ordered_decode && stage_order_done(enc.device(), 1, dec.stream())) return -5;
+		if (b->host_out && dec.download_frames(b->host_out, b->host_out_stride, b->host_out_pitch)) return -5;
+	}
+	if (enc.entropy().download_queue()) return -2;
+	b->t_launched = now();
+	return 0;
+}
+// gop_finish: as batch_finish.  Returns the sum of the sizes of the group samples or < 0.
+long long gop_finish(cfhd_amd_batch *b)
+{
+	GopBatch &enc = *b->genc;
+	const int ng = b->ngroups();
+	if (enc.entropy().download_finish() || enc.wait()) return -2;
+	// -3 (a sample beyond its buffer: size 0) and -8 (a peak table the device stage cannot write) as for intra batches; -9: a group sample so large that the reference
+	// would have coded bands of the frame wavelets as zeros (encoder.c:8332, gop_sample_may_zero_bands) -- what the device stage wrote is not that sample.  All behind
+	// the loop: the other samples are complete and keep their sizes.
+	bool overflow = false, peaks = false, oversize = false;
+	for (int g = 0; g < ng; g++) {
+		const size_t n = enc.entropy().sample_bytes(g);
+		b->sample_size[2 * g] = n; b->sample_size[2 * g + 1] = n ? (size_t)kPFrameSampleBytes : 0;
+		if (!n) { overflow = true; continue; }
+		if (enc.entropy().needs_peak_table(g)) peaks = true;
+		if (gop_sample_may_zero_bands(b->gplan, n)) oversize = true;
+	}
+	const double t_enc = now();
+	if (b->decode && b->gdec->wait()) return -5;
+	if (overflow) return -3;
+	if (peaks) return -8;
+	if (oversize) return -9;
+	if (b->decode && b->gdec->batch_entropy().check()) return -7;
+	if (b->decode && b->host_out) {
+		std::atomic<int> bad(0);
+		parallel_for(b->n, b->n > 8 ? 8 : 1, [&](int i) { if (b->gdec->finish_frame(i, b->host_out + b->host_out_stride * (size_t)i, b->host_out_pitch)) bad.store(1); });
+		if (bad.load()) return -5;
+	}
+	const double t4 = now();
+	b->t_fwd = b->t_launched - b->t_launch0; b->t_entropy_enc = t_enc - b->t_launched; b->t_entropy_dec = 0; b->t_inv = t4 - t_enc;
+	b->steps++;
+	long long total = 0;
+	for (int g = 0; g < ng; g++) total += (long long)b->sample_size[2 * g];
+	return total;
+}
+void gop_drain(cfhd_amd_batch *b) { (void)b->genc->wait(); if (b->decode) (void)b->gdec->wait(); }
+
+// A batch of two-frame groups (cfhd_amd_batch_create_ex with CFHD_ENCODING_FLAGS_YUV_2FRAME_GOP), or null: never a batch that does something else.
+cfhd_amd_batch *create_group_batch(const FrontEndParams &fp, int width, int height, int nframes, int nthreads, int mode)
+{
+	const int kind = fp.pixel_kind;
+	// whole groups; tables that never move (the group twin of the intra rule below); a w[3] lowpass band the device stage codes (the 8-bit RGB inputs' is the host
+	// writer's); round trips to the input's own format where a group decodes to it
+	if (nframes < 2 || (nframes & 1) || !fp.gop_static_quantizer || gop_temporal_lowpass_is_coded(fp.gplan)) return nullptr;
+	if (mode != 0 && mode != 1) return nullptr;
+	if (mode == 0 && !fp.gop_output_served) return nullptr;
+	const char *e = getenv("CFHD_AMD_ENTROPY");
+	if (e && strcmp(e, "host") == 0) return nullptr;      // (the host arrangement is the C ABI's)
+	cfhd_amd_batch *b = new (std::nothrow) cfhd_amd_batch;
+	if (!b) return nullptr;
+	b->n = nframes; b->nthreads = nthreads > 0 ? nthreads : 1; b->quality = fp.quality; b->pixel_kind = kind;
+	b->color_format = fp.color_format; b->color_space = fp.color_space; b->progressive = fp.progressive;
+	b->decode = mode == 0; b->plan = fp.plan; b->gop = true; b->gplan = fp.gplan;
+	const int ng = nframes / 2;
+	const size_t cap = (size_t)width * height * fp.pixel_bytes + 65536;      // SampleEncoder.cpp:387 (a group beyond 80 % of it fails its pass: -9)
+	b->sequence_header_size = write_sequence_header(b->gplan, fp.gop_sequence_format, b->sequence_header, sizeof(b->sequence_header));
+	b->pframes.assign((size_t)kPFrameSampleBytes * ng, 0);
+	b->samples.resize(nframes); b->sample_size.assign(nframes, 0);
+	// streams as for intra batches (cfhd_amd_batch_create_ex): one per object unless CFHD_AMD_STREAMS = 1; CFHD_AMD_CHUNK is not read -- one chunk
+	const char *sp = getenv("CFHD_AMD_STREAMS"), *hq = getenv("GPU_MAX_HW_QUEUES");
+	const int streams = sp && atoi(sp) >= 1 && atoi(sp) <= 3 ? atoi(sp) : (hq && atoi(hq) >= 8 ? 3 : 2);
+	struct Lean { Lean() { device_streams_lean(true); } ~Lean() { device_streams_lean(false); } } lean;
+	b->genc.reset(new GopBatch);
+	if (b->decode) b->gdec.reset(new GopBatch);
+	auto encoder = [&] { return !b->genc->prepare(b->gplan, false, kind, false, ng) && !b->genc->prepare_entropy(cap); };
+	auto decoder = [&] {
+		if (!b->decode) return true;
+		// the decoder's plan is the sample's: geometry and scan (its quantizers travel in the sample)
+		if (b->gdec->prepare(b->gplan, true, kind, false, ng) || b->gdec->prepare_entropy_decode()) return false;
+		// the outputs that convert to RGB take the matrix of the colour space the group samples are tagged with (frame 1 of every group: 709, GopBatch::fill_jobs)
+		b->gdec->set_color_matrix((fp.color_space & 3) == 1 ? 2 : 0);
+		return true;
+	};
+	bool ok;
+	if (streams == 1) { StreamScope scope; ok = encoder() && decoder(); if (scope.stream()) b->shared_streams.push_back(scope.stream()); }
+	else if (streams == 2) {
+		{ StreamScope scope; ok = encoder(); if (scope.stream()) b->shared_streams.push_back(scope.stream()); }
+		if (ok) { StreamScope scope; ok = decoder(); if (scope.stream()) b->shared_streams.push_back(scope.stream()); }
+	} else ok = encoder() && decoder();
+	if (!ok || b->sequence_header_size != kSequenceHeaderBytes) { delete b; return nullptr; }
+	b->genc->set_timed(true);
+	if (b->decode) b->gdec->set_timed(true);
+	return b;
+}
 }
 
 extern "C" {
@@ -156,6 +294,7 @@ cfhd_amd_batch *cfhd_amd_batch_create_ex(int width, int height, uint32_t pixel_f
 	// A batch encodes its frames in one launch with one set of quantizer tables.  Qualities whose tables follow the size of the previous sample
 	// (FILMSCAN2/3, LOW..HIGH up to 1080p: encoder.c:3414 -> quantize.c:2869) need frame i's sample before frame i + 1 can start -- those
 	// sequences go through CFHD_EncodeSample, which applies the feedback per frame; here they are refused instead of encoded differently.
+	if (fp.gop) return create_group_batch(fp, width, height, nframes, nthreads, mode);
 	if (!fp.static_quantizer) return nullptr;
 	const int kind = fp.pixel_kind;
 	const bool yuv = kind == PIX_YUY2 || kind == PIX_2VUY;
@@ -221,6 +360,7 @@ int cfhd_amd_batch_upload(cfhd_amd_batch *b, int i, const void *frame, int pitch
 {
 	CallerDevice caller_device;
 	if (!b || b->in_flight || i < 0 || i >= b->n) return -1;
+	if (b->gop) { const int rc = b->genc->upload_frame(i, frame, pitch); return rc ? rc : b->genc->wait(); }
 	int l; cfhd_amd_chunk &c = b->chunk_of(i, &l);
 	int rc = c.enc.upload_frame(l, frame, pitch);
 	if (rc) return rc;
@@ -238,6 +378,13 @@ long long cfhd_amd_batch_roundtrip(cfhd_amd_batch *b)
 static long long cfhd_amd_batch_roundtrip_locked(cfhd_amd_batch *b)
 {
 	CallerDevice caller_device;
+	if (b->gop) {
+		const int rc = gop_launch(b);
+		if (rc) { gop_drain(b); return rc; }
+		const long long total = gop_finish(b);
+		if (total < 0) gop_drain(b);
+		return total;
+	}
 	const FramePlan &plan = b->plan;
 	double t0 = now(), t1, t2, t3;
 	std::atomic<int> bad(0);
@@ -386,6 +533,13 @@ int cfhd_amd_batch_submit(cfhd_amd_batch *b)
 	// CFHD_AMD_QUEUE=thread: (A/B) the blocking pass on a thread of its own for the default arrangement too, as in round 4.  (Also measured: the launches of a queued
 	// pass -- 2-3 ms of host time with the serialising of 512 sample headers -- on a short-lived thread instead of the caller's: no difference on any line, profiles/r05_q_*.)
 	static const bool threaded = [] { const char *e = getenv("CFHD_AMD_QUEUE"); return e && strcmp(e, "thread") == 0; }();
+	if (b->gop && !threaded) {
+		b->genc->entropy().set_speculative_download(true);
+		const int rc = gop_launch(b);                      // the whole pass is on the batch's streams when this returns; nothing waits
+		if (rc) { gop_drain(b); b->genc->entropy().set_speculative_download(false); return rc; }
+		b->in_flight = true; b->queued = true;
+		return 0;
+	}
 	if (b->gpu_entropy && b->device_handoff && b->chunks.size() == 1 && !threaded) {
 		b->chunks[0]->enc.entropy().set_speculative_download(true);
 		const int rc = batch_launch(b);                   // the whole pass is on the batch's streams when this returns; nothing waits
@@ -411,10 +565,17 @@ int cfhd_amd_batch_submit_host(cfhd_amd_batch *b, const void *frames, size_t fra
 {
 	CallerDevice caller_device;
 	if (!b || b->in_flight || !frames || pitch <= 0 || (pictures && (!b->decode || picture_pitch <= 0))) return -1;
-	if (!(b->gpu_entropy && b->device_handoff && b->chunks.size() == 1)) return -9;      // (the arrangements with host work in the middle of a pass are not queued: cfhd_amd_batch_upload + _submit)
+	if (!b->gop && !(b->gpu_entropy && b->device_handoff && b->chunks.size() == 1)) return -9;      // (the arrangements with host work in the middle of a pass are not queued: cfhd_amd_batch_upload + _submit)
 	b->pending = -1;
 	b->host_in = (const uint8_t *)frames; b->host_in_stride = frame_stride; b->host_in_pitch = pitch;
 	b->host_out = (uint8_t *)pictures; b->host_out_stride = picture_stride; b->host_out_pitch = picture_pitch;
+	if (b->gop) {
+		b->genc->entropy().set_speculative_download(true);
+		const int rc = gop_launch(b);
+		if (rc) { b->host_in = nullptr; b->host_out = nullptr; gop_drain(b); b->genc->entropy().set_speculative_download(false); return rc; }
+		b->in_flight = true; b->queued = true;
+		return 0;
+	}
 	b->chunks[0]->enc.entropy().set_speculative_download(true);
 	const int rc = batch_launch(b);
 	if (rc) { b->host_in = nullptr; b->host_out = nullptr; (void)b->chunks[0]->enc.wait(); if (b->decode) (void)b->chunks[0]->dec.wait(); b->chunks[0]->enc.entropy().set_speculative_download(false); return rc; }
@@ -426,7 +587,11 @@ long long cfhd_amd_batch_wait(cfhd_amd_batch *b)
 {
 	CallerDevice caller_device;
 	if (!b || !b->in_flight) return -1;
-	if (b->queued) {
+	if (b->queued && b->gop) {
+		b->pending = gop_finish(b);
+		if (b->pending < 0) gop_drain(b);
+		b->host_in = nullptr; b->host_out = nullptr;
+	} else if (b->queued) {
 		b->pending = batch_finish(b);
 		if (b->pending < 0) { cfhd_amd_chunk *c = b->chunks[0].get(); (void)c->enc.wait(); if (b->decode) (void)c->dec.wait(); }      // an error exit must not leave work on the batch's streams (advisor, round 5)
 		b->host_in = nullptr; b->host_out = nullptr;
@@ -440,9 +605,23 @@ long long cfhd_amd_batch_wait(cfhd_amd_batch *b)
 // 8..11 k_ent_count / k_ent_scan / k_ent_layout / k_ent_emit, 12..14 k_dec_parse / band decoder (all its kernels) / k_dec_lowpass,
 // 15..17 k_dec_index / k_dec_chain / k_dec_tiles, 18 the level-1 part of k_ent_count on its own stream (then 8 is the rest of it; 0 when the count is one
 // launch), 19 k_dec_plan (the single workgroup that numbers the chunks in front of k_dec_index) (ms, HIP events on the launch streams)
+// Batches of two-frame groups: 0 level 1 of all frames, 1 the temporal step + the two middle wavelets (k_gop_temporal_fwd, k_fwd_plane over 6 jobs a group), 2 the
+// top wavelet (k_fwd_plane over 3); 3 the last level of all frames + the output conversion, 4 the two middle wavelets + the temporal step (k_inv_plane,
+// k_gop_temporal_inv), 5 the top wavelet (k_inv_plane); 6 / 7 the sums of 0..2 / 3..5; 8..11 as above; 12 k_dec_parse_group, 13 the band decoder (k_dec_bands_par of
+// both code sets + k_dec_undiff), 14 k_dec_lowpass; 15..19: 0 (no chunk-indexed decoder, no split count).  The slots are in launch order 0, 1, 2, 5, 4, 3 as for intra batches.
 float cfhd_amd_batch_kernel_ms(cfhd_amd_batch *b, int which)
 {
 	if (!b || b->in_flight) return 0;
+	if (b->gop) {
+		if (which < 0 || (which >= 3 && which != 6 && !(which >= 8 && which < 12) && !b->decode)) return 0;
+		if (which < 3) return b->genc->stage_ms(which);
+		if (which < 6) return b->gdec->stage_ms(which - 3);
+		if (which == 6) return b->genc->stage_ms(0) + b->genc->stage_ms(1) + b->genc->stage_ms(2);
+		if (which == 7) return b->gdec->stage_ms(0) + b->gdec->stage_ms(1) + b->gdec->stage_ms(2);
+		if (which < 12) return b->genc->entropy().kernel_ms(which - 8);
+		if (which < 15) return b->gdec->batch_entropy().kernel_ms(which - 12);
+		return 0;
+	}
 	float ms = 0;                                        // summed over the chunks (each chunk times its own launches with HIP events on its stream)
 	for (auto &c : b->chunks) {
 		if (which >= 3 && which != 6 && which != 18 && !(which >= 8 && which < 12) && !b->decode) continue;
@@ -460,6 +639,7 @@ float cfhd_amd_batch_kernel_ms(cfhd_amd_batch *b, int which)
 // which as in cfhd_amd_batch_kernel_ms, 0..5: the name of the transform kernel behind that number (the shape depends on geometry and batch size)
 const char *cfhd_amd_batch_kernel_name(cfhd_amd_batch *b, int which)
 {
+	if (b && b->gop) { CallerDevice caller_device; return which < 0 || which > 5 || b->in_flight || (which >= 3 && !b->decode) ? "" : (which < 3 ? b->genc->stage_kernel(which) : b->gdec->stage_kernel(which - 3)); }
 	if (!b || which < 0 || which > 5 || b->chunks.empty() || (which >= 3 && !b->decode)) return "";
 	return which < 3 ? b->chunks[0]->enc.level_kernel(which) : b->chunks[0]->dec.level_kernel(which - 3);
 }
@@ -474,7 +654,7 @@ double cfhd_amd_batch_stage_seconds(cfhd_amd_batch *b, int which)
 // CFHD_AMD_DX_STATS=1: convergence counters of the chunk-indexed entropy decoder, summed over the chunks (16 words; GpuEntropyDecoder::stats)
 int cfhd_amd_batch_dx_stats(cfhd_amd_batch *b, uint32_t *out)
 {
-	if (!b || b->in_flight || !out) return -1;
+	if (!b || b->in_flight || !out || b->gop) return -1;      // (group batches have no chunk-indexed decoder)
 	for (int k = 0; k < 16; k++) out[k] = 0;
 	int rc = -1;
 	if (b->decode) for (auto &c : b->chunks) { uint32_t s[16]; if (c->dec.entropy().stats(s) == 0) { rc = 0; for (int k = 0; k < 16; k++) out[k] = k == 2 ? (s[k] > out[k] ? s[k] : out[k]) : out[k] + s[k]; } }
@@ -483,7 +663,12 @@ int cfhd_amd_batch_dx_stats(cfhd_amd_batch *b, uint32_t *out)
 
 int cfhd_amd_batch_get_sample(cfhd_amd_batch *b, int i, const void **data, size_t *size)
 {
-	if (!b || b->in_flight || i < 0 || i >= b->n) return -1;
+	if (!b || b->in_flight || i < 0 || i >= b->n || !data || !size) return -1;
+	if (b->gop) {                                       // sample 2 g: group g; 2 g + 1: the P-frame sample behind it
+		*data = (i & 1) ? (const void *)(b->pframes.data() + (size_t)kPFrameSampleBytes * (i / 2)) : (const void *)b->genc->entropy().host_sample(i / 2);
+		*size = b->sample_size[i];
+		return 0;
+	}
 	int l; cfhd_amd_chunk &c = b->chunk_of(i, &l);
 	*data = b->gpu_entropy ? (const void *)c.enc.entropy().host_sample(l) : (const void *)b->samples[i].data(); *size = b->sample_size[i];
 	return 0;
@@ -493,9 +678,19 @@ int cfhd_amd_batch_download_output(cfhd_amd_batch *b, int i, void *out, int pitc
 {
 	CallerDevice caller_device;
 	if (!b || b->in_flight || i < 0 || i >= b->n || !b->decode) return -1;
+	if (b->gop) { if (b->gdec->download_frame(i, out, pitch) || b->gdec->wait()) return -2; return b->gdec->finish_frame(i, out, pitch); }
 	int l; cfhd_amd_chunk &c = b->chunk_of(i, &l);
 	if (c.dec.download_frame(l, out, pitch) || c.dec.wait()) return -2;
 	return c.dec.finish_frame(l, out, pitch);
+}
+
+// The 40-byte sequence header a stream of two-frame groups starts with (what a CFHD_EncodeSample handle answers its first call with); -1 for a batch without groups.
+// The batch's samples, pass after pass, are that handle's stream with this header taken out.
+int cfhd_amd_batch_get_sequence_header(cfhd_amd_batch *b, const void **data, size_t *size)
+{
+	if (!b || b->in_flight || !b->gop || !data || !size) return -1;
+	*data = b->sequence_header; *size = b->sequence_header_size;
+	return 0;
 }
 
 } // extern "C"

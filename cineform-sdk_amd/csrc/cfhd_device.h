@@ -166,22 +166,28 @@ private:
 	GpuEntropyDecoder ent_; bool ent_ready_ = false;
 };
 
-// One two-frame group on the GPU (cfhd_gop.h): the kernels of the intra path (level 1 of both frames -- from every input that encodes to 4:2:2 --, the plane
-// transforms of the three spatial wavelets) around the temporal step, forward for the encoder and inverse for the decoder.  The run-length / VLC stage of a group stays on the
-// host (write_group_sample / vlc_decode_band): the coefficient pyramid crosses PCIe, as BASELINE.json's north_star arranges the codec.
+// n two-frame groups on the GPU (cfhd_gop.h; n = 1: the C ABI's handles, n > 1: the group batches of cfhd_batch.cpp): the kernels of the intra path (level 1 of all
+// 2 n frames -- from every input that encodes to 4:2:2 --, the plane transforms of the three spatial wavelets) around the temporal step, forward for the encoder and
+// inverse for the decoder, one launch per stage whatever n is (the job tables are n times as long, the job index stays in blockIdx.y / z).  The run-length / VLC stage
+// runs on the device too: GpuEntropyEncoder::prepare_group codes the n group samples, the decoder of a batch parses and decodes them where the coder left them
+// (GpuGroupBatchEntropyDecoder), the C ABI's decoder takes one host-parsed sample (GpuGroupEntropyDecoder); the host writer / host VLC decoder remain for what the device
+// stage hands back (write_group_sample / vlc_decode_band: the pyramid crosses PCIe then).
 class GopBatch {
 public:
 	GopBatch();
 	~GopBatch();
 	// decode: out_pixel_kind is any output a 4:2:2 sample decodes to (OutputRoute: the last level of both frames is the intra path's job and kernel of that output); half: the
 	// level-1 lowpass planes the temporal inverse leaves are the picture (CFHD_DECODED_RESOLUTION_HALF), the last level is not run
-	int prepare(const GopPlan &plan, bool decode, int out_pixel_kind, bool half = false);
+	// ngroups: frames 2 g and 2 g + 1 form group g; pyramids plan.coeff_elems apart.  A count whose job index would pass the grid limit (65 535) is refused.
+	int prepare(const GopPlan &plan, bool decode, int out_pixel_kind, bool half = false, int ngroups = 1);
 	const GopPlan &plan() const { return plan_; }
+	int ngroups() const { return n_; }
 	void set_color_matrix(int m);                    // decoder: the matrix of the outputs that convert to RGB (FramePlan::color_matrix), from the group sample's colour space tag
 	void set_plan(const GopPlan &plan);              // same geometry, new quantizer tables
 	// encoder
-	int upload_frame(int f, const void *frame, int pitch_bytes);      // f = 0, 1: stage one frame of the pair and start its H2D copy
-	int launch_forward();                            // async: level 1 of both frames, temporal step, three spatial transforms per channel
+	int upload_frame(int f, const void *frame, int pitch_bytes);      // f = 0 .. 2 n - 1: stage one frame and start its H2D copy
+	int upload_frames(const void *frames, size_t frame_stride, int pitch_bytes);      // all 2 n frames, asynchronous on the batch's stream (staged through pinned memory unless registered and back to back)
+	int launch_forward();                            // async: level 1 of all frames, temporal step, three spatial transforms per channel
 	const char *level1_kernel() const;               // name of the kernel the next launch_forward() runs for level 1 of both frames (as a profiler shows it)
 	int download_coeffs();                           // async: the group pyramid -> pinned host
 	// GPU entropy stage for the group sample (GpuEntropyEncoder::prepare_group): entropy().set_frame_header(0, hdr), launch_forward(), entropy().launch(),
@@ -195,6 +201,19 @@ public:
 	// GPU entropy decode of a parsed group sample into the pyramid in HBM (GpuGroupEntropyDecoder); < 0: not served / malformed, decode on the host instead
 	int launch_entropy_decode(const uint8_t *sample, size_t size, const ParsedGroup &pg, size_t sample_cap);
 	int entropy_decode_errors() { return dec_.check(); }                    // after wait()
+	// a batch of groups whose samples lie in HBM (the coder's dense buffer): parsed and decoded there, nothing touches the host; then launch_inverse(seed, true)
+	int prepare_entropy_decode();
+	GpuGroupBatchEntropyDecoder &batch_entropy() { return bdec_; }
+	int16_t *device_coeffs() { return d_coeff_; }
+	void *stream() { return stream_; }
+	int device() const { return device_; }
+	int download_frames(void *out, size_t frame_stride, int pitch_bytes);      // all 2 n frames (finish_frame() for each behind wait())
+	// HIP-event times of the last launch_forward() / launch_inverse() once the stream was synchronised, and the kernels behind them.  Forward: 0 level 1 of all frames,
+	// 1 temporal step + the two middle wavelets, 2 the top wavelet.  Inverse: 0 last level of all frames (+ output conversion), 1 the two middle wavelets + temporal
+	// step, 2 the top wavelet.  set_timed(true) before the launches (the C ABI's handles record no events).
+	void set_timed(bool on);
+	float stage_ms(int k);
+	const char *stage_kernel(int k) const;
 	int launch_inverse(uint32_t dither_seed, bool coeffs_on_device = false);      // async: (pyramid H2D,) three inverse spatial transforms, temporal step, last level of both frames
 	int download_frame(int f, void *out, int pitch_bytes);
 	int finish_frame(int f, void *out, int pitch_bytes);
@@ -204,8 +223,8 @@ private:
 	void fill_jobs();
 	GopRoute route() const;                          // decoder: output_route() of a 4:2:2 sample for the output kind, half and interlaced, and the kernel that serves its family
 	FwdL1 forward_route() const;                     // encoder: the level-1 kernel of both frames, from the input kind and interlaced alone
-	GopPlan plan_; bool decode_ = false, half_ = false; int out_kind_ = 0, device_ = 0, matrix_ = 0;
-	void *stream_ = nullptr;
+	GopPlan plan_; bool decode_ = false, half_ = false; int out_kind_ = 0, device_ = 0, matrix_ = 0, n_ = 1;
+	void *stream_ = nullptr, *ev_[4] = {nullptr, nullptr, nullptr, nullptr}; bool timed_ = false, launched_ = false; mutable char stage_name_[3][64];
 	uint8_t *d_frames_ = nullptr, *h_frames_ = nullptr; size_t frame_bytes_ = 0; int pitch_ = 0, rows_ = 0;
 	// decoder outputs behind a conversion (OutputRoute::convert): the YU64 rows of both frames first
 	uint8_t *d_tmp_ = nullptr; size_t tmp_frame_bytes_ = 0; int tmp_pitch_ = 0;
@@ -213,6 +232,7 @@ private:
 	void *d_jobs_ = nullptr, *h_jobs_ = nullptr; size_t jobs_bytes_ = 0; bool jobs_dirty_ = true;
 	GpuEntropyEncoder ent_; bool ent_ready_ = false;
 	GpuGroupEntropyDecoder dec_; bool dec_ready_ = false;
+	GpuGroupBatchEntropyDecoder bdec_; bool bdec_ready_ = false;
 };
 
 int packed_frame_pitch(int pixel_kind, int width);     // bytes per row of a tightly packed frame

@@ -1360,28 +1360,29 @@ int DecodeBatch::finish_frame(int i, void *out, int pitch)
 // GopBatch
 // =============================================================================================
 namespace {
-struct GopJobs {            // layout of a GopBatch's job table
-	dev::FwdYuvJob *yuv;        // [2]      level 1 of the two frames
-	dev::GopTemporalJob *temp;  // [3]      per channel
-	dev::FwdPlaneJob *mid;      // [6]      w[3] (from the temporal highpass band) and w[4] (from the lowpass band), per channel
-	dev::FwdPlaneJob *top;      // [3]      w[5]
-	dev::InvPlaneJob *itop;     // [3]      w[5] -> lowpass band of w[4]
-	dev::InvPlaneJob *imid;     // [6]      w[4] -> temporal lowpass, w[3] -> temporal highpass
-	dev::InvYuvJob *iyuv;       // [2]      last level of the two frames: k_inv_yuv422 / k_inv_frame_yuv422 / k_inv_yuv422_rgb32 / k_inv_frame_yuv422_rows16(_col)
-	dev::InvPlaneJob *l1;       // [2 * 3]  the same as YU64 rows (k_inv_packed16), frame f channel c at 3 f + c
-	dev::HalfYuvJob *half;      // [2]      half resolution: the level-1 lowpass plane of each frame (k_half_yuv422 / k_half_yu64 / k_half_rgb24)
-	dev::FwdPlaneJob *fl1;      // [2 * 3]  level 1 of the two frames from the inputs of the packed-16 loaders (k_fwd_gop_packed16), frame f plane c at 3 f + c
-	dev::GopQuantJob *tq;       // [3]      the lowpass band of w[3] where it is divided and coded (k_gop_quant_lowpass)
+struct GopJobs {            // layout of a GopBatch's job table: n groups, every row n times as long, group g's entries at g times the row's length of one group
+	dev::FwdYuvJob *yuv;        // [2 n]    level 1 of the frames, frame f of group g at 2 g + f
+	dev::GopTemporalJob *temp;  // [3 n]    per channel
+	dev::FwdPlaneJob *mid;      // [6 n]    w[3] (from the temporal highpass band) and w[4] (from the lowpass band), per channel
+	dev::FwdPlaneJob *top;      // [3 n]    w[5]
+	dev::InvPlaneJob *itop;     // [3 n]    w[5] -> lowpass band of w[4]
+	dev::InvPlaneJob *imid;     // [6 n]    w[4] -> temporal lowpass, w[3] -> temporal highpass
+	dev::InvYuvJob *iyuv;       // [2 n]    last level of the frames: k_inv_yuv422 / k_inv_frame_yuv422 / k_inv_yuv422_rgb32 / k_inv_frame_yuv422_rows16(_col)
+	dev::InvPlaneJob *l1;       // [2 n * 3] the same as YU64 rows (k_inv_packed16), frame f channel c at 3 f + c
+	dev::HalfYuvJob *half;      // [2 n]    half resolution: the level-1 lowpass plane of each frame (k_half_yuv422 / k_half_yu64 / k_half_rgb24)
+	dev::FwdPlaneJob *fl1;      // [2 n * 3] level 1 of the frames from the inputs of the packed-16 loaders (k_fwd_gop_packed16), frame f plane c at 3 f + c
+	dev::GopQuantJob *tq;       // [3 n]    the lowpass band of w[3] where it is divided and coded (k_gop_quant_lowpass)
 };
-GopJobs gop_jobs_at(void *base)
+GopJobs gop_jobs_at(void *base, int n)
 {
 	GopJobs j;
-	j.yuv = (dev::FwdYuvJob *)base; j.temp = (dev::GopTemporalJob *)(j.yuv + 2); j.mid = (dev::FwdPlaneJob *)(j.temp + 3); j.top = j.mid + 6;
-	j.itop = (dev::InvPlaneJob *)(j.top + 3); j.imid = j.itop + 3; j.iyuv = (dev::InvYuvJob *)(j.imid + 6);
-	j.l1 = (dev::InvPlaneJob *)(j.iyuv + 2); j.half = (dev::HalfYuvJob *)(j.l1 + 6); j.fl1 = (dev::FwdPlaneJob *)(j.half + 2); j.tq = (dev::GopQuantJob *)(j.fl1 + 6);
+	j.yuv = (dev::FwdYuvJob *)base; j.temp = (dev::GopTemporalJob *)(j.yuv + 2 * n); j.mid = (dev::FwdPlaneJob *)(j.temp + 3 * n); j.top = j.mid + 6 * n;
+	j.itop = (dev::InvPlaneJob *)(j.top + 3 * n); j.imid = j.itop + 3 * n; j.iyuv = (dev::InvYuvJob *)(j.imid + 6 * n);
+	j.l1 = (dev::InvPlaneJob *)(j.iyuv + 2 * n); j.half = (dev::HalfYuvJob *)(j.l1 + 6 * n); j.fl1 = (dev::FwdPlaneJob *)(j.half + 2 * n); j.tq = (dev::GopQuantJob *)(j.fl1 + 6 * n);
 	return j;
 }
-size_t gop_jobs_bytes() { return 2 * sizeof(dev::FwdYuvJob) + 3 * sizeof(dev::GopTemporalJob) + 15 * sizeof(dev::FwdPlaneJob) + 15 * sizeof(dev::InvPlaneJob) + 2 * sizeof(dev::InvYuvJob) + 2 * sizeof(dev::HalfYuvJob) + 3 * sizeof(dev::GopQuantJob); }
+size_t gop_jobs_bytes(int n) { return (size_t)n * (2 * sizeof(dev::FwdYuvJob) + 3 * sizeof(dev::GopTemporalJob) + 15 * sizeof(dev::FwdPlaneJob) + 15 * sizeof(dev::InvPlaneJob) + 2 * sizeof(dev::InvYuvJob) + 2 * sizeof(dev::HalfYuvJob) + 3 * sizeof(dev::GopQuantJob)); }
+enum { kMaxGridYZ = 65535 };
 }
 
 // The forward twin of route(): which kernel transforms the two input frames in one launch (gridDim.z = 2), from the plan's input kind and interlaced alone -- tile
@@ -1425,6 +1426,9 @@ void GopBatch::release()
 	if (stream_) hipStreamSynchronize((hipStream_t)stream_);
 	ent_ready_ = false;                              // (its buffers go with the object or with the next prepare_group(); it is not used before prepare_entropy() ran again)
 	if (dec_ready_) { dec_.release(); dec_ready_ = false; }
+	if (bdec_ready_) { bdec_.release(); bdec_ready_ = false; }
+	for (void *&e : ev_) if (e) { (void)hipEventDestroy((hipEvent_t)e); e = nullptr; }
+	launched_ = false;
 	if (d_frames_) hipFree(d_frames_);
 	if (h_frames_) hipHostFree(h_frames_);
 	if (d_tmp_) hipFree(d_tmp_);
@@ -1436,13 +1440,16 @@ void GopBatch::release()
 	d_frames_ = h_frames_ = d_tmp_ = nullptr; d_coeff_ = h_coeff_ = nullptr; d_jobs_ = h_jobs_ = nullptr; stream_ = nullptr;
 }
 
-int GopBatch::prepare(const GopPlan &plan, bool decode, int out_pixel_kind, bool half)
+int GopBatch::prepare(const GopPlan &plan, bool decode, int out_pixel_kind, bool half, int ngroups)
 {
 	int rc = device_init();
 	if (rc) return rc;
 	release();
+	// the job index of every launch stays in blockIdx.y / z: 6 n plane jobs (k_fwd_plane / k_inv_plane, k_dec_lowpass), 6 n planes of the packed-16 last level
+	if (ngroups < 1 || 6 * (long long)ngroups > kMaxGridYZ) { g_err = "two-frame groups: the batch's job index would pass the grid limit"; return -2; }
 	device_ = device_current(); (void)hipSetDevice(device_);
-	plan_ = plan; decode_ = decode; out_kind_ = out_pixel_kind; half_ = decode && half;
+	plan_ = plan; decode_ = decode; out_kind_ = out_pixel_kind; half_ = decode && half; n_ = ngroups;
+	const size_t nf = 2 * (size_t)n_;
 	const GopRoute r = route();
 	if (decode && r.l1 == InvL1::Refused) { g_err = "two-frame groups: output not served"; return -2; }
 	HIPCHK((hipError_t)device_stream_create(&stream_));
@@ -1450,19 +1457,20 @@ int GopBatch::prepare(const GopPlan &plan, bool decode, int out_pixel_kind, bool
 	pitch_ = packed_frame_pitch(decode ? out_pixel_kind : plan.pixel_kind, out_width); rows_ = half_ ? plan.display_height / 2 : plan.display_height;
 	frame_bytes_ = (size_t)pitch_ * rows_;
 	if (!decode && plan.pixel_kind == PIX_AV28) frame_bytes_ = av28_frame_bytes(plan.width, plan.height, plan.display_height);      // one block, its pitch ignored (upload_frame)
-	HIPCHK(hipMalloc((void **)&d_frames_, 2 * frame_bytes_));
-	HIPCHK(hipHostMalloc((void **)&h_frames_, 2 * frame_bytes_, hipHostMallocPortable));
-	if (decode && out_pixel_kind == PIX_V210) HIPCHK(hipMemsetAsync(d_frames_, 0, 2 * frame_bytes_, (hipStream_t)stream_));      // (row padding beyond the last whole group of 48 pixels stays zero)
+	HIPCHK(hipMalloc((void **)&d_frames_, nf * frame_bytes_));
+	HIPCHK(hipHostMalloc((void **)&h_frames_, nf * frame_bytes_, hipHostMallocPortable));
+	if (decode && out_pixel_kind == PIX_V210) HIPCHK(hipMemsetAsync(d_frames_, 0, nf * frame_bytes_, (hipStream_t)stream_));      // (row padding beyond the last whole group of 48 pixels stays zero)
 	tmp_pitch_ = 0; tmp_frame_bytes_ = 0;
 	if (decode && r.out.convert != OutConvert::None) {
 		tmp_pitch_ = packed_frame_pitch(PIX_YU64, out_width); tmp_frame_bytes_ = (size_t)tmp_pitch_ * rows_;
-		HIPCHK(hipMalloc((void **)&d_tmp_, 2 * tmp_frame_bytes_));
+		HIPCHK(hipMalloc((void **)&d_tmp_, nf * tmp_frame_bytes_));
 	}
-	HIPCHK(hipMalloc((void **)&d_coeff_, plan.coeff_elems * 2));
-	HIPCHK(hipMemsetAsync(d_coeff_, 0, plan.coeff_elems * 2, (hipStream_t)stream_));      // pad columns stay zero forever
+	HIPCHK(hipMalloc((void **)&d_coeff_, (size_t)n_ * plan.coeff_elems * 2));
+	HIPCHK(hipMemsetAsync(d_coeff_, 0, (size_t)n_ * plan.coeff_elems * 2, (hipStream_t)stream_));      // pad columns stay zero forever
+	// (the host's copy of the pyramid serves the host coder of the C ABI's single group: a batch of groups never brings its pyramids to the host)
 	HIPCHK(hipHostMalloc((void **)&h_coeff_, plan.coeff_elems * 2, hipHostMallocPortable));
 	memset(h_coeff_, 0, plan.coeff_elems * 2);
-	jobs_bytes_ = gop_jobs_bytes();
+	jobs_bytes_ = gop_jobs_bytes(n_);
 	HIPCHK(hipMalloc(&d_jobs_, jobs_bytes_));
 	HIPCHK(hipHostMalloc(&h_jobs_, jobs_bytes_, hipHostMallocPortable));
 	memset(h_jobs_, 0, jobs_bytes_);
@@ -1491,9 +1499,53 @@ int GopBatch::prepare_entropy(size_t sample_cap)
 	(void)hipSetDevice(device_);
 	ent_ready_ = false;
 	if (decode_ || !d_coeff_) return -1;
-	const int rc = ent_.prepare_group(plan_, 1, d_coeff_, plan_.coeff_elems, sample_cap, stream_);
+	const int rc = ent_.prepare_group(plan_, n_, d_coeff_, plan_.coeff_elems, sample_cap, stream_);
 	ent_ready_ = rc == 0;
 	return rc;
+}
+
+int GopBatch::prepare_entropy_decode()
+{
+	(void)hipSetDevice(device_);
+	bdec_ready_ = false;
+	if (!decode_ || !d_coeff_) return -1;
+	const int rc = bdec_.prepare(plan_, n_, d_coeff_, plan_.coeff_elems, out_kind_, stream_, device_);
+	bdec_ready_ = rc == 0;
+	return rc;
+}
+
+void GopBatch::set_timed(bool on)
+{
+	(void)hipSetDevice(device_);
+	if (on) for (void *&e : ev_) if (!e && hipEventCreate((hipEvent_t *)&e) != hipSuccess) { (void)hipGetLastError(); e = nullptr; on = false; }
+	timed_ = on;
+}
+
+float GopBatch::stage_ms(int k)
+{
+	float ms = 0;
+	if (!timed_ || !launched_ || k < 0 || k > 2) return 0;
+	// forward: events in launch order; inverse: the top wavelet runs first, the last level last
+	const int a = decode_ ? 2 - k : k;
+	if (hipEventElapsedTime(&ms, (hipEvent_t)ev_[a], (hipEvent_t)ev_[a + 1]) != hipSuccess) { (void)hipGetLastError(); return 0; }
+	return ms;
+}
+
+// (the names as a profiler shows them, "a+b": two launches in that order)
+const char *GopBatch::stage_kernel(int k) const
+{
+	if (k < 0 || k > 2) return "";
+	if (!decode_) {
+		if (k == 0) return level1_kernel();
+		if (k == 2) return "k_fwd_plane";
+		return gop_temporal_lowpass_is_coded(plan_) ? "k_gop_temporal_fwd+k_fwd_plane+k_gop_quant_lowpass" : "k_gop_temporal_fwd+k_fwd_plane";
+	}
+	if (k == 2) return "k_inv_plane";
+	if (k == 1) return "k_inv_plane+k_gop_temporal_inv";
+	const GopRoute r = route();
+	static const char *const conv[] = {"", "+k_yu64_to_v210", "+k_yu64_to_rgb24", "+k_yu64_to_rgb16", "+k_bayer_to_byr4"};
+	snprintf(stage_name_[0], sizeof(stage_name_[0]), "%s%s", kInvL1Name[(int)r.l1], conv[(int)r.out.convert]);
+	return stage_name_[0];
 }
 
 int GopBatch::launch_entropy_decode(const uint8_t *sample, size_t size, const ParsedGroup &pg, size_t sample_cap)
@@ -1510,12 +1562,17 @@ int GopBatch::launch_entropy_decode(const uint8_t *sample, size_t size, const Pa
 void GopBatch::fill_jobs()
 {
 	const GopPlan &plan = plan_;
-	GopJobs j = gop_jobs_at(h_jobs_);
+	const GopJobs all = gop_jobs_at(h_jobs_, n_);
 	const int mpq = plan.midpoint_prequant;
-	int16_t *base = d_coeff_;
 	const OutputRoute o = decode_ ? route().out : OutputRoute();
+	for (int g = 0; g < n_; g++) {
+	// group g: its rows of the table, its pyramid, its two frames
+	GopJobs j = all;
+	j.yuv += 2 * g; j.temp += 3 * g; j.mid += 6 * g; j.top += 3 * g; j.itop += 3 * g; j.imid += 6 * g; j.iyuv += 2 * g; j.l1 += 6 * g; j.half += 2 * g; j.fl1 += 6 * g; j.tq += 3 * g;
+	int16_t *base = d_coeff_ + (size_t)g * plan.coeff_elems;
 	for (int f = 0; f < 2; f++) {
-		const uint8_t *frame = d_frames_ + frame_bytes_ * f;
+		const int fi = 2 * g + f;                          // the frame's place in the batch: its buffers, its dither
+		const uint8_t *frame = d_frames_ + frame_bytes_ * fi;
 		const Level1 l1 = level1_of(plan, f, base);
 		fill_fwd_yuv_job(j.yuv[f], frame, pitch_, plan.width, plan.height, plan.display_height, plan.pixel_kind, plan.precision, l1, mpq, plan.interlaced);
 		if (!decode_ && forward_route() == FwdL1::GopPacked16)
@@ -1527,14 +1584,14 @@ void GopBatch::fill_jobs()
 		if (!decode_) continue;
 		// the last level of frame f: the intra path's job of the output's family (DecodeBatch::prepare) on the group's w[f].  Outputs made from 16-bit rows: the YU64
 		// rows of frame f go to the scratch frame
-		uint8_t *out = d_tmp_ ? d_tmp_ + tmp_frame_bytes_ * f : d_frames_ + frame_bytes_ * f;
+		uint8_t *out = d_tmp_ ? d_tmp_ + tmp_frame_bytes_ * fi : d_frames_ + frame_bytes_ * fi;
 		const int out_pitch = d_tmp_ ? tmp_pitch_ : pitch_;
 		// (the matrix of frame 1 is the default one: the P-frame sample that hands it out carries no colour space tag, and the reference converts it with 709 -- pinned)
 		const int matrix = f == 0 ? matrix_ : 0;
 		switch (o.jobs) {
 		case OutJobs::HalfYuv: fill_half_yuv_job(j.half[f], l1, o, rows_, matrix, out, out_pitch); break;
-		case OutJobs::Planes16: fill_planes16_jobs(&j.l1[3 * f], l1, o, 3, 3, plan.precision, plan.display_height, f, out, out_pitch); break;
-		case OutJobs::Yuv: fill_inv_yuv_job(j.iyuv[f], l1, o, plan.precision, plan.display_height, matrix, f, out, out_pitch); break;
+		case OutJobs::Planes16: fill_planes16_jobs(&j.l1[3 * f], l1, o, 3, 3, plan.precision, plan.display_height, fi, out, out_pitch); break;
+		case OutJobs::Yuv: fill_inv_yuv_job(j.iyuv[f], l1, o, plan.precision, plan.display_height, matrix, fi, out, out_pitch); break;
 		case OutJobs::HalfPacked: break;                 // (no output of a 4:2:2 sample)
 		}
 	}
@@ -1568,13 +1625,14 @@ void GopBatch::fill_jobs()
 		inv(j.imid[2 * c], ch.w[4], base + ch.w[2].offset[0], ch.w[2].pitch);
 		inv(j.imid[2 * c + 1], ch.w[3], base + ch.w[2].offset[1], ch.w[2].pitch);
 	}
+	}
 	jobs_dirty_ = true;
 }
 
 int GopBatch::upload_frame(int f, const void *frame, int pitch)
 {
 	(void)hipSetDevice(device_);
-	if (decode_ || f < 0 || f > 1) return -1;
+	if (decode_ || f < 0 || f >= 2 * n_) return -1;
 	const uint8_t *src = (const uint8_t *)frame;
 	const bool av28 = plan_.pixel_kind == PIX_AV28;      // two planes walked as tightly packed rows whatever the pitch; its sign still moves the start (EncodeBatch::upload_frame)
 	if (pitch < 0) { src += (ptrdiff_t)(rows_ - 1) * pitch; pitch = -pitch; }     // encoder.c:1957
@@ -1585,28 +1643,55 @@ int GopBatch::upload_frame(int f, const void *frame, int pitch)
 	return 0;
 }
 
+// All 2 n frames from the caller's memory, queued on the batch's stream: one copy as they are when they lie back to back at the batch's own pitch in a registered
+// buffer, otherwise staged through the batch's pinned frames by the calling thread (the caller waits for the previous pass before it submits the next: the staging
+// buffer is free) and copied in one piece.
+int GopBatch::upload_frames(const void *frames, size_t frame_stride, int pitch)
+{
+	(void)hipSetDevice(device_);
+	if (decode_ || !frames || pitch <= 0) return -1;
+	const size_t total = 2 * (size_t)n_ * frame_bytes_;
+	const bool av28 = plan_.pixel_kind == PIX_AV28;
+	if ((pitch == pitch_ || av28) && frame_stride == frame_bytes_ && host_buffer_is_registered(frames, total)) {
+		HIPCHK(hipMemcpyAsync(d_frames_, frames, total, hipMemcpyHostToDevice, (hipStream_t)stream_));
+		return 0;
+	}
+	for (int f = 0; f < 2 * n_; f++) {
+		const uint8_t *src = (const uint8_t *)frames + frame_stride * (size_t)f;
+		uint8_t *dst = h_frames_ + frame_bytes_ * f;
+		if (pitch == pitch_ || av28) memcpy(dst, src, frame_bytes_);
+		else for (int r = 0; r < rows_; r++) memcpy(dst + (size_t)r * pitch_, src + (size_t)r * pitch, (size_t)(pitch < pitch_ ? pitch : pitch_));
+	}
+	HIPCHK(hipMemcpyAsync(d_frames_, h_frames_, total, hipMemcpyHostToDevice, (hipStream_t)stream_));
+	return 0;
+}
+
 int GopBatch::launch_forward()
 {
 	(void)hipSetDevice(device_);
 	hipStream_t st = (hipStream_t)stream_;
 	if (jobs_dirty_) { HIPCHK(hipMemcpyAsync(d_jobs_, h_jobs_, jobs_bytes_, hipMemcpyHostToDevice, st)); jobs_dirty_ = false; }
-	GopJobs j = gop_jobs_at(d_jobs_);
+	GopJobs j = gop_jobs_at(d_jobs_, n_);
 	(void)hipGetLastError();
-	// level 1 of both frames (grid z = 2) through the intra path's launcher: the spatial transform, or -- interlaced groups -- the frame transform of interlaced intra
+	if (timed_) HIPCHK(hipEventRecord((hipEvent_t)ev_[0], st));
+	// level 1 of all frames (grid z = 2 n) through the intra path's launcher: the spatial transform, or -- interlaced groups -- the frame transform of interlaced intra
 	// frames (the two kernels share the job table), or -- the 10-bit, 16-bit and RGB inputs -- the packed-16 loaders, the planes of a tile row side by side in gridDim.x
 	const int luma_tiles = (plan_.ch[0].width / 2 + dev::TW - 1) / dev::TW, chroma_tiles = (plan_.ch[1].width / 2 + dev::TW - 1) / dev::TW;
-	const int rc = launch_first_level(forward_route(), { plan_.width, plan_.height, 2, j.yuv, j.fl1, nullptr, 3, plan_.pixel_kind, luma_tiles, chroma_tiles }, st);
+	const int rc = launch_first_level(forward_route(), { plan_.width, plan_.height, 2 * n_, j.yuv, j.fl1, nullptr, 3, plan_.pixel_kind, luma_tiles, chroma_tiles }, st);
 	if (rc) return rc;
+	if (timed_) HIPCHK(hipEventRecord((hipEvent_t)ev_[1], st));
 	const GopWavelet &t = plan_.ch[0].w[2];
-	dev::k_gop_temporal_fwd<<<dim3((unsigned)((t.pitch * t.height / 2 + dev::NTHREADS - 1) / dev::NTHREADS), 3), dev::NTHREADS, 0, st>>>(j.temp);
-	launch_fwd_plane_tiles(j.mid, t.width, t.height, 6, st);
+	dev::k_gop_temporal_fwd<<<dim3((unsigned)((t.pitch * t.height / 2 + dev::NTHREADS - 1) / dev::NTHREADS), 3 * n_), dev::NTHREADS, 0, st>>>(j.temp);
+	launch_fwd_plane_tiles(j.mid, t.width, t.height, 6 * n_, st);
 	if (!decode_ && gop_temporal_lowpass_is_coded(plan_)) {
 		const GopWavelet &w3 = plan_.ch[0].w[3];                         // (luma is the largest of the three bands)
-		dev::k_gop_quant_lowpass<<<dim3((unsigned)((w3.pitch * w3.height / 2 + dev::NTHREADS - 1) / dev::NTHREADS), 3), dev::NTHREADS, 0, st>>>(j.tq);
+		dev::k_gop_quant_lowpass<<<dim3((unsigned)((w3.pitch * w3.height / 2 + dev::NTHREADS - 1) / dev::NTHREADS), 3 * n_), dev::NTHREADS, 0, st>>>(j.tq);
 	}
+	if (timed_) HIPCHK(hipEventRecord((hipEvent_t)ev_[2], st));
 	const GopWavelet &m = plan_.ch[0].w[4];
-	launch_fwd_plane_tiles(j.top, m.width, m.height, 3, st);
+	launch_fwd_plane_tiles(j.top, m.width, m.height, 3 * n_, st);
 	HIPCHK(hipGetLastError());
+	if (timed_) { HIPCHK(hipEventRecord((hipEvent_t)ev_[3], st)); launched_ = true; }
 	return 0;
 }
 
@@ -1623,38 +1708,52 @@ int GopBatch::launch_inverse(uint32_t dither_seed, bool coeffs_on_device)
 	hipStream_t st = (hipStream_t)stream_;
 	if (jobs_dirty_) { HIPCHK(hipMemcpyAsync(d_jobs_, h_jobs_, jobs_bytes_, hipMemcpyHostToDevice, st)); jobs_dirty_ = false; }
 	if (!coeffs_on_device) HIPCHK(hipMemcpyAsync(d_coeff_, h_coeff_, plan_.coeff_elems * 2, hipMemcpyHostToDevice, st));
-	GopJobs j = gop_jobs_at(d_jobs_);
+	if (!coeffs_on_device && n_ != 1) return -1;          // (the host's pyramid is the single group's)
+	GopJobs j = gop_jobs_at(d_jobs_, n_);
 	(void)hipGetLastError();
+	if (timed_) HIPCHK(hipEventRecord((hipEvent_t)ev_[0], st));
 	const GopWavelet &top = plan_.ch[0].w[5], &mid = plan_.ch[0].w[4], &t = plan_.ch[0].w[2], &l1 = plan_.ch[0].w[0];
-	dev::k_inv_plane<<<dim3((top.width + dev::ITW - 1) / dev::ITW, (top.height + dev::ITH - 1) / dev::ITH, 3), dev::NTHREADS, 0, st>>>(j.itop);
-	dev::k_inv_plane<<<dim3((mid.width + dev::ITW - 1) / dev::ITW, (mid.height + dev::ITH - 1) / dev::ITH, 6), dev::NTHREADS, 0, st>>>(j.imid);
-	dev::k_gop_temporal_inv<<<dim3((unsigned)((t.pitch * t.height / 2 + dev::NTHREADS - 1) / dev::NTHREADS), 3), dev::NTHREADS, 0, st>>>(j.temp);
-	// the last level of both frames (grid z = 2): the intra path's kernels through the intra path's launcher
+	dev::k_inv_plane<<<dim3((top.width + dev::ITW - 1) / dev::ITW, (top.height + dev::ITH - 1) / dev::ITH, 3 * n_), dev::NTHREADS, 0, st>>>(j.itop);
+	if (timed_) HIPCHK(hipEventRecord((hipEvent_t)ev_[1], st));
+	dev::k_inv_plane<<<dim3((mid.width + dev::ITW - 1) / dev::ITW, (mid.height + dev::ITH - 1) / dev::ITH, 6 * n_), dev::NTHREADS, 0, st>>>(j.imid);
+	dev::k_gop_temporal_inv<<<dim3((unsigned)((t.pitch * t.height / 2 + dev::NTHREADS - 1) / dev::NTHREADS), 3 * n_), dev::NTHREADS, 0, st>>>(j.temp);
+	if (timed_) HIPCHK(hipEventRecord((hipEvent_t)ev_[2], st));
+	// the last level of all frames (grid z = 2 n): the intra path's kernels through the intra path's launcher
 	const GopRoute r = route();
-	const int rc = launch_last_level(r.l1, { l1.width, l1.height, rows_, 2, plan_.interlaced, j.iyuv, j.l1, j.half, nullptr, 3, dec_words_per_position(PIX_YU64, 3) }, dither_seed, st);
+	const int rc = launch_last_level(r.l1, { l1.width, l1.height, rows_, 2 * n_, plan_.interlaced, j.iyuv, j.l1, j.half, nullptr, 3, dec_words_per_position(PIX_YU64, 3) }, dither_seed, st);
 	if (rc) return rc;
-	// the conversion runs over both frames in one launch -- two when frame 0 takes another matrix than frame 1 (fill_jobs; v210 takes none); frame 1 alone then runs
-	// as z = 0 with the seed that gives it the dither of z = 1
-	auto convert = [&](int f, int nf, int m) {
-		launch_convert(r.out, d_tmp_, tmp_pitch_, tmp_frame_bytes_, d_frames_, pitch_, frame_bytes_, half_ ? plan_.width / 2 : plan_.width, rows_, f, nf, m,
+	// the conversion runs over all frames in one launch -- two when the frames 0 take another matrix than the frames 1 (fill_jobs; v210 takes none): the first frames
+	// of all groups, then the second ones, each launch striding over two frames; a frame 1 then runs as z = g with the seed that gives the single group's the dither of z = 1
+	auto convert = [&](int f, int nf, size_t step, int m) {
+		launch_convert(r.out, d_tmp_ + tmp_frame_bytes_ * f, tmp_pitch_, tmp_frame_bytes_ * step, d_frames_ + frame_bytes_ * f, pitch_, frame_bytes_ * step, half_ ? plan_.width / 2 : plan_.width, rows_, 0, nf, m,
 		               dither_seed + 0x9E3779B9u * (uint32_t)f, nullptr, st);
 	};
-	if (matrix_ == 0 || r.out.convert == OutConvert::V210) convert(0, 2, 0); else { convert(0, 1, matrix_); convert(1, 1, 0); }
+	if (matrix_ == 0 || r.out.convert == OutConvert::V210) convert(0, 2 * n_, 1, 0); else { convert(0, n_, 2, matrix_); convert(1, n_, 2, 0); }
 	HIPCHK(hipGetLastError());
+	if (timed_) { HIPCHK(hipEventRecord((hipEvent_t)ev_[3], st)); launched_ = true; }
 	return 0;
 }
 
 int GopBatch::download_frame(int f, void *, int)
 {
 	(void)hipSetDevice(device_);
-	if (!decode_ || f < 0 || f > 1) return -1;
+	if (!decode_ || f < 0 || f >= 2 * n_) return -1;
 	HIPCHK(hipMemcpyAsync(h_frames_ + frame_bytes_ * f, d_frames_ + frame_bytes_ * f, frame_bytes_, hipMemcpyDeviceToHost, (hipStream_t)stream_));
+	return 0;
+}
+
+// All 2 n pictures on their way to the host behind the inverse transform: one copy into the batch's pinned frames; finish_frame() hands each to the caller behind wait().
+int GopBatch::download_frames(void *out, size_t, int pitch)
+{
+	(void)hipSetDevice(device_);
+	if (!decode_ || !out || pitch <= 0) return -1;
+	HIPCHK(hipMemcpyAsync(h_frames_, d_frames_, 2 * (size_t)n_ * frame_bytes_, hipMemcpyDeviceToHost, (hipStream_t)stream_));
 	return 0;
 }
 
 int GopBatch::finish_frame(int f, void *out, int pitch)
 {
-	if (!decode_ || f < 0 || f > 1) return -1;
+	if (!decode_ || f < 0 || f >= 2 * n_) return -1;
 	const uint8_t *src = h_frames_ + frame_bytes_ * f;
 	if (pitch == pitch_) memcpy(out, src, frame_bytes_);
 	else for (int r = 0; r < rows_; r++) memcpy((uint8_t *)out + (ptrdiff_t)r * pitch, src + (size_t)r * pitch_, (size_t)pitch_);

@@ -194,4 +194,35 @@ private:
 	int *d_errors_ = nullptr, *h_errors_ = nullptr;
 };
 
+// A batch of group samples that lie in HBM where GpuEntropyEncoder::prepare_group left them (dense buffer, offsets, sizes): k_dec_parse_group walks the tag streams
+// on the device -- one wave per sample -- and fills the job tables [slot][group], slots ordered by band area, largest first, the code-set-17 slots in front and the
+// code-set-18 slots (interlaced groups: the difference-coded bands) behind them; then one k_dec_bands_par launch per code set over slots x n jobs (its latency shape
+// up to kLowLatencyFrames groups), k_dec_undiff and k_dec_lowpass over all groups.  Nothing touches the host between the coder and the inverse transform.
+// (The chunk-indexed decoder of the intra batches, k_dec_index / k_dec_tiles, does not know group pyramids yet: DESIGN.md names it as the follow-up.)
+class GpuGroupBatchEntropyDecoder {
+public:
+	GpuGroupBatchEntropyDecoder() {}
+	~GpuGroupBatchEntropyDecoder() { release(); }
+	// d_coeffs: the pyramid of group 0, the groups coeff_stride_elems apart.  < 0: a plan the kernels do not take (band offsets and pitches must be multiples of 8
+	// coefficients -- k_dec_bands_par clears bands with 16-byte stores --, rows of the difference-coded bands up to 4096 coefficients, raw bands of even width)
+	int prepare(const GopPlan &plan, int ngroups, int16_t *d_coeffs, size_t coeff_stride_elems, int out_pixel_kind, void *stream, int device = -1);
+	// sample g at d_samples + d_offsets[g] (256-byte aligned base, offsets multiples of 4), d_sizes[g] bytes; the buffer extends to the end of the 256-byte window,
+	// counted from the last sample's start, that holds its last tag (GpuEntropyEncoder's dense buffer does)
+	int set_samples_device(const uint8_t *d_samples, const uint32_t *d_sizes, const uint32_t *d_offsets);
+	void set_producer_events(void *headers, void *payloads) { ev_headers_ = headers; ev_payloads_ = payloads; }      // the parser waits for the first, the band decoder for the second
+	int launch();                        // async
+	int check();                         // after the stream was synchronised: 0 when every sample parsed and every band decoded cleanly
+	float kernel_ms(int k);              // last launch(): 0 k_dec_parse_group, 1 the band decoder (both code sets + k_dec_undiff), 2 k_dec_lowpass
+	const char *band_kernel() const;     // the band decoder's shape for this batch, as a profiler shows it
+	void release();
+private:
+	GopPlan plan_; int n_ = 0, out_kind_ = 0, device_ = 0, slots17_ = 0, slots18_ = 0; size_t coeff_stride_ = 0; void *stream_ = nullptr;
+	int16_t *d_coeffs_ = nullptr;
+	const uint8_t *ext_samples_ = nullptr; const uint32_t *ext_sizes_ = nullptr, *ext_offsets_ = nullptr;
+	void *d_tables_ = nullptr, *d_tables18_ = nullptr, *d_plan_ = nullptr, *d_bandjobs_ = nullptr, *d_lowjobs_ = nullptr, *d_diffjobs_ = nullptr;
+	int *d_errors_ = nullptr, *h_errors_ = nullptr;
+	void *ev_headers_ = nullptr, *ev_payloads_ = nullptr;
+	void *ev_[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; bool timed_ = false;      // [0] parser begins, [1] parser ends, [2] band decoder begins, [3] ends, [4] lowpass ends
+};
+
 } // namespace cfhd

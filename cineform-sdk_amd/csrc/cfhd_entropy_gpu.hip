@@ -740,4 +740,133 @@ int GpuGroupEntropyDecoder::launch(const uint8_t *sample, size_t size, const Par
 
 int GpuGroupEntropyDecoder::check() { return h_errors_ ? *h_errors_ : -1; }
 
+// =============================================================================================
+// GpuGroupBatchEntropyDecoder
+// =============================================================================================
+void GpuGroupBatchEntropyDecoder::release()
+{
+	(void)hipSetDevice(device_);
+	void *dev[] = { d_tables_, d_tables18_, d_plan_, d_bandjobs_, d_lowjobs_, d_diffjobs_, d_errors_ };
+	for (void *p : dev) if (p) (void)hipFree(p);
+	if (h_errors_) (void)hipHostFree(h_errors_);
+	for (void *&e : ev_) if (e) { (void)hipEventDestroy((hipEvent_t)e); e = nullptr; }
+	d_tables_ = d_tables18_ = d_plan_ = d_bandjobs_ = d_lowjobs_ = d_diffjobs_ = nullptr; d_errors_ = h_errors_ = nullptr;
+	ext_samples_ = nullptr; timed_ = false; n_ = 0;
+}
+
+int GpuGroupBatchEntropyDecoder::prepare(const GopPlan &plan, int ngroups, int16_t *d_coeffs, size_t stride, int out_kind, void *stream, int device)
+{
+	int rc = device_init();
+	if (rc) return rc;
+	release();
+	device_ = device >= 0 ? device : device_current(); (void)hipSetDevice(device_);
+	plan_ = plan; n_ = ngroups; d_coeffs_ = d_coeffs; coeff_stride_ = stride; out_kind_ = out_kind; stream_ = stream;
+	if (n_ < 1 || plan.num_channels != 3) return -1;
+	// the device's view of the group pyramid; the coded bands in launch order: by area, largest first (dec_build_plan's rule), code set 17 in front of code set 18
+	dev::DecGroupPlan dp;
+	memset(&dp, 0, sizeof(dp));
+	dp.width = plan.width; dp.height = plan.height; dp.display_height = plan.display_height; dp.interlaced = plan.interlaced ? 1 : 0;
+	struct Coded { int c, k, b, table; long long area; };
+	std::vector<Coded> coded;
+	for (int c = 0; c < 3; c++) {
+		dp.low_bias[c] = group_lowpass_bias(plan.ch[c].w[5].width, out_kind, c);
+		for (int k = 0; k < kGopWavelets; k++) {
+			const GopWavelet &wv = plan.ch[c].w[k];
+			for (int b = 0; b < 4; b++) {
+				if (wv.offset[b] >= ((size_t)1 << 32)) return -5;
+				dp.band[c][k][b] = dev::DecGroupBand{ wv.width, wv.height, wv.pitch, -1, (uint32_t)wv.offset[b] };
+				if (k == 2 || b == 0 || b >= wv.nbands) continue;
+				// k_dec_bands_par clears its band with 16-byte stores
+				if ((wv.offset[b] & 7) || (wv.pitch & 7) || (stride & 7)) return -3;
+				const bool diff = gop_band_is_difference_coded(plan, k, b);
+				if (diff && wv.width > dev::DXU_MAX * dev::DXU_THREADS) return -3;      // (k_dec_undiff: rows of up to DXU_MAX x DXU_THREADS coefficients)
+				coded.push_back(Coded{ c, k, b, diff ? 1 : 0, (long long)wv.pitch * wv.height });
+			}
+		}
+		if (plan.ch[c].w[3].width & 1) return -3;          // (k_dec_lowpass reads a raw band of odd width as unsigned words: the lowpass rule, not w[3]'s)
+	}
+	std::stable_sort(coded.begin(), coded.end(), [](const Coded &a, const Coded &b) { return a.table != b.table ? a.table < b.table : a.area > b.area; });
+	for (size_t s = 0; s < coded.size(); s++) { dp.band[coded[s].c][coded[s].k][coded[s].b].slot = (int)s; if (coded[s].table) dp.slots18++; else dp.slots17++; }
+	slots17_ = dp.slots17; slots18_ = dp.slots18;
+	if (slots17_ + slots18_ != kGroupBandJobs || slots18_ != (plan.interlaced ? kGroupDiffJobs : 0)) return -3;
+	// one job per workgroup in gridDim.x (k_dec_bands_par, k_dec_undiff), the raw bands in gridDim.y (k_dec_lowpass: 65 535)
+	if ((long long)kGroupRawJobs * n_ > 65535) return -5;
+	HIPCHK(hipMalloc(&d_plan_, sizeof(dp)));
+	HIPCHK(hipMemcpy(d_plan_, &dp, sizeof(dp), hipMemcpyHostToDevice));
+	std::vector<uint32_t> t = build_dec_tables(1);
+	HIPCHK(hipMalloc(&d_tables_, t.size() * 4));
+	HIPCHK(hipMemcpy(d_tables_, t.data(), t.size() * 4, hipMemcpyHostToDevice));
+	if (slots18_) {
+		t = build_dec_tables(2);
+		HIPCHK(hipMalloc(&d_tables18_, t.size() * 4));
+		HIPCHK(hipMemcpy(d_tables18_, t.data(), t.size() * 4, hipMemcpyHostToDevice));
+	}
+	HIPCHK(hipMalloc(&d_bandjobs_, (size_t)kGroupBandJobs * n_ * sizeof(dev::DecBandJob)));
+	HIPCHK(hipMalloc(&d_lowjobs_, (size_t)kGroupRawJobs * n_ * sizeof(dev::DecLowpassJob)));
+	HIPCHK(hipMalloc(&d_diffjobs_, (size_t)kGroupDiffJobs * n_ * sizeof(dev::DecDiffJob)));
+	HIPCHK(hipMalloc((void **)&d_errors_, sizeof(int)));
+	HIPCHK(hipHostMalloc((void **)&h_errors_, sizeof(int), hipHostMallocPortable));
+	*h_errors_ = 0;
+	for (void *&e : ev_) HIPCHK(hipEventCreate((hipEvent_t *)&e));
+	static_assert((int)dev::DEC_GROUP_RAW_JOBS == (int)kGroupRawJobs && (int)dev::DEC_GROUP_DIFF_JOBS == (int)kGroupDiffJobs, "one count of a group's raw and difference jobs");
+	return 0;
+}
+
+int GpuGroupBatchEntropyDecoder::set_samples_device(const uint8_t *d_samples, const uint32_t *d_sizes, const uint32_t *d_offsets)
+{
+	// (k_dec_parse_group reads 256-byte windows counted from each sample's start, longword by longword: cfhd_entropy_gpu.hip GpuEntropyDecoder::set_samples_device)
+	if (!d_samples || !d_sizes || !d_offsets || ((uintptr_t)d_samples & 255)) return -1;
+	ext_samples_ = d_samples; ext_sizes_ = d_sizes; ext_offsets_ = d_offsets;
+	return 0;
+}
+
+const char *GpuGroupBatchEntropyDecoder::band_kernel() const { return par_backend(n_) == DecBackend::ParLowLatency ? "k_dec_bands_par_ll" : "k_dec_bands_par"; }
+
+int GpuGroupBatchEntropyDecoder::launch()
+{
+	(void)hipSetDevice(device_);
+	hipStream_t st = (hipStream_t)stream_;
+	if (!ext_samples_ || !d_plan_) return -1;
+	HIPCHK(hipMemsetAsync(d_errors_, 0, sizeof(int), st));
+	(void)hipGetLastError();
+	// the parser reads the headers and size fields only (k_ent_layout): it runs beside k_ent_emit, the band decoder waits for the payloads
+	if (ev_headers_) HIPCHK(hipStreamWaitEvent(st, (hipEvent_t)ev_headers_, 0));
+	HIPCHK(hipEventRecord((hipEvent_t)ev_[0], st));
+	dev::k_dec_parse_group<<<n_, dev::DEC_PARSE_THREADS, 0, st>>>(ext_samples_, ext_offsets_, ext_sizes_, n_, (const dev::DecGroupPlan *)d_plan_, d_coeffs_, coeff_stride_,
+	                                                              (dev::DecBandJob *)d_bandjobs_, (dev::DecLowpassJob *)d_lowjobs_, (dev::DecDiffJob *)d_diffjobs_, d_errors_);
+	HIPCHK(hipEventRecord((hipEvent_t)ev_[1], st));
+	if (ev_payloads_) HIPCHK(hipStreamWaitEvent(st, (hipEvent_t)ev_payloads_, 0));
+	ev_headers_ = ev_payloads_ = nullptr;
+	HIPCHK(hipEventRecord((hipEvent_t)ev_[2], st));
+	// a workgroup per band, the rows of one code set in one launch: few groups in the latency shape (the launch lasts as long as the longest band's serial steps)
+	const bool ll = par_backend(n_) == DecBackend::ParLowLatency;
+	auto bands = [&](const dev::DecBandJob *jobs, int count, const void *tables) {
+		if (ll) dev::k_dec_bands_par_ll<<<count, dev::DECP_LL_THREADS, 0, st>>>(jobs, (const dev::DecTables *)tables, d_errors_);
+		else dev::k_dec_bands_par<<<count, dev::DECP_THREADS, 0, st>>>(jobs, (const dev::DecTables *)tables, d_errors_);
+	};
+	bands((const dev::DecBandJob *)d_bandjobs_, slots17_ * n_, d_tables_);
+	if (slots18_) {
+		bands((const dev::DecBandJob *)d_bandjobs_ + (size_t)slots17_ * n_, slots18_ * n_, d_tables18_);
+		dev::k_dec_undiff<<<dim3((unsigned)(kGroupDiffJobs * n_), dev::DXU_SPLIT), dev::DXU_THREADS, 0, st>>>((const dev::DecDiffJob *)d_diffjobs_, d_errors_, 0);
+	}
+	HIPCHK(hipEventRecord((hipEvent_t)ev_[3], st));
+	dev::k_dec_lowpass<<<dim3(8, (unsigned)(kGroupRawJobs * n_)), 256, 0, st>>>((const dev::DecLowpassJob *)d_lowjobs_);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord((hipEvent_t)ev_[4], st));
+	timed_ = true;
+	HIPCHK(hipMemcpyAsync(h_errors_, d_errors_, sizeof(int), hipMemcpyDeviceToHost, st));
+	return 0;
+}
+
+int GpuGroupBatchEntropyDecoder::check() { return h_errors_ ? (*h_errors_ ? -1 : 0) : -1; }
+
+float GpuGroupBatchEntropyDecoder::kernel_ms(int k)
+{
+	float ms = 0;
+	if (!timed_ || k < 0 || k > 2) return 0;
+	void *a = k == 0 ? ev_[0] : (k == 1 ? ev_[2] : ev_[3]), *b = k == 0 ? ev_[1] : (k == 1 ? ev_[3] : ev_[4]);
+	if (hipEventElapsedTime(&ms, (hipEvent_t)a, (hipEvent_t)b) != hipSuccess) { (void)hipGetLastError(); return 0; }
+	return ms;
+}
+
 } // namespace cfhd

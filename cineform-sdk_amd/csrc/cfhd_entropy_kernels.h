@@ -1361,6 +1361,149 @@ __global__ void __launch_bounds__(DEC_PARSE_THREADS) k_dec_parse(const uint8_t *
 	}
 }
 
+// ---------------------------------------------------------------------------------------------
+// The same for a batch of two-frame group samples (cfhd_gop.h): one wave per group sample walks its tag stream as parse_group_sample does on the host
+// (cfhd_gop.cpp, after Codec/decoder.c:11180 DecodeSampleGroup: group header, per channel the lowpass band of w[5], then the wavelets 6, 5, 4, the empty temporal
+// wavelet 3 and the frame wavelets 2 and 1 -- 17 subbands) and fills the group's column of the job tables: a DecBandJob for each of the 45 run-length coded bands,
+// [slot][group] with the slots of code set 17 in front (largest band first) and those of code set 18 -- the difference-coded bands of an interlaced group -- behind
+// them; two DecLowpassJobs per channel (w[5]'s lowpass band with the group's bias of the output, w[3]'s as signed raw words without one) and, interlaced groups, two
+// DecDiffJobs per channel.  The checks are those GpuGroupEntropyDecoder::launch makes on a host-parsed sample: dimensions against the plan, payloads on longword
+// boundaries and inside the sample, the code book each band must come in, a divisor of 1 for the raw band.  A sample that fails one leaves its jobs empty (bytes = 0,
+// no rows) and raises DEC_ERR_PARSE.  Every turn of the walk advances by at least 4 bytes and stops at the sample's size; the fetches are 256-byte windows counted
+// from the sample's start, so the buffer must extend to the end of the window that holds the last sample's last tag (GpuGroupBatchEntropyDecoder::set_samples_device).
+// ---------------------------------------------------------------------------------------------
+struct DecGroupBand { int width, height, pitch, slot; uint32_t offset; };      // slot: the band's row of the job table; < 0: not a coded band
+struct DecGroupPlan {
+	int width, height, display_height, interlaced;
+	int slots17, slots18;                   // rows of the band job table: code set 17, then code set 18
+	int low_bias[3];                        // group_lowpass_bias of the output, per channel
+	DecGroupBand band[3][6][4];             // [channel][wavelet][band] of the group pyramid (GopPlan); band 0 of w[5] and w[3]: the raw bands
+};
+enum { DEC_GROUP_RAW_JOBS = 6, DEC_GROUP_DIFF_JOBS = 6 };      // per group: two raw bands, two difference-coded bands per channel
+
+__global__ void __launch_bounds__(DEC_PARSE_THREADS) k_dec_parse_group(const uint8_t *samples, const uint32_t *offsets, const uint32_t *sizes, int ngroups, const DecGroupPlan *P,
+                                                                       int16_t *coeffs, size_t coeff_stride, DecBandJob *bandjobs, DecLowpassJob *lowjobs, DecDiffJob *diffjobs, int *errors)
+{
+	const int g = blockIdx.x;                            // every lane walks the same tags; lane 0 writes the jobs
+	const int lane = wave_lane();
+	const bool writer = lane == 0;
+	const uint8_t *d = samples + offsets[g];
+	int16_t *cbase = coeffs + coeff_stride * (size_t)g;
+	const uint64_t size = sizes[g];
+	const bool interlaced = P->interlaced != 0;
+	// the group's jobs, empty: a band decoder that meets one clears the band and reports it, the raw and difference jobs have no rows
+	if (writer) {
+		for (int c = 0; c < 3; c++)
+			for (int k = 0; k < 6; k++)
+				for (int b = 0; b < 4; b++) {
+					const DecGroupBand pb = P->band[c][k][b];
+					if (pb.slot >= 0) bandjobs[(size_t)pb.slot * ngroups + g] = DecBandJob{ d, 0u, cbase + pb.offset, pb.height * pb.pitch, 1, 0u, pb.slot >= P->slots17 ? 1 : 0 };
+				}
+		for (int k = 0; k < DEC_GROUP_RAW_JOBS; k++) lowjobs[g * DEC_GROUP_RAW_JOBS + k] = DecLowpassJob{ d, cbase, 0, 0, 0, 0 };
+		if (interlaced) for (int k = 0; k < DEC_GROUP_DIFF_JOBS; k++) diffjobs[g * DEC_GROUP_DIFF_JOBS + k] = DecDiffJob{ nullptr, 0, 0, 0, nullptr, 0u, 0 };
+	}
+	DecTagReader rd; rd.d = d; rd.base = ~(uint64_t)0; rd.w = 0; rd.lane = lane;
+	uint64_t pos = 0, pending_at = 0, peak_base = 0;
+	uint32_t pending = 0, peak_offset = 0, seen_raw = 0;
+	uint64_t seen = 0;                                   // one bit per coded band: (channel * 6 + wavelet) * 3 + band - 1
+	int peak_level = 0, channel = 0, wavelet = -1, band = 0, bw = 0, bh = 0, bq = 1, bflags = 0, benc = 3, lw = 0, lh = 0;
+	int width = 0, height = 0, display_height = 0, num_channels = 0, precision = 0, sample_type = -1, progressive = 0;
+	bool bad = size < 4, first = true;
+	while (!bad && pos + 4 <= size) {
+		const uint32_t word = rd.word(pos);
+		int tag = (int)(int16_t)(word >> 16);
+		const int value = (int)(word & 0xffffu);
+		if (tag < 0) tag = -tag;
+		pos += 4;
+		if (first) { first = false; if (tag != 1 || value != 2) bad = true; sample_type = value; continue; }      // TAG_SAMPLE, SAMPLE_TYPE_GROUP
+		if (tag & 0x4000) {
+			const uint32_t bytes = (tag & 0x2000) ? ((((uint32_t)(tag & 0xff) << 16) | (uint32_t)value) * 4u) : (uint32_t)value * 4u;
+			if (pos + bytes > size) { bad = true; break; }
+			pos += bytes;
+			continue;
+		}
+		if (tag & 0x2000) {
+			if ((tag & 0xff00) == 0x2000) { pending = ((((uint32_t)(tag & 0xff)) << 16) | (uint32_t)value) * 4u; pending_at = pos; }
+			continue;
+		}
+		switch (tag) {
+		case 2: pos += 4u * (uint64_t)value; break;                                  // TAG_INDEX
+		case 62: channel = value; if (channel >= 3) bad = true; break;               // TAG_CHANNEL
+		case 12: num_channels = value; break;                                        // TAG_NUM_CHANNELS
+		case 20: width = value; break;                                               // TAG_FRAME_WIDTH
+		case 21: height = value; break;                                              // TAG_FRAME_HEIGHT
+		case 85: display_height = value; break;                                      // TAG_FRAME_DISPLAY_HEIGHT
+		case 70: precision = value; break;                                           // TAG_PRECISION
+		case 68: progressive = value & 1; break;                                     // TAG_SAMPLE_FLAGS (an interlaced group carries none)
+		case 27: lw = value; break;                                                  // TAG_LOWPASS_WIDTH
+		case 28: lh = value; break;                                                  // TAG_LOWPASS_HEIGHT
+		case 4:                                                                      // TAG_MARKER
+			if (value == 0x0f0f) {                                                   // MARK_COEFF_START: the raw words of w[5]'s lowpass band inside the pending chunk
+				const uint64_t end = pending_at + pending;
+				const uint64_t bytes = (uint64_t)lw * (uint64_t)lh * 2u;
+				const DecGroupBand ll = P->band[channel][5][0];
+				if (pending == 0 || pos + bytes > end || end > size || lw != ll.width || lh != ll.height) { bad = true; break; }
+				if (writer) lowjobs[g * DEC_GROUP_RAW_JOBS + 2 * channel] = DecLowpassJob{ d + pos, cbase + ll.offset, ll.width, ll.height, ll.pitch, P->low_bias[channel] };
+				seen_raw |= 1u << (2 * channel);
+				pos = end; pending = 0;
+			}
+			break;
+		case 38: wavelet = value - 1; if (wavelet < 0 || wavelet >= 6) bad = true; break;      // TAG_WAVELET_NUMBER
+		case 48: band = value; if (band < 0 || band > 3) bad = true; bflags = 0; benc = 3; break;      // TAG_BAND_NUMBER
+		case 72: bflags = value; break;                                              // TAG_BAND_CODING_FLAGS
+		case 75: peak_offset = (peak_offset & ~0xffffu) | (uint32_t)value; peak_base = pos; peak_level = 0; break;     // TAG_PEAK_TABLE_OFFSET_L (decoder.c:23978)
+		case 76: peak_offset = (peak_offset & 0xffffu) | ((uint32_t)value << 16); peak_level = 0; break;               // TAG_PEAK_TABLE_OFFSET_H
+		case 74: peak_level = value; break;                                          // TAG_PEAK_LEVEL
+		case 49: bw = value; break;                                                  // TAG_BAND_WIDTH
+		case 50: bh = value; break;                                                  // TAG_BAND_HEIGHT
+		case 52: benc = value; break;                                                // TAG_BAND_ENCODING
+		case 53: bq = value; break;                                                  // TAG_BAND_QUANTIZATION
+		case 55: {                                                                   // TAG_BAND_HEADER: the payload follows, up to the band trailer
+			const uint64_t end = pending_at + pending;
+			if (wavelet < 0 || pending == 0 || end < pos + 4 || end > size) { bad = true; break; }
+			const uint32_t bytes = (uint32_t)(end - 4 - pos);
+			if (wavelet == 2) { pos = end; pending = 0; peak_level = 0; break; }     // the temporal wavelet: a header and one empty band, nothing coded
+			const DecGroupBand pb = P->band[channel][wavelet][band];
+			if (bw != pb.width || bh != pb.height || (pos & 3u)) { bad = true; break; }
+			if (wavelet == 3 && band == 0) {
+				// raw 16-bit words (BAND_ENCODING_16BIT): signed, no bias; a divided band coded in two passes (BAND_ENCODING_LOSSLESS) is the host coder's
+				if (benc != 4 || bq != 1 || (pb.width & 1) || (uint64_t)bytes < (uint64_t)pb.width * (uint64_t)pb.height * 2u) { bad = true; break; }
+				if (writer) lowjobs[g * DEC_GROUP_RAW_JOBS + 2 * channel + 1] = DecLowpassJob{ d + pos, cbase + pb.offset, pb.width, pb.height, pb.pitch, 0 };
+				seen_raw |= 2u << (2 * channel);
+			} else {
+				if (band < 1 || pb.slot < 0 || benc == 4 || benc == 5) { bad = true; break; }
+				const bool diff = interlaced && wavelet < 2 && band == 2;
+				const int codebook = bflags & 0xf;
+				if (codebook != (diff ? 2 : 1) || (((bflags >> 4) & 1) != 0) != diff) { bad = true; break; }
+				if (peak_level && (!diff || peak_base + peak_offset + 2 > size)) { bad = true; break; }
+				if (writer) bandjobs[(size_t)pb.slot * ngroups + g] = DecBandJob{ d + pos, bytes, cbase + pb.offset, pb.height * pb.pitch, bq, 0u, diff ? 1 : 0 };
+				if (writer && diff) diffjobs[g * DEC_GROUP_DIFF_JOBS + 2 * channel + wavelet] = DecDiffJob{ cbase + pb.offset, pb.width, pb.height, pb.pitch, peak_level ? d + peak_base + peak_offset : nullptr,
+				                                                                                       peak_level ? (uint32_t)(size - (peak_base + peak_offset)) : 0u, peak_level };
+				seen |= (uint64_t)1 << ((channel * 6 + wavelet) * 3 + band - 1);
+			}
+			peak_level = 0;
+			pos = end; pending = 0;
+			break; }
+		default: break;
+		}
+	}
+	if (display_height == 0) display_height = height;
+	// the 45 coded bands: the three highpass bands of the wavelets 5, 4, 3, 1 and 0 of every channel
+	uint64_t want = 0;
+	for (int c = 0; c < 3; c++) for (int k = 0; k < 6; k++) if (k != 2) want |= (uint64_t)7 << ((c * 6 + k) * 3);
+	if (bad || sample_type != 2 || width != P->width || height != P->height || display_height != P->display_height || num_channels != 3 || precision != 10
+	    || (progressive != 0) == interlaced || seen != want || seen_raw != 0x3fu) {
+		if (writer) {
+			for (int c = 0; c < 3; c++)
+				for (int k = 0; k < 6; k++)
+					for (int b = 1; b < 4; b++) { const int slot = P->band[c][k][b].slot; if (slot >= 0) bandjobs[(size_t)slot * ngroups + g].bytes = 0u; }
+			for (int k = 0; k < DEC_GROUP_RAW_JOBS; k++) { lowjobs[g * DEC_GROUP_RAW_JOBS + k].width = 0; lowjobs[g * DEC_GROUP_RAW_JOBS + k].height = 0; }
+			if (interlaced) for (int k = 0; k < DEC_GROUP_DIFF_JOBS; k++) diffjobs[g * DEC_GROUP_DIFF_JOBS + k].band = nullptr;
+			atomic_or_u32((uint32_t *)errors, (uint32_t)DEC_ERR_PARSE);
+		}
+	}
+}
+
 // Raw 16-bit big-endian lowpass coefficients + the reference decoder's bias (decoder.c:12240-12290, :12468-12545).
 __global__ void __launch_bounds__(256) k_dec_lowpass(const DecLowpassJob *jobs)
 {

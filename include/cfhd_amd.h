@@ -8,7 +8,8 @@
  *
  * Scope: intra-frame encode of YUY2 / 2vuy (progressive and interlaced), YU64, v210 and the Avid 4:2:2 layouts avu8 / av16 / a106 / a214 / av28 (progressive)
  * -> YUV 4:2:2 10-bit; two-frame groups (CFHD_ENCODING_FLAGS_YUV_2FRAME_GOP) from YUY2 / 2vuy (progressive and interlaced) and from YU64 / v210 / RG24 / BGRA / BGRa /
- * RG48 / b64a / RG64 / avu8 / av16 / a106 / a214 / av28 encoded as YUV 4:2:2 (progressive); RG48 / RG24 / BGRA / BGRa /
+ * RG48 / b64a / RG64 / avu8 / av16 / a106 / a214 / av28 encoded as YUV 4:2:2 (progressive), through CFHD_EncodeSample and, a whole batch of groups per launch,
+ * through the frame queue of cfhd_amd_batch_* (see cfhd_amd_batch_get_sequence_header below); RG48 / RG24 / BGRA / BGRa /
  * r210 / DPX0 / AB10 / AR10 / b64a -> RGB 4:4:4 12-bit, b64a -> RGBA 4:4:4:4 12-bit, BYR4 -> Bayer 12-bit; decode of 4:2:2 samples to
  * YUY2 / 2vuy (full and half resolution, interlaced samples too), RG48 / b64a / BGRA / BGRa (full and half resolution, interlaced samples too)
  * and YU64 (full resolution, progressive samples), RGB 4:4:4 samples to RG48 (and RG24 / BGRA / BGRa
@@ -149,7 +150,7 @@ long long cfhd_amd_batch_roundtrip(cfhd_amd_batch *batch);                      
 /* The same pass as a slot of a frame queue (replaces the reference's EncoderPool job queue, EncoderSDK/EncoderPool.cpp:239-380): submit returns at once -- the whole
  * pass is queued on the batch's HIP streams, the decoder's stream waiting for the encoder's events; no host thread, no host wait inside the pass --, wait returns what
  * cfhd_amd_batch_roundtrip would have; batches in flight at the same time overlap on the GPU.  One pass per batch at a time: between submit and wait every other entry
- * point on that batch (roundtrip, upload, get_sample, download_output, kernel_ms, dx_stats) returns its error value without touching the batch; destroy waits first.
+ * point on that batch (roundtrip, upload, get_sample, get_sequence_header, download_output, kernel_ms, dx_stats) returns its error value without touching the batch; destroy waits first.
  * Encode-only batches in flight on one device take turns (their host copies hide behind the next batch's kernels), round-trip batches run free.  A process that keeps
  * several batches in flight should run with GPU_MAX_HW_QUEUES=16 in its environment (ROCm runtime, read at start-up: by default all HIP streams of a process share 4
  * hardware queues and the streams of several passes wait for each other). */
@@ -162,6 +163,18 @@ int  cfhd_amd_batch_submit_host(cfhd_amd_batch *batch, const void *frames, size_
 long long cfhd_amd_batch_wait(cfhd_amd_batch *batch);
 int  cfhd_amd_batch_get_sample(cfhd_amd_batch *batch, int frame, const void **data, size_t *size);
 int  cfhd_amd_batch_download_output(cfhd_amd_batch *batch, int frame, void *out, int pitch);
+/* Batches of two-frame groups: encoding_flags with CFHD_ENCODING_FLAGS_YUV_2FRAME_GOP (optionally CFHD_ENCODING_FLAGS_YUV_INTERLACED), encoded_format 0, an even
+ * nframes -- frames 2g and 2g + 1 form group g.  mode 1 takes every 4:2:2 input of the group encoder but RG24 / BGRA / BGRa; mode 0 those whose own format a group
+ * decodes to at full resolution (YUY2, 2vuy, YU64, v210, RG48, b64a; interlaced groups: YUY2, 2vuy).  NULL for anything else: an odd nframes, a quality whose group
+ * tables follow the previous key sample (FILMSCAN2 / 3, LOW .. HIGH up to 1080p), CFHD_AMD_ENTROPY=host.  Every entry point keeps its meaning per frame index
+ * (upload, submit_host, download_output: frame i); get_sample(2g) is group sample g, get_sample(2g + 1) the 24-byte P-frame sample behind it.  In pass k (counted from
+ * 0) both carry frame number k * nframes + 2g + 1: the samples of consecutive passes are the stream one CFHD_EncodeSample handle writes when it is fed the same frames,
+ * with the sequence header -- this call -- taken out.  A pass returns the sum of the sizes of its group samples; -9: a group sample reached the size at which the
+ * reference codes bands as zeros (80 % of width x height x bytes per pixel + 64 KB), which the device stage does not do -- the other samples of the pass are complete.
+ * cfhd_amd_batch_kernel_ms / _kernel_name of such a batch: 0 level 1 of all frames, 1 temporal step + middle wavelets, 2 top wavelet, 3 last level (+ conversion),
+ * 4 middle wavelets + temporal step, 5 top wavelet, 12 k_dec_parse_group, 13 band decoder, 14 k_dec_lowpass (cfhd_batch.cpp).
+ * Returns 0 and the 40-byte header, or -1 for a batch without groups (or one between submit and wait). */
+int  cfhd_amd_batch_get_sequence_header(cfhd_amd_batch *batch, const void **data, size_t *size);
 float cfhd_amd_batch_kernel_ms(cfhd_amd_batch *batch, int which);                              /* HIP-event time of the kernels of the last pass */
 const char *cfhd_amd_batch_kernel_name(cfhd_amd_batch *batch, int which);                      /* which 0..5: the transform kernel behind that time */
 double cfhd_amd_batch_stage_seconds(cfhd_amd_batch *batch, int which);
