@@ -79,6 +79,8 @@ static bool yuv422_output_served(int kind, int width, bool half)
 	}
 }
 
+static const char *const kUncompressedRefusal = "uncompressed sample (UNCOMPRESS chunk): the uncompressed mode is not built";
+
 CFHD_Error CFHD_PrepareToDecode(CFHD_DecoderRef ref, int, int, CFHD_PixelFormat fmt, CFHD_DecodedResolution resolution, CFHD_DecodingFlags,
                                 void *sample, size_t size, int *aw, int *ah, CFHD_PixelFormat *af)
 {
@@ -113,6 +115,9 @@ CFHD_Error CFHD_PrepareToDecode(CFHD_DecoderRef ref, int, int, CFHD_PixelFormat 
 		d->gop = false;
 	}
 	if (parse_sample((const uint8_t *)sample, size, &d->header) < 0) return ERR_BADSAMPLE;
+	// a sample of the reference's uncompressed mode (v210, 10-bit RGB and Bayer inputs with the uncompressed bits in the quality word): not built.  Refused here when the
+	// bytes the caller passed reach the chunk tag, at CFHD_DecodeSample otherwise
+	if (d->header.uncompressed) { device_set_last_error(kUncompressedRefusal); d->prepared = false; return ERR_BADFORMAT; }
 	// CFHD_DECODED_RESOLUTION_FULL (1; 0 = unknown is taken as full) and _HALF (2): the level-1 lowpass planes shown as the picture
 	// (decoder.c:14124, :26752).  Quarter / thumbnail resolutions are not built.
 	if (resolution != 1 && resolution != 0 && resolution != 2) return ERR_BAD_RESOLUTION;
@@ -319,7 +324,9 @@ CFHD_Error CFHD_DecodeSample(CFHD_DecoderRef ref, void *sample, size_t size, voi
 		for (int r = 0; r < rows; r++) memset((uint8_t *)out + (ptrdiff_t)r * pitch, 0, (size_t)rowbytes);
 		return err;
 	};
-	if (parse_sample(s, size, &ps) != 0) return fail_zero(ERR_BADSAMPLE);
+	const int parsed = parse_sample(s, size, &ps);
+	if (ps.uncompressed) { device_set_last_error(kUncompressedRefusal); return fail_zero(ERR_BADFORMAT); }
+	if (parsed != 0) return fail_zero(ERR_BADSAMPLE);
 	if (ps.width != d->header.width || ps.display_height != d->header.display_height || ps.encoded_format != d->header.encoded_format ||
 	    ps.num_channels != d->plan.num_channels) return fail_zero(ERR_BADSAMPLE);
 	// interlaced samples (known only now: the SAMPLE_FLAGS tag lies behind the 512 bytes CFHD_PrepareToDecode sees): 4:2:2, full resolution through the

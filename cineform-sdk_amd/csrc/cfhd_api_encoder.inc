@@ -33,6 +33,7 @@ CFHD_Error CFHD_PrepareToEncode(CFHD_EncoderRef ref, int w, int h, CFHD_PixelFor
 	if (e->params.valid && e->params.width == w && e->params.height == h && e->params.pixel_format == fmt && e->params.flags == (uint32_t)flags &&
 	    want_encoded == (int)encoded) {
 		// "just changing quality" (SampleEncoder.cpp:322-327); a different encoded format or other flags take the full path below
+		if (quality_word_refused(e->params.pixel_kind, (int)quality)) return ERR_BADFORMAT;      // (as make_params refuses it; the handle keeps what it was prepared with)
 		e->params.quality = (int)((0xffff0000u & (uint32_t)e->params.quality) | (0xffffu & (uint32_t)quality));
 		derive_quantization(&e->params.plan, e->params.quality, e->params.progressive, 0.0f, &e->params.qstate);
 		e->batch_ready = false;
@@ -97,7 +98,7 @@ CFHD_Error CFHD_EncodeSample(CFHD_EncoderRef ref, void *frame, int pitch)
 		} else {
 			MetaBlock global = e->meta.global, local = e->meta.local;
 			meta_remove_hidden(global); meta_remove_hidden(local);
-			SampleHeaderInfo hdr = { n, color_format_of(e->params.pixel_kind), e->params.color_space, e->params.quality, !e->params.gplan.interlaced, global.data(), global.size(), local.data(), local.size() };
+			SampleHeaderInfo hdr = { n, color_format_of(e->params.pixel_kind), e->params.color_space, header_quality(e->params.quality), !e->params.gplan.interlaced, global.data(), global.size(), local.data(), local.size() };
 			if (e->gop_batch.launch_forward()) return ERR_INTERNAL;
 			bytes = 0;
 			// GPU entropy stage: the finished group sample comes back, not the pyramid.  The host writer takes over (from the same GPU coefficients) when the header

@@ -146,12 +146,17 @@ int encode_gather_slots() { return gather_slots("CFHD_AMD_ENCODE_BATCH", 8); }  
 // derivation itself whether a large previous sample would change them
 bool quantizer_is_static(const EncodeParams &p)
 {
-	FramePlan probe = p.plan; QuantState st = p.qstate;
-	st.lastgopbitcount = (int64_t)p.width * p.height * 64;               // an absurdly large previous sample
-	derive_quantization(&probe, p.quality, p.progressive, 0.0f, &st);
-	for (int c = 0; c < probe.num_channels; c++)
-		for (int lv = 0; lv < kNumLevels; lv++)
-			for (int b = 0; b < kNumBands; b++) if (probe.ch[c].band[lv][b].quant != p.plan.ch[c].band[lv][b].quant) return false;
+	// an absurdly large previous sample, 8 bytes per pixel -- and, from about a megapixel on, where that many bits times the frame rate no longer fit the int the
+	// bit-rate limiter computes its rate in (bitrate_of_previous_sample), also one of 2 MB: 500 Mbit/s at 30 fps, beyond every limit and inside the int
+	const int64_t large = (int64_t)p.width * p.height * 64;
+	for (int64_t bits : { large, std::min<int64_t>(large, 16000000) }) {
+		FramePlan probe = p.plan; QuantState st = p.qstate;
+		st.lastgopbitcount = bits;
+		derive_quantization(&probe, p.quality, p.progressive, 0.0f, &st);
+		for (int c = 0; c < probe.num_channels; c++)
+			for (int lv = 0; lv < kNumLevels; lv++)
+				for (int b = 0; b < kNumBands; b++) if (probe.ch[c].band[lv][b].quant != p.plan.ch[c].band[lv][b].quant) return false;
+	}
 	return true;
 }
 
@@ -183,7 +188,7 @@ int encode_one_gathered(EncodeBatch &own, EncodeParams &p, const void *frame, in
 			}
 			MetaBlock g2 = global, l2 = local;
 			meta_remove_hidden(g2); meta_remove_hidden(l2);
-			SampleHeaderInfo hdr = { frame_number, p.pixel_format == FMT_RG30 ? 122 : color_format_of(p.pixel_kind), p.color_space, p.quality, p.progressive, g2.data(), g2.size(), l2.data(), l2.size() };
+			SampleHeaderInfo hdr = { frame_number, p.pixel_format == FMT_RG30 ? 122 : color_format_of(p.pixel_kind), p.color_space, header_quality(p.quality), p.progressive, g2.data(), g2.size(), l2.data(), l2.size() };
 			uint32_t sz; unsigned char ty;
 			const uint32_t VCHN = CFHD_FOURCC('V', 'C', 'H', 'N');
 			const bool vchn = meta_find(g2.data(), g2.size(), VCHN, &sz, &ty) || meta_find(l2.data(), l2.size(), VCHN, &sz, &ty);       // rare syntax switch: encode_one knows it

@@ -86,12 +86,23 @@ struct EncodeParams {
 	bool valid = false;
 };
 
+// The inputs the reference can store raw (encoder.c:1972-1975): v210, the 10-bit RGB words and the Bayer mosaics.  With the uncompressed bits (0x1f00) in the quality
+// word it writes uncompressed samples for the frames its lottery picks (encoder.c:1977-2019), which this library does not write.
+bool input_is_raw_storable(int kind) { return kind == PIX_V210 || (kind >= PIX_R210 && kind <= PIX_AR10) || kind == PIX_BYR4 || kind == PIX_BYR5; }
+// The quality words no encoder is prepared with: a low byte of 0 (CFHD_ENCODING_QUALITY_FIXED: the reference derives its tables from a bit rate, QuantizationSetRate, which is
+// not built) and the uncompressed bits on an input the reference can store raw (the uncompressed mode is not built).
+bool quality_word_refused(int kind, int quality) { return (quality & 0xff) == 0 || ((quality & 0x1f00) && input_is_raw_storable(kind)); }
+// The quality word of the sample header.  The uncompressed bits on an input that cannot be stored raw: the reference derives its tables from the caller's word (factor 5,
+// no rate feedback) and then writes (word & ~0x1fff) | 6 into the header (encoder.c:2022-2029).
+int header_quality(int quality) { return (quality & 0x1f00) ? ((quality & ~0x1fff) | 6) : quality; }
+
 int make_params(EncodeParams &p, int w, int h, uint32_t fmt, int encoded, uint32_t flags, int quality)
 {
 	p.valid = false;
 	p.api_encoded = encoded; p.api_quality = quality;
 	int kind = pixel_kind_of(fmt);
 	if (kind == PIX_NONE) return ERR_BADFORMAT;
+	if (quality_word_refused(kind, quality)) return ERR_BADFORMAT;
 	// CFHD_ENCODED_FORMAT_YUV_422 (0) from the packed 4:2:2 formats, CFHD_ENCODED_FORMAT_RGB_444 (1) from RG48; the cross
 	// combinations (4:4:4 input subsampled to 4:2:2, ...) go through ConvertLib in the reference and are not built
 	// CFHD_ENCODED_FORMAT_RGBA_4444 (2) from b64a
@@ -137,6 +148,9 @@ int make_params(EncodeParams &p, int w, int h, uint32_t fmt, int encoded, uint32
 	const int yuv601 = (flags & (1u << 2)) ? 1 : 2, vsrgb = (flags & (1u << 8)) ? 2 : 1;   // SampleEncoder.cpp:210-212
 	p.color_space = ((rgb && !deep_rgb_as_422) || kind == PIX_BYR4 || kind == PIX_BYR5) ? 0 : ((yuv601 == 1 ? 1 : 2) | (vsrgb == 2 ? 4 : 0));           // RGB 4:4:4 samples carry no colour space tag
 	if (!build_frame_plan(&p.plan, w, h, kind, enc)) return ERR_BADFORMAT;
+	// Frames so narrow that a channel's top-level bands are 8 columns or fewer (4:2:2 and Bayer: 128 pixels and below, RGB(A): 64 and below): the reference's horizontal
+	// filter leaves other values in column 0 of its horizontal highpass bands there than the transform everywhere else computes.  Not restated, so not encoded.
+	for (int c = 0; c < p.plan.num_channels; c++) if (p.plan.ch[c].band[kNumLevels - 1][0].width <= 8) return ERR_BADFORMAT;
 	p.plan.color_matrix = (p.color_space & 4 ? 1 : 0) + ((p.color_space & 3) == 1 ? 2 : 0);
 	p.plan.interlaced = interlaced;
 	p.qstate = {0, -1, 0};
@@ -176,7 +190,7 @@ int encode_one(EncodeBatch &batch, EncodeParams &p, const void *frame, int pitch
 {
 	int rc;
 	meta_remove_hidden(global); meta_remove_hidden(local);
-	SampleHeaderInfo hdr = { frame_number, p.pixel_format == FMT_RG30 ? 122 /* COLOR_FORMAT_RG30 */ : color_format_of(p.pixel_kind), p.color_space, p.quality, p.progressive,
+	SampleHeaderInfo hdr = { frame_number, p.pixel_format == FMT_RG30 ? 122 /* COLOR_FORMAT_RG30 */ : color_format_of(p.pixel_kind), p.color_space, header_quality(p.quality), p.progressive,
 	                         global.data(), global.size(), local.data(), local.size() };
 	{
 		// The one metadata override that changes the sample syntax for 2-D clips (Codec/encoder.c:9043-9046 UpdateEncoderOverrides):

@@ -38,10 +38,19 @@ CFHD_Error CFHD_PrepareEncoderPool(CFHD_EncoderPoolRef ref, uint_least16_t w, ui
 		std::unique_lock<std::mutex> lk(p->m);
 		p->cv_done.wait(lk, [&] { for (auto &j : p->fifo) if (!j->finished) return false; return true; });
 		p->params = np; p->service = nullptr;           // (shared passes are keyed by quality: the workers go on alone)
+		// The reference hands the word to its workers as a per-frame override (EncoderSDK/AsyncEncoder.h:102, SampleEncoder.cpp:488-492): a worker's encoder is not
+		// prepared again, so it keeps the limiter it was seeded with by the first prepare and the size of its last sample, and the next frame's derivation moves the
+		// feedback once.  The derivation here runs on a copy of the state with no previous sample, so that it moves nothing: its tables are the ones a worker that
+		// has not encoded a frame yet uses for its first; every other worker's encode_one derives them again from its own last sample before the next frame.
+		// (Pinned against the reference's pool with one worker; with more, each worker carries its own state, here as there.)
 		for (auto &wk : p->workers) {
 			device_select(wk->device);
-			wk->params = np;
-			const int urc = wk->batch.update_quant(np.plan);
+			EncodeParams wp = np;
+			QuantState probe = wk->params.qstate; probe.lastgopbitcount = 0;
+			derive_quantization(&wp.plan, wp.quality, wp.progressive, 0.0f, &probe);
+			wp.qstate = wk->params.qstate;
+			wk->params = wp;
+			const int urc = wk->batch.update_quant(wp.plan);
 			device_select(-1);
 			if (urc) return ERR_INTERNAL;
 		}

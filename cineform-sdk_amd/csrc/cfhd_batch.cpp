@@ -636,6 +636,13 @@ float cfhd_amd_batch_kernel_ms(cfhd_amd_batch *b, int which)
 	return ms;
 }
 
+int cfhd_amd_quantizer_is_static(int width, int height, uint32_t pixel_format, int encoded_format, uint32_t encoding_flags, int quality)
+{
+	FrontEndParams fp;
+	if (front_end_params(width, height, pixel_format, encoded_format, encoding_flags, quality, &fp)) return -1;
+	return fp.gop ? (fp.gop_static_quantizer ? 1 : 0) : (fp.static_quantizer ? 1 : 0);
+}
+
 // which as in cfhd_amd_batch_kernel_ms, 0..5: the name of the transform kernel behind that number (the shape depends on geometry and batch size)
 const char *cfhd_amd_batch_kernel_name(cfhd_amd_batch *b, int which)
 {

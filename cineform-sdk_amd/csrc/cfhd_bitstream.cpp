@@ -364,6 +364,7 @@ int parse_sample(const uint8_t *d, size_t size, ParsedSample *ps)
 		if (tag & 0x2000) {                       // 24-bit size chunks: SUBBAND/LEVEL/SAMPLE size (contents are parsed)
 			uint32_t longs = ((uint32_t)(tag & 0xff) << 16) | (uint32_t)value;
 			if ((tag & 0xff00) == 0x2000) { pending_chunk = longs * 4; pending_at = pos; }
+			if ((tag & 0xff00) == 0x2300) { ps->uncompressed = true; break; }      // CODEC_TAG_UNCOMPRESS: raw pixels follow, not tag-value pairs
 			continue;
 		}
 		switch (tag) {

@@ -154,6 +154,7 @@ struct ParsedSample {
 	ParsedBand high[kMaxChannels][kNumLevels][kNumBands]; // [ch][wavelet index][band 1..3]
 	uint32_t metadata_offset = 0, metadata_bytes = 0;     // first metadata chunk
 	size_t size = 0;                                      // bytes handed to parse_sample
+	bool uncompressed = false;                            // the frame is stored raw behind an UNCOMPRESS chunk tag (0x23xx, encoder.c:7625-7741): the walk ends there
 };
 // Returns 0 on success, 1 when the header parsed but the data ends early (header sniffing), <0 on malformed input.
 int parse_sample(const uint8_t *data, size_t size, ParsedSample *out);

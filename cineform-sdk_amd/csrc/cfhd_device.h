@@ -29,6 +29,7 @@ int device_caller_save();          // the caller's current device, -1 when there
 void device_caller_restore(int dev);
 struct CallerDevice { int dev; CallerDevice() : dev(device_caller_save()) {} ~CallerDevice() { device_caller_restore(dev); } CallerDevice(const CallerDevice &) = delete; };
 const char *device_last_error();
+void device_set_last_error(const char *text);      // a refusal decided on the host that the caller should be able to read (cfhd_amd_last_error)
 
 // N frames that travel through the forward path together: one launch per wavelet level covers every channel of
 // every frame (blockIdx.z walks the job table).  N = 1 is the synchronous CFHD_EncodeSample path.

@@ -198,6 +198,7 @@ void fill_fwd_plane_job(dev::FwdPlaneJob &p, const int16_t *in, int in_pitch, in
 } // namespace
 
 const char *device_last_error() { std::lock_guard<std::mutex> l(g_err_mutex); t_err_copy = g_err_text; return t_err_copy.c_str(); }
+void device_set_last_error(const char *text) { g_err = text; }
 
 namespace {
 std::mutex g_pins_mutex;

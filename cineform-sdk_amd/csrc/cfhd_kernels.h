@@ -303,6 +303,8 @@ __device__ __forceinline__ int quantize(int v, const QuantParam &q)
 {
 	if (q.divisor <= 1) return v;
 	int neg = v < 0;
+	// (the mask restates the reference's 16-bit add; for what the callers pass it never acts: v is a 16-bit half, |v| <= 32768, and mid -- a fraction of the divisor --
+	// is far below 2^15, so the sum stays below 2^16.  The packed twin below gets the same wrap from pk_addw.)
 	unsigned a = ((unsigned)(neg ? -v : v) + (unsigned)q.mid) & 0xffffu;
 	int r = (int)((a * (q.mult & 0xffffu)) >> 16);          // (mult < 2^16: cfhd_device.hip quant_param; said here, the product is the full-rate v_mul_u32_u24)
 	return (int)(int16_t)(neg ? -r : r);

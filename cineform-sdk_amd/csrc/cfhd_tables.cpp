@@ -380,7 +380,8 @@ void derive_quantization(FramePlan *plan, int quality, bool progressive, float f
 	(void)precision;
 	// an intra frame has no temporal wavelet: its level-2 bands take the divisors of the group's frame wavelets (quantize.c:548-565)
 	for (int i = 0; i < 3; i++) { qL[7 + i] = qL[11 + i]; qC[7 + i] = qC[11 + i]; qLmax[7 + i] = qLmax[11 + i]; qCmax[7 + i] = qCmax[11 + i]; }
-	const int fixedQuality = factor;     // 0 => bitrate mode (not supported: treated as quality 3 tables w/o VBR)
+	const int fixedQuality = factor;     // (never 0 for a word the API takes: a low byte of 0, the reference's bit-rate mode QuantizationSetRate, is refused by make_params;
+	                                     // low bytes above 10 -- an unknown quality -- take table 0 as in the reference, quantize.c:323, and with it no limiter)
 
 	plan->prescale[0] = 0; plan->prescale[1] = precision >= 10 ? 2 : 0; plan->prescale[2] = precision == 12 ? 2 : 0;
 

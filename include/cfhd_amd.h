@@ -181,6 +181,9 @@ double cfhd_amd_batch_stage_seconds(cfhd_amd_batch *batch, int which);
 /* The level-1 transform kernel of a prepared encoder handle's next CFHD_EncodeSample, intra frame or two-frame group ("" when the handle is not prepared). */
 const char *cfhd_amd_encoder_kernel_name(CFHD_EncoderRef encoderRef);
 int  cfhd_amd_batch_dx_stats(cfhd_amd_batch *batch, uint32_t *out16);
+/* Whether the quantizer tables of these CFHD_PrepareToEncode arguments stay put from frame to frame (1), or follow the size of the previous sample (0: rate feedback --
+ * FILMSCAN2 / FILMSCAN3, LOW .. HIGH up to 1080p -- which cfhd_amd_batch_create_ex refuses and CFHD_EncodeSample applies per frame); -1: arguments no encoder takes. */
+int  cfhd_amd_quantizer_is_static(int width, int height, uint32_t pixel_format, int encoded_format, uint32_t encoding_flags, int quality);
 int  cfhd_amd_device_count(void);
 /* Text of the last HIP / device failure behind a CFHD_ERROR_INTERNAL (the library has no CPU fallback: without a gfx950 device every
  * compute call fails and says why here). */

@@ -16,7 +16,7 @@ def _shards():
     return m
 
 
-W, H, TOTAL = 96, 64, 7
+W, H, TOTAL = 144, 64, 7
 
 
 def _encode(numbers):
