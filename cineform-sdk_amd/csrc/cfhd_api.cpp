@@ -73,6 +73,15 @@ int front_end_params(int width, int height, uint32_t pixel_format, int encoded_f
 	}
 	return 0;
 }
+int decoder_handle_state(void *ref, DecoderHandleState *out)
+{
+	const Decoder *d = (const Decoder *)ref;
+	if (!d || !out || !d->prepared || d->gop) return -1;
+	out->plan = d->plan; out->out_kind = d->out_kind; out->encoded_format = d->header.encoded_format; out->color_space = d->header.color_space;
+	out->half = d->half; out->interlaced = !d->header.progressive; out->progressive_flag = d->header.progressive != 0;
+	out->sample_cap = (size_t)d->plan.width * d->plan.height * pixel_bytes_of(d->out_kind) + 65536;
+	return 0;
+}
 }
 
 extern "C" {

@@ -1,0 +1,358 @@
+// cfhd_decode_queue.hip -- the decode queue (extension API, cfhd_amd_decode_batch_*): batches of intra samples that came from anywhere -- the reference encoder, a camera,
+// a file -- decoded the way the round-trip batch of cfhd_batch.cpp decodes the samples of its own coder: parsed on the GPU, one launch per stage for the whole batch,
+// no host wait inside a pass.
+//
+// A pass on the batch's one stream:
+//   (samples H2D: one DMA of a registered blob as it lies, or of the pinned buffer the calling thread packed plain memory into)  ->  k_dec_ingest: every sample into the
+//   decoder's own 256-byte aligned slot, the size table  ->  k_dec_parse with a verdict per sample  ->  the band decoder, k_dec_lowpass  ->  the three transform levels
+//   and the output conversion (DecodeBatch)  ->  k_dec_blank: the pictures of the samples that failed, zeroed  ->  (pictures D2H).
+// The gates are the handle's: create prepares a CFHD_DecodeSample handle on the first sample and decodes that sample once; what the handle refuses, create refuses with
+// the same text.  That handle stays with the batch as the slow path: the samples k_dec_ingest could not place (longer than a slot, a size that is no multiple of 4),
+// those whose scan or colour-space tag differs from the first sample's, and -- when the band decoders' one error word is set after the pass -- every sample the parser
+// passed get their verdict and picture from it in wait ("every caller decodes alone and gets its own verdict", as DecodeService decides).  A pass of intact samples
+// launches nothing extra.
+#include "../../include/cfhd_amd.h"
+#include "cfhd_core.h"
+#include "cfhd_bitstream.h"
+#include "cfhd_device.h"
+#include "cfhd_params.h"
+#include "cfhd_ingest_kernels.h"
+#include <hip/hip_runtime.h>
+#include <string.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <vector>
+#include <thread>
+#include <atomic>
+#include <new>
+
+using namespace cfhd;
+
+namespace {
+enum { ERR_OKAY = 0, ERR_BADSAMPLE = 5, ERR_INTERNAL = 6 };
+int g_fail(hipError_t e, const char *what) { fprintf(stderr, "[cfhd_amd] %s: %s\n", what, hipGetErrorString(e)); return (int)e ? (int)e : -1; }
+#define HIPCHK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return g_fail(_e, #expr); } while (0)
+
+template <typename F> void parallel_for(int n, int nthreads, F f)
+{
+	if (nthreads <= 1 || n <= 1) { for (int i = 0; i < n; i++) f(i); return; }
+	std::atomic<int> next(0);
+	std::vector<std::thread> pool;
+	for (int k = 0; k < (nthreads < n ? nthreads : n); k++) pool.emplace_back([&] { for (int i; (i = next.fetch_add(1)) < n;) f(i); });
+	for (auto &th : pool) th.join();
+}
+}
+
+struct cfhd_amd_decode_batch {
+	int n = 0, device = 0;
+	DecoderHandleState st;
+	DecodeBatch dec;
+	CFHD_DecoderRef slow = nullptr;          // the handle create prepared on the first sample: the gates, and the slow path of wait
+	void *scope_stream = nullptr;            // the batch's one stream (StreamScope): released behind the decoder
+	// the samples on their way in: the blob in HBM (+ the pinned buffer plain memory is packed into), the table k_dec_ingest reads, what it and the parser write
+	uint8_t *d_blob = nullptr, *h_blob = nullptr; size_t blob_cap = 0;      // (h_blob: allocated by the first pass that stages plain memory)
+	uint8_t *d_table = nullptr, *h_table = nullptr; size_t table_bytes = 0;
+	uint32_t *d_sizes = nullptr, *d_verdicts = nullptr, *h_verdicts = nullptr;      // verdicts: [0, n) k_dec_parse's words, [n, 2 n) k_dec_ingest's marks
+	hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };                      // around k_dec_ingest, around k_dec_blank
+	float ingest_ms = 0, blank_ms = 0; bool timed = false;
+	// the pass in flight
+	bool in_flight = false; int count = 0; uint32_t steps = 0;
+	const uint8_t *src_host = nullptr, *src_device = nullptr;      // where sample i's bytes are for the slow path: src + offsets[i]
+	std::vector<unsigned long long> offsets; std::vector<uint32_t> sizes;      // sizes: as k_dec_ingest sees them (a sample beyond 4 GB: 0xffffffff, no multiple of 4 -- the slow path's)
+	std::vector<size_t> full_sizes;
+	uint8_t *host_out = nullptr; size_t host_out_stride = 0; int host_out_pitch = 0;
+	std::vector<std::vector<uint8_t>> slow_pictures;               // pictures the slow path decoded while the batch keeps its pictures in HBM (download_output serves them)
+	unsigned long long *table_src() const { return (unsigned long long *)h_table; }
+	uint32_t *table_size() const { return (uint32_t *)(h_table + 8 * (size_t)n); }
+	uint32_t *table_first() const { return (uint32_t *)(h_table + 12 * (size_t)n); }
+	dev::DecIngestTable device_table() const { return dev::DecIngestTable{ (const unsigned long long *)d_table, (const uint32_t *)(d_table + 8 * (size_t)n), (const uint32_t *)(d_table + 12 * (size_t)n) }; }
+	uint32_t clean_word() const { return dev::dec_verdict_word(0, st.progressive_flag, st.color_space); }
+	~cfhd_amd_decode_batch()
+	{
+		(void)hipSetDevice(device);
+		dec.release();
+		if (scope_stream) device_stream_release(scope_stream);
+		for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+		void *dv[] = { d_blob, d_table, d_sizes, d_verdicts }; for (void *p : dv) if (p) (void)hipFree(p);
+		void *hv[] = { h_blob, h_table, h_verdicts }; for (void *p : hv) if (p) (void)hipHostFree(p);
+		if (slow) (void)CFHD_CloseDecoder(slow);
+	}
+};
+
+namespace {
+int allocate(cfhd_amd_decode_batch *b)
+{
+	const size_t cap = b->dec.entropy().slot_bytes();
+	b->blob_cap = cap * (size_t)b->n + 32;               // a pass's samples fit whatever their alignment; a registered span with wider gaps is packed like plain memory
+	b->table_bytes = 12 * (size_t)b->n + 4 * ((size_t)b->n + 1);
+	HIPCHK(hipMalloc((void **)&b->d_blob, b->blob_cap));
+	HIPCHK(hipMalloc((void **)&b->d_table, b->table_bytes));
+	HIPCHK(hipHostMalloc((void **)&b->h_table, b->table_bytes, hipHostMallocPortable));
+	HIPCHK(hipMalloc((void **)&b->d_sizes, 4 * (size_t)b->n));
+	HIPCHK(hipMalloc((void **)&b->d_verdicts, 8 * (size_t)b->n));
+	HIPCHK(hipHostMalloc((void **)&b->h_verdicts, 8 * (size_t)b->n, hipHostMallocPortable));
+	HIPCHK(hipMemset(b->d_sizes, 0, 4 * (size_t)b->n));
+	HIPCHK(hipMemset(b->d_verdicts, 0, 8 * (size_t)b->n));
+	for (hipEvent_t &e : b->ev) HIPCHK(hipEventCreate(&e));
+	return 0;
+}
+
+// Everything of a pass behind the samples' arrival in HBM, queued on the batch's stream: blob + table_src()[i] is sample i.  No host wait.
+int launch_pass(cfhd_amd_decode_batch *b, const uint8_t *blob)
+{
+	(void)hipSetDevice(b->device);
+	hipStream_t st = (hipStream_t)b->dec.stream();
+	const size_t cap = b->dec.entropy().slot_bytes();
+	uint32_t pieces = 0;
+	for (int i = 0; i < b->count; i++) { b->table_size()[i] = b->sizes[i]; b->table_first()[i] = pieces; pieces += dev::dec_ingest_pieces(b->sizes[i], cap); }
+	b->table_first()[b->count] = pieces;
+	HIPCHK(hipMemcpyAsync(b->d_table, b->h_table, b->table_bytes, hipMemcpyHostToDevice, st));
+	b->dec.set_active(b->count);
+	HIPCHK(hipEventRecord(b->ev[0], st));
+	dev::k_dec_ingest<<<pieces ? pieces : 1u, dev::DEC_INGEST_THREADS, 0, st>>>(blob, b->device_table(), b->count, b->dec.entropy().sample_slots(), cap, b->d_sizes, b->d_verdicts + b->n);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(b->ev[1], st));
+	// 8-bit outputs: the dither seed follows the pass number as the round-trip batch's does (cfhd_batch.cpp batch_launch): 0xA511E9B3 * (passes completed + 1)
+	if (b->dec.launch_entropy() || b->dec.launch_inverse(0xA511E9B3u * (b->steps + 1))) return -5;
+	HIPCHK(hipEventRecord(b->ev[2], st));
+	dev::k_dec_blank<<<dim3(dev::DEC_BLANK_SPLIT, (unsigned)b->count), dev::DEC_BLANK_THREADS, 0, st>>>(b->d_verdicts, b->d_verdicts + b->n, b->clean_word(), b->dec.device_pictures(), b->dec.picture_bytes(),
+	                                                                                                      b->dec.picture_pitch(), b->dec.picture_pitch(), b->dec.picture_rows());
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(b->ev[3], st));
+	b->timed = true;
+	HIPCHK(hipMemcpyAsync(b->h_verdicts, b->d_verdicts, 8 * (size_t)b->n, hipMemcpyDeviceToHost, st));
+	if (b->host_out && b->dec.download_frames(b->host_out, b->host_out_stride, b->host_out_pitch)) return -5;
+	return 0;
+}
+
+void begin_pass(cfhd_amd_decode_batch *b, const size_t *offsets, const size_t *sizes, int count)
+{
+	b->count = count;
+	b->offsets.assign(offsets, offsets + count); b->full_sizes.assign(sizes, sizes + count);
+	b->sizes.resize((size_t)count);
+	for (int i = 0; i < count; i++) b->sizes[i] = sizes[i] > 0xfffffffeu ? 0xffffffffu : (uint32_t)sizes[i];
+}
+void end_pass(cfhd_amd_decode_batch *b) { b->in_flight = false; b->src_host = b->src_device = nullptr; b->host_out = nullptr; }
+bool refuse(const char *text) { device_set_last_error(text); return false; }
+}
+
+extern "C" {
+
+cfhd_amd_decode_batch *cfhd_amd_decode_batch_create(const void *first_sample, size_t first_size, uint32_t output_format, int decoded_resolution, int nsamples)
+{
+	CallerDevice caller_device;
+	if (!first_sample || first_size < 4) { refuse("decode queue: no first sample"); return nullptr; }
+	if (nsamples < 1) { refuse("decode queue: nsamples < 1"); return nullptr; }
+	{ const char *e = getenv("CFHD_AMD_ENTROPY"); if (e && strcmp(e, "host") == 0) { refuse("decode queue: CFHD_AMD_ENTROPY=host keeps the entropy stage on the host (the C ABI's arrangement)"); return nullptr; } }
+	const uint8_t *s8 = (const uint8_t *)first_sample;
+	const int first_tag = (int16_t)((s8[0] << 8) | s8[1]), sample_type = (s8[2] << 8) | s8[3];
+	if (first_tag == TAG_SAMPLE && (sample_type == 7 || sample_type == 2 || sample_type == 1)) { refuse("decode queue: two-frame groups (group samples, P-frame samples, sequence headers) are decoded by CFHD_DecodeSample"); return nullptr; }
+	ParsedSample ps;
+	const int parsed = parse_sample(s8, first_size, &ps);
+	const bool uncompressed = ps.uncompressed;           // (an UNCOMPRESS chunk: CFHD_PrepareToDecode refuses below with its own text)
+	if (parsed >= 0 && ps.encoded_format == ENC_BAYER) { refuse("decode queue: Bayer samples are decoded by CFHD_DecodeSample"); return nullptr; }
+	cfhd_amd_decode_batch *b = new (std::nothrow) cfhd_amd_decode_batch;
+	if (!b) return nullptr;
+	b->n = nsamples;
+	auto fail = [&](const char *text) { if (text) device_set_last_error(text); delete b; return (cfhd_amd_decode_batch *)nullptr; };
+	// the handle's gates: CFHD_PrepareToDecode on the whole first sample, then that sample through CFHD_DecodeSample once (the scan is only known there)
+	char text[200];
+	if (CFHD_OpenDecoder(&b->slow, nullptr) != ERR_OKAY) return fail("decode queue: no decoder handle");
+	int aw = 0, ah = 0; CFHD_PixelFormat af = 0; int32_t pitch = 0;
+	int rc = CFHD_PrepareToDecode(b->slow, 0, 0, output_format, decoded_resolution, 0, (void *)first_sample, first_size, &aw, &ah, &af);
+	if (rc != ERR_OKAY) {
+		if (!uncompressed) { snprintf(text, sizeof(text), "decode queue: CFHD_PrepareToDecode refuses this sample, output and resolution (CFHD_Error %d)", rc); return fail(text); }
+		return fail(nullptr);                              // (the uncompressed mode: the handle's own text)
+	}
+	if (CFHD_GetImagePitch((uint32_t)aw, af, &pitch) != ERR_OKAY || pitch <= 0 || ah <= 0) return fail("decode queue: no picture geometry");
+	{
+		std::vector<uint8_t> scratch((size_t)pitch * ah);
+		device_set_last_error("");
+		rc = CFHD_DecodeSample(b->slow, (void *)first_sample, first_size, scratch.data(), pitch);
+		if (rc != ERR_OKAY) {
+			if (*device_last_error()) return fail(nullptr);      // (the device layer said why: output_route()'s refusal texts, a missing device)
+			snprintf(text, sizeof(text), "decode queue: CFHD_DecodeSample refuses this sample, output and resolution (CFHD_Error %d)", rc); return fail(text);
+		}
+	}
+	if (decoder_handle_state(b->slow, &b->st)) return fail("decode queue: the first sample is not an intra sample");
+	// (k_dec_lowpass and the plane transforms carry sample x channel in a grid dimension)
+	if ((long long)nsamples * b->st.plan.num_channels > 65535) return fail("decode queue: the batch's job index would pass the grid limit (65 535)");
+	// on the calling thread's device, one stream for the whole pass, as cfhd_amd_batch_create_ex places its batches
+	struct Lean { Lean() { device_streams_lean(true); } ~Lean() { device_streams_lean(false); } } lean;
+	{
+		StreamScope scope;
+		b->dec.set_interlaced(b->st.interlaced);
+		const int prc = b->dec.prepare(b->st.plan, nsamples, b->st.out_kind, b->st.half) || b->dec.prepare_entropy(b->st.sample_cap);
+		b->scope_stream = scope.stream();
+		if (prc) return fail(nullptr);
+	}
+	b->device = device_current();
+	if (!b->dec.entropy().chunk_indexed()) return fail("decode queue: the chunk-indexed band decoder only (CFHD_AMD_DEC is set)");
+	if (allocate(b)) return fail("decode queue: out of device or pinned memory");
+	if (b->dec.entropy().set_samples_device(b->dec.entropy().sample_slots(), b->dec.entropy().slot_bytes(), b->d_sizes)) return fail("decode queue: sample slots");
+	b->dec.entropy().set_verdicts(b->d_verdicts);
+	b->slow_pictures.resize((size_t)nsamples);
+	return b;
+}
+
+void cfhd_amd_decode_batch_destroy(cfhd_amd_decode_batch *b)
+{
+	CallerDevice caller_device;
+	if (b && b->in_flight) (void)cfhd_amd_decode_batch_wait(b, nullptr);
+	delete b;
+}
+
+int cfhd_amd_decode_batch_geometry(cfhd_amd_decode_batch *b, int *width, int *height, int *row_bytes)
+{
+	if (!b || b->in_flight) return -1;
+	if (width) *width = b->st.half ? b->st.plan.width / 2 : b->st.plan.width;
+	if (height) *height = b->dec.picture_rows();
+	if (row_bytes) *row_bytes = b->dec.picture_pitch();
+	return 0;
+}
+
+int cfhd_amd_decode_batch_submit_host(cfhd_amd_decode_batch *b, const void *base, const size_t *offsets, const size_t *sizes, int count, void *pictures, size_t picture_stride, int picture_pitch)
+{
+	CallerDevice caller_device;
+	if (!b || b->in_flight || !base || !offsets || !sizes || count < 1 || count > b->n) return -1;
+	if (pictures && (picture_pitch < b->dec.picture_pitch() || picture_stride < (size_t)picture_pitch * (size_t)(b->dec.picture_rows() - 1) + (size_t)b->dec.picture_pitch())) return -1;
+	(void)hipSetDevice(b->device);
+	const size_t cap = b->dec.entropy().slot_bytes();
+	begin_pass(b, offsets, sizes, count);
+	const std::vector<uint32_t> &size = b->sizes;
+	size_t lo = ~(size_t)0, hi = 0;                        // the span of the samples k_dec_ingest will place
+	for (int i = 0; i < count; i++)
+		if (dev::dec_ingest_pieces(size[i], cap)) { if (offsets[i] < lo) lo = offsets[i]; if (offsets[i] + sizes[i] > hi) hi = offsets[i] + sizes[i]; }
+	b->src_host = (const uint8_t *)base; b->src_device = nullptr;
+	b->host_out = (uint8_t *)pictures; b->host_out_stride = picture_stride; b->host_out_pitch = picture_pitch;
+	hipStream_t st = (hipStream_t)b->dec.stream();
+	int rc = 0;
+	if (hi <= lo) {                                        // nothing to copy: every sample is empty or the slow path's
+		for (int i = 0; i < count; i++) b->table_src()[i] = 0;
+	} else if (hi - lo <= b->blob_cap - 32 && host_buffer_is_registered((const uint8_t *)base + lo, hi - lo)) {
+		// a registered blob: one DMA of the span as it lies, k_dec_ingest aligns
+		for (int i = 0; i < count; i++) b->table_src()[i] = dev::dec_ingest_pieces(size[i], cap) ? offsets[i] - lo : 0;
+		if (hipMemcpyAsync(b->d_blob, (const uint8_t *)base + lo, hi - lo, hipMemcpyHostToDevice, st) != hipSuccess) rc = -2;
+	} else {
+		// plain memory (or a span with gaps wider than the batch's buffer): the calling thread packs the samples back to back into pinned memory -- the only host
+		// work of a pass, in front of its first launch --, then the same DMA and the same kernel
+		size_t at = 0;
+		if (!b->h_blob && hipHostMalloc((void **)&b->h_blob, b->blob_cap, hipHostMallocPortable) != hipSuccess) { (void)hipGetLastError(); b->h_blob = nullptr; end_pass(b); device_set_last_error("decode queue: no pinned memory to stage the samples"); return -2; }
+		for (int i = 0; i < count; i++) { b->table_src()[i] = at; if (dev::dec_ingest_pieces(size[i], cap)) at += size[i]; }
+		parallel_for(count, count > 8 ? 8 : 1, [&](int i) { if (dev::dec_ingest_pieces(size[i], cap)) memcpy(b->h_blob + b->table_src()[i], (const uint8_t *)base + offsets[i], size[i]); });
+		if (at && hipMemcpyAsync(b->d_blob, b->h_blob, at, hipMemcpyHostToDevice, st) != hipSuccess) rc = -2;
+	}
+	if (!rc) rc = launch_pass(b, b->d_blob);
+	if (rc) { (void)b->dec.wait(); end_pass(b); return rc < 0 ? rc : -2; }
+	b->in_flight = true;
+	return 0;
+}
+
+int cfhd_amd_decode_batch_submit_device(cfhd_amd_decode_batch *b, const void *d_base, size_t span_bytes, const size_t *offsets, const size_t *sizes, int count)
+{
+	CallerDevice caller_device;
+	if (!b || b->in_flight || !d_base || !offsets || !sizes || count < 1 || count > b->n) return -1;
+	for (int i = 0; i < count; i++) if (offsets[i] > span_bytes || sizes[i] > span_bytes - offsets[i]) return -1;      // a sample outside the span the caller vouched for
+	(void)hipSetDevice(b->device);
+	begin_pass(b, offsets, sizes, count);
+	b->src_host = nullptr; b->src_device = (const uint8_t *)d_base; b->host_out = nullptr;
+	for (int i = 0; i < count; i++) b->table_src()[i] = offsets[i];
+	const int rc = launch_pass(b, (const uint8_t *)d_base);
+	if (rc) { (void)b->dec.wait(); end_pass(b); return rc < 0 ? rc : -2; }
+	b->in_flight = true;
+	return 0;
+}
+
+int cfhd_amd_decode_batch_wait(cfhd_amd_decode_batch *b, CFHD_Error *status)
+{
+	CallerDevice caller_device;
+	if (!b || !b->in_flight) return -1;
+	(void)hipSetDevice(b->device);
+	const int n = b->n, count = b->count;
+	auto device_failure = [&](int code) { if (status) for (int i = 0; i < count; i++) status[i] = ERR_INTERNAL; end_pass(b); return code; };
+	if (b->dec.wait()) return device_failure(-2);
+	if (b->timed) {
+		b->timed = false;
+		if (hipEventElapsedTime(&b->ingest_ms, b->ev[0], b->ev[1]) != hipSuccess) { (void)hipGetLastError(); b->ingest_ms = 0; }
+		if (hipEventElapsedTime(&b->blank_ms, b->ev[2], b->ev[3]) != hipSuccess) { (void)hipGetLastError(); b->blank_ms = 0; }
+	}
+	if (b->host_out) {                                     // (pictures staged through pinned memory -- a plain buffer -- leave it on a few threads side by side; nothing to do for a registered one)
+		std::atomic<int> bad(0);
+		parallel_for(count, count > 8 ? 8 : 1, [&](int i) { if (b->dec.finish_frame(i, b->host_out + b->host_out_stride * (size_t)i, b->host_out_pitch)) bad.store(1); });
+		if (bad.load()) return device_failure(-2);
+	}
+	// the verdicts.  Final on the spot: a sample the parser refused (malformed, geometry, encoded format or channel count, bands missing) while its scan flag is the
+	// prepared one -- CFHD_ERROR_BADSAMPLE, its picture already zeroed by k_dec_blank.  The slow path: what k_dec_ingest marked, what only the host parser judges, a
+	// scan flag or colour-space tag other than the first sample's, and -- the band decoders' error word is one for the pass -- every sample the parser passed.
+	const bool stream_damage = b->dec.entropy().check() != 0;
+	const uint32_t clean = b->clean_word();
+	const int picture_pitch = b->dec.picture_pitch(); const size_t picture_bytes = b->dec.picture_bytes();
+	std::vector<uint8_t> bytes;
+	int decoded = 0, failure = 0;
+	for (int i = count; i < n; i++) b->slow_pictures[i].clear();      // (a short pass: what an earlier pass left behind its count is that pass's picture in HBM again)
+	for (int i = 0; i < count; i++) {
+		const uint32_t v = b->h_verdicts[i], mark = b->h_verdicts[n + i];
+		const int reason = (int)(v & 0xffu);
+		const bool scan_as_prepared = ((v >> 8) & 1u) == (b->st.progressive_flag ? 1u : 0u);
+		b->slow_pictures[i].clear();
+		int rc;
+		if (!mark && reason >= dev::DEC_VERDICT_MALFORMED && reason <= dev::DEC_VERDICT_BANDS && scan_as_prepared) rc = ERR_BADSAMPLE;
+		else if (!mark && v == clean && !stream_damage) rc = ERR_OKAY;
+		else {
+			const size_t size = b->full_sizes[i];
+			const uint8_t *s = b->src_host ? b->src_host + b->offsets[i] : nullptr;
+			if (!s) {
+				bytes.resize(size ? size : 1);
+				if (size && hipMemcpy(bytes.data(), b->src_device + b->offsets[i], size, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); failure = -2; }
+				s = bytes.data();
+			}
+			// the handle's picture is kept with the batch whichever way the pass delivers its pictures: download_output(i) then agrees with status[i], not with what the
+			// device stage left in HBM
+			b->slow_pictures[i].assign(picture_bytes, 0);
+			rc = failure ? ERR_INTERNAL : CFHD_DecodeSample(b->slow, (void *)s, size, b->slow_pictures[i].data(), picture_pitch);
+			if (b->host_out) for (int r = 0; r < b->dec.picture_rows(); r++)
+				memcpy(b->host_out + b->host_out_stride * (size_t)i + (size_t)r * b->host_out_pitch, b->slow_pictures[i].data() + (size_t)r * picture_pitch, (size_t)picture_pitch);
+			(void)hipSetDevice(b->device);
+		}
+		if (status) status[i] = rc;
+		decoded += rc == ERR_OKAY;
+	}
+	b->steps++;
+	end_pass(b);
+	return failure ? failure : decoded;
+}
+
+int cfhd_amd_decode_batch_download_output(cfhd_amd_decode_batch *b, int i, void *out, int pitch)
+{
+	CallerDevice caller_device;
+	if (!b || b->in_flight || i < 0 || i >= b->n || !out || pitch < b->dec.picture_pitch()) return -1;
+	const int rows = b->dec.picture_rows(), row_bytes = b->dec.picture_pitch();
+	if (!b->slow_pictures[i].empty()) {                    // decoded by the slow path of the last pass
+		for (int r = 0; r < rows; r++) memcpy((uint8_t *)out + (size_t)r * pitch, b->slow_pictures[i].data() + (size_t)r * row_bytes, (size_t)row_bytes);
+		return 0;
+	}
+	if (b->dec.download_frame(i, out, pitch) || b->dec.wait()) return -2;
+	return b->dec.finish_frame(i, out, pitch);
+}
+
+// which: 0 k_dec_ingest, 1 k_dec_parse, 2 the band decoder (all its kernels), 3 k_dec_lowpass, 4 / 5 / 6 the transform levels in launch order (wavelet 3, wavelet 2, the
+// last level + output conversion), 7 k_dec_blank (ms of the last pass, HIP events on the batch's stream)
+float cfhd_amd_decode_batch_kernel_ms(cfhd_amd_decode_batch *b, int which)
+{
+	if (!b || b->in_flight || which < 0 || which > 7) return 0;
+	if (which == 0) return b->ingest_ms;
+	if (which == 7) return b->blank_ms;
+	if (which < 4) return b->dec.entropy().kernel_ms(which - 1);
+	return b->dec.last_level_ms(6 - which);
+}
+
+const char *cfhd_amd_decode_batch_kernel_name(cfhd_amd_decode_batch *b, int which)
+{
+	if (!b || b->in_flight || which < 0 || which > 7) return "";
+	static const char *const fixed[4] = { "k_dec_ingest", "k_dec_parse", "k_dec_plan+k_dec_index+k_dec_chain+k_dec_tiles", "k_dec_lowpass" };
+	if (which < 4) return fixed[which];
+	if (which == 7) return "k_dec_blank";
+	return b->dec.level_kernel(6 - which);
+}
+
+} // extern "C"

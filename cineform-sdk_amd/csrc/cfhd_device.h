@@ -129,7 +129,12 @@ public:
 	const char *level_kernel(int level) const;      // name of the kernel the next launch_entropy() + launch_inverse() use for level 0 / 1 / 2 (as a profiler shows it)
 	int launch_inverse(uint32_t dither_seed);          // async
 	int download_frame(int i, void *out, int pitch_bytes);   // async D2H into pinned staging, then row copy after wait
-	int download_frames(void *out, size_t frame_stride, int pitch_bytes);      // all n frames (finish_frame() for each behind wait()); ONE copy into a registered buffer that takes them back to back
+	int download_frames(void *out, size_t frame_stride, int pitch_bytes);      // all n frames -- the first k after set_active(k) -- (finish_frame() for each behind wait()); ONE copy into a registered buffer that takes them back to back
+	// the decoded pictures in HBM, for a kernel queued behind launch_inverse() on stream() (the decode queue's k_dec_blank): picture i at device_pictures() + i * picture_bytes()
+	uint8_t *device_pictures() const { return d_out_; }
+	size_t picture_bytes() const { return frame_bytes_; }
+	int picture_pitch() const { return out_pitch_; }
+	int picture_rows() const { return out_rows_; }
 	int after(void *producer_stream);                  // async: later work on this batch's stream waits for what the producer stream holds now
 	int wait();
 	int finish_frame(int i, void *out, int pitch_bytes);      // after wait(): copy the staged frame to the caller's buffer

@@ -1288,19 +1288,20 @@ int DecodeBatch::download_frames(void *out, size_t frame_stride, int pitch)
 {
 	(void)hipSetDevice(device_);
 	if (!out) return -1;
-	if (pitch == out_pitch_ && frame_stride == frame_bytes_ && host_buffer_is_registered(out, frame_bytes_ * (size_t)n_)) {
-		HIPCHK(hipMemcpyAsync(out, d_out_, frame_bytes_ * (size_t)n_, hipMemcpyDeviceToHost, (hipStream_t)stream_));
+	const int act = active_frames(active_, n_);          // frames 0 .. act-1 carry pictures (set_active)
+	if (pitch == out_pitch_ && frame_stride == frame_bytes_ && host_buffer_is_registered(out, frame_bytes_ * (size_t)act)) {
+		HIPCHK(hipMemcpyAsync(out, d_out_, frame_bytes_ * (size_t)act, hipMemcpyDeviceToHost, (hipStream_t)stream_));
 		direct_.assign((size_t)n_, 1);
 		return 0;
 	}
 	if (n_ > 8 && !host_buffer_is_registered(out, 1)) {
 		// plain memory, many frames: ONE copy into the batch's pinned memory; finish_frame() copies every frame out behind wait() (the caller runs them on several threads)
-		HIPCHK(hipMemcpyAsync(h_out_, d_out_, frame_bytes_ * (size_t)n_, hipMemcpyDeviceToHost, (hipStream_t)stream_));
+		HIPCHK(hipMemcpyAsync(h_out_, d_out_, frame_bytes_ * (size_t)act, hipMemcpyDeviceToHost, (hipStream_t)stream_));
 		direct_.assign((size_t)n_, 0);
 		out_pieces_.assign((size_t)n_, 0);
 		return 0;
 	}
-	for (int i = 0; i < n_; i++) { const int rc = download_frame(i, (uint8_t *)out + frame_stride * (size_t)i, pitch); if (rc) return rc; }
+	for (int i = 0; i < act; i++) { const int rc = download_frame(i, (uint8_t *)out + frame_stride * (size_t)i, pitch); if (rc) return rc; }
 	return 0;
 }
 

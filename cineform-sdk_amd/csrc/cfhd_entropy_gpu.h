@@ -109,7 +109,7 @@ public:
 	~GpuEntropyDecoder();
 	// before the samples are set: interlaced samples (frame transform; one band per channel in code set 18, difference coded, maybe with a peak table)
 	void set_interlaced(bool on) { interlaced_ = on; }
-	// host-parsed samples only: the next launch() covers frames 0 .. k-1 of the batch (0 = all; a batch that gathers concurrent callers is rarely full)
+	// the next launch() covers frames 0 .. k-1 of the batch (0 = all; a batch that gathers concurrent callers is rarely full, a pass of the decode queue may be short)
 	void set_active(int k) { active_ = k; }
 	void set_skip_level1(bool skip) { skip_level1_ = skip; }            // before prepare(): host-parsed samples decode levels 2 and 3 only
 	int prepare(const FramePlan &plan, int nframes, int16_t *d_coeffs, size_t coeff_stride_elems, size_t sample_cap, int out_pixel_kind, void *stream);
@@ -124,6 +124,12 @@ public:
 	// Optional, for device-resident samples still being written by another stream: the next launch() lets k_dec_parse wait for
 	// `headers` only (it reads the tag stream, not the coded payloads) and the band decoder for `payloads`.
 	void set_producer_events(void *headers, void *payloads) { ev_headers_ = headers; ev_payloads_ = payloads; }
+	// The decode queue (cfhd_decode_queue.hip) fills the decoder's own sample slots on the device (k_dec_ingest): slot i at sample_slots() + i * slot_bytes(), a
+	// multiple of 256, the sizes in a table of the caller's -- both handed back through set_samples_device().  With a verdict table (device memory, one word per
+	// frame, null: none) k_dec_parse stores a verdict per sample and leaves DEC_ERR_PARSE alone: check() then speaks of the code streams only.
+	uint8_t *sample_slots() const { return d_samples_; }
+	size_t slot_bytes() const { return cap_; }
+	void set_verdicts(uint32_t *d_verdicts) { d_verdicts_ = d_verdicts; }
 	int launch();                        // async: (H2D samples, job tables | k_dec_parse), the band decoder (k_dec_index .. k_dec_tiles by default) + k_dec_lowpass
 	int check();                         // after the stream was synchronised: 0 when every band decoded cleanly
 	float kernel_ms(int k);              // last launch(): 0 k_dec_parse (device-resident samples only), 1 band decoder (all its kernels), 2 k_dec_lowpass, 3 k_dec_plan + k_dec_index, 4 k_dec_chain + k_dec_tile_index, 5 k_dec_tiles
@@ -150,6 +156,7 @@ private:
 	bool skip_level1_ = false, interlaced_ = false; void *d_diffjobs_ = nullptr;
 	int active_ = 0;
 	int active_frames() const { return active_ > 0 && active_ < n_ ? active_ : n_; }
+	uint32_t *d_verdicts_ = nullptr;
 	const uint8_t *ext_samples_ = nullptr; size_t ext_stride_ = 0; const uint32_t *ext_sizes_ = nullptr, *ext_offsets_ = nullptr;   // set_samples_device()
 	int *d_errors_ = nullptr, *h_errors_ = nullptr;
 	DecBackend backend_ = DecBackend::ChunkIndexed;

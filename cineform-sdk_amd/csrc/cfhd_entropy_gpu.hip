@@ -483,7 +483,8 @@ int GpuEntropyDecoder::launch()
 	const int nch = plan_.num_channels;
 	l23_split_ = false; blocks_written_ = false;
 	// device-resident samples: the job tables have one row per band type (largest first), nframes wide, and the device numbers the chunks
-	Pass p = { true, n_, n_ * nch * 9, n_ * nch, max_chunks_ };
+	const int nd = active_frames();                      // (device-resident samples: all of them unless a short pass of the decode queue said otherwise)
+	Pass p = { true, nd, nd * nch * 9, nd * nch, max_chunks_ };
 	if (!ext_samples_) {
 		if (chunk_indexed()) HIPCHK(hipStreamSynchronize(st));                    // the pinned tables of the previous launch may still be in flight
 		const int rc = flatten_host_jobs(&p);
@@ -497,9 +498,9 @@ int GpuEntropyDecoder::launch()
 		if (!parse_early && ev_payloads_) ev_headers_ = ev_payloads_;
 		if (ev_headers_) HIPCHK(hipStreamWaitEvent(st, (hipEvent_t)ev_headers_, 0));
 		HIPCHK(hipEventRecord((hipEvent_t)ev_[0], st));
-		dev::k_dec_parse<<<n_, dev::DEC_PARSE_THREADS, 0, st>>>(ext_samples_, ext_stride_, ext_sizes_, n_,
+		dev::k_dec_parse<<<nd, dev::DEC_PARSE_THREADS, 0, st>>>(ext_samples_, ext_stride_, ext_sizes_, nd,
 			(const dev::DecPlan *)d_plan_, d_coeffs_, coeff_stride_, (dev::DecBandJob *)d_bandjobs_, (dev::DecLowpassJob *)d_lowjobs_, d_errors_,
-			interlaced_ && chunk_indexed() ? (dev::DecDiffJob *)d_diffjobs_ : nullptr, ext_offsets_);
+			interlaced_ && chunk_indexed() ? (dev::DecDiffJob *)d_diffjobs_ : nullptr, ext_offsets_, d_verdicts_);
 		parse_end_ = ev_payloads_ != nullptr;
 		if (parse_end_) { HIPCHK(hipEventRecord((hipEvent_t)ev_[4], st)); HIPCHK(hipStreamWaitEvent(st, (hipEvent_t)ev_payloads_, 0)); }
 		ev_headers_ = ev_payloads_ = nullptr;

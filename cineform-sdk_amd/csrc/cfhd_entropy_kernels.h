@@ -1259,7 +1259,8 @@ struct DecTagReader {
 __global__ void __launch_bounds__(DEC_PARSE_THREADS) k_dec_parse(const uint8_t *samples, size_t sample_stride, const uint32_t *sizes, int nframes, const DecPlan *P,
                                                                  int16_t *coeffs, size_t coeff_stride, DecBandJob *bandjobs, DecLowpassJob *lowjobs, int *errors,
                                                                  DecDiffJob *diffjobs /* [nframes * channels], may be null: progressive samples only */,
-                                                                 const uint32_t *offsets = nullptr /* sample f at samples + offsets[f] (the encoder's dense buffer); null: at samples + f * sample_stride */)
+                                                                 const uint32_t *offsets = nullptr /* sample f at samples + offsets[f] (the encoder's dense buffer); null: at samples + f * sample_stride */,
+                                                                 uint32_t *verdicts = nullptr /* [nframes], the decode queue: a verdict per sample instead of DEC_ERR_PARSE for the pass -- low byte 0, or why the walk failed (1 malformed, 2 geometry, 3 encoded format / channel count, 4 bands missing, 5 only the host parser judges it: an UNCOMPRESS chunk); bit 8 the progressive flag, bits 16 .. 31 the colour-space tag (cfhd_ingest_kernels.h dec_verdict_word) */)
 {
 	const int f = blockIdx.x;                            // every lane walks the same tags; lane 0 writes the jobs
 	const int lane = wave_lane();
@@ -1284,6 +1285,7 @@ __global__ void __launch_bounds__(DEC_PARSE_THREADS) k_dec_parse(const uint8_t *
 	uint64_t seen = 0;                                   // one bit per coded band: up to 4 channels x 9
 	int channel = 0, lv = -1, band = 0, bw = 0, bh = 0, bq = 1, bflags = 0, lw = 0, lh = 0;
 	int width = 0, height = 0, display_height = 0, num_channels = 0, encoded_format = 0;
+	int progressive = 0, color_space = 0; bool host_only = false;      // (for the verdict: what parse_sample keeps of TAG_SAMPLE_FLAGS and TAG_ENCODED_COLORSPACE)
 	bool bad = size < 4;
 	while (!bad && pos + 4 <= size) {
 		const uint32_t word = rd.word(pos);
@@ -1299,10 +1301,13 @@ __global__ void __launch_bounds__(DEC_PARSE_THREADS) k_dec_parse(const uint8_t *
 		}
 		if (tag & 0x2000) {
 			if ((tag & 0xff00) == 0x2000) { pending = ((((uint32_t)(tag & 0xff)) << 16) | (uint32_t)value) * 4u; pending_at = pos; }
+			if (verdicts && (tag & 0xff00) == 0x2300) { host_only = true; bad = true; break; }      // CODEC_TAG_UNCOMPRESS: raw pixels follow (parse_sample stops here too)
 			continue;
 		}
 		switch (tag) {
 		case 2: pos += 4u * (uint64_t)value; break;                                  // TAG_INDEX
+		case 68: progressive = value & 1; break;                                     // TAG_SAMPLE_FLAGS
+		case 91: color_space = value; break;                                         // TAG_ENCODED_COLORSPACE
 		case 62: channel = value; if (channel >= 4) bad = true; break;               // TAG_CHANNEL
 		case 12: num_channels = value; break;                                        // TAG_NUM_CHANNELS
 		case 84: encoded_format = value; break;                                      // TAG_ENCODED_FORMAT
@@ -1352,13 +1357,16 @@ __global__ void __launch_bounds__(DEC_PARSE_THREADS) k_dec_parse(const uint8_t *
 	}
 	if (display_height == 0) display_height = height;
 	const uint64_t want = ((uint64_t)1 << (nch * 9)) - 1u;
+	int reason = 0;
 	if (bad || width != P->width || display_height != P->display_height || encoded_format != P->encoded_format || num_channels != nch
 	    || seen != want || seen_low != (1u << nch) - 1u) {
 		if (writer) for (int c = 0; c < nch; c++)
 			for (int l = 0; l < 3; l++)
 				for (int b = 1; b < 4; b++) bandjobs[(size_t)P->slot[c][l][b] * nframes + f].bytes = 0u;
-		if (writer) atomic_or_u32((uint32_t *)errors, (uint32_t)DEC_ERR_PARSE);
+		if (writer && !verdicts) atomic_or_u32((uint32_t *)errors, (uint32_t)DEC_ERR_PARSE);
+		reason = host_only ? 5 : bad ? 1 : (width != P->width || display_height != P->display_height) ? 2 : (encoded_format != P->encoded_format || num_channels != nch) ? 3 : 4;
 	}
+	if (writer && verdicts) verdicts[f] = (uint32_t)reason | ((uint32_t)progressive << 8) | ((uint32_t)(color_space & 0xffff) << 16);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -20,5 +20,14 @@ struct FrontEndParams {
 };
 // Same checks and derivations as CFHD_PrepareToEncode (cfhd_api.cpp make_params).  Returns a CFHD_Error value (0 = OK).
 int front_end_params(int width, int height, uint32_t pixel_format, int encoded_format, uint32_t encoding_flags, int quality, FrontEndParams *out);
+// What a decoder handle knows once CFHD_PrepareToDecode has accepted a whole sample, for the other front end of the same decoder (the decode queue,
+// cfhd_decode_queue.hip): the handle's own gates decide, this only reads their result.  Returns 0, or -1 for a handle that is not prepared on an intra sample.
+struct DecoderHandleState {
+	FramePlan plan;                                           // geometry, precision, prescale, colour matrix: as the handle decodes every sample it is given
+	int out_kind = 0, encoded_format = 0, color_space = 0;
+	bool half = false, interlaced = false, progressive_flag = false;      // of the sample the handle was prepared on (the whole sample: the flag lies behind the first 512 bytes)
+	size_t sample_cap = 0;                                    // the longest sample the handle's device stage takes
+};
+int decoder_handle_state(void *decoder_ref, DecoderHandleState *out);
 
 } // namespace cfhd

@@ -184,6 +184,49 @@ int  cfhd_amd_batch_dx_stats(cfhd_amd_batch *batch, uint32_t *out16);
 /* Whether the quantizer tables of these CFHD_PrepareToEncode arguments stay put from frame to frame (1), or follow the size of the previous sample (0: rate feedback --
  * FILMSCAN2 / FILMSCAN3, LOW .. HIGH up to 1080p -- which cfhd_amd_batch_create_ex refuses and CFHD_EncodeSample applies per frame); -1: arguments no encoder takes. */
 int  cfhd_amd_quantizer_is_static(int width, int height, uint32_t pixel_format, int encoded_format, uint32_t encoding_flags, int quality);
+/* ---------------- the decode queue: batches of intra samples from any encoder, parsed and decoded on the GPU (cfhd_decode_queue.hip) ----------------
+ * What cfhd_amd_batch_* is to a caller who has just encoded, for a caller who holds a clip: nsamples samples a pass, one launch per stage for all of them, no host
+ * tag walk and no device wait per picture.  Progressive and interlaced 4:2:2, RGB 4:4:4 and RGBA 4:4:4:4 samples, to every output and resolution CFHD_DecodeSample
+ * serves for them; two-frame groups and Bayer samples stay with CFHD_DecodeSample. */
+typedef struct cfhd_amd_decode_batch cfhd_amd_decode_batch;
+/* Prepares from one complete intra sample, as CFHD_PrepareToDecode prepares a handle: geometry, encoded format, precision, scan and colour space are the first
+ * sample's, output_format / decoded_resolution those of CFHD_PrepareToDecode.  NULL, with the reason in cfhd_amd_last_error(), for whatever CFHD_PrepareToDecode or
+ * CFHD_DecodeSample refuses for that sample, output and resolution (the sample is decoded once on a handle of its own to find out), for group samples, P-frame samples,
+ * sequence headers, Bayer samples, samples with an UNCOMPRESS chunk, under CFHD_AMD_ENTROPY=host, for nsamples < 1 or nsamples x channels > 65 535.  The batch lives on
+ * the device a cfhd_amd_batch_create_ex of the same thread would. */
+cfhd_amd_decode_batch *cfhd_amd_decode_batch_create(const void *first_sample, size_t first_size, uint32_t output_format, int decoded_resolution, int nsamples);
+/* Waits for a pass in flight, then frees the batch. */
+void cfhd_amd_decode_batch_destroy(cfhd_amd_decode_batch *batch);
+/* One decoded picture: width x height pixels in rows of row_bytes bytes (any of the three may be NULL).  0, or -1. */
+int  cfhd_amd_decode_batch_geometry(cfhd_amd_decode_batch *batch, int *width, int *height, int *row_bytes);
+/* Starts a pass and returns at once: sample i is sizes[i] bytes at base + offsets[i] -- any byte alignment, any order, gaps allowed --, count <= nsamples; picture i goes
+ * to pictures + i * picture_stride in rows picture_pitch apart (NULL: the pictures stay in HBM for cfhd_amd_decode_batch_download_output).  Exactly count pictures are
+ * written, row_bytes of every row and nothing behind them.  Both buffers are borrowed until cfhd_amd_decode_batch_wait returns (offsets / sizes are copied).  A span
+ * inside a buffer registered with cfhd_amd_register_host_buffer travels as one DMA as it lies; anything else is packed into the batch's pinned memory inside this call,
+ * before the first launch -- the only host work of a pass: by the calling thread and, for passes of more than 8 samples, up to seven short-lived helper threads it joins
+ * before it launches anything (wait copies pictures out of pinned memory into a plain picture buffer the same way).  Several decode batches in flight overlap on the GPU; one pass per batch at a time: between submit and
+ * wait every other entry point on that batch returns its error value (-1, 0, ""), destroy waits first.  0, -1 for bad arguments, < -1 for a device failure.
+ * 8-bit outputs: the dither seed of pass k (counted from 0 per batch) is 0xA511E9B3 * (k + 1), the rule of cfhd_amd_batch_submit's round trip -- CFHD_DecodeSample's
+ * n-th call uses 0x2545F491 * n, so such pictures agree with the handle's to within the one dither step, all others byte for byte. */
+int  cfhd_amd_decode_batch_submit_host(cfhd_amd_decode_batch *batch, const void *base, const size_t *offsets, const size_t *sizes, int count,
+                                       void *pictures, size_t picture_stride, int picture_pitch);
+/* The same for samples that already lie in HBM on the batch's device: sample i at d_base + offsets[i] (offsets, sizes: host arrays; every sample inside
+ * [d_base, d_base + span_bytes), else -1).  The library reads the 16-byte aligned blocks that hold bytes of [d_base, d_base + span_bytes) -- its 16-byte hull -- and
+ * nothing else, until wait returns.  The pictures stay in HBM. */
+int  cfhd_amd_decode_batch_submit_device(cfhd_amd_decode_batch *batch, const void *d_base, size_t span_bytes, const size_t *offsets, const size_t *sizes, int count);
+/* Collects the pass: the number of samples that decoded, or < 0 (-1: nothing in flight, -2: device failure).  status (NULL or count entries): status[i] is the CFHD_Error
+ * CFHD_DecodeSample returns for sample i on a handle prepared on the first sample; the picture of a sample that failed is zero.  Samples the device parser refuses are
+ * final there; samples the device stage does not place (longer than width x height x bytes per pixel + 64 KB, a size that is no multiple of 4), samples whose scan or
+ * colour-space tag differs from the first sample's and -- when any code stream of the pass is damaged -- every sample the parser passed are decoded by that handle
+ * inside this call. */
+int  cfhd_amd_decode_batch_wait(cfhd_amd_decode_batch *batch, CFHD_Error *status);
+/* Picture i of the last pass into out (rows `pitch` >= row_bytes apart): from HBM, or, for a sample the handle decoded inside wait, the handle's picture, which the
+ * batch keeps whichever way the pass delivered its pictures -- what this call gives always agrees with status[i].  0, -1 for bad arguments or a pass in flight, -2 for a device failure. */
+int  cfhd_amd_decode_batch_download_output(cfhd_amd_decode_batch *batch, int i, void *out, int pitch);
+/* HIP-event time (ms) of the kernels of the last pass and their names as a profiler shows them.  which: 0 k_dec_ingest, 1 k_dec_parse, 2 the band decoder (all its
+ * kernels), 3 k_dec_lowpass, 4 / 5 / 6 the transform levels in launch order (the last one with the output conversion), 7 k_dec_blank.  0 / "" otherwise. */
+float cfhd_amd_decode_batch_kernel_ms(cfhd_amd_decode_batch *batch, int which);
+const char *cfhd_amd_decode_batch_kernel_name(cfhd_amd_decode_batch *batch, int which);
 int  cfhd_amd_device_count(void);
 /* Text of the last HIP / device failure behind a CFHD_ERROR_INTERNAL (the library has no CPU fallback: without a gfx950 device every
  * compute call fails and says why here). */
