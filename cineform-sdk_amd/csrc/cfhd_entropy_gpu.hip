@@ -84,7 +84,16 @@ int GpuEntropyEncoder::prepare_units(int nframes, int16_t *d_coeffs, size_t stri
 	// k_ent_count_blocks / k_ent_emit is paid a quarter as often.  CFHD_AMD_L1_SEG=1024 .. 8192 (multiples of 1024): another length, for A/B runs and the sweep.
 	static const int l1_seg_env = [] { const char *e = getenv("CFHD_AMD_L1_SEG"); const int v = e ? atoi(e) : 0;
 	                                   return v >= dev::ENT_SEG && v <= dev::ENT_SEG_MAX && v % dev::ENT_SEG == 0 ? v : (int)dev::ENT_SEG_L1; }();
-	if (!ent_build_band_jobs(host_->geom, tmpl_[0], n_, d_coeffs, stride, &jobs, lists ? l1_seg_env : (int)dev::ENT_SEG)) return -3;
+	// The bands k_ent_count counts densely pay the same fixed cost per wave: cfhd_entropy_jobs.h EntSegRule, one length per level.  Long segments trade waves for fixed
+	// cost, which pays once the launches have more waves than the chip holds at a time (256 CUs x 4 SIMDs x 8 waves of k_ent_count / k_ent_emit); a pass below that -- a
+	// single frame of the C ABI, a few small ones -- runs all its waves side by side and takes as long as its longest wave: it keeps dev::ENT_SEG.
+	// CFHD_AMD_SEG_L1_DENSE, CFHD_AMD_SEG_L2, CFHD_AMD_SEG_L3 = 1024 .. 8192 (multiples of 1024): that length whatever the size of the pass; read at every prepare, so that
+	// one process can hold encoders of different lengths (tests, sweeps).
+	enum { kWaveSlots = 256 * 4 * 8 };
+	const bool fills_chip = (size_t)n_ * stride / dev::ENT_SEG >= (size_t)kWaveSlots;
+	auto seg_env = [&](const char *name, int dflt) { const char *e = getenv(name); const int v = e ? atoi(e) : 0; return ent_seg_len_ok(v) ? v : (fills_chip ? dflt : (int)dev::ENT_SEG); };
+	const EntSegRule rule = { seg_env("CFHD_AMD_SEG_L1_DENSE", dev::ENT_SEG_L1_DENSE), seg_env("CFHD_AMD_SEG_L2", dev::ENT_SEG_L2), seg_env("CFHD_AMD_SEG_L3", dev::ENT_SEG_L3), lists };
+	if (!ent_build_band_jobs(host_->geom, tmpl_[0], n_, d_coeffs, stride, &jobs, lists ? l1_seg_env : (int)dev::ENT_SEG, &rule)) return -3;
 	nbands_ = jobs.nbands; total_segs_ = (int)jobs.segjobs.size(); tok_per_frame_ = jobs.tok_per_frame;
 	HIPCHK(hipMalloc(&d_bands_, jobs.bands.size() * sizeof(dev::EntBandJob)));
 	HIPCHK(hipMemcpy(d_bands_, jobs.bands.data(), jobs.bands.size() * sizeof(dev::EntBandJob), hipMemcpyHostToDevice));

@@ -230,7 +230,8 @@ struct EntHostJobs {
 };
 
 // Where the holes of a template find their coefficients: the band of the pyramid behind every hole, in template order (the same for every frame of a batch).
-struct EntHoleGeom { size_t offset; int width, height, pitch; int table /* 0: code set 17, 1: code set 18 */; int mask_base /* block lists: first mask, or -1 */; bool level1; };
+struct EntHoleGeom { size_t offset; int width, height, pitch; int table /* 0: code set 17, 1: code set 18 */; int mask_base /* block lists: first mask, or -1 */; bool level1;
+                     int level /* pyramid level of the band: 1, 2, 3 (what EntSegRule goes by) */; };
 inline std::vector<EntHoleGeom> ent_hole_geometry(const FramePlan &plan, const SampleTemplate &t)
 {
 	int mask_base[kMaxChannels][kNumBands];
@@ -240,7 +241,7 @@ inline std::vector<EntHoleGeom> ent_hole_geometry(const FramePlan &plan, const S
 		const BandDesc &bd = plan.ch[hole.channel].band[hole.level][hole.band];
 		g.push_back(EntHoleGeom{ bd.offset, bd.width, bd.height, bd.pitch,
 		                         plan.interlaced && hole.level == 0 && hole.band == 2 ? 1 : 0,      // subband 8 of the channel (cfhd_bitstream.cpp walk_sample)
-		                         hole.kind == 1 && hole.level == 0 ? mask_base[hole.channel][hole.band] : -1, hole.level == 0 });
+		                         hole.kind == 1 && hole.level == 0 ? mask_base[hole.channel][hole.band] : -1, hole.level == 0, hole.level + 1 });
 	}
 	return g;
 }
@@ -250,18 +251,27 @@ inline std::vector<EntHoleGeom> ent_hole_geometry(const GopPlan &plan, const Sam
 	std::vector<EntHoleGeom> g;
 	for (const SampleTemplate::Hole &hole : t.holes) {
 		const GopWavelet &wv = plan.ch[hole.channel].w[hole.level];
-		g.push_back(EntHoleGeom{ wv.offset[hole.band], wv.width, wv.height, wv.pitch, gop_band_is_difference_coded(plan, hole.level, hole.band) ? 1 : 0, -1, hole.level < 2 });      // (code set 18: subbands 12 and 15 of an interlaced group)
+		g.push_back(EntHoleGeom{ wv.offset[hole.band], wv.width, wv.height, wv.pitch, gop_band_is_difference_coded(plan, hole.level, hole.band) ? 1 : 0, -1, hole.level < 2,
+		                         hole.level < 2 ? 1 : (hole.level < 5 ? 2 : 3) });      // (w[3] and w[4] are as large as an intra frame's level 2, w[5] as its level 3; code set 18: subbands 12 and 15 of an interlaced group)
 	}
 	return g;
 }
 
+// Segment lengths of the bands coded with table 0 that are counted densely (k_ent_count), by pyramid level: multiples of dev::ENT_SEG up to dev::ENT_SEG_MAX.
+// GpuEntropyEncoder::prepare_units fills it from dev::ENT_SEG_L1_DENSE / _L2 / _L3 and their switches; {ENT_SEG, ENT_SEG, ENT_SEG} is the cut of every band before the rule existed.
+// lists: the level-1 bands that have block lists (EntHoleGeom::mask_base >= 0) are counted from them (k_ent_count_blocks) and keep l1_seg; false: they are counted
+// densely like any other level-1 band (interlaced frames, CFHD_AMD_BLOCKS=0 aside) and take l1_dense.
+struct EntSegRule { int l1_dense, l2, l3; bool lists; };
+inline bool ent_seg_len_ok(int v) { return v >= dev::ENT_SEG && v <= dev::ENT_SEG_MAX && v % dev::ENT_SEG == 0; }
+
 // l1_seg: segment length of the level-1 bands that are coded with table 0 from block lists (k_ent_count_blocks; the caller opts in when it has allocated them):
-// a multiple of dev::ENT_SEG up to dev::ENT_SEG_MAX.  Every other band -- and every band by default -- has segments of dev::ENT_SEG.
+// a multiple of dev::ENT_SEG up to dev::ENT_SEG_MAX.  Every other band -- and every band by default -- has segments of dev::ENT_SEG, unless the caller passes a
+// rule: then the other bands coded with table 0 take the rule's length for their level.  A band coded with table 1 has segments of dev::ENT_SEG whatever is asked.
 inline bool ent_build_band_jobs(const std::vector<EntHoleGeom> &geom, const SampleTemplate &t0, int nframes, int16_t *coeffs, size_t stride, EntHostJobs *out,
-                                int l1_seg = dev::ENT_SEG)
+                                int l1_seg = dev::ENT_SEG, const EntSegRule *rule = nullptr)
 {
 	if ((int)t0.holes.size() > dev::ENT_MAX_HOLES || (int)t0.patches.size() > kEntMaxPatches || geom.size() != t0.holes.size()) return false;
-	if (l1_seg < dev::ENT_SEG || l1_seg > dev::ENT_SEG_MAX || l1_seg % dev::ENT_SEG) return false;
+	if (!ent_seg_len_ok(l1_seg) || (rule && !(ent_seg_len_ok(rule->l1_dense) && ent_seg_len_ok(rule->l2) && ent_seg_len_ok(rule->l3)))) return false;
 	out->bands.clear(); out->segjobs.clear(); out->ranges_l1.clear(); out->ranges_rest.clear();
 	out->tok_per_frame = 0;
 	out->band_of_hole.assign(t0.holes.size(), -1);
@@ -274,7 +284,8 @@ inline bool ent_build_band_jobs(const std::vector<EntHoleGeom> &geom, const Samp
 			const EntHoleGeom &bd = geom[h];
 			dev::EntBandJob j;
 			j.coeffs = base + bd.offset; j.n = bd.height * bd.pitch;
-			const int len = bd.level1 && bd.table == 0 && bd.mask_base >= 0 ? l1_seg : (int)dev::ENT_SEG;      // (table 1 keeps ENT_SEG: EntSegState::peaks)
+			int len = bd.level1 && bd.table == 0 && bd.mask_base >= 0 ? l1_seg : (int)dev::ENT_SEG;      // (table 1 keeps ENT_SEG: EntSegState::peaks)
+			if (rule && bd.table == 0 && !(bd.level1 && bd.mask_base >= 0 && rule->lists)) len = bd.level1 ? rule->l1_dense : (bd.level <= 2 ? rule->l2 : rule->l3);
 			j.nseg = (j.n + len - 1) / len; j.seg_base = (int)out->segjobs.size();
 			j.frame = f; j.hole = (int)h;
 			j.table = bd.table;
@@ -297,9 +308,10 @@ inline bool ent_build_band_jobs(const std::vector<EntHoleGeom> &geom, const Samp
 	out->nbands = (int)out->bands.size() / nframes;
 	return true;
 }
-inline bool ent_build_band_jobs(const FramePlan &plan, const SampleTemplate &t0, int nframes, int16_t *coeffs, size_t stride, EntHostJobs *out, int l1_seg = dev::ENT_SEG)
+inline bool ent_build_band_jobs(const FramePlan &plan, const SampleTemplate &t0, int nframes, int16_t *coeffs, size_t stride, EntHostJobs *out, int l1_seg = dev::ENT_SEG,
+                                const EntSegRule *rule = nullptr)
 {
-	return ent_build_band_jobs(ent_hole_geometry(plan, t0), t0, nframes, coeffs, stride, out, l1_seg);
+	return ent_build_band_jobs(ent_hole_geometry(plan, t0), t0, nframes, coeffs, stride, out, l1_seg, rule);
 }
 
 // Serialises frame f's template into one kEntTmplStride block: bytes | holes-in-front-of-word | EntHole[] | EntPatch[].

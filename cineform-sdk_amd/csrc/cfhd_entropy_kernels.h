@@ -28,7 +28,7 @@ namespace cfhd {
 namespace dev {
 
 // A segment = ENT_SEG = 1024 consecutive raster coefficients of a band = the work of one wave (16 coefficients per lane; 512 was measured
-// slower: the per-wave descriptor loads dominate) -- ENT_SEG_L1 on the sparse level-1 bands counted from block lists (below); four waves per
+// slower: the per-wave descriptor loads dominate) -- longer on the bands coded with table 0, by level and count kernel (ENT_SEG_L1 .. ENT_SEG_L3 below); four waves per
 // workgroup, no workgroup barriers in k_ent_count / k_ent_emit: all exchanges are wave-level (ballot / bpermute / shuffles).
 #ifndef CFHD_ENT_FILL
 #define CFHD_ENT_FILL 16384      // (the emulated tests build with a few words, so that trailers span many pieces)
@@ -52,9 +52,16 @@ enum { ENT_THREADS = 256, ENT_LANES = 64, ENT_WAVES = ENT_THREADS / ENT_LANES, E
        // ENT_SEG_MAX (EntSegJob::len; GpuEntropyEncoder::prepare_units, CFHD_AMD_L1_SEG).  The count kernels work a segment in windows of ENT_SEG token slots
        // (their LDS stays 4 x ENT_SEG words), k_ent_count_blocks deals out the listed blocks of ENT_BLK_SPAN coefficients at a time (8 blocks per lane).
        ENT_SEG_L1 = 4096, ENT_SEG_MAX = 8192, ENT_BLK_SPAN = 4096,
+       // Segments of the other bands coded with table 0, which k_ent_count counts densely (cfhd_entropy_jobs.h EntSegRule; CFHD_AMD_SEG_L1_DENSE, CFHD_AMD_SEG_L2,
+       // CFHD_AMD_SEG_L3): the level-1 bands of the inputs without block lists (RGB, Bayer, interlaced, two-frame groups), the bands of level 2, those of level 3.
+       // A band coded with table 1 keeps ENT_SEG (EntSegState::peaks).  Level 2 stops at 2048: at FILMSCAN1 its segments of 4096 coefficients code into more than
+       // ENT_LDS_WORDS words five times a 1080p frame and then take k_ent_emit's global atomics (2048: five times in 32 frames), and 4096 and 8192 measured slower.  Level 3
+       // (a tenth of the segments) measured the same at 1024 and 2048 and slower beyond: it keeps ENT_SEG.  Dense level 1: 4096 and 8192 measured alike.  profiles/r09_*.
+       ENT_SEG_L1_DENSE = 4096, ENT_SEG_L2 = 2048, ENT_SEG_L3 = 1024,
        // a complex token: run << ENT_REC_RUN_SHIFT | (value clamped to +-1023, 11 bits) << 6 | ENT_CODE_COMPLEX
        ENT_REC_RUN_SHIFT = 17 };
 static_assert(ENT_SEG_MAX - 1 < (1 << (32 - ENT_REC_RUN_SHIFT)), "the longest run inside a segment fits the token record's run field");
+static_assert(ENT_SEG_L1_DENSE % ENT_SEG == 0 && ENT_SEG_L2 % ENT_SEG == 0 && ENT_SEG_L3 % ENT_SEG == 0 && ENT_SEG_L1_DENSE <= ENT_SEG_MAX && ENT_SEG_L2 <= ENT_SEG_MAX && ENT_SEG_L3 <= ENT_SEG_MAX, "dense segments are whole token windows too");
 static_assert(ENT_SEG_L1 % ENT_SEG == 0 && ENT_SEG_MAX % ENT_SEG == 0 && ENT_BLK_SPAN % ENT_SEG == 0 && ENT_BLK_SPAN / 8 <= 8 * ENT_LANES, "segments are whole token windows; a span is 8 blocks per lane");
 // ENT_LDS_WORDS: 32-bit words of the per-wave bit window in LDS (a segment of 1024 coefficients of ordinary pictures codes into 10-40 words, one of the
 // level-1 segments of ENT_SEG_L1 into 20-200; beyond the window the code words go to the payload with global atomics).  1024 words = 8 bits per coefficient
@@ -89,7 +96,7 @@ struct EntSegJob {                 // static per segment: everything k_ent_count
 	int table;                     // entropy table of the band (EntBandJob::table); such a band is also the one that may need a peak table
 	int pitch;                     // coefficients per band row (k_ent_count_blocks: a level-1 band's chunks are cut row by row)
 	int mask_base;                 // the band's first chunk in a frame's mask array (FwdBlockLists::mask_base); -1: the band has no block lists
-	int len;                       // coefficients of the segment (ENT_SEG, or ENT_SEG_L1 on level-1 bands coded from block lists); the band's last one may end early
+	int len;                       // coefficients of the segment (a multiple of ENT_SEG up to ENT_SEG_MAX: ent_build_band_jobs(); ENT_SEG in a band coded with table 1); the band's last one may end early
 	int tok_base;                  // its first token slot in frame 0's part of `tokens` (a prefix of the segments' token slots: len rounded to whole ENT_TOK_STRIDE)
 };
 
@@ -321,7 +328,8 @@ __device__ __forceinline__ void ent_count_finish(int seg, const EntSegJob &job, 
 }
 
 // One segment of k_ent_count: the wave's loaded coefficients (the segment's first window) -> token strings in `tokens`, the segment's state in segs[seg]; a segment
-// longer than ENT_SEG is loaded, compacted and coded one window of ENT_SEG coefficients after the other.
+// longer than ENT_SEG is compacted and coded one window of ENT_SEG coefficients after the other, the next window's eight dwords per lane in flight meanwhile (as
+// k_ent_count_blocks fetches its next pass: a load at the top of each window had nothing in front of it to hide behind).
 // The picture is sparse (about one coefficient in twelve is nonzero), so the code lookups run over a compacted token list, one token per lane
 // and round.  Compaction is what this kernel's instructions went into while every lane held 16 consecutive coefficients (a count, a wave scan and
 // 16 predicated LDS stores per lane: VALU-bound at 1.7 ms).  With lane L holding the dwords j * 64 + L raster order is j-major, lane, low / high
@@ -335,7 +343,9 @@ __device__ __forceinline__ void ent_count_segment(int seg, const EntSegJob &job,
 	EntTokCarry c = ent_tok_carry();
 	const int span = job.n - job.first < job.len ? job.n - job.first : job.len;
 	for (int off = 0; off < span; off += ENT_SEG) {      // wave-uniform
-		if (off) ent_load_segment(job, lane, w, off);
+		const bool more = off + ENT_SEG < span;          // wave-uniform
+		uint32_t wn[ENT_SEG / 128];
+		if (more) ent_load_segment(job, lane, wn, off + ENT_SEG);
 		int nwin = 0;                                    // wave-uniform
 #pragma unroll
 		for (int j = 0; j < ENT_SEG / 128; j++) {
@@ -351,6 +361,10 @@ __device__ __forceinline__ void ent_count_segment(int seg, const EntSegJob &job,
 		if (CFHD_PROBE(probe) == 2) { const unsigned long long q = __ballot(s_tok[lane] == 0x12345u); if (lane == 0) { EntSegState &z = segs[seg]; z.first_nz = -1; z.last_nz = -1; z.bits = q == 0x123456789ull && nwin == 0x12345; z.ntok = 0; z.lead32 = 0; z.lead_valid = 0; } return; }
 		ent_count_window(job, T, nwin, lane, s_tok, tokens + tok_base, c, probe);
 		CFHD_WAVE_SYNC();                                // the next window reuses s_tok
+		if (more) {
+#pragma unroll
+			for (int j = 0; j < ENT_SEG / 128; j++) w[j] = wn[j];
+		}
 	}
 	ent_count_finish(seg, job, frame, tok_base, lane, c, segs, peak_flags);
 }
@@ -845,11 +859,13 @@ __device__ __forceinline__ void ent_emit_segment(const EntSegState &st, const En
 	if (st.run_size == (uint32_t)ENT_RUN_COMPLEX) ent_put_long_run(T, s_words, out, use_lds, first_word, seg_pos, (uint32_t)(st.first_nz - st.prev_nz - 1), 0);
 	else if (st.run_size && lane == 0) ent_put_string(s_words, out, use_lds, first_word, seg_pos, (uint64_t)st.run_code << (64u - st.run_size));
 	// 2. one token per lane and round: bit position by a wave scan over the lengths, the string OR-ed into the wave's LDS window
+	//    (the records of round r + 1 are fetched before round r is placed: a segment of ENT_SEG_L1 coefficients has a few rounds, each of which waited for its load)
 	uint64_t round_pos = seg_pos + st.run_bits;
+	uint32_t next_rec = first_rec;
 	for (int t = lane, t0 = 0; t0 < ntok; t0 += ENT_LANES, t += ENT_LANES) {
 		const bool have = t < ntok;
-		uint32_t rec = t0 == 0 ? first_rec : seg_str[have ? t : 0];
-		if (!have) rec = 0u;
+		uint32_t rec = have ? next_rec : 0u;
+		if (t0 + ENT_LANES < ntok) next_rec = seg_str[t + ENT_LANES < ntok ? t + ENT_LANES : 0];      // wave-uniform condition
 		uint32_t len = rec & 63u;
 		const bool complex = len == (uint32_t)ENT_CODE_COMPLEX;
 		uint32_t run = 0, ve = 0;
