@@ -82,6 +82,14 @@ int decoder_handle_state(void *ref, DecoderHandleState *out)
 	out->sample_cap = (size_t)d->plan.width * d->plan.height * pixel_bytes_of(d->out_kind) + 65536;
 	return 0;
 }
+int decoder_group_state(void *ref, DecoderGroupState *out)
+{
+	const Decoder *d = (const Decoder *)ref;
+	if (!d || !out || !d->prepared || !d->gop || !d->gop_ready) return -1;
+	out->plan = d->gplan; out->out_kind = d->out_kind; out->half = d->half;
+	return 0;
+}
+void decoder_group_reset(void *ref) { if (ref) ((Decoder *)ref)->gop_second = false; }
 }
 
 extern "C" {

@@ -11,6 +11,12 @@
 // those whose scan or colour-space tag differs from the first sample's, and -- when the band decoders' one error word is set after the pass -- every sample the parser
 // passed get their verdict and picture from it in wait ("every caller decodes alone and gets its own verdict", as DecodeService decides).  A pass of intact samples
 // launches nothing extra.
+//
+// A batch of two-frame groups (cfhd_amd_decode_batch_create_groups): entry 2 g of a pass is group sample g, entry 2 g + 1 the P-frame sample behind it, pictures 2 g
+// and 2 g + 1 the group's two frames.  The same pass with the group decoder's parts: k_dec_ingest places group g in a slot of the handle's capacity and its follower
+// in a small slot behind the group slots (the table names every entry's slot: groups in front, followers behind them)  ->  k_dec_parse_group with a verdict per
+// group and per follower  ->  the band decoder (k_dec_band_two_pass for subband 7 of the groups from 8-bit RGB sources), k_dec_lowpass  ->  GopBatch's inverse
+// stages  ->  k_dec_blank over pairs.  A pair is judged alone: the slow handle forgets its last group in front of every pair it is given.
 #include "../../include/cfhd_amd.h"
 #include "cfhd_core.h"
 #include "cfhd_bitstream.h"
@@ -47,6 +53,10 @@ struct cfhd_amd_decode_batch {
 	int n = 0, device = 0;
 	DecoderHandleState st;
 	DecodeBatch dec;
+	// a batch of two-frame groups: n = 2 ngroups samples, decoded by gdec; group g is table entry g, its follower entry ngroups + g (entry_of)
+	bool groups = false; int ngroups = 0; GopBatch gdec; DecoderGroupState gst;
+	uint8_t *d_slots = nullptr; size_t group_cap = 0; char band_name[96] = "";
+	enum { kFollowerCap = 1024 };            // the slot of a P-frame sample (24 bytes as the encoders write it); a longer one is the slow path's
 	CFHD_DecoderRef slow = nullptr;          // the handle create prepared on the first sample: the gates, and the slow path of wait
 	void *scope_stream = nullptr;            // the batch's one stream (StreamScope): released behind the decoder
 	// the samples on their way in: the blob in HBM (+ the pinned buffer plain memory is packed into), the table k_dec_ingest reads, what it and the parser write
@@ -65,15 +75,35 @@ struct cfhd_amd_decode_batch {
 	unsigned long long *table_src() const { return (unsigned long long *)h_table; }
 	uint32_t *table_size() const { return (uint32_t *)(h_table + 8 * (size_t)n); }
 	uint32_t *table_first() const { return (uint32_t *)(h_table + 12 * (size_t)n); }
-	dev::DecIngestTable device_table() const { return dev::DecIngestTable{ (const unsigned long long *)d_table, (const uint32_t *)(d_table + 8 * (size_t)n), (const uint32_t *)(d_table + 12 * (size_t)n) }; }
+	// (groups: the entries' slots behind the intra table -- offsets from d_slots, capacities)
+	size_t table_dst_at() const { return (16 * (size_t)n + 4 + 7) & ~(size_t)7; }
+	unsigned long long *table_dst() const { return (unsigned long long *)(h_table + table_dst_at()); }
+	uint32_t *table_cap() const { return (uint32_t *)(h_table + table_dst_at() + 8 * (size_t)n); }
+	dev::DecIngestTable device_table() const
+	{
+		return dev::DecIngestTable{ (const unsigned long long *)d_table, (const uint32_t *)(d_table + 8 * (size_t)n), (const uint32_t *)(d_table + 12 * (size_t)n),
+		                            groups ? (const unsigned long long *)(d_table + table_dst_at()) : nullptr, groups ? (const uint32_t *)(d_table + table_dst_at() + 8 * (size_t)n) : nullptr };
+	}
 	uint32_t clean_word() const { return dev::dec_verdict_word(0, st.progressive_flag, st.color_space); }
+	// sample i of a pass: its table entry, the capacity of its slot; the decoder behind the batch
+	int entry_of(int i) const { return groups ? ((i & 1) ? ngroups + (i >> 1) : (i >> 1)) : i; }
+	size_t cap_of(int i) { return groups ? ((i & 1) ? (size_t)kFollowerCap : group_cap) : dec.entropy().slot_bytes(); }
+	size_t slots_bytes() { return groups ? (size_t)ngroups * (group_cap + kFollowerCap) : dec.entropy().slot_bytes() * (size_t)n; }
+	void *stream() { return groups ? gdec.stream() : dec.stream(); }
+	int wait_stream() { return groups ? gdec.wait() : dec.wait(); }
+	int picture_pitch() const { return groups ? gdec.picture_pitch() : dec.picture_pitch(); }
+	int picture_rows() const { return groups ? gdec.picture_rows() : dec.picture_rows(); }
+	size_t picture_bytes() const { return groups ? gdec.picture_bytes() : dec.picture_bytes(); }
+	uint8_t *device_pictures() const { return groups ? gdec.device_pictures() : dec.device_pictures(); }
+	int finish_frame(int i, void *out, int pitch) { return groups ? gdec.finish_frame(i, out, pitch) : dec.finish_frame(i, out, pitch); }
+	int download_frame(int i, void *out, int pitch) { return groups ? gdec.download_frame(i, out, pitch) : dec.download_frame(i, out, pitch); }
 	~cfhd_amd_decode_batch()
 	{
 		(void)hipSetDevice(device);
-		dec.release();
+		dec.release(); gdec.release();
 		if (scope_stream) device_stream_release(scope_stream);
 		for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-		void *dv[] = { d_blob, d_table, d_sizes, d_verdicts }; for (void *p : dv) if (p) (void)hipFree(p);
+		void *dv[] = { d_blob, d_table, d_sizes, d_verdicts, d_slots }; for (void *p : dv) if (p) (void)hipFree(p);
 		void *hv[] = { h_blob, h_table, h_verdicts }; for (void *p : hv) if (p) (void)hipHostFree(p);
 		if (slow) (void)CFHD_CloseDecoder(slow);
 	}
@@ -82,9 +112,9 @@ struct cfhd_amd_decode_batch {
 namespace {
 int allocate(cfhd_amd_decode_batch *b)
 {
-	const size_t cap = b->dec.entropy().slot_bytes();
-	b->blob_cap = cap * (size_t)b->n + 32;               // a pass's samples fit whatever their alignment; a registered span with wider gaps is packed like plain memory
-	b->table_bytes = 12 * (size_t)b->n + 4 * ((size_t)b->n + 1);
+	b->blob_cap = b->slots_bytes() + 32;                 // a pass's samples fit whatever their alignment; a registered span with wider gaps is packed like plain memory
+	b->table_bytes = b->groups ? b->table_dst_at() + 12 * (size_t)b->n : 12 * (size_t)b->n + 4 * ((size_t)b->n + 1);
+	if (b->groups) HIPCHK(hipMalloc((void **)&b->d_slots, b->slots_bytes()));
 	HIPCHK(hipMalloc((void **)&b->d_blob, b->blob_cap));
 	HIPCHK(hipMalloc((void **)&b->d_table, b->table_bytes));
 	HIPCHK(hipHostMalloc((void **)&b->h_table, b->table_bytes, hipHostMallocPortable));
@@ -97,11 +127,47 @@ int allocate(cfhd_amd_decode_batch *b)
 	return 0;
 }
 
+// The same for a batch of two-frame groups: blob + table_src()[entry_of(i)] is sample i.  The table covers every entry of the batch -- those behind the pass are
+// empty --, the decoder the count / 2 groups of the pass.
+int launch_group_pass(cfhd_amd_decode_batch *b, const uint8_t *blob)
+{
+	hipStream_t st = (hipStream_t)b->stream();
+	const int n = b->n, ng = b->ngroups;
+	for (int j = 0; j < n; j++) b->table_size()[j] = 0u;
+	for (int i = 0; i < b->count; i++) b->table_size()[b->entry_of(i)] = b->sizes[i];
+	uint32_t pieces = 0;
+	for (int j = 0; j < n; j++) {
+		const bool follower = j >= ng;
+		b->table_dst()[j] = follower ? (size_t)ng * b->group_cap + (size_t)(j - ng) * cfhd_amd_decode_batch::kFollowerCap : (size_t)j * b->group_cap;
+		b->table_cap()[j] = (uint32_t)(follower ? (size_t)cfhd_amd_decode_batch::kFollowerCap : b->group_cap);
+		b->table_first()[j] = pieces; pieces += dev::dec_ingest_pieces(b->table_size()[j], b->table_cap()[j]);
+	}
+	b->table_first()[n] = pieces;
+	HIPCHK(hipMemcpyAsync(b->d_table, b->h_table, b->table_bytes, hipMemcpyHostToDevice, st));
+	b->gdec.set_active(b->count / 2);
+	HIPCHK(hipEventRecord(b->ev[0], st));
+	dev::k_dec_ingest<<<pieces ? pieces : 1u, dev::DEC_INGEST_THREADS, 0, st>>>(blob, b->device_table(), n, b->d_slots, b->group_cap, b->d_sizes, b->d_verdicts + n);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(b->ev[1], st));
+	// (the dither seed of pass k: as the intra batches')
+	if (b->gdec.batch_entropy().launch() || b->gdec.launch_inverse(0xA511E9B3u * (b->steps + 1), true)) return -5;
+	HIPCHK(hipEventRecord(b->ev[2], st));
+	dev::k_dec_blank<<<dim3(dev::DEC_BLANK_SPLIT, (unsigned)b->count), dev::DEC_BLANK_THREADS, 0, st>>>(b->d_verdicts, b->d_verdicts + n, b->clean_word(), b->gdec.device_pictures(), b->gdec.picture_bytes(),
+	                                                                                                      b->gdec.picture_pitch(), b->gdec.picture_pitch(), b->gdec.picture_rows(), ng);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(b->ev[3], st));
+	b->timed = true;
+	HIPCHK(hipMemcpyAsync(b->h_verdicts, b->d_verdicts, 8 * (size_t)n, hipMemcpyDeviceToHost, st));
+	if (b->host_out && b->gdec.download_frames(b->host_out, b->host_out_stride, b->host_out_pitch)) return -5;
+	return 0;
+}
+
 // Everything of a pass behind the samples' arrival in HBM, queued on the batch's stream: blob + table_src()[i] is sample i.  No host wait.
 int launch_pass(cfhd_amd_decode_batch *b, const uint8_t *blob)
 {
 	(void)hipSetDevice(b->device);
-	hipStream_t st = (hipStream_t)b->dec.stream();
+	hipStream_t st = (hipStream_t)b->stream();
+	if (b->groups) return launch_group_pass(b, blob);
 	const size_t cap = b->dec.entropy().slot_bytes();
 	uint32_t pieces = 0;
 	for (int i = 0; i < b->count; i++) { b->table_size()[i] = b->sizes[i]; b->table_first()[i] = pieces; pieces += dev::dec_ingest_pieces(b->sizes[i], cap); }
@@ -146,7 +212,7 @@ cfhd_amd_decode_batch *cfhd_amd_decode_batch_create(const void *first_sample, si
 	{ const char *e = getenv("CFHD_AMD_ENTROPY"); if (e && strcmp(e, "host") == 0) { refuse("decode queue: CFHD_AMD_ENTROPY=host keeps the entropy stage on the host (the C ABI's arrangement)"); return nullptr; } }
 	const uint8_t *s8 = (const uint8_t *)first_sample;
 	const int first_tag = (int16_t)((s8[0] << 8) | s8[1]), sample_type = (s8[2] << 8) | s8[3];
-	if (first_tag == TAG_SAMPLE && (sample_type == 7 || sample_type == 2 || sample_type == 1)) { refuse("decode queue: two-frame groups (group samples, P-frame samples, sequence headers) are decoded by CFHD_DecodeSample"); return nullptr; }
+	if (first_tag == TAG_SAMPLE && (sample_type == 7 || sample_type == 2 || sample_type == 1)) { refuse("decode queue: two-frame groups (group samples, P-frame samples, sequence headers) are decoded by cfhd_amd_decode_batch_create_groups or CFHD_DecodeSample"); return nullptr; }
 	ParsedSample ps;
 	const int parsed = parse_sample(s8, first_size, &ps);
 	const bool uncompressed = ps.uncompressed;           // (an UNCOMPRESS chunk: CFHD_PrepareToDecode refuses below with its own text)
@@ -195,6 +261,73 @@ cfhd_amd_decode_batch *cfhd_amd_decode_batch_create(const void *first_sample, si
 	return b;
 }
 
+cfhd_amd_decode_batch *cfhd_amd_decode_batch_create_groups(const void *first_group_sample, size_t first_size, uint32_t output_format, int decoded_resolution, int ngroups)
+{
+	CallerDevice caller_device;
+	if (!first_group_sample || first_size < 4) { refuse("decode queue: no first group sample"); return nullptr; }
+	if (ngroups < 1) { refuse("decode queue: ngroups < 1"); return nullptr; }
+	{ const char *e = getenv("CFHD_AMD_ENTROPY"); if (e && strcmp(e, "host") == 0) { refuse("decode queue: CFHD_AMD_ENTROPY=host keeps the entropy stage on the host (the C ABI's arrangement)"); return nullptr; } }
+	const uint8_t *s8 = (const uint8_t *)first_group_sample;
+	const int first_tag = (int16_t)((s8[0] << 8) | s8[1]), sample_type = (s8[2] << 8) | s8[3];
+	if (first_tag != TAG_SAMPLE || sample_type != 2) {
+		refuse(first_tag == TAG_SAMPLE && sample_type == 7 ? "decode queue: a batch of groups is prepared on a group sample, not on the sequence header (a reader skips it)"
+		       : first_tag == TAG_SAMPLE && sample_type == 1 ? "decode queue: a batch of groups is prepared on a group sample, not on the P-frame sample behind one"
+		       : "decode queue: a batch of groups is prepared on a group sample; intra samples go to cfhd_amd_decode_batch_create");
+		return nullptr;
+	}
+	// (k_dec_lowpass and the plane transforms carry group x 6 jobs in a grid dimension: GpuGroupBatchEntropyDecoder::prepare, GopBatch::prepare)
+	if (6LL * ngroups > 65535) { refuse("decode queue: the batch's job index would pass the grid limit (65 535)"); return nullptr; }
+	cfhd_amd_decode_batch *b = new (std::nothrow) cfhd_amd_decode_batch;
+	if (!b) return nullptr;
+	b->groups = true; b->ngroups = ngroups; b->n = 2 * ngroups;
+	auto fail = [&](const char *text) { if (text) device_set_last_error(text); delete b; return (cfhd_amd_decode_batch *)nullptr; };
+	// the handle's gates, as cfhd_amd_decode_batch_create: CFHD_PrepareToDecode on the group sample, then that sample through CFHD_DecodeSample once (the scan is only known there)
+	char text[200];
+	if (CFHD_OpenDecoder(&b->slow, nullptr) != ERR_OKAY) return fail("decode queue: no decoder handle");
+	int aw = 0, ah = 0; CFHD_PixelFormat af = 0; int32_t pitch = 0;
+	int rc = CFHD_PrepareToDecode(b->slow, 0, 0, output_format, decoded_resolution, 0, (void *)first_group_sample, first_size, &aw, &ah, &af);
+	if (rc != ERR_OKAY) { snprintf(text, sizeof(text), "decode queue: CFHD_PrepareToDecode refuses this sample, output and resolution (CFHD_Error %d)", rc); return fail(text); }
+	if (CFHD_GetImagePitch((uint32_t)aw, af, &pitch) != ERR_OKAY || pitch <= 0 || ah <= 0) return fail("decode queue: no picture geometry");
+	{
+		std::vector<uint8_t> scratch((size_t)pitch * ah);
+		device_set_last_error("");
+		rc = CFHD_DecodeSample(b->slow, (void *)first_group_sample, first_size, scratch.data(), pitch);
+		if (rc != ERR_OKAY) {
+			if (*device_last_error()) return fail(nullptr);      // (the device layer said why)
+			snprintf(text, sizeof(text), "decode queue: CFHD_DecodeSample refuses this sample, output and resolution (CFHD_Error %d)", rc); return fail(text);
+		}
+	}
+	if (decoder_group_state(b->slow, &b->gst)) return fail("decode queue: the first sample is not a group sample");
+	{
+		// what the verdict of a clean group of the prepared kind carries, and the matrix of the outputs that convert to RGB (decode_group_sample)
+		ParsedGroup pg;
+		if (parse_group_sample(s8, first_size, &pg) != 0) return fail("decode queue: the first sample is not a group sample");
+		b->st.progressive_flag = pg.progressive != 0; b->st.color_space = pg.color_space; b->st.interlaced = b->gst.plan.interlaced; b->st.half = b->gst.half; b->st.out_kind = b->gst.out_kind;
+	}
+	const GopPlan &gp = b->gst.plan;
+	b->group_cap = ((size_t)gp.width * gp.display_height * 8 + 131072 + 255) & ~(size_t)255;      // the handle's (decode_group_sample)
+	struct Lean { Lean() { device_streams_lean(true); } ~Lean() { device_streams_lean(false); } } lean;
+	{
+		StreamScope scope;
+		int prc = b->gdec.prepare(gp, true, b->gst.out_kind, b->gst.half, ngroups);
+		b->scope_stream = scope.stream();
+		if (prc) return fail(nullptr);
+		prc = b->gdec.prepare_entropy_decode();
+		if (prc < 0) return fail("decode queue: the device stage does not take groups of this geometry (CFHD_DecodeSample decodes them)");
+		if (prc) return fail("decode queue: out of device or pinned memory");
+	}
+	b->device = device_current();
+	b->gdec.set_color_matrix((b->st.color_space & 3) == 1 ? 2 : 0);
+	b->gdec.set_timed(true);
+	if (allocate(b)) return fail("decode queue: out of device or pinned memory");
+	GpuGroupBatchEntropyDecoder &ent = b->gdec.batch_entropy();
+	if (ent.set_samples_slots(b->d_slots, b->group_cap, b->d_sizes, b->d_slots + (size_t)ngroups * b->group_cap, cfhd_amd_decode_batch::kFollowerCap, b->d_sizes + ngroups)) return fail("decode queue: sample slots");
+	ent.set_verdicts(b->d_verdicts);
+	snprintf(b->band_name, sizeof(b->band_name), "%s%s+k_dec_band_two_pass", ent.band_kernel(), gp.interlaced ? "+k_dec_undiff" : "");
+	b->slow_pictures.resize((size_t)b->n);
+	return b;
+}
+
 void cfhd_amd_decode_batch_destroy(cfhd_amd_decode_batch *b)
 {
 	CallerDevice caller_device;
@@ -205,45 +338,47 @@ void cfhd_amd_decode_batch_destroy(cfhd_amd_decode_batch *b)
 int cfhd_amd_decode_batch_geometry(cfhd_amd_decode_batch *b, int *width, int *height, int *row_bytes)
 {
 	if (!b || b->in_flight) return -1;
-	if (width) *width = b->st.half ? b->st.plan.width / 2 : b->st.plan.width;
-	if (height) *height = b->dec.picture_rows();
-	if (row_bytes) *row_bytes = b->dec.picture_pitch();
+	const int full_width = b->groups ? b->gst.plan.width : b->st.plan.width;
+	if (width) *width = (b->groups ? b->gst.half : b->st.half) ? full_width / 2 : full_width;
+	if (height) *height = b->picture_rows();
+	if (row_bytes) *row_bytes = b->picture_pitch();
 	return 0;
 }
 
 int cfhd_amd_decode_batch_submit_host(cfhd_amd_decode_batch *b, const void *base, const size_t *offsets, const size_t *sizes, int count, void *pictures, size_t picture_stride, int picture_pitch)
 {
 	CallerDevice caller_device;
-	if (!b || b->in_flight || !base || !offsets || !sizes || count < 1 || count > b->n) return -1;
-	if (pictures && (picture_pitch < b->dec.picture_pitch() || picture_stride < (size_t)picture_pitch * (size_t)(b->dec.picture_rows() - 1) + (size_t)b->dec.picture_pitch())) return -1;
+	if (!b || b->in_flight || !base || !offsets || !sizes || count < 1 || count > b->n || (b->groups && (count & 1))) return -1;
+	if (pictures && (picture_pitch < b->picture_pitch() || picture_stride < (size_t)picture_pitch * (size_t)(b->picture_rows() - 1) + (size_t)b->picture_pitch())) return -1;
 	(void)hipSetDevice(b->device);
-	const size_t cap = b->dec.entropy().slot_bytes();
 	begin_pass(b, offsets, sizes, count);
 	const std::vector<uint32_t> &size = b->sizes;
+	auto placed = [&](int i) { return dev::dec_ingest_pieces(size[i], b->cap_of(i)) != 0; };      // sample i is one k_dec_ingest copies
 	size_t lo = ~(size_t)0, hi = 0;                        // the span of the samples k_dec_ingest will place
 	for (int i = 0; i < count; i++)
-		if (dev::dec_ingest_pieces(size[i], cap)) { if (offsets[i] < lo) lo = offsets[i]; if (offsets[i] + sizes[i] > hi) hi = offsets[i] + sizes[i]; }
+		if (placed(i)) { if (offsets[i] < lo) lo = offsets[i]; if (offsets[i] + sizes[i] > hi) hi = offsets[i] + sizes[i]; }
 	b->src_host = (const uint8_t *)base; b->src_device = nullptr;
 	b->host_out = (uint8_t *)pictures; b->host_out_stride = picture_stride; b->host_out_pitch = picture_pitch;
-	hipStream_t st = (hipStream_t)b->dec.stream();
+	hipStream_t st = (hipStream_t)b->stream();
 	int rc = 0;
+	if (b->groups) for (int j = 0; j < b->n; j++) b->table_src()[j] = 0;      // (the entries behind a short pass)
 	if (hi <= lo) {                                        // nothing to copy: every sample is empty or the slow path's
-		for (int i = 0; i < count; i++) b->table_src()[i] = 0;
+		for (int i = 0; i < count; i++) b->table_src()[b->entry_of(i)] = 0;
 	} else if (hi - lo <= b->blob_cap - 32 && host_buffer_is_registered((const uint8_t *)base + lo, hi - lo)) {
 		// a registered blob: one DMA of the span as it lies, k_dec_ingest aligns
-		for (int i = 0; i < count; i++) b->table_src()[i] = dev::dec_ingest_pieces(size[i], cap) ? offsets[i] - lo : 0;
+		for (int i = 0; i < count; i++) b->table_src()[b->entry_of(i)] = placed(i) ? offsets[i] - lo : 0;
 		if (hipMemcpyAsync(b->d_blob, (const uint8_t *)base + lo, hi - lo, hipMemcpyHostToDevice, st) != hipSuccess) rc = -2;
 	} else {
 		// plain memory (or a span with gaps wider than the batch's buffer): the calling thread packs the samples back to back into pinned memory -- the only host
 		// work of a pass, in front of its first launch --, then the same DMA and the same kernel
 		size_t at = 0;
 		if (!b->h_blob && hipHostMalloc((void **)&b->h_blob, b->blob_cap, hipHostMallocPortable) != hipSuccess) { (void)hipGetLastError(); b->h_blob = nullptr; end_pass(b); device_set_last_error("decode queue: no pinned memory to stage the samples"); return -2; }
-		for (int i = 0; i < count; i++) { b->table_src()[i] = at; if (dev::dec_ingest_pieces(size[i], cap)) at += size[i]; }
-		parallel_for(count, count > 8 ? 8 : 1, [&](int i) { if (dev::dec_ingest_pieces(size[i], cap)) memcpy(b->h_blob + b->table_src()[i], (const uint8_t *)base + offsets[i], size[i]); });
+		for (int i = 0; i < count; i++) { b->table_src()[b->entry_of(i)] = at; if (placed(i)) at += size[i]; }
+		parallel_for(count, count > 8 ? 8 : 1, [&](int i) { if (placed(i)) memcpy(b->h_blob + b->table_src()[b->entry_of(i)], (const uint8_t *)base + offsets[i], size[i]); });
 		if (at && hipMemcpyAsync(b->d_blob, b->h_blob, at, hipMemcpyHostToDevice, st) != hipSuccess) rc = -2;
 	}
 	if (!rc) rc = launch_pass(b, b->d_blob);
-	if (rc) { (void)b->dec.wait(); end_pass(b); return rc < 0 ? rc : -2; }
+	if (rc) { (void)b->wait_stream(); end_pass(b); return rc < 0 ? rc : -2; }
 	b->in_flight = true;
 	return 0;
 }
@@ -251,14 +386,15 @@ int cfhd_amd_decode_batch_submit_host(cfhd_amd_decode_batch *b, const void *base
 int cfhd_amd_decode_batch_submit_device(cfhd_amd_decode_batch *b, const void *d_base, size_t span_bytes, const size_t *offsets, const size_t *sizes, int count)
 {
 	CallerDevice caller_device;
-	if (!b || b->in_flight || !d_base || !offsets || !sizes || count < 1 || count > b->n) return -1;
+	if (!b || b->in_flight || !d_base || !offsets || !sizes || count < 1 || count > b->n || (b->groups && (count & 1))) return -1;
 	for (int i = 0; i < count; i++) if (offsets[i] > span_bytes || sizes[i] > span_bytes - offsets[i]) return -1;      // a sample outside the span the caller vouched for
 	(void)hipSetDevice(b->device);
 	begin_pass(b, offsets, sizes, count);
 	b->src_host = nullptr; b->src_device = (const uint8_t *)d_base; b->host_out = nullptr;
-	for (int i = 0; i < count; i++) b->table_src()[i] = offsets[i];
+	if (b->groups) for (int j = 0; j < b->n; j++) b->table_src()[j] = 0;
+	for (int i = 0; i < count; i++) b->table_src()[b->entry_of(i)] = offsets[i];
 	const int rc = launch_pass(b, (const uint8_t *)d_base);
-	if (rc) { (void)b->dec.wait(); end_pass(b); return rc < 0 ? rc : -2; }
+	if (rc) { (void)b->wait_stream(); end_pass(b); return rc < 0 ? rc : -2; }
 	b->in_flight = true;
 	return 0;
 }
@@ -270,7 +406,7 @@ int cfhd_amd_decode_batch_wait(cfhd_amd_decode_batch *b, CFHD_Error *status)
 	(void)hipSetDevice(b->device);
 	const int n = b->n, count = b->count;
 	auto device_failure = [&](int code) { if (status) for (int i = 0; i < count; i++) status[i] = ERR_INTERNAL; end_pass(b); return code; };
-	if (b->dec.wait()) return device_failure(-2);
+	if (b->wait_stream()) return device_failure(-2);
 	if (b->timed) {
 		b->timed = false;
 		if (hipEventElapsedTime(&b->ingest_ms, b->ev[0], b->ev[1]) != hipSuccess) { (void)hipGetLastError(); b->ingest_ms = 0; }
@@ -278,20 +414,28 @@ int cfhd_amd_decode_batch_wait(cfhd_amd_decode_batch *b, CFHD_Error *status)
 	}
 	if (b->host_out) {                                     // (pictures staged through pinned memory -- a plain buffer -- leave it on a few threads side by side; nothing to do for a registered one)
 		std::atomic<int> bad(0);
-		parallel_for(count, count > 8 ? 8 : 1, [&](int i) { if (b->dec.finish_frame(i, b->host_out + b->host_out_stride * (size_t)i, b->host_out_pitch)) bad.store(1); });
+		parallel_for(count, count > 8 ? 8 : 1, [&](int i) { if (b->finish_frame(i, b->host_out + b->host_out_stride * (size_t)i, b->host_out_pitch)) bad.store(1); });
 		if (bad.load()) return device_failure(-2);
 	}
 	// the verdicts.  Final on the spot: a sample the parser refused (malformed, geometry, encoded format or channel count, bands missing) while its scan flag is the
 	// prepared one -- CFHD_ERROR_BADSAMPLE, its picture already zeroed by k_dec_blank.  The slow path: what k_dec_ingest marked, what only the host parser judges, a
 	// scan flag or colour-space tag other than the first sample's, and -- the band decoders' error word is one for the pass -- every sample the parser passed.
-	const bool stream_damage = b->dec.entropy().check() != 0;
+	const bool stream_damage = (b->groups ? b->gdec.batch_entropy().check() : b->dec.entropy().check()) != 0;
 	const uint32_t clean = b->clean_word();
-	const int picture_pitch = b->dec.picture_pitch(); const size_t picture_bytes = b->dec.picture_bytes();
+	const int picture_pitch = b->picture_pitch(); const size_t picture_bytes = b->picture_bytes();
 	std::vector<uint8_t> bytes;
 	int decoded = 0, failure = 0;
 	for (int i = count; i < n; i++) b->slow_pictures[i].clear();      // (a short pass: what an earlier pass left behind its count is that pass's picture in HBM again)
 	for (int i = 0; i < count; i++) {
-		const uint32_t v = b->h_verdicts[i], mark = b->h_verdicts[n + i];
+		uint32_t v = b->h_verdicts[i], mark = b->h_verdicts[n + i];
+		if (b->groups) {
+			// a pair is judged alone and as one, entry 2 g and entry 2 g + 1 alike: final where both samples were placed, the follower is a clean P-frame sample and
+			// the group is clean -- both OKAY -- or failed the parser for a reason the handle calls a bad sample -- both BADSAMPLE: a follower without its group has
+			// no picture on the handle either --; the slow handle, which forgets its last group in front of the pair, otherwise
+			const int g = i >> 1, ng = b->ngroups;
+			v = b->h_verdicts[g]; mark = b->h_verdicts[n + g] | b->h_verdicts[n + ng + g] | b->h_verdicts[ng + g];
+			if (!(i & 1)) decoder_group_reset(b->slow);
+		}
 		const int reason = (int)(v & 0xffu);
 		const bool scan_as_prepared = ((v >> 8) & 1u) == (b->st.progressive_flag ? 1u : 0u);
 		b->slow_pictures[i].clear();
@@ -310,7 +454,7 @@ int cfhd_amd_decode_batch_wait(cfhd_amd_decode_batch *b, CFHD_Error *status)
 			// device stage left in HBM
 			b->slow_pictures[i].assign(picture_bytes, 0);
 			rc = failure ? ERR_INTERNAL : CFHD_DecodeSample(b->slow, (void *)s, size, b->slow_pictures[i].data(), picture_pitch);
-			if (b->host_out) for (int r = 0; r < b->dec.picture_rows(); r++)
+			if (b->host_out) for (int r = 0; r < b->picture_rows(); r++)
 				memcpy(b->host_out + b->host_out_stride * (size_t)i + (size_t)r * b->host_out_pitch, b->slow_pictures[i].data() + (size_t)r * picture_pitch, (size_t)picture_pitch);
 			(void)hipSetDevice(b->device);
 		}
@@ -325,23 +469,26 @@ int cfhd_amd_decode_batch_wait(cfhd_amd_decode_batch *b, CFHD_Error *status)
 int cfhd_amd_decode_batch_download_output(cfhd_amd_decode_batch *b, int i, void *out, int pitch)
 {
 	CallerDevice caller_device;
-	if (!b || b->in_flight || i < 0 || i >= b->n || !out || pitch < b->dec.picture_pitch()) return -1;
-	const int rows = b->dec.picture_rows(), row_bytes = b->dec.picture_pitch();
+	if (!b || b->in_flight || i < 0 || i >= b->n || !out || pitch < b->picture_pitch()) return -1;
+	const int rows = b->picture_rows(), row_bytes = b->picture_pitch();
 	if (!b->slow_pictures[i].empty()) {                    // decoded by the slow path of the last pass
 		for (int r = 0; r < rows; r++) memcpy((uint8_t *)out + (size_t)r * pitch, b->slow_pictures[i].data() + (size_t)r * row_bytes, (size_t)row_bytes);
 		return 0;
 	}
-	if (b->dec.download_frame(i, out, pitch) || b->dec.wait()) return -2;
-	return b->dec.finish_frame(i, out, pitch);
+	if (b->download_frame(i, out, pitch) || b->wait_stream()) return -2;
+	return b->finish_frame(i, out, pitch);
 }
 
 // which: 0 k_dec_ingest, 1 k_dec_parse, 2 the band decoder (all its kernels), 3 k_dec_lowpass, 4 / 5 / 6 the transform levels in launch order (wavelet 3, wavelet 2, the
 // last level + output conversion), 7 k_dec_blank (ms of the last pass, HIP events on the batch's stream)
 float cfhd_amd_decode_batch_kernel_ms(cfhd_amd_decode_batch *b, int which)
 {
-	if (!b || b->in_flight || which < 0 || which > 7) return 0;
+	if (!b || b->in_flight || which < 0 || which > (b->groups ? 8 : 7)) return 0;
 	if (which == 0) return b->ingest_ms;
 	if (which == 7) return b->blank_ms;
+	// a batch of groups: 1 k_dec_parse_group, 2 the band decoder (every kernel of it), 3 k_dec_lowpass, 4 / 5 / 6 GopBatch's inverse stages in launch order (the top wavelet;
+	// the two middle wavelets + the temporal step; the last level of all frames + the output conversion), and 8: k_dec_band_two_pass alone
+	if (b->groups) return which == 8 ? b->gdec.batch_entropy().kernel_ms(3) : (which < 4 ? b->gdec.batch_entropy().kernel_ms(which - 1) : b->gdec.stage_ms(6 - which));
 	if (which < 4) return b->dec.entropy().kernel_ms(which - 1);
 	return b->dec.last_level_ms(6 - which);
 }
@@ -350,8 +497,9 @@ const char *cfhd_amd_decode_batch_kernel_name(cfhd_amd_decode_batch *b, int whic
 {
 	if (!b || b->in_flight || which < 0 || which > 7) return "";
 	static const char *const fixed[4] = { "k_dec_ingest", "k_dec_parse", "k_dec_plan+k_dec_index+k_dec_chain+k_dec_tiles", "k_dec_lowpass" };
-	if (which < 4) return fixed[which];
+	if (which < 4 && !(b->groups && which)) return fixed[which];
 	if (which == 7) return "k_dec_blank";
+	if (b->groups) return which == 1 ? "k_dec_parse_group" : (which == 2 ? b->band_name : (which == 3 ? fixed[3] : b->gdec.stage_kernel(6 - which)));
 	return b->dec.level_kernel(6 - which);
 }
 

@@ -176,7 +176,7 @@ private:
 // 2 n frames -- from every input that encodes to 4:2:2 --, the plane transforms of the three spatial wavelets) around the temporal step, forward for the encoder and
 // inverse for the decoder, one launch per stage whatever n is (the job tables are n times as long, the job index stays in blockIdx.y / z).  The run-length / VLC stage
 // runs on the device too: GpuEntropyEncoder::prepare_group codes the n group samples, the decoder of a batch parses and decodes them where the coder left them
-// (GpuGroupBatchEntropyDecoder), the C ABI's decoder takes one host-parsed sample (GpuGroupEntropyDecoder); the host writer / host VLC decoder remain for what the device
+// (GpuGroupBatchEntropyDecoder), the decode queue brings group samples of any encoder in slots of their own (cfhd_decode_queue.hip), the C ABI's decoder takes one host-parsed sample (GpuGroupEntropyDecoder); the host writer / host VLC decoder remain for what the device
 // stage hands back (write_group_sample / vlc_decode_band: the pyramid crosses PCIe then).
 class GopBatch {
 public:
@@ -210,10 +210,17 @@ public:
 	// a batch of groups whose samples lie in HBM (the coder's dense buffer): parsed and decoded there, nothing touches the host; then launch_inverse(seed, true)
 	int prepare_entropy_decode();
 	GpuGroupBatchEntropyDecoder &batch_entropy() { return bdec_; }
+	// the next launches of the decoder (batch_entropy().launch(), launch_inverse(), download_frames()) cover groups 0 .. k-1 only (0 = all): pictures 0 .. 2 k - 1
+	void set_active(int k) { active_ = k; bdec_.set_active(k); }
+	// the decoded pictures in HBM, for a kernel queued behind launch_inverse() on stream() (the decode queue's k_dec_blank): picture f at device_pictures() + f * picture_bytes()
+	uint8_t *device_pictures() const { return d_frames_; }
+	size_t picture_bytes() const { return frame_bytes_; }
+	int picture_pitch() const { return pitch_; }
+	int picture_rows() const { return rows_; }
 	int16_t *device_coeffs() { return d_coeff_; }
 	void *stream() { return stream_; }
 	int device() const { return device_; }
-	int download_frames(void *out, size_t frame_stride, int pitch_bytes);      // all 2 n frames (finish_frame() for each behind wait())
+	int download_frames(void *out, size_t frame_stride, int pitch_bytes);      // all 2 n frames -- the first 2 k after set_active(k) -- (finish_frame() for each behind wait())
 	// HIP-event times of the last launch_forward() / launch_inverse() once the stream was synchronised, and the kernels behind them.  Forward: 0 level 1 of all frames,
 	// 1 temporal step + the two middle wavelets, 2 the top wavelet.  Inverse: 0 last level of all frames (+ output conversion), 1 the two middle wavelets + temporal
 	// step, 2 the top wavelet.  set_timed(true) before the launches (the C ABI's handles record no events).
@@ -229,7 +236,8 @@ private:
 	void fill_jobs();
 	GopRoute route() const;                          // decoder: output_route() of a 4:2:2 sample for the output kind, half and interlaced, and the kernel that serves its family
 	FwdL1 forward_route() const;                     // encoder: the level-1 kernel of both frames, from the input kind and interlaced alone
-	GopPlan plan_; bool decode_ = false, half_ = false; int out_kind_ = 0, device_ = 0, matrix_ = 0, n_ = 1;
+	GopPlan plan_; bool decode_ = false, half_ = false; int out_kind_ = 0, device_ = 0, matrix_ = 0, n_ = 1, active_ = 0;
+	int active_groups() const { return active_ > 0 && active_ < n_ ? active_ : n_; }
 	void *stream_ = nullptr, *ev_[4] = {nullptr, nullptr, nullptr, nullptr}; bool timed_ = false, launched_ = false; mutable char stage_name_[3][64];
 	uint8_t *d_frames_ = nullptr, *h_frames_ = nullptr; size_t frame_bytes_ = 0; int pitch_ = 0, rows_ = 0;
 	// decoder outputs behind a conversion (OutputRoute::convert): the YU64 rows of both frames first

@@ -1712,17 +1712,18 @@ int GopBatch::launch_inverse(uint32_t dither_seed, bool coeffs_on_device)
 	if (!coeffs_on_device) HIPCHK(hipMemcpyAsync(d_coeff_, h_coeff_, plan_.coeff_elems * 2, hipMemcpyHostToDevice, st));
 	if (!coeffs_on_device && n_ != 1) return -1;          // (the host's pyramid is the single group's)
 	GopJobs j = gop_jobs_at(d_jobs_, n_);
+	const int ng = active_groups();                      // (the tables hold every group's rows; a short pass launches the first ones)
 	(void)hipGetLastError();
 	if (timed_) HIPCHK(hipEventRecord((hipEvent_t)ev_[0], st));
 	const GopWavelet &top = plan_.ch[0].w[5], &mid = plan_.ch[0].w[4], &t = plan_.ch[0].w[2], &l1 = plan_.ch[0].w[0];
-	dev::k_inv_plane<<<dim3((top.width + dev::ITW - 1) / dev::ITW, (top.height + dev::ITH - 1) / dev::ITH, 3 * n_), dev::NTHREADS, 0, st>>>(j.itop);
+	dev::k_inv_plane<<<dim3((top.width + dev::ITW - 1) / dev::ITW, (top.height + dev::ITH - 1) / dev::ITH, 3 * ng), dev::NTHREADS, 0, st>>>(j.itop);
 	if (timed_) HIPCHK(hipEventRecord((hipEvent_t)ev_[1], st));
-	dev::k_inv_plane<<<dim3((mid.width + dev::ITW - 1) / dev::ITW, (mid.height + dev::ITH - 1) / dev::ITH, 6 * n_), dev::NTHREADS, 0, st>>>(j.imid);
-	dev::k_gop_temporal_inv<<<dim3((unsigned)((t.pitch * t.height / 2 + dev::NTHREADS - 1) / dev::NTHREADS), 3 * n_), dev::NTHREADS, 0, st>>>(j.temp);
+	dev::k_inv_plane<<<dim3((mid.width + dev::ITW - 1) / dev::ITW, (mid.height + dev::ITH - 1) / dev::ITH, 6 * ng), dev::NTHREADS, 0, st>>>(j.imid);
+	dev::k_gop_temporal_inv<<<dim3((unsigned)((t.pitch * t.height / 2 + dev::NTHREADS - 1) / dev::NTHREADS), 3 * ng), dev::NTHREADS, 0, st>>>(j.temp);
 	if (timed_) HIPCHK(hipEventRecord((hipEvent_t)ev_[2], st));
 	// the last level of all frames (grid z = 2 n): the intra path's kernels through the intra path's launcher
 	const GopRoute r = route();
-	const int rc = launch_last_level(r.l1, { l1.width, l1.height, rows_, 2 * n_, plan_.interlaced, j.iyuv, j.l1, j.half, nullptr, 3, dec_words_per_position(PIX_YU64, 3) }, dither_seed, st);
+	const int rc = launch_last_level(r.l1, { l1.width, l1.height, rows_, 2 * ng, plan_.interlaced, j.iyuv, j.l1, j.half, nullptr, 3, dec_words_per_position(PIX_YU64, 3) }, dither_seed, st);
 	if (rc) return rc;
 	// the conversion runs over all frames in one launch -- two when the frames 0 take another matrix than the frames 1 (fill_jobs; v210 takes none): the first frames
 	// of all groups, then the second ones, each launch striding over two frames; a frame 1 then runs as z = g with the seed that gives the single group's the dither of z = 1
@@ -1730,7 +1731,7 @@ int GopBatch::launch_inverse(uint32_t dither_seed, bool coeffs_on_device)
 		launch_convert(r.out, d_tmp_ + tmp_frame_bytes_ * f, tmp_pitch_, tmp_frame_bytes_ * step, d_frames_ + frame_bytes_ * f, pitch_, frame_bytes_ * step, half_ ? plan_.width / 2 : plan_.width, rows_, 0, nf, m,
 		               dither_seed + 0x9E3779B9u * (uint32_t)f, nullptr, st);
 	};
-	if (matrix_ == 0 || r.out.convert == OutConvert::V210) convert(0, 2 * n_, 1, 0); else { convert(0, n_, 2, matrix_); convert(1, n_, 2, 0); }
+	if (matrix_ == 0 || r.out.convert == OutConvert::V210) convert(0, 2 * ng, 1, 0); else { convert(0, ng, 2, matrix_); convert(1, ng, 2, 0); }
 	HIPCHK(hipGetLastError());
 	if (timed_) { HIPCHK(hipEventRecord((hipEvent_t)ev_[3], st)); launched_ = true; }
 	return 0;
@@ -1749,7 +1750,7 @@ int GopBatch::download_frames(void *out, size_t, int pitch)
 {
 	(void)hipSetDevice(device_);
 	if (!decode_ || !out || pitch <= 0) return -1;
-	HIPCHK(hipMemcpyAsync(h_frames_, d_frames_, 2 * (size_t)n_ * frame_bytes_, hipMemcpyDeviceToHost, (hipStream_t)stream_));
+	HIPCHK(hipMemcpyAsync(h_frames_, d_frames_, 2 * (size_t)active_groups() * frame_bytes_, hipMemcpyDeviceToHost, (hipStream_t)stream_));
 	return 0;
 }
 

@@ -206,6 +206,8 @@ private:
 // code-set-18 slots (interlaced groups: the difference-coded bands) behind them; then one k_dec_bands_par launch per code set over slots x n jobs (its latency shape
 // up to kLowLatencyFrames groups), k_dec_undiff and k_dec_lowpass over all groups.  Nothing touches the host between the coder and the inverse transform.
 // (The chunk-indexed decoder of the intra batches, k_dec_index / k_dec_tiles, does not know group pyramids yet: DESIGN.md names it as the follow-up.)
+// The decode queue (cfhd_decode_queue.hip) brings group samples of any encoder instead: every group in a slot of its own, the P-frame sample behind it in another,
+// a verdict per pair (set_samples_slots, set_verdicts), and subband 7 of the groups from 8-bit RGB sources decoded by k_dec_band_two_pass.
 class GpuGroupBatchEntropyDecoder {
 public:
 	GpuGroupBatchEntropyDecoder() {}
@@ -216,20 +218,31 @@ public:
 	// sample g at d_samples + d_offsets[g] (256-byte aligned base, offsets multiples of 4), d_sizes[g] bytes; the buffer extends to the end of the 256-byte window,
 	// counted from the last sample's start, that holds its last tag (GpuEntropyEncoder's dense buffer does)
 	int set_samples_device(const uint8_t *d_samples, const uint32_t *d_sizes, const uint32_t *d_offsets);
+	// group g at d_groups + g * group_stride, the P-frame sample behind it at d_followers + g * follower_stride (all multiples of 256; every slot readable to the end of
+	// the 256-byte window that holds its sample's last tag, zeros behind the sample), d_sizes[g] and d_follower_sizes[g] bytes.  With these the parser judges the
+	// follower and takes the bands coded in two passes; set_verdicts() is required: [0, ngroups) the groups' words (cfhd_ingest_kernels.h dec_verdict_word),
+	// [ngroups, 2 ngroups) the followers' (0: a clean P-frame sample), and check() then speaks of the code streams only.
+	int set_samples_slots(const uint8_t *d_groups, size_t group_stride, const uint32_t *d_sizes, const uint8_t *d_followers, size_t follower_stride, const uint32_t *d_follower_sizes);
+	void set_verdicts(uint32_t *d_verdicts) { d_verdicts_ = d_verdicts; }
+	// the next launch() covers groups 0 .. k-1 of the batch (0 = all): a short pass of the decode queue
+	void set_active(int k) { active_ = k; }
 	void set_producer_events(void *headers, void *payloads) { ev_headers_ = headers; ev_payloads_ = payloads; }      // the parser waits for the first, the band decoder for the second
 	int launch();                        // async
 	int check();                         // after the stream was synchronised: 0 when every sample parsed and every band decoded cleanly
-	float kernel_ms(int k);              // last launch(): 0 k_dec_parse_group, 1 the band decoder (both code sets + k_dec_undiff), 2 k_dec_lowpass
+	float kernel_ms(int k);              // last launch(): 0 k_dec_parse_group, 1 the band decoder (both code sets + k_dec_undiff + k_dec_band_two_pass), 2 k_dec_lowpass, 3 k_dec_band_two_pass alone (launched for sample slots only)
 	const char *band_kernel() const;     // the band decoder's shape for this batch, as a profiler shows it
 	void release();
 private:
 	GopPlan plan_; int n_ = 0, out_kind_ = 0, device_ = 0, slots17_ = 0, slots18_ = 0; size_t coeff_stride_ = 0; void *stream_ = nullptr;
 	int16_t *d_coeffs_ = nullptr;
 	const uint8_t *ext_samples_ = nullptr; const uint32_t *ext_sizes_ = nullptr, *ext_offsets_ = nullptr;
-	void *d_tables_ = nullptr, *d_tables18_ = nullptr, *d_plan_ = nullptr, *d_bandjobs_ = nullptr, *d_lowjobs_ = nullptr, *d_diffjobs_ = nullptr;
+	size_t ext_stride_ = 0, follower_stride_ = 0; const uint8_t *ext_followers_ = nullptr; const uint32_t *ext_follower_sizes_ = nullptr;      // set_samples_slots()
+	uint32_t *d_verdicts_ = nullptr; int active_ = 0; bool two_pass_timed_ = false;
+	int active_groups() const { return active_ > 0 && active_ < n_ ? active_ : n_; }
+	void *d_tables_ = nullptr, *d_tables18_ = nullptr, *d_plan_ = nullptr, *d_bandjobs_ = nullptr, *d_lowjobs_ = nullptr, *d_diffjobs_ = nullptr, *d_twojobs_ = nullptr;
 	int *d_errors_ = nullptr, *h_errors_ = nullptr;
 	void *ev_headers_ = nullptr, *ev_payloads_ = nullptr;
-	void *ev_[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; bool timed_ = false;      // [0] parser begins, [1] parser ends, [2] band decoder begins, [3] ends, [4] lowpass ends
+	void *ev_[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; bool timed_ = false;      // [0] parser begins, [1] parser ends, [2] band decoder begins, [3] ends, [4] lowpass ends, [5] in front of k_dec_band_two_pass (which ends at [3])
 };
 
 } // namespace cfhd

@@ -756,12 +756,12 @@ int GpuGroupEntropyDecoder::check() { return h_errors_ ? *h_errors_ : -1; }
 void GpuGroupBatchEntropyDecoder::release()
 {
 	(void)hipSetDevice(device_);
-	void *dev[] = { d_tables_, d_tables18_, d_plan_, d_bandjobs_, d_lowjobs_, d_diffjobs_, d_errors_ };
+	void *dev[] = { d_tables_, d_tables18_, d_plan_, d_bandjobs_, d_lowjobs_, d_diffjobs_, d_twojobs_, d_errors_ };
 	for (void *p : dev) if (p) (void)hipFree(p);
 	if (h_errors_) (void)hipHostFree(h_errors_);
 	for (void *&e : ev_) if (e) { (void)hipEventDestroy((hipEvent_t)e); e = nullptr; }
-	d_tables_ = d_tables18_ = d_plan_ = d_bandjobs_ = d_lowjobs_ = d_diffjobs_ = nullptr; d_errors_ = h_errors_ = nullptr;
-	ext_samples_ = nullptr; timed_ = false; n_ = 0;
+	d_tables_ = d_tables18_ = d_plan_ = d_bandjobs_ = d_lowjobs_ = d_diffjobs_ = d_twojobs_ = nullptr; d_errors_ = h_errors_ = nullptr;
+	ext_samples_ = ext_followers_ = nullptr; d_verdicts_ = nullptr; active_ = 0; timed_ = false; n_ = 0;
 }
 
 int GpuGroupBatchEntropyDecoder::prepare(const GopPlan &plan, int ngroups, int16_t *d_coeffs, size_t stride, int out_kind, void *stream, int device)
@@ -795,6 +795,9 @@ int GpuGroupBatchEntropyDecoder::prepare(const GopPlan &plan, int ngroups, int16
 		}
 		if (plan.ch[c].w[3].width & 1) return -3;          // (k_dec_lowpass reads a raw band of odd width as unsigned words: the lowpass rule, not w[3]'s)
 	}
+	// (k_dec_band_two_pass clears subband 7 with 16-byte stores; where it cannot, such a group stays with the host)
+	dp.two_pass = 1;
+	for (int c = 0; c < 3; c++) if ((plan.ch[c].w[3].offset[0] & 7) || (plan.ch[c].w[3].pitch & 7) || (stride & 7)) dp.two_pass = 0;
 	std::stable_sort(coded.begin(), coded.end(), [](const Coded &a, const Coded &b) { return a.table != b.table ? a.table < b.table : a.area > b.area; });
 	for (size_t s = 0; s < coded.size(); s++) { dp.band[coded[s].c][coded[s].k][coded[s].b].slot = (int)s; if (coded[s].table) dp.slots18++; else dp.slots17++; }
 	slots17_ = dp.slots17; slots18_ = dp.slots18;
@@ -806,11 +809,11 @@ int GpuGroupBatchEntropyDecoder::prepare(const GopPlan &plan, int ngroups, int16
 	std::vector<uint32_t> t = build_dec_tables(1);
 	HIPCHK(hipMalloc(&d_tables_, t.size() * 4));
 	HIPCHK(hipMemcpy(d_tables_, t.data(), t.size() * 4, hipMemcpyHostToDevice));
-	if (slots18_) {
-		t = build_dec_tables(2);
-		HIPCHK(hipMalloc(&d_tables18_, t.size() * 4));
-		HIPCHK(hipMemcpy(d_tables18_, t.data(), t.size() * 4, hipMemcpyHostToDevice));
-	}
+	// (code set 18: the difference-coded bands of interlaced groups, and the two passes of subband 7 of any group from an 8-bit RGB source)
+	t = build_dec_tables(2);
+	HIPCHK(hipMalloc(&d_tables18_, t.size() * 4));
+	HIPCHK(hipMemcpy(d_tables18_, t.data(), t.size() * 4, hipMemcpyHostToDevice));
+	HIPCHK(hipMalloc(&d_twojobs_, (size_t)3 * n_ * sizeof(dev::DecTwoPassJob)));
 	HIPCHK(hipMalloc(&d_bandjobs_, (size_t)kGroupBandJobs * n_ * sizeof(dev::DecBandJob)));
 	HIPCHK(hipMalloc(&d_lowjobs_, (size_t)kGroupRawJobs * n_ * sizeof(dev::DecLowpassJob)));
 	HIPCHK(hipMalloc(&d_diffjobs_, (size_t)kGroupDiffJobs * n_ * sizeof(dev::DecDiffJob)));
@@ -826,7 +829,15 @@ int GpuGroupBatchEntropyDecoder::set_samples_device(const uint8_t *d_samples, co
 {
 	// (k_dec_parse_group reads 256-byte windows counted from each sample's start, longword by longword: cfhd_entropy_gpu.hip GpuEntropyDecoder::set_samples_device)
 	if (!d_samples || !d_sizes || !d_offsets || ((uintptr_t)d_samples & 255)) return -1;
-	ext_samples_ = d_samples; ext_sizes_ = d_sizes; ext_offsets_ = d_offsets;
+	ext_samples_ = d_samples; ext_sizes_ = d_sizes; ext_offsets_ = d_offsets; ext_followers_ = nullptr;
+	return 0;
+}
+
+int GpuGroupBatchEntropyDecoder::set_samples_slots(const uint8_t *d_groups, size_t group_stride, const uint32_t *d_sizes, const uint8_t *d_followers, size_t follower_stride, const uint32_t *d_follower_sizes)
+{
+	if (!d_groups || !d_sizes || !d_followers || !d_follower_sizes || (((uintptr_t)d_groups | (uintptr_t)d_followers | group_stride | follower_stride) & 255)) return -1;
+	ext_samples_ = d_groups; ext_stride_ = group_stride; ext_sizes_ = d_sizes; ext_offsets_ = nullptr;
+	ext_followers_ = d_followers; follower_stride_ = follower_stride; ext_follower_sizes_ = d_follower_sizes;
 	return 0;
 }
 
@@ -836,31 +847,42 @@ int GpuGroupBatchEntropyDecoder::launch()
 {
 	(void)hipSetDevice(device_);
 	hipStream_t st = (hipStream_t)stream_;
-	if (!ext_samples_ || !d_plan_) return -1;
+	if (!ext_samples_ || !d_plan_ || (ext_followers_ && !d_verdicts_)) return -1;
+	// the groups of this pass: the job tables are [slot][n], the launches n times as long
+	const int ng = active_groups();
+	const bool slots = ext_followers_ != nullptr;
 	HIPCHK(hipMemsetAsync(d_errors_, 0, sizeof(int), st));
 	(void)hipGetLastError();
 	// the parser reads the headers and size fields only (k_ent_layout): it runs beside k_ent_emit, the band decoder waits for the payloads
 	if (ev_headers_) HIPCHK(hipStreamWaitEvent(st, (hipEvent_t)ev_headers_, 0));
 	HIPCHK(hipEventRecord((hipEvent_t)ev_[0], st));
-	dev::k_dec_parse_group<<<n_, dev::DEC_PARSE_THREADS, 0, st>>>(ext_samples_, ext_offsets_, ext_sizes_, n_, (const dev::DecGroupPlan *)d_plan_, d_coeffs_, coeff_stride_,
-	                                                              (dev::DecBandJob *)d_bandjobs_, (dev::DecLowpassJob *)d_lowjobs_, (dev::DecDiffJob *)d_diffjobs_, d_errors_);
+	dev::k_dec_parse_group<<<ng, dev::DEC_PARSE_THREADS, 0, st>>>(ext_samples_, ext_offsets_, ext_sizes_, ng, (const dev::DecGroupPlan *)d_plan_, d_coeffs_, coeff_stride_,
+	                                                              (dev::DecBandJob *)d_bandjobs_, (dev::DecLowpassJob *)d_lowjobs_, (dev::DecDiffJob *)d_diffjobs_, d_errors_,
+	                                                              ext_stride_, slots ? d_verdicts_ : nullptr, slots ? d_verdicts_ + n_ : nullptr, ext_followers_, follower_stride_, ext_follower_sizes_,
+	                                                              slots ? (dev::DecTwoPassJob *)d_twojobs_ : nullptr);
 	HIPCHK(hipEventRecord((hipEvent_t)ev_[1], st));
 	if (ev_payloads_) HIPCHK(hipStreamWaitEvent(st, (hipEvent_t)ev_payloads_, 0));
 	ev_headers_ = ev_payloads_ = nullptr;
 	HIPCHK(hipEventRecord((hipEvent_t)ev_[2], st));
 	// a workgroup per band, the rows of one code set in one launch: few groups in the latency shape (the launch lasts as long as the longest band's serial steps)
-	const bool ll = par_backend(n_) == DecBackend::ParLowLatency;
+	const bool ll = par_backend(ng) == DecBackend::ParLowLatency;
 	auto bands = [&](const dev::DecBandJob *jobs, int count, const void *tables) {
 		if (ll) dev::k_dec_bands_par_ll<<<count, dev::DECP_LL_THREADS, 0, st>>>(jobs, (const dev::DecTables *)tables, d_errors_);
 		else dev::k_dec_bands_par<<<count, dev::DECP_THREADS, 0, st>>>(jobs, (const dev::DecTables *)tables, d_errors_);
 	};
-	bands((const dev::DecBandJob *)d_bandjobs_, slots17_ * n_, d_tables_);
+	bands((const dev::DecBandJob *)d_bandjobs_, slots17_ * ng, d_tables_);
 	if (slots18_) {
-		bands((const dev::DecBandJob *)d_bandjobs_ + (size_t)slots17_ * n_, slots18_ * n_, d_tables18_);
-		dev::k_dec_undiff<<<dim3((unsigned)(kGroupDiffJobs * n_), dev::DXU_SPLIT), dev::DXU_THREADS, 0, st>>>((const dev::DecDiffJob *)d_diffjobs_, d_errors_, 0);
+		bands((const dev::DecBandJob *)d_bandjobs_ + (size_t)slots17_ * ng, slots18_ * ng, d_tables18_);
+		dev::k_dec_undiff<<<dim3((unsigned)(kGroupDiffJobs * ng), dev::DXU_SPLIT), dev::DXU_THREADS, 0, st>>>((const dev::DecDiffJob *)d_diffjobs_, d_errors_, 0);
 	}
+	if (slots) {
+		// subband 7 of the groups from 8-bit RGB sources: a workgroup per (group, channel), the jobs of raw-word groups are empty
+		HIPCHK(hipEventRecord((hipEvent_t)ev_[5], st));
+		dev::k_dec_band_two_pass<<<3 * ng, dev::DECP_THREADS, 0, st>>>((const dev::DecTwoPassJob *)d_twojobs_, (const dev::DecTables *)d_tables18_, d_errors_);
+	}
+	two_pass_timed_ = slots;
 	HIPCHK(hipEventRecord((hipEvent_t)ev_[3], st));
-	dev::k_dec_lowpass<<<dim3(8, (unsigned)(kGroupRawJobs * n_)), 256, 0, st>>>((const dev::DecLowpassJob *)d_lowjobs_);
+	dev::k_dec_lowpass<<<dim3(8, (unsigned)(kGroupRawJobs * ng)), 256, 0, st>>>((const dev::DecLowpassJob *)d_lowjobs_);
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipEventRecord((hipEvent_t)ev_[4], st));
 	timed_ = true;
@@ -873,8 +895,8 @@ int GpuGroupBatchEntropyDecoder::check() { return h_errors_ ? (*h_errors_ ? -1 :
 float GpuGroupBatchEntropyDecoder::kernel_ms(int k)
 {
 	float ms = 0;
-	if (!timed_ || k < 0 || k > 2) return 0;
-	void *a = k == 0 ? ev_[0] : (k == 1 ? ev_[2] : ev_[3]), *b = k == 0 ? ev_[1] : (k == 1 ? ev_[3] : ev_[4]);
+	if (!timed_ || k < 0 || k > 3 || (k == 3 && !two_pass_timed_)) return 0;
+	void *a = k == 0 ? ev_[0] : (k == 1 ? ev_[2] : (k == 2 ? ev_[3] : ev_[5])), *b = k == 0 ? ev_[1] : (k == 2 ? ev_[4] : ev_[3]);
 	if (hipEventElapsedTime(&ms, (hipEvent_t)a, (hipEvent_t)b) != hipSuccess) { (void)hipGetLastError(); return 0; }
 	return ms;
 }

@@ -1142,10 +1142,11 @@ struct DecSub { uint32_t end, cnt; };
 
 // Decodes the code words that start in [p, limit) of the sequence held in s_words (big-endian bit order, already byte
 // swapped).  Returns where the next code word starts (DECP_END after the band end marker, DECP_BAD for an invalid code) and
-// how many coefficients (zero runs included) were produced; WRITE stores the nonzero ones at dst[idx...].
-template <bool WRITE>
+// how many coefficients (zero runs included) were produced; WRITE stores the nonzero ones at dst[idx...].  The second pass of a band coded in two passes
+// (k_dec_band_two_pass): ADD adds value << 8 to what the first pass left there, in 16 bits; END_AT stores where the code behind the band end marker would start.
+template <bool WRITE, bool ADD = false, bool END_AT = false>
 __device__ __forceinline__ DecSub dec_sub(const uint32_t *s_words, const uint32_t *s_lut1, const DecTables *T, uint32_t p, const uint32_t limit,
-                                          int16_t *dst, uint32_t idx, const uint32_t n, const int quant)
+                                          int16_t *dst, uint32_t idx, const uint32_t n, const int quant, uint32_t *end_at = nullptr)
 {
 	uint32_t wi = p >> 5;
 	const int sh = (int)(p & 31u);
@@ -1163,12 +1164,13 @@ __device__ __forceinline__ DecSub dec_sub(const uint32_t *s_words, const uint32_
 		int len = (int)(e & 31u);
 		if (len == 0) return DecSub{ DECP_BAD, cnt };
 		const uint32_t mag = e >> 16;
-		if (mag == 0xffffu) return DecSub{ DECP_END, cnt };
+		if (mag == 0xffffu) { if (END_AT) *end_at = p + (uint32_t)len; return DecSub{ DECP_END, cnt }; }
 		if (mag) {
 			if (WRITE) {
 				const int negative = (int)((acc << len) >> 63);
 				const int v = (int)mag * quant;
-				if (idx + cnt < n) dst[idx + cnt] = (int16_t)(negative ? -v : v);
+				if (ADD) { if (idx + cnt < n) dst[idx + cnt] = (int16_t)((uint32_t)(uint16_t)dst[idx + cnt] + ((uint32_t)(negative ? -v : v) << 8)); }
+				else if (idx + cnt < n) dst[idx + cnt] = (int16_t)(negative ? -v : v);
 			}
 			len++; cnt++;
 		} else cnt += (e >> 5) & 0x7ffu;
@@ -1188,6 +1190,7 @@ __device__ __forceinline__ void dec_bands_par(const DecBandJob *jobs, const DecT
 	__shared__ int s_flag[2];
 	const int t = threadIdx.x;
 	const DecBandJob job = jobs[blockIdx.x];
+	if (!job.dst) return;                                // (k_dec_parse_group with a verdict table: a group that failed its parse has no band here and says so itself)
 	const uint32_t *words = (const uint32_t *)job.bits;
 	const uint32_t nwords = job.bytes >> 2, n = (uint32_t)job.n;
 	for (int i = t; i < (1 << DEC_K1); i += DECP_THREADS) s_lut1[i] = T->lut1[i];
@@ -1242,6 +1245,100 @@ __device__ __forceinline__ void dec_bands_par(const DecBandJob *jobs, const DecT
 }
 __global__ void __launch_bounds__(DECP_THREADS) k_dec_bands_par(const DecBandJob *jobs, const DecTables *T, int *errors) { dec_bands_par<DECP_THREADS, DECP_SUB_BITS>(jobs, T, errors); }
 __global__ void __launch_bounds__(DECP_LL_THREADS) k_dec_bands_par_ll(const DecBandJob *jobs, const DecTables *T, int *errors) { dec_bands_par<DECP_LL_THREADS, DECP_LL_SUB_BITS>(jobs, T, errors); }
+
+// ---------------------------------------------------------------------------------------------
+// k_dec_band_two_pass: the lowpass band of the temporal highpass wavelet (subband 7) of a group from an 8-bit RGB source, divided and coded in two passes of code
+// set 18 (cfhd_gop.h: BAND_ENCODING_LOSSLESS; cfhd_gop.cpp vlc_decode_band_two_pass, after Codec/decoder.c:12862 DecodeBand16sLossless).  One workgroup per job on
+// the walk of dec_bands_par: the band zeroed, pass 1 decoded over the raster; the longword at the bit position behind its band end code, rounded up to a longword,
+// must be the BAND_SECONDPASS tag (bytes 00 52); pass 2 decoded from the longword behind the tag over the same raster.  The result is
+// (int16)((int16)(pass 1 + (pass 2 << 8)) * divisor): in 16 bits that is pass 1 * divisor + ((pass 2 << 8) * divisor), so pass 1 stores its products and pass 2 adds
+// its own to them -- every coefficient belongs to one lane in either pass, the barrier at the head of a walk lies between them.  Pass 1 walks a payload that goes on
+// behind its band end code: the lanes behind that code learn one per round that they have nothing to decode (a round without a decode is two barriers), once a band.
+// The error word as the other band decoders set it: 1 << 1 an invalid code, 1 << 2 more coefficients than the band holds, 1 << 3 a payload that ends early, and
+// 1 << 4 no tag behind pass 1.  A job without a band (the group is a raw-word group, or failed its parse) ends at once.
+// ---------------------------------------------------------------------------------------------
+struct DecTwoPassJob { const uint8_t *bits; uint32_t bytes; int16_t *dst; int width, height, pitch, quant; };      // payload behind BAND_HEADER, up to the band trailer; dst: height * pitch, both multiples of 8 elements
+
+// One coded pass: dec_bands_par's loop over the 8 KB sequences of `words`, which also answers where the pass ended (bits from words[0], behind the band end code).
+template <int NT, int SUB_BITS, bool ADD>
+__device__ __forceinline__ int decp_walk(const uint32_t *words, const uint32_t nwords, int16_t *dst, const uint32_t n, const int quant, const DecTables *T, const uint32_t *s_lut1,
+                                         uint32_t *s_words, uint32_t *s_end, uint32_t *s_wsum, int *s_flag, uint32_t *s_at, uint64_t *end_bit)
+{
+	enum { SEQ_BITS = NT * SUB_BITS, SEQ_WORDS = SEQ_BITS / 32 };
+	const int t = threadIdx.x;
+	uint32_t carry = 0, base_idx = 0;
+	for (uint32_t seq0 = 0; ; seq0 += SEQ_WORDS) {
+		if (seq0 >= nwords) return 3;                    // ran off the payload without meeting the end marker
+		__syncthreads();
+		for (int i = t; i < SEQ_WORDS + 4; i += NT) { const uint32_t w = seq0 + (uint32_t)i; s_words[i] = w < nwords ? bswap32(words[w]) : 0u; }
+		__syncthreads();
+		const uint64_t left = (uint64_t)(nwords - seq0) * 32u;
+		const uint32_t seq_bits = left < (uint64_t)SEQ_BITS ? (uint32_t)left : (uint32_t)SEQ_BITS;
+		const int nsub = (int)((seq_bits + SUB_BITS - 1) / SUB_BITS);
+		const bool active = t < nsub;
+		uint32_t start = t ? (uint32_t)t * SUB_BITS : carry, at = 0;
+		const uint32_t limit = (uint32_t)(t + 1) * SUB_BITS < seq_bits ? (uint32_t)(t + 1) * SUB_BITS : seq_bits;
+		DecSub r = active ? dec_sub<false, false, true>(s_words, s_lut1, T, start, limit, nullptr, 0u, 0u, 0, &at) : DecSub{ DECP_END, 0u };
+		for (int round = 0; ; round++) {
+			s_end[t] = r.end;
+			__syncthreads();
+			if (t == 0) s_flag[(round + 1) & 1] = 0;
+			const uint32_t ns = t ? s_end[t - 1] : start;
+			const bool changed = active && ns != start;
+			if (changed) s_flag[round & 1] = 1;
+			__syncthreads();
+			if (!s_flag[round & 1]) break;
+			if (changed) {
+				start = ns;
+				if (ns >= DECP_BAD) { r.end = ns; r.cnt = 0; }
+				else r = dec_sub<false, false, true>(s_words, s_lut1, T, start, limit, nullptr, 0u, 0u, 0, &at);
+			}
+		}
+		if (active && start < DECP_BAD && r.end == DECP_END) s_at[0] = at;      // (the one lane that met the band end code from an exact start)
+		uint32_t total;
+		const uint32_t my_idx = base_idx + decp_excl_sum<NT>(r.cnt, s_wsum, &total);
+		const uint32_t last = s_end[nsub - 1];
+		if (last == DECP_BAD) return 1;
+		if (total > n - base_idx) return 2;              // more coefficients than the band holds
+		if (active && start < DECP_BAD && r.cnt) (void)dec_sub<true, ADD>(s_words, s_lut1, T, start, r.end, dst, my_idx, n, quant);
+		if (last == DECP_END) { *end_bit = (uint64_t)seq0 * 32u + s_at[0]; return 0; }
+		if (seq_bits < (uint32_t)SEQ_BITS) return 3;     // the payload ended without the band end marker
+		carry = last - SEQ_BITS;
+		base_idx += total;
+	}
+}
+
+__global__ void __launch_bounds__(DECP_THREADS) k_dec_band_two_pass(const DecTwoPassJob *jobs, const DecTables *T, int *errors)
+{
+	enum { SEQ_WORDS = DECP_THREADS * DECP_SUB_BITS / 32 };
+	__shared__ uint32_t s_lut1[1 << DEC_K1];             // 16 KB
+	__shared__ uint32_t s_words[SEQ_WORDS + 4];          // 8 KB: the current sequence of the payload
+	__shared__ uint32_t s_end[DECP_THREADS];
+	__shared__ uint32_t s_wsum[DECP_THREADS / 64];
+	__shared__ int s_flag[2];
+	__shared__ uint32_t s_at[1];
+	const int t = threadIdx.x;
+	const DecTwoPassJob job = jobs[blockIdx.x];
+	if (!job.dst) return;
+	const uint32_t *words = (const uint32_t *)job.bits;
+	const uint32_t nwords = job.bytes >> 2, n = (uint32_t)(job.height * job.pitch);
+	for (int i = t; i < (1 << DEC_K1); i += DECP_THREADS) s_lut1[i] = T->lut1[i];
+	if (t < 2) s_flag[t] = 0;
+	if (t == 0) s_at[0] = 0u;
+	{
+		uint4 *z = (uint4 *)job.dst;
+		const uint4 zero = { 0u, 0u, 0u, 0u };
+		for (uint32_t i = t; i < n / 8; i += DECP_THREADS) z[i] = zero;
+	}
+	uint64_t end_bit = 0;
+	int err = decp_walk<DECP_THREADS, DECP_SUB_BITS, false>(words, nwords, job.dst, n, job.quant, T, s_lut1, s_words, s_end, s_wsum, s_flag, s_at, &end_bit);
+	if (!err) {
+		const uint64_t tag_at = (end_bit + 31u) >> 5;    // the first pass is padded to a whole longword
+		if (tag_at >= nwords || (bswap32(words[tag_at]) >> 16) != 0x0052u) err = 4;      // CODEC_TAG_BAND_SECONDPASS
+		else err = decp_walk<DECP_THREADS, DECP_SUB_BITS, true>(words + tag_at + 1, nwords - (uint32_t)tag_at - 1u, job.dst, n, job.quant, T, s_lut1, s_words, s_end, s_wsum, s_flag, s_at, &end_bit);
+	}
+	if (err && t == 0) atomic_or_u32((uint32_t *)errors, 1u << err);
+}
 
 // ---------------------------------------------------------------------------------------------
 // Sample parser on the GPU, for samples that already live in HBM (the batched round trip hands the encoder's output straight
@@ -1395,23 +1492,37 @@ __global__ void __launch_bounds__(DEC_PARSE_THREADS) k_dec_parse(const uint8_t *
 // boundaries and inside the sample, the code book each band must come in, a divisor of 1 for the raw band.  A sample that fails one leaves its jobs empty (bytes = 0,
 // no rows) and raises DEC_ERR_PARSE.  Every turn of the walk advances by at least 4 bytes and stops at the sample's size; the fetches are 256-byte windows counted
 // from the sample's start, so the buffer must extend to the end of the window that holds the last sample's last tag (GpuGroupBatchEntropyDecoder::set_samples_device).
+// With a verdict table (the decode queue, cfhd_decode_queue.hip: samples from any encoder in slots of their own, group g at samples + g * sample_stride):
+//   - a verdict word per group instead of DEC_ERR_PARSE for the pass (cfhd_ingest_kernels.h dec_verdict_word): the progressive flag, the colour-space tag, and in the low
+//     byte 0 or why the group has no jobs -- 1 malformed, 2 frame width / height, 3 channel count / precision, 4 bands missing: what CFHD_DecodeSample calls a bad sample
+//     whatever else it holds; 5: only the host decides (not a group sample at all, or a band the handle's host coder may still take) --;
+//   - the P-frame sample behind the group (follower g at followers + g * follower_stride, fsizes[g] bytes) is judged: fverdicts[g] = 0 when its first longword is
+//     TAG_SAMPLE / 1 and its tag walk stays inside its size and meets nothing but plain tags (what parse_group_sample answers 1 for), 1 otherwise;
+//   - subband 7 coded in two passes (wavelet 3, band 0, BAND_ENCODING 5, code book 2) fills the group's DecTwoPassJob of the channel and leaves its raw job empty --
+//     the choice is the sample's, a pass may mix both kinds --;
+//   - the jobs of a group that failed carry no band (dst = null): the band decoders pass them by, the error word speaks of the code streams alone.
 // ---------------------------------------------------------------------------------------------
 struct DecGroupBand { int width, height, pitch, slot; uint32_t offset; };      // slot: the band's row of the job table; < 0: not a coded band
 struct DecGroupPlan {
 	int width, height, display_height, interlaced;
 	int slots17, slots18;                   // rows of the band job table: code set 17, then code set 18
 	int low_bias[3];                        // group_lowpass_bias of the output, per channel
+	int two_pass;                           // subband 7 lies where k_dec_band_two_pass can clear it with 16-byte stores
 	DecGroupBand band[3][6][4];             // [channel][wavelet][band] of the group pyramid (GopPlan); band 0 of w[5] and w[3]: the raw bands
 };
 enum { DEC_GROUP_RAW_JOBS = 6, DEC_GROUP_DIFF_JOBS = 6 };      // per group: two raw bands, two difference-coded bands per channel
 
 __global__ void __launch_bounds__(DEC_PARSE_THREADS) k_dec_parse_group(const uint8_t *samples, const uint32_t *offsets, const uint32_t *sizes, int ngroups, const DecGroupPlan *P,
-                                                                       int16_t *coeffs, size_t coeff_stride, DecBandJob *bandjobs, DecLowpassJob *lowjobs, DecDiffJob *diffjobs, int *errors)
+                                                                       int16_t *coeffs, size_t coeff_stride, DecBandJob *bandjobs, DecLowpassJob *lowjobs, DecDiffJob *diffjobs, int *errors,
+                                                                       size_t sample_stride = 0 /* offsets == null: group g at samples + g * sample_stride */,
+                                                                       uint32_t *verdicts = nullptr, uint32_t *fverdicts = nullptr /* [ngroups] each; null: none */,
+                                                                       const uint8_t *followers = nullptr, size_t follower_stride = 0, const uint32_t *fsizes = nullptr,
+                                                                       DecTwoPassJob *twojobs = nullptr /* [ngroups * 3] */)
 {
 	const int g = blockIdx.x;                            // every lane walks the same tags; lane 0 writes the jobs
 	const int lane = wave_lane();
 	const bool writer = lane == 0;
-	const uint8_t *d = samples + offsets[g];
+	const uint8_t *d = offsets ? samples + offsets[g] : samples + sample_stride * (size_t)g;
 	int16_t *cbase = coeffs + coeff_stride * (size_t)g;
 	const uint64_t size = sizes[g];
 	const bool interlaced = P->interlaced != 0;
@@ -1425,10 +1536,37 @@ __global__ void __launch_bounds__(DEC_PARSE_THREADS) k_dec_parse_group(const uin
 				}
 		for (int k = 0; k < DEC_GROUP_RAW_JOBS; k++) lowjobs[g * DEC_GROUP_RAW_JOBS + k] = DecLowpassJob{ d, cbase, 0, 0, 0, 0 };
 		if (interlaced) for (int k = 0; k < DEC_GROUP_DIFF_JOBS; k++) diffjobs[g * DEC_GROUP_DIFF_JOBS + k] = DecDiffJob{ nullptr, 0, 0, 0, nullptr, 0u, 0 };
+		if (twojobs) for (int c = 0; c < 3; c++) twojobs[g * 3 + c] = DecTwoPassJob{ d, 0u, nullptr, 0, 0, 0, 1 };
+	}
+	if (fverdicts) {
+		// the follower: its tags are read as parse_group_sample reads those of a sample that is no group; a tag that would make that walk look at bands sends the pair to the host
+		const uint8_t *fd = followers + follower_stride * (size_t)g;
+		const uint64_t fsize = fsizes[g];
+		DecTagReader fr; fr.d = fd; fr.base = ~(uint64_t)0; fr.w = 0; fr.lane = lane;
+		bool fbad = fsize < 4, ffirst = true;
+		for (uint64_t p = 0; !fbad && p + 4 <= fsize; ) {
+			const uint32_t word = fr.word(p);
+			int tag = (int)(int16_t)(word >> 16);
+			const int value = (int)(word & 0xffffu);
+			if (tag < 0) tag = -tag;
+			p += 4;
+			if (ffirst) { ffirst = false; if (tag != 1 || value != 1) fbad = true; continue; }      // TAG_SAMPLE, SAMPLE_TYPE_FRAME
+			if (tag & 0x4000) {
+				const uint32_t bytes = (tag & 0x2000) ? ((((uint32_t)(tag & 0xff) << 16) | (uint32_t)value) * 4u) : (uint32_t)value * 4u;
+				if (p + bytes > fsize) fbad = true;
+				p += bytes;
+				continue;
+			}
+			if (tag & 0x2000) continue;
+			if (tag == 2) p += 4u * (uint64_t)value;                                     // TAG_INDEX
+			else if (tag == 62 || tag == 38 || tag == 48 || tag == 55 || (tag == 4 && value == 0x0f0f)) fbad = true;      // TAG_CHANNEL, TAG_WAVELET_NUMBER, TAG_BAND_NUMBER, TAG_BAND_HEADER, MARK_COEFF_START
+		}
+		if (writer) fverdicts[g] = fbad ? 1u : 0u;
 	}
 	DecTagReader rd; rd.d = d; rd.base = ~(uint64_t)0; rd.w = 0; rd.lane = lane;
 	uint64_t pos = 0, pending_at = 0, peak_base = 0;
 	uint32_t pending = 0, peak_offset = 0, seen_raw = 0;
+	int color_space = 0; bool host_only = false;         // (for the verdict)
 	uint64_t seen = 0;                                   // one bit per coded band: (channel * 6 + wavelet) * 3 + band - 1
 	int peak_level = 0, channel = 0, wavelet = -1, band = 0, bw = 0, bh = 0, bq = 1, bflags = 0, benc = 3, lw = 0, lh = 0;
 	int width = 0, height = 0, display_height = 0, num_channels = 0, precision = 0, sample_type = -1, progressive = 0;
@@ -1439,7 +1577,7 @@ __global__ void __launch_bounds__(DEC_PARSE_THREADS) k_dec_parse_group(const uin
 		const int value = (int)(word & 0xffffu);
 		if (tag < 0) tag = -tag;
 		pos += 4;
-		if (first) { first = false; if (tag != 1 || value != 2) bad = true; sample_type = value; continue; }      // TAG_SAMPLE, SAMPLE_TYPE_GROUP
+		if (first) { first = false; if (tag != 1 || value != 2) { bad = true; host_only = true; } sample_type = value; continue; }      // TAG_SAMPLE, SAMPLE_TYPE_GROUP (another sample: the handle answers by its kind)
 		if (tag & 0x4000) {
 			const uint32_t bytes = (tag & 0x2000) ? ((((uint32_t)(tag & 0xff) << 16) | (uint32_t)value) * 4u) : (uint32_t)value * 4u;
 			if (pos + bytes > size) { bad = true; break; }
@@ -1459,6 +1597,7 @@ __global__ void __launch_bounds__(DEC_PARSE_THREADS) k_dec_parse_group(const uin
 		case 85: display_height = value; break;                                      // TAG_FRAME_DISPLAY_HEIGHT
 		case 70: precision = value; break;                                           // TAG_PRECISION
 		case 68: progressive = value & 1; break;                                     // TAG_SAMPLE_FLAGS (an interlaced group carries none)
+		case 91: color_space = value; break;                                         // TAG_ENCODED_COLORSPACE
 		case 27: lw = value; break;                                                  // TAG_LOWPASS_WIDTH
 		case 28: lh = value; break;                                                  // TAG_LOWPASS_HEIGHT
 		case 4:                                                                      // TAG_MARKER
@@ -1488,18 +1627,26 @@ __global__ void __launch_bounds__(DEC_PARSE_THREADS) k_dec_parse_group(const uin
 			const uint32_t bytes = (uint32_t)(end - 4 - pos);
 			if (wavelet == 2) { pos = end; pending = 0; peak_level = 0; break; }     // the temporal wavelet: a header and one empty band, nothing coded
 			const DecGroupBand pb = P->band[channel][wavelet][band];
+			if (band == 0 && wavelet != 3) { bad = true; host_only = true; break; }      // (a band the host parser files and nobody reads)
 			if (bw != pb.width || bh != pb.height || (pos & 3u)) { bad = true; break; }
+			// (from here on: what the device stage does not take, while the handle's host coder may)
 			if (wavelet == 3 && band == 0) {
-				// raw 16-bit words (BAND_ENCODING_16BIT): signed, no bias; a divided band coded in two passes (BAND_ENCODING_LOSSLESS) is the host coder's
-				if (benc != 4 || bq != 1 || (pb.width & 1) || (uint64_t)bytes < (uint64_t)pb.width * (uint64_t)pb.height * 2u) { bad = true; break; }
-				if (writer) lowjobs[g * DEC_GROUP_RAW_JOBS + 2 * channel + 1] = DecLowpassJob{ d + pos, cbase + pb.offset, pb.width, pb.height, pb.pitch, 0 };
+				if (twojobs && benc == 5 && P->two_pass && (bflags & 0x1f) == 2) {
+					// divided and coded in two passes of code set 18 (BAND_ENCODING_LOSSLESS): k_dec_band_two_pass
+					if (writer) { twojobs[g * 3 + channel] = DecTwoPassJob{ d + pos, bytes, cbase + pb.offset, pb.width, pb.height, pb.pitch, bq }; lowjobs[g * DEC_GROUP_RAW_JOBS + 2 * channel + 1] = DecLowpassJob{ d, cbase, 0, 0, 0, 0 }; }
+				} else {
+					// raw 16-bit words (BAND_ENCODING_16BIT): signed, no bias; without a two-pass job table a divided band coded in two passes is the host coder's
+					if (benc != 4 || bq != 1 || (pb.width & 1) || (uint64_t)bytes < (uint64_t)pb.width * (uint64_t)pb.height * 2u) { bad = true; host_only = true; break; }
+					if (writer) lowjobs[g * DEC_GROUP_RAW_JOBS + 2 * channel + 1] = DecLowpassJob{ d + pos, cbase + pb.offset, pb.width, pb.height, pb.pitch, 0 };
+					if (writer && twojobs) twojobs[g * 3 + channel].dst = nullptr;
+				}
 				seen_raw |= 2u << (2 * channel);
 			} else {
-				if (band < 1 || pb.slot < 0 || benc == 4 || benc == 5) { bad = true; break; }
+				if (band < 1 || pb.slot < 0 || benc == 4 || benc == 5) { bad = true; host_only = true; break; }
 				const bool diff = interlaced && wavelet < 2 && band == 2;
 				const int codebook = bflags & 0xf;
-				if (codebook != (diff ? 2 : 1) || (((bflags >> 4) & 1) != 0) != diff) { bad = true; break; }
-				if (peak_level && (!diff || peak_base + peak_offset + 2 > size)) { bad = true; break; }
+				if (codebook != (diff ? 2 : 1) || (((bflags >> 4) & 1) != 0) != diff) { bad = true; host_only = true; break; }
+				if (peak_level && (!diff || peak_base + peak_offset + 2 > size)) { bad = true; host_only = true; break; }
 				if (writer) bandjobs[(size_t)pb.slot * ngroups + g] = DecBandJob{ d + pos, bytes, cbase + pb.offset, pb.height * pb.pitch, bq, 0u, diff ? 1 : 0 };
 				if (writer && diff) diffjobs[g * DEC_GROUP_DIFF_JOBS + 2 * channel + wavelet] = DecDiffJob{ cbase + pb.offset, pb.width, pb.height, pb.pitch, peak_level ? d + peak_base + peak_offset : nullptr,
 				                                                                                       peak_level ? (uint32_t)(size - (peak_base + peak_offset)) : 0u, peak_level };
@@ -1515,17 +1662,23 @@ __global__ void __launch_bounds__(DEC_PARSE_THREADS) k_dec_parse_group(const uin
 	// the 45 coded bands: the three highpass bands of the wavelets 5, 4, 3, 1 and 0 of every channel
 	uint64_t want = 0;
 	for (int c = 0; c < 3; c++) for (int k = 0; k < 6; k++) if (k != 2) want |= (uint64_t)7 << ((c * 6 + k) * 3);
+	int reason = 0;
 	if (bad || sample_type != 2 || width != P->width || height != P->height || display_height != P->display_height || num_channels != 3 || precision != 10
 	    || (progressive != 0) == interlaced || seen != want || seen_raw != 0x3fu) {
 		if (writer) {
 			for (int c = 0; c < 3; c++)
 				for (int k = 0; k < 6; k++)
-					for (int b = 1; b < 4; b++) { const int slot = P->band[c][k][b].slot; if (slot >= 0) bandjobs[(size_t)slot * ngroups + g].bytes = 0u; }
+					for (int b = 1; b < 4; b++) { const int slot = P->band[c][k][b].slot; if (slot >= 0) { bandjobs[(size_t)slot * ngroups + g].bytes = 0u; if (verdicts) bandjobs[(size_t)slot * ngroups + g].dst = nullptr; } }
 			for (int k = 0; k < DEC_GROUP_RAW_JOBS; k++) { lowjobs[g * DEC_GROUP_RAW_JOBS + k].width = 0; lowjobs[g * DEC_GROUP_RAW_JOBS + k].height = 0; }
 			if (interlaced) for (int k = 0; k < DEC_GROUP_DIFF_JOBS; k++) diffjobs[g * DEC_GROUP_DIFF_JOBS + k].band = nullptr;
-			atomic_or_u32((uint32_t *)errors, (uint32_t)DEC_ERR_PARSE);
+			if (twojobs) for (int c = 0; c < 3; c++) twojobs[g * 3 + c].dst = nullptr;
+			if (!verdicts) atomic_or_u32((uint32_t *)errors, (uint32_t)DEC_ERR_PARSE);
 		}
+		// (the handle compares the frame's width and height, not its display height; a scan other than the prepared one is told by the flag above the reason)
+		reason = host_only ? 5 : bad ? 1 : (width != P->width || height != P->height) ? 2 : (num_channels != 3 || precision != 10) ? 3
+		       : (display_height != P->display_height || (progressive != 0) == interlaced) ? 5 : 4;
 	}
+	if (writer && verdicts) verdicts[g] = (uint32_t)reason | ((uint32_t)(progressive & 1) << 8) | ((uint32_t)(color_space & 0xffff) << 16);
 }
 
 // Raw 16-bit big-endian lowpass coefficients + the reference decoder's bias (decoder.c:12240-12290, :12468-12545).

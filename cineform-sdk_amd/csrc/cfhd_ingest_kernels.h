@@ -24,10 +24,12 @@ __host__ __device__ inline uint32_t dec_verdict_word(int reason, int progressive
 // A sample's pieces cover its bytes and the zeros behind them up to the next multiple of 256: the window the parser's last fetch reads (DecTagReader) never shows what
 // an earlier pass left in the slot.  A sample longer than its slot or of a size that is no multiple of 4 is not copied: size 0, marks[i] = 1 (the caller decodes it
 // elsewhere).  Nothing is read outside the 16-byte blocks that hold bytes of a sample, so nothing outside the 16-byte hull of the blob.
+// Slots of two sizes (a batch of two-frame groups: a group sample's slot, and a small one for the P-frame sample behind it): the table names entry i's slot -- dst[i]
+// bytes from `slots`, a multiple of 256, cap[i] bytes long, a multiple of 256 too -- instead of i * slot_stride and slot_stride.
 // grid: max(1, first_piece[n]) workgroups of DEC_INGEST_THREADS.
 // ---------------------------------------------------------------------------------------------
 enum { DEC_INGEST_THREADS = 256, DEC_INGEST_PIECE = 16384 };      // four 16-byte vectors a lane
-struct DecIngestTable { const unsigned long long *src; const uint32_t *size, *first_piece; };      // [n], [n], [n + 1] in device memory
+struct DecIngestTable { const unsigned long long *src; const uint32_t *size, *first_piece; const unsigned long long *dst; const uint32_t *cap; };      // [n], [n], [n + 1], and [n], [n] or null, in device memory
 
 __host__ __device__ inline uint32_t dec_ingest_pieces(uint32_t size, size_t slot_stride)
 {
@@ -56,7 +58,7 @@ __global__ void __launch_bounds__(DEC_INGEST_THREADS) k_dec_ingest(const uint8_t
 	// the size table and the marks: one entry a lane over the whole grid
 	for (int i = (int)(blockIdx.x * DEC_INGEST_THREADS + threadIdx.x); i < n; i += (int)(gridDim.x * DEC_INGEST_THREADS)) {
 		const uint32_t size = T.size[i];
-		const bool copied = !(size & 3u) && size <= slot_stride;
+		const bool copied = !(size & 3u) && size <= (T.cap ? (size_t)T.cap[i] : slot_stride);
 		d_sizes[i] = copied ? size : 0u;
 		marks[i] = copied ? 0u : 1u;
 	}
@@ -72,7 +74,7 @@ __global__ void __launch_bounds__(DEC_INGEST_THREADS) k_dec_ingest(const uint8_t
 	const unsigned long long s0 = T.src[i];
 	const uint32_t shift = (uint32_t)wave_uniform((int)((uint32_t)((uintptr_t)blob + s0) & 15u));
 	const uint8_t *src = blob + s0 - shift;                  // 16-byte aligned: the block that holds the sample's first byte
-	uint8_t *dst = slots + slot_stride * (size_t)i;
+	uint8_t *dst = T.dst ? slots + T.dst[i] : slots + slot_stride * (size_t)i;
 	const cfhd_u4 zero = { 0u, 0u, 0u, 0u };
 	for (uint32_t p = p0 + 16u * threadIdx.x; p < p1; p += 16u * DEC_INGEST_THREADS) {
 		cfhd_u4 v = zero;
@@ -93,12 +95,16 @@ __global__ void __launch_bounds__(DEC_INGEST_THREADS) k_dec_ingest(const uint8_t
 // k_dec_blank: behind the last transform launch and its conversion.  Zeroes the picture rows (row_bytes of each, nothing behind them) of every sample whose verdict is
 // not the clean word of the prepared kind or that k_dec_ingest marked: a sample that failed -- or that is decoded elsewhere -- never shows the picture an earlier pass
 // left in its place (CFHD_DecodeSample zero-fills on failure, decoder.c:11850-11859).  grid (DEC_BLANK_SPLIT, samples); clean samples cost one load.
+// A batch of two-frame groups (followers > 0: their number of table entries in front of the followers' entries): pictures 2 g and 2 g + 1 belong to the pair of
+// group g, verdicts[g] / marks[g], and its follower, verdicts[followers + g] (0: clean) / marks[followers + g]; a pair that is not clean on both sides has both zeroed.
 // ---------------------------------------------------------------------------------------------
 enum { DEC_BLANK_THREADS = 256, DEC_BLANK_SPLIT = 8 };
-__global__ void __launch_bounds__(DEC_BLANK_THREADS) k_dec_blank(const uint32_t *verdicts, const uint32_t *marks, uint32_t clean, uint8_t *pictures, size_t picture_bytes, int pitch, int row_bytes, int rows)
+__global__ void __launch_bounds__(DEC_BLANK_THREADS) k_dec_blank(const uint32_t *verdicts, const uint32_t *marks, uint32_t clean, uint8_t *pictures, size_t picture_bytes, int pitch, int row_bytes, int rows,
+                                                                 int followers = 0)
 {
 	const int i = blockIdx.y;
-	if (verdicts[i] == clean && !marks[i]) return;
+	if (followers) { const int g = i >> 1; if (verdicts[g] == clean && !marks[g] && verdicts[followers + g] == 0u && !marks[followers + g]) return; }
+	else if (verdicts[i] == clean && !marks[i]) return;
 	uint8_t *pic = pictures + picture_bytes * (size_t)i;
 	const bool longwords = !((row_bytes | pitch | (int)(picture_bytes & 3u)) & 3);      // rows of whole longwords on a longword pitch: every output but RG24 at some widths
 	for (int r = blockIdx.x; r < rows; r += DEC_BLANK_SPLIT) {

@@ -29,5 +29,14 @@ struct DecoderHandleState {
 	size_t sample_cap = 0;                                    // the longest sample the handle's device stage takes
 };
 int decoder_handle_state(void *decoder_ref, DecoderHandleState *out);
+// The same for a handle prepared on a stream of two-frame groups that has decoded its first group (the scan is known from there): 0, or -1 for any other handle.
+struct DecoderGroupState {
+	GopPlan plan;                                             // geometry and scan, as the handle decodes every group it is given
+	int out_kind = 0;
+	bool half = false;
+};
+int decoder_group_state(void *decoder_ref, DecoderGroupState *out);
+// Forgets the group the handle decoded last: the P-frame sample it is given next has no picture to hand out (the state of a freshly prepared handle).
+void decoder_group_reset(void *decoder_ref);
 
 } // namespace cfhd

@@ -184,10 +184,10 @@ int  cfhd_amd_batch_dx_stats(cfhd_amd_batch *batch, uint32_t *out16);
 /* Whether the quantizer tables of these CFHD_PrepareToEncode arguments stay put from frame to frame (1), or follow the size of the previous sample (0: rate feedback --
  * FILMSCAN2 / FILMSCAN3, LOW .. HIGH up to 1080p -- which cfhd_amd_batch_create_ex refuses and CFHD_EncodeSample applies per frame); -1: arguments no encoder takes. */
 int  cfhd_amd_quantizer_is_static(int width, int height, uint32_t pixel_format, int encoded_format, uint32_t encoding_flags, int quality);
-/* ---------------- the decode queue: batches of intra samples from any encoder, parsed and decoded on the GPU (cfhd_decode_queue.hip) ----------------
+/* ---------------- the decode queue: batches of samples from any encoder, parsed and decoded on the GPU (cfhd_decode_queue.hip) ----------------
  * What cfhd_amd_batch_* is to a caller who has just encoded, for a caller who holds a clip: nsamples samples a pass, one launch per stage for all of them, no host
  * tag walk and no device wait per picture.  Progressive and interlaced 4:2:2, RGB 4:4:4 and RGBA 4:4:4:4 samples, to every output and resolution CFHD_DecodeSample
- * serves for them; two-frame groups and Bayer samples stay with CFHD_DecodeSample. */
+ * serves for them; streams of two-frame groups through cfhd_amd_decode_batch_create_groups below; Bayer samples stay with CFHD_DecodeSample. */
 typedef struct cfhd_amd_decode_batch cfhd_amd_decode_batch;
 /* Prepares from one complete intra sample, as CFHD_PrepareToDecode prepares a handle: geometry, encoded format, precision, scan and colour space are the first
  * sample's, output_format / decoded_resolution those of CFHD_PrepareToDecode.  NULL, with the reason in cfhd_amd_last_error(), for whatever CFHD_PrepareToDecode or
@@ -195,6 +195,26 @@ typedef struct cfhd_amd_decode_batch cfhd_amd_decode_batch;
  * sequence headers, Bayer samples, samples with an UNCOMPRESS chunk, under CFHD_AMD_ENTROPY=host, for nsamples < 1 or nsamples x channels > 65 535.  The batch lives on
  * the device a cfhd_amd_batch_create_ex of the same thread would. */
 cfhd_amd_decode_batch *cfhd_amd_decode_batch_create(const void *first_sample, size_t first_size, uint32_t output_format, int decoded_resolution, int nsamples);
+/* The same batch for a stream of two-frame groups (CFHD_ENCODING_FLAGS_YUV_2FRAME_GOP, progressive or interlaced, from the reference's encoder, a camera or
+ * CFHD_EncodeSample).  Prepares from one complete group sample (TAG_SAMPLE, type 2), the way a CFHD_DecodeSample handle is prepared on the first group of a stream;
+ * every other entry point is shared and keeps its meaning per sample / picture index.  A pass carries count samples, count even and <= 2 * ngroups (an odd count: -1):
+ * entry 2g is group sample g, entry 2g + 1 the P-frame sample behind it; picture 2g is the group's first frame, picture 2g + 1 its second.  Sequence headers are not
+ * passed: a reader skips them.  What submit_host / submit_device say about alignment, registered spans, borrowed buffers, "exactly count pictures are written" and the
+ * dither seed of pass k holds unchanged.
+ * Every pair is judged alone: status[2g] and status[2g + 1] are what CFHD_DecodeSample returns for those two samples, in that order, on a handle prepared on the first
+ * group sample that has no group behind it yet.  The picture of a sample that failed is zero, and so is that of a sample the handle answers CFHD_ERROR_OKAY for without
+ * writing one (a sequence header passed as a sample).  Final on the device: a group the device parser refuses as a bad sample, with the P-frame sample behind it (no
+ * picture without its group).  Decoded as a pair by the handle inside wait: a pair with a sample the device stage does not place (a group longer than
+ * width x display height x 8 + 128 KB, a P-frame sample longer than 1 KB, a size that is no multiple of 4), a group whose scan or colour-space tag differs from the
+ * first sample's, a follower that is not a plain P-frame sample, a group only the host decides and -- when any code stream of the pass is damaged -- every pair the
+ * parser passed.
+ * NULL, with the reason in cfhd_amd_last_error(): whatever CFHD_PrepareToDecode or CFHD_DecodeSample refuses for that sample, output and resolution, with the same text
+ * (an interlaced group to YU64 at full resolution, the widths an output needs, quarter resolution); a sequence header, a P-frame sample or an intra sample as first
+ * sample; CFHD_AMD_ENTROPY=host; ngroups < 1 or 6 x ngroups > 65 535; a geometry the device's group decoder does not take (such streams stay with CFHD_DecodeSample).
+ * cfhd_amd_decode_batch_kernel_ms / _kernel_name of such a batch: 0 k_dec_ingest, 1 k_dec_parse_group, 2 the band decoder (every kernel of it, k_dec_band_two_pass --
+ * subband 7 of the groups from 8-bit RGB sources -- included), 3 k_dec_lowpass, 4 / 5 / 6 the three inverse stages in launch order (the last with the output
+ * conversion), 7 k_dec_blank; kernel_ms alone also answers 8: k_dec_band_two_pass by itself. */
+cfhd_amd_decode_batch *cfhd_amd_decode_batch_create_groups(const void *first_group_sample, size_t first_size, uint32_t output_format, int decoded_resolution, int ngroups);
 /* Waits for a pass in flight, then frees the batch. */
 void cfhd_amd_decode_batch_destroy(cfhd_amd_decode_batch *batch);
 /* One decoded picture: width x height pixels in rows of row_bytes bytes (any of the three may be NULL).  0, or -1. */
