@@ -57,9 +57,9 @@ static int prepare_group_encoder(Encoder *e)
 	if (e->gop_batch.prepare(e->params.gplan, false, e->params.pixel_kind)) return -1;
 	e->gop_ready = true;
 	e->sample.assign(2 * sample_capacity(e->params), 0);
-	// (a group whose w[3] lowpass band is divided and coded in two passes -- the 8-bit RGB inputs, cfhd_gop.h gop_temporal_lowpass_is_coded -- is written by the host
-	// writer from the GPU's coefficients: the device entropy stage codes that band as raw words only)
-	if (gpu_entropy_enabled() && !gop_temporal_lowpass_is_coded(e->params.gplan) && e->gop_batch.prepare_entropy(e->sample.size())) return -1;
+	// (a group whose w[3] lowpass band is divided and coded in two passes -- the 8-bit RGB inputs, cfhd_gop.h gop_temporal_lowpass_is_coded -- takes the device stage
+	// too: k_ent_split_two_pass in front of the count stage)
+	if (gpu_entropy_enabled() && e->gop_batch.prepare_entropy(e->sample.size())) return -1;
 	return 0;
 }
 

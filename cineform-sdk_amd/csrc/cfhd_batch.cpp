@@ -231,13 +231,14 @@ long long gop_finish(cfhd_amd_batch *b)
 }
 void gop_drain(cfhd_amd_batch *b) { (void)b->genc->wait(); if (b->decode) (void)b->gdec->wait(); }
 
-// A batch of two-frame groups (cfhd_amd_batch_create_ex with CFHD_ENCODING_FLAGS_YUV_2FRAME_GOP), or null: never a batch that does something else.
-cfhd_amd_batch *create_group_batch(const FrontEndParams &fp, int width, int height, int nframes, int nthreads, int mode)
+// A batch of two-frame groups (cfhd_amd_batch_create_ex with CFHD_ENCODING_FLAGS_YUV_2FRAME_GOP, cfhd_amd_batch_create_groups), or null: never a batch that does
+// something else.  coded_lowpass: groups whose w[3] lowpass band is divided and coded in two passes (the 8-bit RGB inputs) are taken too -- cfhd_amd_batch_create_groups;
+// cfhd_amd_batch_create_ex keeps refusing them, as the callers that probe with it expect.
+cfhd_amd_batch *create_group_batch(const FrontEndParams &fp, int width, int height, int nframes, int nthreads, int mode, bool coded_lowpass)
 {
 	const int kind = fp.pixel_kind;
-	// whole groups; tables that never move (the group twin of the intra rule below); a w[3] lowpass band the device stage codes (the 8-bit RGB inputs' is the host
-	// writer's); round trips to the input's own format where a group decodes to it
-	if (nframes < 2 || (nframes & 1) || !fp.gop_static_quantizer || gop_temporal_lowpass_is_coded(fp.gplan)) return nullptr;
+	// whole groups; tables that never move (the group twin of the intra rule below); round trips to the input's own format where a group decodes to it
+	if (nframes < 2 || (nframes & 1) || !fp.gop_static_quantizer || (gop_temporal_lowpass_is_coded(fp.gplan) && !coded_lowpass)) return nullptr;
 	if (mode != 0 && mode != 1) return nullptr;
 	if (mode == 0 && !fp.gop_output_served) return nullptr;
 	const char *e = getenv("CFHD_AMD_ENTROPY");
@@ -263,6 +264,8 @@ cfhd_amd_batch *create_group_batch(const FrontEndParams &fp, int width, int heig
 		if (!b->decode) return true;
 		// the decoder's plan is the sample's: geometry and scan (its quantizers travel in the sample)
 		if (b->gdec->prepare(b->gplan, true, kind, false, ng) || b->gdec->prepare_entropy_decode()) return false;
+		// (subband 7 coded in two passes: only where the device group decoder takes it -- dev::DecGroupPlan::two_pass)
+		if (gop_temporal_lowpass_is_coded(b->gplan) && !b->gdec->batch_entropy().two_pass_served()) return false;
 		// the outputs that convert to RGB take the matrix of the colour space the group samples are tagged with (frame 1 of every group: 709, GopBatch::fill_jobs)
 		b->gdec->set_color_matrix((fp.color_space & 3) == 1 ? 2 : 0);
 		return true;
@@ -294,7 +297,7 @@ cfhd_amd_batch *cfhd_amd_batch_create_ex(int width, int height, uint32_t pixel_f
 	// A batch encodes its frames in one launch with one set of quantizer tables.  Qualities whose tables follow the size of the previous sample
 	// (FILMSCAN2/3, LOW..HIGH up to 1080p: encoder.c:3414 -> quantize.c:2869) need frame i's sample before frame i + 1 can start -- those
 	// sequences go through CFHD_EncodeSample, which applies the feedback per frame; here they are refused instead of encoded differently.
-	if (fp.gop) return create_group_batch(fp, width, height, nframes, nthreads, mode);
+	if (fp.gop) return create_group_batch(fp, width, height, nframes, nthreads, mode, false);
 	if (!fp.static_quantizer) return nullptr;
 	const int kind = fp.pixel_kind;
 	const bool yuv = kind == PIX_YUY2 || kind == PIX_2VUY;
@@ -346,6 +349,16 @@ cfhd_amd_batch *cfhd_amd_batch_create_ex(int width, int height, uint32_t pixel_f
 	b->samples.resize(nframes); b->sample_size.assign(nframes, 0);
 	if (!b->gpu_entropy) for (auto &s : b->samples) s.resize(cap);
 	return b;
+}
+
+// Two-frame groups from any input cfhd_amd_batch_create_ex takes with encoded format 0 and CFHD_ENCODING_FLAGS_YUV_2FRAME_GOP (implied here) -- the same batch, byte
+// for byte -- and from RG24 / BGRA / BGRa, whose subband 7 is divided and coded in two passes (k_ent_split_two_pass; mode 0: k_dec_band_two_pass).
+cfhd_amd_batch *cfhd_amd_batch_create_groups(int width, int height, uint32_t pixel_format, uint32_t encoding_flags, int quality, int nframes, int nthreads, int mode)
+{
+	CallerDevice caller_device;
+	FrontEndParams fp;
+	if (nframes < 1 || front_end_params(width, height, pixel_format, 0, encoding_flags | (1u << 1) /* CFHD_ENCODING_FLAGS_YUV_2FRAME_GOP */, quality, &fp) || !fp.gop) return nullptr;
+	return create_group_batch(fp, width, height, nframes, nthreads, mode, true);
 }
 
 cfhd_amd_batch *cfhd_amd_batch_create(int width, int height, uint32_t pixel_format, int quality, int nframes, int nthreads)

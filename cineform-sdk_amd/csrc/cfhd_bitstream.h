@@ -78,7 +78,8 @@ struct BandSource {
 // inserts payloads (holes: raw lowpass words, entropy coded bands) and the size fields that depend on the payload sizes.
 // A template byte at offset x preceded by h holes ends up at x + (sum of the sizes of the first h holes) in the sample.
 struct SampleTemplate {
-	struct Hole { int tmpl_offset; int kind /*0 = lowpass raw, 1 = coded band, 2 = peak table of the coded band in front of it (empty when the band has no peaks; fixed_bytes: the band's divisor)*/; int channel, level, band; int fixed_bytes; };
+	struct Hole { int tmpl_offset; int kind /*0 = lowpass raw, 1 = coded band, 2 = peak table of the coded band in front of it (empty when the band has no peaks; fixed_bytes: the band's divisor)*/; int channel, level, band; int fixed_bytes;
+	              int pass; /* kind 1: 0 the band as it lies in the pyramid; 1, 2: that pass of a band coded in two (cfhd_gop.cpp vlc_encode_band_two_pass) */ };
 	struct Patch {          // kind 0: 24/16-bit chunk size at (at_tmpl, at_holes), chunk ends at (end_tmpl, end_holes)
 		int kind;           // kind 1: 32-bit big-endian byte count end - start written at at_tmpl (channel index entry)
 		                    // kind 2: the three peak tags at (at_tmpl, at_holes) of the table in hole start_holes, which begins at (end_tmpl, end_holes); tag: the band's divisor.  Left zero when the hole is empty.
@@ -117,7 +118,7 @@ struct TemplateRecorder {
 		p.start_tmpl = ch_start_tmpl; p.start_holes = ch_start_holes; p.end_tmpl = (int)b.size(); p.end_holes = holes;
 		t.patches.push_back(p);
 	}
-	void hole(int kind, int c, int lv, int bnd, int fixed) { SampleTemplate::Hole h = { (int)b.size(), kind, c, lv, bnd, fixed }; t.holes.push_back(h); holes++; }
+	void hole(int kind, int c, int lv, int bnd, int fixed, int pass = 0) { SampleTemplate::Hole h = { (int)b.size(), kind, c, lv, bnd, fixed, pass }; t.holes.push_back(h); holes++; }
 	// The peak table of a difference-coded band (codec.c:1804-1809, encoder.c:6543-6585): three optional tags in front of the band's size chunk, zero while the band has
 	// no values beyond the threshold, and behind the band trailer the table chunk -- a hole that stays empty for such a band.  The device fills both (k_ent_layout, k_ent_peaks).
 	int peak_at_tmpl = 0, peak_at_holes = 0;

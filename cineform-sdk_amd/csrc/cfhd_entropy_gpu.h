@@ -59,7 +59,7 @@ public:
 	bool peak_flags_in_use() const { return group_ ? gplan_.interlaced : plan_.interlaced; }
 	size_t sample_cap() const { return cap_; }
 	int total_segments() const { return total_segs_; }
-	// HIP-event time of kernel k of the last launch() (0 k_ent_count -- when the level-1 bands are counted on the second stream: the launches on the main stream
+	// HIP-event time of kernel k of the last launch() (0 k_ent_count, with k_ent_split_two_pass in front of it where a group's subband 7 is coded in two passes -- when the level-1 bands are counted on the second stream: the launches on the main stream
 	// only --, 1 k_ent_scan, 2 k_ent_sizes + k_ent_pack_offsets + k_ent_layout, 3 k_ent_emit, 4 the level-1 part of k_ent_count on the second stream, 0 when there is none); valid once the stream was synchronised
 	float kernel_ms(int k);
 	// Events of the last launch() on the encoder's stream: every sample's header, size fields and raw lowpass bands are in place
@@ -96,6 +96,7 @@ private:
 	bool split_ = false, serial_split_ = false; void *ev_level1_ = nullptr, *stream2_ = nullptr, *ev2_[3] = {nullptr, nullptr, nullptr};      // the level-1 part of k_ent_count on its own stream
 	int16_t *d_coeffs_ = nullptr; size_t coeff_stride_ = 0;
 	void *d_blocks_ = nullptr; unsigned long long *d_masks_ = nullptr; size_t masks_per_frame_ = 0; bool use_blocks_ = false;
+	int16_t *d_scratch_ = nullptr; size_t scratch_stride_ = 0;      // groups whose subband 7 is coded in two passes: the planes of the passes (k_ent_split_two_pass), scratch_stride_ elements a group
 };
 
 
@@ -207,7 +208,8 @@ private:
 // up to kLowLatencyFrames groups), k_dec_undiff and k_dec_lowpass over all groups.  Nothing touches the host between the coder and the inverse transform.
 // (The chunk-indexed decoder of the intra batches, k_dec_index / k_dec_tiles, does not know group pyramids yet: DESIGN.md names it as the follow-up.)
 // The decode queue (cfhd_decode_queue.hip) brings group samples of any encoder instead: every group in a slot of its own, the P-frame sample behind it in another,
-// a verdict per pair (set_samples_slots, set_verdicts), and subband 7 of the groups from 8-bit RGB sources decoded by k_dec_band_two_pass.
+// a verdict per pair (set_samples_slots, set_verdicts), and subband 7 of the groups from 8-bit RGB sources decoded by k_dec_band_two_pass -- as it is for the
+// coder's dense buffer when the batch's own plan codes that band (the frame queue's groups from RG24 / BGRA / BGRa).
 class GpuGroupBatchEntropyDecoder {
 public:
 	GpuGroupBatchEntropyDecoder() {}
@@ -229,15 +231,16 @@ public:
 	void set_producer_events(void *headers, void *payloads) { ev_headers_ = headers; ev_payloads_ = payloads; }      // the parser waits for the first, the band decoder for the second
 	int launch();                        // async
 	int check();                         // after the stream was synchronised: 0 when every sample parsed and every band decoded cleanly
-	float kernel_ms(int k);              // last launch(): 0 k_dec_parse_group, 1 the band decoder (both code sets + k_dec_undiff + k_dec_band_two_pass), 2 k_dec_lowpass, 3 k_dec_band_two_pass alone (launched for sample slots only)
+	float kernel_ms(int k);              // last launch(): 0 k_dec_parse_group, 1 the band decoder (both code sets + k_dec_undiff + k_dec_band_two_pass), 2 k_dec_lowpass, 3 k_dec_band_two_pass alone (launched for sample slots, and for a dense buffer of groups whose plan codes subband 7)
 	const char *band_kernel() const;     // the band decoder's shape for this batch, as a profiler shows it
+	bool two_pass_served() const { return two_pass_ok_; }      // after prepare(): subband 7 lies where k_dec_band_two_pass takes it (a batch of groups from 8-bit RGB decodes only then)
 	void release();
 private:
 	GopPlan plan_; int n_ = 0, out_kind_ = 0, device_ = 0, slots17_ = 0, slots18_ = 0; size_t coeff_stride_ = 0; void *stream_ = nullptr;
 	int16_t *d_coeffs_ = nullptr;
 	const uint8_t *ext_samples_ = nullptr; const uint32_t *ext_sizes_ = nullptr, *ext_offsets_ = nullptr;
 	size_t ext_stride_ = 0, follower_stride_ = 0; const uint8_t *ext_followers_ = nullptr; const uint32_t *ext_follower_sizes_ = nullptr;      // set_samples_slots()
-	uint32_t *d_verdicts_ = nullptr; int active_ = 0; bool two_pass_timed_ = false;
+	uint32_t *d_verdicts_ = nullptr; int active_ = 0; bool two_pass_timed_ = false, two_pass_ok_ = false;
 	int active_groups() const { return active_ > 0 && active_ < n_ ? active_ : n_; }
 	void *d_tables_ = nullptr, *d_tables18_ = nullptr, *d_plan_ = nullptr, *d_bandjobs_ = nullptr, *d_lowjobs_ = nullptr, *d_diffjobs_ = nullptr, *d_twojobs_ = nullptr;
 	int *d_errors_ = nullptr, *h_errors_ = nullptr;

@@ -22,8 +22,9 @@ GpuEntropyEncoder::~GpuEntropyEncoder() { release(); delete host_; }
 void GpuEntropyEncoder::release()
 {
 	(void)hipSetDevice(device_);
-	void *dev[] = { d_sizes_, d_tables_, d_bands_, d_segband_, d_segs_, d_bandstate_, d_frames_, d_tmpl_, d_packed_, d_offsets_, d_tokens_, d_blocks_, d_masks_ };
+	void *dev[] = { d_sizes_, d_tables_, d_bands_, d_segband_, d_segs_, d_bandstate_, d_frames_, d_tmpl_, d_packed_, d_offsets_, d_tokens_, d_blocks_, d_masks_, d_scratch_ };
 	for (void *p : dev) if (p) (void)hipFree(p);
+	d_scratch_ = nullptr; scratch_stride_ = 0;
 	if (h_samples_) (void)hipHostFree(h_samples_);
 	if (h_sizes_) (void)hipHostFree(h_sizes_);
 	if (h_offsets_) (void)hipHostFree(h_offsets_);
@@ -93,7 +94,14 @@ int GpuEntropyEncoder::prepare_units(int nframes, int16_t *d_coeffs, size_t stri
 	const bool fills_chip = (size_t)n_ * stride / dev::ENT_SEG >= (size_t)kWaveSlots;
 	auto seg_env = [&](const char *name, int dflt) { const char *e = getenv(name); const int v = e ? atoi(e) : 0; return ent_seg_len_ok(v) ? v : (fills_chip ? dflt : (int)dev::ENT_SEG); };
 	const EntSegRule rule = { seg_env("CFHD_AMD_SEG_L1_DENSE", dev::ENT_SEG_L1_DENSE), seg_env("CFHD_AMD_SEG_L2", dev::ENT_SEG_L2), seg_env("CFHD_AMD_SEG_L3", dev::ENT_SEG_L3), lists };
-	if (!ent_build_band_jobs(host_->geom, tmpl_[0], n_, d_coeffs, stride, &jobs, lists ? l1_seg_env : (int)dev::ENT_SEG, &rule)) return -3;
+	// a group whose subband 7 is coded in two passes (8-bit RGB sources): the planes k_ent_split_two_pass fills for the two holes of every channel, the encoder's own
+	scratch_stride_ = group_ ? ent_scratch_stride(gplan_) : 0;
+	if (scratch_stride_) {
+		dev::EntSplitJob probe;
+		if (!ent_split_job(gplan_, d_coeffs, stride, nullptr, &probe)) return -3;
+		HIPCHK(hipMalloc((void **)&d_scratch_, scratch_stride_ * 2 * (size_t)n_));
+	}
+	if (!ent_build_band_jobs(host_->geom, tmpl_[0], n_, d_coeffs, stride, &jobs, lists ? l1_seg_env : (int)dev::ENT_SEG, &rule, d_scratch_, scratch_stride_)) return -3;
 	nbands_ = jobs.nbands; total_segs_ = (int)jobs.segjobs.size(); tok_per_frame_ = jobs.tok_per_frame;
 	HIPCHK(hipMalloc(&d_bands_, jobs.bands.size() * sizeof(dev::EntBandJob)));
 	HIPCHK(hipMemcpy(d_bands_, jobs.bands.data(), jobs.bands.size() * sizeof(dev::EntBandJob), hipMemcpyHostToDevice));
@@ -165,13 +173,14 @@ int GpuEntropyEncoder::launch()
 	const int count_probe = 0;
 #endif
 	const dev::EntBlockLists lists = { (const uint4 *)d_blocks_, d_masks_, d_coeffs_, masks_per_frame_ };
-	auto count_range = [&](hipStream_t s, int lo, int n, bool level1 = false) {
+	auto count_range = [&](hipStream_t s, int lo, int n, bool level1 = false, const dev::EntBatchGeom *other = nullptr) {
+		const dev::EntBatchGeom &g = other ? *other : geom;      // (other: the segments that read the scratch buffer)
 		const int total = n * act;
 		if (level1 && use_blocks_)
-			dev::k_ent_count_blocks<<<(total + dev::ENT_WAVES - 1) / dev::ENT_WAVES, dev::ENT_THREADS, 0, s>>>((const dev::EntSegJob *)d_segband_, geom, total, (dev::EntSegState *)d_segs_, T,
+			dev::k_ent_count_blocks<<<(total + dev::ENT_WAVES - 1) / dev::ENT_WAVES, dev::ENT_THREADS, 0, s>>>((const dev::EntSegJob *)d_segband_, g, total, (dev::EntSegState *)d_segs_, T,
 			                                                                                                 d_sizes_ + n_, (uint32_t *)d_tokens_, lo, n, lists);
 		else
-			dev::k_ent_count<<<(total + dev::ENT_WAVES - 1) / dev::ENT_WAVES, dev::ENT_THREADS, 0, s>>>((const dev::EntSegJob *)d_segband_, geom, total, (dev::EntSegState *)d_segs_, T,
+			dev::k_ent_count<<<(total + dev::ENT_WAVES - 1) / dev::ENT_WAVES, dev::ENT_THREADS, 0, s>>>((const dev::EntSegJob *)d_segband_, g, total, (dev::EntSegState *)d_segs_, T,
 			                                                                                          d_sizes_ + n_, (uint32_t *)d_tokens_, lo, n, count_probe);
 	};
 	// CFHD_AMD_COUNT_SPLIT=0: (A/B) the level-1 bands counted on the main stream behind the level-2 / level-3 transforms instead of beside them
@@ -183,14 +192,29 @@ int GpuEntropyEncoder::launch()
 	if (s1 != st) HIPCHK(hipStreamWaitEvent(s1, (hipEvent_t)ev_level1_, 0));
 	// the peak flags are raised by the difference-coded band only, a level-1 band: cleared on the stream that counts it
 	if (peak_flags_in_use()) HIPCHK(hipMemsetAsync(d_sizes_ + n_, 0, sizeof(uint32_t) * n_, s1));
+	// subband 7 in two passes: the two planes of every group and channel in one launch, behind the transforms and the division on the main stream; their segments are
+	// counted apart from the others, with the scratch buffer's stride between the groups -- so a pass over such groups always counts range by range
+	const std::vector<std::pair<int, int>> &scratch_ranges = host_->jobs.ranges_scratch;
+	const dev::EntBatchGeom geom_scratch = { geom.segs_per_frame, geom.bands_per_frame, scratch_stride_, geom.tok_per_frame };
+	dev::EntSplitJob sj;
+	if (!scratch_ranges.empty() && !ent_split_job(gplan_, d_coeffs_, coeff_stride_, d_scratch_, &sj)) return -3;
+	auto count_scratch = [&] {      // (on the main stream, inside the span kernel_ms(0) times)
+		if (scratch_ranges.empty()) return;
+		uint32_t longest = 0;
+		for (int c = 0; c < 3; c++) longest = sj.band[c].n > longest ? sj.band[c].n : longest;
+		dev::k_ent_split_two_pass<<<dim3((longest / 8 + dev::ENT_THREADS - 1) / dev::ENT_THREADS, 3u * (unsigned)act), dev::ENT_THREADS, 0, st>>>(sj);
+		for (const auto &r : scratch_ranges) count_range(st, r.first, r.second, false, &geom_scratch);
+	};
 	if (split_) {
 		HIPCHK(hipEventRecord((hipEvent_t)ev2_[0], s1));
 		for (const auto &r : host_->jobs.ranges_l1) count_range(s1, r.first, r.second, true);
 		HIPCHK(hipEventRecord((hipEvent_t)ev2_[1], s1));
+		count_scratch();
 		for (const auto &r : host_->jobs.ranges_rest) count_range(st, r.first, r.second);
 		HIPCHK(hipEventRecord((hipEvent_t)ev2_[2], st));
 		if (s1 != st) HIPCHK(hipStreamWaitEvent(st, (hipEvent_t)ev2_[1], 0));
-	} else if (use_blocks_) {
+	} else if (use_blocks_ || !scratch_ranges.empty()) {
+		count_scratch();
 		for (const auto &r : host_->jobs.ranges_l1) count_range(st, r.first, r.second, true);
 		for (const auto &r : host_->jobs.ranges_rest) count_range(st, r.first, r.second);
 	} else count_range(st, 0, total_segs_ / n_);
@@ -800,7 +824,7 @@ int GpuGroupBatchEntropyDecoder::prepare(const GopPlan &plan, int ngroups, int16
 	for (int c = 0; c < 3; c++) if ((plan.ch[c].w[3].offset[0] & 7) || (plan.ch[c].w[3].pitch & 7) || (stride & 7)) dp.two_pass = 0;
 	std::stable_sort(coded.begin(), coded.end(), [](const Coded &a, const Coded &b) { return a.table != b.table ? a.table < b.table : a.area > b.area; });
 	for (size_t s = 0; s < coded.size(); s++) { dp.band[coded[s].c][coded[s].k][coded[s].b].slot = (int)s; if (coded[s].table) dp.slots18++; else dp.slots17++; }
-	slots17_ = dp.slots17; slots18_ = dp.slots18;
+	slots17_ = dp.slots17; slots18_ = dp.slots18; two_pass_ok_ = dp.two_pass != 0;
 	if (slots17_ + slots18_ != kGroupBandJobs || slots18_ != (plan.interlaced ? kGroupDiffJobs : 0)) return -3;
 	// one job per workgroup in gridDim.x (k_dec_bands_par, k_dec_undiff), the raw bands in gridDim.y (k_dec_lowpass: 65 535)
 	if ((long long)kGroupRawJobs * n_ > 65535) return -5;
@@ -851,6 +875,8 @@ int GpuGroupBatchEntropyDecoder::launch()
 	// the groups of this pass: the job tables are [slot][n], the launches n times as long
 	const int ng = active_groups();
 	const bool slots = ext_followers_ != nullptr;
+	// subband 7 coded in two passes: whatever the sample says in the slots of the decode queue; in the coder's dense buffer where the batch's own plan codes it so
+	const bool two_pass = slots || (two_pass_ok_ && gop_temporal_lowpass_is_coded(plan_));
 	HIPCHK(hipMemsetAsync(d_errors_, 0, sizeof(int), st));
 	(void)hipGetLastError();
 	// the parser reads the headers and size fields only (k_ent_layout): it runs beside k_ent_emit, the band decoder waits for the payloads
@@ -859,7 +885,7 @@ int GpuGroupBatchEntropyDecoder::launch()
 	dev::k_dec_parse_group<<<ng, dev::DEC_PARSE_THREADS, 0, st>>>(ext_samples_, ext_offsets_, ext_sizes_, ng, (const dev::DecGroupPlan *)d_plan_, d_coeffs_, coeff_stride_,
 	                                                              (dev::DecBandJob *)d_bandjobs_, (dev::DecLowpassJob *)d_lowjobs_, (dev::DecDiffJob *)d_diffjobs_, d_errors_,
 	                                                              ext_stride_, slots ? d_verdicts_ : nullptr, slots ? d_verdicts_ + n_ : nullptr, ext_followers_, follower_stride_, ext_follower_sizes_,
-	                                                              slots ? (dev::DecTwoPassJob *)d_twojobs_ : nullptr);
+	                                                              two_pass ? (dev::DecTwoPassJob *)d_twojobs_ : nullptr);
 	HIPCHK(hipEventRecord((hipEvent_t)ev_[1], st));
 	if (ev_payloads_) HIPCHK(hipStreamWaitEvent(st, (hipEvent_t)ev_payloads_, 0));
 	ev_headers_ = ev_payloads_ = nullptr;
@@ -875,12 +901,12 @@ int GpuGroupBatchEntropyDecoder::launch()
 		bands((const dev::DecBandJob *)d_bandjobs_ + (size_t)slots17_ * ng, slots18_ * ng, d_tables18_);
 		dev::k_dec_undiff<<<dim3((unsigned)(kGroupDiffJobs * ng), dev::DXU_SPLIT), dev::DXU_THREADS, 0, st>>>((const dev::DecDiffJob *)d_diffjobs_, d_errors_, 0);
 	}
-	if (slots) {
+	if (two_pass) {
 		// subband 7 of the groups from 8-bit RGB sources: a workgroup per (group, channel), the jobs of raw-word groups are empty
 		HIPCHK(hipEventRecord((hipEvent_t)ev_[5], st));
 		dev::k_dec_band_two_pass<<<3 * ng, dev::DECP_THREADS, 0, st>>>((const dev::DecTwoPassJob *)d_twojobs_, (const dev::DecTables *)d_tables18_, d_errors_);
 	}
-	two_pass_timed_ = slots;
+	two_pass_timed_ = two_pass;
 	HIPCHK(hipEventRecord((hipEvent_t)ev_[3], st));
 	dev::k_dec_lowpass<<<dim3(8, (unsigned)(kGroupRawJobs * ng)), 256, 0, st>>>((const dev::DecLowpassJob *)d_lowjobs_);
 	HIPCHK(hipGetLastError());

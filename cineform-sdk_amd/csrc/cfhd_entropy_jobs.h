@@ -224,14 +224,16 @@ struct EntHostJobs {
 	std::vector<dev::EntSegJob> segjobs;
 	std::vector<int> band_of_hole;      // template hole -> band job of frame 0 (-1 for lowpass holes)
 	int nbands = 0;                     // coded bands per frame
-	// segment ranges [first, count) inside one frame's table: the level-1 bands (final once the level-1 transform has run) and everything else
-	std::vector<std::pair<int, int>> ranges_l1, ranges_rest;
+	// segment ranges [first, count) inside one frame's table: the level-1 bands (final once the level-1 transform has run), the planes in the encoder's scratch buffer
+	// (EntHoleGeom::scratch: counted with the scratch buffer's stride between the frames) and everything else
+	std::vector<std::pair<int, int>> ranges_l1, ranges_rest, ranges_scratch;
 	size_t tok_per_frame = 0;           // token slots of one frame's segments (EntBatchGeom::tok_per_frame)
 };
 
 // Where the holes of a template find their coefficients: the band of the pyramid behind every hole, in template order (the same for every frame of a batch).
 struct EntHoleGeom { size_t offset; int width, height, pitch; int table /* 0: code set 17, 1: code set 18 */; int mask_base /* block lists: first mask, or -1 */; bool level1;
-                     int level /* pyramid level of the band: 1, 2, 3 (what EntSegRule goes by) */; };
+                     int level /* pyramid level of the band: 1, 2, 3 (what EntSegRule goes by) */;
+                     bool peaks /* coded with peaks (dev::EntBandJob::peaks) */; bool scratch /* offset counts inside a frame's part of the encoder's scratch buffer, not inside its pyramid */; };
 inline std::vector<EntHoleGeom> ent_hole_geometry(const FramePlan &plan, const SampleTemplate &t)
 {
 	int mask_base[kMaxChannels][kNumBands];
@@ -241,20 +243,52 @@ inline std::vector<EntHoleGeom> ent_hole_geometry(const FramePlan &plan, const S
 		const BandDesc &bd = plan.ch[hole.channel].band[hole.level][hole.band];
 		g.push_back(EntHoleGeom{ bd.offset, bd.width, bd.height, bd.pitch,
 		                         plan.interlaced && hole.level == 0 && hole.band == 2 ? 1 : 0,      // subband 8 of the channel (cfhd_bitstream.cpp walk_sample)
-		                         hole.kind == 1 && hole.level == 0 ? mask_base[hole.channel][hole.band] : -1, hole.level == 0, hole.level + 1 });
+		                         hole.kind == 1 && hole.level == 0 ? mask_base[hole.channel][hole.band] : -1, hole.level == 0, hole.level + 1,
+		                         plan.interlaced && hole.level == 0 && hole.band == 2, false });
 	}
 	return g;
 }
 // a two-frame group (cfhd_gop.cpp walk_group_sample): `level` is the wavelet index; the bands of the two frame wavelets are final once level 1 of both frames has run
+// The two passes of a coded subband 7 (SampleTemplate::Hole::pass) read a plane each of the encoder's scratch buffer, where k_ent_split_two_pass leaves what they code:
+// the planes of channel 0 pass 1, pass 2, channel 1 ... one behind the other, each on a 128-byte boundary (ent_split_job below names the same places).  Code set 18
+// without peaks: the passes hold +-251 .. 255 as ordinary values.
+inline size_t ent_scratch_plane_elems(const GopWavelet &wv) { return ((size_t)wv.pitch * wv.height + 63) & ~(size_t)63; }
+inline size_t ent_scratch_stride(const GopPlan &plan)
+{
+	size_t at = 0;
+	if (gop_temporal_lowpass_is_coded(plan)) for (int c = 0; c < plan.num_channels; c++) at += 2 * ent_scratch_plane_elems(plan.ch[c].w[3]);
+	return at;
+}
+inline size_t ent_scratch_plane(const GopPlan &plan, int channel, int pass)
+{
+	size_t at = 0;
+	for (int c = 0; c < channel; c++) at += 2 * ent_scratch_plane_elems(plan.ch[c].w[3]);
+	return at + (pass == 2 ? ent_scratch_plane_elems(plan.ch[channel].w[3]) : 0);
+}
 inline std::vector<EntHoleGeom> ent_hole_geometry(const GopPlan &plan, const SampleTemplate &t)
 {
 	std::vector<EntHoleGeom> g;
 	for (const SampleTemplate::Hole &hole : t.holes) {
 		const GopWavelet &wv = plan.ch[hole.channel].w[hole.level];
-		g.push_back(EntHoleGeom{ wv.offset[hole.band], wv.width, wv.height, wv.pitch, gop_band_is_difference_coded(plan, hole.level, hole.band) ? 1 : 0, -1, hole.level < 2,
-		                         hole.level < 2 ? 1 : (hole.level < 5 ? 2 : 3) });      // (w[3] and w[4] are as large as an intra frame's level 2, w[5] as its level 3; code set 18: subbands 12 and 15 of an interlaced group)
+		if (hole.kind == 1 && hole.pass) { g.push_back(EntHoleGeom{ ent_scratch_plane(plan, hole.channel, hole.pass), wv.width, wv.height, wv.pitch, 1, -1, false, 2, false, true }); continue; }
+		const bool diff = gop_band_is_difference_coded(plan, hole.level, hole.band);
+		g.push_back(EntHoleGeom{ wv.offset[hole.band], wv.width, wv.height, wv.pitch, diff ? 1 : 0, -1, hole.level < 2,
+		                         hole.level < 2 ? 1 : (hole.level < 5 ? 2 : 3), diff, false });      // (w[3] and w[4] are as large as an intra frame's level 2, w[5] as its level 3; code set 18: subbands 12 and 15 of an interlaced group)
 	}
 	return g;
+}
+// k_ent_split_two_pass's job for a batch of groups; false: the plan codes no subband 7, or one the kernel's 16-byte accesses do not take
+inline bool ent_split_job(const GopPlan &plan, const int16_t *coeffs, size_t coeff_stride, int16_t *scratch, dev::EntSplitJob *job)
+{
+	if (!gop_temporal_lowpass_is_coded(plan) || plan.num_channels != 3 || (coeff_stride & 7)) return false;
+	job->coeffs = coeffs; job->coeff_stride = coeff_stride; job->scratch = scratch; job->scratch_stride = ent_scratch_stride(plan);
+	for (int c = 0; c < 3; c++) {
+		const GopWavelet &wv = plan.ch[c].w[3];
+		const size_t n = (size_t)wv.pitch * wv.height;
+		if ((wv.offset[0] & 7) || (n & 7) || wv.offset[0] + n > coeff_stride || wv.offset[0] + n >= ((size_t)1 << 32)) return false;
+		job->band[c] = dev::EntSplitBand{ (uint32_t)wv.offset[0], (uint32_t)n, (uint32_t)ent_scratch_plane(plan, c, 1), (uint32_t)ent_scratch_plane(plan, c, 2) };
+	}
+	return true;
 }
 
 // Segment lengths of the bands coded with table 0 that are counted densely (k_ent_count), by pyramid level: multiples of dev::ENT_SEG up to dev::ENT_SEG_MAX.
@@ -267,12 +301,13 @@ inline bool ent_seg_len_ok(int v) { return v >= dev::ENT_SEG && v <= dev::ENT_SE
 // l1_seg: segment length of the level-1 bands that are coded with table 0 from block lists (k_ent_count_blocks; the caller opts in when it has allocated them):
 // a multiple of dev::ENT_SEG up to dev::ENT_SEG_MAX.  Every other band -- and every band by default -- has segments of dev::ENT_SEG, unless the caller passes a
 // rule: then the other bands coded with table 0 take the rule's length for their level.  A band coded with table 1 has segments of dev::ENT_SEG whatever is asked.
+// scratch, scratch_stride: the encoder's scratch buffer and the elements between two frames' parts of it, for the holes whose geometry says `scratch`.
 inline bool ent_build_band_jobs(const std::vector<EntHoleGeom> &geom, const SampleTemplate &t0, int nframes, int16_t *coeffs, size_t stride, EntHostJobs *out,
-                                int l1_seg = dev::ENT_SEG, const EntSegRule *rule = nullptr)
+                                int l1_seg = dev::ENT_SEG, const EntSegRule *rule = nullptr, int16_t *scratch = nullptr, size_t scratch_stride = 0)
 {
 	if ((int)t0.holes.size() > dev::ENT_MAX_HOLES || (int)t0.patches.size() > kEntMaxPatches || geom.size() != t0.holes.size()) return false;
 	if (!ent_seg_len_ok(l1_seg) || (rule && !(ent_seg_len_ok(rule->l1_dense) && ent_seg_len_ok(rule->l2) && ent_seg_len_ok(rule->l3)))) return false;
-	out->bands.clear(); out->segjobs.clear(); out->ranges_l1.clear(); out->ranges_rest.clear();
+	out->bands.clear(); out->segjobs.clear(); out->ranges_l1.clear(); out->ranges_rest.clear(); out->ranges_scratch.clear();
 	out->tok_per_frame = 0;
 	out->band_of_hole.assign(t0.holes.size(), -1);
 	for (int f = 0; f < nframes; f++) {
@@ -283,21 +318,22 @@ inline bool ent_build_band_jobs(const std::vector<EntHoleGeom> &geom, const Samp
 			if (hole.kind != 1) continue;
 			const EntHoleGeom &bd = geom[h];
 			dev::EntBandJob j;
-			j.coeffs = base + bd.offset; j.n = bd.height * bd.pitch;
+			if (bd.scratch && (!scratch || bd.offset + (size_t)bd.height * bd.pitch > scratch_stride)) return false;
+			j.coeffs = (bd.scratch ? scratch + (size_t)f * scratch_stride : base) + bd.offset; j.n = bd.height * bd.pitch;
 			int len = bd.level1 && bd.table == 0 && bd.mask_base >= 0 ? l1_seg : (int)dev::ENT_SEG;      // (table 1 keeps ENT_SEG: EntSegState::peaks)
 			if (rule && bd.table == 0 && !(bd.level1 && bd.mask_base >= 0 && rule->lists)) len = bd.level1 ? rule->l1_dense : (bd.level <= 2 ? rule->l2 : rule->l3);
 			j.nseg = (j.n + len - 1) / len; j.seg_base = (int)out->segjobs.size();
 			j.frame = f; j.hole = (int)h;
-			j.table = bd.table;
+			j.table = bd.table; j.peaks = bd.peaks ? 1 : 0;
 			if (f == 0) {
 				out->band_of_hole[h] = (int)out->bands.size();
-				std::vector<std::pair<int, int>> &r = bd.level1 ? out->ranges_l1 : out->ranges_rest;
+				std::vector<std::pair<int, int>> &r = bd.scratch ? out->ranges_scratch : (bd.level1 ? out->ranges_l1 : out->ranges_rest);
 				if (!r.empty() && r.back().first + r.back().second == j.seg_base) r.back().second += j.nseg; else r.push_back({ j.seg_base, j.nseg });
 			}
 			for (int s = 0; s < j.nseg; s++) {
 				// token slots: the segment's coefficients up to the band's end, in whole ENT_TOK_STRIDE (every coefficient may be a token); frame 0's table holds them
 				const int first = s * len, slots = ((j.n - first < len ? j.n - first : len) + dev::ENT_TOK_STRIDE - 1) / dev::ENT_TOK_STRIDE * dev::ENT_TOK_STRIDE;
-				out->segjobs.push_back(dev::EntSegJob{ j.coeffs, j.n, first, (int)out->bands.size(), j.table, bd.pitch, bd.mask_base, len, (int)tok_at });
+				out->segjobs.push_back(dev::EntSegJob{ j.coeffs, j.n, first, (int)out->bands.size(), j.table, bd.pitch, bd.mask_base, len, (int)tok_at, j.peaks });
 				tok_at += (size_t)slots;
 			}
 			out->bands.push_back(j);

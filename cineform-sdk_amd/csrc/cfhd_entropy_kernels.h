@@ -2,6 +2,7 @@
 // host loop (Codec/encoder.c:5386 EncodeQuantLongRuns + band end code :6538 + PadBitsTag), and assembly of the complete
 // sample (headers, size chunks, raw lowpass words) in HBM.
 //
+//   k_ent_split_two_pass  (groups from 8-bit RGB only) subband 7 into the two planes its two passes code, in front of the count stage
 //   k_ent_count   one workgroup per 2048-coefficient segment: zero-run structure + bits of the tokens that start in it
 //   k_ent_scan    one workgroup per band: previous-nonzero max-scan and bit-offset sum-scan over its segments, band size
 //   k_ent_sizes   one wave per frame: the sample's size from the bands' sizes; k_ent_pack_offsets: the samples' 64-byte aligned places in one dense buffer
@@ -41,7 +42,7 @@ namespace dev {
 #endif
 enum { FWD_CHUNK_COLS_ENT = 496 };      // = FWD_CHUNK_COLS of cfhd_kernels.h (static_assert in cfhd_device.hip, which sees both headers)
 enum { ENT_THREADS = 256, ENT_LANES = 64, ENT_WAVES = ENT_THREADS / ENT_LANES, ENT_PER_THREAD = CFHD_ENT_PER_THREAD, ENT_SEG = ENT_LANES * ENT_PER_THREAD,
-       ENT_LDS_WORDS = 1024, ENT_TOK_CAP = CFHD_ENT_TOK_CAP, ENT_MAX_HOLES = 60 /* an intra sample has up to 40, a two-frame group 51; k_ent_layout sums them in one wave */,
+       ENT_LDS_WORDS = 1024, ENT_TOK_CAP = CFHD_ENT_TOK_CAP, ENT_MAX_HOLES = 60 /* an intra sample has up to 40, a two-frame group 51, 57 with peak tables (interlaced), 54 with subband 7 in two passes; k_ent_layout sums them in one wave */,
        ENT_FILL = CFHD_ENT_FILL /* bytes of a sample one workgroup of k_ent_layout fills at a time */,
        // what k_ent_count leaves per segment for k_ent_emit: one 32-bit word per token -- its finished bit string (run code + value code, left aligned in
        // the upper 26 bits) and its length in the low 6 bits; a token whose run takes several run codes or whose string is longer than 26 bits carries
@@ -85,7 +86,8 @@ struct EntBandJob {
 	int n;                         // raster length = height * pitch
 	int seg_base, nseg;            // its segments in the per-segment arrays
 	int frame, hole;               // frame of the batch, hole index in the frame's template
-	int table;                     // 0: code set 17 (codebook 1), 1: code set 18 (codebook 2, the difference-coded band of interlaced frames)
+	int table;                     // 0: code set 17 (codebook 1), 1: code set 18 (codebook 2: the difference-coded band of interlaced frames, the two passes of a group's divided subband 7)
+	int peaks;                     // coded with peaks (EncodeQuantLongRunsPlusPeaks): the difference-coded bands -- every band but the two passes of subband 7 has peaks == (table == 1)
 };
 
 struct EntSegJob {                 // static per segment: everything k_ent_count / k_ent_emit need to find their coefficients with one scalar load
@@ -93,11 +95,12 @@ struct EntSegJob {                 // static per segment: everything k_ent_count
 	int n;                         // raster length of the band
 	int first;                     // raster index of the segment's first coefficient
 	int band;                      // band job index
-	int table;                     // entropy table of the band (EntBandJob::table); such a band is also the one that may need a peak table
+	int table;                     // entropy table of the band (EntBandJob::table)
 	int pitch;                     // coefficients per band row (k_ent_count_blocks: a level-1 band's chunks are cut row by row)
 	int mask_base;                 // the band's first chunk in a frame's mask array (FwdBlockLists::mask_base); -1: the band has no block lists
 	int len;                       // coefficients of the segment (a multiple of ENT_SEG up to ENT_SEG_MAX: ent_build_band_jobs(); ENT_SEG in a band coded with table 1); the band's last one may end early
 	int tok_base;                  // its first token slot in frame 0's part of `tokens` (a prefix of the segments' token slots: len rounded to whole ENT_TOK_STRIDE)
+	int peaks;                     // EntBandJob::peaks: values beyond the peak threshold are clamped in the stream and counted for the band's peak table
 };
 
 struct EntSegState {               // per segment, written by k_ent_count / k_ent_scan
@@ -265,7 +268,7 @@ __device__ __forceinline__ void ent_count_window(const EntSegJob &job, const Ent
 		const bool long_run = run >= 3072u;
 		const uint32_t ri = long_run ? 0u : run;
 		int value = (int)(int16_t)(tok & 0xffffu);
-		const bool is_peak = job.table && (value > ENT_PEAK_THRESHOLD || value < -ENT_PEAK_THRESHOLD);
+		const bool is_peak = job.peaks && (value > ENT_PEAK_THRESHOLD || value < -ENT_PEAK_THRESHOLD);
 		if (is_peak) value = value > 0 ? ENT_PEAK_THRESHOLD + 1 : -ENT_PEAK_THRESHOLD - 1;
 		c.npeaks += (uint32_t)__popcll(__ballot(is_peak));
 		const uint32_t ve = value_entry(T, value);
@@ -509,6 +512,39 @@ __global__ void __launch_bounds__(ENT_THREADS) k_ent_count_blocks(const EntSegJo
 }
 
 // =============================================================================================
+// k_ent_split_two_pass: subband 7 of a group from an 8-bit RGB source -- the lowpass band of w[3], divided by k_gop_quant_lowpass -- is coded in two passes of code
+// set 18 (cfhd_gop.cpp vlc_encode_band_two_pass, after encoder.c:5112-5238).  The kernel writes what each pass codes into a plane of its own in the encoder's scratch
+// buffer, in front of the count stage, which then meets two ordinary dense bands.  Per coefficient v:
+//   (v & 0xff) != 0 and -255 <= v < 0:  pass 1 codes v whole, pass 2 codes 0
+//   otherwise:                          pass 1 codes v & 0xff, pass 2 codes (v >> 8) & 0xff
+// A value the first rule takes has the high byte 0xff: pass 1 is the low byte with 0xff00 put back, pass 2 the high byte with 0xff taken out -- two lanes of 16 bits
+// at a time.  The band is read as it lies in the pyramid, pad columns included: zeros stay zeros in both planes, so the zero runs cross the rows as in any band.
+// grid: (pieces of 8 x ENT_THREADS coefficients of the longest band, 3 x groups); eight coefficients a lane, one 16-byte load and two 16-byte stores.
+struct EntSplitBand { uint32_t src, n, low, high; };      // element offsets: the band in a group's pyramid, its pitch x height (a multiple of 8, as the offsets are), the two planes in a group's scratch
+struct EntSplitJob { const int16_t *coeffs; size_t coeff_stride; int16_t *scratch; size_t scratch_stride; EntSplitBand band[3]; };
+__device__ __forceinline__ void ent_split_two_pass(uint32_t x, uint32_t *low, uint32_t *high)
+{
+	const uint32_t lb = x & 0x00ff00ffu, hb = pk_sra(x, 8) & 0x00ff00ffu;
+	// 0xffff in the lanes the first rule takes: negative, not below -256 (v + 256 wraps only for v > 32511, which is not negative), low byte not zero (which leaves -256 out)
+	const uint32_t whole = pk_sra(x, 15) & ~pk_sra(pk_addw(x, 0x01000100u), 15) & pk_sra(pk_negw(lb), 15);
+	*low = lb | (whole & 0xff00ff00u);
+	*high = hb & ~whole;
+}
+__global__ void __launch_bounds__(ENT_THREADS) k_ent_split_two_pass(EntSplitJob job)
+{
+	const int g = (int)blockIdx.y / 3, c = (int)blockIdx.y - 3 * g;
+	const EntSplitBand b = job.band[c];
+	const uint32_t i = (blockIdx.x * ENT_THREADS + threadIdx.x) * 8u;
+	if (i >= b.n) return;
+	const cfhd_u4 v = CFHD_LDG128(job.coeffs + (size_t)g * job.coeff_stride + b.src + i);
+	int16_t *planes = job.scratch + (size_t)g * job.scratch_stride;
+	uint32_t lo[4], hi[4];
+	ent_split_two_pass(v.x, &lo[0], &hi[0]); ent_split_two_pass(v.y, &lo[1], &hi[1]); ent_split_two_pass(v.z, &lo[2], &hi[2]); ent_split_two_pass(v.w, &lo[3], &hi[3]);
+	store_u32x4_global(planes + b.low + i, lo[0], lo[1], lo[2], lo[3]);
+	store_u32x4_global(planes + b.high + i, hi[0], hi[1], hi[2], hi[3]);
+}
+
+// =============================================================================================
 __global__ void __launch_bounds__(ENT_THREADS) k_ent_scan(const EntBandJob *bands, EntSegState *segs, EntBandState *band_state, const EntTables *tables)
 {
 	// One workgroup per band, ENT_SCAN_PER consecutive segments per thread and round: a round is a chain of three dependent memory round trips
@@ -560,7 +596,7 @@ __global__ void __launch_bounds__(ENT_THREADS) k_ent_scan(const EntBandJob *band
 		uint32_t off = carry_bits + (uint32_t)block_excl_sum((int)total, s_scan, &chunk_bits);
 		// a band coded with peaks (uniform): where each segment's peak values go in the band's table
 		uint32_t pk_off = 0; int chunk_peaks = 0;
-		if (job.table) {
+		if (job.peaks) {
 			uint32_t mine_pk = 0;
 #pragma unroll
 			for (int k = 0; k < ENT_SCAN_PER; k++) mine_pk += s[k].peaks;
@@ -571,7 +607,7 @@ __global__ void __launch_bounds__(ENT_THREADS) k_ent_scan(const EntBandJob *band
 			if (i0 + k < job.nseg) {
 				EntSegState &o = segs[job.seg_base + i0 + k];
 				o.prev_nz = prevs[k]; o.bits = bits[k]; o.bitoff = off; o.run_code = rcode[k]; o.run_size = rsize[k]; o.run_bits = rbits[k]; o.lead32 = s[k].lead32; o.lead_valid = s[k].lead_valid;
-				if (job.table) o.peaks = (s[k].peaks << ENT_PEAK_OFF_BITS) | (pk_off < (uint32_t)ENT_PEAK_MAX ? pk_off : (uint32_t)ENT_PEAK_MAX);
+				if (job.peaks) o.peaks = (s[k].peaks << ENT_PEAK_OFF_BITS) | (pk_off < (uint32_t)ENT_PEAK_MAX ? pk_off : (uint32_t)ENT_PEAK_MAX);
 			}
 			off += bits[k]; pk_off += s[k].peaks;
 		}

@@ -199,7 +199,13 @@ struct GroupTemplateSink : TemplateRecorder {
 	GroupTemplateSink(SampleTemplate &tt, const GopPlan &p) : TemplateRecorder(tt), plan(p) {}
 	// holes: `level` is the wavelet index (0 .. 5), band 0 of wavelets 5 and 3 are raw 16-bit words
 	void raw16(int c, int k) { const GopWavelet &wv = plan.ch[c].w[k]; hole(0, c, k, 0, (((wv.width * wv.height * 2) + 3) / 4) * 4); }
-	void band(int c, int k, int b) { hole(1, c, k, b, 0); }
+	// a coded subband 7 (arrives here only where it is coded): pass 1, the BAND_SECONDPASS tag, pass 2 -- both holes inside the band's size chunk, each ending in its own
+	// band end code padded to a longword, as any coded band's hole does (vlc_encode_band_two_pass)
+	void band(int c, int k, int b)
+	{
+		if (k == 3 && b == 0) { hole(1, c, k, b, 0, 1); tag(82, 0); hole(1, c, k, b, 0, 2); return; }
+		hole(1, c, k, b, 0);
+	}
 	void frame_band_begins() {}          // (data dependent: the caller checks the finished sample against gop_sample_may_zero_bands())
 };
 

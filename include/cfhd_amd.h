@@ -164,8 +164,8 @@ long long cfhd_amd_batch_wait(cfhd_amd_batch *batch);
 int  cfhd_amd_batch_get_sample(cfhd_amd_batch *batch, int frame, const void **data, size_t *size);
 int  cfhd_amd_batch_download_output(cfhd_amd_batch *batch, int frame, void *out, int pitch);
 /* Batches of two-frame groups: encoding_flags with CFHD_ENCODING_FLAGS_YUV_2FRAME_GOP (optionally CFHD_ENCODING_FLAGS_YUV_INTERLACED), encoded_format 0, an even
- * nframes -- frames 2g and 2g + 1 form group g.  mode 1 takes every 4:2:2 input of the group encoder but RG24 / BGRA / BGRa; mode 0 those whose own format a group
- * decodes to at full resolution (YUY2, 2vuy, YU64, v210, RG48, b64a; interlaced groups: YUY2, 2vuy).  NULL for anything else: an odd nframes, a quality whose group
+ * nframes -- frames 2g and 2g + 1 form group g.  mode 1 takes every 4:2:2 input of the group encoder but RG24 / BGRA / BGRa (those: cfhd_amd_batch_create_groups
+ * below); mode 0 those whose own format a group decodes to at full resolution (YUY2, 2vuy, YU64, v210, RG48, b64a; interlaced groups: YUY2, 2vuy).  NULL for anything else: an odd nframes, a quality whose group
  * tables follow the previous key sample (FILMSCAN2 / 3, LOW .. HIGH up to 1080p), CFHD_AMD_ENTROPY=host.  Every entry point keeps its meaning per frame index
  * (upload, submit_host, download_output: frame i); get_sample(2g) is group sample g, get_sample(2g + 1) the 24-byte P-frame sample behind it.  In pass k (counted from
  * 0) both carry frame number k * nframes + 2g + 1: the samples of consecutive passes are the stream one CFHD_EncodeSample handle writes when it is fed the same frames,
@@ -175,6 +175,16 @@ int  cfhd_amd_batch_download_output(cfhd_amd_batch *batch, int frame, void *out,
  * 4 middle wavelets + temporal step, 5 top wavelet, 12 k_dec_parse_group, 13 band decoder, 14 k_dec_lowpass (cfhd_batch.cpp).
  * Returns 0 and the 40-byte header, or -1 for a batch without groups (or one between submit and wait). */
 int  cfhd_amd_batch_get_sequence_header(cfhd_amd_batch *batch, const void **data, size_t *size);
+/* A batch of two-frame groups from any input: what cfhd_amd_batch_create_ex makes with encoded_format 0 and CFHD_ENCODING_FLAGS_YUV_2FRAME_GOP (implied here, OR-ed into
+ * encoding_flags) -- the same samples byte for byte --, and in addition groups from RG24 / BGRA / BGRa.  The reference marks those sources
+ * CFEncode_Temporal_Quality_32: subband 7 of every channel (the lowpass band of the temporal highpass wavelet) is divided by 32 and coded in two passes of code set 18,
+ * here on the device (k_ent_split_two_pass in front of the entropy coder's count stage; its time falls under cfhd_amd_batch_kernel_ms index 8, with k_ent_count).
+ * mode 1: encode only; mode 0: round trip to the input's own format (k_dec_band_two_pass decodes that band; its time falls under index 13, the band decoder).
+ * cfhd_amd_batch_create_ex keeps refusing the three inputs, for callers that probe with it.  NULL as there: an odd nframes, a quality whose group tables follow the
+ * previous key sample, CFHD_AMD_ENTROPY=host, a width that is no multiple of 16, interlaced groups from anything but YUY2 / 2vuy, mode 0 for an input without a
+ * decoder output (RG64, the Avid layouts), a geometry the device group decoder does not take.  Every other cfhd_amd_batch_* entry point is shared and keeps its meaning
+ * per frame index; -9 keeps its meaning. */
+cfhd_amd_batch *cfhd_amd_batch_create_groups(int width, int height, uint32_t pixel_format, uint32_t encoding_flags, int quality, int nframes, int nthreads, int mode);
 float cfhd_amd_batch_kernel_ms(cfhd_amd_batch *batch, int which);                              /* HIP-event time of the kernels of the last pass */
 const char *cfhd_amd_batch_kernel_name(cfhd_amd_batch *batch, int which);                      /* which 0..5: the transform kernel behind that time */
 double cfhd_amd_batch_stage_seconds(cfhd_amd_batch *batch, int which);
