@@ -64,6 +64,7 @@ int front_end_params(int width, int height, uint32_t pixel_format, int encoded_f
 	out->pixel_kind = p.pixel_kind; out->encoded_format = p.encoded_format; out->pixel_bytes = pixel_bytes_of(p.pixel_kind);
 	out->color_format = p.pixel_format == FMT_RG30 ? 122 : color_format_of(p.pixel_kind); out->color_space = p.color_space; out->quality = header_quality(p.quality); out->progressive = p.progressive;
 	out->plan = p.plan; out->static_quantizer = quantizer_is_static(p);
+	out->derive_quality = p.quality; out->qstate = p.qstate;
 	out->gop = p.gop;
 	if (p.gop) {
 		out->gplan = p.gplan; out->gop_static_quantizer = group_quantizer_is_static(p);

@@ -63,10 +63,26 @@ struct cfhd_amd_batch {
 	std::unique_ptr<GopBatch> genc, gdec;
 	std::vector<uint8_t> pframes; uint8_t sequence_header[64]; size_t sequence_header_size = 0;
 	int ngroups() const { return n / 2; }
+	// cfhd_amd_batch_create_stream: the batch is one encoder's stream, pass behind pass -- frame i of pass k is call k n + i + 1 of one CFHD_EncodeSample handle, rate
+	// feedback included.  moving: the quality's tables follow the size of the sample in front (encode_one, cfhd_api_params.h); then every frame carries tables of its
+	// own, a pass is coded on a guess of them and the frames from the first wrong guess on are coded again (stream_rounds).  The state below is the handle's
+	// EncodeParams::qstate / plan, held at the pass boundary; a pass that fails leaves it alone.
+	struct Stream {
+		bool on = false, moving = false;
+		int derive_quality = 0;                         // the quality word derive_quantization takes (the caller's with the format marks)
+		QuantState carried = {0, -1, 0};                // behind the last frame of the last completed pass
+		FramePlan carried_plan;                         // that frame's tables (before the first pass: the tables CFHD_PrepareToEncode derives)
+		size_t carried_bytes = 0;                       // that frame's sample size (0: no frame yet -- the first frame of a stream derives nothing)
+		std::vector<FramePlan> coded;                   // the tables frame i was coded with last: a pass's guess, then its result, then the next pass's guess
+		std::vector<QuantState> before;                 // the state in front of frame i's derivation, as far as the pass is verified
+		QuantState next = {0, -1, 0};                   // what a pass that ends well carries on
+		int rounds = 0, frames_coded = 0, stats[3] = {0, 0, 0}; bool stats_valid = false;
+	} stream;
 	~cfhd_amd_batch() { if (worker.joinable()) worker.join(); chunks.clear(); genc.reset(); gdec.reset(); for (void *s : shared_streams) device_stream_release(s); }
 };
 
 namespace {
+cfhd_amd_batch *create_intra_batch(const FrontEndParams &fp, int width, int height, int nframes, int nthreads, int mode, bool stream);
 template <typename F> void parallel_for(int n, int nthreads, F f)
 {
 	if (nthreads <= 1 || n <= 1) { for (int i = 0; i < n; i++) f(i); return; }
@@ -77,6 +93,103 @@ template <typename F> void parallel_for(int n, int nthreads, F f)
 	for (auto &th : pool) th.join();
 }
 double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// ---- streams with rate feedback (cfhd_amd_batch_create_stream, tables that move)
+bool same_tables(const FramePlan &a, const FramePlan &b)      // (tables, not states: two states can give the same divisors)
+{
+	for (int c = 0; c < a.num_channels; c++)
+		for (int lv = 0; lv < kNumLevels; lv++)
+			for (int k = 0; k < kNumBands; k++) if (a.ch[c].band[lv][k].quant != b.ch[c].band[lv][k].quant) return false;
+	return true;
+}
+// One step of the handle's walk (encode_one): `plan` holds the tables of the frame in front and becomes this frame's, derived from the size of that frame's sample --
+// or stays, when there is no such sample (the first frame of a stream).
+void stream_step(const cfhd_amd_batch *b, QuantState *st, size_t bytes_in_front, FramePlan *plan)
+{
+	st->lastgopbitcount = (int64_t)bytes_in_front * 8;
+	if (st->lastgopbitcount) derive_quantization(plan, b->stream.derive_quality, b->progressive, 0.0f, st);
+}
+SampleHeaderInfo stream_header(const cfhd_amd_batch *b, int i)
+{
+	SampleHeaderInfo h = { b->steps * (uint32_t)b->n + (uint32_t)i + 1, b->color_format, b->color_space, b->quality, b->progressive, b->frame_meta[i].data(), b->frame_meta[i].size(), nullptr, 0 };
+	return h;
+}
+// Round 0 of a pass: frame 0 carries the tables the carried state gives it, the frames behind it a guess -- in the first pass the same tables, afterwards the tables
+// the last pass ended with, frame by frame (on ordinary material the tables stand still for long runs, and a cut that repeats -- a loop, a benchmark -- repeats them).
+int stream_begin_pass(cfhd_amd_batch *b)
+{
+	cfhd_amd_batch::Stream &s = b->stream;
+	cfhd_amd_chunk *c = b->chunks[0].get();
+	s.rounds = 1; s.frames_coded = b->n;
+	QuantState st = s.carried; FramePlan first = s.carried_plan;
+	stream_step(b, &st, s.carried_bytes, &first);
+	for (int i = 0; i < b->n; i++) {
+		const FramePlan &guess = i && b->steps ? s.coded[i] : first;
+		if (same_tables(guess, c->enc.frame_plan(i))) { s.coded[i] = c->enc.frame_plan(i); continue; }
+		s.coded[i] = guess;
+		if (c->enc.set_frame_quant(i, guess)) return -2;
+	}
+	return 0;
+}
+// The rounds behind round 0, with the sizes of the round before on the host and the encoder's stream drained.  The walk starts at the first frame whose tables are not
+// verified yet, j, with the state in front of it, and derives every frame's tables from the size of the sample in front -- the handle's own steps.  Up to the first frame
+// whose tables differ from the ones it was coded with, every sample is the handle's: sample i - 1 final makes the tables of frame i final.  That frame and the ones behind
+// it get the tables the walk has found (a guess again behind the first) and are coded again, as a window of the batch; j rises every round, so a pass takes at most n
+// rounds and ends on the handle's samples.  The metadata blocks are the ones batch_launch dealt: one per frame and pass.  Returns 0 -- also for a pass that batch_finish
+// is about to fail (a verified frame that does not fit) -- or < 0.
+int stream_rounds(cfhd_amd_batch *b)
+{
+	cfhd_amd_batch::Stream &s = b->stream;
+	cfhd_amd_chunk *c = b->chunks[0].get();
+	GpuEntropyEncoder &ent = c->enc.entropy();
+	const int n = b->n;
+	std::vector<FramePlan> found((size_t)n);
+	bool recoded = false;
+	s.before[0] = s.carried;
+	for (int j = 0;;) {
+		QuantState st = s.before[j]; FramePlan plan = j ? s.coded[j - 1] : s.carried_plan;
+		int wrong = -1;
+		for (int i = j; i < n; i++) {
+			const size_t in_front = i ? ent.sample_bytes(i - 1) : s.carried_bytes;
+			if (wrong < 0 && i && !in_front) return 0;      // (sample i - 1 is final and does not fit its buffer: -3)
+			if (wrong < 0) s.before[i] = st;
+			stream_step(b, &st, in_front, &plan);
+			if (wrong < 0 && !same_tables(plan, s.coded[i])) wrong = i;
+			found[i] = plan;
+		}
+		if (wrong < 0) { s.next = st; break; }
+		// (mode 0: the decoder of the round before is reading the dense buffer the coder is about to write again)
+		if (b->decode && c->dec.wait()) return -5;
+		for (int i = wrong; i < n; i++) {
+			s.coded[i] = found[i];
+			if (c->enc.set_frame_quant(i, found[i])) return -2;
+			ent.set_plan(found[i]);
+			if (ent.set_frame_header(i, stream_header(b, i))) return -6;
+		}
+		const int count = n - wrong;
+		if (c->enc.launch_forward(false, wrong, count) || ent.launch(wrong, count) || ent.download_queue(wrong, count) || ent.download_finish(wrong, count) || c->enc.wait()) return -2;
+		s.rounds++; s.frames_coded += count; recoded = true;
+		j = wrong;
+	}
+	if (recoded && b->decode) {                         // the decoder's half again, over the final samples
+		c->dec.entropy().set_producer_events(ent.headers_event(), ent.samples_event());
+		if (c->dec.entropy().set_samples_device(ent.device_samples(), 0, ent.device_sizes(), ent.device_offsets())) return -4;
+		if (c->dec.launch_entropy() || c->dec.launch_inverse(0xA511E9B3u * (b->steps + 1) + (uint32_t)c->first)) return -5;
+		if (b->host_out && c->dec.download_frames(b->host_out, b->host_out_stride, b->host_out_pitch)) return -5;
+	}
+	return 0;
+}
+// A pass that ended well: its last frame is what the next pass goes on from.  stats: rounds, frames coded over all rounds, frames whose tables differ from those of
+// the frame in front (frame 0: from the last frame of the pass before).
+void stream_end_pass(cfhd_amd_batch *b)
+{
+	cfhd_amd_batch::Stream &s = b->stream;
+	if (!s.moving) { s.stats[0] = 1; s.stats[1] = b->n; s.stats[2] = 0; s.stats_valid = true; return; }
+	int moved = 0;
+	for (int i = 0; i < b->n; i++) moved += !same_tables(s.coded[i], i ? s.coded[i - 1] : s.carried_plan);
+	s.stats[0] = s.rounds; s.stats[1] = s.frames_coded; s.stats[2] = moved; s.stats_valid = true;
+	s.carried = s.next; s.carried_plan = s.coded[b->n - 1]; s.carried_bytes = b->sample_size[b->n - 1];
+}
 
 // The default pass (all stages on the GPU, samples handed over in HBM, one chunk) in two halves with no host wait inside either.
 // batch_launch: every launch of the pass queued -- forward transform, entropy coder, dense copy of the samples + their sizes on the way to the host on the encoder's
@@ -90,6 +203,7 @@ int batch_launch(cfhd_amd_batch *b)
 	b->frame_meta.resize(b->n);
 	for (int i = 0; i < b->n; i++) { b->meta.handle(); b->frame_meta[i] = b->meta.global; meta_remove_hidden(b->frame_meta[i]); }
 	const uint32_t seed = 0xA511E9B3u * (b->steps + 1);
+	if (b->stream.moving && stream_begin_pass(b)) return -2;
 	// Encode-only passes in flight on one device take turns (cfhd_device.h stage_order_wait): this pass's forward transform starts behind the entropy coder of the pass
 	// queued before it.  Passes that start together otherwise run in lock step -- all encode, then all copy their samples to the host, and the copies (the PCIe link) and
 	// the kernels never overlap: byr4-2160p 18.9 k fps with turns, 11.9 k without; rg48-2160p 15.9 / 12.4 k.  Round-trip passes run free: their decode halves fill the
@@ -105,6 +219,7 @@ int batch_launch(cfhd_amd_batch *b)
 	if (c->enc.launch_forward(false)) return -2;         // (nothing but the entropy stage reads these coefficients)
 	for (int l = 0; l < c->n; l++) {
 		SampleHeaderInfo h = { base_number + (uint32_t)(c->first + l) + 1, b->color_format, b->color_space, b->quality, b->progressive, b->frame_meta[c->first + l].data(), b->frame_meta[c->first + l].size(), nullptr, 0 };
+		if (b->stream.moving) c->enc.entropy().set_plan(b->stream.coded[l]);      // (the header carries the frame's own tables)
 		if (c->enc.entropy().set_frame_header(l, h)) return -6;
 	}
 	if (c->enc.entropy().launch()) return -2;
@@ -127,6 +242,9 @@ long long batch_finish(cfhd_amd_batch *b)
 {
 	cfhd_amd_chunk *c = b->chunks[0].get();
 	if (c->enc.entropy().download_finish() || c->enc.wait()) return -2;
+	// a stream whose tables move: the sizes say whether the guess of the tables held; if not, the frames behind the first wrong one are coded again (no turns taken:
+	// stage_order_wait is round 0's)
+	if (b->stream.moving) { const int rc = stream_rounds(b); if (rc) return rc; }
 	// A frame whose sample does not fit its buffer has size 0 (k_ent_layout) and fails the pass with -3 -- behind the loop: the samples of the other frames are complete
 	// and keep their sizes for cfhd_amd_batch_get_sample, and the decoder's stream, which is parsing these buffers, has drained before the caller gets the batch back.
 	bool overflow = false, peaks = false;
@@ -147,6 +265,7 @@ long long batch_finish(cfhd_amd_batch *b)
 	}
 	const double t4 = now();
 	b->t_fwd = b->t_launched - b->t_launch0; b->t_entropy_enc = t_enc - b->t_launched; b->t_entropy_dec = 0; b->t_inv = t4 - t_enc;
+	if (b->stream.on) stream_end_pass(b);
 	b->steps++;
 	long long total = 0;
 	for (int i = 0; i < b->n; i++) total += (long long)b->sample_size[i];
@@ -296,9 +415,37 @@ cfhd_amd_batch *cfhd_amd_batch_create_ex(int width, int height, uint32_t pixel_f
 	if (nframes < 1 || front_end_params(width, height, pixel_format, encoded_format, encoding_flags, quality, &fp)) return nullptr;
 	// A batch encodes its frames in one launch with one set of quantizer tables.  Qualities whose tables follow the size of the previous sample
 	// (FILMSCAN2/3, LOW..HIGH up to 1080p: encoder.c:3414 -> quantize.c:2869) need frame i's sample before frame i + 1 can start -- those
-	// sequences go through CFHD_EncodeSample, which applies the feedback per frame; here they are refused instead of encoded differently.
+	// sequences go through CFHD_EncodeSample, which applies the feedback per frame, or through cfhd_amd_batch_create_stream, which codes a pass on a guess of
+	// every frame's tables and codes the frames behind a wrong guess again; here they are refused instead of encoded differently (callers probe with this entry).
 	if (fp.gop) return create_group_batch(fp, width, height, nframes, nthreads, mode, false);
 	if (!fp.static_quantizer) return nullptr;
+	return create_intra_batch(fp, width, height, nframes, nthreads, mode, false);
+}
+
+// One encoder's stream on the frame queue (include/cfhd_amd.h): every quality word CFHD_PrepareToEncode takes for intra frames.  A word whose tables never move makes
+// exactly cfhd_amd_batch_create_ex's batch; one whose tables follow the sizes makes the same batch with tables per frame and the rounds of stream_rounds behind round 0.
+cfhd_amd_batch *cfhd_amd_batch_create_stream(int width, int height, uint32_t pixel_format, int encoded_format, uint32_t encoding_flags, int quality, int nframes, int nthreads, int mode)
+{
+	CallerDevice caller_device;
+	FrontEndParams fp;
+	auto refuse = [](const char *text) { device_set_last_error(text); return (cfhd_amd_batch *)nullptr; };
+	if (nframes < 1) return refuse("cfhd_amd_batch_create_stream: a batch has at least one frame");
+	if (mode != 0 && mode != 1) return refuse("cfhd_amd_batch_create_stream: mode is 0 (round trip) or 1 (encode only)");
+	if (encoding_flags & (1u << 1)) return refuse("cfhd_amd_batch_create_stream: two-frame groups go through cfhd_amd_batch_create_groups (their tables must stand still)");
+	if (front_end_params(width, height, pixel_format, encoded_format, encoding_flags, quality, &fp)) return refuse("cfhd_amd_batch_create_stream: arguments CFHD_PrepareToEncode refuses");
+	const char *e = getenv("CFHD_AMD_ENTROPY");
+	if (e && strcmp(e, "host") == 0) return refuse("cfhd_amd_batch_create_stream: CFHD_AMD_ENTROPY=host keeps the entropy stage on the host; a stream is coded on the device");
+	device_set_last_error("");
+	cfhd_amd_batch *b = create_intra_batch(fp, width, height, nframes, nthreads, mode, true);
+	if (!b && !*device_last_error()) device_set_last_error("cfhd_amd_batch_create_stream: cfhd_amd_batch_create_ex refuses this input, mode or arrangement");
+	return b;
+}
+}
+
+namespace {
+// An intra batch: cfhd_amd_batch_create_ex's (tables that stand still) and, with stream, cfhd_amd_batch_create_stream's (any tables).
+cfhd_amd_batch *create_intra_batch(const FrontEndParams &fp, int width, int height, int nframes, int nthreads, int mode, bool stream)
+{
 	const int kind = fp.pixel_kind;
 	const bool yuv = kind == PIX_YUY2 || kind == PIX_2VUY;
 	cfhd_amd_batch *b = new (std::nothrow) cfhd_amd_batch;
@@ -348,8 +495,25 @@ cfhd_amd_batch *cfhd_amd_batch_create_ex(int width, int height, uint32_t pixel_f
 	}
 	b->samples.resize(nframes); b->sample_size.assign(nframes, 0);
 	if (!b->gpu_entropy) for (auto &s : b->samples) s.resize(cap);
+	if (stream) {
+		cfhd_amd_batch::Stream &s = b->stream;
+		s.on = true; s.moving = !fp.static_quantizer; s.derive_quality = fp.derive_quality;
+		s.carried = fp.qstate; s.carried_plan = fp.plan; s.carried_bytes = 0; s.next = fp.qstate;
+		if (s.moving) {
+			// the rounds sit between the two halves of the default pass: nothing else has them
+			if (!(b->gpu_entropy && b->device_handoff && b->chunks.size() == 1)) {
+				delete b;
+				device_set_last_error("cfhd_amd_batch_create_stream: tables that follow the sample sizes need the default arrangement (no CFHD_AMD_HANDOFF=host, no CFHD_AMD_CHUNK)");
+				return nullptr;
+			}
+			s.coded.assign((size_t)nframes, fp.plan); s.before.assign((size_t)nframes, fp.qstate);
+		}
+	}
 	return b;
 }
+}
+
+extern "C" {
 
 // Two-frame groups from any input cfhd_amd_batch_create_ex takes with encoded format 0 and CFHD_ENCODING_FLAGS_YUV_2FRAME_GOP (implied here) -- the same batch, byte
 // for byte -- and from RG24 / BGRA / BGRa, whose subband 7 is divided and coded in two passes (k_ent_split_two_pass; mode 0: k_dec_band_two_pass).
@@ -527,6 +691,7 @@ static long long cfhd_amd_batch_roundtrip_locked(cfhd_amd_batch *b)
 	}
 	double t4 = now();
 	b->t_fwd = t1 - t0; b->t_entropy_enc = t2 - t1; b->t_entropy_dec = t3 - t2; b->t_inv = t4 - t3;
+	if (b->stream.on) stream_end_pass(b);               // (a stream whose tables stand still, in one of the other arrangements)
 	b->steps++;
 	long long total = 0;
 	for (int i = 0; i < b->n; i++) total += (long long)b->sample_size[i];
@@ -647,6 +812,14 @@ float cfhd_amd_batch_kernel_ms(cfhd_amd_batch *b, int which)
 		else ms += which == 6 ? c->enc.last_kernel_ms() : c->dec.last_kernel_ms();
 	}
 	return ms;
+}
+
+// The last completed pass of a stream: rounds, frames coded over all rounds, frames whose tables differ from those of the frame in front.
+int cfhd_amd_batch_stream_stats(cfhd_amd_batch *b, int out[3])
+{
+	if (!b || !out || !b->stream.on || b->in_flight || !b->stream.stats_valid) return -1;
+	for (int k = 0; k < 3; k++) out[k] = b->stream.stats[k];
+	return 0;
 }
 
 int cfhd_amd_quantizer_is_static(int width, int height, uint32_t pixel_format, int encoded_format, uint32_t encoding_flags, int quality)

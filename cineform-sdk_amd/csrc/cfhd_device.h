@@ -48,8 +48,14 @@ public:
 	void set_active(int k) { active_ = k; ent_.set_active(k); }
 	// async: all levels, all frames.  coeffs_needed = false: nothing but the GPU entropy stage will read this launch's coefficients -- where the level-1 bands
 	// leave as block lists (k_fwd_yuv422_strip_blocks, cfhd_kernels.h FwdBlockLists) their dense rows are then not written at all.
-	int launch_forward(bool coeffs_needed = true);
-	int update_quant(const FramePlan &plan);           // same geometry, new quantizer tables (per-frame rate feedback)
+	int launch_forward(bool coeffs_needed = true) { return launch_forward(coeffs_needed, 0, 0); }
+	// the same over a window of the batch, frames first .. first + count - 1 (count 0: frames 0 .. active - 1): the job tables from `first` on, grids sized by count, the
+	// kernels a batch of count frames would pick.  The block lists and the pyramids are the frames' own, numbered over the whole batch.
+	int launch_forward(bool coeffs_needed, int first, int count);
+	int update_quant(const FramePlan &plan);           // same geometry, new quantizer tables for every frame (per-frame rate feedback of the handles)
+	// new quantizer tables for frame i alone (the frame queue's rate-feedback streams: every frame of a pass carries its own).  The caller has drained the stream.
+	int set_frame_quant(int i, const FramePlan &plan);
+	const FramePlan &frame_plan(int i) const { return frame_plans_.empty() ? plan_ : frame_plans_[i]; }
 	// GPU entropy stage (cfhd_entropy_kernels.h): complete samples are produced in HBM after launch_forward().
 	int prepare_entropy(size_t sample_cap);
 	GpuEntropyEncoder &entropy() { return ent_; }
@@ -69,9 +75,11 @@ public:
 private:
 	int sync_jobs();
 	void fill_jobs();
+	void fill_frame_jobs(int i);                    // frame i's rows of the job tables, from frame_plan(i)
 	void fill_block_lists();
-	ForwardRoute forward_route(bool coeffs_needed) const;      // which kernels the next launch_forward() runs: launch_forward() and level_kernel() both read this
+	ForwardRoute forward_route(bool coeffs_needed, int frames) const;      // which kernels a launch_forward() over `frames` frames runs: launch_forward() and level_kernel() both read this
 	FramePlan plan_;
+	std::vector<FramePlan> frame_plans_;            // empty: every frame carries plan_'s divisors; else frame i its own (set_frame_quant)
 	int n_ = 0, active_ = 0, device_ = 0; bool jobs_dirty_ = true;
 	void *stream_ = nullptr, *ev0_ = nullptr, *ev1_ = nullptr, *evl_[2] = {nullptr, nullptr};
 	float level_ms_[3] = {0, 0, 0};

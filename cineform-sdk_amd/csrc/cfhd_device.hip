@@ -393,7 +393,7 @@ int EncodeBatch::prepare(const FramePlan &plan, int nframes)
 	device_ = device_current(); (void)hipSetDevice(device_);      // (release() went to the device of the buffers it freed)
 	const bool bayer = plan.pixel_kind == PIX_BYR4 || plan.pixel_kind == PIX_BYR5;
 	if (plan.pixel_kind != PIX_YUY2 && plan.pixel_kind != PIX_2VUY && !enc_packed16(plan.pixel_kind) && !bayer) { g_err = "pixel format not supported by the GPU path yet"; return -2; }
-	plan_ = plan; n_ = nframes;
+	plan_ = plan; n_ = nframes; frame_plans_.clear();
 	HIPCHK((hipError_t)device_stream_create(&stream_));
 	HIPCHK(hipEventCreate((hipEvent_t *)&ev0_));
 	HIPCHK(hipEventCreate((hipEvent_t *)&ev1_));
@@ -428,11 +428,15 @@ int EncodeBatch::prepare(const FramePlan &plan, int nframes)
 // (Re)writes the job tables from plan_: geometry, band addresses and quantizer parameters.
 void EncodeBatch::fill_jobs()
 {
-	const FramePlan &plan = plan_;
+	for (int i = 0; i < n_; i++) fill_frame_jobs(i);
+}
+void EncodeBatch::fill_frame_jobs(int i)
+{
+	const FramePlan &plan = frame_plan(i);              // (the geometry is plan_'s; the divisors are the frame's own)
 	const bool bayer = plan.pixel_kind == PIX_BYR4 || plan.pixel_kind == PIX_BYR5;
 	const int nch = plan.num_channels, mpq = plan.midpoint_prequant;
 	EncJobs j = enc_jobs_at(h_jobs_, n_, nch);
-	for (int i = 0; i < n_; i++) {
+	{
 		int16_t *base = d_coeff_ + (size_t)i * plan.coeff_elems;
 		const uint8_t *frame = d_in_ + frame_bytes_ * i;
 		const Level1 l1 = level1_of(plan, base);
@@ -470,9 +474,20 @@ int EncodeBatch::update_quant(const FramePlan &plan)
 	(void)hipSetDevice(device_);
 	if (plan.coeff_elems != plan_.coeff_elems || plan.num_channels != plan_.num_channels) return -1;
 	if (stream_) HIPCHK(hipStreamSynchronize((hipStream_t)stream_));      // the pinned job table may still be in flight
-	plan_ = plan;
+	plan_ = plan; frame_plans_.clear();
 	fill_jobs();
 	if (ent_ready_) ent_.set_plan(plan);
+	return 0;
+}
+
+// Frame i's divisors alone: its rows of the job tables are rewritten, the others keep theirs.  The sample header is the caller's (GpuEntropyEncoder::set_plan +
+// set_frame_header); the pinned job table must not be in flight (the frame queue rewrites it between the rounds of a pass, behind a drained stream).
+int EncodeBatch::set_frame_quant(int i, const FramePlan &plan)
+{
+	if (i < 0 || i >= n_ || plan.coeff_elems != plan_.coeff_elems || plan.num_channels != plan_.num_channels) return -1;
+	if (frame_plans_.empty()) frame_plans_.assign((size_t)n_, plan_);
+	frame_plans_[i] = plan;
+	fill_frame_jobs(i);
 	return 0;
 }
 
@@ -658,10 +673,10 @@ struct ForwardRoute {
 template <typename F> static bool every_frame(int n, F ok) { for (int i = 0; i < n; i++) if (!ok(i)) return false; return true; }
 
 // The kernels of the next launch_forward(), from the prepared batch alone: the environment switches, the active frame count and the job table are read here and nowhere else.
-ForwardRoute EncodeBatch::forward_route(bool coeffs_needed) const
+ForwardRoute EncodeBatch::forward_route(bool coeffs_needed, int frames) const
 {
 	static const int blocks_env = [] { const char *e = getenv("CFHD_AMD_BLOCKS"); return e ? atoi(e) : 1; }();      // 0: dense bands and k_ent_count (A/B runs)
-	const int act = active_frames(active_, n_), forced = shape_override("CFHD_AMD_FORWARD"), kind = plan_.pixel_kind, nch = plan_.num_channels;
+	const int act = frames, forced = shape_override("CFHD_AMD_FORWARD"), kind = plan_.pixel_kind, nch = plan_.num_channels;
 	const EncJobs j = enc_jobs_at(h_jobs_, n_, nch);
 	ForwardRoute r;
 	for (int lv = 1; lv < 3; lv++) r.strip_planes[lv - 1] = planes_as_strips(plan_, lv, act);
@@ -734,21 +749,28 @@ static int launch_first_level(FwdL1 k, const FirstLevel &g, hipStream_t st)
 
 const char *EncodeBatch::level_kernel(int level, bool coeffs_needed) const
 {
-	const ForwardRoute r = forward_route(coeffs_needed);
+	const ForwardRoute r = forward_route(coeffs_needed, active_frames(active_, n_));
 	return level > 0 ? kFwdPlaneName[r.strip_planes[level - 1]] : kFwdL1Name[(int)r.l1];
 }
 
-int EncodeBatch::launch_forward(bool coeffs_needed)
+int EncodeBatch::launch_forward(bool coeffs_needed, int first, int count)
 {
+	if (!count) count = active_frames(active_, n_);      // frames 0 .. count-1 of the batch hold frames (set_active)
+	if (first < 0 || count < 1 || first + count > n_) return -1;
 	(void)hipSetDevice(device_);
-	const ForwardRoute r = forward_route(coeffs_needed);
+	const ForwardRoute r = forward_route(coeffs_needed, count);
 	if (ent_ready_) ent_.set_block_lists(r.block_lists());
 	int rc = sync_jobs();
 	if (rc) return rc;
 	hipStream_t st = (hipStream_t)stream_;
 	const int nch = plan_.num_channels;
-	const int act = active_frames(active_, n_);                    // frames 0 .. act-1 of the batch hold frames (set_active)
+	const int act = count;
 	EncJobs j = enc_jobs_at(d_jobs_, n_, nch);
+	// (a window: every table from its first frame on -- the jobs hold the addresses of their own frames, pyramids and block lists)
+	if (j.yuv) j.yuv += first;
+	if (j.bayer) j.bayer += first;
+	if (j.l1) j.l1 += (size_t)first * nch;
+	j.l2 += (size_t)first * nch; j.l3 += (size_t)first * nch;
 	(void)hipGetLastError();                            // drop stale sticky errors: the check below is for these launches only
 	timed_ = true;
 	HIPCHK(hipEventRecord((hipEvent_t)ev0_, st));

@@ -37,10 +37,17 @@ public:
 	// A sample beyond gop_sample_may_zero_bands() is not valid (the reference zeroes bands there, encoder.c:8332): the caller writes it on the host.
 	int prepare_group(const GopPlan &plan, int ngroups, int16_t *d_coeffs, size_t coeff_stride_elems, size_t sample_cap, void *stream);
 	void set_group_plan(const GopPlan &plan) { gplan_ = plan; }
-	int launch();                                                    // async: templates H2D + the kernels; leaves the samples densely in HBM
+	int launch() { return launch(0, active_frames()); }              // async: templates H2D + the kernels; leaves the samples densely in HBM
 	int download();                                                  // sizes + offsets -> sync -> one async copy of all sample bytes (wait on the stream afterwards)
-	int download_queue();                                            // the two halves of download(): what can be queued behind launch() without the host ...
-	int download_finish();                                           // ... and what needs the sizes on the host (synchronises the stream, queues the copy of the sample bytes)
+	int download_queue() { return download_queue(0, active_frames()); }      // the two halves of download(): what can be queued behind launch() without the host ...
+	int download_finish() { return download_finish(0, active_frames()); }    // ... and what needs the sizes on the host (synchronises the stream, queues the copy of the sample bytes)
+	// The same over a window of the batch, frames first .. first + count - 1 (intra frames; the frame queue's rate-feedback streams code the frames behind a wrong guess
+	// of their tables again, cfhd_batch.cpp): the grids are sized by count, the segment states, token bases and block lists are those of the frames' own numbers.  In the
+	// dense buffer the samples in front of `first` keep their bytes and offsets -- the sizes of all first + count frames are summed again, the prefix's are final --, the
+	// window's samples are written at their new offsets, and the copy to the host covers [offsets[first], offsets[first + count]).  (0, n) is launch() / download_*().
+	int launch(int first, int count);
+	int download_queue(int first, int count);
+	int download_finish(int first, int count);
 	int fetch_sizes();                                               // sizes only (device-resident consumers); synchronises the stream
 	const uint32_t *device_sizes() const { return d_sizes_; }
 	const uint8_t *host_sample(int i) const { return h_samples_ + h_offsets_[i]; }   // after download() + stream wait

@@ -153,8 +153,9 @@ int GpuEntropyEncoder::set_frame_header(int f, const SampleHeaderInfo &hdr)
 	return 0;
 }
 
-int GpuEntropyEncoder::launch()
+int GpuEntropyEncoder::launch(int first, int count)
 {
+	if (first < 0 || count < 1 || first + count > n_ || (first && group_)) return -1;      // (windows: intra frames)
 	(void)hipSetDevice(device_);
 	hipStream_t st = (hipStream_t)stream_;
 	if (dirty_) {
@@ -164,7 +165,8 @@ int GpuEntropyEncoder::launch()
 	}
 	const dev::EntTables *T = (const dev::EntTables *)d_tables_;
 	const dev::EntBatchGeom geom = { total_segs_ / n_, nbands_, coeff_stride_, tok_per_frame_ };
-	const int act = active_frames(), total_segs = total_segs_ / n_ * act;      // frames 0 .. act-1 (set_active)
+	const int act = count, segs_per_frame = total_segs_ / n_, total_segs = segs_per_frame * act;      // frames first .. first + act - 1 (set_active: 0 .. act-1)
+	const dev::EntFrameJob *frames = (const dev::EntFrameJob *)d_frames_ + first;
 	(void)hipGetLastError();
 	HIPCHK(hipEventRecord((hipEvent_t)ev_[0], st));
 #ifdef CFHD_AMD_PROBES
@@ -178,10 +180,10 @@ int GpuEntropyEncoder::launch()
 		const int total = n * act;
 		if (level1 && use_blocks_)
 			dev::k_ent_count_blocks<<<(total + dev::ENT_WAVES - 1) / dev::ENT_WAVES, dev::ENT_THREADS, 0, s>>>((const dev::EntSegJob *)d_segband_, g, total, (dev::EntSegState *)d_segs_, T,
-			                                                                                                 d_sizes_ + n_, (uint32_t *)d_tokens_, lo, n, lists);
+			                                                                                                 d_sizes_ + n_, (uint32_t *)d_tokens_, lo, n, lists, first);
 		else
 			dev::k_ent_count<<<(total + dev::ENT_WAVES - 1) / dev::ENT_WAVES, dev::ENT_THREADS, 0, s>>>((const dev::EntSegJob *)d_segband_, g, total, (dev::EntSegState *)d_segs_, T,
-			                                                                                          d_sizes_ + n_, (uint32_t *)d_tokens_, lo, n, count_probe);
+			                                                                                          d_sizes_ + n_, (uint32_t *)d_tokens_, lo, n, count_probe, first);
 	};
 	// CFHD_AMD_COUNT_SPLIT=0: (A/B) the level-1 bands counted on the main stream behind the level-2 / level-3 transforms instead of beside them
 	static const bool split_on = [] { const char *e = getenv("CFHD_AMD_COUNT_SPLIT"); return !(e && atoi(e) == 0); }();
@@ -191,7 +193,7 @@ int GpuEntropyEncoder::launch()
 	hipStream_t s1 = split_ ? (hipStream_t)stream2_ : st;
 	if (s1 != st) HIPCHK(hipStreamWaitEvent(s1, (hipEvent_t)ev_level1_, 0));
 	// the peak flags are raised by the difference-coded band only, a level-1 band: cleared on the stream that counts it
-	if (peak_flags_in_use()) HIPCHK(hipMemsetAsync(d_sizes_ + n_, 0, sizeof(uint32_t) * n_, s1));
+	if (peak_flags_in_use()) HIPCHK(hipMemsetAsync(d_sizes_ + n_ + first, 0, sizeof(uint32_t) * (first ? act : n_), s1));
 	// subband 7 in two passes: the two planes of every group and channel in one launch, behind the transforms and the division on the main stream; their segments are
 	// counted apart from the others, with the scratch buffer's stride between the groups -- so a pass over such groups always counts range by range
 	const std::vector<std::pair<int, int>> &scratch_ranges = host_->jobs.ranges_scratch;
@@ -219,21 +221,23 @@ int GpuEntropyEncoder::launch()
 		for (const auto &r : host_->jobs.ranges_rest) count_range(st, r.first, r.second);
 	} else count_range(st, 0, total_segs_ / n_);
 	HIPCHK(hipEventRecord((hipEvent_t)ev_[1], st));
-	dev::k_ent_scan<<<nbands_ * act, dev::ENT_THREADS, 0, st>>>((const dev::EntBandJob *)d_bands_, (dev::EntSegState *)d_segs_, (dev::EntBandState *)d_bandstate_, T);
+	// (a band job names its segments by their numbers in the whole batch: the window's bands and their states start first * nbands_ in)
+	dev::k_ent_scan<<<nbands_ * act, dev::ENT_THREADS, 0, st>>>((const dev::EntBandJob *)d_bands_ + (size_t)first * nbands_, (dev::EntSegState *)d_segs_, (dev::EntBandState *)d_bandstate_ + (size_t)first * nbands_, T);
 	HIPCHK(hipEventRecord((hipEvent_t)ev_[2], st));
 	// every sample's size and its place in the dense buffer follow from what the scan left: nothing is written anywhere else, nothing is copied afterwards
-	dev::k_ent_sizes<<<(act + dev::ENT_WAVES - 1) / dev::ENT_WAVES, dev::ENT_THREADS, 0, st>>>((const dev::EntFrameJob *)d_frames_, act, (const dev::EntBandState *)d_bandstate_);
-	dev::k_ent_pack_offsets<<<1, dev::ENT_THREADS, 0, st>>>(d_sizes_, act, d_offsets_);
+	dev::k_ent_sizes<<<(act + dev::ENT_WAVES - 1) / dev::ENT_WAVES, dev::ENT_THREADS, 0, st>>>(frames, act, (const dev::EntBandState *)d_bandstate_);
+	// (the offsets of all first + act frames: the sizes in front of the window are final, so their offsets come out as they were)
+	dev::k_ent_pack_offsets<<<1, dev::ENT_THREADS, 0, st>>>(d_sizes_, first + act, d_offsets_);
 	// workgroups per frame: enough to fill the chip for short batches of large frames, at least the 8 that 512 1080p frames were tuned with
 	const unsigned layout_parts = act >= 256 ? 8u : (unsigned)((2048 + act - 1) / act > 256 ? 256 : (2048 + act - 1) / act);
-	dev::k_ent_layout<<<dim3((unsigned)act, layout_parts), dev::ENT_THREADS, 0, st>>>((const dev::EntFrameJob *)d_frames_, (const dev::EntBandJob *)d_bands_, (dev::EntSegState *)d_segs_,
+	dev::k_ent_layout<<<dim3((unsigned)act, layout_parts), dev::ENT_THREADS, 0, st>>>(frames, (const dev::EntBandJob *)d_bands_, (dev::EntSegState *)d_segs_,
 	                                                  (dev::EntBandState *)d_bandstate_, T);
 	HIPCHK(hipEventRecord((hipEvent_t)ev_[3], st));
 	// the values of the peak tables (interlaced plans: the difference-coded bands; a wave looks at a segment's record and leaves unless the segment has peaks)
 	{
 		dev::EntPeakHoles which; which.n = 0;
 		for (size_t h = 0; h < tmpl_[0].holes.size() && which.n < 7; h++) if (tmpl_[0].holes[h].kind == 2) which.hole[which.n++] = (int)h;
-		if (which.n) dev::k_ent_peaks<<<dim3(act >= 64 ? 4u : 32u, (unsigned)which.n, (unsigned)act), dev::ENT_THREADS, 0, st>>>((const dev::EntFrameJob *)d_frames_, which, (const dev::EntBandJob *)d_bands_,
+		if (which.n) dev::k_ent_peaks<<<dim3(act >= 64 ? 4u : 32u, (unsigned)which.n, (unsigned)act), dev::ENT_THREADS, 0, st>>>(frames, which, (const dev::EntBandJob *)d_bands_,
 		                                                  (const dev::EntSegJob *)d_segband_, geom, (const dev::EntSegState *)d_segs_, (const dev::EntBandState *)d_bandstate_);
 	}
 #ifdef CFHD_AMD_PROBES
@@ -241,8 +245,8 @@ int GpuEntropyEncoder::launch()
 #else
 	const int emit_probe = 0;
 #endif
-	dev::k_ent_emit<<<(total_segs + dev::ENT_WAVES * dev::ENT_EMIT_SEGS - 1) / (dev::ENT_WAVES * dev::ENT_EMIT_SEGS), dev::ENT_THREADS, 0, st>>>(total_segs, (const dev::EntSegState *)d_segs_,
-	                                                          T, (const uint32_t *)d_tokens_, emit_probe);
+	dev::k_ent_emit<<<(total_segs + dev::ENT_WAVES * dev::ENT_EMIT_SEGS - 1) / (dev::ENT_WAVES * dev::ENT_EMIT_SEGS), dev::ENT_THREADS, 0, st>>>(total_segs, (const dev::EntSegState *)d_segs_ + (size_t)first * segs_per_frame,
+	                                                          T, (const uint32_t *)d_tokens_, emit_probe);      // (a segment's record names its tokens' place itself; the window's first segment opens a band)
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipEventRecord((hipEvent_t)ev_[4], st));
 	timed_ = true;
@@ -272,23 +276,24 @@ int GpuEntropyEncoder::fetch_sizes()
 	return 0;
 }
 
-int GpuEntropyEncoder::download() { const int rc = download_queue(); return rc ? rc : download_finish(); }
+int GpuEntropyEncoder::download() { const int rc = download_queue(); return rc ? rc : download_finish(); }      // (frames 0 .. active - 1)
 
 // The part of download() that can be queued behind the kernels without the host: sizes and offsets on their way to the host, the samples -- written densely in HBM by
 // launch() -- behind them.
-int GpuEntropyEncoder::download_queue()
+int GpuEntropyEncoder::download_queue(int first, int count)
 {
+	if (first < 0 || count < 1 || first + count > n_) return -1;
 	(void)hipSetDevice(device_);
 	hipStream_t st = (hipStream_t)stream_;
 	// one copy out of HBM (SDMA engine when the runtime has it enabled; the kernels storing straight into the pinned host buffer measured slower in round 2)
-	const int act = active_frames();
+	const int act = first + count;                       // (the sizes and offsets of the frames in front of a window travel again: they are what they were)
 	HIPCHK(hipMemcpyAsync(h_sizes_, d_sizes_, sizeof(uint32_t) * 2 * n_, hipMemcpyDeviceToHost, st));
 	HIPCHK(hipMemcpyAsync(h_offsets_, d_offsets_, sizeof(uint32_t) * (act + 1), hipMemcpyDeviceToHost, st));
 	// The copy of the sample bytes needs their number, which the host learns when the sizes arrive (download_finish()).  A pass that is queued as a whole
 	// (cfhd_amd_batch_submit) would start that copy only when its result is collected, a step or two later; so the copy goes out now, sized by what the last pass of this
 	// many frames produced plus a margin, and download_finish() adds the remainder if this pass turned out larger (consecutive passes of a sequence differ by a few percent).
 	copied_ahead_ = 0;
-	if (expect_bytes_ && expect_frames_ == act) {
+	if (expect_bytes_ && expect_frames_ == act && !first) {
 		copied_ahead_ = expect_bytes_ < cap_ * (size_t)act ? expect_bytes_ : cap_ * (size_t)act;
 		HIPCHK(hipMemcpyAsync(h_samples_, d_packed_, copied_ahead_, hipMemcpyDeviceToHost, st));
 	}
@@ -296,13 +301,15 @@ int GpuEntropyEncoder::download_queue()
 }
 
 // ... and the part that needs the sizes: waits for the stream, then queues the one copy of all sample bytes (wait on the stream afterwards).
-int GpuEntropyEncoder::download_finish()
+int GpuEntropyEncoder::download_finish(int first, int count)
 {
+	if (first < 0 || count < 1 || first + count > n_) return -1;
 	(void)hipSetDevice(device_);
 	hipStream_t st = (hipStream_t)stream_;
-	const int act = active_frames();
+	const int act = first + count;
 	HIPCHK(hipStreamSynchronize(st));
 	const size_t total = h_offsets_[act];
+	if (first) copied_ahead_ = h_offsets_[first];        // (a window: the samples in front of it are on the host already, and unchanged)
 	if (total > copied_ahead_) HIPCHK(hipMemcpyAsync(h_samples_ + copied_ahead_, d_packed_ + copied_ahead_, total - copied_ahead_, hipMemcpyDeviceToHost, st));
 	expect_bytes_ = speculative_download_ ? ((total + total / 32 + 4095) & ~(size_t)4095) : 0; expect_frames_ = act;
 	return 0;

@@ -381,14 +381,15 @@ enum { ENT_COUNT_SEGS = 1 };
 // beside the level-2 / level-3 transforms (GpuEntropyEncoder::launch).
 __global__ void __launch_bounds__(ENT_THREADS) k_ent_count(const EntSegJob *seg_jobs, EntBatchGeom geom, int total_segs, EntSegState *segs, const EntTables *tables,
                                                             uint32_t *peak_flags, uint32_t *tokens, int range_lo, int range_n,
-                                                            int probe = 0 /* timing experiments: 1 behind the loads, 2 behind the compaction, 4 no token stores */)
+                                                            int probe = 0 /* timing experiments: 1 behind the loads, 2 behind the compaction, 4 no token stores */,
+                                                            int frame_base = 0 /* the launch covers the frames from this one on (a window of the batch: GpuEntropyEncoder::launch) */)
 {
 	__shared__ uint32_t s_tok_all[ENT_WAVES][ENT_SEG];       // a window's tokens: raster index in the segment << 16 | value (16 bits); every coefficient may be one
 	const int lane = wave_lane();
 	const int wave = wave_uniform((int)(threadIdx.x >> 6));
 	const int idx0 = wave_uniform(((int)blockIdx.x * ENT_WAVES + wave) * ENT_COUNT_SEGS);
 	if (idx0 >= total_segs) return;                      // whole wave
-	const int seg0 = (idx0 / range_n) * geom.segs_per_frame + range_lo + idx0 % range_n;      // (ENT_COUNT_SEGS == 1: one index, one segment)
+	const int seg0 = (frame_base + idx0 / range_n) * geom.segs_per_frame + range_lo + idx0 % range_n;      // (ENT_COUNT_SEGS == 1: one index, one segment)
 	static_assert(ENT_COUNT_SEGS == 1, "the range mapping takes one segment per wave");
 	EntSegJob job[ENT_COUNT_SEGS]; int frame[ENT_COUNT_SEGS]; size_t tok_base[ENT_COUNT_SEGS];
 	uint32_t w[ENT_COUNT_SEGS][ENT_SEG / 128];
@@ -413,7 +414,7 @@ __global__ void __launch_bounds__(ENT_THREADS) k_ent_count(const EntSegJob *seg_
 // band on ordinary pictures -- and 8 bytes per chunk.  Same segment states and token strings as k_ent_count, by construction (the same token coder).
 struct EntBlockLists { const uint4 *blocks; const unsigned long long *masks; const int16_t *coeff0; size_t masks_per_frame; };
 __global__ void __launch_bounds__(ENT_THREADS) k_ent_count_blocks(const EntSegJob *seg_jobs, EntBatchGeom geom, int total_segs, EntSegState *segs, const EntTables *tables,
-                                                                   uint32_t *peak_flags, uint32_t *tokens, int range_lo, int range_n, EntBlockLists lists)
+                                                                   uint32_t *peak_flags, uint32_t *tokens, int range_lo, int range_n, EntBlockLists lists, int frame_base = 0 /* as for k_ent_count */)
 {
 	__shared__ uint32_t s_tok_all[ENT_WAVES][ENT_SEG];
 	enum { SPAN_BLOCKS = ENT_BLK_SPAN / 8, HMAX = SPAN_BLOCKS / ENT_LANES };
@@ -421,7 +422,7 @@ __global__ void __launch_bounds__(ENT_THREADS) k_ent_count_blocks(const EntSegJo
 	const int wave = wave_uniform((int)(threadIdx.x >> 6));
 	const int idx0 = wave_uniform((int)blockIdx.x * ENT_WAVES + wave);
 	if (idx0 >= total_segs) return;                      // whole wave
-	const int seg = (idx0 / range_n) * geom.segs_per_frame + range_lo + idx0 % range_n;
+	const int seg = (frame_base + idx0 / range_n) * geom.segs_per_frame + range_lo + idx0 % range_n;
 	int frame; size_t tok_base;
 	const EntSegJob job = ent_seg_job(seg_jobs, geom, seg, &frame, &tok_base);
 	const EntTables *T = tables + job.table;

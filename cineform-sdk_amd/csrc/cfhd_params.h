@@ -12,6 +12,9 @@ struct FrontEndParams {
 	bool progressive = true;
 	bool static_quantizer = true;                             // false: the quality re-derives its tables from the size of the previous sample (rate feedback)
 	FramePlan plan;                                           // geometry + first-frame quantizer
+	// what the rate feedback goes on from (cfhd_batch.cpp, the frame queue's streams): the quality word derive_quantization takes -- the caller's with the format
+	// marks, where `quality` above is the header's -- and the quantizer state behind the derivation of the first frame's tables
+	int derive_quality = 0; QuantState qstate = {0, -1, 0};
 	// CFHD_ENCODING_FLAGS_YUV_2FRAME_GOP: the group's plan with its quantizer tables; whether those tables follow the size of the previous key sample (rate feedback);
 	// whether the input's own pixel format is an output a group of this scan and width decodes to at full resolution; the input format of the sequence header
 	bool gop = false, gop_static_quantizer = true, gop_output_served = false;

@@ -140,6 +140,8 @@ CFHD_Error CFHD_CloseMetadata(CFHD_MetadataRef metadataRef);                    
 typedef struct cfhd_amd_batch cfhd_amd_batch;
 /* nframes frames of one geometry travel through every stage together, one launch per stage (cfhd_batch.cpp).  The arguments are those of
  * CFHD_PrepareToEncode; mode 0: encode + decode back to the same pixel format, mode 1: encode only (the only mode for BYR4).
+ * NULL for a quality word whose quantizer tables follow the size of the sample in front (cfhd_amd_quantizer_is_static answers 0): those streams go through
+ * cfhd_amd_batch_create_stream below; this entry keeps refusing them, for callers that probe with it.
  * cfhd_amd_batch_create: 4:2:2 progressive round trip (YUY2 / 2vuy), kept for callers of the first release. */
 cfhd_amd_batch *cfhd_amd_batch_create_ex(int width, int height, uint32_t pixel_format, int encoded_format, uint32_t encoding_flags,
                                          int quality, int nframes, int nthreads, int mode);
@@ -185,6 +187,32 @@ int  cfhd_amd_batch_get_sequence_header(cfhd_amd_batch *batch, const void **data
  * decoder output (RG64, the Avid layouts), a geometry the device group decoder does not take.  Every other cfhd_amd_batch_* entry point is shared and keeps its meaning
  * per frame index; -9 keeps its meaning. */
 cfhd_amd_batch *cfhd_amd_batch_create_groups(int width, int height, uint32_t pixel_format, uint32_t encoding_flags, int quality, int nframes, int nthreads, int mode);
+/* One encoder's stream on the frame queue, rate feedback included.  The arguments are cfhd_amd_batch_create_ex's for intra frames, and every quality word
+ * CFHD_PrepareToEncode takes for them is taken: also the words whose quantizer tables follow the size of the sample in front (cfhd_amd_quantizer_is_static answers 0:
+ * MEDIUM and HIGH on 4:2:2 frames up to 1920 x 1080, FILMSCAN2 / FILMSCAN3 everywhere), which cfhd_amd_batch_create_ex keeps refusing, for callers that probe with it.
+ * A batch made here is ONE encoder's stream: frame i of pass k (counted from 0) is call k * nframes + i + 1 of one CFHD_EncodeSample handle prepared with the same
+ * arguments and fed the same frames, and its sample is that call's sample byte for byte -- quantizer tables, header, frame number, metadata.  The quantizer state is
+ * carried from the last frame of a pass to the first of the next.  For a word whose tables stand still this is exactly cfhd_amd_batch_create_ex's batch, same samples,
+ * same launches.  For the others a pass is coded on a guess of every frame's tables (the first pass: the first frame's; afterwards: the tables the pass before ended
+ * with, frame by frame) and checked against the sizes that come back in cfhd_amd_batch_wait; the frames from the first wrong guess on are coded again, as often as it
+ * takes -- n rounds at the most, one on material whose tables stand still, which is the rule (the bit-rate limiter moves beyond 110 - 150 Mbit/s at 30 fps, the
+ * FILMSCAN2 / 3 limiter settles within about twenty frames).  cfhd_amd_batch_submit queues round 0 without a host wait, as for every batch; the further rounds run inside
+ * cfhd_amd_batch_wait.  Every other cfhd_amd_batch_* entry point is shared and keeps its meaning per frame index (upload, roundtrip, submit, submit_host, wait,
+ * get_sample, download_output, kernel_ms / kernel_name -- of the last round).  mode 0 / 1 as for cfhd_amd_batch_create_ex; in mode 0 the pictures are those of the
+ * final samples (the decoder's half runs again when round 0 did not hold).
+ * A pass that fails (-3: a sample that does not fit its buffer, ...) leaves the stream's quantizer state as it was when the pass began; its samples are not the
+ * handle's, and the stream is not to be continued behind it -- make a new batch.  A stream's tail shorter than nframes is padded by the caller (repeat the last
+ * frame): feedback only flows forward, so the samples of the real frames do not depend on the padding; drop the padding's samples.  Independent streams -- several
+ * batches -- overlap in flight like any batches; the passes of one stream depend on each other and run one at a time.
+ * NULL, with the reason in cfhd_amd_last_error(): whatever cfhd_amd_batch_create_ex refuses for reasons other than moving tables; nframes < 1;
+ * CFHD_ENCODING_FLAGS_YUV_2FRAME_GOP (groups: cfhd_amd_batch_create_groups, tables that stand still only); CFHD_AMD_ENTROPY=host; for words whose tables move, the
+ * arrangements with host work inside a pass (CFHD_AMD_HANDOFF=host, CFHD_AMD_CHUNK). */
+cfhd_amd_batch *cfhd_amd_batch_create_stream(int width, int height, uint32_t pixel_format, int encoded_format, uint32_t encoding_flags,
+                                             int quality, int nframes, int nthreads, int mode);
+/* The last completed pass of a stream batch: out[0] encode rounds (>= 1), out[1] frames coded over all rounds (>= nframes), out[2] frames whose tables differ from
+ * those of the frame in front (frame 0: from the last frame of the pass before; in pass 0 it counts 0).  0, or -1 for a batch not made by
+ * cfhd_amd_batch_create_stream, before its first pass has completed, and between submit and wait. */
+int  cfhd_amd_batch_stream_stats(cfhd_amd_batch *batch, int out[3]);
 float cfhd_amd_batch_kernel_ms(cfhd_amd_batch *batch, int which);                              /* HIP-event time of the kernels of the last pass */
 const char *cfhd_amd_batch_kernel_name(cfhd_amd_batch *batch, int which);                      /* which 0..5: the transform kernel behind that time */
 double cfhd_amd_batch_stage_seconds(cfhd_amd_batch *batch, int which);
