@@ -67,7 +67,7 @@ int front_end_params(int width, int height, uint32_t pixel_format, int encoded_f
 	out->derive_quality = p.quality; out->qstate = p.qstate;
 	out->gop = p.gop;
 	if (p.gop) {
-		out->gplan = p.gplan; out->gop_static_quantizer = group_quantizer_is_static(p);
+		out->gplan = p.gplan; out->gqstate = p.gstate; out->gop_static_quantizer = group_quantizer_is_static(p);
 		// (interlaced groups exist from YUY2 / 2vuy only, and those decode to themselves)
 		out->gop_output_served = yuv422_output_served(p.pixel_kind, width, false);
 		out->gop_sequence_format = gop_sequence_input_format(p.pixel_kind, out->color_format);

@@ -79,16 +79,10 @@ CFHD_Error CFHD_EncodeSample(CFHD_EncoderRef ref, void *frame, int pitch)
 		// and so does the P-frame header behind it (pinned on the reference's samples).
 		if (prepare_group_encoder(e)) return ERR_INTERNAL;
 		const uint32_t n = e->gop_calls++;
-		// Rate feedback (encoder.c:2880-2905): every call re-derives the subband tables from the size of the last key sample (the FILMSCAN2/3 limiter moves), the
-		// call that opens a group also runs the bit-rate limiter and deals the divisors to the group's wavelets -- both frames of the group are quantized with them
-		if (!(n & 1u)) {
-			GopPlan next = e->params.gplan;
-			if (!derive_gop_quantization(&next, e->params.quality, &e->params.gstate, 0.0f, true)) return ERR_INTERNAL;
-			bool changed = next.midpoint_prequant != e->params.gplan.midpoint_prequant;
-			for (int c = 0; c < 3 && !changed; c++)
-				for (int k = 0; k < kGopWavelets && !changed; k++) changed = memcmp(next.ch[c].w[k].quant, e->params.gplan.ch[c].w[k].quant, sizeof(next.ch[c].w[k].quant)) != 0;
-			if (changed) { e->params.gplan = next; e->gop_batch.set_plan(next); }
-		} else derive_gop_quantization(&e->params.gplan, e->params.quality, &e->params.gstate, 0.0f, false);
+		// Rate feedback: this call's step of the walk the frame queue's group streams take too (cfhd_gop.h gop_quant_call)
+		bool changed = false;
+		if (!gop_quant_call(&e->params.gplan, e->params.quality, &e->params.gstate, !(n & 1u), &changed)) return ERR_INTERNAL;
+		if (changed) e->gop_batch.set_plan(e->params.gplan);
 		if (e->gop_batch.upload_frame((int)(n & 1u), frame, pitch)) return ERR_INTERNAL;
 		size_t bytes;
 		if (!(n & 1u)) {
@@ -119,7 +113,7 @@ CFHD_Error CFHD_EncodeSample(CFHD_EncoderRef ref, void *frame, int pitch)
 		e->meta.local.clear();
 		if (!bytes) return ERR_CODEC_ERROR;
 		e->sample_size = bytes;
-		if (n == 0 || (n & 1u)) e->params.gstate.lastgopbitcount = (int64_t)bytes * 8;      // key samples: the sequence header and the groups (encoder.c:3414)
+		if (n == 0 || (n & 1u)) gop_quant_key_sample(&e->params.gstate, bytes);      // key samples: the sequence header and the groups (encoder.c:3414)
 		return ERR_OKAY;
 	}
 	if (!e->batch_ready) {

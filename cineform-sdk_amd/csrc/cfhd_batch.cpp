@@ -9,7 +9,8 @@
 //
 // Two-frame groups (CFHD_ENCODING_FLAGS_YUV_2FRAME_GOP): a batch of nframes / 2 groups, frames 2 g and 2 g + 1 forming group g, through two GopBatch objects (encoder |
 // decoder) in the default arrangement only -- every stage on the GPU, the group samples parsed where the coder left them (k_dec_parse_group), one chunk, no host wait
-// between submit and wait.  The P-frame samples and the sequence header are host code.
+// between submit and wait.  The P-frame samples and the sequence header are host code.  cfhd_amd_batch_create_group_stream: the same batch as one group encoder's
+// stream, tables that follow the key samples included (Stream, GroupUnits).
 #include "../../include/cfhd_amd.h"
 #include "cfhd_core.h"
 #include "cfhd_bitstream.h"
@@ -67,14 +68,19 @@ struct cfhd_amd_batch {
 	// feedback included.  moving: the quality's tables follow the size of the sample in front (encode_one, cfhd_api_params.h); then every frame carries tables of its
 	// own, a pass is coded on a guess of them and the frames from the first wrong guess on are coded again (stream_rounds).  The state below is the handle's
 	// EncodeParams::qstate / plan, held at the pass boundary; a pass that fails leaves it alone.
+	// cfhd_amd_batch_create_group_stream: the same for two-frame groups -- "frame" reads "group" (a unit of the pass), the handle is one that was prepared with the group
+	// flag, its state EncodeParams::gstate / gplan, the size that feeds back the one of the key sample in front (the group sample; the sequence header for the first).
+	template <typename Plan> struct StreamTables {
+		Plan carried_plan;                              // the tables of the last unit of the last completed pass (before the first pass: the tables CFHD_PrepareToEncode derives)
+		std::vector<Plan> coded;                        // the tables unit i was coded with last: a pass's guess, then its result, then the next pass's guess
+	};
 	struct Stream {
 		bool on = false, moving = false;
 		int derive_quality = 0;                         // the quality word derive_quantization takes (the caller's with the format marks)
-		QuantState carried = {0, -1, 0};                // behind the last frame of the last completed pass
-		FramePlan carried_plan;                         // that frame's tables (before the first pass: the tables CFHD_PrepareToEncode derives)
-		size_t carried_bytes = 0;                       // that frame's sample size (0: no frame yet -- the first frame of a stream derives nothing)
-		std::vector<FramePlan> coded;                   // the tables frame i was coded with last: a pass's guess, then its result, then the next pass's guess
-		std::vector<QuantState> before;                 // the state in front of frame i's derivation, as far as the pass is verified
+		QuantState carried = {0, -1, 0};                // behind the last unit of the last completed pass
+		size_t carried_bytes = 0;                       // that unit's sample size (0: none yet -- the first frame of a stream derives nothing)
+		StreamTables<FramePlan> frames; StreamTables<GopPlan> groups;      // (the one the batch's units are)
+		std::vector<QuantState> before;                 // the state in front of unit i's derivation, as far as the pass is verified
 		QuantState next = {0, -1, 0};                   // what a pass that ends well carries on
 		int rounds = 0, frames_coded = 0, stats[3] = {0, 0, 0}; bool stats_valid = false;
 	} stream;
@@ -114,20 +120,96 @@ SampleHeaderInfo stream_header(const cfhd_amd_batch *b, int i)
 	SampleHeaderInfo h = { b->steps * (uint32_t)b->n + (uint32_t)i + 1, b->color_format, b->color_space, b->quality, b->progressive, b->frame_meta[i].data(), b->frame_meta[i].size(), nullptr, 0 };
 	return h;
 }
-// Round 0 of a pass: frame 0 carries the tables the carried state gives it, the frames behind it a guess -- in the first pass the same tables, afterwards the tables
-// the last pass ended with, frame by frame (on ordinary material the tables stand still for long runs, and a cut that repeats -- a loop, a benchmark -- repeats them).
-int stream_begin_pass(cfhd_amd_batch *b)
+// The header of group g's sample: the number and the metadata of the handle's call that completes the group (gop_launch deals the blocks, one per frame and pass)
+SampleHeaderInfo group_header(const cfhd_amd_batch *b, int g)
 {
+	const MetaBlock &m = b->frame_meta[2 * g + 1];
+	SampleHeaderInfo h = { b->steps * (uint32_t)b->n + 2u * (uint32_t)g + 1u, b->color_format, b->color_space, b->quality, b->progressive, m.data(), m.size(), nullptr, 0 };
+	return h;
+}
+uint32_t pass_seed(const cfhd_amd_batch *b) { return 0xA511E9B3u * (b->steps + 1); }
+
+// What the passes of a stream ask of their units: the frames of an intra batch (FrameUnits) or the groups of a group batch (GroupUnits).  stream_begin_pass,
+// stream_rounds and stream_end_pass below are written once against these.
+struct FrameUnits {
+	typedef FramePlan Plan;
+	cfhd_amd_batch *b; cfhd_amd_chunk *c;
+	explicit FrameUnits(cfhd_amd_batch *batch) : b(batch), c(batch->chunks[0].get()) {}
+	int count() const { return b->n; }
+	int frames_per_unit() const { return 1; }
+	cfhd_amd_batch::StreamTables<Plan> &tables() const { return b->stream.frames; }
+	GpuEntropyEncoder &entropy() const { return c->enc.entropy(); }
+	static bool same(const Plan &x, const Plan &y) { return same_tables(x, y); }
+	bool step(QuantState *st, size_t bytes_in_front, Plan *plan, int) const { stream_step(b, st, bytes_in_front, plan); return true; }
+	const Plan &device_plan(int i) const { return c->enc.frame_plan(i); }
+	int set_tables(int i, const Plan &p) const { return c->enc.set_frame_quant(i, p); }
+	int set_header(int i, const Plan &p) const { entropy().set_plan(p); return entropy().set_frame_header(i, stream_header(b, i)); }      // (the header carries the unit's own tables)
+	bool spoils_the_pass(int i) const { return !entropy().sample_bytes(i); }      // (a final sample that does not fit its buffer: -3)
+	int launch_window(int first, int n) const { return c->enc.launch_forward(false, first, n); }
+	int encoder_wait() const { return c->enc.wait(); }
+	int decoder_wait() const { return c->dec.wait(); }
+	int decode_again() const                            // the decoder's half over the final samples
+	{
+		GpuEntropyEncoder &ent = entropy();
+		c->dec.entropy().set_producer_events(ent.headers_event(), ent.samples_event());
+		if (c->dec.entropy().set_samples_device(ent.device_samples(), 0, ent.device_sizes(), ent.device_offsets())) return -4;
+		if (c->dec.launch_entropy() || c->dec.launch_inverse(pass_seed(b) + (uint32_t)c->first)) return -5;
+		if (b->host_out && c->dec.download_frames(b->host_out, b->host_out_stride, b->host_out_pitch)) return -5;
+		return 0;
+	}
+	size_t last_sample_bytes() const { return b->sample_size[b->n - 1]; }
+};
+struct GroupUnits {
+	typedef GopPlan Plan;
+	cfhd_amd_batch *b;
+	explicit GroupUnits(cfhd_amd_batch *batch) : b(batch) {}
+	int count() const { return b->ngroups(); }
+	int frames_per_unit() const { return 2; }
+	cfhd_amd_batch::StreamTables<Plan> &tables() const { return b->stream.groups; }
+	GpuEntropyEncoder &entropy() const { return b->genc->entropy(); }
+	static bool same(const Plan &x, const Plan &y) { return gop_same_tables(x, y); }
+	// the two calls of the handle that make group g (cfhd_gop.h gop_quant_group), on the bytes of the key sample in front; the stream's first group: on none, the
+	// sequence header lying between its two calls
+	bool step(QuantState *st, size_t bytes_in_front, Plan *plan, int g) const
+	{
+		gop_quant_key_sample(st, bytes_in_front);
+		return gop_quant_group(plan, b->stream.derive_quality, st, b->steps == 0 && g == 0, kSequenceHeaderBytes);
+	}
+	const Plan &device_plan(int g) const { return b->genc->group_plan(g); }
+	int set_tables(int g, const Plan &p) const { return b->genc->set_group_plan(g, p); }
+	int set_header(int g, const Plan &p) const { entropy().set_group_plan(p); return entropy().set_frame_header(g, group_header(b, g)); }
+	// (-3, and -9: the handle would hand such a group to the host writer, whose sample the device stage cannot give -- gop_finish fails the pass)
+	bool spoils_the_pass(int g) const { const size_t n = entropy().sample_bytes(g); return !n || gop_sample_may_zero_bands(b->gplan, n); }
+	int launch_window(int first, int n) const { return b->genc->launch_forward(first, n); }
+	int encoder_wait() const { return b->genc->wait(); }
+	int decoder_wait() const { return b->gdec->wait(); }
+	int decode_again() const
+	{
+		GpuEntropyEncoder &ent = entropy(); GopBatch &dec = *b->gdec;
+		dec.batch_entropy().set_producer_events(ent.headers_event(), ent.samples_event());
+		if (dec.batch_entropy().set_samples_device(ent.device_samples(), ent.device_sizes(), ent.device_offsets())) return -4;
+		if (dec.batch_entropy().launch() || dec.launch_inverse(pass_seed(b), true)) return -5;
+		if (b->host_out && dec.download_frames(b->host_out, b->host_out_stride, b->host_out_pitch)) return -5;
+		return 0;
+	}
+	size_t last_sample_bytes() const { return b->sample_size[b->n - 2]; }
+};
+
+// Round 0 of a pass: unit 0 carries the tables the carried state gives it, the units behind it a guess -- in the first pass the same tables, afterwards the tables
+// the last pass ended with, unit by unit (on ordinary material the tables stand still for long runs, and a cut that repeats -- a loop, a benchmark -- repeats them).
+template <typename Units> int stream_begin_pass(const Units &u)
+{
+	cfhd_amd_batch *b = u.b;
 	cfhd_amd_batch::Stream &s = b->stream;
-	cfhd_amd_chunk *c = b->chunks[0].get();
+	std::vector<typename Units::Plan> &coded = u.tables().coded;
 	s.rounds = 1; s.frames_coded = b->n;
-	QuantState st = s.carried; FramePlan first = s.carried_plan;
-	stream_step(b, &st, s.carried_bytes, &first);
-	for (int i = 0; i < b->n; i++) {
-		const FramePlan &guess = i && b->steps ? s.coded[i] : first;
-		if (same_tables(guess, c->enc.frame_plan(i))) { s.coded[i] = c->enc.frame_plan(i); continue; }
-		s.coded[i] = guess;
-		if (c->enc.set_frame_quant(i, guess)) return -2;
+	QuantState st = s.carried; typename Units::Plan first = u.tables().carried_plan;
+	if (!u.step(&st, s.carried_bytes, &first, 0)) return -2;
+	for (int i = 0; i < u.count(); i++) {
+		const typename Units::Plan &guess = i && b->steps ? coded[i] : first;
+		if (Units::same(guess, u.device_plan(i))) { coded[i] = u.device_plan(i); continue; }
+		coded[i] = guess;
+		if (u.set_tables(i, guess)) return -2;
 	}
 	return 0;
 }
@@ -137,58 +219,56 @@ int stream_begin_pass(cfhd_amd_batch *b)
 // it get the tables the walk has found (a guess again behind the first) and are coded again, as a window of the batch; j rises every round, so a pass takes at most n
 // rounds and ends on the handle's samples.  The metadata blocks are the ones batch_launch dealt: one per frame and pass.  Returns 0 -- also for a pass that batch_finish
 // is about to fail (a verified frame that does not fit) -- or < 0.
-int stream_rounds(cfhd_amd_batch *b)
+template <typename Units> int stream_rounds(const Units &u)
 {
+	typedef typename Units::Plan Plan;
+	cfhd_amd_batch *b = u.b;
 	cfhd_amd_batch::Stream &s = b->stream;
-	cfhd_amd_chunk *c = b->chunks[0].get();
-	GpuEntropyEncoder &ent = c->enc.entropy();
-	const int n = b->n;
-	std::vector<FramePlan> found((size_t)n);
+	std::vector<Plan> &coded = u.tables().coded;
+	GpuEntropyEncoder &ent = u.entropy();
+	const int n = u.count();
+	std::vector<Plan> found((size_t)n);
 	bool recoded = false;
 	s.before[0] = s.carried;
 	for (int j = 0;;) {
-		QuantState st = s.before[j]; FramePlan plan = j ? s.coded[j - 1] : s.carried_plan;
+		QuantState st = s.before[j]; Plan plan = j ? coded[j - 1] : u.tables().carried_plan;
 		int wrong = -1;
 		for (int i = j; i < n; i++) {
 			const size_t in_front = i ? ent.sample_bytes(i - 1) : s.carried_bytes;
-			if (wrong < 0 && i && !in_front) return 0;      // (sample i - 1 is final and does not fit its buffer: -3)
+			if (wrong < 0 && i && u.spoils_the_pass(i - 1)) return 0;      // (sample i - 1 is final, and fails the pass)
 			if (wrong < 0) s.before[i] = st;
-			stream_step(b, &st, in_front, &plan);
-			if (wrong < 0 && !same_tables(plan, s.coded[i])) wrong = i;
+			if (!u.step(&st, in_front, &plan, i)) return -2;
+			if (wrong < 0 && !Units::same(plan, coded[i])) wrong = i;
 			found[i] = plan;
 		}
 		if (wrong < 0) { s.next = st; break; }
 		// (mode 0: the decoder of the round before is reading the dense buffer the coder is about to write again)
-		if (b->decode && c->dec.wait()) return -5;
+		if (b->decode && u.decoder_wait()) return -5;
 		for (int i = wrong; i < n; i++) {
-			s.coded[i] = found[i];
-			if (c->enc.set_frame_quant(i, found[i])) return -2;
-			ent.set_plan(found[i]);
-			if (ent.set_frame_header(i, stream_header(b, i))) return -6;
+			coded[i] = found[i];
+			if (u.set_tables(i, found[i])) return -2;
+			if (u.set_header(i, found[i])) return -6;
 		}
 		const int count = n - wrong;
-		if (c->enc.launch_forward(false, wrong, count) || ent.launch(wrong, count) || ent.download_queue(wrong, count) || ent.download_finish(wrong, count) || c->enc.wait()) return -2;
-		s.rounds++; s.frames_coded += count; recoded = true;
+		if (u.launch_window(wrong, count) || ent.launch(wrong, count) || ent.download_queue(wrong, count) || ent.download_finish(wrong, count) || u.encoder_wait()) return -2;
+		s.rounds++; s.frames_coded += count * u.frames_per_unit(); recoded = true;
 		j = wrong;
 	}
-	if (recoded && b->decode) {                         // the decoder's half again, over the final samples
-		c->dec.entropy().set_producer_events(ent.headers_event(), ent.samples_event());
-		if (c->dec.entropy().set_samples_device(ent.device_samples(), 0, ent.device_sizes(), ent.device_offsets())) return -4;
-		if (c->dec.launch_entropy() || c->dec.launch_inverse(0xA511E9B3u * (b->steps + 1) + (uint32_t)c->first)) return -5;
-		if (b->host_out && c->dec.download_frames(b->host_out, b->host_out_stride, b->host_out_pitch)) return -5;
-	}
+	if (recoded && b->decode) return u.decode_again();
 	return 0;
 }
-// A pass that ended well: its last frame is what the next pass goes on from.  stats: rounds, frames coded over all rounds, frames whose tables differ from those of
-// the frame in front (frame 0: from the last frame of the pass before).
-void stream_end_pass(cfhd_amd_batch *b)
+// A pass that ended well: its last unit is what the next pass goes on from.  stats: rounds, frames coded over all rounds, units whose tables differ from those of
+// the unit in front (unit 0: from the last unit of the pass before; in a stream's first pass it has none in front).
+template <typename Units> void stream_end_pass(const Units &u)
 {
+	cfhd_amd_batch *b = u.b;
 	cfhd_amd_batch::Stream &s = b->stream;
 	if (!s.moving) { s.stats[0] = 1; s.stats[1] = b->n; s.stats[2] = 0; s.stats_valid = true; return; }
+	const std::vector<typename Units::Plan> &coded = u.tables().coded;
 	int moved = 0;
-	for (int i = 0; i < b->n; i++) moved += !same_tables(s.coded[i], i ? s.coded[i - 1] : s.carried_plan);
+	for (int i = 0; i < u.count(); i++) moved += (i || b->steps) && !Units::same(coded[i], i ? coded[i - 1] : u.tables().carried_plan);
 	s.stats[0] = s.rounds; s.stats[1] = s.frames_coded; s.stats[2] = moved; s.stats_valid = true;
-	s.carried = s.next; s.carried_plan = s.coded[b->n - 1]; s.carried_bytes = b->sample_size[b->n - 1];
+	s.carried = s.next; u.tables().carried_plan = coded[u.count() - 1]; s.carried_bytes = u.last_sample_bytes();
 }
 
 // The default pass (all stages on the GPU, samples handed over in HBM, one chunk) in two halves with no host wait inside either.
@@ -203,7 +283,7 @@ int batch_launch(cfhd_amd_batch *b)
 	b->frame_meta.resize(b->n);
 	for (int i = 0; i < b->n; i++) { b->meta.handle(); b->frame_meta[i] = b->meta.global; meta_remove_hidden(b->frame_meta[i]); }
 	const uint32_t seed = 0xA511E9B3u * (b->steps + 1);
-	if (b->stream.moving && stream_begin_pass(b)) return -2;
+	if (b->stream.moving && stream_begin_pass(FrameUnits(b))) return -2;
 	// Encode-only passes in flight on one device take turns (cfhd_device.h stage_order_wait): this pass's forward transform starts behind the entropy coder of the pass
 	// queued before it.  Passes that start together otherwise run in lock step -- all encode, then all copy their samples to the host, and the copies (the PCIe link) and
 	// the kernels never overlap: byr4-2160p 18.9 k fps with turns, 11.9 k without; rg48-2160p 15.9 / 12.4 k.  Round-trip passes run free: their decode halves fill the
@@ -219,7 +299,7 @@ int batch_launch(cfhd_amd_batch *b)
 	if (c->enc.launch_forward(false)) return -2;         // (nothing but the entropy stage reads these coefficients)
 	for (int l = 0; l < c->n; l++) {
 		SampleHeaderInfo h = { base_number + (uint32_t)(c->first + l) + 1, b->color_format, b->color_space, b->quality, b->progressive, b->frame_meta[c->first + l].data(), b->frame_meta[c->first + l].size(), nullptr, 0 };
-		if (b->stream.moving) c->enc.entropy().set_plan(b->stream.coded[l]);      // (the header carries the frame's own tables)
+		if (b->stream.moving) c->enc.entropy().set_plan(b->stream.frames.coded[l]);      // (the header carries the frame's own tables)
 		if (c->enc.entropy().set_frame_header(l, h)) return -6;
 	}
 	if (c->enc.entropy().launch()) return -2;
@@ -244,7 +324,7 @@ long long batch_finish(cfhd_amd_batch *b)
 	if (c->enc.entropy().download_finish() || c->enc.wait()) return -2;
 	// a stream whose tables move: the sizes say whether the guess of the tables held; if not, the frames behind the first wrong one are coded again (no turns taken:
 	// stage_order_wait is round 0's)
-	if (b->stream.moving) { const int rc = stream_rounds(b); if (rc) return rc; }
+	if (b->stream.moving) { const int rc = stream_rounds(FrameUnits(b)); if (rc) return rc; }
 	// A frame whose sample does not fit its buffer has size 0 (k_ent_layout) and fails the pass with -3 -- behind the loop: the samples of the other frames are complete
 	// and keep their sizes for cfhd_amd_batch_get_sample, and the decoder's stream, which is parsing these buffers, has drained before the caller gets the batch back.
 	bool overflow = false, peaks = false;
@@ -265,7 +345,7 @@ long long batch_finish(cfhd_amd_batch *b)
 	}
 	const double t4 = now();
 	b->t_fwd = b->t_launched - b->t_launch0; b->t_entropy_enc = t_enc - b->t_launched; b->t_entropy_dec = 0; b->t_inv = t4 - t_enc;
-	if (b->stream.on) stream_end_pass(b);
+	if (b->stream.on) stream_end_pass(FrameUnits(b));
 	b->steps++;
 	long long total = 0;
 	for (int i = 0; i < b->n; i++) total += (long long)b->sample_size[i];
@@ -280,7 +360,6 @@ int gop_launch(cfhd_amd_batch *b)
 	GopBatch &enc = *b->genc;
 	const int ng = b->ngroups();
 	b->t_launch0 = now();
-	const uint32_t base_number = b->steps * (uint32_t)b->n;
 	// the metadata of the handle's call that completes group g: CFHD_EncodeSample advances it on every call, frame by frame
 	b->frame_meta.resize(b->n);
 	for (int i = 0; i < b->n; i++) { b->meta.handle(); b->frame_meta[i] = b->meta.global; meta_remove_hidden(b->frame_meta[i]); }
@@ -289,14 +368,14 @@ int gop_launch(cfhd_amd_batch *b)
 	const int turns = forced >= 0 ? forced : (b->decode ? 0 : 1);      // (encode-only passes take turns, round trips run free: batch_launch says why)
 	const bool ordered = turns >= 1, ordered_decode = turns >= 2;
 	if (ordered && stage_order_wait(enc.device(), 0, enc.stream())) return -2;
+	if (b->stream.moving && stream_begin_pass(GroupUnits(b))) return -2;      // (in front of the first launch: it rewrites rows of the job tables)
 	if (b->host_in && enc.upload_frames(b->host_in, b->host_in_stride, b->host_in_pitch)) return -2;
 	if (enc.launch_forward()) return -2;
 	for (int g = 0; g < ng; g++) {
-		const MetaBlock &m = b->frame_meta[2 * g + 1];
-		const uint32_t number = base_number + 2u * (uint32_t)g + 1u;
-		SampleHeaderInfo h = { number, b->color_format, b->color_space, b->quality, b->progressive, m.data(), m.size(), nullptr, 0 };
+		const SampleHeaderInfo h = group_header(b, g);
+		if (b->stream.moving) enc.entropy().set_group_plan(b->stream.groups.coded[g]);      // (the header carries the group's own tables)
 		if (enc.entropy().set_frame_header(g, h)) return -6;
-		if (write_pframe_sample(b->gplan, number, b->pframes.data() + (size_t)kPFrameSampleBytes * g, kPFrameSampleBytes) != kPFrameSampleBytes) return -6;
+		if (write_pframe_sample(b->gplan, h.frame_number, b->pframes.data() + (size_t)kPFrameSampleBytes * g, kPFrameSampleBytes) != kPFrameSampleBytes) return -6;
 	}
 	if (enc.entropy().launch()) return -2;
 	if (ordered && stage_order_done(enc.device(), 0, enc.stream())) return -2;
@@ -319,6 +398,8 @@ long long gop_finish(cfhd_amd_batch *b)
 	GopBatch &enc = *b->genc;
 	const int ng = b->ngroups();
 	if (enc.entropy().download_finish() || enc.wait()) return -2;
+	// a stream whose tables move: the rounds behind round 0, as in batch_finish
+	if (b->stream.moving) { const int rc = stream_rounds(GroupUnits(b)); if (rc) return rc; }
 	// -3 (a sample beyond its buffer: size 0) and -8 (a peak table the device stage cannot write) as for intra batches; -9: a group sample so large that the reference
 	// would have coded bands of the frame wavelets as zeros (encoder.c:8332, gop_sample_may_zero_bands) -- what the device stage wrote is not that sample.  All behind
 	// the loop: the other samples are complete and keep their sizes.
@@ -343,6 +424,7 @@ long long gop_finish(cfhd_amd_batch *b)
 	}
 	const double t4 = now();
 	b->t_fwd = b->t_launched - b->t_launch0; b->t_entropy_enc = t_enc - b->t_launched; b->t_entropy_dec = 0; b->t_inv = t4 - t_enc;
+	if (b->stream.on) stream_end_pass(GroupUnits(b));
 	b->steps++;
 	long long total = 0;
 	for (int g = 0; g < ng; g++) total += (long long)b->sample_size[2 * g];
@@ -353,11 +435,12 @@ void gop_drain(cfhd_amd_batch *b) { (void)b->genc->wait(); if (b->decode) (void)
 // A batch of two-frame groups (cfhd_amd_batch_create_ex with CFHD_ENCODING_FLAGS_YUV_2FRAME_GOP, cfhd_amd_batch_create_groups), or null: never a batch that does
 // something else.  coded_lowpass: groups whose w[3] lowpass band is divided and coded in two passes (the 8-bit RGB inputs) are taken too -- cfhd_amd_batch_create_groups;
 // cfhd_amd_batch_create_ex keeps refusing them, as the callers that probe with it expect.
-cfhd_amd_batch *create_group_batch(const FrontEndParams &fp, int width, int height, int nframes, int nthreads, int mode, bool coded_lowpass)
+// stream: cfhd_amd_batch_create_group_stream's batch -- one encoder's stream, tables that move included (then every group carries tables of its own: stream_rounds).
+cfhd_amd_batch *create_group_batch(const FrontEndParams &fp, int width, int height, int nframes, int nthreads, int mode, bool coded_lowpass, bool stream)
 {
 	const int kind = fp.pixel_kind;
-	// whole groups; tables that never move (the group twin of the intra rule below); round trips to the input's own format where a group decodes to it
-	if (nframes < 2 || (nframes & 1) || !fp.gop_static_quantizer || (gop_temporal_lowpass_is_coded(fp.gplan) && !coded_lowpass)) return nullptr;
+	// whole groups; tables that never move unless the batch is a stream (the group twin of the intra rule below); round trips to the input's own format where a group decodes to it
+	if (nframes < 2 || (nframes & 1) || (!fp.gop_static_quantizer && !stream) || (gop_temporal_lowpass_is_coded(fp.gplan) && !coded_lowpass)) return nullptr;
 	if (mode != 0 && mode != 1) return nullptr;
 	if (mode == 0 && !fp.gop_output_served) return nullptr;
 	const char *e = getenv("CFHD_AMD_ENTROPY");
@@ -368,7 +451,9 @@ cfhd_amd_batch *create_group_batch(const FrontEndParams &fp, int width, int heig
 	b->color_format = fp.color_format; b->color_space = fp.color_space; b->progressive = fp.progressive;
 	b->decode = mode == 0; b->plan = fp.plan; b->gop = true; b->gplan = fp.gplan;
 	const int ng = nframes / 2;
-	const size_t cap = (size_t)width * height * fp.pixel_bytes + 65536;      // SampleEncoder.cpp:387 (a group beyond 80 % of it fails its pass: -9)
+	// SampleEncoder.cpp:387 (a group beyond 80 % of it fails its pass: -9).  A stream is one handle's, and the handle keeps two frames' worth for a group
+	// (cfhd_api_encoder.inc prepare_group_encoder): the groups the handle can write fit here too -- the bit-rate limiter only trips on groups near one frame's worth
+	const size_t cap = ((size_t)width * height * fp.pixel_bytes + 65536) * (stream ? 2 : 1);
 	b->sequence_header_size = write_sequence_header(b->gplan, fp.gop_sequence_format, b->sequence_header, sizeof(b->sequence_header));
 	b->pframes.assign((size_t)kPFrameSampleBytes * ng, 0);
 	b->samples.resize(nframes); b->sample_size.assign(nframes, 0);
@@ -398,6 +483,12 @@ cfhd_amd_batch *create_group_batch(const FrontEndParams &fp, int width, int heig
 	if (!ok || b->sequence_header_size != kSequenceHeaderBytes) { delete b; return nullptr; }
 	b->genc->set_timed(true);
 	if (b->decode) b->gdec->set_timed(true);
+	if (stream) {
+		cfhd_amd_batch::Stream &s = b->stream;
+		s.on = true; s.moving = !fp.gop_static_quantizer; s.derive_quality = fp.derive_quality;
+		s.carried = fp.gqstate; s.groups.carried_plan = fp.gplan; s.carried_bytes = 0; s.next = fp.gqstate;
+		if (s.moving) { s.groups.coded.assign((size_t)ng, fp.gplan); s.before.assign((size_t)ng, fp.gqstate); }
+	}
 	return b;
 }
 }
@@ -417,7 +508,7 @@ cfhd_amd_batch *cfhd_amd_batch_create_ex(int width, int height, uint32_t pixel_f
 	// (FILMSCAN2/3, LOW..HIGH up to 1080p: encoder.c:3414 -> quantize.c:2869) need frame i's sample before frame i + 1 can start -- those
 	// sequences go through CFHD_EncodeSample, which applies the feedback per frame, or through cfhd_amd_batch_create_stream, which codes a pass on a guess of
 	// every frame's tables and codes the frames behind a wrong guess again; here they are refused instead of encoded differently (callers probe with this entry).
-	if (fp.gop) return create_group_batch(fp, width, height, nframes, nthreads, mode, false);
+	if (fp.gop) return create_group_batch(fp, width, height, nframes, nthreads, mode, false, false);
 	if (!fp.static_quantizer) return nullptr;
 	return create_intra_batch(fp, width, height, nframes, nthreads, mode, false);
 }
@@ -431,7 +522,7 @@ cfhd_amd_batch *cfhd_amd_batch_create_stream(int width, int height, uint32_t pix
 	auto refuse = [](const char *text) { device_set_last_error(text); return (cfhd_amd_batch *)nullptr; };
 	if (nframes < 1) return refuse("cfhd_amd_batch_create_stream: a batch has at least one frame");
 	if (mode != 0 && mode != 1) return refuse("cfhd_amd_batch_create_stream: mode is 0 (round trip) or 1 (encode only)");
-	if (encoding_flags & (1u << 1)) return refuse("cfhd_amd_batch_create_stream: two-frame groups go through cfhd_amd_batch_create_groups (their tables must stand still)");
+	if (encoding_flags & (1u << 1)) return refuse("cfhd_amd_batch_create_stream: two-frame groups go through cfhd_amd_batch_create_groups (tables that stand still) or cfhd_amd_batch_create_group_stream (any tables)");
 	if (front_end_params(width, height, pixel_format, encoded_format, encoding_flags, quality, &fp)) return refuse("cfhd_amd_batch_create_stream: arguments CFHD_PrepareToEncode refuses");
 	const char *e = getenv("CFHD_AMD_ENTROPY");
 	if (e && strcmp(e, "host") == 0) return refuse("cfhd_amd_batch_create_stream: CFHD_AMD_ENTROPY=host keeps the entropy stage on the host; a stream is coded on the device");
@@ -498,7 +589,7 @@ cfhd_amd_batch *create_intra_batch(const FrontEndParams &fp, int width, int heig
 	if (stream) {
 		cfhd_amd_batch::Stream &s = b->stream;
 		s.on = true; s.moving = !fp.static_quantizer; s.derive_quality = fp.derive_quality;
-		s.carried = fp.qstate; s.carried_plan = fp.plan; s.carried_bytes = 0; s.next = fp.qstate;
+		s.carried = fp.qstate; s.frames.carried_plan = fp.plan; s.carried_bytes = 0; s.next = fp.qstate;
 		if (s.moving) {
 			// the rounds sit between the two halves of the default pass: nothing else has them
 			if (!(b->gpu_entropy && b->device_handoff && b->chunks.size() == 1)) {
@@ -506,7 +597,7 @@ cfhd_amd_batch *create_intra_batch(const FrontEndParams &fp, int width, int heig
 				device_set_last_error("cfhd_amd_batch_create_stream: tables that follow the sample sizes need the default arrangement (no CFHD_AMD_HANDOFF=host, no CFHD_AMD_CHUNK)");
 				return nullptr;
 			}
-			s.coded.assign((size_t)nframes, fp.plan); s.before.assign((size_t)nframes, fp.qstate);
+			s.frames.coded.assign((size_t)nframes, fp.plan); s.before.assign((size_t)nframes, fp.qstate);
 		}
 	}
 	return b;
@@ -522,7 +613,31 @@ cfhd_amd_batch *cfhd_amd_batch_create_groups(int width, int height, uint32_t pix
 	CallerDevice caller_device;
 	FrontEndParams fp;
 	if (nframes < 1 || front_end_params(width, height, pixel_format, 0, encoding_flags | (1u << 1) /* CFHD_ENCODING_FLAGS_YUV_2FRAME_GOP */, quality, &fp) || !fp.gop) return nullptr;
-	return create_group_batch(fp, width, height, nframes, nthreads, mode, true);
+	return create_group_batch(fp, width, height, nframes, nthreads, mode, true, false);
+}
+
+// One group encoder's stream on the frame queue (include/cfhd_amd.h): every quality word CFHD_PrepareToEncode takes for groups.  A word whose group tables never move
+// makes exactly cfhd_amd_batch_create_groups' batch; one whose tables follow the key samples makes the same batch with tables per group and the rounds of
+// stream_rounds behind round 0.
+cfhd_amd_batch *cfhd_amd_batch_create_group_stream(int width, int height, uint32_t pixel_format, uint32_t encoding_flags, int quality, int nframes, int nthreads, int mode)
+{
+	CallerDevice caller_device;
+	FrontEndParams fp;
+	auto refuse = [](const char *text) { device_set_last_error(text); return (cfhd_amd_batch *)nullptr; };
+	if (nframes < 2 || (nframes & 1)) return refuse("cfhd_amd_batch_create_group_stream: a batch holds whole two-frame groups, at least one");
+	if (mode != 0 && mode != 1) return refuse("cfhd_amd_batch_create_group_stream: mode is 0 (round trip) or 1 (encode only)");
+	if (front_end_params(width, height, pixel_format, 0, encoding_flags | (1u << 1) /* CFHD_ENCODING_FLAGS_YUV_2FRAME_GOP */, quality, &fp) || !fp.gop)
+		return refuse("cfhd_amd_batch_create_group_stream: arguments CFHD_PrepareToEncode refuses for two-frame groups");
+	const char *e = getenv("CFHD_AMD_ENTROPY");
+	if (e && strcmp(e, "host") == 0) return refuse("cfhd_amd_batch_create_group_stream: CFHD_AMD_ENTROPY=host keeps the entropy stage on the host; a stream is coded on the device");
+	const char *ho = getenv("CFHD_AMD_HANDOFF");
+	if (!fp.gop_static_quantizer && ho && strcmp(ho, "host") == 0)
+		return refuse("cfhd_amd_batch_create_group_stream: tables that follow the sample sizes need the default arrangement (no CFHD_AMD_HANDOFF=host)");
+	if (mode == 0 && !fp.gop_output_served) return refuse("cfhd_amd_batch_create_group_stream: a group does not decode to this input's format; mode 1 encodes only");
+	device_set_last_error("");
+	cfhd_amd_batch *b = create_group_batch(fp, width, height, nframes, nthreads, mode, true, true);
+	if (!b && !*device_last_error()) device_set_last_error("cfhd_amd_batch_create_group_stream: cfhd_amd_batch_create_groups refuses this input, mode or arrangement");
+	return b;
 }
 
 cfhd_amd_batch *cfhd_amd_batch_create(int width, int height, uint32_t pixel_format, int quality, int nframes, int nthreads)
@@ -691,7 +806,7 @@ static long long cfhd_amd_batch_roundtrip_locked(cfhd_amd_batch *b)
 	}
 	double t4 = now();
 	b->t_fwd = t1 - t0; b->t_entropy_enc = t2 - t1; b->t_entropy_dec = t3 - t2; b->t_inv = t4 - t3;
-	if (b->stream.on) stream_end_pass(b);               // (a stream whose tables stand still, in one of the other arrangements)
+	if (b->stream.on) stream_end_pass(FrameUnits(b));   // (a stream whose tables stand still, in one of the other arrangements)
 	b->steps++;
 	long long total = 0;
 	for (int i = 0; i < b->n; i++) total += (long long)b->sample_size[i];
@@ -814,7 +929,7 @@ float cfhd_amd_batch_kernel_ms(cfhd_amd_batch *b, int which)
 	return ms;
 }
 
-// The last completed pass of a stream: rounds, frames coded over all rounds, frames whose tables differ from those of the frame in front.
+// The last completed pass of a stream: rounds, frames coded over all rounds, frames -- a group stream: groups -- whose tables differ from those of the one in front.
 int cfhd_amd_batch_stream_stats(cfhd_amd_batch *b, int out[3])
 {
 	if (!b || !out || !b->stream.on || b->in_flight || !b->stream.stats_valid) return -1;

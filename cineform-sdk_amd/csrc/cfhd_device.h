@@ -198,10 +198,18 @@ public:
 	int ngroups() const { return n_; }
 	void set_color_matrix(int m);                    // decoder: the matrix of the outputs that convert to RGB (FramePlan::color_matrix), from the group sample's colour space tag
 	void set_plan(const GopPlan &plan);              // same geometry, new quantizer tables
+	// Group g's divisors alone (the frame queue's group streams: every group carries tables of its own, EncodeBatch::set_frame_quant's twin): its rows of the job tables
+	// are rewritten and travel to the device with the next launch, the rows of the other groups neither.  The sample header is the caller's
+	// (GpuEntropyEncoder::set_group_plan + set_frame_header); the pinned job table must not be in flight.
+	int set_group_plan(int g, const GopPlan &plan);
+	const GopPlan &group_plan(int g) const { return group_plans_.empty() ? plan_ : group_plans_[(size_t)g]; }
 	// encoder
 	int upload_frame(int f, const void *frame, int pitch_bytes);      // f = 0 .. 2 n - 1: stage one frame and start its H2D copy
 	int upload_frames(const void *frames, size_t frame_stride, int pitch_bytes);      // all 2 n frames, asynchronous on the batch's stream (staged through pinned memory unless registered and back to back)
-	int launch_forward();                            // async: level 1 of all frames, temporal step, three spatial transforms per channel
+	int launch_forward() { return launch_forward(0, n_); }      // async: level 1 of all frames, temporal step, three spatial transforms per channel
+	// the same over groups first_group .. first_group + count - 1: the job tables are group-major, so a window is every table from its first group's rows on and grids
+	// sized by count; (0, n) is launch_forward()
+	int launch_forward(int first_group, int count);
 	const char *level1_kernel() const;               // name of the kernel the next launch_forward() runs for level 1 of both frames (as a profiler shows it)
 	int download_coeffs();                           // async: the group pyramid -> pinned host
 	// GPU entropy stage for the group sample (GpuEntropyEncoder::prepare_group): entropy().set_frame_header(0, hdr), launch_forward(), entropy().launch(),
@@ -242,6 +250,10 @@ public:
 	void release();
 private:
 	void fill_jobs();
+	void fill_group_jobs(int g);                     // group g's rows of the job tables, from group_plan(g)
+	int sync_jobs();                                 // the whole table, or the rows of the groups set_group_plan() rewrote
+	std::vector<GopPlan> group_plans_;               // empty: every group carries plan_'s divisors; else group g its own (set_group_plan)
+	std::vector<char> group_dirty_;                  // encoder: groups whose rows differ from the device's copy
 	GopRoute route() const;                          // decoder: output_route() of a 4:2:2 sample for the output kind, half and interlaced, and the kernel that serves its family
 	FwdL1 forward_route() const;                     // encoder: the level-1 kernel of both frames, from the input kind and interlaced alone
 	GopPlan plan_; bool decode_ = false, half_ = false; int out_kind_ = 0, device_ = 0, matrix_ = 0, n_ = 1, active_ = 0;

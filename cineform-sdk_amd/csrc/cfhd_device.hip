@@ -1473,6 +1473,7 @@ int GopBatch::prepare(const GopPlan &plan, bool decode, int out_pixel_kind, bool
 	if (ngroups < 1 || 6 * (long long)ngroups > kMaxGridYZ) { g_err = "two-frame groups: the batch's job index would pass the grid limit"; return -2; }
 	device_ = device_current(); (void)hipSetDevice(device_);
 	plan_ = plan; decode_ = decode; out_kind_ = out_pixel_kind; half_ = decode && half; n_ = ngroups;
+	group_plans_.clear(); group_dirty_.clear();
 	const size_t nf = 2 * (size_t)n_;
 	const GopRoute r = route();
 	if (decode && r.l1 == InvL1::Refused) { g_err = "two-frame groups: output not served"; return -2; }
@@ -1513,7 +1514,7 @@ void GopBatch::set_color_matrix(int m)
 void GopBatch::set_plan(const GopPlan &plan)
 {
 	if (stream_) (void)hipStreamSynchronize((hipStream_t)stream_);
-	plan_ = plan;
+	plan_ = plan; group_plans_.clear();
 	if (ent_ready_) ent_.set_group_plan(plan);
 	fill_jobs();
 }
@@ -1585,13 +1586,17 @@ int GopBatch::launch_entropy_decode(const uint8_t *sample, size_t size, const Pa
 
 void GopBatch::fill_jobs()
 {
-	const GopPlan &plan = plan_;
-	const GopJobs all = gop_jobs_at(h_jobs_, n_);
+	for (int g = 0; g < n_; g++) fill_group_jobs(g);
+	jobs_dirty_ = true;
+}
+
+// group g: its rows of the table, its pyramid, its two frames, its divisors
+void GopBatch::fill_group_jobs(int g)
+{
+	const GopPlan &plan = group_plan(g);
 	const int mpq = plan.midpoint_prequant;
 	const OutputRoute o = decode_ ? route().out : OutputRoute();
-	for (int g = 0; g < n_; g++) {
-	// group g: its rows of the table, its pyramid, its two frames
-	GopJobs j = all;
+	GopJobs j = gop_jobs_at(h_jobs_, n_);
 	j.yuv += 2 * g; j.temp += 3 * g; j.mid += 6 * g; j.top += 3 * g; j.itop += 3 * g; j.imid += 6 * g; j.iyuv += 2 * g; j.l1 += 6 * g; j.half += 2 * g; j.fl1 += 6 * g; j.tq += 3 * g;
 	int16_t *base = d_coeff_ + (size_t)g * plan.coeff_elems;
 	for (int f = 0; f < 2; f++) {
@@ -1649,8 +1654,43 @@ void GopBatch::fill_jobs()
 		inv(j.imid[2 * c], ch.w[4], base + ch.w[2].offset[0], ch.w[2].pitch);
 		inv(j.imid[2 * c + 1], ch.w[3], base + ch.w[2].offset[1], ch.w[2].pitch);
 	}
+}
+
+int GopBatch::set_group_plan(int g, const GopPlan &plan)
+{
+	if (g < 0 || g >= n_ || decode_ || !h_jobs_ || plan.coeff_elems != plan_.coeff_elems || plan.interlaced != plan_.interlaced || plan.pixel_kind != plan_.pixel_kind) return -1;
+	if (group_plans_.empty()) group_plans_.assign((size_t)n_, plan_);
+	if (group_dirty_.empty()) group_dirty_.assign((size_t)n_, 0);
+	group_plans_[(size_t)g] = plan;
+	fill_group_jobs(g);
+	group_dirty_[(size_t)g] = 1;
+	return 0;
+}
+
+// The encoder's rows that carry divisors: level 1 of both frames (either job family), the temporal highpass wavelet with the division of its lowpass band, the two
+// wavelets above.  Runs of rewritten groups travel in one copy per table.
+int GopBatch::sync_jobs()
+{
+	hipStream_t st = (hipStream_t)stream_;
+	if (jobs_dirty_) {
+		HIPCHK(hipMemcpyAsync(d_jobs_, h_jobs_, jobs_bytes_, hipMemcpyHostToDevice, st));
+		jobs_dirty_ = false; group_dirty_.assign(group_dirty_.size(), 0);
+		return 0;
 	}
-	jobs_dirty_ = true;
+	const GopJobs h = gop_jobs_at(h_jobs_, n_), d = gop_jobs_at(d_jobs_, n_);
+	for (int g = 0; g < (int)group_dirty_.size();) {
+		if (!group_dirty_[(size_t)g]) { g++; continue; }
+		int e = g;
+		while (e < (int)group_dirty_.size() && group_dirty_[(size_t)e]) group_dirty_[(size_t)e++] = 0;
+		const size_t k = (size_t)(e - g);
+		HIPCHK(hipMemcpyAsync(d.yuv + 2 * g, h.yuv + 2 * g, 2 * k * sizeof(dev::FwdYuvJob), hipMemcpyHostToDevice, st));
+		HIPCHK(hipMemcpyAsync(d.fl1 + 6 * g, h.fl1 + 6 * g, 6 * k * sizeof(dev::FwdPlaneJob), hipMemcpyHostToDevice, st));
+		HIPCHK(hipMemcpyAsync(d.mid + 6 * g, h.mid + 6 * g, 6 * k * sizeof(dev::FwdPlaneJob), hipMemcpyHostToDevice, st));
+		HIPCHK(hipMemcpyAsync(d.top + 3 * g, h.top + 3 * g, 3 * k * sizeof(dev::FwdPlaneJob), hipMemcpyHostToDevice, st));
+		HIPCHK(hipMemcpyAsync(d.tq + 3 * g, h.tq + 3 * g, 3 * k * sizeof(dev::GopQuantJob), hipMemcpyHostToDevice, st));
+		g = e;
+	}
+	return 0;
 }
 
 int GopBatch::upload_frame(int f, const void *frame, int pitch)
@@ -1690,30 +1730,34 @@ int GopBatch::upload_frames(const void *frames, size_t frame_stride, int pitch)
 	return 0;
 }
 
-int GopBatch::launch_forward()
+int GopBatch::launch_forward(int first, int count)
 {
+	if (first < 0 || count < 1 || first + count > n_) return -1;
 	(void)hipSetDevice(device_);
 	hipStream_t st = (hipStream_t)stream_;
-	if (jobs_dirty_) { HIPCHK(hipMemcpyAsync(d_jobs_, h_jobs_, jobs_bytes_, hipMemcpyHostToDevice, st)); jobs_dirty_ = false; }
+	const int rcj = sync_jobs();
+	if (rcj) return rcj;
 	GopJobs j = gop_jobs_at(d_jobs_, n_);
+	// (a window: every table from its first group's rows on -- the jobs hold the addresses of their own frames and pyramids)
+	j.yuv += 2 * first; j.fl1 += 6 * first; j.temp += 3 * first; j.mid += 6 * first; j.top += 3 * first; j.tq += 3 * first;
 	(void)hipGetLastError();
 	if (timed_) HIPCHK(hipEventRecord((hipEvent_t)ev_[0], st));
-	// level 1 of all frames (grid z = 2 n) through the intra path's launcher: the spatial transform, or -- interlaced groups -- the frame transform of interlaced intra
+	// level 1 of all frames (grid z = 2 count) through the intra path's launcher: the spatial transform, or -- interlaced groups -- the frame transform of interlaced intra
 	// frames (the two kernels share the job table), or -- the 10-bit, 16-bit and RGB inputs -- the packed-16 loaders, the planes of a tile row side by side in gridDim.x
 	const int luma_tiles = (plan_.ch[0].width / 2 + dev::TW - 1) / dev::TW, chroma_tiles = (plan_.ch[1].width / 2 + dev::TW - 1) / dev::TW;
-	const int rc = launch_first_level(forward_route(), { plan_.width, plan_.height, 2 * n_, j.yuv, j.fl1, nullptr, 3, plan_.pixel_kind, luma_tiles, chroma_tiles }, st);
+	const int rc = launch_first_level(forward_route(), { plan_.width, plan_.height, 2 * count, j.yuv, j.fl1, nullptr, 3, plan_.pixel_kind, luma_tiles, chroma_tiles }, st);
 	if (rc) return rc;
 	if (timed_) HIPCHK(hipEventRecord((hipEvent_t)ev_[1], st));
 	const GopWavelet &t = plan_.ch[0].w[2];
-	dev::k_gop_temporal_fwd<<<dim3((unsigned)((t.pitch * t.height / 2 + dev::NTHREADS - 1) / dev::NTHREADS), 3 * n_), dev::NTHREADS, 0, st>>>(j.temp);
-	launch_fwd_plane_tiles(j.mid, t.width, t.height, 6 * n_, st);
+	dev::k_gop_temporal_fwd<<<dim3((unsigned)((t.pitch * t.height / 2 + dev::NTHREADS - 1) / dev::NTHREADS), 3 * count), dev::NTHREADS, 0, st>>>(j.temp);
+	launch_fwd_plane_tiles(j.mid, t.width, t.height, 6 * count, st);
 	if (!decode_ && gop_temporal_lowpass_is_coded(plan_)) {
 		const GopWavelet &w3 = plan_.ch[0].w[3];                         // (luma is the largest of the three bands)
-		dev::k_gop_quant_lowpass<<<dim3((unsigned)((w3.pitch * w3.height / 2 + dev::NTHREADS - 1) / dev::NTHREADS), 3 * n_), dev::NTHREADS, 0, st>>>(j.tq);
+		dev::k_gop_quant_lowpass<<<dim3((unsigned)((w3.pitch * w3.height / 2 + dev::NTHREADS - 1) / dev::NTHREADS), 3 * count), dev::NTHREADS, 0, st>>>(j.tq);
 	}
 	if (timed_) HIPCHK(hipEventRecord((hipEvent_t)ev_[2], st));
 	const GopWavelet &m = plan_.ch[0].w[4];
-	launch_fwd_plane_tiles(j.top, m.width, m.height, 3 * n_, st);
+	launch_fwd_plane_tiles(j.top, m.width, m.height, 3 * count, st);
 	HIPCHK(hipGetLastError());
 	if (timed_) { HIPCHK(hipEventRecord((hipEvent_t)ev_[3], st)); launched_ = true; }
 	return 0;

@@ -41,8 +41,8 @@ public:
 	int download();                                                  // sizes + offsets -> sync -> one async copy of all sample bytes (wait on the stream afterwards)
 	int download_queue() { return download_queue(0, active_frames()); }      // the two halves of download(): what can be queued behind launch() without the host ...
 	int download_finish() { return download_finish(0, active_frames()); }    // ... and what needs the sizes on the host (synchronises the stream, queues the copy of the sample bytes)
-	// The same over a window of the batch, frames first .. first + count - 1 (intra frames; the frame queue's rate-feedback streams code the frames behind a wrong guess
-	// of their tables again, cfhd_batch.cpp): the grids are sized by count, the segment states, token bases and block lists are those of the frames' own numbers.  In the
+	// The same over a window of the batch, units first .. first + count - 1 (intra frames or groups; the frame queue's rate-feedback streams code the units behind a wrong
+	// guess of their tables again, cfhd_batch.cpp; a group's own tables: set_group_plan + set_frame_header): the grids are sized by count, the segment states, token bases and block lists are those of the frames' own numbers.  In the
 	// dense buffer the samples in front of `first` keep their bytes and offsets -- the sizes of all first + count frames are summed again, the prefix's are final --, the
 	// window's samples are written at their new offsets, and the copy to the host covers [offsets[first], offsets[first + count]).  (0, n) is launch() / download_*().
 	int launch(int first, int count);

@@ -155,7 +155,7 @@ int GpuEntropyEncoder::set_frame_header(int f, const SampleHeaderInfo &hdr)
 
 int GpuEntropyEncoder::launch(int first, int count)
 {
-	if (first < 0 || count < 1 || first + count > n_ || (first && group_)) return -1;      // (windows: intra frames)
+	if (first < 0 || count < 1 || first + count > n_) return -1;
 	(void)hipSetDevice(device_);
 	hipStream_t st = (hipStream_t)stream_;
 	if (dirty_) {
@@ -199,7 +199,8 @@ int GpuEntropyEncoder::launch(int first, int count)
 	const std::vector<std::pair<int, int>> &scratch_ranges = host_->jobs.ranges_scratch;
 	const dev::EntBatchGeom geom_scratch = { geom.segs_per_frame, geom.bands_per_frame, scratch_stride_, geom.tok_per_frame };
 	dev::EntSplitJob sj;
-	if (!scratch_ranges.empty() && !ent_split_job(gplan_, d_coeffs_, coeff_stride_, d_scratch_, &sj)) return -3;
+	// (a window: the kernel numbers the groups from blockIdx.y = 0, so its job starts at the window's first pyramid and the window's first planes)
+	if (!scratch_ranges.empty() && !ent_split_job(gplan_, d_coeffs_ + (size_t)first * coeff_stride_, coeff_stride_, d_scratch_ + (size_t)first * scratch_stride_, &sj)) return -3;
 	auto count_scratch = [&] {      // (on the main stream, inside the span kernel_ms(0) times)
 		if (scratch_ranges.empty()) return;
 		uint32_t longest = 0;

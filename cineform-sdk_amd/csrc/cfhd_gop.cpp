@@ -96,6 +96,35 @@ bool derive_gop_quantization(GopPlan *plan, int quality, QuantState *st, float f
 	return true;
 }
 
+bool gop_same_tables(const GopPlan &a, const GopPlan &b)
+{
+	if (a.midpoint_prequant != b.midpoint_prequant) return false;
+	for (int c = 0; c < 3; c++)
+		for (int k = 0; k < kGopWavelets; k++) if (memcmp(a.ch[c].w[k].quant, b.ch[c].w[k].quant, sizeof(a.ch[c].w[k].quant)) != 0) return false;
+	return true;
+}
+
+// Rate feedback (encoder.c:2880-2905): every call re-derives the subband tables from the size of the last key sample (the FILMSCAN2/3 limiter moves), the call that
+// opens a group also runs the bit-rate limiter and deals the divisors to the group's wavelets -- both frames of the group are quantized with them
+bool gop_quant_call(GopPlan *plan, int quality, QuantState *st, bool opens, bool *changed)
+{
+	if (changed) *changed = false;
+	if (!opens) return derive_gop_quantization(plan, quality, st, 0.0f, false);
+	GopPlan next = *plan;
+	if (!derive_gop_quantization(&next, quality, st, 0.0f, true)) return false;
+	if (gop_same_tables(next, *plan)) return true;
+	*plan = next;
+	if (changed) *changed = true;
+	return true;
+}
+
+bool gop_quant_group(GopPlan *plan, int quality, QuantState *st, bool stream_begins, size_t sequence_header_bytes)
+{
+	if (!gop_quant_call(plan, quality, st, true)) return false;
+	if (stream_begins) gop_quant_key_sample(st, sequence_header_bytes);
+	return gop_quant_call(plan, quality, st, false);
+}
+
 // ------------------------------------------------------------------------------------------
 // The two-pass coding of a divided w[3] lowpass band (cfhd_gop.h)
 // ------------------------------------------------------------------------------------------

@@ -60,6 +60,15 @@ bool build_gop_plan(GopPlan *plan, int width, int height, int pixel_kind, bool i
 // the last key sample -- the 40-byte sequence header counts as one (encoder.c:3414) -- in `st`: deal = true for the opening call (the tables are written into the
 // plan), false for the call that completes the group (only the FILMSCAN2/3 limiter in `st` moves).
 bool derive_gop_quantization(GopPlan *plan, int quality, QuantState *st, float framerate = 0.0f, bool deal = true);
+// The walk of one encoder's stream over those two steps -- CFHD_EncodeSample's group branch and the frame queue's group streams (cfhd_batch.cpp) both call these and
+// nothing else.  gop_quant_call: one call's step; opens: the call opens a group, the tables the step deals replace the plan's where they differ (*changed says so),
+// else only the state moves.  gop_quant_key_sample: a key sample -- the sequence header, a group -- of `bytes` bytes was written.  gop_quant_group: the two calls of
+// one group with the state as the key sample in front left it; stream_begins: the group is its stream's first, whose opening call answers with the sequence header
+// (a key sample itself: the closing call already counts its bytes).
+bool gop_same_tables(const GopPlan &a, const GopPlan &b);      // (tables, not states: two states can give the same divisors)
+bool gop_quant_call(GopPlan *plan, int quality, QuantState *st, bool opens, bool *changed = nullptr);
+inline void gop_quant_key_sample(QuantState *st, size_t bytes) { st->lastgopbitcount = (int64_t)bytes * 8; }
+bool gop_quant_group(GopPlan *plan, int quality, QuantState *st, bool stream_begins, size_t sequence_header_bytes);
 
 // The group sample (codec.c:835 PutVideoGroupHeader + encoder.c:7461 EncodeQuantizedGroup + :8078 EncodeQuantizedFieldPlusTransform) from the
 // group's coefficient pyramid; 0 on overflow.

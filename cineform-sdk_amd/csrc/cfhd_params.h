@@ -19,7 +19,7 @@ struct FrontEndParams {
 	// whether the input's own pixel format is an output a group of this scan and width decodes to at full resolution; the input format of the sequence header
 	bool gop = false, gop_static_quantizer = true, gop_output_served = false;
 	int gop_sequence_format = 0;
-	GopPlan gplan;
+	GopPlan gplan; QuantState gqstate = {0, -1, 0};           // (the group encoder's state behind CFHD_PrepareToEncode: what a group stream's walk starts from)
 };
 // Same checks and derivations as CFHD_PrepareToEncode (cfhd_api.cpp make_params).  Returns a CFHD_Error value (0 = OK).
 int front_end_params(int width, int height, uint32_t pixel_format, int encoded_format, uint32_t encoding_flags, int quality, FrontEndParams *out);

@@ -205,13 +205,34 @@ cfhd_amd_batch *cfhd_amd_batch_create_groups(int width, int height, uint32_t pix
  * frame): feedback only flows forward, so the samples of the real frames do not depend on the padding; drop the padding's samples.  Independent streams -- several
  * batches -- overlap in flight like any batches; the passes of one stream depend on each other and run one at a time.
  * NULL, with the reason in cfhd_amd_last_error(): whatever cfhd_amd_batch_create_ex refuses for reasons other than moving tables; nframes < 1;
- * CFHD_ENCODING_FLAGS_YUV_2FRAME_GOP (groups: cfhd_amd_batch_create_groups, tables that stand still only); CFHD_AMD_ENTROPY=host; for words whose tables move, the
+ * CFHD_ENCODING_FLAGS_YUV_2FRAME_GOP (groups: cfhd_amd_batch_create_groups, or cfhd_amd_batch_create_group_stream below for any tables); CFHD_AMD_ENTROPY=host; for words whose tables move, the
  * arrangements with host work inside a pass (CFHD_AMD_HANDOFF=host, CFHD_AMD_CHUNK). */
 cfhd_amd_batch *cfhd_amd_batch_create_stream(int width, int height, uint32_t pixel_format, int encoded_format, uint32_t encoding_flags,
                                              int quality, int nframes, int nthreads, int mode);
-/* The last completed pass of a stream batch: out[0] encode rounds (>= 1), out[1] frames coded over all rounds (>= nframes), out[2] frames whose tables differ from
- * those of the frame in front (frame 0: from the last frame of the pass before; in pass 0 it counts 0).  0, or -1 for a batch not made by
- * cfhd_amd_batch_create_stream, before its first pass has completed, and between submit and wait. */
+/* The group twin of cfhd_amd_batch_create_stream: one group encoder's stream on the frame queue, rate feedback included.  The arguments and the inputs served are
+ * cfhd_amd_batch_create_groups' (the group flag implied, encoded format 4:2:2: every 4:2:2 input of the group encoder, RG24 / BGRA / BGRa with subband 7 coded in two
+ * passes, interlaced groups from YUY2 / 2vuy; mode 1, and mode 0 where cfhd_amd_batch_create_groups serves it), and EVERY quality word CFHD_PrepareToEncode takes for
+ * groups is taken -- also the words whose group tables follow the size of the key sample in front (cfhd_amd_quantizer_is_static with the group flag answers 0: LOW ..
+ * HIGH up to 1920 x 1080, FILMSCAN2 / FILMSCAN3 everywhere), which cfhd_amd_batch_create_ex and cfhd_amd_batch_create_groups keep refusing.
+ * A batch made here is ONE encoder's stream: with cfhd_amd_batch_get_sequence_header in front, the samples of consecutive passes -- get_sample(2g) group g,
+ * get_sample(2g + 1) the 24-byte P-frame sample behind it -- are the stream of one CFHD_EncodeSample handle prepared with the same arguments and fed the same frames,
+ * byte for byte: quantizer tables, headers, frame numbers, metadata.  The handle deals a group's tables on the call that opens it, from the size of the key sample in
+ * front (the sequence header for the first group, the group sample in front afterwards), and quantizes both frames with them; the batch walks the same steps
+ * (cfhd_gop.h gop_quant_group, the handle's own code).  The quantizer state is carried from the last group of a pass to the first of the next.  For a word whose group
+ * tables stand still this is exactly cfhd_amd_batch_create_groups' batch, same samples, same launches.  For the others a pass is coded on a guess of every group's
+ * tables (the first pass: the first group's; afterwards: the tables the pass before ended with, group by group) and checked against the sizes that come back in
+ * cfhd_amd_batch_wait; the groups from the first wrong guess on are coded again as a window of the batch, as often as it takes -- nframes / 2 rounds at the most, one
+ * where the tables stand still.  Every other cfhd_amd_batch_* entry point is shared and keeps its meaning per frame index (upload, roundtrip, submit, submit_host,
+ * wait, get_sample, download_output, kernel_ms / kernel_name -- of the last round); in mode 0 the pictures are those of the final samples.
+ * A pass that fails (-3: a sample that does not fit its buffer, -8: a peak table the device stage cannot write, -9: a group at the size where the reference codes
+ * bands as zeros) commits nothing: the carried state is the one the pass began with; its samples are not the handle's, and the stream is not to be continued
+ * behind it.  A tail shorter than nframes is padded by the caller, as for cfhd_amd_batch_create_stream.
+ * NULL, with the reason in cfhd_amd_last_error(): whatever cfhd_amd_batch_create_groups refuses for reasons other than moving tables; an odd nframes, or nframes < 2;
+ * CFHD_AMD_ENTROPY=host; for words whose tables move, CFHD_AMD_HANDOFF=host. */
+cfhd_amd_batch *cfhd_amd_batch_create_group_stream(int width, int height, uint32_t pixel_format, uint32_t encoding_flags, int quality, int nframes, int nthreads, int mode);
+/* The last completed pass of a stream batch: out[0] encode rounds (>= 1), out[1] frames coded over all rounds (>= nframes; a group stream: even), out[2] frames whose
+ * tables differ from those of the frame in front (frame 0: from the last frame of the pass before; in pass 0 it counts 0) -- a group stream: groups, likewise.  0, or
+ * -1 for a batch not made by cfhd_amd_batch_create_stream / cfhd_amd_batch_create_group_stream, before its first pass has completed, and between submit and wait. */
 int  cfhd_amd_batch_stream_stats(cfhd_amd_batch *batch, int out[3]);
 float cfhd_amd_batch_kernel_ms(cfhd_amd_batch *batch, int which);                              /* HIP-event time of the kernels of the last pass */
 const char *cfhd_amd_batch_kernel_name(cfhd_amd_batch *batch, int which);                      /* which 0..5: the transform kernel behind that time */
