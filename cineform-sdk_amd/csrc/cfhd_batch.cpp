@@ -659,6 +659,16 @@ int cfhd_amd_batch_upload(cfhd_amd_batch *b, int i, const void *frame, int pitch
 	return c.enc.wait();
 }
 
+// Frame i from HBM on the batch's device: queued on the stream the pass runs on, no host wait (the source is borrowed until the next wait / roundtrip returns).
+int cfhd_amd_batch_upload_device(cfhd_amd_batch *b, int i, const void *d_frame, int pitch)
+{
+	CallerDevice caller_device;
+	if (!b || b->in_flight || i < 0 || i >= b->n || !d_frame) return -1;
+	if (b->gop) return b->genc->upload_frame_device(i, d_frame, pitch);
+	int l; cfhd_amd_chunk &c = b->chunk_of(i, &l);
+	return c.enc.upload_frame_device(l, d_frame, pitch);
+}
+
 // One step of the hot path over the whole batch.  Returns the total number of sample bytes, or < 0.
 static long long cfhd_amd_batch_roundtrip_locked(cfhd_amd_batch *b);
 // (A batch with a pass in flight -- cfhd_amd_batch_submit without its _wait -- refuses every entry point that would touch its streams, job tables or pinned buffers: -1.)

@@ -5,7 +5,8 @@
 // A pass on the batch's one stream:
 //   (samples H2D: one DMA of a registered blob as it lies, or of the pinned buffer the calling thread packed plain memory into)  ->  k_dec_ingest: every sample into the
 //   decoder's own 256-byte aligned slot, the size table  ->  k_dec_parse with a verdict per sample  ->  the band decoder, k_dec_lowpass  ->  the three transform levels
-//   and the output conversion (DecodeBatch)  ->  k_dec_blank: the pictures of the samples that failed, zeroed  ->  (pictures D2H).
+//   and the output conversion (DecodeBatch)  ->  k_dec_blank: the pictures of the samples that failed, zeroed  ->  (k_dec_deliver: the pictures into the
+//   device memory cfhd_amd_decode_batch_set_device_pictures named, packed or as planes)  ->  (pictures D2H).
 // The gates are the handle's: create prepares a CFHD_DecodeSample handle on the first sample and decodes that sample once; what the handle refuses, create refuses with
 // the same text.  That handle stays with the batch as the slow path: the samples k_dec_ingest could not place (longer than a slot, a size that is no multiple of 4),
 // those whose scan or colour-space tag differs from the first sample's, and -- when the band decoders' one error word is set after the pass -- every sample the parser
@@ -23,6 +24,7 @@
 #include "cfhd_device.h"
 #include "cfhd_params.h"
 #include "cfhd_ingest_kernels.h"
+#include "cfhd_deliver_kernels.h"
 #include <hip/hip_runtime.h>
 #include <string.h>
 #include <stdio.h>
@@ -63,8 +65,10 @@ struct cfhd_amd_decode_batch {
 	uint8_t *d_blob = nullptr, *h_blob = nullptr; size_t blob_cap = 0;      // (h_blob: allocated by the first pass that stages plain memory)
 	uint8_t *d_table = nullptr, *h_table = nullptr; size_t table_bytes = 0;
 	uint32_t *d_sizes = nullptr, *d_verdicts = nullptr, *h_verdicts = nullptr;      // verdicts: [0, n) k_dec_parse's words, [n, 2 n) k_dec_ingest's marks
-	hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };                      // around k_dec_ingest, around k_dec_blank
-	float ingest_ms = 0, blank_ms = 0; bool timed = false;
+	hipEvent_t ev[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };    // around k_dec_ingest, around k_dec_blank, around k_dec_deliver
+	float ingest_ms = 0, blank_ms = 0, deliver_ms = 0; bool timed = false, deliver_timed = false;
+	// where every pass delivers its pictures on the device (cfhd_amd_decode_batch_set_device_pictures; null: nowhere): the caller's memory, borrowed from submit to wait
+	uint8_t *dev_out = nullptr; size_t dev_out_stride = 0; int dev_out_pitch = 0, dev_out_layout = 0;
 	// the pass in flight
 	bool in_flight = false; int count = 0; uint32_t steps = 0;
 	const uint8_t *src_host = nullptr, *src_device = nullptr;      // where sample i's bytes are for the slow path: src + offsets[i]
@@ -97,6 +101,7 @@ struct cfhd_amd_decode_batch {
 	uint8_t *device_pictures() const { return groups ? gdec.device_pictures() : dec.device_pictures(); }
 	int finish_frame(int i, void *out, int pitch) { return groups ? gdec.finish_frame(i, out, pitch) : dec.finish_frame(i, out, pitch); }
 	int download_frame(int i, void *out, int pitch) { return groups ? gdec.download_frame(i, out, pitch) : dec.download_frame(i, out, pitch); }
+	int picture_width() const { const int full = groups ? gst.plan.width : st.plan.width; return (groups ? gst.half : st.half) ? full / 2 : full; }
 	~cfhd_amd_decode_batch()
 	{
 		(void)hipSetDevice(device);
@@ -124,6 +129,26 @@ int allocate(cfhd_amd_decode_batch *b)
 	HIPCHK(hipMemset(b->d_sizes, 0, 4 * (size_t)b->n));
 	HIPCHK(hipMemset(b->d_verdicts, 0, 8 * (size_t)b->n));
 	for (hipEvent_t &e : b->ev) HIPCHK(hipEventCreate(&e));
+	return 0;
+}
+
+// k_dec_deliver over pictures [first, first + count) of the batch's own buffer, queued on the batch's stream: into the caller's device memory, in the layout it asked for.
+int launch_deliver(cfhd_amd_decode_batch *b, int first, int count)
+{
+	dev::k_dec_deliver<<<dim3(dev::dec_deliver_pieces(b->picture_rows()), (unsigned)count), dev::DEC_DELIVER_THREADS, 0, (hipStream_t)b->stream()>>>(
+		b->device_pictures() + b->picture_bytes() * (size_t)first, b->picture_bytes(), b->picture_pitch(), b->picture_rows(), b->picture_width(),
+		b->dev_out + b->dev_out_stride * (size_t)first, b->dev_out_stride, b->dev_out_pitch, b->dev_out_layout);
+	HIPCHK(hipGetLastError());
+	return 0;
+}
+// ... behind k_dec_blank in a pass, between two events of its own (cfhd_amd_decode_batch_kernel_ms index 9)
+int launch_pass_deliver(cfhd_amd_decode_batch *b)
+{
+	hipStream_t st = (hipStream_t)b->stream();
+	HIPCHK(hipEventRecord(b->ev[4], st));
+	if (launch_deliver(b, 0, b->count)) return -5;
+	HIPCHK(hipEventRecord(b->ev[5], st));
+	b->deliver_timed = true;
 	return 0;
 }
 
@@ -157,6 +182,7 @@ int launch_group_pass(cfhd_amd_decode_batch *b, const uint8_t *blob)
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipEventRecord(b->ev[3], st));
 	b->timed = true;
+	if (b->dev_out && launch_pass_deliver(b)) return -5;
 	HIPCHK(hipMemcpyAsync(b->h_verdicts, b->d_verdicts, 8 * (size_t)n, hipMemcpyDeviceToHost, st));
 	if (b->host_out && b->gdec.download_frames(b->host_out, b->host_out_stride, b->host_out_pitch)) return -5;
 	return 0;
@@ -186,6 +212,7 @@ int launch_pass(cfhd_amd_decode_batch *b, const uint8_t *blob)
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipEventRecord(b->ev[3], st));
 	b->timed = true;
+	if (b->dev_out && launch_pass_deliver(b)) return -5;
 	HIPCHK(hipMemcpyAsync(b->h_verdicts, b->d_verdicts, 8 * (size_t)b->n, hipMemcpyDeviceToHost, st));
 	if (b->host_out && b->dec.download_frames(b->host_out, b->host_out_stride, b->host_out_pitch)) return -5;
 	return 0;
@@ -345,6 +372,23 @@ int cfhd_amd_decode_batch_geometry(cfhd_amd_decode_batch *b, int *width, int *he
 	return 0;
 }
 
+int cfhd_amd_decode_batch_set_device_pictures(cfhd_amd_decode_batch *b, void *d_pictures, size_t picture_stride, int picture_pitch, int layout)
+{
+	if (!b) { refuse("decode queue: no batch"); return -1; }
+	if (b->in_flight) { refuse("decode queue: device pictures are set between passes, not while one is in flight"); return -1; }
+	if (!d_pictures) { b->dev_out = nullptr; return 0; }
+	if (layout < CFHD_AMD_PICTURES_PACKED || layout > CFHD_AMD_PICTURES_PLANAR_F32) { refuse("decode queue: unknown layout of the device pictures"); return -1; }
+	const bool planar = layout != CFHD_AMD_PICTURES_PACKED;
+	if (planar && b->st.out_kind != PIX_RG48) { refuse("decode queue: the planar layouts serve batches whose output is RG48"); return -1; }
+	if (((uintptr_t)d_pictures | picture_stride | (size_t)(unsigned)picture_pitch) & 15) { refuse("decode queue: the device pictures' pointer, stride and pitch are multiples of 16"); return -1; }
+	const int rows = b->picture_rows();
+	const long long row_bytes = planar ? (long long)b->picture_width() * (layout == CFHD_AMD_PICTURES_PLANAR_F32 ? 4 : 2) : b->picture_pitch();
+	if (picture_pitch < row_bytes) { refuse("decode queue: the device pictures' pitch is below the row bytes of the layout"); return -1; }
+	if (picture_stride < (size_t)picture_pitch * ((size_t)(planar ? 3 : 1) * rows - 1) + (size_t)row_bytes) { refuse("decode queue: the device pictures' stride is below what one picture occupies"); return -1; }
+	b->dev_out = (uint8_t *)d_pictures; b->dev_out_stride = picture_stride; b->dev_out_pitch = picture_pitch; b->dev_out_layout = layout;
+	return 0;
+}
+
 int cfhd_amd_decode_batch_submit_host(cfhd_amd_decode_batch *b, const void *base, const size_t *offsets, const size_t *sizes, int count, void *pictures, size_t picture_stride, int picture_pitch)
 {
 	CallerDevice caller_device;
@@ -411,6 +455,9 @@ int cfhd_amd_decode_batch_wait(cfhd_amd_decode_batch *b, CFHD_Error *status)
 		b->timed = false;
 		if (hipEventElapsedTime(&b->ingest_ms, b->ev[0], b->ev[1]) != hipSuccess) { (void)hipGetLastError(); b->ingest_ms = 0; }
 		if (hipEventElapsedTime(&b->blank_ms, b->ev[2], b->ev[3]) != hipSuccess) { (void)hipGetLastError(); b->blank_ms = 0; }
+		b->deliver_ms = 0;      // (a pass that delivers nothing on the device has no such time)
+		if (b->deliver_timed && hipEventElapsedTime(&b->deliver_ms, b->ev[4], b->ev[5]) != hipSuccess) { (void)hipGetLastError(); b->deliver_ms = 0; }
+		b->deliver_timed = false;
 	}
 	if (b->host_out) {                                     // (pictures staged through pinned memory -- a plain buffer -- leave it on a few threads side by side; nothing to do for a registered one)
 		std::atomic<int> bad(0);
@@ -425,6 +472,7 @@ int cfhd_amd_decode_batch_wait(cfhd_amd_decode_batch *b, CFHD_Error *status)
 	const int picture_pitch = b->picture_pitch(); const size_t picture_bytes = b->picture_bytes();
 	std::vector<uint8_t> bytes;
 	int decoded = 0, failure = 0;
+	std::vector<int> slow;                                 // the samples the handle decoded, for k_dec_deliver behind the loop
 	for (int i = count; i < n; i++) b->slow_pictures[i].clear();      // (a short pass: what an earlier pass left behind its count is that pass's picture in HBM again)
 	for (int i = 0; i < count; i++) {
 		uint32_t v = b->h_verdicts[i], mark = b->h_verdicts[n + i];
@@ -457,10 +505,25 @@ int cfhd_amd_decode_batch_wait(cfhd_amd_decode_batch *b, CFHD_Error *status)
 			if (b->host_out) for (int r = 0; r < b->picture_rows(); r++)
 				memcpy(b->host_out + b->host_out_stride * (size_t)i + (size_t)r * b->host_out_pitch, b->slow_pictures[i].data() + (size_t)r * picture_pitch, (size_t)picture_pitch);
 			(void)hipSetDevice(b->device);
+			// ... and what the caller's device memory holds agrees with it too: the handle's picture (zeros where it refused) takes the sample's place in the batch's own
+			// buffer, k_dec_deliver runs again below.  (A synchronous copy out of pageable memory on the null stream: the launch below, on the batch's stream, is ordered
+			// behind it only because hipMemcpy returns when the bytes are in HBM -- the batch's stream is idle here, wait_stream() above.)
+			if (b->dev_out) {
+				if (hipMemcpy(b->device_pictures() + picture_bytes * (size_t)i, b->slow_pictures[i].data(), picture_bytes, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); failure = -2; }
+				slow.push_back(i);
+			}
 		}
 		if (status) status[i] = rc;
 		decoded += rc == ERR_OKAY;
 	}
+	// one launch per run of neighbouring slow samples (a damaged code stream: one run, the whole pass), then one wait
+	for (size_t k = 0; k < slow.size() && !failure;) {
+		size_t e = k + 1;
+		while (e < slow.size() && slow[e] == slow[e - 1] + 1) e++;
+		if (launch_deliver(b, slow[k], (int)(e - k))) failure = -2;
+		k = e;
+	}
+	if (!slow.empty() && !failure && b->wait_stream()) failure = -2;
 	b->steps++;
 	end_pass(b);
 	return failure ? failure : decoded;
@@ -480,9 +543,11 @@ int cfhd_amd_decode_batch_download_output(cfhd_amd_decode_batch *b, int i, void 
 }
 
 // which: 0 k_dec_ingest, 1 k_dec_parse, 2 the band decoder (all its kernels), 3 k_dec_lowpass, 4 / 5 / 6 the transform levels in launch order (wavelet 3, wavelet 2, the
-// last level + output conversion), 7 k_dec_blank (ms of the last pass, HIP events on the batch's stream)
+// last level + output conversion), 7 k_dec_blank, 9 k_dec_deliver -- both kinds of batch; 0 when the last pass delivered nothing on the device -- (ms of the last pass,
+// HIP events on the batch's stream)
 float cfhd_amd_decode_batch_kernel_ms(cfhd_amd_decode_batch *b, int which)
 {
+	if (b && !b->in_flight && which == 9) return b->deliver_ms;
 	if (!b || b->in_flight || which < 0 || which > (b->groups ? 8 : 7)) return 0;
 	if (which == 0) return b->ingest_ms;
 	if (which == 7) return b->blank_ms;
@@ -495,6 +560,7 @@ float cfhd_amd_decode_batch_kernel_ms(cfhd_amd_decode_batch *b, int which)
 
 const char *cfhd_amd_decode_batch_kernel_name(cfhd_amd_decode_batch *b, int which)
 {
+	if (b && !b->in_flight && which == 9) return "k_dec_deliver";
 	if (!b || b->in_flight || which < 0 || which > 7) return "";
 	static const char *const fixed[4] = { "k_dec_ingest", "k_dec_parse", "k_dec_plan+k_dec_index+k_dec_chain+k_dec_tiles", "k_dec_lowpass" };
 	if (which < 4 && !(b->groups && which)) return fixed[which];

@@ -1,0 +1,129 @@
+// cfhd_deliver_kernels.h -- k_dec_deliver, the last kernel of a decode-queue pass that delivers into the caller's device memory (cfhd_amd_decode_batch_set_device_pictures,
+// cfhd_decode_queue.hip): behind k_dec_blank, the pictures of the pass out of the batch's own tightly packed buffer into memory the caller owns -- as the packed
+// pictures they are, at the caller's pitch, or, for RG48, as three planes R, G, B of u16, f16 or f32 elements (a torch tensor N x 3 x H x W).
+#pragma once
+#include <stdint.h>
+#include <stddef.h>
+#include <string.h>
+#include <cfhd_gfx950.h>
+
+namespace cfhd {
+namespace dev {
+
+// (the values of CFHD_AMD_PICTURES_* in include/cfhd_amd.h)
+enum { DELIVER_PACKED = 0, DELIVER_PLANAR_U16 = 1, DELIVER_PLANAR_F16 = 2, DELIVER_PLANAR_F32 = 3 };
+
+// The element rules of the planar layouts for the RG48 word w.  F32: (float)w * (1.0f / 65535.0f), one IEEE single multiply.  F16: that value rounded to nearest-even
+// to binary16, subnormals kept (w = 1 .. 3 land there: 1 / 65535 < 2^-14) -- under device compilation the hardware's convert (v_cvt_pk_f16_f32 in the gfx950 build; the kernels run
+// with the default mode: round to nearest even, 16-bit denormals kept), on a host-compiled build the same rule in integer arithmetic on the bits of the single.
+__host__ __device__ inline float deliver_unit_f32(uint32_t w) { return (float)w * (1.0f / 65535.0f); }
+__host__ __device__ inline uint32_t deliver_f16_bits(float f)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+	const _Float16 h = (_Float16)f;
+	return (uint32_t)__builtin_bit_cast(unsigned short, h);
+#else
+	uint32_t x; memcpy(&x, &f, 4);
+	const uint32_t sign = (x >> 16) & 0x8000u, e = (x >> 23) & 0xffu, m = x & 0x7fffffu;
+	if (e == 0xffu) return sign | 0x7c00u | (m ? 0x200u | (m >> 13) : 0u);      // infinity, NaN (quiet)
+	if (e >= 143u) return sign | 0x7c00u;                                        // 2^16 and beyond: infinity (65520 .. 65536 get there by the carry below)
+	uint32_t h, rest, half;
+	if (e >= 113u) { h = ((e - 112u) << 10) | (m >> 13); rest = m & 0x1fffu; half = 0x1000u; }      // a normal binary16: 13 bits of the fraction go
+	else if (e >= 102u) { const uint32_t full = m | 0x800000u, shift = 126u - e; h = full >> shift; rest = full & ((1u << shift) - 1u); half = 1u << (shift - 1u); }      // a subnormal one: units of 2^-24
+	else return sign;                                                            // below 2^-25 (zero, the singles' own subnormals): zero
+	if (rest > half || (rest == half && (h & 1u))) h++;                          // to nearest, ties to even; a carry runs into the exponent, as it should
+	return sign | h;
+#endif
+}
+
+// the words (a.lo, b.hi) and (a.hi, b.lo) of two longwords
+__device__ __forceinline__ uint32_t deliver_lo_hi(uint32_t a, uint32_t b) { return byte_perm(b, a, 0x07060100u); }
+__device__ __forceinline__ uint32_t deliver_hi_lo(uint32_t a, uint32_t b) { return byte_perm(b, a, 0x05040302u); }
+__device__ __forceinline__ cfhd_u4 deliver_load_dword_aligned(const uint8_t *p) { cfhd_u4 v; v.x = CFHD_LDG32(p); v.y = CFHD_LDG32(p + 4); v.z = CFHD_LDG32(p + 8); v.w = CFHD_LDG32(p + 12); return v; }
+
+// eight elements of one plane, two to a longword as they come out of the RG48 words: 16 bytes of u16 or f16, 32 bytes of f32 (at, a multiple of 16)
+__device__ __forceinline__ void deliver_store_plane(uint8_t *at, uint32_t p0, uint32_t p1, uint32_t p2, uint32_t p3, int layout)
+{
+	if (layout == DELIVER_PLANAR_U16) { store_u32x4_global(at, p0, p1, p2, p3); return; }
+	const uint32_t p[4] = { p0, p1, p2, p3 };
+	if (layout == DELIVER_PLANAR_F16) {
+		uint32_t h[4];
+		for (int k = 0; k < 4; k++) h[k] = deliver_f16_bits(deliver_unit_f32(p[k] & 0xffffu)) | (deliver_f16_bits(deliver_unit_f32(p[k] >> 16)) << 16);
+		store_u32x4_global(at, h[0], h[1], h[2], h[3]);
+		return;
+	}
+	uint32_t f[8];
+	for (int k = 0; k < 4; k++) { const float lo = deliver_unit_f32(p[k] & 0xffffu), hi = deliver_unit_f32(p[k] >> 16); memcpy(&f[2 * k], &lo, 4); memcpy(&f[2 * k + 1], &hi, 4); }
+	store_u32x4_global(at, f[0], f[1], f[2], f[3]);
+	store_u32x4_global(at + 16, f[4], f[5], f[6], f[7]);
+}
+// one element of a plane (the columns behind the last whole group of eight)
+__device__ __forceinline__ void deliver_store_element(uint8_t *plane_row, int x, uint32_t w, int layout)
+{
+	if (layout == DELIVER_PLANAR_U16) ((uint16_t *)plane_row)[x] = (uint16_t)w;
+	else if (layout == DELIVER_PLANAR_F16) ((uint16_t *)plane_row)[x] = (uint16_t)deliver_f16_bits(deliver_unit_f32(w));
+	else ((float *)plane_row)[x] = deliver_unit_f32(w);
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_dec_deliver: picture i of the pass, `rows` rows of row_bytes bytes back to back at src + i * src_stride (the batch's own buffer: its pitch is its row bytes), into
+// dst + i * dst_stride.  Every row gets its bytes and nothing else: pitch padding, the space between planes and pictures stay as they are.
+//   PACKED: row r at dst_pitch * r.  A lane moves 16 bytes: one 16-byte load, one 16-byte store at the caller's pitch (a multiple of 16, as dst and dst_stride are).
+//     Rows that are no multiple of 16 bytes long (RG24 of RGB 4:4:4 samples: 3 x width, a multiple of 4 at the least) start on longword boundaries in the batch's
+//     buffer: their 16-byte pieces are loaded longword by longword, and the bytes behind the last piece leave as longwords, then bytes.
+//   PLANAR_*: RG48 pictures of `width` pixels (row_bytes = 6 x width).  Plane c (R, G, B) at dst_pitch * rows * c, row r of it at dst_pitch * r, `width` elements.
+//     A lane takes 8 pixels: three 16-byte loads -- 48 bytes a lane, a wave reads 3 KB of the row without a gap --, the components separated in registers (v_perm: the
+//     words 3 k + c of the 24), one 16-byte store per plane for u16 / f16, two for f32 -- every store instruction of a wave writes consecutive 16-byte pieces of a plane
+//     row.  The widths the RG48 gates admit are multiples of 8 but for the half-resolution pictures of RGB 4:4:4 samples (width / 2, a multiple of 4): every second
+//     row of such a picture starts off a 16-byte boundary, and the whole picture goes element by element (2-byte loads, 2- or 4-byte stores; correct, slow, its rate
+//     not measured).  The element loop also takes the columns behind the last whole group of eight of an aligned picture, should a gate ever admit such a width.
+// No LDS, no scratch.  A wave owns a row at a time: grid (row pieces, pictures), DEC_DELIVER_WAVES rows per piece and step.
+// ---------------------------------------------------------------------------------------------
+enum { DEC_DELIVER_THREADS = 256, DEC_DELIVER_WAVES = DEC_DELIVER_THREADS / 64, DEC_DELIVER_SPLIT = 32 };
+inline unsigned dec_deliver_pieces(int rows) { const int p = (rows + DEC_DELIVER_WAVES - 1) / DEC_DELIVER_WAVES; return (unsigned)(p < 1 ? 1 : (p > DEC_DELIVER_SPLIT ? DEC_DELIVER_SPLIT : p)); }
+
+__global__ void __launch_bounds__(DEC_DELIVER_THREADS) k_dec_deliver(const uint8_t *src, size_t src_stride, int row_bytes, int rows, int width, uint8_t *dst, size_t dst_stride, int dst_pitch, int layout)
+{
+	const int lane = (int)(threadIdx.x & 63u), wave = wave_uniform((int)(threadIdx.x >> 6));
+	const uint8_t *pic = src + src_stride * (size_t)blockIdx.y;
+	uint8_t *out = dst + dst_stride * (size_t)blockIdx.y;
+	const bool rows_aligned = !(((uintptr_t)src | src_stride | (size_t)row_bytes) & 15);      // every row of the batch's pictures starts on a 16-byte boundary
+	for (int r = (int)blockIdx.x * DEC_DELIVER_WAVES + wave; r < rows; r += (int)gridDim.x * DEC_DELIVER_WAVES) {
+		const uint8_t *row = pic + (size_t)r * row_bytes;
+		if (layout == DELIVER_PACKED) {
+			uint8_t *orow = out + (size_t)r * dst_pitch;
+			const int whole = row_bytes & ~15;
+			for (int x = 16 * lane; x < whole; x += 16 * 64) {
+				const cfhd_u4 v = rows_aligned ? CFHD_LDG128(row + x) : deliver_load_dword_aligned(row + x);
+				store_u32x4_global(orow + x, v.x, v.y, v.z, v.w);
+			}
+			if (!rows_aligned) {                                     // the tail: up to three longwords, then up to three bytes
+				const int words_end = row_bytes & ~3;
+				for (int x = whole + 4 * lane; x < words_end; x += 4 * 64) *(uint32_t *)(orow + x) = CFHD_LDG32(row + x);
+				for (int x = words_end + lane; x < row_bytes; x += 64) orow[x] = row[x];
+			}
+			continue;
+		}
+		const int elt = layout == DELIVER_PLANAR_F32 ? 4 : 2;
+		const size_t plane = (size_t)dst_pitch * (size_t)rows;
+		uint8_t *orow = out + (size_t)r * dst_pitch;
+		const int groups = rows_aligned ? width >> 3 : 0;          // (width % 8 = 4: every second row starts off a 16-byte boundary; those pictures go element by element)
+		for (int g = lane; g < groups; g += 64) {
+			const cfhd_u4 a = CFHD_LDG128(row + 48 * g), b = CFHD_LDG128(row + 48 * g + 16), c = CFHD_LDG128(row + 48 * g + 32);
+			// the 12 longwords hold the words R0 G0 | B0 R1 | G1 B1 of every pair of pixels
+			uint8_t *at = orow + (size_t)g * 8 * elt;
+			deliver_store_plane(at, deliver_lo_hi(a.x, a.y), deliver_lo_hi(a.w, b.x), deliver_lo_hi(b.z, b.w), deliver_lo_hi(c.y, c.z), layout);
+			deliver_store_plane(at + plane, deliver_hi_lo(a.x, a.z), deliver_hi_lo(a.w, b.y), deliver_hi_lo(b.z, c.x), deliver_hi_lo(c.y, c.w), layout);
+			deliver_store_plane(at + 2 * plane, deliver_lo_hi(a.y, a.z), deliver_lo_hi(b.x, b.y), deliver_lo_hi(b.w, c.x), deliver_lo_hi(c.z, c.w), layout);
+		}
+		for (int x = 8 * groups + lane; x < width; x += 64) {
+			const uint16_t *px = (const uint16_t *)row + 3 * x;
+			deliver_store_element(orow, x, px[0], layout);
+			deliver_store_element(orow + plane, x, px[1], layout);
+			deliver_store_element(orow + 2 * plane, x, px[2], layout);
+		}
+	}
+}
+
+} // namespace dev
+} // namespace cfhd

@@ -43,6 +43,7 @@ public:
 	const FramePlan &plan() const { return plan_; }
 	// Stage one host frame (any pitch, negative allowed as in Codec/encoder.c:1957) and start its H2D copy.
 	int upload_frame(int i, const void *frame, int pitch_bytes);
+	int upload_frame_device(int i, const void *d_frame, int pitch_bytes);      // the same for a frame in HBM on the batch's device: one strided D2D copy on the batch's stream, no staging
 	int upload_frames(const void *frames, size_t frame_stride, int pitch_bytes);      // all n frames, asynchronous on the batch's stream; ONE copy when the frames lie back to back in a registered buffer
 	// the next launches (forward transform, entropy coder, sample download) cover frames 0 .. k-1 only (0 = all)
 	void set_active(int k) { active_ = k; ent_.set_active(k); }
@@ -205,6 +206,7 @@ public:
 	const GopPlan &group_plan(int g) const { return group_plans_.empty() ? plan_ : group_plans_[(size_t)g]; }
 	// encoder
 	int upload_frame(int f, const void *frame, int pitch_bytes);      // f = 0 .. 2 n - 1: stage one frame and start its H2D copy
+	int upload_frame_device(int f, const void *d_frame, int pitch_bytes);      // the same for a frame in HBM on the batch's device: one strided D2D copy on the batch's stream
 	int upload_frames(const void *frames, size_t frame_stride, int pitch_bytes);      // all 2 n frames, asynchronous on the batch's stream (staged through pinned memory unless registered and back to back)
 	int launch_forward() { return launch_forward(0, n_); }      // async: level 1 of all frames, temporal step, three spatial transforms per channel
 	// the same over groups first_group .. first_group + count - 1: the job tables are group-major, so a window is every table from its first group's rows on and grids

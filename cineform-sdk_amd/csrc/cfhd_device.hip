@@ -531,11 +531,11 @@ int EncodeBatch::sync_jobs()
 // frames from this size on are staged in pieces (below it the extra calls cost more than the overlap gives); CFHD_AMD_STAGE_MIN_BYTES: tests lower it
 static size_t stage_piece_min_bytes() { static const size_t v = [] { const char *e = getenv("CFHD_AMD_STAGE_MIN_BYTES") /* test hook: pieces at the small frames of the CPU suite too */; return e ? (size_t)atoll(e) : ((size_t)1 << 20); }(); return v; }
 
-int EncodeBatch::upload_frame(int i, const void *frame, int pitch)
+// The first row in memory of a frame handed over with `pitch`, and in *pitch the (positive) distance its rows are walked at: upload_frame and upload_frame_device.
+static const uint8_t *frame_first_row(const FramePlan &plan_, int in_pitch_, int in_rows_, const void *frame, int *pitch_io)
 {
-	(void)hipSetDevice(device_);
-	if (i < 0 || i >= n_) return -1;
 	const uint8_t *src = (const uint8_t *)frame;
+	int pitch = *pitch_io;
 	if (plan_.pixel_kind == PIX_BYR4) {
 		// The reference reads a BYR4 frame as tightly packed rows whatever pitch it was given (frame.c:5376-5377: line1 = data + row * width * 4,
 		// line2 = line1 + width * 2, in 16-bit words of the component plane width); only the sign of the pitch moves the start (encoder.c:1957,
@@ -549,6 +549,27 @@ int EncodeBatch::upload_frame(int i, const void *frame, int pitch)
 		pitch = in_pitch_;
 	}
 	if (pitch < 0) { src += (ptrdiff_t)(in_rows_ - 1) * pitch; pitch = -pitch; }     // encoder.c:1957
+	*pitch_io = pitch;
+	return src;
+}
+
+// upload_frame for a frame that lies in HBM on the batch's device: the same start and pitch, one strided device-to-device copy into the frame's slot on the batch's
+// stream, no staging.  The source is the caller's until the stream has drained.
+int EncodeBatch::upload_frame_device(int i, const void *d_frame, int pitch)
+{
+	(void)hipSetDevice(device_);
+	if (i < 0 || i >= n_ || !d_frame) return -1;
+	const uint8_t *src = frame_first_row(plan_, in_pitch_, in_rows_, d_frame, &pitch);
+	if (pitch < in_pitch_) return -1;
+	HIPCHK(hipMemcpy2DAsync(d_in_ + frame_bytes_ * i, (size_t)in_pitch_, src, (size_t)pitch, (size_t)in_pitch_, (size_t)in_rows_, hipMemcpyDeviceToDevice, (hipStream_t)stream_));
+	return 0;
+}
+
+int EncodeBatch::upload_frame(int i, const void *frame, int pitch)
+{
+	(void)hipSetDevice(device_);
+	if (i < 0 || i >= n_) return -1;
+	const uint8_t *src = frame_first_row(plan_, in_pitch_, in_rows_, frame, &pitch);
 	if (pitch >= in_pitch_ && host_buffer_is_registered(src, (size_t)pitch * (in_rows_ - 1) + in_pitch_)) {
 		// a buffer the caller registered: DMA straight out of it (the frame is borrowed until the encode completes, as in the reference)
 		HIPCHK(hipMemcpy2DAsync(d_in_ + frame_bytes_ * i, (size_t)in_pitch_, src, (size_t)pitch, (size_t)in_pitch_, (size_t)in_rows_, hipMemcpyHostToDevice, (hipStream_t)stream_));
@@ -1704,6 +1725,22 @@ int GopBatch::upload_frame(int f, const void *frame, int pitch)
 	if (pitch == pitch_ || av28) memcpy(dst, src, frame_bytes_);
 	else for (int r = 0; r < rows_; r++) memcpy(dst + (size_t)r * pitch_, src + (size_t)r * pitch, (size_t)pitch_);
 	HIPCHK(hipMemcpyAsync(d_frames_ + frame_bytes_ * f, dst, frame_bytes_, hipMemcpyHostToDevice, (hipStream_t)stream_));
+	return 0;
+}
+
+// upload_frame for a frame that lies in HBM on the batch's device (EncodeBatch::upload_frame_device): one strided device-to-device copy on the batch's stream.
+int GopBatch::upload_frame_device(int f, const void *d_frame, int pitch)
+{
+	(void)hipSetDevice(device_);
+	if (decode_ || f < 0 || f >= 2 * n_ || !d_frame) return -1;
+	const uint8_t *src = (const uint8_t *)d_frame;
+	if (pitch < 0) { src += (ptrdiff_t)(rows_ - 1) * pitch; pitch = -pitch; }     // encoder.c:1957
+	if (plan_.pixel_kind == PIX_AV28) {                     // (one block of two planes, walked as tightly packed rows whatever the pitch: upload_frame)
+		HIPCHK(hipMemcpyAsync(d_frames_ + frame_bytes_ * f, src, frame_bytes_, hipMemcpyDeviceToDevice, (hipStream_t)stream_));
+		return 0;
+	}
+	if (pitch < pitch_) return -1;
+	HIPCHK(hipMemcpy2DAsync(d_frames_ + frame_bytes_ * f, (size_t)pitch_, src, (size_t)pitch, (size_t)pitch_, (size_t)rows_, hipMemcpyDeviceToDevice, (hipStream_t)stream_));
 	return 0;
 }
 

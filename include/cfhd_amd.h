@@ -17,6 +17,9 @@
  * samples to b64a at full and half resolution (DESIGN.md section 1 lists what each round added).  The Avid layouts are encoder inputs only: as decoder outputs
  * they hang off the reference's active-metadata colour engine, which is out of scope ("Refused").  Anything else
  * returns CFHD_ERROR_BADFORMAT (3) / CFHD_ERROR_BAD_RESOLUTION (11).
+ * Both queues of the extension API have a device-memory side: the decode queue delivers its pictures into device memory the caller owns, packed or -- RG48 -- as
+ * planar R, G, B tensors of u16 / f16 / f32 (cfhd_amd_decode_batch_set_device_pictures), the frame queue takes frames that lie in device memory
+ * (cfhd_amd_batch_upload_device).
  * There is no CPU fallback: without a HIP device the encode/decode calls return CFHD_ERROR_INTERNAL (6).
  */
 #ifndef CFHD_AMD_H
@@ -148,6 +151,12 @@ cfhd_amd_batch *cfhd_amd_batch_create_ex(int width, int height, uint32_t pixel_f
 cfhd_amd_batch *cfhd_amd_batch_create(int width, int height, uint32_t pixel_format, int quality, int nframes, int nthreads);
 void cfhd_amd_batch_destroy(cfhd_amd_batch *batch);
 int  cfhd_amd_batch_upload(cfhd_amd_batch *batch, int frame, const void *pixels, int pitch);   /* host frame -> HBM (outside any timed region) */
+/* cfhd_amd_batch_upload for a frame that lies in HBM on the batch's device (a renderer's, PyTorch's, the decode queue's pictures: the caller vouches for the device):
+ * the same frame index -- intra, group and stream batches -- and the same pitch rules, a negative pitch and the inputs walked as tightly packed rows whatever the
+ * pitch (BYR4, BYR5, av28) included.  One strided device-to-device copy queued on the batch's stream, no staging, no host wait: the source is borrowed until the next
+ * cfhd_amd_batch_wait / cfhd_amd_batch_roundtrip of the batch returns, and whatever produced it has completed before this call.  0; -1 for bad arguments (no batch, a
+ * frame outside the batch, no pointer, a pitch whose magnitude is below the row bytes) or a pass in flight; another value for a device failure. */
+int  cfhd_amd_batch_upload_device(cfhd_amd_batch *batch, int frame, const void *d_pixels, int pitch);
 long long cfhd_amd_batch_roundtrip(cfhd_amd_batch *batch);                                     /* one pass; total sample bytes, or < 0 */
 /* The same pass as a slot of a frame queue (replaces the reference's EncoderPool job queue, EncoderSDK/EncoderPool.cpp:239-380): submit returns at once -- the whole
  * pass is queued on the batch's HIP streams, the decoder's stream waiting for the encoder's events; no host thread, no host wait inside the pass --, wait returns what
@@ -293,6 +302,25 @@ int  cfhd_amd_decode_batch_submit_host(cfhd_amd_decode_batch *batch, const void 
  * [d_base, d_base + span_bytes), else -1).  The library reads the 16-byte aligned blocks that hold bytes of [d_base, d_base + span_bytes) -- its 16-byte hull -- and
  * nothing else, until wait returns.  The pictures stay in HBM. */
 int  cfhd_amd_decode_batch_submit_device(cfhd_amd_decode_batch *batch, const void *d_base, size_t span_bytes, const size_t *offsets, const size_t *sizes, int count);
+/* Names the device memory every later pass of the batch -- submit_host and submit_device, intra batches and group batches -- delivers its pictures into: picture i of a
+ * pass at d_pictures + i * picture_stride, written by k_dec_deliver behind the pass's last kernel on the batch's stream.  d_pictures = NULL switches delivery off
+ * again (the other arguments are ignored).  The memory lies on the batch's device -- the caller vouches for that, as for d_base of submit_device --, is borrowed from
+ * submit until cfhd_amd_decode_batch_wait returns, and the caller's own work on it has completed before it submits; when wait has returned the pictures are complete
+ * and visible to any stream.  Host delivery (`pictures` of submit_host) and cfhd_amd_decode_batch_download_output work unchanged beside it, the dither seed of pass k
+ * is unchanged, and what the memory holds agrees with status[i] of wait as download_output does: zeros (0.0) for a sample that failed, the handle's picture for one the
+ * handle decoded inside wait.
+ * CFHD_AMD_PICTURES_PACKED: the batch's own output format and resolution, whatever it was created with -- `height` rows of `row_bytes` bytes
+ * (cfhd_amd_decode_batch_geometry), picture_pitch bytes apart.
+ * CFHD_AMD_PICTURES_PLANAR_U16 / _F16 / _F32: a batch created with output RG48 only (full or half resolution; 4:2:2, RGB 4:4:4 and RGBA 4:4:4:4 samples, progressive and
+ * interlaced groups).  A picture is three planes, R, then G, then B, each `height` rows of `width` elements, rows picture_pitch bytes apart, planes height * picture_pitch
+ * bytes apart: a contiguous tensor (n, 3, H, W) is picture_pitch = W * element size, picture_stride = 3 * H * W * element size.  For the RG48 word w: U16 is w; F32 is
+ * (float)w * (1.0f / 65535.0f), one IEEE single multiply; F16 is that value rounded to nearest-even to binary16, subnormals kept.
+ * Exactly count pictures are written, of every row its row bytes and nothing else: pitch padding, the space between planes and pictures and the pictures behind a short
+ * pass are not touched.
+ * 0; -1 with the reason in cfhd_amd_last_error(): a pass in flight, an unknown layout, a planar layout on a batch whose output is not RG48, a pointer, stride or pitch
+ * that is no multiple of 16, a pitch below the row bytes of the layout, a stride below what one picture occupies. */
+enum { CFHD_AMD_PICTURES_PACKED = 0, CFHD_AMD_PICTURES_PLANAR_U16 = 1, CFHD_AMD_PICTURES_PLANAR_F16 = 2, CFHD_AMD_PICTURES_PLANAR_F32 = 3 };
+int  cfhd_amd_decode_batch_set_device_pictures(cfhd_amd_decode_batch *batch, void *d_pictures, size_t picture_stride, int picture_pitch, int layout);
 /* Collects the pass: the number of samples that decoded, or < 0 (-1: nothing in flight, -2: device failure).  status (NULL or count entries): status[i] is the CFHD_Error
  * CFHD_DecodeSample returns for sample i on a handle prepared on the first sample; the picture of a sample that failed is zero.  Samples the device parser refuses are
  * final there; samples the device stage does not place (longer than width x height x bytes per pixel + 64 KB, a size that is no multiple of 4), samples whose scan or
@@ -303,7 +331,8 @@ int  cfhd_amd_decode_batch_wait(cfhd_amd_decode_batch *batch, CFHD_Error *status
  * batch keeps whichever way the pass delivered its pictures -- what this call gives always agrees with status[i].  0, -1 for bad arguments or a pass in flight, -2 for a device failure. */
 int  cfhd_amd_decode_batch_download_output(cfhd_amd_decode_batch *batch, int i, void *out, int pitch);
 /* HIP-event time (ms) of the kernels of the last pass and their names as a profiler shows them.  which: 0 k_dec_ingest, 1 k_dec_parse, 2 the band decoder (all its
- * kernels), 3 k_dec_lowpass, 4 / 5 / 6 the transform levels in launch order (the last one with the output conversion), 7 k_dec_blank.  0 / "" otherwise. */
+ * kernels), 3 k_dec_lowpass, 4 / 5 / 6 the transform levels in launch order (the last one with the output conversion), 7 k_dec_blank, 9 k_dec_deliver (both kinds of
+ * batch; 0 ms when the last pass delivered nothing into device memory).  0 / "" otherwise. */
 float cfhd_amd_decode_batch_kernel_ms(cfhd_amd_decode_batch *batch, int which);
 const char *cfhd_amd_decode_batch_kernel_name(cfhd_amd_decode_batch *batch, int which);
 int  cfhd_amd_device_count(void);
