@@ -278,6 +278,7 @@ int batch_launch(cfhd_amd_batch *b)
 {
 	cfhd_amd_chunk *c = b->chunks[0].get();
 	b->t_launch0 = now();
+	c->enc.collect_begin_pass();                        // (the k_enc_collect launches that fed this pass, if any: cfhd_amd_batch_kernel_ms index 20)
 	const uint32_t base_number = b->steps * (uint32_t)b->n;
 	// every frame gets the metadata CFHD_EncodeSample would give it: GUID, encode date / time, a timecode and a unique frame number that advance per frame
 	b->frame_meta.resize(b->n);
@@ -360,6 +361,7 @@ int gop_launch(cfhd_amd_batch *b)
 	GopBatch &enc = *b->genc;
 	const int ng = b->ngroups();
 	b->t_launch0 = now();
+	enc.collect_begin_pass();                           // (the k_enc_collect launches that fed this pass, if any: cfhd_amd_batch_kernel_ms index 20)
 	// the metadata of the handle's call that completes group g: CFHD_EncodeSample advances it on every call, frame by frame
 	b->frame_meta.resize(b->n);
 	for (int i = 0; i < b->n; i++) { b->meta.handle(); b->frame_meta[i] = b->meta.global; meta_remove_hidden(b->frame_meta[i]); }
@@ -669,6 +671,36 @@ int cfhd_amd_batch_upload_device(cfhd_amd_batch *b, int i, const void *d_frame, 
 	return c.enc.upload_frame_device(l, d_frame, pitch);
 }
 
+// Frames first_frame .. first_frame + count - 1 of an RG48 batch from planar R, G, B tensors in HBM on the batch's device: one k_enc_collect launch on the stream the
+// pass runs on (an intra batch cut into chunks: one per chunk the run touches, on that chunk's stream), no staging, no host wait.  The gates that need the geometry
+// are the encoder objects' (collect_planar_frames, cfhd_device.hip); they depend on nothing a chunk has of its own, so a run is refused before any of it is launched.
+int cfhd_amd_batch_upload_device_planar(cfhd_amd_batch *b, int first_frame, int count, const void *d_frames, size_t frame_stride, int row_pitch, int layout)
+{
+	CallerDevice caller_device;
+	if (!b) { device_set_last_error("cfhd_amd_batch_upload_device_planar: no batch"); return -1; }
+	if (b->in_flight) { device_set_last_error("cfhd_amd_batch_upload_device_planar: a pass is in flight"); return -1; }
+	if (count < 1 || first_frame < 0 || first_frame > b->n - count) { device_set_last_error("cfhd_amd_batch_upload_device_planar: the run of frames leaves the batch"); return -1; }
+	if (b->gop) return b->genc->upload_frames_device_planar(first_frame, count, d_frames, frame_stride, row_pitch, layout);
+	for (auto &c : b->chunks) {
+		const int lo = first_frame > c->first ? first_frame : c->first, hi = first_frame + count < c->first + c->n ? first_frame + count : c->first + c->n;
+		if (lo >= hi) continue;
+		const uint8_t *src = d_frames ? (const uint8_t *)d_frames + frame_stride * (size_t)(lo - first_frame) : nullptr;
+		const int rc = c->enc.upload_frames_device_planar(lo - c->first, hi - lo, src, frame_stride, row_pitch, layout);
+		if (rc) return rc;
+	}
+	return 0;
+}
+
+// Frame i as the batch holds it, in its packed input format (the twin of cfhd_amd_batch_download_output for the input side): waits for the stream the uploads run on.
+int cfhd_amd_batch_download_frame(cfhd_amd_batch *b, int i, void *out, int pitch)
+{
+	CallerDevice caller_device;
+	if (!b || b->in_flight || i < 0 || i >= b->n || !out) return -1;
+	if (b->gop) return b->genc->download_input_frame(i, out, pitch);
+	int l; cfhd_amd_chunk &c = b->chunk_of(i, &l);
+	return c.enc.download_input_frame(l, out, pitch);
+}
+
 // One step of the hot path over the whole batch.  Returns the total number of sample bytes, or < 0.
 static long long cfhd_amd_batch_roundtrip_locked(cfhd_amd_batch *b);
 // (A batch with a pass in flight -- cfhd_amd_batch_submit without its _wait -- refuses every entry point that would touch its streams, job tables or pinned buffers: -1.)
@@ -701,7 +733,9 @@ static long long cfhd_amd_batch_roundtrip_locked(cfhd_amd_batch *b)
 		const int rc = batch_launch(b);
 		if (rc) return rc;
 		return batch_finish(b);
-	} else if (b->gpu_entropy && b->device_handoff) {
+	}
+	for (auto &c : b->chunks) c->enc.collect_begin_pass();      // (as in batch_launch)
+	if (b->gpu_entropy && b->device_handoff) {
 		// Samples stay in HBM between the encoder and the decoder: the decoder's stream waits for the encoder's kernels, parses
 		// the samples on the GPU and decodes, while the finished samples travel to the host (the encoder's product) on the
 		// encoder's stream beside it.
@@ -907,7 +941,8 @@ long long cfhd_amd_batch_wait(cfhd_amd_batch *b)
 // which: 0..2 forward level launches (0 = k_fwd_yuv422), 3..5 inverse level launches (3 = k_inv_yuv422), 6 forward total, 7 inverse total,
 // 8..11 k_ent_count / k_ent_scan / k_ent_layout / k_ent_emit, 12..14 k_dec_parse / band decoder (all its kernels) / k_dec_lowpass,
 // 15..17 k_dec_index / k_dec_chain / k_dec_tiles, 18 the level-1 part of k_ent_count on its own stream (then 8 is the rest of it; 0 when the count is one
-// launch), 19 k_dec_plan (the single workgroup that numbers the chunks in front of k_dec_index) (ms, HIP events on the launch streams)
+// launch), 19 k_dec_plan (the single workgroup that numbers the chunks in front of k_dec_index) (ms, HIP events on the launch streams),
+// 20 -- both kinds of batch -- the k_enc_collect launches that fed the pass (cfhd_amd_batch_upload_device_planar; 0 when none did)
 // Batches of two-frame groups: 0 level 1 of all frames, 1 the temporal step + the two middle wavelets (k_gop_temporal_fwd, k_fwd_plane over 6 jobs a group), 2 the
 // top wavelet (k_fwd_plane over 3); 3 the last level of all frames + the output conversion, 4 the two middle wavelets + the temporal step (k_inv_plane,
 // k_gop_temporal_inv), 5 the top wavelet (k_inv_plane); 6 / 7 the sums of 0..2 / 3..5; 8..11 as above; 12 k_dec_parse_group, 13 the band decoder (k_dec_bands_par of
@@ -915,6 +950,7 @@ long long cfhd_amd_batch_wait(cfhd_amd_batch *b)
 float cfhd_amd_batch_kernel_ms(cfhd_amd_batch *b, int which)
 {
 	if (!b || b->in_flight) return 0;
+	if (which == 20) { float ms = b->gop ? b->genc->collect_ms() : 0.0f; for (auto &c : b->chunks) ms += c->enc.collect_ms(); return ms; }
 	if (b->gop) {
 		if (which < 0 || (which >= 3 && which != 6 && !(which >= 8 && which < 12) && !b->decode)) return 0;
 		if (which < 3) return b->genc->stage_ms(which);
@@ -954,9 +990,10 @@ int cfhd_amd_quantizer_is_static(int width, int height, uint32_t pixel_format, i
 	return fp.gop ? (fp.gop_static_quantizer ? 1 : 0) : (fp.static_quantizer ? 1 : 0);
 }
 
-// which as in cfhd_amd_batch_kernel_ms, 0..5: the name of the transform kernel behind that number (the shape depends on geometry and batch size)
+// which as in cfhd_amd_batch_kernel_ms, 0..5: the name of the transform kernel behind that number (the shape depends on geometry and batch size); 20: k_enc_collect
 const char *cfhd_amd_batch_kernel_name(cfhd_amd_batch *b, int which)
 {
+	if (b && which == 20) return "k_enc_collect";
 	if (b && b->gop) { CallerDevice caller_device; return which < 0 || which > 5 || b->in_flight || (which >= 3 && !b->decode) ? "" : (which < 3 ? b->genc->stage_kernel(which) : b->gdec->stage_kernel(which - 3)); }
 	if (!b || which < 0 || which > 5 || b->chunks.empty() || (which >= 3 && !b->decode)) return "";
 	return which < 3 ? b->chunks[0]->enc.level_kernel(which) : b->chunks[0]->dec.level_kernel(which - 3);

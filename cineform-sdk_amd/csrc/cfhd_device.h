@@ -31,6 +31,18 @@ struct CallerDevice { int dev; CallerDevice() : dev(device_caller_save()) {} ~Ca
 const char *device_last_error();
 void device_set_last_error(const char *text);      // a refusal decided on the host that the caller should be able to read (cfhd_amd_last_error)
 
+// The HIP-event times of the k_enc_collect launches (cfhd_collect_kernels.h: frames from planar tensors in device memory) that feed a frame-queue pass, for EncodeBatch
+// and GopBatch alike.  A call of upload_frames_device_planar records a pair of events around its launch; begin_pass() (the pass's first launch) closes the set that
+// fed it, the first wait() behind it sums the set into `ms` -- 0 for a pass no such call fed.  A batch that is never fed this way makes and records no event.
+struct CollectTimes {
+	std::vector<void *> ev;             // pairs, made when first needed
+	int recorded = 0, in_pass = 0; bool open = false; float ms = 0;
+	int record(void *stream, bool end);      // the event in front of (end = false) / behind (true: the pair is complete) a launch on `stream`; 0 or a hipError_t
+	void begin_pass() { if (!open) { open = true; in_pass = recorded; recorded = 0; } }
+	void resolve();                     // behind a stream synchronise
+	void release();
+};
+
 // N frames that travel through the forward path together: one launch per wavelet level covers every channel of
 // every frame (blockIdx.z walks the job table).  N = 1 is the synchronous CFHD_EncodeSample path.
 struct ForwardRoute; struct InverseRoute; struct GopRoute; enum class FwdL1;      // (cfhd_device.hip: the kernels a launch picks)
@@ -45,6 +57,13 @@ public:
 	int upload_frame(int i, const void *frame, int pitch_bytes);
 	int upload_frame_device(int i, const void *d_frame, int pitch_bytes);      // the same for a frame in HBM on the batch's device: one strided D2D copy on the batch's stream, no staging
 	int upload_frames(const void *frames, size_t frame_stride, int pitch_bytes);      // all n frames, asynchronous on the batch's stream; ONE copy when the frames lie back to back in a registered buffer
+	// frames first .. first + count - 1 of an RG48 batch from planar R, G, B tensors in HBM on the batch's device (layout: dev::COLLECT_PLANAR_*; frame first + k at
+	// d_frames + k * frame_stride, rows row_pitch apart, planes display_height * row_pitch apart): ONE k_enc_collect launch on the batch's stream, no staging, no host
+	// wait.  -1 with the reason in device_last_error() for what the gates refuse (cfhd_amd_batch_upload_device_planar lists them); a hipError_t for a device failure.
+	int upload_frames_device_planar(int first, int count, const void *d_frames, size_t frame_stride, int row_pitch, int layout);
+	void collect_begin_pass() { collect_.begin_pass(); }      // the frame queue calls this in front of a pass's first launch
+	float collect_ms() const { return collect_.ms; }          // k_enc_collect launches that fed the last completed pass (0: none did)
+	int download_input_frame(int i, void *out, int pitch_bytes);      // frame i as the batch holds it, packed: a strided D2H copy behind what the stream holds, waited for
 	// the next launches (forward transform, entropy coder, sample download) cover frames 0 .. k-1 only (0 = all)
 	void set_active(int k) { active_ = k; ent_.set_active(k); }
 	// async: all levels, all frames.  coeffs_needed = false: nothing but the GPU entropy stage will read this launch's coefficients -- where the level-1 bands
@@ -93,6 +112,7 @@ private:
 	bool timed_ = false;
 	GpuEntropyEncoder ent_; bool ent_ready_ = false;
 	int stage_pieces_ = 1;
+	CollectTimes collect_;
 };
 
 // What a decoder output needs, computed once from (the sample's encoded format, the requested output, half, interlaced) by output_route() in cfhd_device.hip -- the one
@@ -208,6 +228,11 @@ public:
 	int upload_frame(int f, const void *frame, int pitch_bytes);      // f = 0 .. 2 n - 1: stage one frame and start its H2D copy
 	int upload_frame_device(int f, const void *d_frame, int pitch_bytes);      // the same for a frame in HBM on the batch's device: one strided D2D copy on the batch's stream
 	int upload_frames(const void *frames, size_t frame_stride, int pitch_bytes);      // all 2 n frames, asynchronous on the batch's stream (staged through pinned memory unless registered and back to back)
+	// EncodeBatch::upload_frames_device_planar / collect_begin_pass / collect_ms / download_input_frame for the 2 n frames of the groups
+	int upload_frames_device_planar(int first, int count, const void *d_frames, size_t frame_stride, int row_pitch, int layout);
+	void collect_begin_pass() { collect_.begin_pass(); }
+	float collect_ms() const { return collect_.ms; }
+	int download_input_frame(int f, void *out, int pitch_bytes);
 	int launch_forward() { return launch_forward(0, n_); }      // async: level 1 of all frames, temporal step, three spatial transforms per channel
 	// the same over groups first_group .. first_group + count - 1: the job tables are group-major, so a window is every table from its first group's rows on and grids
 	// sized by count; (0, n) is launch_forward()
@@ -269,6 +294,7 @@ private:
 	GpuEntropyEncoder ent_; bool ent_ready_ = false;
 	GpuGroupEntropyDecoder dec_; bool dec_ready_ = false;
 	GpuGroupBatchEntropyDecoder bdec_; bool bdec_ready_ = false;
+	CollectTimes collect_;
 };
 
 int packed_frame_pitch(int pixel_kind, int width);     // bytes per row of a tightly packed frame

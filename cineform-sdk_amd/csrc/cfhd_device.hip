@@ -5,6 +5,7 @@
 // queued back to back on it, batches on different streams overlap.
 #include "cfhd_device.h"
 #include "cfhd_kernels.h"
+#include "cfhd_collect_kernels.h"
 #include <hip/hip_runtime.h>
 #include <string.h>
 #include <stddef.h>
@@ -381,6 +382,7 @@ void EncodeBatch::release()
 	if (ev0_) hipEventDestroy((hipEvent_t)ev0_);
 	if (ev1_) hipEventDestroy((hipEvent_t)ev1_);
 	for (int k = 0; k < 2; k++) if (evl_[k]) { hipEventDestroy((hipEvent_t)evl_[k]); evl_[k] = nullptr; }
+	collect_.release();
 	if (stream_) device_stream_destroy(stream_);
 	d_in_ = h_in_ = nullptr; d_coeff_ = h_coeff_ = nullptr; d_jobs_ = h_jobs_ = nullptr; stream_ = ev0_ = ev1_ = nullptr; n_ = 0;
 }
@@ -562,6 +564,73 @@ int EncodeBatch::upload_frame_device(int i, const void *d_frame, int pitch)
 	const uint8_t *src = frame_first_row(plan_, in_pitch_, in_rows_, d_frame, &pitch);
 	if (pitch < in_pitch_) return -1;
 	HIPCHK(hipMemcpy2DAsync(d_in_ + frame_bytes_ * i, (size_t)in_pitch_, src, (size_t)pitch, (size_t)in_pitch_, (size_t)in_rows_, hipMemcpyDeviceToDevice, (hipStream_t)stream_));
+	return 0;
+}
+
+// ---- frames from planar tensors in device memory (k_enc_collect)
+int CollectTimes::record(void *stream, bool end)
+{
+	const size_t at = 2 * (size_t)recorded + (end ? 1 : 0);
+	while (ev.size() <= at) { hipEvent_t e = nullptr; HIPCHK(hipEventCreate(&e)); ev.push_back((void *)e); }
+	HIPCHK(hipEventRecord((hipEvent_t)ev[at], (hipStream_t)stream));
+	if (end) recorded++;
+	return 0;
+}
+void CollectTimes::resolve()
+{
+	if (!open) return;
+	open = false; ms = 0;
+	for (int k = 0; k < in_pass; k++) {
+		float one = 0;
+		if (hipEventElapsedTime(&one, (hipEvent_t)ev[2 * (size_t)k], (hipEvent_t)ev[2 * (size_t)k + 1]) == hipSuccess) ms += one; else (void)hipGetLastError();
+	}
+	in_pass = 0;
+}
+void CollectTimes::release()
+{
+	for (void *e : ev) if (e) (void)hipEventDestroy((hipEvent_t)e);
+	ev.clear(); recorded = in_pass = 0; open = false; ms = 0;
+}
+
+// The gates and the launch of EncodeBatch:: / GopBatch::upload_frames_device_planar: `slots` holds the batch's `nframes` packed frames, frame_bytes apart, `rows` rows of
+// 6 x width bytes back to back (RG48; checked here).  Frame slots, widths and the caller's geometry together put every row of either side on a 16-byte boundary and
+// make it a whole number of the kernel's groups of eight pixels (cfhd_collect_kernels.h).
+static int collect_planar_frames(int pixel_kind, uint8_t *slots, size_t frame_bytes, int slot_pitch, int width, int rows, int nframes, int first, int count,
+                                 const void *d_frames, size_t frame_stride, int row_pitch, int layout, void *stream, CollectTimes &times)
+{
+	auto refuse = [](const char *text) { g_err = text; return -1; };
+	if (pixel_kind != PIX_RG48) return refuse("frames from planar tensors: the batch's input is not RG48");
+	if (layout != dev::COLLECT_PLANAR_U16 && layout != dev::COLLECT_PLANAR_F16 && layout != dev::COLLECT_PLANAR_F32) return refuse("frames from planar tensors: unknown layout");
+	if (count < 1 || first < 0 || first > nframes - count) return refuse("frames from planar tensors: the run of frames leaves the batch");
+	if (!d_frames) return refuse("frames from planar tensors: no pointer");
+	if (((uintptr_t)d_frames | frame_stride | (size_t)(unsigned)row_pitch) & 15) return refuse("frames from planar tensors: pointer, frame stride and row pitch are multiples of 16");
+	const int elt = layout == dev::COLLECT_PLANAR_F32 ? 4 : 2;
+	if (row_pitch < 0 || (long long)row_pitch < (long long)width * elt) return refuse("frames from planar tensors: a row pitch below width x element size");
+	if (frame_stride < 3 * (size_t)rows * (size_t)row_pitch) return refuse("frames from planar tensors: a frame stride below three planes (3 x height x row pitch)");
+	if ((width & 7) || slot_pitch != 6 * width || frame_bytes != (size_t)slot_pitch * rows || (((uintptr_t)slots | frame_bytes) & 15) || count > 65535 /* blockIdx.y */)
+		return refuse("frames from planar tensors: frame slots the collect kernel does not take");
+	int rc = times.record(stream, false);
+	if (rc) return rc;
+	(void)hipGetLastError();
+	dev::k_enc_collect<<<dim3(dev::enc_collect_pieces(rows), (unsigned)count), dev::ENC_COLLECT_THREADS, 0, (hipStream_t)stream>>>(
+		(const uint8_t *)d_frames, frame_stride, row_pitch, rows, width, slots + frame_bytes * (size_t)first, frame_bytes, layout);
+	HIPCHK(hipGetLastError());
+	return times.record(stream, true);
+}
+
+int EncodeBatch::upload_frames_device_planar(int first, int count, const void *d_frames, size_t frame_stride, int row_pitch, int layout)
+{
+	(void)hipSetDevice(device_);
+	return collect_planar_frames(plan_.pixel_kind, d_in_, frame_bytes_, in_pitch_, plan_.width, in_rows_, n_, first, count, d_frames, frame_stride, row_pitch, layout, stream_, collect_);
+}
+
+// Frame i as the batch holds it, in its packed input format: in_rows_ rows of in_pitch_ bytes (av28: the frame's one block), behind whatever the stream holds.
+int EncodeBatch::download_input_frame(int i, void *out, int pitch)
+{
+	(void)hipSetDevice(device_);
+	if (i < 0 || i >= n_ || !out || pitch < in_pitch_) return -1;
+	HIPCHK(hipMemcpy2DAsync(out, (size_t)pitch, d_in_ + frame_bytes_ * i, (size_t)in_pitch_, (size_t)in_pitch_, (size_t)in_rows_, hipMemcpyDeviceToHost, (hipStream_t)stream_));
+	HIPCHK(hipStreamSynchronize((hipStream_t)stream_));
 	return 0;
 }
 
@@ -827,6 +896,7 @@ int EncodeBatch::wait()
 {
 	(void)hipSetDevice(device_);
 	HIPCHK(hipStreamSynchronize((hipStream_t)stream_));
+	collect_.resolve();
 	float ms = 0;
 	if (!timed_) return 0;
 	timed_ = false;
@@ -1473,6 +1543,7 @@ void GopBatch::release()
 	if (dec_ready_) { dec_.release(); dec_ready_ = false; }
 	if (bdec_ready_) { bdec_.release(); bdec_ready_ = false; }
 	for (void *&e : ev_) if (e) { (void)hipEventDestroy((hipEvent_t)e); e = nullptr; }
+	collect_.release();
 	launched_ = false;
 	if (d_frames_) hipFree(d_frames_);
 	if (h_frames_) hipHostFree(h_frames_);
@@ -1744,6 +1815,24 @@ int GopBatch::upload_frame_device(int f, const void *d_frame, int pitch)
 	return 0;
 }
 
+int GopBatch::upload_frames_device_planar(int first, int count, const void *d_frames, size_t frame_stride, int row_pitch, int layout)
+{
+	(void)hipSetDevice(device_);
+	if (decode_) return -1;
+	return collect_planar_frames(plan_.pixel_kind, d_frames_, frame_bytes_, pitch_, plan_.width, rows_, 2 * n_, first, count, d_frames, frame_stride, row_pitch, layout, stream_, collect_);
+}
+
+// Frame f as the encoder's batch holds it, packed: rows_ rows of pitch_ bytes (av28: the frame's one block), behind whatever the stream holds.
+int GopBatch::download_input_frame(int f, void *out, int pitch)
+{
+	(void)hipSetDevice(device_);
+	const size_t row = pitch_ ? (size_t)pitch_ : frame_bytes_, nrows = pitch_ ? (size_t)rows_ : 1;
+	if (decode_ || f < 0 || f >= 2 * n_ || !out || pitch < 0 || (size_t)pitch < row) return -1;
+	HIPCHK(hipMemcpy2DAsync(out, (size_t)pitch, d_frames_ + frame_bytes_ * f, row, row, nrows, hipMemcpyDeviceToHost, (hipStream_t)stream_));
+	HIPCHK(hipStreamSynchronize((hipStream_t)stream_));
+	return 0;
+}
+
 // All 2 n frames from the caller's memory, queued on the batch's stream: one copy as they are when they lie back to back at the batch's own pitch in a registered
 // buffer, otherwise staged through the batch's pinned frames by the calling thread (the caller waits for the previous pass before it submits the next: the staging
 // buffer is free) and copied in one piece.
@@ -1870,6 +1959,7 @@ int GopBatch::wait()
 {
 	(void)hipSetDevice(device_);
 	HIPCHK(hipStreamSynchronize((hipStream_t)stream_));
+	collect_.resolve();
 	return 0;
 }
 

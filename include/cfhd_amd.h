@@ -157,6 +157,31 @@ int  cfhd_amd_batch_upload(cfhd_amd_batch *batch, int frame, const void *pixels,
  * cfhd_amd_batch_wait / cfhd_amd_batch_roundtrip of the batch returns, and whatever produced it has completed before this call.  0; -1 for bad arguments (no batch, a
  * frame outside the batch, no pointer, a pitch whose magnitude is below the row bytes) or a pass in flight; another value for a device failure. */
 int  cfhd_amd_batch_upload_device(cfhd_amd_batch *batch, int frame, const void *d_pixels, int pitch);
+/* Frames first_frame .. first_frame + count - 1 of a batch whose pixel format is RG48 from planar tensors in HBM on the batch's device: what
+ * cfhd_amd_decode_batch_set_device_pictures' PLANAR_* layouts are to the decode queue, for the frame queue (a renderer's or a model's output, the decode queue's own
+ * planar pictures after some processing).  Every kind of batch that takes RG48 -- intra to 4:2:2 and to RGB 4:4:4, cfhd_amd_batch_create_groups, _create_stream,
+ * _create_group_stream --, the frame indices with their per-frame meaning as for cfhd_amd_batch_upload_device.
+ * Frame first_frame + i is read from d_frames + i * frame_stride: three planes, R, then G, then B, each `height` rows of `width` elements, rows row_pitch bytes apart,
+ * planes height * row_pitch bytes apart -- the geometry of cfhd_amd_decode_batch_set_device_pictures.  A contiguous tensor (n, 3, H, W) is row_pitch = W * element
+ * size, frame_stride = 3 * H * row_pitch.
+ * One kernel launch (k_enc_collect) for the whole run, queued on the stream the pass runs on; no staging, no host wait.  The source is borrowed until the next
+ * cfhd_amd_batch_wait / cfhd_amd_batch_roundtrip of the batch returns, whatever produced it has completed before this call, and it is never written.
+ * Element -> RG48 word w.  CFHD_AMD_FRAMES_PLANAR_U16: w is the element.  _F32: t = x * 65535.0f, one IEEE single multiply; NaN gives 0; t is clamped to [0, 65535]
+ * and rounded to nearest, ties to even -- so -0, everything negative and -inf give 0, everything >= 1 and +inf give 65535.  _F16: the binary16 value widened exactly
+ * to single, subnormals kept, then the F32 rule.  These rules invert the delivery rules of cfhd_amd_decode_batch_set_device_pictures: a picture delivered as
+ * PLANAR_U16 or PLANAR_F32 and collected in the same layout gives back every one of the 65 536 words w.  binary16 has 11 significant bits and cannot: what holds for
+ * F16 is that a tensor collected as F16 and delivered as PLANAR_F16 again returns the binary16 bit pattern of every element that PLANAR_F16 delivery can produce.
+ * 0; -1 with the reason in cfhd_amd_last_error(): no batch, a pass in flight, a batch whose input is not RG48, an unknown layout (0 included), count < 1 or a run
+ * that leaves the batch, no pointer, a pointer, frame stride or row pitch that is no multiple of 16, a row pitch that is negative or below width * element size, a
+ * frame stride below 3 * height * row_pitch; another value for a device failure.
+ * cfhd_amd_batch_kernel_ms(batch, 20) is the HIP-event time of the k_enc_collect launches that fed the last completed pass (0 when none did),
+ * cfhd_amd_batch_kernel_name(batch, 20) "k_enc_collect". */
+enum { CFHD_AMD_FRAMES_PLANAR_U16 = 1, CFHD_AMD_FRAMES_PLANAR_F16 = 2, CFHD_AMD_FRAMES_PLANAR_F32 = 3 };      /* values equal to CFHD_AMD_PICTURES_PLANAR_* */
+int  cfhd_amd_batch_upload_device_planar(cfhd_amd_batch *batch, int first_frame, int count, const void *d_frames, size_t frame_stride, int row_pitch, int layout);
+/* Frame `frame` as the batch holds it, in its packed input format, into out (rows `pitch` >= row bytes apart): the twin of cfhd_amd_batch_download_output for the
+ * input side, for every kind of batch and input format (av28: the frame's one block as one row).  Waits for the stream the uploads run on.  0; -1 for bad arguments
+ * or a pass in flight; another value for a device failure. */
+int  cfhd_amd_batch_download_frame(cfhd_amd_batch *batch, int frame, void *out, int pitch);
 long long cfhd_amd_batch_roundtrip(cfhd_amd_batch *batch);                                     /* one pass; total sample bytes, or < 0 */
 /* The same pass as a slot of a frame queue (replaces the reference's EncoderPool job queue, EncoderSDK/EncoderPool.cpp:239-380): submit returns at once -- the whole
  * pass is queued on the batch's HIP streams, the decoder's stream waiting for the encoder's events; no host thread, no host wait inside the pass --, wait returns what
@@ -244,7 +269,7 @@ cfhd_amd_batch *cfhd_amd_batch_create_group_stream(int width, int height, uint32
  * -1 for a batch not made by cfhd_amd_batch_create_stream / cfhd_amd_batch_create_group_stream, before its first pass has completed, and between submit and wait. */
 int  cfhd_amd_batch_stream_stats(cfhd_amd_batch *batch, int out[3]);
 float cfhd_amd_batch_kernel_ms(cfhd_amd_batch *batch, int which);                              /* HIP-event time of the kernels of the last pass */
-const char *cfhd_amd_batch_kernel_name(cfhd_amd_batch *batch, int which);                      /* which 0..5: the transform kernel behind that time */
+const char *cfhd_amd_batch_kernel_name(cfhd_amd_batch *batch, int which);                      /* which 0..5: the transform kernel behind that time; 20: "k_enc_collect" */
 double cfhd_amd_batch_stage_seconds(cfhd_amd_batch *batch, int which);
 /* The level-1 transform kernel of a prepared encoder handle's next CFHD_EncodeSample, intra frame or two-frame group ("" when the handle is not prepared). */
 const char *cfhd_amd_encoder_kernel_name(CFHD_EncoderRef encoderRef);
