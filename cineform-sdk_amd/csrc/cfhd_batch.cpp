@@ -35,7 +35,7 @@ struct cfhd_amd_batch {
 	FramePlan plan;
 	int n = 0, nthreads = 1, quality = 4, pixel_kind = PIX_YUY2;
 	int color_format = 2, color_space = 2; bool progressive = true;
-	bool decode = true;                // false: encode only (cfhd_amd_batch_create_ex mode 1; Bayer samples, which this library does not decode)
+	bool decode = true;                // false: encode only (cfhd_amd_batch_create_ex mode 1: the Avid 4:2:2 layouts and BYR5, which no decoder output has; BYR4 round trips through cfhd_amd_batch_create_bayer)
 	// The batch is cut into chunks with their own HIP streams: while one chunk's entropy decode (latency bound: one lane per
 	// band) is in flight, the next chunk's bandwidth-bound kernels and PCIe copies run beside it.
 	std::vector<std::unique_ptr<cfhd_amd_chunk>> chunks;
@@ -88,7 +88,7 @@ struct cfhd_amd_batch {
 };
 
 namespace {
-cfhd_amd_batch *create_intra_batch(const FrontEndParams &fp, int width, int height, int nframes, int nthreads, int mode, bool stream);
+cfhd_amd_batch *create_intra_batch(const FrontEndParams &fp, int width, int height, int nframes, int nthreads, int mode, bool stream, bool bayer_round_trip = false);
 template <typename F> void parallel_for(int n, int nthreads, F f)
 {
 	if (nthreads <= 1 || n <= 1) { for (int i = 0; i < n; i++) f(i); return; }
@@ -535,9 +535,32 @@ cfhd_amd_batch *cfhd_amd_batch_create_stream(int width, int height, uint32_t pix
 }
 }
 
+extern "C" {
+// Bayer mosaics on the frame queue (include/cfhd_amd.h): BYR4 / BYR5 -> Bayer samples; mode 1 is exactly cfhd_amd_batch_create_ex's batch, mode 0 -- BYR4 -- adds the
+// decode back to the mosaic.  The tables stand still (as cfhd_amd_batch_create_ex: a Bayer stream with rate feedback is not built).
+cfhd_amd_batch *cfhd_amd_batch_create_bayer(int width, int height, uint32_t pixel_format, uint32_t encoding_flags, int quality, int nframes, int nthreads, int mode)
+{
+	CallerDevice caller_device;
+	FrontEndParams fp;
+	auto refuse = [](const char *text) { device_set_last_error(text); return (cfhd_amd_batch *)nullptr; };
+	if (nframes < 1) return refuse("cfhd_amd_batch_create_bayer: a batch has at least one frame");
+	if (mode != 0 && mode != 1) return refuse("cfhd_amd_batch_create_bayer: mode is 0 (round trip) or 1 (encode only)");
+	if (pixel_format != 0x42595234u /* 'BYR4' */ && pixel_format != 0x42595235u /* 'BYR5' */) return refuse("cfhd_amd_batch_create_bayer: the input is a Bayer mosaic, BYR4 or BYR5");
+	if (front_end_params(width, height, pixel_format, 3 /* CFHD_ENCODED_FORMAT_BAYER */, encoding_flags, quality, &fp) || fp.gop)
+		return refuse("cfhd_amd_batch_create_bayer: arguments CFHD_PrepareToEncode refuses");
+	if (fp.pixel_kind == PIX_BYR5 && mode == 0) return refuse("cfhd_amd_batch_create_bayer: BYR5 is no decoder output; mode 1 encodes only");
+	if (!fp.static_quantizer) return refuse("cfhd_amd_batch_create_bayer: the tables of this quality follow the sample sizes (a Bayer stream is not built: CFHD_EncodeSample encodes such a sequence)");
+	device_set_last_error("");
+	cfhd_amd_batch *b = create_intra_batch(fp, width, height, nframes, nthreads, mode, false, true);
+	if (!b && !*device_last_error()) device_set_last_error("cfhd_amd_batch_create_bayer: cfhd_amd_batch_create_ex refuses this arrangement");
+	return b;
+}
+}
+
 namespace {
-// An intra batch: cfhd_amd_batch_create_ex's (tables that stand still) and, with stream, cfhd_amd_batch_create_stream's (any tables).
-cfhd_amd_batch *create_intra_batch(const FrontEndParams &fp, int width, int height, int nframes, int nthreads, int mode, bool stream)
+// An intra batch: cfhd_amd_batch_create_ex's (tables that stand still) and, with stream, cfhd_amd_batch_create_stream's (any tables).  bayer_round_trip:
+// cfhd_amd_batch_create_bayer's -- the same batch, whose mode 0 decodes BYR4 back to the mosaic (large launches by the fused last level, DecodeBatch::set_bayer_strips).
+cfhd_amd_batch *create_intra_batch(const FrontEndParams &fp, int width, int height, int nframes, int nthreads, int mode, bool stream, bool bayer_round_trip)
 {
 	const int kind = fp.pixel_kind;
 	const bool yuv = kind == PIX_YUY2 || kind == PIX_2VUY;
@@ -547,7 +570,7 @@ cfhd_amd_batch *create_intra_batch(const FrontEndParams &fp, int width, int heig
 	b->color_format = fp.color_format; b->color_space = fp.color_space; b->progressive = fp.progressive;
 	b->decode = mode == 0;
 	b->plan = fp.plan;
-	if (b->decode && (kind == PIX_BYR4 || kind == PIX_BYR5 || is_avid_422(kind))) { delete b; return nullptr; }      // (no decoder output of these layouts)
+	if (b->decode && ((kind == PIX_BYR4 && !bayer_round_trip) || kind == PIX_BYR5 || is_avid_422(kind))) { delete b; return nullptr; }      // (no decoder output of these layouts; BYR4: cfhd_amd_batch_create_bayer)
 	const char *e = getenv("CFHD_AMD_ENTROPY");
 	b->gpu_entropy = !(e && strcmp(e, "host") == 0);
 	if (!b->gpu_entropy && (!yuv || !b->progressive || !b->decode)) { delete b; return nullptr; }      // the host-entropy arrangement is kept for the headline workload only
@@ -570,7 +593,7 @@ cfhd_amd_batch *create_intra_batch(const FrontEndParams &fp, int width, int heig
 		c->first = first; c->n = nframes - first < chunk ? nframes - first : chunk;
 		bool ok = true;
 		auto encoder = [&] { return !c->enc.prepare(b->plan, c->n) && !(b->gpu_entropy && c->enc.prepare_entropy(cap)); };
-		auto decoder = [&] { if (!b->decode) return true; c->dec.set_interlaced(!b->progressive); return !c->dec.prepare(b->plan, c->n, kind) && !(b->gpu_entropy && c->dec.prepare_entropy(cap)); };
+		auto decoder = [&] { if (!b->decode) return true; c->dec.set_interlaced(!b->progressive); c->dec.set_bayer_strips(bayer_round_trip); return !c->dec.prepare(b->plan, c->n, kind) && !(b->gpu_entropy && c->dec.prepare_entropy(cap)); };
 		if (streams == 1) { StreamScope scope; ok = encoder() && decoder(); if (scope.stream()) b->shared_streams.push_back(scope.stream()); }
 		else if (streams == 2) {
 			// (CFHD_AMD_STREAM_ORDER=alt, A/B: every second batch of the process creates its decoder's stream first -- with four queues dealt in creation order the encoder of

@@ -101,7 +101,8 @@ struct cfhd_amd_decode_batch {
 	uint8_t *device_pictures() const { return groups ? gdec.device_pictures() : dec.device_pictures(); }
 	int finish_frame(int i, void *out, int pitch) { return groups ? gdec.finish_frame(i, out, pitch) : dec.finish_frame(i, out, pitch); }
 	int download_frame(int i, void *out, int pitch) { return groups ? gdec.download_frame(i, out, pitch) : dec.download_frame(i, out, pitch); }
-	int picture_width() const { const int full = groups ? gst.plan.width : st.plan.width; return (groups ? gst.half : st.half) ? full / 2 : full; }
+	// (a Bayer plan counts photosite quads: the mosaic is twice as wide)
+	int picture_width() const { const int full = groups ? gst.plan.width : (st.plan.encoded_format == ENC_BAYER ? 2 * st.plan.width : st.plan.width); return (groups ? gst.half : st.half) ? full / 2 : full; }
 	~cfhd_amd_decode_batch()
 	{
 		(void)hipSetDevice(device);
@@ -227,13 +228,11 @@ void begin_pass(cfhd_amd_decode_batch *b, const size_t *offsets, const size_t *s
 }
 void end_pass(cfhd_amd_decode_batch *b) { b->in_flight = false; b->src_host = b->src_device = nullptr; b->host_out = nullptr; }
 bool refuse(const char *text) { device_set_last_error(text); return false; }
-}
 
-extern "C" {
-
-cfhd_amd_decode_batch *cfhd_amd_decode_batch_create(const void *first_sample, size_t first_size, uint32_t output_format, int decoded_resolution, int nsamples)
+// A batch of intra samples: cfhd_amd_decode_batch_create's, and -- bayer -- cfhd_amd_decode_batch_create_bayer's (the same gates and the same pass; the Bayer batch
+// answers the mosaic's geometry and lets large launches take the fused last level, DecodeBatch::set_bayer_strips).
+cfhd_amd_decode_batch *create_intra_batch(const void *first_sample, size_t first_size, uint32_t output_format, int decoded_resolution, int nsamples, bool bayer)
 {
-	CallerDevice caller_device;
 	if (!first_sample || first_size < 4) { refuse("decode queue: no first sample"); return nullptr; }
 	if (nsamples < 1) { refuse("decode queue: nsamples < 1"); return nullptr; }
 	{ const char *e = getenv("CFHD_AMD_ENTROPY"); if (e && strcmp(e, "host") == 0) { refuse("decode queue: CFHD_AMD_ENTROPY=host keeps the entropy stage on the host (the C ABI's arrangement)"); return nullptr; } }
@@ -243,7 +242,13 @@ cfhd_amd_decode_batch *cfhd_amd_decode_batch_create(const void *first_sample, si
 	ParsedSample ps;
 	const int parsed = parse_sample(s8, first_size, &ps);
 	const bool uncompressed = ps.uncompressed;           // (an UNCOMPRESS chunk: CFHD_PrepareToDecode refuses below with its own text)
-	if (parsed >= 0 && ps.encoded_format == ENC_BAYER) { refuse("decode queue: Bayer samples are decoded by CFHD_DecodeSample"); return nullptr; }
+	if (!bayer && parsed >= 0 && ps.encoded_format == ENC_BAYER) { refuse("decode queue: Bayer samples are decoded by CFHD_DecodeSample"); return nullptr; }
+	if (bayer) {
+		// served for what the handle serves: the BYR4 mosaic at full resolution (decoded_resolution 0 is taken as full, as CFHD_PrepareToDecode takes it)
+		if (!uncompressed && (parsed < 0 || ps.encoded_format != ENC_BAYER)) { refuse("decode queue: a Bayer batch is prepared on a Bayer intra sample; other intra samples go to cfhd_amd_decode_batch_create"); return nullptr; }
+		if (output_format != 0x42595234u /* 'BYR4' */) { refuse("decode queue: Bayer samples decode to BYR4, the raw mosaic (no other output is built)"); return nullptr; }
+		if (decoded_resolution != 0 && decoded_resolution != 1) { refuse("decode queue: Bayer samples decode at full resolution only"); return nullptr; }
+	}
 	cfhd_amd_decode_batch *b = new (std::nothrow) cfhd_amd_decode_batch;
 	if (!b) return nullptr;
 	b->n = nsamples;
@@ -275,6 +280,7 @@ cfhd_amd_decode_batch *cfhd_amd_decode_batch_create(const void *first_sample, si
 	{
 		StreamScope scope;
 		b->dec.set_interlaced(b->st.interlaced);
+		b->dec.set_bayer_strips(bayer);
 		const int prc = b->dec.prepare(b->st.plan, nsamples, b->st.out_kind, b->st.half) || b->dec.prepare_entropy(b->st.sample_cap);
 		b->scope_stream = scope.stream();
 		if (prc) return fail(nullptr);
@@ -286,6 +292,22 @@ cfhd_amd_decode_batch *cfhd_amd_decode_batch_create(const void *first_sample, si
 	b->dec.entropy().set_verdicts(b->d_verdicts);
 	b->slow_pictures.resize((size_t)nsamples);
 	return b;
+}
+}
+
+extern "C" {
+
+cfhd_amd_decode_batch *cfhd_amd_decode_batch_create(const void *first_sample, size_t first_size, uint32_t output_format, int decoded_resolution, int nsamples)
+{
+	CallerDevice caller_device;
+	return create_intra_batch(first_sample, first_size, output_format, decoded_resolution, nsamples, false);
+}
+
+// Bayer intra samples to BYR4 (include/cfhd_amd.h): cfhd_amd_decode_batch_create's batch with the mosaic as the picture; every other entry point is shared.
+cfhd_amd_decode_batch *cfhd_amd_decode_batch_create_bayer(const void *first_sample, size_t first_size, uint32_t output_format, int decoded_resolution, int nsamples)
+{
+	CallerDevice caller_device;
+	return create_intra_batch(first_sample, first_size, output_format, decoded_resolution, nsamples, true);
 }
 
 cfhd_amd_decode_batch *cfhd_amd_decode_batch_create_groups(const void *first_group_sample, size_t first_size, uint32_t output_format, int decoded_resolution, int ngroups)
@@ -365,8 +387,7 @@ void cfhd_amd_decode_batch_destroy(cfhd_amd_decode_batch *b)
 int cfhd_amd_decode_batch_geometry(cfhd_amd_decode_batch *b, int *width, int *height, int *row_bytes)
 {
 	if (!b || b->in_flight) return -1;
-	const int full_width = b->groups ? b->gst.plan.width : b->st.plan.width;
-	if (width) *width = (b->groups ? b->gst.half : b->st.half) ? full_width / 2 : full_width;
+	if (width) *width = b->picture_width();
 	if (height) *height = b->picture_rows();
 	if (row_bytes) *row_bytes = b->picture_pitch();
 	return 0;

@@ -120,7 +120,7 @@ private:
 // its conversion from it; GopBatch asks the same function for the outputs of 4:2:2 samples.  A new output format is a new answer of output_route(), at most one job
 // helper and at most one case of launch_convert().  (Which widths a caller may ask for is the C ABI's gate: cfhd_api_decoder.inc yuv422_output_served.)
 enum class OutJobs { Yuv, Planes16, HalfYuv, HalfPacked };      // the table the last launch reads: InvYuvJob | InvPlaneJob per output plane | HalfYuvJob | HalfPackedJob
-enum class OutConvert { None, V210, Rgb24, Rgb16, Byr4 };       // the pass behind the last level (k_yu64_to_v210 / _rgb24 / _rgb16, k_bayer_to_byr4); any but None: the last level writes a scratch frame
+enum class OutConvert { None, V210, Rgb24, Rgb16, Byr4 };       // the pass behind the last level (k_yu64_to_v210 / _rgb24 / _rgb16, k_bayer_to_byr4); any but None: the last level writes a scratch frame (Byr4: unless k_inv_bayer_strip runs)
 struct OutputRoute {
 	const char *refusal = nullptr;                  // not served: the text device_last_error() gives, prepare() answers -2
 	int width_multiple = 1; const char *width_refusal = nullptr;      // the output's width in pixels is a multiple of this, or the same answer with this text
@@ -142,6 +142,9 @@ public:
 	// (k_inv_frame_yuv422_rows16) for RG48 / b64a / BGRA / BGRa; set before prepare()
 	void set_interlaced(bool on) { interlaced_ = on; ent_.set_interlaced(on); }
 	bool interlaced() const { return interlaced_; }
+	// BYR4 output: large launches write the mosaic straight from the last level (k_inv_bayer_strip) where the geometry fits; off, the default, keeps the pair
+	// k_inv_packed16 + k_bayer_to_byr4 at every size (the C ABI's handles).  Set by the queues' Bayer batches (cfhd_amd_decode_batch_create_bayer, cfhd_amd_batch_create_bayer).
+	void set_bayer_strips(bool on) { bayer_strips_ = on; }
 	// the next launches (entropy decoder with host-parsed samples, inverse transform) cover frames 0 .. k-1 only (0 = all)
 	void set_active(int k) { active_ = k; ent_.set_active(k); }
 	int nframes() const { return n_; }
@@ -175,7 +178,7 @@ private:
 	int sync_jobs();
 	InverseRoute inverse_route() const;             // which kernels the next launch_entropy() + launch_inverse() run: both and level_kernel() read this
 	FramePlan plan_;
-	int n_ = 0, device_ = 0; bool jobs_dirty_ = true, half_ = false, interlaced_ = false; int active_ = 0;
+	int n_ = 0, device_ = 0; bool jobs_dirty_ = true, half_ = false, interlaced_ = false, bayer_strips_ = false; int active_ = 0;
 	int out_kind_ = 0; OutputRoute route_;          // the REQUESTED output kind, never rewritten, and what it needs (the kind the kernels write is route_.work)
 	void *stream_ = nullptr, *ev0_ = nullptr, *ev1_ = nullptr, *evl_[2] = {nullptr, nullptr};
 	float level_ms_[3] = {0, 0, 0};

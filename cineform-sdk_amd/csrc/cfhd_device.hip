@@ -67,7 +67,7 @@ EncJobs enc_jobs_at(void *base, int n, int nch)
 }
 size_t enc_jobs_bytes(int n, int nch) { return (size_t)n * sizeof(dev::FwdYuvJob) + 3 * (size_t)n * nch * sizeof(dev::FwdPlaneJob) + (size_t)n * sizeof(dev::BayerJob); }
 
-struct DecJobs { dev::InvPlaneJob *l3, *l2; dev::InvYuvJob *yuv; dev::InvPlaneJob *l1; /* last level of the 4:4:4(:4) formats (k_inv_packed16) */ dev::HalfYuvJob *half; /* [n] half-resolution output */ dev::HalfPackedJob *halfp; /* [n] the same for the 4:4:4(:4) formats */ };
+struct DecJobs { dev::InvPlaneJob *l3, *l2; dev::InvYuvJob *yuv; dev::InvPlaneJob *l1; /* last level of the 4:4:4(:4) formats (k_inv_packed16) */ dev::HalfYuvJob *half; /* [n] half-resolution output */ dev::HalfPackedJob *halfp; /* [n] the same for the 4:4:4(:4) formats */ dev::InvBayerJob *bayer; /* [n] BYR4 output: the mosaic and the restore table (k_inv_bayer_strip, beside l1) */ };
 DecJobs dec_jobs_at(void *base, int n, int nch)
 {
 	DecJobs j;
@@ -77,9 +77,10 @@ DecJobs dec_jobs_at(void *base, int n, int nch)
 	j.l1 = (dev::InvPlaneJob *)(j.yuv + n);
 	j.half = (dev::HalfYuvJob *)(j.l1 + (size_t)n * nch);
 	j.halfp = (dev::HalfPackedJob *)(j.half + n);
+	j.bayer = (dev::InvBayerJob *)(j.halfp + n);
 	return j;
 }
-size_t dec_jobs_bytes(int n, int nch) { return 3 * (size_t)n * nch * sizeof(dev::InvPlaneJob) + (size_t)n * sizeof(dev::InvYuvJob) + (size_t)n * sizeof(dev::HalfYuvJob) + (size_t)n * sizeof(dev::HalfPackedJob); }
+size_t dec_jobs_bytes(int n, int nch) { return 3 * (size_t)n * nch * sizeof(dev::InvPlaneJob) + (size_t)n * sizeof(dev::InvYuvJob) + (size_t)n * sizeof(dev::HalfYuvJob) + (size_t)n * sizeof(dev::HalfPackedJob) + (size_t)n * sizeof(dev::InvBayerJob); }
 
 // Word of component plane c inside an interleaved 16-bit pixel: planes are G, R, B(, A) (frame.c:6128-6157, convert.c:6750-6752),
 // RG48 pixels are R, G, B; b64a pixels are A, R, G, B (frame.c:6676-6683).
@@ -1135,7 +1136,11 @@ int DecodeBatch::prepare(const FramePlan &plan, int nframes, int out_kind, bool 
 		switch (r.jobs) {                                // the one table the last launch reads
 		case OutJobs::HalfYuv: fill_half_yuv_job(j.half[i], l1, r, out_rows_, plan.color_matrix, out, job_pitch); break;
 		case OutJobs::HalfPacked: fill_half_packed_job(j.halfp[i], l1, r, onch, plan.precision, out_rows_, i, out, job_pitch); break;
-		case OutJobs::Planes16: fill_planes16_jobs(&j.l1[(size_t)i * onch], l1, r, nch, onch, plan.precision, plan.display_height, i, out, job_pitch); break;
+		case OutJobs::Planes16:
+			fill_planes16_jobs(&j.l1[(size_t)i * onch], l1, r, nch, onch, plan.precision, plan.display_height, i, out, job_pitch);
+			// (BYR4: where the fused last level writes the mosaic itself, past the scratch frame)
+			if (byr4) { j.bayer[i].out = (uint16_t *)(d_out_ + frame_bytes_ * i); j.bayer[i].out_pitch = out_pitch_ / 2; j.bayer[i].curve = d_restore_; }
+			break;
 		case OutJobs::Yuv: {
 			fill_inv_yuv_job(j.yuv[i], l1, r, plan.precision, plan.display_height, plan.color_matrix, i, out, job_pitch);
 			// (block lists: prepare_entropy() knows the mask buffer)
@@ -1183,10 +1188,10 @@ int DecodeBatch::upload_coeffs()
 
 // The last level of the inverse transform: every kernel launch_inverse() can pick, and the name a profiler shows it under (level_kernel()).  Where a strip kernel and
 // an LDS-tiled one serve the same output they produce the same bytes.
-enum class InvL1 { Refused, HalfRgb24, HalfRgb, HalfYu64, HalfPacked16, HalfYuv422, FrameRows16, FrameRows16Col, Packed16Strip, Yuv422Rgb32, Rgb10, Packed16,
+enum class InvL1 { Refused, HalfRgb24, HalfRgb, HalfYu64, HalfPacked16, HalfYuv422, FrameRows16, FrameRows16Col, Packed16Strip, BayerStrip, Yuv422Rgb32, Rgb10, Packed16,
                    FrameYuv422StripBlocks, FrameYuv422Strip, FrameYuv422Quad, FrameYuv422, Yuv422StripBlocks, Yuv422Strip, Yuv422 };
 static const char *const kInvL1Name[] = {"refused", "k_half_rgb24", "k_half_rgb", "k_half_yu64", "k_half_packed16", "k_half_yuv422", "k_inv_frame_yuv422_rows16", "k_inv_frame_yuv422_rows16_col",
-                                         "k_inv_packed16_strip", "k_inv_yuv422_rgb32", "k_inv_rgb10", "k_inv_packed16", "k_inv_frame_yuv422_strip_blocks", "k_inv_frame_yuv422_strip",
+                                         "k_inv_packed16_strip", "k_inv_bayer_strip", "k_inv_yuv422_rgb32", "k_inv_rgb10", "k_inv_packed16", "k_inv_frame_yuv422_strip_blocks", "k_inv_frame_yuv422_strip",
                                          "k_inv_frame_yuv422_quad", "k_inv_frame_yuv422", "k_inv_yuv422_strip_blocks", "k_inv_yuv422_strip", "k_inv_yuv422"};
 static const char *const kInvPlaneName[2] = {"k_inv_plane", "k_inv_plane_strip"};      // levels 3 and 2: [planes_as_strips()]
 static_assert(sizeof(kInvL1Name) / sizeof(*kInvL1Name) == (size_t)InvL1::Yuv422 + 1, "one name per last-level kernel");
@@ -1215,6 +1220,10 @@ InverseRoute DecodeBatch::inverse_route() const
 	for (int lv = 1; lv < 3; lv++) r.strip_planes[lv - 1] = planes_as_strips(plan_, lv, act);
 	// the register-strip kernels pay from 12 frames of 1080p on (CFHD_AMD_INVERSE=tile / strip, for A/B runs: never / wherever the geometry allows)
 	const bool strips = forced != 1 && (forced != 0 || frames_1080p_equivalent(plan_, act) >= 12.0);
+	// ... the fused last level of BYR4 from 4 on: measured at 2, 4, 12 and 32 mosaics of 3840 x 2160 (one 1080p frame's worth of quads each), the pair wins beyond
+	// the spread at 2 (0.079 against 0.098 ms: a strip launch has a floor of 0.10 ms) and the fused kernel from 4 on (0.100 against 0.130, 0.156 against 0.379,
+	// 0.324 against 0.982 ms)
+	const bool bayer_strips = forced != 1 && (forced != 0 || frames_1080p_equivalent(plan_, act) >= 4.0);
 	const int pitch[3] = { b.pitch, plan_.ch[1].band[0][0].pitch, plan_.ch[2].band[0][0].pitch };
 	auto rows_aligned = [&] { return every_frame(n_, [&](int i) { return !((uintptr_t)j.yuv[i].out & 15) && !(j.yuv[i].out_pitch & 15); }); };      // 16-byte stores
 	auto quads = [&] { return frame_quads_fit(forced, b.width, pitch) && rows_aligned(); };
@@ -1233,6 +1242,12 @@ InverseRoute DecodeBatch::inverse_route() const
 			const dev::InvPlaneJob &p = j.l1[(size_t)i * dec_out_channels(work, plan_)];
 			const uintptr_t frame = (uintptr_t)((const uint16_t *)p.out - packed_word_of_channel(work, 0));
 			return !(frame & 15) && !((p.out_pitch * 2) & 15) && !(p.band_pitch & 3); })) r.l1 = InvL1::Packed16Strip;
+		// BYR4 output of a batch that opted in (set_bayer_strips: the queues' Bayer batches, never a handle): the mosaic straight from the last level, no scratch
+		// frame and no k_bayer_to_byr4 -- band rows of whole 8-byte words, mosaic rows in 16-byte words
+		else if (bayer_strips && bayer_strips_ && route_.convert == OutConvert::Byr4 && b.width % 4 == 0 && every_frame(n_, [&](int i) {
+			const dev::InvPlaneJob *p = &j.l1[(size_t)i * nch];
+			for (int c = 0; c < nch; c++) if ((p[c].band_pitch & 3) || p[c].width != b.width || p[c].height != b.height) return false;
+			return nch == 4 && !((uintptr_t)j.bayer[i].out & 15) && !((j.bayer[i].out_pitch * 2) & 15); })) r.l1 = InvL1::BayerStrip;
 		else r.l1 = dec_rgb10(work) ? InvL1::Rgb10 : InvL1::Packed16;
 		break;
 	case OutJobs::Yuv:
@@ -1254,6 +1269,7 @@ struct LastLevel {
 	int band_w, band_h, out_rows, frames; bool interlaced;      // the luma band of level 1; the rows of a half-resolution output; grid z
 	const dev::InvYuvJob *yuv; const dev::InvPlaneJob *l1; const dev::HalfYuvJob *half; const dev::HalfPackedJob *halfp;      // job tables (null: the caller has none)
 	int out_channels, words_per_position;                       // of the packed 16-bit outputs
+	const dev::InvBayerJob *bayer;                              // beside l1 for k_inv_bayer_strip (null: the caller has none)
 };
 static int launch_last_level(InvL1 k, const LastLevel &g, uint32_t dither_seed, hipStream_t st)
 {
@@ -1279,6 +1295,12 @@ static int launch_last_level(InvL1 k, const LastLevel &g, uint32_t dither_seed, 
 		else dev::k_inv_packed16_strip<3><<<(waves + 3) / 4, dev::NTHREADS, 0, st>>>(g.l1, g.frames, nseg, nstrips);
 		break;
 	}
+	case InvL1::BayerStrip: {
+		if (!g.l1 || !g.bayer) return unserved();
+		const int nseg = (g.band_w / 4 + dev::PSTEP - 1) / dev::PSTEP, nstrips = (g.band_h + dev::QSR - 1) / dev::QSR, waves = g.frames * nseg * nstrips;
+		dev::k_inv_bayer_strip<<<(waves + 3) / 4, dev::NTHREADS, 0, st>>>(g.l1, g.bayer, g.frames, nseg, nstrips);
+		break;
+	}
 	case InvL1::Yuv422Rgb32: if (!g.yuv) return unserved(); dev::k_inv_yuv422_rgb32<<<tiles, dev::NTHREADS, 0, st>>>(g.yuv); break;
 	case InvL1::Rgb10: if (!g.l1) return unserved(); dev::k_inv_rgb10<<<tiles, dev::NTHREADS, 0, st>>>(g.l1); break;
 	case InvL1::Packed16: if (!g.l1) return unserved(); dev::k_inv_packed16<<<tiles, dev::NTHREADS, 0, st>>>(g.l1, g.out_channels, g.words_per_position, dither_seed); break;
@@ -1296,6 +1318,7 @@ static int launch_last_level(InvL1 k, const LastLevel &g, uint32_t dither_seed, 
 const char *DecodeBatch::level_kernel(int level) const
 {
 	const InverseRoute r = inverse_route();
+	if (level == 0 && route_.convert == OutConvert::Byr4 && r.l1 == InvL1::Packed16) return "k_inv_packed16+k_bayer_to_byr4";      // (the pair behind BYR4; the fused kernel carries its own name)
 	return level > 0 ? kInvPlaneName[r.strip_planes[level - 1]] : kInvL1Name[(int)r.l1];
 }
 
@@ -1352,9 +1375,10 @@ int DecodeBatch::launch_inverse(uint32_t dither_seed)
 	}
 	const BandDesc &b = plan_.ch[0].band[0][0];
 	const int onch = dec_out_channels(route_.work, plan_);
-	rc = launch_last_level(r.l1, { b.width, b.height, out_rows_, act, interlaced_, j.yuv, j.l1, j.half, j.halfp, onch, dec_words_per_position(route_.work, onch) }, dither_seed, st);
+	rc = launch_last_level(r.l1, { b.width, b.height, out_rows_, act, interlaced_, j.yuv, j.l1, j.half, j.halfp, onch, dec_words_per_position(route_.work, onch), j.bayer }, dither_seed, st);
 	if (rc) return rc;
-	launch_convert(route_, d_tmp_, tmp_pitch_, tmp_frame_bytes_, d_out_, out_pitch_, frame_bytes_, half_ ? plan_.width / 2 : plan_.width, half_ ? plan_.display_height / 2 : plan_.display_height,
+	if (r.l1 != InvL1::BayerStrip)                      // (the fused last level of BYR4 wrote the mosaic itself)
+		launch_convert(route_, d_tmp_, tmp_pitch_, tmp_frame_bytes_, d_out_, out_pitch_, frame_bytes_, half_ ? plan_.width / 2 : plan_.width, half_ ? plan_.display_height / 2 : plan_.display_height,
 	               0, act, plan_.color_matrix, dither_seed, d_restore_, st);
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipEventRecord((hipEvent_t)ev1_, st));

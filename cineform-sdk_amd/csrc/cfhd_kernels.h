@@ -2220,6 +2220,130 @@ __global__ void __launch_bounds__(NTHREADS) k_inv_packed16_strip(const InvPlaneJ
 }
 
 // =============================================================================================
+// k_inv_bayer_strip: the last level of a Bayer sample written as the BYR4 mosaic in one pass -- k_inv_packed16_strip<4> with the quad recombination and the
+// linear-restore table of k_bayer_to_byr4 in place of the packed store, the mirror image of k_fwd_bayer_strip.  One lane = 4 band columns of all four component
+// planes (8-byte loads of LL, LH, HL, HH; the three-row window in registers; neighbours by __shfl) -> per band row 8 photosite quads of two quad rows = 16
+// photosites on each of 4 mosaic rows, two 16-byte words a row.  Between the synthesis and the store exactly what the pair does: to16() with the tail-column
+// rule, the planes as the words R-G, G, B-G, G1-G2 of a quad, k_bayer_to_byr4's recombination and clamps, table[x >> 2], red-green phase.  The 32 KB table sits in
+// LDS, filled once per workgroup (as the encode curve of k_fwd_bayer_strip).  The scratch frame of four words per quad (8 bytes out, 8 back in) never exists:
+// 8 B of coefficients in and 8 B of mosaic out per quad.  Same bytes as k_inv_packed16 + k_bayer_to_byr4 (tested against them), which stay for other geometries,
+// small launches and the C ABI's handles.  Geometry served: band width % 4 == 0, band rows of whole 8-byte words, mosaic rows 16-byte aligned.
+// =============================================================================================
+struct InvBayerJob {                        // k_inv_bayer_strip, beside the frame's four InvPlaneJob (planes G, R-G, B-G, G1-G2: bands, geometry, precision, display height in quad rows)
+	uint16_t *out; int out_pitch;           // the mosaic; words per mosaic row
+	const uint16_t *curve;                  // the linear-restore table over 14-bit input (build_bayer_linear_restore_curve)
+};
+__device__ __forceinline__ uint32_t byr4_clamp16(int v) { return (uint32_t)(v < 0 ? 0 : (v > 0xffff ? 0xffff : v)); }
+
+__global__ void __launch_bounds__(NTHREADS) k_inv_bayer_strip(const InvPlaneJob *jobs, const InvBayerJob *bayer, int nframes, int nseg, int nstrips)
+{
+	__shared__ uint16_t s_curve[1 << 14];
+	{
+		const uint4 *src = (const uint4 *)bayer[0].curve;     // (one table per batch: every frame's job points at it)
+		uint4 *dst = (uint4 *)s_curve;
+		for (int i = threadIdx.x; i < (1 << 14) * 2 / 16; i += NTHREADS) dst[i] = src[i];
+	}
+	__syncthreads();
+	const int lane = threadIdx.x & 63, gwave = (int)blockIdx.x * (NTHREADS / 64) + wave_uniform((int)(threadIdx.x >> 6));
+	const int seg = gwave % nseg, strip = (gwave / nseg) % nstrips, frame = gwave / (nseg * nstrips);
+	if (frame >= nframes) return;                         // whole wave (behind the only barrier)
+	const InvPlaneJob *job = jobs + (size_t)frame * 4;
+	const int w = job->width, h = job->height, nblk = w / 4;
+	const int b = seg * PSTEP - 1 + lane;
+	const bool stores = b >= 0 && b < nblk && lane >= 1 && lane <= PSTEP;
+	const int blk = b < 0 ? 0 : (b >= nblk ? nblk - 1 : b);
+	const bool first = blk == 0, last = blk == nblk - 1;
+	const int pitch = job->band_pitch, precision = job->precision, dh = job->display_height, out_pitch = bayer[frame].out_pitch;
+	uint16_t *const mosaic = bayer[frame].out + (size_t)blk * 16;      // the lane's 16 photosites of every mosaic row
+	const int16_t *band[4][4];
+#pragma unroll
+	for (int c = 0; c < 4; c++) {
+#pragma unroll
+		for (int k = 0; k < 4; k++) band[c][k] = job[c].band[k];      // (wave-uniform: scalar registers)
+	}
+	const int tail0 = w - (w & 7) - 9;                    // band columns from here on: the reference's scalar loop (to16)
+	const int r0 = strip * QSR, nrows = h - r0 < QSR ? h - r0 : QSR;
+	const uint32_t col_off = (uint32_t)blk * 8u;          // bytes into a band row
+	int j = inv_window_first_row(r0, h);
+	cfhd_u2 ll[4][3], lh[4][3], hl[4], hh[4];
+#pragma unroll
+	for (int c = 0; c < 4; c++) {
+#pragma unroll
+		for (int k = 0; k < 3; k++) { const uint32_t at = (uint32_t)(j + k) * (uint32_t)pitch * 2u + col_off; ll[c][k] = ldg64_at(band[c][0], at); lh[c][k] = ldg64_at(band[c][1], at); }
+		const uint32_t at = (uint32_t)r0 * (uint32_t)pitch * 2u + col_off;
+		hl[c] = ldg64_at(band[c][2], at); hh[c] = ldg64_at(band[c][3], at);
+	}
+	for (int s = 0; s < nrows; s++) {
+		const int r = r0 + s;
+		const bool more = s + 1 < nrows;
+		const int jn = more ? inv_window_first_row(r + 1, h) : j;
+		const bool advance = jn != j;
+		// the next band row's loads are in flight while this one is synthesised
+		cfhd_u2 nll[4], nlh[4], nhl[4], nhh[4];
+#pragma unroll
+		for (int c = 0; c < 4; c++) {
+			nll[c] = ll[c][2]; nlh[c] = lh[c][2]; nhl[c] = hl[c]; nhh[c] = hh[c];
+			if (advance) { const uint32_t at = (uint32_t)(jn + 2) * (uint32_t)pitch * 2u + col_off; nll[c] = ldg64_at(band[c][0], at); nlh[c] = ldg64_at(band[c][1], at); }
+			if (more) { const uint32_t at = (uint32_t)(r + 1) * (uint32_t)pitch * 2u + col_off; nhl[c] = ldg64_at(band[c][2], at); nhh[c] = ldg64_at(band[c][3], at); }
+		}
+		const int pos = r == 0 ? 0 : (r == h - 1 ? 2 : 1);
+		uint32_t Lv[4][2][2], Hv[4][2][2];                  // [plane][row parity][column pair]
+#pragma unroll
+		for (int c = 0; c < 4; c++) {
+			inv_vert_pk(ll[c][0].x, ll[c][1].x, ll[c][2].x, hl[c].x, pos, Lv[c][0][0], Lv[c][1][0]);
+			inv_vert_pk(ll[c][0].y, ll[c][1].y, ll[c][2].y, hl[c].y, pos, Lv[c][0][1], Lv[c][1][1]);
+			inv_vert_pk(lh[c][0].x, lh[c][1].x, lh[c][2].x, hh[c].x, pos, Hv[c][0][0], Hv[c][1][0]);
+			inv_vert_pk(lh[c][0].y, lh[c][1].y, lh[c][2].y, hh[c].y, pos, Hv[c][0][1], Hv[c][1][1]);
+		}
+#pragma unroll
+		for (int par = 0; par < 2; par++) {
+			uint32_t v[4][8];                                 // [plane][quad of the lane]: the 16-bit words of the pair's scratch frame
+#pragma unroll
+			for (int c = 0; c < 4; c++) {
+				const uint32_t L0 = Lv[c][par][0], L1 = Lv[c][par][1], H0 = Hv[c][par][0], H1 = Hv[c][par][1];
+				const uint32_t prev = __shfl(L1, lane - 1), next = __shfl(L0, lane + 1);
+				uint32_t ev[2], od[2];
+				inv_horiz_pk((prev >> 16) | (L0 << 16), L0, (L0 >> 16) | (L1 << 16), H0, ev[0], od[0]);
+				inv_horiz_pk((L0 >> 16) | (L1 << 16), L1, (L1 >> 16) | (next << 16), H1, ev[1], od[1]);
+				int e[4] = { lo16(ev[0]), hi16(ev[0]), lo16(ev[1]), hi16(ev[1]) }, o[4] = { lo16(od[0]), hi16(od[0]), lo16(od[1]), hi16(od[1]) };     // columns 0..3 before the >>1
+				if (first) { const int l[6] = { 0, 0, lo16(L0), hi16(L0), lo16(L1), hi16(L1) }; inv_horiz_border(l, 2, lo16(H0), 0, e[0], o[0]); }
+				if (last) { const int l[6] = { lo16(L0), hi16(L0), lo16(L1), hi16(L1), 0, 0 }; inv_horiz_border(l, 3, hi16(H1), 2, e[3], o[3]); }
+#pragma unroll
+				for (int k = 0; k < 4; k++) {
+					const bool tail = 4 * blk + k >= tail0;
+					v[c][2 * k] = to16(e[k], precision, tail); v[c][2 * k + 1] = to16(o[k], precision, tail);
+				}
+			}
+			// planes G, R-G, B-G, G1-G2 (the pair's words 1, 0, 2, 3) -> rows r g1 / g2 b of every quad, through the table
+			uint32_t top[8], bot[8];
+#pragma unroll
+			for (int q = 0; q < 8; q++) {
+				const int g = (int)v[0][q], gd = (int)v[3][q] - 32768;
+				const uint32_t rr = byr4_clamp16((((int)v[1][q] - 32768) << 1) + g), bb = byr4_clamp16((((int)v[2][q] - 32768) << 1) + g);
+				const uint32_t g1 = byr4_clamp16(g + gd), g2 = byr4_clamp16(g - gd);
+				top[q] = (uint32_t)s_curve[rr >> 2] | ((uint32_t)s_curve[g1 >> 2] << 16);
+				bot[q] = (uint32_t)s_curve[g2 >> 2] | ((uint32_t)s_curve[bb >> 2] << 16);
+			}
+			const int orow = 2 * r + par;                     // quad row: mosaic rows 2 orow and 2 orow + 1
+			if (stores && orow < dh) {
+				uint4 *d0 = (uint4 *)(mosaic + (size_t)(2 * orow) * out_pitch), *d1 = (uint4 *)(mosaic + (size_t)(2 * orow + 1) * out_pitch);
+#pragma unroll
+				for (int i = 0; i < 2; i++) {
+					uint4 t; t.x = top[4 * i]; t.y = top[4 * i + 1]; t.z = top[4 * i + 2]; t.w = top[4 * i + 3]; d0[i] = t;
+					uint4 u; u.x = bot[4 * i]; u.y = bot[4 * i + 1]; u.z = bot[4 * i + 2]; u.w = bot[4 * i + 3]; d1[i] = u;
+				}
+			}
+		}
+#pragma unroll
+		for (int c = 0; c < 4; c++) {
+			if (advance) { ll[c][0] = ll[c][1]; ll[c][1] = ll[c][2]; ll[c][2] = nll[c]; lh[c][0] = lh[c][1]; lh[c][1] = lh[c][2]; lh[c][2] = nlh[c]; }
+			hl[c] = nhl[c]; hh[c] = nhh[c];
+		}
+		if (advance) j = jn;
+	}
+}
+
+// =============================================================================================
 // Half-resolution decode of 4:2:2 samples (CFHD_DECODED_RESOLUTION_HALF): the reference does not run the last wavelet level at all
 // and shows the level-1 lowpass planes, four times the 10-bit sample, as the picture: decoder.c:14124 -> :22883 CopyLowpass16sToBuffer
 // -> frame.c:11742 ConvertLowpass16s10bitToYUV, scalar loop: SATURATE_8U(value >> 4), bytes Y U Y V from the planes Y, U, V (channel

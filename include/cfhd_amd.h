@@ -264,6 +264,17 @@ cfhd_amd_batch *cfhd_amd_batch_create_stream(int width, int height, uint32_t pix
  * NULL, with the reason in cfhd_amd_last_error(): whatever cfhd_amd_batch_create_groups refuses for reasons other than moving tables; an odd nframes, or nframes < 2;
  * CFHD_AMD_ENTROPY=host; for words whose tables move, CFHD_AMD_HANDOFF=host. */
 cfhd_amd_batch *cfhd_amd_batch_create_group_stream(int width, int height, uint32_t pixel_format, uint32_t encoding_flags, int quality, int nframes, int nthreads, int mode);
+/* Bayer mosaics on the frame queue, both ways.  pixel_format BYR4 or BYR5 (the encoded format is Bayer, implied), the other arguments as for
+ * cfhd_amd_batch_create_ex.  mode 1 is exactly cfhd_amd_batch_create_ex's batch: the same samples, the same launches.  mode 0 -- BYR4 only -- adds the decode back to
+ * the BYR4 mosaic: picture i is what CFHD_DecodeSample gives for get_sample(i) with output BYR4 at full resolution, byte for byte (16-bit photosites, no dither).
+ * Passes of 4 frames of 1080p-equivalent work and more (a 3840 x 2160 mosaic is one) write the mosaic straight from the last wavelet level (k_inv_bayer_strip);
+ * smaller ones and CFHD_AMD_INVERSE=tile run the handle's pair k_inv_packed16 + k_bayer_to_byr4 -- the same bytes.  Every other cfhd_amd_batch_* entry point is shared and keeps its meaning per frame index (upload,
+ * upload_device, roundtrip, submit, submit_host, wait, get_sample, download_output: the mosaic, width x height photosites in rows of 2 * width bytes; kernel_ms /
+ * kernel_name 3..5 and 12..14 as for every round-trip batch, 3 naming the last-level kernel that ran).
+ * NULL, with the reason in cfhd_amd_last_error(): an input that is no Bayer mosaic; BYR5 at mode 0 (no decoder output exists); a quality word whose tables follow
+ * the sample sizes (as cfhd_amd_batch_create_ex: a Bayer stream with rate feedback is not built); whatever CFHD_PrepareToEncode or cfhd_amd_batch_create_ex refuses
+ * otherwise.  cfhd_amd_batch_create_ex and cfhd_amd_batch_create_stream keep refusing mode 0 for Bayer inputs, for callers that probe with them. */
+cfhd_amd_batch *cfhd_amd_batch_create_bayer(int width, int height, uint32_t pixel_format, uint32_t encoding_flags, int quality, int nframes, int nthreads, int mode);
 /* The last completed pass of a stream batch: out[0] encode rounds (>= 1), out[1] frames coded over all rounds (>= nframes; a group stream: even), out[2] frames whose
  * tables differ from those of the frame in front (frame 0: from the last frame of the pass before; in pass 0 it counts 0) -- a group stream: groups, likewise.  0, or
  * -1 for a batch not made by cfhd_amd_batch_create_stream / cfhd_amd_batch_create_group_stream, before its first pass has completed, and between submit and wait. */
@@ -280,7 +291,7 @@ int  cfhd_amd_quantizer_is_static(int width, int height, uint32_t pixel_format, 
 /* ---------------- the decode queue: batches of samples from any encoder, parsed and decoded on the GPU (cfhd_decode_queue.hip) ----------------
  * What cfhd_amd_batch_* is to a caller who has just encoded, for a caller who holds a clip: nsamples samples a pass, one launch per stage for all of them, no host
  * tag walk and no device wait per picture.  Progressive and interlaced 4:2:2, RGB 4:4:4 and RGBA 4:4:4:4 samples, to every output and resolution CFHD_DecodeSample
- * serves for them; streams of two-frame groups through cfhd_amd_decode_batch_create_groups below; Bayer samples stay with CFHD_DecodeSample. */
+ * serves for them; streams of two-frame groups through cfhd_amd_decode_batch_create_groups, Bayer samples (to BYR4) through cfhd_amd_decode_batch_create_bayer below. */
 typedef struct cfhd_amd_decode_batch cfhd_amd_decode_batch;
 /* Prepares from one complete intra sample, as CFHD_PrepareToDecode prepares a handle: geometry, encoded format, precision, scan and colour space are the first
  * sample's, output_format / decoded_resolution those of CFHD_PrepareToDecode.  NULL, with the reason in cfhd_amd_last_error(), for whatever CFHD_PrepareToDecode or
@@ -308,6 +319,19 @@ cfhd_amd_decode_batch *cfhd_amd_decode_batch_create(const void *first_sample, si
  * subband 7 of the groups from 8-bit RGB sources -- included), 3 k_dec_lowpass, 4 / 5 / 6 the three inverse stages in launch order (the last with the output
  * conversion), 7 k_dec_blank; kernel_ms alone also answers 8: k_dec_band_two_pass by itself. */
 cfhd_amd_decode_batch *cfhd_amd_decode_batch_create_groups(const void *first_group_sample, size_t first_size, uint32_t output_format, int decoded_resolution, int ngroups);
+/* The same batch for Bayer intra samples (CineForm RAW, from any encoder), decoded to what CFHD_DecodeSample serves for them: the BYR4 mosaic at full resolution,
+ * no demosaic.  Prepares from one complete Bayer intra sample with the gates of cfhd_amd_decode_batch_create (CFHD_PrepareToDecode, then the first sample once through
+ * CFHD_DecodeSample on the batch's own handle); cfhd_amd_decode_batch_create itself keeps refusing Bayer samples, for callers that probe with it.  Every other entry
+ * point is shared and keeps its meaning: cfhd_amd_decode_batch_geometry answers the mosaic -- twice the sample's (component plane) width and rows, row_bytes =
+ * 2 * width --; submit_host, submit_device, wait and download_output work as for any batch; status[i] is what CFHD_DecodeSample returns for sample i, the picture of
+ * a sample that failed is zero, and the slow path inside wait is the handle's; every picture equals the handle's byte for byte (16-bit photosites, no dither).
+ * cfhd_amd_decode_batch_set_device_pictures takes CFHD_AMD_PICTURES_PACKED; the planar layouts stay refused (the output is not RG48).
+ * cfhd_amd_decode_batch_kernel_ms / _kernel_name: indices 0 .. 9 keep their meaning; 6 names the last level that ran -- "k_inv_bayer_strip", the mosaic written
+ * straight from the last wavelet level (passes of 4 frames of 1080p-equivalent work and more -- a 3840 x 2160 mosaic is one --, or CFHD_AMD_INVERSE=strip), or
+ * "k_inv_packed16+k_bayer_to_byr4", the handle's pair (smaller passes, or CFHD_AMD_INVERSE=tile); both give the same bytes.
+ * NULL, with the reason in cfhd_amd_last_error(): a first sample that is not a Bayer intra sample; an output other than BYR4; half or quarter resolution;
+ * CFHD_AMD_ENTROPY=host; nsamples < 1 or 4 x nsamples > 65 535; whatever CFHD_PrepareToDecode or CFHD_DecodeSample refuses for that sample. */
+cfhd_amd_decode_batch *cfhd_amd_decode_batch_create_bayer(const void *first_sample, size_t first_size, uint32_t output_format, int decoded_resolution, int nsamples);
 /* Waits for a pass in flight, then frees the batch. */
 void cfhd_amd_decode_batch_destroy(cfhd_amd_decode_batch *batch);
 /* One decoded picture: width x height pixels in rows of row_bytes bytes (any of the three may be NULL).  0, or -1. */
