@@ -136,6 +136,14 @@ int allocate(cfhd_amd_decode_batch *b)
 // k_dec_deliver over pictures [first, first + count) of the batch's own buffer, queued on the batch's stream: into the caller's device memory, in the layout it asked for.
 int launch_deliver(cfhd_amd_decode_batch *b, int first, int count)
 {
+	if (dev::deliver_is_bayer(b->dev_out_layout)) {      // the BYR4 mosaics of a Bayer batch as four planes (set_device_pictures checked the geometry the kernel assumes)
+		const int quad_rows = b->picture_rows() / 2;
+		dev::k_dec_deliver_bayer<<<dim3(dev::dec_deliver_pieces(quad_rows), (unsigned)count), dev::DEC_DELIVER_THREADS, 0, (hipStream_t)b->stream()>>>(
+			b->device_pictures() + b->picture_bytes() * (size_t)first, b->picture_bytes(), quad_rows, b->picture_width() / 2,
+			b->dev_out + b->dev_out_stride * (size_t)first, b->dev_out_stride, b->dev_out_pitch, dev::deliver_bayer_element(b->dev_out_layout));
+		HIPCHK(hipGetLastError());
+		return 0;
+	}
 	dev::k_dec_deliver<<<dim3(dev::dec_deliver_pieces(b->picture_rows()), (unsigned)count), dev::DEC_DELIVER_THREADS, 0, (hipStream_t)b->stream()>>>(
 		b->device_pictures() + b->picture_bytes() * (size_t)first, b->picture_bytes(), b->picture_pitch(), b->picture_rows(), b->picture_width(),
 		b->dev_out + b->dev_out_stride * (size_t)first, b->dev_out_stride, b->dev_out_pitch, b->dev_out_layout);
@@ -398,14 +406,21 @@ int cfhd_amd_decode_batch_set_device_pictures(cfhd_amd_decode_batch *b, void *d_
 	if (!b) { refuse("decode queue: no batch"); return -1; }
 	if (b->in_flight) { refuse("decode queue: device pictures are set between passes, not while one is in flight"); return -1; }
 	if (!d_pictures) { b->dev_out = nullptr; return 0; }
-	if (layout < CFHD_AMD_PICTURES_PACKED || layout > CFHD_AMD_PICTURES_PLANAR_F32) { refuse("decode queue: unknown layout of the device pictures"); return -1; }
-	const bool planar = layout != CFHD_AMD_PICTURES_PACKED;
+	// (the BAYER_* layouts exist for the BYR4 mosaics of cfhd_amd_decode_batch_create_bayer's batches alone: to every other batch they are unknown)
+	const bool bayer = dev::deliver_is_bayer(layout) && !b->groups && b->st.out_kind == PIX_BYR4;
+	if (!bayer && (layout < CFHD_AMD_PICTURES_PACKED || layout > CFHD_AMD_PICTURES_PLANAR_F32)) { refuse("decode queue: unknown layout of the device pictures"); return -1; }
+	const bool planar = !bayer && layout != CFHD_AMD_PICTURES_PACKED;
 	if (planar && b->st.out_kind != PIX_RG48) { refuse("decode queue: the planar layouts serve batches whose output is RG48"); return -1; }
 	if (((uintptr_t)d_pictures | picture_stride | (size_t)(unsigned)picture_pitch) & 15) { refuse("decode queue: the device pictures' pointer, stride and pitch are multiples of 16"); return -1; }
-	const int rows = b->picture_rows();
-	const long long row_bytes = planar ? (long long)b->picture_width() * (layout == CFHD_AMD_PICTURES_PLANAR_F32 ? 4 : 2) : b->picture_pitch();
+	// the rows and planes a picture has in the layout: the mosaic's four planes are half as high and half as wide
+	const int rows = bayer ? b->picture_rows() / 2 : b->picture_rows(), planes = bayer ? 4 : (planar ? 3 : 1);
+	const int elt = layout == CFHD_AMD_PICTURES_PLANAR_F32 || layout == CFHD_AMD_PICTURES_BAYER_F32 ? 4 : 2;
+	const long long row_bytes = bayer ? (long long)(b->picture_width() / 2) * elt : (planar ? (long long)b->picture_width() * elt : b->picture_pitch());
+	// what k_dec_deliver_bayer assumes of the batch's own pictures: whole quads, plane rows of whole groups of eight, mosaic rows back to back on 16-byte boundaries
+	if (bayer && ((b->picture_width() & 15) || (b->picture_rows() & 1) || b->picture_pitch() != 2 * b->picture_width() || b->picture_bytes() != (size_t)b->picture_pitch() * (size_t)b->picture_rows() ||
+	              ((uintptr_t)b->device_pictures() & 15) || b->n > 65535 /* blockIdx.y */)) { refuse("decode queue: mosaics the Bayer deliver kernel does not take"); return -1; }
 	if (picture_pitch < row_bytes) { refuse("decode queue: the device pictures' pitch is below the row bytes of the layout"); return -1; }
-	if (picture_stride < (size_t)picture_pitch * ((size_t)(planar ? 3 : 1) * rows - 1) + (size_t)row_bytes) { refuse("decode queue: the device pictures' stride is below what one picture occupies"); return -1; }
+	if (picture_stride < (size_t)picture_pitch * ((size_t)planes * rows - 1) + (size_t)row_bytes) { refuse("decode queue: the device pictures' stride is below what one picture occupies"); return -1; }
 	b->dev_out = (uint8_t *)d_pictures; b->dev_out_stride = picture_stride; b->dev_out_pitch = picture_pitch; b->dev_out_layout = layout;
 	return 0;
 }
@@ -581,7 +596,7 @@ float cfhd_amd_decode_batch_kernel_ms(cfhd_amd_decode_batch *b, int which)
 
 const char *cfhd_amd_decode_batch_kernel_name(cfhd_amd_decode_batch *b, int which)
 {
-	if (b && !b->in_flight && which == 9) return "k_dec_deliver";
+	if (b && !b->in_flight && which == 9) return b->dev_out && dev::deliver_is_bayer(b->dev_out_layout) ? "k_dec_deliver_bayer" : "k_dec_deliver";
 	if (!b || b->in_flight || which < 0 || which > 7) return "";
 	static const char *const fixed[4] = { "k_dec_ingest", "k_dec_parse", "k_dec_plan+k_dec_index+k_dec_chain+k_dec_tiles", "k_dec_lowpass" };
 	if (which < 4 && !(b->groups && which)) return fixed[which];

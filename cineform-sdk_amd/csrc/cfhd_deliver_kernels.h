@@ -1,6 +1,7 @@
 // cfhd_deliver_kernels.h -- k_dec_deliver, the last kernel of a decode-queue pass that delivers into the caller's device memory (cfhd_amd_decode_batch_set_device_pictures,
 // cfhd_decode_queue.hip): behind k_dec_blank, the pictures of the pass out of the batch's own tightly packed buffer into memory the caller owns -- as the packed
-// pictures they are, at the caller's pitch, or, for RG48, as three planes R, G, B of u16, f16 or f32 elements (a torch tensor N x 3 x H x W).
+// pictures they are, at the caller's pitch, or, for RG48, as three planes R, G, B of u16, f16 or f32 elements (a torch tensor N x 3 x H x W) -- and k_dec_deliver_bayer,
+// which takes its place for the BYR4 mosaics of a Bayer batch delivered as four planes, one per position of the 2 x 2 quad (N x 4 x H/2 x W/2).
 #pragma once
 #include <stdint.h>
 #include <stddef.h>
@@ -11,7 +12,10 @@ namespace cfhd {
 namespace dev {
 
 // (the values of CFHD_AMD_PICTURES_* in include/cfhd_amd.h)
-enum { DELIVER_PACKED = 0, DELIVER_PLANAR_U16 = 1, DELIVER_PLANAR_F16 = 2, DELIVER_PLANAR_F32 = 3 };
+enum { DELIVER_PACKED = 0, DELIVER_PLANAR_U16 = 1, DELIVER_PLANAR_F16 = 2, DELIVER_PLANAR_F32 = 3, DELIVER_BAYER_U16 = 4, DELIVER_BAYER_F16 = 5, DELIVER_BAYER_F32 = 6 };
+inline bool deliver_is_bayer(int layout) { return layout >= DELIVER_BAYER_U16 && layout <= DELIVER_BAYER_F32; }
+// the element type of a BAYER_* layout as the PLANAR_* value the element rules below are written for
+inline int deliver_bayer_element(int layout) { return layout - DELIVER_BAYER_U16 + DELIVER_PLANAR_U16; }
 
 // The element rules of the planar layouts for the RG48 word w.  F32: (float)w * (1.0f / 65535.0f), one IEEE single multiply.  F16: that value rounded to nearest-even
 // to binary16, subnormals kept (w = 1 .. 3 land there: 1 / 65535 < 2^-14) -- under device compilation the hardware's convert (v_cvt_pk_f16_f32 in the gfx950 build; the kernels run
@@ -39,6 +43,9 @@ __host__ __device__ inline uint32_t deliver_f16_bits(float f)
 // the words (a.lo, b.hi) and (a.hi, b.lo) of two longwords
 __device__ __forceinline__ uint32_t deliver_lo_hi(uint32_t a, uint32_t b) { return byte_perm(b, a, 0x07060100u); }
 __device__ __forceinline__ uint32_t deliver_hi_lo(uint32_t a, uint32_t b) { return byte_perm(b, a, 0x05040302u); }
+// ... and (a.lo, b.lo), (a.hi, b.hi): the even and the odd words of four
+__device__ __forceinline__ uint32_t deliver_lo_lo(uint32_t a, uint32_t b) { return byte_perm(b, a, 0x05040100u); }
+__device__ __forceinline__ uint32_t deliver_hi_hi(uint32_t a, uint32_t b) { return byte_perm(b, a, 0x07060302u); }
 __device__ __forceinline__ cfhd_u4 deliver_load_dword_aligned(const uint8_t *p) { cfhd_u4 v; v.x = CFHD_LDG32(p); v.y = CFHD_LDG32(p + 4); v.z = CFHD_LDG32(p + 8); v.w = CFHD_LDG32(p + 12); return v; }
 
 // eight elements of one plane, two to a longword as they come out of the RG48 words: 16 bytes of u16 or f16, 32 bytes of f32 (at, a multiple of 16)
@@ -121,6 +128,42 @@ __global__ void __launch_bounds__(DEC_DELIVER_THREADS) k_dec_deliver(const uint8
 			deliver_store_element(orow, x, px[0], layout);
 			deliver_store_element(orow + plane, x, px[1], layout);
 			deliver_store_element(orow + 2 * plane, x, px[2], layout);
+		}
+	}
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_dec_deliver_bayer: BYR4 picture i of the pass -- the mosaic, 2 x quad_rows rows of 2 x width photosites (4 x width bytes) back to back at src + i * src_stride --
+// into dst + i * dst_stride as four planes of quad_rows rows of `width` elements: plane k = 2 * (row & 1) + (column & 1) holds the photosites at that position of every
+// 2 x 2 quad (red-green phase: R, G1, G2, B -- the rows r g1 / g2 b of k_inv_bayer_strip).  Plane k at dst_pitch * quad_rows * k, row q of it at dst_pitch * q.  Every
+// plane row gets its bytes and nothing else.  `layout`: the element type as DELIVER_PLANAR_U16 / _F16 / _F32 (deliver_bayer_element), the element rules those of
+// deliver_store_plane.
+//   A wave owns a quad row at a time, two mosaic rows.  A lane takes 8 quads: two 16-byte loads from the even mosaic row and two from the odd one -- 32 consecutive
+//   bytes of each row per lane, a wave reads 2 KB of each row without a gap --, the even and the odd words of each row separated in registers (v_perm_b32: 8 per
+//   mosaic row, 16 per lane and step), one 16-byte store per plane for u16 / f16, two for f32 -- every store instruction of a wave writes consecutive pieces of one
+//   plane row.  Every Bayer plan has component planes of whole groups of eight (build_frame_plan in cfhd_tables.cpp admits no other width), the batch's pictures come
+//   from hipMalloc and lie 8 x width x quad_rows apart, and the entry point admits only pointers, strides and pitches that are multiples of 16 (checked where the
+//   layout is set): every row on either side starts on a 16-byte boundary.  There is no element-by-element path.
+// No LDS, no scratch.  Grid (pieces of quad rows: dec_deliver_pieces(quad_rows), pictures), DEC_DELIVER_WAVES quad rows per piece and step.
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(DEC_DELIVER_THREADS) k_dec_deliver_bayer(const uint8_t *src, size_t src_stride, int quad_rows, int width, uint8_t *dst, size_t dst_stride, int dst_pitch, int layout)
+{
+	const int lane = (int)(threadIdx.x & 63u), wave = wave_uniform((int)(threadIdx.x >> 6));
+	const uint8_t *pic = src + src_stride * (size_t)blockIdx.y;
+	uint8_t *out = dst + dst_stride * (size_t)blockIdx.y;
+	const int elt = layout == DELIVER_PLANAR_F32 ? 4 : 2, groups = width >> 3;
+	const size_t plane = (size_t)dst_pitch * (size_t)quad_rows;
+	for (int q = (int)blockIdx.x * DEC_DELIVER_WAVES + wave; q < quad_rows; q += (int)gridDim.x * DEC_DELIVER_WAVES) {
+		const uint8_t *even = pic + (size_t)q * 8 * width, *odd = even + (size_t)4 * width;
+		uint8_t *orow = out + (size_t)q * dst_pitch;
+		for (int g = lane; g < groups; g += 64) {
+			const cfhd_u4 a = CFHD_LDG128(even + 32 * g), b = CFHD_LDG128(even + 32 * g + 16), c = CFHD_LDG128(odd + 32 * g), d = CFHD_LDG128(odd + 32 * g + 16);
+			// every longword holds the photosites of one quad row of a quad: positions 0 1 of the even mosaic row, 2 3 of the odd one
+			uint8_t *at = orow + (size_t)g * 8 * elt;
+			deliver_store_plane(at, deliver_lo_lo(a.x, a.y), deliver_lo_lo(a.z, a.w), deliver_lo_lo(b.x, b.y), deliver_lo_lo(b.z, b.w), layout);
+			deliver_store_plane(at + plane, deliver_hi_hi(a.x, a.y), deliver_hi_hi(a.z, a.w), deliver_hi_hi(b.x, b.y), deliver_hi_hi(b.z, b.w), layout);
+			deliver_store_plane(at + 2 * plane, deliver_lo_lo(c.x, c.y), deliver_lo_lo(c.z, c.w), deliver_lo_lo(d.x, d.y), deliver_lo_lo(d.z, d.w), layout);
+			deliver_store_plane(at + 3 * plane, deliver_hi_hi(c.x, c.y), deliver_hi_hi(c.z, c.w), deliver_hi_hi(d.x, d.y), deliver_hi_hi(d.z, d.w), layout);
 		}
 	}
 }

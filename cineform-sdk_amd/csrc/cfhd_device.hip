@@ -596,17 +596,35 @@ void CollectTimes::release()
 // The gates and the launch of EncodeBatch:: / GopBatch::upload_frames_device_planar: `slots` holds the batch's `nframes` packed frames, frame_bytes apart, `rows` rows of
 // 6 x width bytes back to back (RG48; checked here).  Frame slots, widths and the caller's geometry together put every row of either side on a 16-byte boundary and
 // make it a whole number of the kernel's groups of eight pixels (cfhd_collect_kernels.h).
+// A BYR4 batch (width: the plan's, photosite quads; rows: the mosaic's, 2 x display height; slot rows of 4 x width bytes) takes the BAYER_* layouts and no other:
+// four planes of rows / 2 rows of `width` elements through k_enc_collect_bayer, the same gates over its own geometry.
 static int collect_planar_frames(int pixel_kind, uint8_t *slots, size_t frame_bytes, int slot_pitch, int width, int rows, int nframes, int first, int count,
                                  const void *d_frames, size_t frame_stride, int row_pitch, int layout, void *stream, CollectTimes &times)
 {
 	auto refuse = [](const char *text) { g_err = text; return -1; };
-	if (pixel_kind != PIX_RG48) return refuse("frames from planar tensors: the batch's input is not RG48");
-	if (layout != dev::COLLECT_PLANAR_U16 && layout != dev::COLLECT_PLANAR_F16 && layout != dev::COLLECT_PLANAR_F32) return refuse("frames from planar tensors: unknown layout");
+	const bool bayer = pixel_kind == PIX_BYR4;
+	if (pixel_kind == PIX_BYR5) return refuse("frames from planar tensors: BYR5 mosaics are not served (BYR4 mosaics are, from four planes)");
+	if (bayer && !dev::collect_is_bayer(layout)) return refuse("frames from planar tensors: a BYR4 batch takes the four planes of a mosaic (the BAYER layouts) and no other layout");
+	if (!bayer && pixel_kind != PIX_RG48) return refuse(dev::collect_is_bayer(layout) ? "frames from planar tensors: the batch's input is not BYR4" : "frames from planar tensors: the batch's input is not RG48");
+	if (!bayer && layout != dev::COLLECT_PLANAR_U16 && layout != dev::COLLECT_PLANAR_F16 && layout != dev::COLLECT_PLANAR_F32) return refuse("frames from planar tensors: unknown layout");
 	if (count < 1 || first < 0 || first > nframes - count) return refuse("frames from planar tensors: the run of frames leaves the batch");
 	if (!d_frames) return refuse("frames from planar tensors: no pointer");
 	if (((uintptr_t)d_frames | frame_stride | (size_t)(unsigned)row_pitch) & 15) return refuse("frames from planar tensors: pointer, frame stride and row pitch are multiples of 16");
-	const int elt = layout == dev::COLLECT_PLANAR_F32 ? 4 : 2;
+	const int elt = layout == dev::COLLECT_PLANAR_F32 || layout == dev::COLLECT_BAYER_F32 ? 4 : 2;
 	if (row_pitch < 0 || (long long)row_pitch < (long long)width * elt) return refuse("frames from planar tensors: a row pitch below width x element size");
+	if (bayer) {
+		const int quad_rows = rows / 2;
+		if (frame_stride < 4 * (size_t)quad_rows * (size_t)row_pitch) return refuse("frames from planar tensors: a frame stride below four planes (4 x height / 2 x row pitch)");
+		if ((width & 7) || (rows & 1) || slot_pitch != 4 * width || frame_bytes != (size_t)slot_pitch * rows || (((uintptr_t)slots | frame_bytes) & 15) || count > 65535 /* blockIdx.y */)
+			return refuse("frames from planar tensors: frame slots the Bayer collect kernel does not take");
+		int rc = times.record(stream, false);
+		if (rc) return rc;
+		(void)hipGetLastError();
+		dev::k_enc_collect_bayer<<<dim3(dev::enc_collect_pieces(quad_rows), (unsigned)count), dev::ENC_COLLECT_THREADS, 0, (hipStream_t)stream>>>(
+			(const uint8_t *)d_frames, frame_stride, row_pitch, quad_rows, width, slots + frame_bytes * (size_t)first, frame_bytes, dev::collect_bayer_element(layout));
+		HIPCHK(hipGetLastError());
+		return times.record(stream, true);
+	}
 	if (frame_stride < 3 * (size_t)rows * (size_t)row_pitch) return refuse("frames from planar tensors: a frame stride below three planes (3 x height x row pitch)");
 	if ((width & 7) || slot_pitch != 6 * width || frame_bytes != (size_t)slot_pitch * rows || (((uintptr_t)slots | frame_bytes) & 15) || count > 65535 /* blockIdx.y */)
 		return refuse("frames from planar tensors: frame slots the collect kernel does not take");

@@ -175,8 +175,17 @@ int  cfhd_amd_batch_upload_device(cfhd_amd_batch *batch, int frame, const void *
  * that leaves the batch, no pointer, a pointer, frame stride or row pitch that is no multiple of 16, a row pitch that is negative or below width * element size, a
  * frame stride below 3 * height * row_pitch; another value for a device failure.
  * cfhd_amd_batch_kernel_ms(batch, 20) is the HIP-event time of the k_enc_collect launches that fed the last completed pass (0 when none did),
- * cfhd_amd_batch_kernel_name(batch, 20) "k_enc_collect". */
+ * cfhd_amd_batch_kernel_name(batch, 20) "k_enc_collect".
+ * CFHD_AMD_FRAMES_BAYER_U16 / _F16 / _F32: the same for every batch whose input is BYR4 -- cfhd_amd_batch_create_ex mode 1, cfhd_amd_batch_create_bayer modes 0 and 1,
+ * cfhd_amd_batch_create_stream -- and for no other (BYR5 is not served; a BYR4 batch takes no PLANAR_* layout, an RG48 batch no BAYER_* one).  A mosaic of W x H
+ * photosites (the batch's width and height) is read as four planes of H / 2 rows of W / 2 elements: plane k = 2 * (row & 1) + (column & 1) holds the photosites at
+ * that position of every 2 x 2 quad -- the codec does not know the CFA phase, the planes are named by position; for an RGGB mosaic they are R, G1, G2, B.  Rows
+ * row_pitch bytes apart, planes (H / 2) * row_pitch apart: the geometry of CFHD_AMD_PICTURES_BAYER_*.  A contiguous tensor (n, 4, H / 2, W / 2) is row_pitch =
+ * (W / 2) * element size, frame_stride = 4 * (H / 2) * row_pitch.  The element rules are the ones above, on the 16-bit photosite word, and so are the inversion
+ * properties.  One launch of k_enc_collect_bayer per run (per chunk of a cut intra batch), timed under index 20; cfhd_amd_batch_kernel_name(batch, 20) answers
+ * "k_enc_collect_bayer" for a BYR4 batch.  Refused as above, with W / 2 for the width and a frame stride below 4 * (H / 2) * row_pitch. */
 enum { CFHD_AMD_FRAMES_PLANAR_U16 = 1, CFHD_AMD_FRAMES_PLANAR_F16 = 2, CFHD_AMD_FRAMES_PLANAR_F32 = 3 };      /* values equal to CFHD_AMD_PICTURES_PLANAR_* */
+enum { CFHD_AMD_FRAMES_BAYER_U16 = 4, CFHD_AMD_FRAMES_BAYER_F16 = 5, CFHD_AMD_FRAMES_BAYER_F32 = 6 };         /* values equal to CFHD_AMD_PICTURES_BAYER_* */
 int  cfhd_amd_batch_upload_device_planar(cfhd_amd_batch *batch, int first_frame, int count, const void *d_frames, size_t frame_stride, int row_pitch, int layout);
 /* Frame `frame` as the batch holds it, in its packed input format, into out (rows `pitch` >= row bytes apart): the twin of cfhd_amd_batch_download_output for the
  * input side, for every kind of batch and input format (av28: the frame's one block as one row).  Waits for the stream the uploads run on.  0; -1 for bad arguments
@@ -325,7 +334,8 @@ cfhd_amd_decode_batch *cfhd_amd_decode_batch_create_groups(const void *first_gro
  * point is shared and keeps its meaning: cfhd_amd_decode_batch_geometry answers the mosaic -- twice the sample's (component plane) width and rows, row_bytes =
  * 2 * width --; submit_host, submit_device, wait and download_output work as for any batch; status[i] is what CFHD_DecodeSample returns for sample i, the picture of
  * a sample that failed is zero, and the slow path inside wait is the handle's; every picture equals the handle's byte for byte (16-bit photosites, no dither).
- * cfhd_amd_decode_batch_set_device_pictures takes CFHD_AMD_PICTURES_PACKED; the planar layouts stay refused (the output is not RG48).
+ * cfhd_amd_decode_batch_set_device_pictures takes CFHD_AMD_PICTURES_PACKED -- the mosaic as it is -- and CFHD_AMD_PICTURES_BAYER_U16 / _F16 / _F32 -- the mosaic as four
+ * planes, one per position of the 2 x 2 quad; the PLANAR_* layouts stay refused (the output is not RG48).
  * cfhd_amd_decode_batch_kernel_ms / _kernel_name: indices 0 .. 9 keep their meaning; 6 names the last level that ran -- "k_inv_bayer_strip", the mosaic written
  * straight from the last wavelet level (passes of 4 frames of 1080p-equivalent work and more -- a 3840 x 2160 mosaic is one --, or CFHD_AMD_INVERSE=strip), or
  * "k_inv_packed16+k_bayer_to_byr4", the handle's pair (smaller passes, or CFHD_AMD_INVERSE=tile); both give the same bytes.
@@ -364,11 +374,18 @@ int  cfhd_amd_decode_batch_submit_device(cfhd_amd_decode_batch *batch, const voi
  * interlaced groups).  A picture is three planes, R, then G, then B, each `height` rows of `width` elements, rows picture_pitch bytes apart, planes height * picture_pitch
  * bytes apart: a contiguous tensor (n, 3, H, W) is picture_pitch = W * element size, picture_stride = 3 * H * W * element size.  For the RG48 word w: U16 is w; F32 is
  * (float)w * (1.0f / 65535.0f), one IEEE single multiply; F16 is that value rounded to nearest-even to binary16, subnormals kept.
+ * CFHD_AMD_PICTURES_BAYER_U16 / _F16 / _F32: a batch made by cfhd_amd_decode_batch_create_bayer only (to every other batch these values are unknown layouts).  The
+ * mosaic of W x H photosites (cfhd_amd_decode_batch_geometry) is four planes of H / 2 rows of W / 2 elements: plane k = 2 * (row & 1) + (column & 1) holds the
+ * photosites at that position of every 2 x 2 quad -- the codec does not know the CFA phase, the planes are named by position; for an RGGB mosaic they are R, G1, G2,
+ * B.  Rows picture_pitch bytes apart, planes (H / 2) * picture_pitch apart: a contiguous tensor (n, 4, H / 2, W / 2) is picture_pitch = (W / 2) * element size,
+ * picture_stride = 4 * (H / 2) * picture_pitch.  The element rules are the RG48 ones on the 16-bit photosite word.  Written by k_dec_deliver_bayer in place of
+ * k_dec_deliver (cfhd_amd_decode_batch_kernel_name(batch, 9) answers it while such a layout is set; kernel_ms index 9 times it).
  * Exactly count pictures are written, of every row its row bytes and nothing else: pitch padding, the space between planes and pictures and the pictures behind a short
  * pass are not touched.
  * 0; -1 with the reason in cfhd_amd_last_error(): a pass in flight, an unknown layout, a planar layout on a batch whose output is not RG48, a pointer, stride or pitch
  * that is no multiple of 16, a pitch below the row bytes of the layout, a stride below what one picture occupies. */
 enum { CFHD_AMD_PICTURES_PACKED = 0, CFHD_AMD_PICTURES_PLANAR_U16 = 1, CFHD_AMD_PICTURES_PLANAR_F16 = 2, CFHD_AMD_PICTURES_PLANAR_F32 = 3 };
+enum { CFHD_AMD_PICTURES_BAYER_U16 = 4, CFHD_AMD_PICTURES_BAYER_F16 = 5, CFHD_AMD_PICTURES_BAYER_F32 = 6 };
 int  cfhd_amd_decode_batch_set_device_pictures(cfhd_amd_decode_batch *batch, void *d_pictures, size_t picture_stride, int picture_pitch, int layout);
 /* Collects the pass: the number of samples that decoded, or < 0 (-1: nothing in flight, -2: device failure).  status (NULL or count entries): status[i] is the CFHD_Error
  * CFHD_DecodeSample returns for sample i on a handle prepared on the first sample; the picture of a sample that failed is zero.  Samples the device parser refuses are
@@ -381,7 +398,7 @@ int  cfhd_amd_decode_batch_wait(cfhd_amd_decode_batch *batch, CFHD_Error *status
 int  cfhd_amd_decode_batch_download_output(cfhd_amd_decode_batch *batch, int i, void *out, int pitch);
 /* HIP-event time (ms) of the kernels of the last pass and their names as a profiler shows them.  which: 0 k_dec_ingest, 1 k_dec_parse, 2 the band decoder (all its
  * kernels), 3 k_dec_lowpass, 4 / 5 / 6 the transform levels in launch order (the last one with the output conversion), 7 k_dec_blank, 9 k_dec_deliver (both kinds of
- * batch; 0 ms when the last pass delivered nothing into device memory).  0 / "" otherwise. */
+ * batch; k_dec_deliver_bayer while a BAYER_* layout is set; 0 ms when the last pass delivered nothing into device memory).  0 / "" otherwise. */
 float cfhd_amd_decode_batch_kernel_ms(cfhd_amd_decode_batch *batch, int which);
 const char *cfhd_amd_decode_batch_kernel_name(cfhd_amd_decode_batch *batch, int which);
 int  cfhd_amd_device_count(void);
