@@ -1,7 +1,8 @@
 // cfhd_collect_kernels.h -- k_enc_collect, the mirror image of k_dec_deliver (cfhd_deliver_kernels.h) on the frame queue's side: a run of frames that lie in the caller's
 // device memory as planar R, G, B tensors of u16, f16 or f32 elements (a torch tensor N x 3 x H x W) into the batch's RG48 frame slots, one launch for the whole run
 // (cfhd_amd_batch_upload_device_planar, cfhd_device.hip collect_planar_frames) -- and k_enc_collect_bayer, the same for the BYR4 frames of a Bayer batch out of four
-// planes, one per position of the 2 x 2 quad (N x 4 x H/2 x W/2).
+// planes, one per position of the 2 x 2 quad (N x 4 x H/2 x W/2), and k_enc_collect_yuv422, the same for the packed 4:2:2 frames (YUY2, 2vuy, YU64) of a batch out of
+// a luma plane and two chroma planes of half the width (I422).
 #pragma once
 #include <stdint.h>
 #include <stddef.h>
@@ -16,6 +17,11 @@ enum { COLLECT_PLANAR_U16 = 1, COLLECT_PLANAR_F16 = 2, COLLECT_PLANAR_F32 = 3, C
 inline bool collect_is_bayer(int layout) { return layout >= COLLECT_BAYER_U16 && layout <= COLLECT_BAYER_F32; }
 // the element type of a BAYER_* layout as the PLANAR_* value the element rules below are written for
 inline int collect_bayer_element(int layout) { return layout - COLLECT_BAYER_U16 + COLLECT_PLANAR_U16; }
+// (CFHD_AMD_FRAMES_YUV422_*) and the packed orders they are collected into: Y0 U Y1 V bytes, U Y0 V Y1 bytes, Y0 Cr Y1 Cb words
+enum { COLLECT_YUV422_U8 = 7, COLLECT_YUV422_U16 = 8, COLLECT_YUV422_F16 = 9, COLLECT_YUV422_F32 = 10 };
+enum { COLLECT_ORDER_YUY2 = 0, COLLECT_ORDER_2VUY = 1, COLLECT_ORDER_YU64 = 2 };
+inline bool collect_is_yuv422(int layout) { return layout >= COLLECT_YUV422_U8 && layout <= COLLECT_YUV422_F32; }
+inline int collect_yuv422_element_bytes(int layout) { return layout == COLLECT_YUV422_U8 ? 1 : (layout == COLLECT_YUV422_F32 ? 4 : 2); }
 
 // The element rules, element -> RG48 word w.  U16: w is the element.  F32: t = x * 65535.0f, one IEEE single multiply; NaN gives 0; t clamped to [0, 65535] and
 // rounded to nearest, ties to even (-0, everything negative, -inf: 0; everything >= 1, +inf: 65535).  F16: the binary16 value widened exactly to single, subnormals
@@ -49,6 +55,16 @@ __host__ __device__ inline uint32_t collect_word_f32(float x)
 	return (uint32_t)__builtin_rintf(t);       // to nearest, ties to even (the default rounding mode)
 }
 __host__ __device__ inline uint32_t collect_word_f16(uint32_t h) { return collect_word_f32(collect_f16_value(h)); }
+// ... and the same rules with the unit of the word: 255 for the bytes of YUY2 and 2vuy, 65535 for the words of YU64 (the 4:2:2 plane layouts).  For the 8-bit unit
+// collect(deliver(b)) = b for all 256 bytes through U8, F32 and F16 alike: the binary16 values of b / 255 are 256 distinct numbers that come back within 0.063 of b.
+template <int UNIT> __host__ __device__ inline uint32_t collect_word_f32_of(float x)
+{
+	float t = x * (float)UNIT;
+	t = t > 0.0f ? t : 0.0f;
+	t = t < (float)UNIT ? t : (float)UNIT;
+	return (uint32_t)__builtin_rintf(t);
+}
+template <int UNIT> __host__ __device__ inline uint32_t collect_word_f16_of(uint32_t h) { return collect_word_f32_of<UNIT>(collect_f16_value(h)); }
 
 // two 16-bit words of two longwords into one: (a.lo, b.lo), (a.lo, b.hi), (a.hi, b.hi) as (low word, high word)
 __device__ __forceinline__ uint32_t collect_lo_lo(uint32_t a, uint32_t b) { return byte_perm(b, a, 0x05040100u); }
@@ -148,6 +164,109 @@ __global__ void __launch_bounds__(ENC_COLLECT_THREADS) k_enc_collect_bayer(const
 			store_u32x4_global(even + 32 * g + 16, e[4], e[5], e[6], e[7]);
 			store_u32x4_global(odd + 32 * g, o[0], o[1], o[2], o[3]);
 			store_u32x4_global(odd + 32 * g + 16, o[4], o[5], o[6], o[7]);
+		}
+	}
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_enc_collect_yuv422: the mirror image of k_dec_deliver_yuv422.  Frame i of the run out of src + i * src_stride -- three planes in the I422 convention: Y, `rows` rows
+// of `width` elements src_pitch bytes apart, at 0; Cb, `rows` rows of width / 2 elements src_pitch / 2 bytes apart, at rows * src_pitch; Cr, the same, behind it -- into
+// dst + i * dst_stride, the batch's own packed 4:2:2 frames: `rows` rows back to back, 2 x width bytes a row (order COLLECT_ORDER_YUY2: Y0 U Y1 V, _2VUY: U Y0 V Y1)
+// or 4 x width (_YU64: the words Y0 Cr Y1 Cb).  The source is read, never written.  `layout`: COLLECT_YUV422_U8 (8-bit frames) / _U16 (YU64) -- the element as it is --,
+// _F16 / _F32: collect_word_f32_of with the unit of the frame's own word, 255 or 65535.
+//   A wave owns a row at a time, a lane takes 16 pixels: 16 elements of the luma row and 8 of each chroma row -- 16-byte loads, one 8-byte load per chroma plane for
+//   U8; the loads of a wave cover consecutive bytes of a plane row --, the elements turned into bytes or words in registers and interleaved (v_perm_b32: 12 for the
+//   8-bit orders, 16 for YU64), then two (8-bit) or four (YU64) 16-byte stores of 32 or 64 consecutive bytes: a wave writes 2 or 4 KB of the frame row without a gap.
+//   Every 4:2:2 plan has a width that is a multiple of 16 (build_frame_plan in cfhd_tables.cpp: chroma planes of whole groups of eight; build_gop_plan in cfhd_gop.cpp),
+//   the frame slots come from hipMalloc and lie rows x row bytes apart, and the entry point admits only pointers and strides that are multiples of 16 and pitches that
+//   are multiples of 32 (collect_planar_frames checks all of it): every row on either side starts on a 16-byte boundary and is a whole number of groups.  There is
+//   no tail path.
+// No LDS, no scratch.  Grid (row pieces: enc_collect_pieces(rows), frames), ENC_COLLECT_WAVES rows per piece and step.
+// ---------------------------------------------------------------------------------------------
+enum { ENC_COLLECT_YUV422_PIXELS = 16 };
+__device__ __forceinline__ uint32_t collect_hi_lo(uint32_t a, uint32_t b) { return byte_perm(b, a, 0x05040302u); }      // (a.hi, b.lo)
+
+// B bytes (8 or a multiple of 16) at `at` as longwords
+template <int B> __device__ __forceinline__ void collect_load_longwords(const uint8_t *at, uint32_t *d)
+{
+	if constexpr (B == 8) { const cfhd_u2 v = CFHD_LDG64(at); d[0] = v.x; d[1] = v.y; }
+	else for (int k = 0; k < B / 16; k++) { const cfhd_u4 v = CFHD_LDG128(at + 16 * k); d[4 * k] = v.x; d[4 * k + 1] = v.y; d[4 * k + 2] = v.z; d[4 * k + 3] = v.w; }
+}
+// N elements of one plane row as the frame's own bytes (UNIT 255: four to a longword) or words (UNIT 65535: two to a longword), in element order
+template <int LAYOUT, int UNIT, int N> __device__ __forceinline__ void collect_load_elements(const uint8_t *at, uint32_t *out)
+{
+	constexpr int E = LAYOUT == COLLECT_YUV422_U8 ? 1 : (LAYOUT == COLLECT_YUV422_F32 ? 4 : 2);
+	uint32_t d[N * E / 4];
+	collect_load_longwords<N * E>(at, d);
+	if constexpr (LAYOUT == COLLECT_YUV422_U8 || LAYOUT == COLLECT_YUV422_U16) { for (int k = 0; k < N * E / 4; k++) out[k] = d[k]; }
+	else {
+		uint32_t w[N];
+		for (int k = 0; k < N; k++) {
+			if constexpr (LAYOUT == COLLECT_YUV422_F32) { float x; memcpy(&x, &d[k], 4); w[k] = collect_word_f32_of<UNIT>(x); }
+			else w[k] = collect_word_f16_of<UNIT>((d[k / 2] >> (16 * (k & 1))) & 0xffffu);
+		}
+		if constexpr (UNIT == 255) { for (int k = 0; k < N / 4; k++) out[k] = w[4 * k] | (w[4 * k + 1] << 8) | (w[4 * k + 2] << 16) | (w[4 * k + 3] << 24); }
+		else for (int k = 0; k < N / 2; k++) out[k] = w[2 * k] | (w[2 * k + 1] << 16);
+	}
+}
+// one row of `width` pixels
+template <int ORDER, int LAYOUT> __device__ __forceinline__ void collect_yuv422_row(const uint8_t *y, const uint8_t *cb, const uint8_t *cr, int width, uint8_t *orow, int lane)
+{
+	constexpr int E = LAYOUT == COLLECT_YUV422_U8 ? 1 : (LAYOUT == COLLECT_YUV422_F32 ? 4 : 2), P = ENC_COLLECT_YUV422_PIXELS;
+	const int groups = width / P;
+	for (int g = lane; g < groups; g += 64) {
+		if constexpr (ORDER == COLLECT_ORDER_YU64) {
+			uint32_t Y[P / 2], U[P / 4], V[P / 4], o[P];
+			collect_load_elements<LAYOUT, 65535, P>(y + (size_t)g * P * E, Y);
+			collect_load_elements<LAYOUT, 65535, P / 2>(cb + (size_t)g * (P / 2) * E, U);
+			collect_load_elements<LAYOUT, 65535, P / 2>(cr + (size_t)g * (P / 2) * E, V);
+			// the longwords (Y0, Cr), (Y1, Cb) of every pair of pixels; a chroma longword serves two pairs
+			for (int m = 0; m < P / 4; m++) {
+				o[4 * m] = collect_lo_lo(Y[2 * m], V[m]); o[4 * m + 1] = collect_hi_lo(Y[2 * m], U[m]);
+				o[4 * m + 2] = collect_lo_hi(Y[2 * m + 1], V[m]); o[4 * m + 3] = collect_hi_hi(Y[2 * m + 1], U[m]);
+			}
+			uint8_t *to = orow + (size_t)g * 4 * P;
+			for (int k = 0; k < P; k += 4) store_u32x4_global(to + 4 * k, o[k], o[k + 1], o[k + 2], o[k + 3]);
+		} else {
+			uint32_t Y[P / 4], U[P / 8], V[P / 8], o[P / 2];
+			collect_load_elements<LAYOUT, 255, P>(y + (size_t)g * P * E, Y);
+			collect_load_elements<LAYOUT, 255, P / 2>(cb + (size_t)g * (P / 2) * E, U);
+			collect_load_elements<LAYOUT, 255, P / 2>(cr + (size_t)g * (P / 2) * E, V);
+			// a longword per pair of pixels: two luma bytes (selector bytes 0 .. 3) and the pair's Cb Cr out of the interleaved chroma (4 .. 7)
+			constexpr uint32_t even = ORDER == COLLECT_ORDER_YUY2 ? 0x05010400u : 0x01050004u, odd = ORDER == COLLECT_ORDER_YUY2 ? 0x07030602u : 0x03070206u;
+			for (int m = 0; m < P / 8; m++) {
+				const uint32_t uv0 = byte_perm(V[m], U[m], 0x05010400u), uv1 = byte_perm(V[m], U[m], 0x07030602u);      // Cb0 Cr0 Cb1 Cr1, Cb2 Cr2 Cb3 Cr3
+				o[4 * m] = byte_perm(uv0, Y[2 * m], even); o[4 * m + 1] = byte_perm(uv0, Y[2 * m], odd);
+				o[4 * m + 2] = byte_perm(uv1, Y[2 * m + 1], even); o[4 * m + 3] = byte_perm(uv1, Y[2 * m + 1], odd);
+			}
+			uint8_t *to = orow + (size_t)g * 2 * P;
+			for (int k = 0; k < P / 2; k += 4) store_u32x4_global(to + 4 * k, o[k], o[k + 1], o[k + 2], o[k + 3]);
+		}
+	}
+}
+
+__global__ void __launch_bounds__(ENC_COLLECT_THREADS) k_enc_collect_yuv422(const uint8_t *src, size_t src_stride, int src_pitch, int rows, int width, uint8_t *dst, size_t dst_stride, int layout, int order)
+{
+	const int lane = (int)(threadIdx.x & 63u), wave = wave_uniform((int)(threadIdx.x >> 6));
+	const uint8_t *in = src + src_stride * (size_t)blockIdx.y;
+	uint8_t *frame = dst + dst_stride * (size_t)blockIdx.y;
+	const int row_bytes = (order == COLLECT_ORDER_YU64 ? 4 : 2) * width, chroma_pitch = src_pitch >> 1;
+	const uint8_t *cb_plane = in + (size_t)src_pitch * (size_t)rows, *cr_plane = cb_plane + (size_t)chroma_pitch * (size_t)rows;
+	for (int r = (int)blockIdx.x * ENC_COLLECT_WAVES + wave; r < rows; r += (int)gridDim.x * ENC_COLLECT_WAVES) {
+		const uint8_t *y = in + (size_t)r * src_pitch, *cb = cb_plane + (size_t)r * chroma_pitch, *cr = cr_plane + (size_t)r * chroma_pitch;
+		uint8_t *orow = frame + (size_t)r * row_bytes;
+		if (order == COLLECT_ORDER_YU64) {
+			if (layout == COLLECT_YUV422_U16) collect_yuv422_row<COLLECT_ORDER_YU64, COLLECT_YUV422_U16>(y, cb, cr, width, orow, lane);
+			else if (layout == COLLECT_YUV422_F16) collect_yuv422_row<COLLECT_ORDER_YU64, COLLECT_YUV422_F16>(y, cb, cr, width, orow, lane);
+			else collect_yuv422_row<COLLECT_ORDER_YU64, COLLECT_YUV422_F32>(y, cb, cr, width, orow, lane);
+		} else if (order == COLLECT_ORDER_YUY2) {
+			if (layout == COLLECT_YUV422_U8) collect_yuv422_row<COLLECT_ORDER_YUY2, COLLECT_YUV422_U8>(y, cb, cr, width, orow, lane);
+			else if (layout == COLLECT_YUV422_F16) collect_yuv422_row<COLLECT_ORDER_YUY2, COLLECT_YUV422_F16>(y, cb, cr, width, orow, lane);
+			else collect_yuv422_row<COLLECT_ORDER_YUY2, COLLECT_YUV422_F32>(y, cb, cr, width, orow, lane);
+		} else {
+			if (layout == COLLECT_YUV422_U8) collect_yuv422_row<COLLECT_ORDER_2VUY, COLLECT_YUV422_U8>(y, cb, cr, width, orow, lane);
+			else if (layout == COLLECT_YUV422_F16) collect_yuv422_row<COLLECT_ORDER_2VUY, COLLECT_YUV422_F16>(y, cb, cr, width, orow, lane);
+			else collect_yuv422_row<COLLECT_ORDER_2VUY, COLLECT_YUV422_F32>(y, cb, cr, width, orow, lane);
 		}
 	}
 }

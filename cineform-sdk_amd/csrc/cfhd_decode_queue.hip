@@ -144,6 +144,14 @@ int launch_deliver(cfhd_amd_decode_batch *b, int first, int count)
 		HIPCHK(hipGetLastError());
 		return 0;
 	}
+	if (dev::deliver_is_yuv422(b->dev_out_layout)) {     // packed 4:2:2 pictures as a luma plane and two chroma planes (set_device_pictures checked the geometry the kernel assumes)
+		const int order = b->st.out_kind == PIX_YU64 ? dev::YUV422_YU64 : (b->st.out_kind == PIX_2VUY ? dev::YUV422_2VUY : dev::YUV422_YUY2);
+		dev::k_dec_deliver_yuv422<<<dim3(dev::dec_deliver_pieces(b->picture_rows()), (unsigned)count), dev::DEC_DELIVER_THREADS, 0, (hipStream_t)b->stream()>>>(
+			b->device_pictures() + b->picture_bytes() * (size_t)first, b->picture_bytes(), b->picture_rows(), b->picture_width(),
+			b->dev_out + b->dev_out_stride * (size_t)first, b->dev_out_stride, b->dev_out_pitch, b->dev_out_layout, order);
+		HIPCHK(hipGetLastError());
+		return 0;
+	}
 	dev::k_dec_deliver<<<dim3(dev::dec_deliver_pieces(b->picture_rows()), (unsigned)count), dev::DEC_DELIVER_THREADS, 0, (hipStream_t)b->stream()>>>(
 		b->device_pictures() + b->picture_bytes() * (size_t)first, b->picture_bytes(), b->picture_pitch(), b->picture_rows(), b->picture_width(),
 		b->dev_out + b->dev_out_stride * (size_t)first, b->dev_out_stride, b->dev_out_pitch, b->dev_out_layout);
@@ -408,10 +416,34 @@ int cfhd_amd_decode_batch_set_device_pictures(cfhd_amd_decode_batch *b, void *d_
 	if (!d_pictures) { b->dev_out = nullptr; return 0; }
 	// (the BAYER_* layouts exist for the BYR4 mosaics of cfhd_amd_decode_batch_create_bayer's batches alone: to every other batch they are unknown)
 	const bool bayer = dev::deliver_is_bayer(layout) && !b->groups && b->st.out_kind == PIX_BYR4;
-	if (!bayer && (layout < CFHD_AMD_PICTURES_PACKED || layout > CFHD_AMD_PICTURES_PLANAR_F32)) { refuse("decode queue: unknown layout of the device pictures"); return -1; }
-	const bool planar = !bayer && layout != CFHD_AMD_PICTURES_PACKED;
+	// (the YUV422_* layouts exist for packed 4:2:2 pictures: to a Bayer batch they are unknown, every other output that is not YUY2, 2vuy or YU64 is told so)
+	const bool yuv422 = dev::deliver_is_yuv422(layout) && b->st.out_kind != PIX_BYR4;
+	if (!bayer && !yuv422 && (layout < CFHD_AMD_PICTURES_PACKED || layout > CFHD_AMD_PICTURES_PLANAR_F32)) { refuse("decode queue: unknown layout of the device pictures"); return -1; }
+	if (yuv422) {
+		const int kind = b->st.out_kind;
+		if (kind != PIX_YUY2 && kind != PIX_2VUY && kind != PIX_YU64) { refuse("decode queue: the 4:2:2 plane layouts serve batches whose output is YUY2, 2vuy or YU64"); return -1; }
+		if (layout == CFHD_AMD_PICTURES_YUV422_U8 && kind == PIX_YU64) { refuse("decode queue: YUV422_U8 serves the 8-bit outputs YUY2 and 2vuy; a YU64 batch delivers YUV422_U16"); return -1; }
+		if (layout == CFHD_AMD_PICTURES_YUV422_U16 && kind != PIX_YU64) { refuse("decode queue: YUV422_U16 serves YU64; a YUY2 or 2vuy batch delivers YUV422_U8"); return -1; }
+	}
+	const bool planar = !bayer && !yuv422 && layout != CFHD_AMD_PICTURES_PACKED;
 	if (planar && b->st.out_kind != PIX_RG48) { refuse("decode queue: the planar layouts serve batches whose output is RG48"); return -1; }
 	if (((uintptr_t)d_pictures | picture_stride | (size_t)(unsigned)picture_pitch) & 15) { refuse("decode queue: the device pictures' pointer, stride and pitch are multiples of 16"); return -1; }
+	if (yuv422) {
+		// Y at the pitch, Cb and Cr at half of it: H * pitch + 2 H * (pitch / 2) bytes a picture, of which the last chroma row needs its row bytes only
+		if (picture_pitch & 31) { refuse("decode queue: the pitch of a 4:2:2 plane layout is a multiple of 32 (the chroma planes' is half of it)"); return -1; }
+		const int w = b->picture_width(), h = b->picture_rows(), word = b->st.out_kind == PIX_YU64 ? 2 : 1;
+		const long long luma_row = (long long)w * dev::deliver_yuv422_element_bytes(layout);
+		// what k_dec_deliver_yuv422 assumes of the batch's own pictures: whole groups of eight pixels, rows back to back on 16-byte boundaries
+		if ((w & 7) || b->picture_pitch() != 2 * word * w || b->picture_bytes() != (size_t)b->picture_pitch() * (size_t)h || ((uintptr_t)b->device_pictures() & 15) || b->n > 65535 /* blockIdx.y */) {
+			refuse("decode queue: pictures the 4:2:2 deliver kernel does not take"); return -1;
+		}
+		if (picture_pitch < luma_row) { refuse("decode queue: the pitch is below the luma row of the 4:2:2 plane layout (width x element size)"); return -1; }
+		if (picture_stride < (size_t)picture_pitch * (size_t)h + (size_t)(picture_pitch / 2) * (2 * (size_t)h - 1) + (size_t)(luma_row / 2)) {
+			refuse("decode queue: the stride is below the three planes of the 4:2:2 layout (H x pitch, then 2 H chroma rows pitch / 2 apart)"); return -1;
+		}
+		b->dev_out = (uint8_t *)d_pictures; b->dev_out_stride = picture_stride; b->dev_out_pitch = picture_pitch; b->dev_out_layout = layout;
+		return 0;
+	}
 	// the rows and planes a picture has in the layout: the mosaic's four planes are half as high and half as wide
 	const int rows = bayer ? b->picture_rows() / 2 : b->picture_rows(), planes = bayer ? 4 : (planar ? 3 : 1);
 	const int elt = layout == CFHD_AMD_PICTURES_PLANAR_F32 || layout == CFHD_AMD_PICTURES_BAYER_F32 ? 4 : 2;
@@ -596,7 +628,7 @@ float cfhd_amd_decode_batch_kernel_ms(cfhd_amd_decode_batch *b, int which)
 
 const char *cfhd_amd_decode_batch_kernel_name(cfhd_amd_decode_batch *b, int which)
 {
-	if (b && !b->in_flight && which == 9) return b->dev_out && dev::deliver_is_bayer(b->dev_out_layout) ? "k_dec_deliver_bayer" : "k_dec_deliver";
+	if (b && !b->in_flight && which == 9) return b->dev_out && dev::deliver_is_bayer(b->dev_out_layout) ? "k_dec_deliver_bayer" : (b->dev_out && dev::deliver_is_yuv422(b->dev_out_layout) ? "k_dec_deliver_yuv422" : "k_dec_deliver");
 	if (!b || b->in_flight || which < 0 || which > 7) return "";
 	static const char *const fixed[4] = { "k_dec_ingest", "k_dec_parse", "k_dec_plan+k_dec_index+k_dec_chain+k_dec_tiles", "k_dec_lowpass" };
 	if (which < 4 && !(b->groups && which)) return fixed[which];

@@ -1,7 +1,8 @@
 // cfhd_deliver_kernels.h -- k_dec_deliver, the last kernel of a decode-queue pass that delivers into the caller's device memory (cfhd_amd_decode_batch_set_device_pictures,
 // cfhd_decode_queue.hip): behind k_dec_blank, the pictures of the pass out of the batch's own tightly packed buffer into memory the caller owns -- as the packed
 // pictures they are, at the caller's pitch, or, for RG48, as three planes R, G, B of u16, f16 or f32 elements (a torch tensor N x 3 x H x W) -- and k_dec_deliver_bayer,
-// which takes its place for the BYR4 mosaics of a Bayer batch delivered as four planes, one per position of the 2 x 2 quad (N x 4 x H/2 x W/2).
+// which takes its place for the BYR4 mosaics of a Bayer batch delivered as four planes, one per position of the 2 x 2 quad (N x 4 x H/2 x W/2), and k_dec_deliver_yuv422,
+// which takes it for the packed 4:2:2 pictures (YUY2, 2vuy, YU64) delivered as a luma plane and two chroma planes of half the width (I422: N x [H x W | 2 x H x W/2]).
 #pragma once
 #include <stdint.h>
 #include <stddef.h>
@@ -16,11 +17,18 @@ enum { DELIVER_PACKED = 0, DELIVER_PLANAR_U16 = 1, DELIVER_PLANAR_F16 = 2, DELIV
 inline bool deliver_is_bayer(int layout) { return layout >= DELIVER_BAYER_U16 && layout <= DELIVER_BAYER_F32; }
 // the element type of a BAYER_* layout as the PLANAR_* value the element rules below are written for
 inline int deliver_bayer_element(int layout) { return layout - DELIVER_BAYER_U16 + DELIVER_PLANAR_U16; }
+// (CFHD_AMD_PICTURES_YUV422_*) and the packed orders they are written from: Y0 U Y1 V bytes, U Y0 V Y1 bytes, Y0 Cr Y1 Cb words
+enum { DELIVER_YUV422_U8 = 7, DELIVER_YUV422_U16 = 8, DELIVER_YUV422_F16 = 9, DELIVER_YUV422_F32 = 10 };
+enum { YUV422_YUY2 = 0, YUV422_2VUY = 1, YUV422_YU64 = 2 };
+inline bool deliver_is_yuv422(int layout) { return layout >= DELIVER_YUV422_U8 && layout <= DELIVER_YUV422_F32; }
+inline int deliver_yuv422_element_bytes(int layout) { return layout == DELIVER_YUV422_U8 ? 1 : (layout == DELIVER_YUV422_F32 ? 4 : 2); }
 
 // The element rules of the planar layouts for the RG48 word w.  F32: (float)w * (1.0f / 65535.0f), one IEEE single multiply.  F16: that value rounded to nearest-even
 // to binary16, subnormals kept (w = 1 .. 3 land there: 1 / 65535 < 2^-14) -- under device compilation the hardware's convert (v_cvt_pk_f16_f32 in the gfx950 build; the kernels run
 // with the default mode: round to nearest even, 16-bit denormals kept), on a host-compiled build the same rule in integer arithmetic on the bits of the single.
 __host__ __device__ inline float deliver_unit_f32(uint32_t w) { return (float)w * (1.0f / 65535.0f); }
+// ... and the same rule with the unit of the word: 255 for the bytes of YUY2 and 2vuy, 65535 for the words of YU64 (the 4:2:2 plane layouts; F16 is deliver_f16_bits of it)
+template <int UNIT> __host__ __device__ inline float deliver_unit_f32_of(uint32_t w) { return (float)w * (1.0f / (float)UNIT); }
 __host__ __device__ inline uint32_t deliver_f16_bits(float f)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -164,6 +172,138 @@ __global__ void __launch_bounds__(DEC_DELIVER_THREADS) k_dec_deliver_bayer(const
 			deliver_store_plane(at + plane, deliver_hi_hi(a.x, a.y), deliver_hi_hi(a.z, a.w), deliver_hi_hi(b.x, b.y), deliver_hi_hi(b.z, b.w), layout);
 			deliver_store_plane(at + 2 * plane, deliver_lo_lo(c.x, c.y), deliver_lo_lo(c.z, c.w), deliver_lo_lo(d.x, d.y), deliver_lo_lo(d.z, d.w), layout);
 			deliver_store_plane(at + 3 * plane, deliver_hi_hi(c.x, c.y), deliver_hi_hi(c.z, c.w), deliver_hi_hi(d.x, d.y), deliver_hi_hi(d.z, d.w), layout);
+		}
+	}
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_dec_deliver_yuv422: packed 4:2:2 picture i of the pass -- `rows` rows of `width` pixels back to back at src + i * src_stride, 2 x width bytes a row (order
+// YUV422_YUY2: Y0 U Y1 V, YUV422_2VUY: U Y0 V Y1) or 4 x width (YUV422_YU64: the words Y0 Cr Y1 Cb) -- into dst + i * dst_stride as three planes, the I422 convention:
+// Y, `rows` rows of `width` elements dst_pitch bytes apart, at 0; Cb, `rows` rows of width / 2 elements dst_pitch / 2 bytes apart, at rows * dst_pitch; Cr, the same,
+// behind it.  Every plane row gets its bytes and nothing else.  `layout`: DELIVER_YUV422_U8 (the bytes of an 8-bit picture as they are), _U16 (the words of YU64), _F16 /
+// _F32 (deliver_unit_f32_of with the unit of the picture's own word, 255 or 65535; F16: deliver_f16_bits of it).
+//   A wave owns a row at a time; a lane takes deliver_yuv422_pixels<layout> pixels, 16-byte loads of consecutive bytes, and a wave reads its stretch of the row
+//   without a gap.  U8: 32 pixels, four loads (64 bytes); luma and chroma separated in registers (v_perm_b32: six per load), two 16-byte stores of luma and one
+//   16-byte store per chroma plane.  U16 (YU64): 16 pixels, four loads; four v_perm_b32 per load, two 16-byte stores of luma, one per chroma plane.  F16: 16 pixels,
+//   two loads of an 8-bit row or four of a YU64 row; every byte converted straight out of its longword (v_cvt_f32_ubyte0 .. 3; YU64: the words out of the halves of
+//   their longwords), one multiply, v_cvt_pk_f16_f32; two 16-byte stores of luma, one per chroma plane.  F32: 8 pixels, one load or two, the same conversion, two
+//   16-byte stores of luma and one per chroma plane -- measured, a lane's stores to one plane row are best kept to 32 consecutive bytes (four stores of 64 bytes a
+//   lane ran at 3.8 TB/s, two of 32 bytes run at the rate of the other layouts; 16 against 32 pixels a lane for U8 was measured too: DESIGN.md section 5).  Every
+//   store instruction of a wave writes consecutive pieces of one plane row.
+//   The widths the decode queue serves are multiples of 16 at full resolution and of 8 at half resolution: behind the last whole group a row may have groups of
+//   eight pixels left (one at 16 pixels a lane, up to three at 32), which go the same way through fewer loads and narrower stores, spread over the lanes like the
+//   whole groups (U8: 8 bytes of luma, a longword per chroma plane).  The batch's
+//   pictures come from hipMalloc and lie rows x row bytes apart, the entry point admits only pointers and strides that are multiples of 16 and pitches that are
+//   multiples of 32 (the chroma pitch: of 16), and checks the rest where the layout is set: every row on either side starts on a 16-byte boundary.
+// No LDS, no scratch.  Grid (row pieces: dec_deliver_pieces(rows), pictures), DEC_DELIVER_WAVES rows per piece and step.
+// ---------------------------------------------------------------------------------------------
+// the pixels a lane takes per step, by the element type (measured: DESIGN.md section 5)
+template <int LAYOUT> struct deliver_yuv422_pixels { static constexpr int value = LAYOUT == DELIVER_YUV422_U8 ? 32 : (LAYOUT == DELIVER_YUV422_F32 ? 8 : 16); };
+
+// K longwords at `at`: 16-byte stores (at: a multiple of 16), one 8-byte store, one longword
+template <int K> __device__ __forceinline__ void deliver_store_longwords(uint8_t *at, const uint32_t *d)
+{
+	if constexpr (K >= 4) { for (int k = 0; k < K; k += 4) store_u32x4_global(at + 4 * k, d[k], d[k + 1], d[k + 2], d[k + 3]); }
+	else if constexpr (K == 2) store_u32x2_dword_aligned((uint32_t *)at, d[0], d[1]);
+	else *(uint32_t *)at = d[0];
+}
+// N values of the F32 rule as the elements of LAYOUT (F32: the singles; F16: deliver_f16_bits, two to a longword)
+template <int LAYOUT, int N> __device__ __forceinline__ void deliver_store_floats(uint8_t *at, const float *f)
+{
+	if constexpr (LAYOUT == DELIVER_YUV422_F32) {
+		uint32_t d[N];
+		for (int k = 0; k < N; k++) memcpy(&d[k], &f[k], 4);
+		deliver_store_longwords<N>(at, d);
+	} else {
+		uint32_t d[N / 2];
+		for (int k = 0; k < N / 2; k++) d[k] = deliver_f16_bits(f[2 * k]) | (deliver_f16_bits(f[2 * k + 1]) << 16);
+		deliver_store_longwords<N / 2>(at, d);
+	}
+}
+// N pixels (8 or a multiple of 16) of an 8-bit row, 2 N bytes at `in`, to their places in the three plane rows
+template <int ORDER, int LAYOUT, int N> __device__ __forceinline__ void deliver_yuv422_bytes(const uint8_t *in, uint8_t *y, uint8_t *cb, uint8_t *cr)
+{
+	uint32_t p[N / 2];                                           // a longword per pair of pixels
+	for (int k = 0; k < N / 8; k++) { const cfhd_u4 v = CFHD_LDG128(in + 16 * k); p[4 * k] = v.x; p[4 * k + 1] = v.y; p[4 * k + 2] = v.z; p[4 * k + 3] = v.w; }
+	if constexpr (LAYOUT == DELIVER_YUV422_U8) {
+		// of two longwords (a: bytes 0 .. 3, b: 4 .. 7 of the selector) the four luma bytes, and the chroma bytes as Cb Cb Cr Cr
+		constexpr uint32_t sel_y = ORDER == YUV422_YUY2 ? 0x06040200u : 0x07050301u, sel_c = ORDER == YUV422_YUY2 ? 0x07030501u : 0x06020400u;
+		uint32_t yy[N / 4], u[N / 8], v[N / 8];
+		for (int k = 0; k < N / 8; k++) {
+			yy[2 * k] = byte_perm(p[4 * k + 1], p[4 * k], sel_y); yy[2 * k + 1] = byte_perm(p[4 * k + 3], p[4 * k + 2], sel_y);
+			const uint32_t c01 = byte_perm(p[4 * k + 1], p[4 * k], sel_c), c23 = byte_perm(p[4 * k + 3], p[4 * k + 2], sel_c);
+			u[k] = deliver_lo_lo(c01, c23); v[k] = deliver_hi_hi(c01, c23);
+		}
+		deliver_store_longwords<N / 4>(y, yy); deliver_store_longwords<N / 8>(cb, u); deliver_store_longwords<N / 8>(cr, v);
+	} else {
+		constexpr int Y0 = ORDER == YUV422_YUY2 ? 0 : 8, CB = ORDER == YUV422_YUY2 ? 8 : 0;      // the bit positions of Y0 and Cb in the longword; Y1 and Cr: 16 further
+		float yf[N], uf[N / 2], vf[N / 2];
+		for (int j = 0; j < N / 2; j++) {
+			yf[2 * j] = deliver_unit_f32_of<255>((p[j] >> Y0) & 0xffu); yf[2 * j + 1] = deliver_unit_f32_of<255>((p[j] >> (Y0 + 16)) & 0xffu);
+			uf[j] = deliver_unit_f32_of<255>((p[j] >> CB) & 0xffu); vf[j] = deliver_unit_f32_of<255>((p[j] >> (CB + 16)) & 0xffu);
+		}
+		deliver_store_floats<LAYOUT, N>(y, yf); deliver_store_floats<LAYOUT, N / 2>(cb, uf); deliver_store_floats<LAYOUT, N / 2>(cr, vf);
+	}
+}
+// N pixels (a multiple of 8) of a YU64 row, 4 N bytes at `in`: the longwords (Y0, Cr), (Y1, Cb) of every pair of pixels
+template <int LAYOUT, int N> __device__ __forceinline__ void deliver_yuv422_words(const uint8_t *in, uint8_t *y, uint8_t *cb, uint8_t *cr)
+{
+	uint32_t p[N];
+	for (int k = 0; k < N / 4; k++) { const cfhd_u4 v = CFHD_LDG128(in + 16 * k); p[4 * k] = v.x; p[4 * k + 1] = v.y; p[4 * k + 2] = v.z; p[4 * k + 3] = v.w; }
+	if constexpr (LAYOUT == DELIVER_YUV422_U16) {
+		uint32_t yy[N / 2], u[N / 4], v[N / 4];
+		for (int k = 0; k < N / 4; k++) {
+			yy[2 * k] = deliver_lo_lo(p[4 * k], p[4 * k + 1]); yy[2 * k + 1] = deliver_lo_lo(p[4 * k + 2], p[4 * k + 3]);
+			v[k] = deliver_hi_hi(p[4 * k], p[4 * k + 2]); u[k] = deliver_hi_hi(p[4 * k + 1], p[4 * k + 3]);
+		}
+		deliver_store_longwords<N / 2>(y, yy); deliver_store_longwords<N / 4>(cb, u); deliver_store_longwords<N / 4>(cr, v);
+	} else {
+		float yf[N], uf[N / 2], vf[N / 2];
+		for (int j = 0; j < N / 2; j++) {
+			yf[2 * j] = deliver_unit_f32_of<65535>(p[2 * j] & 0xffffu); yf[2 * j + 1] = deliver_unit_f32_of<65535>(p[2 * j + 1] & 0xffffu);
+			vf[j] = deliver_unit_f32_of<65535>(p[2 * j] >> 16); uf[j] = deliver_unit_f32_of<65535>(p[2 * j + 1] >> 16);
+		}
+		deliver_store_floats<LAYOUT, N>(y, yf); deliver_store_floats<LAYOUT, N / 2>(cb, uf); deliver_store_floats<LAYOUT, N / 2>(cr, vf);
+	}
+}
+// one row of `width` pixels
+template <int ORDER, int LAYOUT> __device__ __forceinline__ void deliver_yuv422_row(const uint8_t *row, int width, uint8_t *y, uint8_t *cb, uint8_t *cr, int lane)
+{
+	constexpr int E = LAYOUT == DELIVER_YUV422_U8 ? 1 : (LAYOUT == DELIVER_YUV422_F32 ? 4 : 2);
+	constexpr int P = deliver_yuv422_pixels<LAYOUT>::value;
+	const int groups = width / P, units = width >> 3;            // (every width served is a multiple of 8)
+	// whole groups, then the groups of eight behind the last whole one (P = 16: one, in half-resolution pictures; P = 32: up to three; P = 8: none)
+	if constexpr (ORDER == YUV422_YU64) {
+		for (int g = lane; g < groups; g += 64) deliver_yuv422_words<LAYOUT, P>(row + 4 * P * g, y + P * E * g, cb + (P / 2) * E * g, cr + (P / 2) * E * g);
+		for (int u = groups * (P / 8) + lane; u < units; u += 64) deliver_yuv422_words<LAYOUT, 8>(row + 32 * u, y + 8 * E * u, cb + 4 * E * u, cr + 4 * E * u);
+	} else {
+		for (int g = lane; g < groups; g += 64) deliver_yuv422_bytes<ORDER, LAYOUT, P>(row + 2 * P * g, y + P * E * g, cb + (P / 2) * E * g, cr + (P / 2) * E * g);
+		for (int u = groups * (P / 8) + lane; u < units; u += 64) deliver_yuv422_bytes<ORDER, LAYOUT, 8>(row + 16 * u, y + 8 * E * u, cb + 4 * E * u, cr + 4 * E * u);
+	}
+}
+
+__global__ void __launch_bounds__(DEC_DELIVER_THREADS) k_dec_deliver_yuv422(const uint8_t *src, size_t src_stride, int rows, int width, uint8_t *dst, size_t dst_stride, int dst_pitch, int layout, int order)
+{
+	const int lane = (int)(threadIdx.x & 63u), wave = wave_uniform((int)(threadIdx.x >> 6));
+	const uint8_t *pic = src + src_stride * (size_t)blockIdx.y;
+	uint8_t *out = dst + dst_stride * (size_t)blockIdx.y;
+	const int row_bytes = (order == YUV422_YU64 ? 4 : 2) * width, chroma_pitch = dst_pitch >> 1;
+	uint8_t *cb_plane = out + (size_t)dst_pitch * (size_t)rows, *cr_plane = cb_plane + (size_t)chroma_pitch * (size_t)rows;
+	for (int r = (int)blockIdx.x * DEC_DELIVER_WAVES + wave; r < rows; r += (int)gridDim.x * DEC_DELIVER_WAVES) {
+		const uint8_t *row = pic + (size_t)r * row_bytes;
+		uint8_t *y = out + (size_t)r * dst_pitch, *cb = cb_plane + (size_t)r * chroma_pitch, *cr = cr_plane + (size_t)r * chroma_pitch;
+		if (order == YUV422_YU64) {
+			if (layout == DELIVER_YUV422_U16) deliver_yuv422_row<YUV422_YU64, DELIVER_YUV422_U16>(row, width, y, cb, cr, lane);
+			else if (layout == DELIVER_YUV422_F16) deliver_yuv422_row<YUV422_YU64, DELIVER_YUV422_F16>(row, width, y, cb, cr, lane);
+			else deliver_yuv422_row<YUV422_YU64, DELIVER_YUV422_F32>(row, width, y, cb, cr, lane);
+		} else if (order == YUV422_YUY2) {
+			if (layout == DELIVER_YUV422_U8) deliver_yuv422_row<YUV422_YUY2, DELIVER_YUV422_U8>(row, width, y, cb, cr, lane);
+			else if (layout == DELIVER_YUV422_F16) deliver_yuv422_row<YUV422_YUY2, DELIVER_YUV422_F16>(row, width, y, cb, cr, lane);
+			else deliver_yuv422_row<YUV422_YUY2, DELIVER_YUV422_F32>(row, width, y, cb, cr, lane);
+		} else {
+			if (layout == DELIVER_YUV422_U8) deliver_yuv422_row<YUV422_2VUY, DELIVER_YUV422_U8>(row, width, y, cb, cr, lane);
+			else if (layout == DELIVER_YUV422_F16) deliver_yuv422_row<YUV422_2VUY, DELIVER_YUV422_F16>(row, width, y, cb, cr, lane);
+			else deliver_yuv422_row<YUV422_2VUY, DELIVER_YUV422_F32>(row, width, y, cb, cr, lane);
 		}
 	}
 }

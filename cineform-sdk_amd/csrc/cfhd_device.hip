@@ -605,6 +605,30 @@ static int collect_planar_frames(int pixel_kind, uint8_t *slots, size_t frame_by
 	const bool bayer = pixel_kind == PIX_BYR4;
 	if (pixel_kind == PIX_BYR5) return refuse("frames from planar tensors: BYR5 mosaics are not served (BYR4 mosaics are, from four planes)");
 	if (bayer && !dev::collect_is_bayer(layout)) return refuse("frames from planar tensors: a BYR4 batch takes the four planes of a mosaic (the BAYER layouts) and no other layout");
+	// A packed 4:2:2 batch (YUY2, 2vuy, YU64; width and rows: the frame's; slot rows of 2 x or 4 x width bytes) takes the YUV422_* layouts: a luma plane and two chroma
+	// planes of half the width through k_enc_collect_yuv422.  To every other batch but a Bayer one those layouts are named as what they are.
+	if (dev::collect_is_yuv422(layout)) {
+		if (pixel_kind != PIX_YUY2 && pixel_kind != PIX_2VUY && pixel_kind != PIX_YU64) return refuse("frames from planar tensors: the 4:2:2 plane layouts serve batches whose input is YUY2, 2vuy or YU64");
+		const bool words = pixel_kind == PIX_YU64;
+		if (layout == dev::COLLECT_YUV422_U8 && words) return refuse("frames from planar tensors: YUV422_U8 serves the 8-bit inputs YUY2 and 2vuy; a YU64 batch takes YUV422_U16");
+		if (layout == dev::COLLECT_YUV422_U16 && !words) return refuse("frames from planar tensors: YUV422_U16 serves YU64; a YUY2 or 2vuy batch takes YUV422_U8");
+		if (count < 1 || first < 0 || first > nframes - count) return refuse("frames from planar tensors: the run of frames leaves the batch");
+		if (!d_frames) return refuse("frames from planar tensors: no pointer");
+		if (((uintptr_t)d_frames | frame_stride | (size_t)(unsigned)row_pitch) & 15) return refuse("frames from planar tensors: pointer, frame stride and row pitch are multiples of 16");
+		if (row_pitch & 31) return refuse("frames from planar tensors: the row pitch of a 4:2:2 plane layout is a multiple of 32 (the chroma planes' is half of it)");
+		if (row_pitch < 0 || (long long)row_pitch < (long long)width * dev::collect_yuv422_element_bytes(layout)) return refuse("frames from planar tensors: a row pitch below the luma row of the 4:2:2 plane layout (width x element size)");
+		if (frame_stride < 2 * (size_t)rows * (size_t)row_pitch) return refuse("frames from planar tensors: a frame stride below the three planes of the 4:2:2 layout (2 x height x row pitch)");
+		if ((width & 15) || slot_pitch != (words ? 4 : 2) * width || frame_bytes != (size_t)slot_pitch * rows || (((uintptr_t)slots | frame_bytes) & 15) || count > 65535 /* blockIdx.y */)
+			return refuse("frames from planar tensors: frame slots the 4:2:2 collect kernel does not take");
+		int rc = times.record(stream, false);
+		if (rc) return rc;
+		(void)hipGetLastError();
+		dev::k_enc_collect_yuv422<<<dim3(dev::enc_collect_pieces(rows), (unsigned)count), dev::ENC_COLLECT_THREADS, 0, (hipStream_t)stream>>>(
+			(const uint8_t *)d_frames, frame_stride, row_pitch, rows, width, slots + frame_bytes * (size_t)first, frame_bytes, layout,
+			words ? dev::COLLECT_ORDER_YU64 : (pixel_kind == PIX_2VUY ? dev::COLLECT_ORDER_2VUY : dev::COLLECT_ORDER_YUY2));
+		HIPCHK(hipGetLastError());
+		return times.record(stream, true);
+	}
 	if (!bayer && pixel_kind != PIX_RG48) return refuse(dev::collect_is_bayer(layout) ? "frames from planar tensors: the batch's input is not BYR4" : "frames from planar tensors: the batch's input is not RG48");
 	if (!bayer && layout != dev::COLLECT_PLANAR_U16 && layout != dev::COLLECT_PLANAR_F16 && layout != dev::COLLECT_PLANAR_F32) return refuse("frames from planar tensors: unknown layout");
 	if (count < 1 || first < 0 || first > nframes - count) return refuse("frames from planar tensors: the run of frames leaves the batch");

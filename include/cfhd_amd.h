@@ -19,7 +19,9 @@
  * returns CFHD_ERROR_BADFORMAT (3) / CFHD_ERROR_BAD_RESOLUTION (11).
  * Both queues of the extension API have a device-memory side: the decode queue delivers its pictures into device memory the caller owns, packed or -- RG48 -- as
  * planar R, G, B tensors of u16 / f16 / f32 (cfhd_amd_decode_batch_set_device_pictures), the frame queue takes frames that lie in device memory
- * (cfhd_amd_batch_upload_device).
+ * (cfhd_amd_batch_upload_device) or there as planar tensors (cfhd_amd_batch_upload_device_planar).  The plane layouts of both sides: RG48 as R, G, B, BYR4 mosaics as
+ * the four planes of the 2 x 2 quad, and the packed 4:2:2 formats YUY2 / 2vuy / YU64 as Y, Cb, Cr in the I422 convention (CFHD_AMD_PICTURES_YUV422_* /
+ * CFHD_AMD_FRAMES_YUV422_*), each as integer, f16 or f32 elements.
  * There is no CPU fallback: without a HIP device the encode/decode calls return CFHD_ERROR_INTERNAL (6).
  */
 #ifndef CFHD_AMD_H
@@ -183,9 +185,22 @@ int  cfhd_amd_batch_upload_device(cfhd_amd_batch *batch, int frame, const void *
  * row_pitch bytes apart, planes (H / 2) * row_pitch apart: the geometry of CFHD_AMD_PICTURES_BAYER_*.  A contiguous tensor (n, 4, H / 2, W / 2) is row_pitch =
  * (W / 2) * element size, frame_stride = 4 * (H / 2) * row_pitch.  The element rules are the ones above, on the 16-bit photosite word, and so are the inversion
  * properties.  One launch of k_enc_collect_bayer per run (per chunk of a cut intra batch), timed under index 20; cfhd_amd_batch_kernel_name(batch, 20) answers
- * "k_enc_collect_bayer" for a BYR4 batch.  Refused as above, with W / 2 for the width and a frame stride below 4 * (H / 2) * row_pitch. */
+ * "k_enc_collect_bayer" for a BYR4 batch.  Refused as above, with W / 2 for the width and a frame stride below 4 * (H / 2) * row_pitch.
+ * CFHD_AMD_FRAMES_YUV422_U8 / _U16 / _F16 / _F32: the same for every batch whose pixel format is YUY2, 2vuy or YU64 -- cfhd_amd_batch_create, _create_ex, _create_groups,
+ * _create_stream, _create_group_stream; interlaced YUY2 / 2vuy included, the frame rows in their frame order -- and for no other (v210, the Avid layouts and the RGB
+ * formats are refused with a text of their own; to a BYR4 batch the values are unknown layouts).  A frame of W x H pixels is read as three planes in the I422
+ * convention, the geometry of CFHD_AMD_PICTURES_YUV422_*: Y, H rows of W elements row_pitch bytes apart, at 0; Cb, H rows of W / 2 elements row_pitch / 2 bytes apart,
+ * at H * row_pitch; Cr, the same, at H * row_pitch + H * row_pitch / 2 -- always Y, Cb, Cr, whatever the packed order (Cb becomes byte 1 of YUY2's Y0 U Y1 V, byte 0
+ * of 2vuy's U Y0 V Y1, word 3 of YU64's Y0 C1 Y1 C2; Cr byte 3, byte 2, word 1).  A contiguous frame is row_pitch = W * element size, frame_stride = 2 * H *
+ * row_pitch.  _U8 exists for YUY2 and 2vuy only, _U16 for YU64 only: the element as it is.  _F16 / _F32: the rules above with the unit of the batch's own word,
+ * 255 or 65535 (t = x * unit, NaN to 0, clamped to [0, unit], rounded to nearest even); no range scaling, no chroma offset.  The inversion properties: for the
+ * 16-bit unit as above; for the 8-bit unit collect(deliver(b)) = b for all 256 bytes through U8, F32 and also F16 (the binary16 values of b / 255 are 256 distinct
+ * numbers that come back within 0.063 of b).  One launch of k_enc_collect_yuv422 per run (per chunk of a cut intra batch), timed under index 20;
+ * cfhd_amd_batch_kernel_name(batch, 20) answers "k_enc_collect_yuv422" for a batch of these three formats.  Refused as above, and: _U8 on a YU64 batch, _U16 on an
+ * 8-bit one, a row pitch that is no multiple of 32 or below W * element size, a frame stride below 2 * H * row_pitch. */
 enum { CFHD_AMD_FRAMES_PLANAR_U16 = 1, CFHD_AMD_FRAMES_PLANAR_F16 = 2, CFHD_AMD_FRAMES_PLANAR_F32 = 3 };      /* values equal to CFHD_AMD_PICTURES_PLANAR_* */
 enum { CFHD_AMD_FRAMES_BAYER_U16 = 4, CFHD_AMD_FRAMES_BAYER_F16 = 5, CFHD_AMD_FRAMES_BAYER_F32 = 6 };         /* values equal to CFHD_AMD_PICTURES_BAYER_* */
+enum { CFHD_AMD_FRAMES_YUV422_U8 = 7, CFHD_AMD_FRAMES_YUV422_U16 = 8, CFHD_AMD_FRAMES_YUV422_F16 = 9, CFHD_AMD_FRAMES_YUV422_F32 = 10 };      /* values equal to CFHD_AMD_PICTURES_YUV422_* */
 int  cfhd_amd_batch_upload_device_planar(cfhd_amd_batch *batch, int first_frame, int count, const void *d_frames, size_t frame_stride, int row_pitch, int layout);
 /* Frame `frame` as the batch holds it, in its packed input format, into out (rows `pitch` >= row bytes apart): the twin of cfhd_amd_batch_download_output for the
  * input side, for every kind of batch and input format (av28: the frame's one block as one row).  Waits for the stream the uploads run on.  0; -1 for bad arguments
@@ -380,12 +395,27 @@ int  cfhd_amd_decode_batch_submit_device(cfhd_amd_decode_batch *batch, const voi
  * B.  Rows picture_pitch bytes apart, planes (H / 2) * picture_pitch apart: a contiguous tensor (n, 4, H / 2, W / 2) is picture_pitch = (W / 2) * element size,
  * picture_stride = 4 * (H / 2) * picture_pitch.  The element rules are the RG48 ones on the 16-bit photosite word.  Written by k_dec_deliver_bayer in place of
  * k_dec_deliver (cfhd_amd_decode_batch_kernel_name(batch, 9) answers it while such a layout is set; kernel_ms index 9 times it).
+ * CFHD_AMD_PICTURES_YUV422_U8 / _U16 / _F16 / _F32: every batch whose output is YUY2, 2vuy or YU64 -- intra batches of progressive and interlaced samples, group
+ * batches, full and half resolution -- and no other (v210 and the RGB outputs are refused with a text of their own; to a Bayer batch the values are unknown layouts).
+ * The picture of W x H pixels (cfhd_amd_decode_batch_geometry) is three planes in one block, the I422 convention: Y, H rows of W elements picture_pitch bytes apart, at
+ * 0; Cb, H rows of W / 2 elements picture_pitch / 2 bytes apart, at H * picture_pitch; Cr, the same, at H * picture_pitch + H * picture_pitch / 2 -- always Y, Cb, Cr,
+ * whatever the packed order (Cb is byte 1 of YUY2's Y0 U Y1 V, byte 0 of 2vuy's U Y0 V Y1, word 3 of YU64's Y0 C1 Y1 C2; Cr byte 3, byte 2, word 1); interlaced
+ * pictures keep their frame rows.  A contiguous picture is picture_pitch = W * element size and occupies 2 * H * picture_pitch bytes: one row of a torch tensor
+ * (n, 2 * H * W) views as Y (H, W) and CbCr (2, H, W / 2).  _U8 exists for YUY2 and 2vuy only, _U16 for YU64 only: the byte or word as it is.  _F32: (float)w *
+ * (1.0f / unit) with the unit of the batch's own word, 255 or 65535, one IEEE single multiply; _F16: that value rounded to nearest-even to binary16, subnormals
+ * kept.  No range scaling and no chroma offset: 0.5 is roughly neutral chroma.  CFHD_AMD_FRAMES_YUV422_* of cfhd_amd_batch_upload_device_planar invert these rules:
+ * for the 8-bit unit collect(deliver(b)) = b for all 256 bytes through U8, F32 and also F16; for the 16-bit unit U16 and F32 are exact for all 65 536 words and F16
+ * is idempotent.  The pitch is a multiple of 32 (the chroma pitch: of 16) and >= W * element size; the stride is >= H * picture_pitch + (2 H - 1) * (picture_pitch / 2)
+ * + the chroma row bytes.  Written by k_dec_deliver_yuv422 in place of k_dec_deliver (kernel_name(batch, 9) answers it while such a layout is set; kernel_ms index 9
+ * times it).
  * Exactly count pictures are written, of every row its row bytes and nothing else: pitch padding, the space between planes and pictures and the pictures behind a short
  * pass are not touched.
  * 0; -1 with the reason in cfhd_amd_last_error(): a pass in flight, an unknown layout, a planar layout on a batch whose output is not RG48, a pointer, stride or pitch
- * that is no multiple of 16, a pitch below the row bytes of the layout, a stride below what one picture occupies. */
+ * that is no multiple of 16, a pitch below the row bytes of the layout, a stride below what one picture occupies; a 4:2:2 plane layout on a batch whose output is not
+ * YUY2, 2vuy or YU64, _U8 on a YU64 batch, _U16 on an 8-bit one, a pitch of such a layout that is no multiple of 32. */
 enum { CFHD_AMD_PICTURES_PACKED = 0, CFHD_AMD_PICTURES_PLANAR_U16 = 1, CFHD_AMD_PICTURES_PLANAR_F16 = 2, CFHD_AMD_PICTURES_PLANAR_F32 = 3 };
 enum { CFHD_AMD_PICTURES_BAYER_U16 = 4, CFHD_AMD_PICTURES_BAYER_F16 = 5, CFHD_AMD_PICTURES_BAYER_F32 = 6 };
+enum { CFHD_AMD_PICTURES_YUV422_U8 = 7, CFHD_AMD_PICTURES_YUV422_U16 = 8, CFHD_AMD_PICTURES_YUV422_F16 = 9, CFHD_AMD_PICTURES_YUV422_F32 = 10 };
 int  cfhd_amd_decode_batch_set_device_pictures(cfhd_amd_decode_batch *batch, void *d_pictures, size_t picture_stride, int picture_pitch, int layout);
 /* Collects the pass: the number of samples that decoded, or < 0 (-1: nothing in flight, -2: device failure).  status (NULL or count entries): status[i] is the CFHD_Error
  * CFHD_DecodeSample returns for sample i on a handle prepared on the first sample; the picture of a sample that failed is zero.  Samples the device parser refuses are
@@ -398,7 +428,7 @@ int  cfhd_amd_decode_batch_wait(cfhd_amd_decode_batch *batch, CFHD_Error *status
 int  cfhd_amd_decode_batch_download_output(cfhd_amd_decode_batch *batch, int i, void *out, int pitch);
 /* HIP-event time (ms) of the kernels of the last pass and their names as a profiler shows them.  which: 0 k_dec_ingest, 1 k_dec_parse, 2 the band decoder (all its
  * kernels), 3 k_dec_lowpass, 4 / 5 / 6 the transform levels in launch order (the last one with the output conversion), 7 k_dec_blank, 9 k_dec_deliver (both kinds of
- * batch; k_dec_deliver_bayer while a BAYER_* layout is set; 0 ms when the last pass delivered nothing into device memory).  0 / "" otherwise. */
+ * batch; k_dec_deliver_bayer while a BAYER_* layout is set, k_dec_deliver_yuv422 while a YUV422_* one is; 0 ms when the last pass delivered nothing into device memory).  0 / "" otherwise. */
 float cfhd_amd_decode_batch_kernel_ms(cfhd_amd_decode_batch *batch, int which);
 const char *cfhd_amd_decode_batch_kernel_name(cfhd_amd_decode_batch *batch, int which);
 int  cfhd_amd_device_count(void);
