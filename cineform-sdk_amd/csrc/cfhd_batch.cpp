@@ -695,7 +695,7 @@ int cfhd_amd_batch_upload_device(cfhd_amd_batch *b, int i, const void *d_frame, 
 }
 
 // Frames first_frame .. first_frame + count - 1 of an RG48 batch from planar R, G, B tensors -- of a BYR4 batch from the four planes of a mosaic, k_enc_collect_bayer; of
-// a YUY2, 2vuy or YU64 batch from a luma and two chroma planes, k_enc_collect_yuv422 -- in HBM on the batch's device: one k_enc_collect launch on the stream the
+// a YUY2, 2vuy or YU64 batch from a luma and two chroma planes, k_enc_collect_yuv422; of a b64a, BGRA or BGRa batch from four planes R, G, B, A, k_enc_collect_rgba -- in HBM on the batch's device: one k_enc_collect launch on the stream the
 // pass runs on (an intra batch cut into chunks: one per chunk the run touches, on that chunk's stream), no staging, no host wait.  The gates that need the geometry
 // are the encoder objects' (collect_planar_frames, cfhd_device.hip); they depend on nothing a chunk has of its own, so a run is refused before any of it is launched.
 int cfhd_amd_batch_upload_device_planar(cfhd_amd_batch *b, int first_frame, int count, const void *d_frames, size_t frame_stride, int row_pitch, int layout)
@@ -1019,6 +1019,7 @@ int cfhd_amd_quantizer_is_static(int width, int height, uint32_t pixel_format, i
 const char *cfhd_amd_batch_kernel_name(cfhd_amd_batch *b, int which)
 {
 	if (b && which == 20 && (b->pixel_kind == PIX_YUY2 || b->pixel_kind == PIX_2VUY || b->pixel_kind == PIX_YU64)) return "k_enc_collect_yuv422";      // (the kernel a packed 4:2:2 batch's plane layouts run)
+	if (b && which == 20 && (b->pixel_kind == PIX_B64A || b->pixel_kind == PIX_BGRA || b->pixel_kind == PIX_BGRa)) return "k_enc_collect_rgba";      // (... a b64a, BGRA or BGRa batch's)
 	if (b && which == 20) return !b->gop && b->pixel_kind == PIX_BYR4 ? "k_enc_collect_bayer" : "k_enc_collect";
 	if (b && b->gop) { CallerDevice caller_device; return which < 0 || which > 5 || b->in_flight || (which >= 3 && !b->decode) ? "" : (which < 3 ? b->genc->stage_kernel(which) : b->gdec->stage_kernel(which - 3)); }
 	if (!b || which < 0 || which > 5 || b->chunks.empty() || (which >= 3 && !b->decode)) return "";

@@ -2,7 +2,8 @@
 // device memory as planar R, G, B tensors of u16, f16 or f32 elements (a torch tensor N x 3 x H x W) into the batch's RG48 frame slots, one launch for the whole run
 // (cfhd_amd_batch_upload_device_planar, cfhd_device.hip collect_planar_frames) -- and k_enc_collect_bayer, the same for the BYR4 frames of a Bayer batch out of four
 // planes, one per position of the 2 x 2 quad (N x 4 x H/2 x W/2), and k_enc_collect_yuv422, the same for the packed 4:2:2 frames (YUY2, 2vuy, YU64) of a batch out of
-// a luma plane and two chroma planes of half the width (I422).
+// a luma plane and two chroma planes of half the width (I422), and k_enc_collect_rgba, the same for the four-component frames (b64a, BGRA, BGRa) of a batch out of
+// four planes R, G, B, A, top row first (N x 4 x H x W).
 #pragma once
 #include <stdint.h>
 #include <stddef.h>
@@ -267,6 +268,115 @@ __global__ void __launch_bounds__(ENC_COLLECT_THREADS) k_enc_collect_yuv422(cons
 			if (layout == COLLECT_YUV422_U8) collect_yuv422_row<COLLECT_ORDER_2VUY, COLLECT_YUV422_U8>(y, cb, cr, width, orow, lane);
 			else if (layout == COLLECT_YUV422_F16) collect_yuv422_row<COLLECT_ORDER_2VUY, COLLECT_YUV422_F16>(y, cb, cr, width, orow, lane);
 			else collect_yuv422_row<COLLECT_ORDER_2VUY, COLLECT_YUV422_F32>(y, cb, cr, width, orow, lane);
+		}
+	}
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_enc_collect_rgba: the mirror image of k_dec_deliver_rgba.  Frame i of the run out of src + i * src_stride -- four planes R, G, B, A, top row first, each `rows` rows
+// of `width` elements, rows src_pitch bytes apart, planes rows * src_pitch apart -- into dst + i * dst_stride, the batch's own packed frames: `rows` rows back to back,
+// 8 x width bytes a row (order COLLECT_ORDER_B64A: the native 16-bit words A R G B) or 4 x width (_BGRA, _BGRa: the bytes B G R A).  A BGRA frame lies bottom row first
+// in its slot: plane row r goes to slot row rows - 1 - r, an address.  The source is read, never written.  `layout`: COLLECT_RGBA_U8 (BGRA / BGRa) / _U16 (b64a) -- the
+// element as it is --, _F16 / _F32: collect_word_f32_of with the unit of the frame's own word, 255 or 65535.  Alpha is a component like the others.
+//   A wave owns a row at a time.  b64a: a lane takes 8 pixels, 8 elements of each plane row (one 16-byte load per plane for u16 / f16, two for f32), the words of two
+//   pixels per plane longword dealt to the longwords (A, R), (G, B) of each pixel (v_perm_b32: 16), four 16-byte stores of 64 consecutive bytes: a wave writes 4 KB of
+//   the frame row without a gap.  BGRA / BGRa: 16 pixels for U8 and F16 (one or two 16-byte loads per plane), 8 for F32 (two); the bytes of four pixels per plane
+//   longword transposed in two rounds of v_perm_b32 (8 per four pixels), four or two 16-byte stores of consecutive bytes.  The loads of a wave cover consecutive bytes
+//   of a plane row.
+//   The columns behind the last whole group go element by element (no plan of these formats is known to have any: build_frame_plan, build_gop_plan).  The frame slots
+//   come from hipMalloc and lie rows x row bytes apart, the entry point admits only slot rows, pointers, strides and pitches that are multiples of 16
+//   (collect_planar_frames checks all of it): every row on either side starts on a 16-byte boundary.
+// No LDS, no scratch.  Grid (row pieces: enc_collect_pieces(rows), frames), ENC_COLLECT_WAVES rows per piece and step.
+// ---------------------------------------------------------------------------------------------
+// (CFHD_AMD_FRAMES_RGBA_*) and the packed orders they are collected into
+enum { COLLECT_RGBA_U8 = 11, COLLECT_RGBA_U16 = 12, COLLECT_RGBA_F16 = 13, COLLECT_RGBA_F32 = 14 };
+enum { COLLECT_ORDER_B64A = 0, COLLECT_ORDER_BGRA = 1, COLLECT_ORDER_BGRa = 2 };
+inline bool collect_is_rgba(int layout) { return layout >= COLLECT_RGBA_U8 && layout <= COLLECT_RGBA_F32; }
+inline int collect_rgba_element_bytes(int layout) { return layout == COLLECT_RGBA_U8 ? 1 : (layout == COLLECT_RGBA_F32 ? 4 : 2); }
+// the element type of an RGBA_* layout as the YUV422_* value collect_load_elements is written for
+template <int LAYOUT> struct collect_rgba_as_yuv422 { static constexpr int value = LAYOUT - COLLECT_RGBA_U8 + COLLECT_YUV422_U8; };
+
+// one element of a plane row as the frame's own byte or word (the columns behind the last whole group)
+template <int LAYOUT, int UNIT> __device__ __forceinline__ uint32_t collect_rgba_element(const uint8_t *plane_row, int x)
+{
+	if constexpr (LAYOUT == COLLECT_RGBA_U8) return plane_row[x];
+	else if constexpr (LAYOUT == COLLECT_RGBA_U16) return ((const uint16_t *)plane_row)[x];
+	else if constexpr (LAYOUT == COLLECT_RGBA_F16) return collect_word_f16_of<UNIT>(((const uint16_t *)plane_row)[x]);
+	else return collect_word_f32_of<UNIT>(((const float *)plane_row)[x]);
+}
+// one row of `width` pixels out of row `irow` of plane R (the planes `plane` bytes apart) into a b64a frame row
+template <int LAYOUT> __device__ __forceinline__ void collect_rgba_row_words(const uint8_t *irow, size_t plane, int width, uint8_t *orow, int lane)
+{
+	constexpr int E = LAYOUT == COLLECT_RGBA_F32 ? 4 : 2, L = collect_rgba_as_yuv422<LAYOUT>::value;
+	const int groups = width >> 3;
+	for (int g = lane; g < groups; g += 64) {
+		const uint8_t *at = irow + (size_t)g * 8 * E;
+		uint32_t R[4], G[4], B[4], A[4], o[16];
+		collect_load_elements<L, 65535, 8>(at, R);
+		collect_load_elements<L, 65535, 8>(at + plane, G);
+		collect_load_elements<L, 65535, 8>(at + 2 * plane, B);
+		collect_load_elements<L, 65535, 8>(at + 3 * plane, A);
+		for (int k = 0; k < 4; k++) {
+			o[4 * k] = collect_lo_lo(A[k], R[k]); o[4 * k + 1] = collect_lo_lo(G[k], B[k]);
+			o[4 * k + 2] = collect_hi_hi(A[k], R[k]); o[4 * k + 3] = collect_hi_hi(G[k], B[k]);
+		}
+		uint8_t *to = orow + 64 * (size_t)g;
+		for (int k = 0; k < 16; k += 4) store_u32x4_global(to + 4 * k, o[k], o[k + 1], o[k + 2], o[k + 3]);
+	}
+	for (int x = 8 * groups + lane; x < width; x += 64) {
+		const uint32_t r = collect_rgba_element<LAYOUT, 65535>(irow, x), g = collect_rgba_element<LAYOUT, 65535>(irow + plane, x);
+		const uint32_t b = collect_rgba_element<LAYOUT, 65535>(irow + 2 * plane, x), a = collect_rgba_element<LAYOUT, 65535>(irow + 3 * plane, x);
+		uint32_t *to = (uint32_t *)(orow + 8 * (size_t)x);
+		to[0] = a | (r << 16); to[1] = g | (b << 16);
+	}
+}
+// ... into a row of B G R A bytes
+template <int LAYOUT> __device__ __forceinline__ void collect_rgba_row_bytes(const uint8_t *irow, size_t plane, int width, uint8_t *orow, int lane)
+{
+	constexpr int E = LAYOUT == COLLECT_RGBA_U8 ? 1 : (LAYOUT == COLLECT_RGBA_F32 ? 4 : 2), P = LAYOUT == COLLECT_RGBA_F32 ? 8 : 16, L = collect_rgba_as_yuv422<LAYOUT>::value;
+	const int groups = width / P;
+	for (int g = lane; g < groups; g += 64) {
+		const uint8_t *at = irow + (size_t)g * P * E;
+		uint32_t R[P / 4], G[P / 4], B[P / 4], A[P / 4], o[P];
+		collect_load_elements<L, 255, P>(at, R);
+		collect_load_elements<L, 255, P>(at + plane, G);
+		collect_load_elements<L, 255, P>(at + 2 * plane, B);
+		collect_load_elements<L, 255, P>(at + 3 * plane, A);
+		for (int m = 0; m < P / 4; m++) {
+			// B0 G0 B1 G1 | B2 G2 B3 G3 and R0 A0 R1 A1 | R2 A2 R3 A3, then a longword per pixel
+			const uint32_t bg01 = byte_perm(G[m], B[m], 0x05010400u), bg23 = byte_perm(G[m], B[m], 0x07030602u);
+			const uint32_t ra01 = byte_perm(A[m], R[m], 0x05010400u), ra23 = byte_perm(A[m], R[m], 0x07030602u);
+			o[4 * m] = collect_lo_lo(bg01, ra01); o[4 * m + 1] = collect_hi_hi(bg01, ra01);
+			o[4 * m + 2] = collect_lo_lo(bg23, ra23); o[4 * m + 3] = collect_hi_hi(bg23, ra23);
+		}
+		uint8_t *to = orow + 4 * P * (size_t)g;
+		for (int k = 0; k < P; k += 4) store_u32x4_global(to + 4 * k, o[k], o[k + 1], o[k + 2], o[k + 3]);
+	}
+	for (int x = P * groups + lane; x < width; x += 64) {
+		const uint32_t r = collect_rgba_element<LAYOUT, 255>(irow, x), g = collect_rgba_element<LAYOUT, 255>(irow + plane, x);
+		const uint32_t b = collect_rgba_element<LAYOUT, 255>(irow + 2 * plane, x), a = collect_rgba_element<LAYOUT, 255>(irow + 3 * plane, x);
+		*(uint32_t *)(orow + 4 * (size_t)x) = b | (g << 8) | (r << 16) | (a << 24);
+	}
+}
+
+__global__ void __launch_bounds__(ENC_COLLECT_THREADS) k_enc_collect_rgba(const uint8_t *src, size_t src_stride, int src_pitch, int rows, int width, uint8_t *dst, size_t dst_stride, int layout, int order)
+{
+	const int lane = (int)(threadIdx.x & 63u), wave = wave_uniform((int)(threadIdx.x >> 6));
+	const uint8_t *in = src + src_stride * (size_t)blockIdx.y;
+	uint8_t *frame = dst + dst_stride * (size_t)blockIdx.y;
+	const int row_bytes = (order == COLLECT_ORDER_B64A ? 8 : 4) * width;
+	const size_t plane = (size_t)src_pitch * (size_t)rows;
+	for (int r = (int)blockIdx.x * ENC_COLLECT_WAVES + wave; r < rows; r += (int)gridDim.x * ENC_COLLECT_WAVES) {
+		const uint8_t *irow = in + (size_t)r * src_pitch;
+		uint8_t *orow = frame + (size_t)(order == COLLECT_ORDER_BGRA ? rows - 1 - r : r) * row_bytes;
+		if (order == COLLECT_ORDER_B64A) {
+			if (layout == COLLECT_RGBA_U16) collect_rgba_row_words<COLLECT_RGBA_U16>(irow, plane, width, orow, lane);
+			else if (layout == COLLECT_RGBA_F16) collect_rgba_row_words<COLLECT_RGBA_F16>(irow, plane, width, orow, lane);
+			else collect_rgba_row_words<COLLECT_RGBA_F32>(irow, plane, width, orow, lane);
+		} else {
+			if (layout == COLLECT_RGBA_U8) collect_rgba_row_bytes<COLLECT_RGBA_U8>(irow, plane, width, orow, lane);
+			else if (layout == COLLECT_RGBA_F16) collect_rgba_row_bytes<COLLECT_RGBA_F16>(irow, plane, width, orow, lane);
+			else collect_rgba_row_bytes<COLLECT_RGBA_F32>(irow, plane, width, orow, lane);
 		}
 	}
 }

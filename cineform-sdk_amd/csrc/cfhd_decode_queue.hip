@@ -152,6 +152,14 @@ int launch_deliver(cfhd_amd_decode_batch *b, int first, int count)
 		HIPCHK(hipGetLastError());
 		return 0;
 	}
+	if (dev::deliver_is_rgba(b->dev_out_layout)) {       // b64a, BGRA, BGRa pictures as four planes R, G, B, A, top row first (set_device_pictures checked the geometry the kernel assumes)
+		const int order = b->st.out_kind == PIX_B64A ? dev::RGBA_B64A : (b->st.out_kind == PIX_BGRA ? dev::RGBA_BGRA : dev::RGBA_BGRa);
+		dev::k_dec_deliver_rgba<<<dim3(dev::dec_deliver_pieces(b->picture_rows()), (unsigned)count), dev::DEC_DELIVER_THREADS, 0, (hipStream_t)b->stream()>>>(
+			b->device_pictures() + b->picture_bytes() * (size_t)first, b->picture_bytes(), b->picture_rows(), b->picture_width(),
+			b->dev_out + b->dev_out_stride * (size_t)first, b->dev_out_stride, b->dev_out_pitch, b->dev_out_layout, order);
+		HIPCHK(hipGetLastError());
+		return 0;
+	}
 	dev::k_dec_deliver<<<dim3(dev::dec_deliver_pieces(b->picture_rows()), (unsigned)count), dev::DEC_DELIVER_THREADS, 0, (hipStream_t)b->stream()>>>(
 		b->device_pictures() + b->picture_bytes() * (size_t)first, b->picture_bytes(), b->picture_pitch(), b->picture_rows(), b->picture_width(),
 		b->dev_out + b->dev_out_stride * (size_t)first, b->dev_out_stride, b->dev_out_pitch, b->dev_out_layout);
@@ -418,14 +426,20 @@ int cfhd_amd_decode_batch_set_device_pictures(cfhd_amd_decode_batch *b, void *d_
 	const bool bayer = dev::deliver_is_bayer(layout) && !b->groups && b->st.out_kind == PIX_BYR4;
 	// (the YUV422_* layouts exist for packed 4:2:2 pictures: to a Bayer batch they are unknown, every other output that is not YUY2, 2vuy or YU64 is told so)
 	const bool yuv422 = dev::deliver_is_yuv422(layout) && b->st.out_kind != PIX_BYR4;
-	if (!bayer && !yuv422 && (layout < CFHD_AMD_PICTURES_PACKED || layout > CFHD_AMD_PICTURES_PLANAR_F32)) { refuse("decode queue: unknown layout of the device pictures"); return -1; }
+	// (the RGBA_* layouts exist for the pictures that carry an alpha component -- b64a, BGRA, BGRa --: to every other batch they are unknown)
+	const bool rgba = dev::deliver_is_rgba(layout) && (b->st.out_kind == PIX_B64A || b->st.out_kind == PIX_BGRA || b->st.out_kind == PIX_BGRa);
+	if (!bayer && !yuv422 && !rgba && (layout < CFHD_AMD_PICTURES_PACKED || layout > CFHD_AMD_PICTURES_PLANAR_F32)) { refuse("decode queue: unknown layout of the device pictures"); return -1; }
 	if (yuv422) {
 		const int kind = b->st.out_kind;
 		if (kind != PIX_YUY2 && kind != PIX_2VUY && kind != PIX_YU64) { refuse("decode queue: the 4:2:2 plane layouts serve batches whose output is YUY2, 2vuy or YU64"); return -1; }
 		if (layout == CFHD_AMD_PICTURES_YUV422_U8 && kind == PIX_YU64) { refuse("decode queue: YUV422_U8 serves the 8-bit outputs YUY2 and 2vuy; a YU64 batch delivers YUV422_U16"); return -1; }
 		if (layout == CFHD_AMD_PICTURES_YUV422_U16 && kind != PIX_YU64) { refuse("decode queue: YUV422_U16 serves YU64; a YUY2 or 2vuy batch delivers YUV422_U8"); return -1; }
 	}
-	const bool planar = !bayer && !yuv422 && layout != CFHD_AMD_PICTURES_PACKED;
+	if (rgba) {
+		if (layout == CFHD_AMD_PICTURES_RGBA_U8 && b->st.out_kind == PIX_B64A) { refuse("decode queue: RGBA_U8 serves the 8-bit outputs BGRA and BGRa; a b64a batch delivers RGBA_U16"); return -1; }
+		if (layout == CFHD_AMD_PICTURES_RGBA_U16 && b->st.out_kind != PIX_B64A) { refuse("decode queue: RGBA_U16 serves b64a; a BGRA or BGRa batch delivers RGBA_U8"); return -1; }
+	}
+	const bool planar = !bayer && !yuv422 && !rgba && layout != CFHD_AMD_PICTURES_PACKED;
 	if (planar && b->st.out_kind != PIX_RG48) { refuse("decode queue: the planar layouts serve batches whose output is RG48"); return -1; }
 	if (((uintptr_t)d_pictures | picture_stride | (size_t)(unsigned)picture_pitch) & 15) { refuse("decode queue: the device pictures' pointer, stride and pitch are multiples of 16"); return -1; }
 	if (yuv422) {
@@ -441,6 +455,20 @@ int cfhd_amd_decode_batch_set_device_pictures(cfhd_amd_decode_batch *b, void *d_
 		if (picture_stride < (size_t)picture_pitch * (size_t)h + (size_t)(picture_pitch / 2) * (2 * (size_t)h - 1) + (size_t)(luma_row / 2)) {
 			refuse("decode queue: the stride is below the three planes of the 4:2:2 layout (H x pitch, then 2 H chroma rows pitch / 2 apart)"); return -1;
 		}
+		b->dev_out = (uint8_t *)d_pictures; b->dev_out_stride = picture_stride; b->dev_out_pitch = picture_pitch; b->dev_out_layout = layout;
+		return 0;
+	}
+	if (rgba) {
+		// four planes of H rows at the pitch, of which the last row needs its row bytes only
+		const int w = b->picture_width(), h = b->picture_rows(), pixel = b->st.out_kind == PIX_B64A ? 8 : 4;
+		const long long plane_row = (long long)w * dev::deliver_rgba_element_bytes(layout);
+		// what k_dec_deliver_rgba assumes of the batch's own pictures: rows of whole pixels back to back, the pictures on 16-byte boundaries (rows that are no multiple of
+		// 16 bytes long go element by element: no width the queue serves has them)
+		if (b->picture_pitch() != pixel * w || b->picture_bytes() != (size_t)b->picture_pitch() * (size_t)h || (((uintptr_t)b->device_pictures() | b->picture_bytes()) & 15) || b->n > 65535 /* blockIdx.y */) {
+			refuse("decode queue: pictures the RGBA deliver kernel does not take"); return -1;
+		}
+		if (picture_pitch < plane_row) { refuse("decode queue: the pitch is below the plane row of the RGBA layout (width x element size)"); return -1; }
+		if (picture_stride < (size_t)picture_pitch * (4 * (size_t)h - 1) + (size_t)plane_row) { refuse("decode queue: the stride is below the four planes of the RGBA layout (4 x H rows a pitch apart)"); return -1; }
 		b->dev_out = (uint8_t *)d_pictures; b->dev_out_stride = picture_stride; b->dev_out_pitch = picture_pitch; b->dev_out_layout = layout;
 		return 0;
 	}
@@ -628,7 +656,7 @@ float cfhd_amd_decode_batch_kernel_ms(cfhd_amd_decode_batch *b, int which)
 
 const char *cfhd_amd_decode_batch_kernel_name(cfhd_amd_decode_batch *b, int which)
 {
-	if (b && !b->in_flight && which == 9) return b->dev_out && dev::deliver_is_bayer(b->dev_out_layout) ? "k_dec_deliver_bayer" : (b->dev_out && dev::deliver_is_yuv422(b->dev_out_layout) ? "k_dec_deliver_yuv422" : "k_dec_deliver");
+	if (b && !b->in_flight && which == 9) return b->dev_out && dev::deliver_is_bayer(b->dev_out_layout) ? "k_dec_deliver_bayer" : (b->dev_out && dev::deliver_is_yuv422(b->dev_out_layout) ? "k_dec_deliver_yuv422" : (b->dev_out && dev::deliver_is_rgba(b->dev_out_layout) ? "k_dec_deliver_rgba" : "k_dec_deliver"));
 	if (!b || b->in_flight || which < 0 || which > 7) return "";
 	static const char *const fixed[4] = { "k_dec_ingest", "k_dec_parse", "k_dec_plan+k_dec_index+k_dec_chain+k_dec_tiles", "k_dec_lowpass" };
 	if (which < 4 && !(b->groups && which)) return fixed[which];

@@ -2,7 +2,8 @@
 // cfhd_decode_queue.hip): behind k_dec_blank, the pictures of the pass out of the batch's own tightly packed buffer into memory the caller owns -- as the packed
 // pictures they are, at the caller's pitch, or, for RG48, as three planes R, G, B of u16, f16 or f32 elements (a torch tensor N x 3 x H x W) -- and k_dec_deliver_bayer,
 // which takes its place for the BYR4 mosaics of a Bayer batch delivered as four planes, one per position of the 2 x 2 quad (N x 4 x H/2 x W/2), and k_dec_deliver_yuv422,
-// which takes it for the packed 4:2:2 pictures (YUY2, 2vuy, YU64) delivered as a luma plane and two chroma planes of half the width (I422: N x [H x W | 2 x H x W/2]).
+// which takes it for the packed 4:2:2 pictures (YUY2, 2vuy, YU64) delivered as a luma plane and two chroma planes of half the width (I422: N x [H x W | 2 x H x W/2]), and
+// k_dec_deliver_rgba, which takes it for the four-component pictures (b64a, BGRA, BGRa) delivered as four planes R, G, B, A, top row first (N x 4 x H x W).
 #pragma once
 #include <stdint.h>
 #include <stddef.h>
@@ -304,6 +305,145 @@ __global__ void __launch_bounds__(DEC_DELIVER_THREADS) k_dec_deliver_yuv422(cons
 			if (layout == DELIVER_YUV422_U8) deliver_yuv422_row<YUV422_2VUY, DELIVER_YUV422_U8>(row, width, y, cb, cr, lane);
 			else if (layout == DELIVER_YUV422_F16) deliver_yuv422_row<YUV422_2VUY, DELIVER_YUV422_F16>(row, width, y, cb, cr, lane);
 			else deliver_yuv422_row<YUV422_2VUY, DELIVER_YUV422_F32>(row, width, y, cb, cr, lane);
+		}
+	}
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_dec_deliver_rgba: packed four-component picture i of the pass -- `rows` rows of `width` pixels back to back at src + i * src_stride, 8 x width bytes a row (order
+// RGBA_B64A: the native 16-bit words A R G B) or 4 x width (RGBA_BGRA, RGBA_BGRa: the bytes B G R A) -- into dst + i * dst_stride as four planes R, G, B, A (a torch
+// tensor N x 4 x H x W): plane c at dst_pitch * rows * c, row r of it at dst_pitch * r, `width` elements.  The planes have the top row first: a BGRA picture lies bottom
+// row first in the batch's buffer, and plane row r is read from packed row rows - 1 - r -- an address, not a second pass.  Every plane row gets its bytes and nothing
+// else.  `layout`: DELIVER_RGBA_U8 (the bytes of BGRA / BGRa as they are), _U16 (the words of b64a), _F16 / _F32 (deliver_unit_f32_of with the unit of the picture's own
+// word, 255 or 65535; F16: deliver_f16_bits of it).  Alpha is a component like the others.
+//   A wave owns a plane row at a time; a lane's loads are 16 bytes wide and cover consecutive bytes, a wave reads its stretch of the packed row without a gap.
+//   b64a: a lane takes 8 pixels, four loads (64 bytes, 4 KB a wave); every longword holds (A, R) or (G, B) of a pixel, the components of two pixels meet in one
+//   longword by v_perm_b32 (16 per lane and step); one 16-byte store per plane for u16 / f16, two for f32.
+//   BGRA / BGRa, U8: 16 pixels, four loads; the 4 x 4 bytes of every four pixels are transposed in two rounds of v_perm_b32 (B G and R A of a pair of pixels, then the
+//   pairs of pairs: 32 per lane and step), one 16-byte store per plane.  F16: 16 pixels, every byte converted straight out of its longword (v_cvt_f32_ubyte0 .. 3),
+//   one multiply, v_cvt_pk_f16_f32, two 16-byte stores per plane.  F32: 8 pixels, two loads, two 16-byte stores per plane -- a lane's stores to one plane row kept to
+//   32 consecutive bytes, as measured for k_dec_deliver_yuv422.  Every store instruction of a wave writes consecutive pieces of one plane row.
+//   The widths the decode queue serves for these outputs are multiples of 4 (half resolution: 100 of 200), not always of 8 or 16: the columns behind the last whole
+//   group go element by element, as in k_dec_deliver.  A packed row is 8 x width or 4 x width bytes: with a width that is a multiple of 4 every row starts on a
+//   16-byte boundary (the batch's pictures come from hipMalloc and lie rows x row bytes apart; the entry point checks that and admits only pointers, strides and
+//   pitches that are multiples of 16).  Should a gate ever admit another width, the rows of that picture are not aligned and the whole picture goes element by element.
+// No LDS, no scratch.  Grid (row pieces: dec_deliver_pieces(rows), pictures), DEC_DELIVER_WAVES rows per piece and step.
+// ---------------------------------------------------------------------------------------------
+// (CFHD_AMD_PICTURES_RGBA_*) and the packed orders they are written from
+enum { DELIVER_RGBA_U8 = 11, DELIVER_RGBA_U16 = 12, DELIVER_RGBA_F16 = 13, DELIVER_RGBA_F32 = 14 };
+enum { RGBA_B64A = 0, RGBA_BGRA = 1, RGBA_BGRa = 2 };
+inline bool deliver_is_rgba(int layout) { return layout >= DELIVER_RGBA_U8 && layout <= DELIVER_RGBA_F32; }
+inline int deliver_rgba_element_bytes(int layout) { return layout == DELIVER_RGBA_U8 ? 1 : (layout == DELIVER_RGBA_F32 ? 4 : 2); }
+// the pixels a lane takes per step
+template <int UNIT, int LAYOUT> struct deliver_rgba_pixels { static constexpr int value = UNIT == 65535 || LAYOUT == DELIVER_RGBA_F32 ? 8 : 16; };
+
+// N values of the F32 rule as the elements of LAYOUT (F32: the singles; F16: deliver_f16_bits, two to a longword)
+template <int LAYOUT, int N> __device__ __forceinline__ void deliver_rgba_floats(uint8_t *at, const float *f)
+{
+	if constexpr (LAYOUT == DELIVER_RGBA_F32) {
+		uint32_t d[N];
+		for (int k = 0; k < N; k++) memcpy(&d[k], &f[k], 4);
+		deliver_store_longwords<N>(at, d);
+	} else {
+		uint32_t d[N / 2];
+		for (int k = 0; k < N / 2; k++) d[k] = deliver_f16_bits(f[2 * k]) | (deliver_f16_bits(f[2 * k + 1]) << 16);
+		deliver_store_longwords<N / 2>(at, d);
+	}
+}
+// one element of a plane (the columns behind the last whole group)
+template <int LAYOUT, int UNIT> __device__ __forceinline__ void deliver_rgba_element(uint8_t *plane_row, int x, uint32_t w)
+{
+	if constexpr (LAYOUT == DELIVER_RGBA_U8) plane_row[x] = (uint8_t)w;
+	else if constexpr (LAYOUT == DELIVER_RGBA_U16) ((uint16_t *)plane_row)[x] = (uint16_t)w;
+	else if constexpr (LAYOUT == DELIVER_RGBA_F16) ((uint16_t *)plane_row)[x] = (uint16_t)deliver_f16_bits(deliver_unit_f32_of<UNIT>(w));
+	else ((float *)plane_row)[x] = deliver_unit_f32_of<UNIT>(w);
+}
+// one row of `width` b64a pixels into row `orow` of plane R; the planes `plane` bytes apart
+template <int LAYOUT> __device__ __forceinline__ void deliver_rgba_row_words(const uint8_t *row, int width, bool aligned, uint8_t *orow, size_t plane, int lane)
+{
+	constexpr int E = LAYOUT == DELIVER_RGBA_F32 ? 4 : 2;
+	const int groups = aligned ? width >> 3 : 0;
+	for (int g = lane; g < groups; g += 64) {
+		uint32_t p[16];                                          // (A, R), (G, B) of every pixel
+		for (int k = 0; k < 4; k++) { const cfhd_u4 v = CFHD_LDG128(row + 64 * (size_t)g + 16 * k); p[4 * k] = v.x; p[4 * k + 1] = v.y; p[4 * k + 2] = v.z; p[4 * k + 3] = v.w; }
+		uint32_t c[4][4];                                        // plane R, G, B, A: two pixels to a longword
+		for (int k = 0; k < 4; k++) {
+			c[3][k] = deliver_lo_lo(p[4 * k], p[4 * k + 2]); c[0][k] = deliver_hi_hi(p[4 * k], p[4 * k + 2]);
+			c[1][k] = deliver_lo_lo(p[4 * k + 1], p[4 * k + 3]); c[2][k] = deliver_hi_hi(p[4 * k + 1], p[4 * k + 3]);
+		}
+		uint8_t *at = orow + (size_t)g * 8 * E;
+		for (int q = 0; q < 4; q++) {
+			if constexpr (LAYOUT == DELIVER_RGBA_U16) store_u32x4_global(at + q * plane, c[q][0], c[q][1], c[q][2], c[q][3]);
+			else {
+				float f[8];
+				for (int k = 0; k < 4; k++) { f[2 * k] = deliver_unit_f32_of<65535>(c[q][k] & 0xffffu); f[2 * k + 1] = deliver_unit_f32_of<65535>(c[q][k] >> 16); }
+				deliver_rgba_floats<LAYOUT, 8>(at + q * plane, f);
+			}
+		}
+	}
+	for (int x = 8 * groups + lane; x < width; x += 64) {
+		const uint16_t *px = (const uint16_t *)row + 4 * (size_t)x;
+		deliver_rgba_element<LAYOUT, 65535>(orow + 3 * plane, x, px[0]);
+		deliver_rgba_element<LAYOUT, 65535>(orow, x, px[1]);
+		deliver_rgba_element<LAYOUT, 65535>(orow + plane, x, px[2]);
+		deliver_rgba_element<LAYOUT, 65535>(orow + 2 * plane, x, px[3]);
+	}
+}
+// ... and of B G R A bytes
+template <int LAYOUT> __device__ __forceinline__ void deliver_rgba_row_bytes(const uint8_t *row, int width, bool aligned, uint8_t *orow, size_t plane, int lane)
+{
+	constexpr int E = LAYOUT == DELIVER_RGBA_U8 ? 1 : (LAYOUT == DELIVER_RGBA_F32 ? 4 : 2), P = deliver_rgba_pixels<255, LAYOUT>::value;
+	const int groups = aligned ? width / P : 0;
+	for (int g = lane; g < groups; g += 64) {
+		uint32_t p[P];                                           // a longword per pixel: B | G << 8 | R << 16 | A << 24
+		for (int k = 0; k < P / 4; k++) { const cfhd_u4 v = CFHD_LDG128(row + 4 * P * (size_t)g + 16 * k); p[4 * k] = v.x; p[4 * k + 1] = v.y; p[4 * k + 2] = v.z; p[4 * k + 3] = v.w; }
+		uint8_t *at = orow + (size_t)g * P * E;
+		if constexpr (LAYOUT == DELIVER_RGBA_U8) {
+			uint32_t b[P / 4], gr[P / 4], r[P / 4], a[P / 4];
+			for (int k = 0; k < P / 4; k++) {
+				// of two pixels B0 B1 G0 G1 and R0 R1 A0 A1, then the like halves of two such pairs
+				const uint32_t bg01 = byte_perm(p[4 * k + 1], p[4 * k], 0x05010400u), ra01 = byte_perm(p[4 * k + 1], p[4 * k], 0x07030602u);
+				const uint32_t bg23 = byte_perm(p[4 * k + 3], p[4 * k + 2], 0x05010400u), ra23 = byte_perm(p[4 * k + 3], p[4 * k + 2], 0x07030602u);
+				b[k] = deliver_lo_lo(bg01, bg23); gr[k] = deliver_hi_hi(bg01, bg23); r[k] = deliver_lo_lo(ra01, ra23); a[k] = deliver_hi_hi(ra01, ra23);
+			}
+			deliver_store_longwords<P / 4>(at, r); deliver_store_longwords<P / 4>(at + plane, gr); deliver_store_longwords<P / 4>(at + 2 * plane, b); deliver_store_longwords<P / 4>(at + 3 * plane, a);
+		} else {
+			for (int q = 0; q < 4; q++) {                          // plane q: R (bits 16), G (8), B (0), A (24)
+				const int shift = q == 0 ? 16 : (q == 1 ? 8 : (q == 2 ? 0 : 24));
+				float f[P];
+				for (int k = 0; k < P; k++) f[k] = deliver_unit_f32_of<255>((p[k] >> shift) & 0xffu);
+				deliver_rgba_floats<LAYOUT, P>(at + q * plane, f);
+			}
+		}
+	}
+	for (int x = P * groups + lane; x < width; x += 64) {
+		const uint8_t *px = row + 4 * (size_t)x;
+		deliver_rgba_element<LAYOUT, 255>(orow + 2 * plane, x, px[0]);
+		deliver_rgba_element<LAYOUT, 255>(orow + plane, x, px[1]);
+		deliver_rgba_element<LAYOUT, 255>(orow, x, px[2]);
+		deliver_rgba_element<LAYOUT, 255>(orow + 3 * plane, x, px[3]);
+	}
+}
+
+__global__ void __launch_bounds__(DEC_DELIVER_THREADS) k_dec_deliver_rgba(const uint8_t *src, size_t src_stride, int rows, int width, uint8_t *dst, size_t dst_stride, int dst_pitch, int layout, int order)
+{
+	const int lane = (int)(threadIdx.x & 63u), wave = wave_uniform((int)(threadIdx.x >> 6));
+	const uint8_t *pic = src + src_stride * (size_t)blockIdx.y;
+	uint8_t *out = dst + dst_stride * (size_t)blockIdx.y;
+	const int row_bytes = (order == RGBA_B64A ? 8 : 4) * width;
+	const bool aligned = !(((uintptr_t)src | src_stride | (size_t)row_bytes) & 15);      // every row of the batch's pictures starts on a 16-byte boundary
+	const size_t plane = (size_t)dst_pitch * (size_t)rows;
+	for (int r = (int)blockIdx.x * DEC_DELIVER_WAVES + wave; r < rows; r += (int)gridDim.x * DEC_DELIVER_WAVES) {
+		const uint8_t *row = pic + (size_t)(order == RGBA_BGRA ? rows - 1 - r : r) * row_bytes;
+		uint8_t *orow = out + (size_t)r * dst_pitch;
+		if (order == RGBA_B64A) {
+			if (layout == DELIVER_RGBA_U16) deliver_rgba_row_words<DELIVER_RGBA_U16>(row, width, aligned, orow, plane, lane);
+			else if (layout == DELIVER_RGBA_F16) deliver_rgba_row_words<DELIVER_RGBA_F16>(row, width, aligned, orow, plane, lane);
+			else deliver_rgba_row_words<DELIVER_RGBA_F32>(row, width, aligned, orow, plane, lane);
+		} else {
+			if (layout == DELIVER_RGBA_U8) deliver_rgba_row_bytes<DELIVER_RGBA_U8>(row, width, aligned, orow, plane, lane);
+			else if (layout == DELIVER_RGBA_F16) deliver_rgba_row_bytes<DELIVER_RGBA_F16>(row, width, aligned, orow, plane, lane);
+			else deliver_rgba_row_bytes<DELIVER_RGBA_F32>(row, width, aligned, orow, plane, lane);
 		}
 	}
 }

@@ -598,6 +598,7 @@ void CollectTimes::release()
 // make it a whole number of the kernel's groups of eight pixels (cfhd_collect_kernels.h).
 // A BYR4 batch (width: the plan's, photosite quads; rows: the mosaic's, 2 x display height; slot rows of 4 x width bytes) takes the BAYER_* layouts and no other:
 // four planes of rows / 2 rows of `width` elements through k_enc_collect_bayer, the same gates over its own geometry.
+// A packed 4:2:2 batch takes the YUV422_* layouts (k_enc_collect_yuv422), a b64a, BGRA or BGRa batch the RGBA_* ones (k_enc_collect_rgba), each with gates of its own below.
 static int collect_planar_frames(int pixel_kind, uint8_t *slots, size_t frame_bytes, int slot_pitch, int width, int rows, int nframes, int first, int count,
                                  const void *d_frames, size_t frame_stride, int row_pitch, int layout, void *stream, CollectTimes &times)
 {
@@ -626,6 +627,28 @@ static int collect_planar_frames(int pixel_kind, uint8_t *slots, size_t frame_by
 		dev::k_enc_collect_yuv422<<<dim3(dev::enc_collect_pieces(rows), (unsigned)count), dev::ENC_COLLECT_THREADS, 0, (hipStream_t)stream>>>(
 			(const uint8_t *)d_frames, frame_stride, row_pitch, rows, width, slots + frame_bytes * (size_t)first, frame_bytes, layout,
 			words ? dev::COLLECT_ORDER_YU64 : (pixel_kind == PIX_2VUY ? dev::COLLECT_ORDER_2VUY : dev::COLLECT_ORDER_YUY2));
+		HIPCHK(hipGetLastError());
+		return times.record(stream, true);
+	}
+	// A b64a, BGRA or BGRa batch (width and rows: the frame's; slot rows of 8 x or 4 x width bytes, a BGRA slot bottom row first) takes the RGBA_* layouts: four planes
+	// R, G, B, A, top row first, through k_enc_collect_rgba.  To every other batch those layouts are what they were before they existed.
+	if (dev::collect_is_rgba(layout) && (pixel_kind == PIX_B64A || pixel_kind == PIX_BGRA || pixel_kind == PIX_BGRa)) {
+		const bool words = pixel_kind == PIX_B64A;
+		if (layout == dev::COLLECT_RGBA_U8 && words) return refuse("frames from planar tensors: RGBA_U8 serves the 8-bit inputs BGRA and BGRa; a b64a batch takes RGBA_U16");
+		if (layout == dev::COLLECT_RGBA_U16 && !words) return refuse("frames from planar tensors: RGBA_U16 serves b64a; a BGRA or BGRa batch takes RGBA_U8");
+		if (count < 1 || first < 0 || first > nframes - count) return refuse("frames from planar tensors: the run of frames leaves the batch");
+		if (!d_frames) return refuse("frames from planar tensors: no pointer");
+		if (((uintptr_t)d_frames | frame_stride | (size_t)(unsigned)row_pitch) & 15) return refuse("frames from planar tensors: pointer, frame stride and row pitch are multiples of 16");
+		if (row_pitch < 0 || (long long)row_pitch < (long long)width * dev::collect_rgba_element_bytes(layout)) return refuse("frames from planar tensors: a row pitch below the plane row of the RGBA layout (width x element size)");
+		if (frame_stride < 4 * (size_t)rows * (size_t)row_pitch) return refuse("frames from planar tensors: a frame stride below four planes of the RGBA layout (4 x height x row pitch)");
+		if (slot_pitch != (words ? 8 : 4) * width || frame_bytes != (size_t)slot_pitch * rows || (((uintptr_t)slots | frame_bytes | (size_t)slot_pitch) & 15) || count > 65535 /* blockIdx.y */)
+			return refuse("frames from planar tensors: frame slots the RGBA collect kernel does not take");
+		int rc = times.record(stream, false);
+		if (rc) return rc;
+		(void)hipGetLastError();
+		dev::k_enc_collect_rgba<<<dim3(dev::enc_collect_pieces(rows), (unsigned)count), dev::ENC_COLLECT_THREADS, 0, (hipStream_t)stream>>>(
+			(const uint8_t *)d_frames, frame_stride, row_pitch, rows, width, slots + frame_bytes * (size_t)first, frame_bytes, layout,
+			words ? dev::COLLECT_ORDER_B64A : (pixel_kind == PIX_BGRA ? dev::COLLECT_ORDER_BGRA : dev::COLLECT_ORDER_BGRa));
 		HIPCHK(hipGetLastError());
 		return times.record(stream, true);
 	}

@@ -2406,6 +2406,19 @@ __global__ void __launch_bounds__(NTHREADS) k_half_packed16(const HalfPackedJob 
 		}
 	}
 	uint8_t *dst = (uint8_t *)job.out + (size_t)row * job.out_pitch;
+	const int left = job.width - 8 * c8;                 // the pixels of this thread that lie inside the row: 8, or fewer in the last group of a width that is no multiple of 8
+	if (left < 8) {
+		// (half of a sample 200 pixels wide: 100.)  Pixel by pixel, and nothing behind the row: eight whole pixels would run into the next row -- written by another
+		// workgroup, in no order -- and, in the last row of the last picture, past the end of the buffer.
+		uint16_t *o = (uint16_t *)dst + (size_t)8 * c8 * job.nch;
+#pragma unroll
+		for (int k = 0; k < 8; k++) {
+			if (k >= left) continue;
+			o[k * job.nch] = (uint16_t)px[k][0]; o[k * job.nch + 1] = (uint16_t)(px[k][0] >> 16); o[k * job.nch + 2] = (uint16_t)px[k][1];
+			if (job.nch == 4) o[k * job.nch + 3] = (uint16_t)(px[k][1] >> 16);
+		}
+		return;
+	}
 	if (job.nch == 4) {
 		uint4 *o = (uint4 *)(dst + 64 * (size_t)c8);
 #pragma unroll

@@ -20,8 +20,9 @@
  * Both queues of the extension API have a device-memory side: the decode queue delivers its pictures into device memory the caller owns, packed or -- RG48 -- as
  * planar R, G, B tensors of u16 / f16 / f32 (cfhd_amd_decode_batch_set_device_pictures), the frame queue takes frames that lie in device memory
  * (cfhd_amd_batch_upload_device) or there as planar tensors (cfhd_amd_batch_upload_device_planar).  The plane layouts of both sides: RG48 as R, G, B, BYR4 mosaics as
- * the four planes of the 2 x 2 quad, and the packed 4:2:2 formats YUY2 / 2vuy / YU64 as Y, Cb, Cr in the I422 convention (CFHD_AMD_PICTURES_YUV422_* /
- * CFHD_AMD_FRAMES_YUV422_*), each as integer, f16 or f32 elements.
+ * the four planes of the 2 x 2 quad, the packed 4:2:2 formats YUY2 / 2vuy / YU64 as Y, Cb, Cr in the I422 convention (CFHD_AMD_PICTURES_YUV422_* /
+ * CFHD_AMD_FRAMES_YUV422_*), and the formats that carry alpha, b64a / BGRA / BGRa, as R, G, B, A with the top row first (CFHD_AMD_PICTURES_RGBA_* /
+ * CFHD_AMD_FRAMES_RGBA_*), each as integer, f16 or f32 elements.
  * There is no CPU fallback: without a HIP device the encode/decode calls return CFHD_ERROR_INTERNAL (6).
  */
 #ifndef CFHD_AMD_H
@@ -197,10 +198,24 @@ int  cfhd_amd_batch_upload_device(cfhd_amd_batch *batch, int frame, const void *
  * 16-bit unit as above; for the 8-bit unit collect(deliver(b)) = b for all 256 bytes through U8, F32 and also F16 (the binary16 values of b / 255 are 256 distinct
  * numbers that come back within 0.063 of b).  One launch of k_enc_collect_yuv422 per run (per chunk of a cut intra batch), timed under index 20;
  * cfhd_amd_batch_kernel_name(batch, 20) answers "k_enc_collect_yuv422" for a batch of these three formats.  Refused as above, and: _U8 on a YU64 batch, _U16 on an
- * 8-bit one, a row pitch that is no multiple of 32 or below W * element size, a frame stride below 2 * H * row_pitch. */
+ * 8-bit one, a row pitch that is no multiple of 32 or below W * element size, a frame stride below 2 * H * row_pitch.
+ * CFHD_AMD_FRAMES_RGBA_U8 / _U16 / _F16 / _F32: the same for every batch whose pixel format is b64a, BGRA or BGRa -- cfhd_amd_batch_create_ex to 4:2:2, RGB 4:4:4 and
+ * RGBA 4:4:4:4, _create_groups, _create_stream, _create_group_stream -- and for no other (to every other batch the values are what they were before these layouts
+ * existed: an unknown layout, or the text that batch has for every foreign value).  A frame of W x H pixels is read as four planes, R, then G, then B, then A, each H
+ * rows of W elements, rows row_pitch bytes apart, planes H * row_pitch apart: the geometry of CFHD_AMD_PICTURES_RGBA_*.  A contiguous tensor (n, 4, H, W) is
+ * row_pitch = W * element size, frame_stride = 4 * H * row_pitch.  The plane order is always R, G, B, A, whatever the packed order (b64a: the native 16-bit words A, R,
+ * G, B; BGRA and BGRa: the bytes B, G, R, A), and the planes always have the top row first: BGRA, whose packed frame has the bottom row first, takes plane row r into
+ * packed row H - 1 - r; BGRa and b64a keep their order.  _U8 exists for BGRA and BGRa only, _U16 for b64a only: the element as it is.  _F16 / _F32: the rules above
+ * with the unit of the batch's own word, 255 or 65535.  Alpha is a component like the others: the packed byte or word, no companding, no premultiplication.  A batch
+ * that encodes to 4:2:2 or RGB 4:4:4 still reads the A plane into the frame slot; the encoder drops it, as it does for an uploaded packed frame.  The inversion
+ * properties are those of the YUV422 layouts: for the 8-bit unit collect(deliver(b)) = b for all 256 bytes through U8, F32 and F16; for the 16-bit unit U16 and F32
+ * are exact for all 65 536 words and F16 is idempotent.  One launch of k_enc_collect_rgba per run (per chunk of a cut intra batch), timed under index 20;
+ * cfhd_amd_batch_kernel_name(batch, 20) answers "k_enc_collect_rgba" for a batch of these three formats.  Refused as above, and: _U8 on a b64a batch, _U16 on an
+ * 8-bit one, a row pitch below W * element size, a frame stride below 4 * H * row_pitch. */
 enum { CFHD_AMD_FRAMES_PLANAR_U16 = 1, CFHD_AMD_FRAMES_PLANAR_F16 = 2, CFHD_AMD_FRAMES_PLANAR_F32 = 3 };      /* values equal to CFHD_AMD_PICTURES_PLANAR_* */
 enum { CFHD_AMD_FRAMES_BAYER_U16 = 4, CFHD_AMD_FRAMES_BAYER_F16 = 5, CFHD_AMD_FRAMES_BAYER_F32 = 6 };         /* values equal to CFHD_AMD_PICTURES_BAYER_* */
 enum { CFHD_AMD_FRAMES_YUV422_U8 = 7, CFHD_AMD_FRAMES_YUV422_U16 = 8, CFHD_AMD_FRAMES_YUV422_F16 = 9, CFHD_AMD_FRAMES_YUV422_F32 = 10 };      /* values equal to CFHD_AMD_PICTURES_YUV422_* */
+enum { CFHD_AMD_FRAMES_RGBA_U8 = 11, CFHD_AMD_FRAMES_RGBA_U16 = 12, CFHD_AMD_FRAMES_RGBA_F16 = 13, CFHD_AMD_FRAMES_RGBA_F32 = 14 };          /* values equal to CFHD_AMD_PICTURES_RGBA_* */
 int  cfhd_amd_batch_upload_device_planar(cfhd_amd_batch *batch, int first_frame, int count, const void *d_frames, size_t frame_stride, int row_pitch, int layout);
 /* Frame `frame` as the batch holds it, in its packed input format, into out (rows `pitch` >= row bytes apart): the twin of cfhd_amd_batch_download_output for the
  * input side, for every kind of batch and input format (av28: the frame's one block as one row).  Waits for the stream the uploads run on.  0; -1 for bad arguments
@@ -408,14 +423,28 @@ int  cfhd_amd_decode_batch_submit_device(cfhd_amd_decode_batch *batch, const voi
  * is idempotent.  The pitch is a multiple of 32 (the chroma pitch: of 16) and >= W * element size; the stride is >= H * picture_pitch + (2 H - 1) * (picture_pitch / 2)
  * + the chroma row bytes.  Written by k_dec_deliver_yuv422 in place of k_dec_deliver (kernel_name(batch, 9) answers it while such a layout is set; kernel_ms index 9
  * times it).
+ * CFHD_AMD_PICTURES_RGBA_U8 / _U16 / _F16 / _F32: every batch whose output is b64a, BGRA or BGRa -- intra batches of 4:2:2, RGB 4:4:4 and RGBA 4:4:4:4 samples and group
+ * batches, at full and half resolution where the batch serves it -- and no other (to every other batch the values are unknown layouts).  The picture of W x H pixels
+ * (cfhd_amd_decode_batch_geometry) is four planes, R, then G, then B, then A, each H rows of W elements, rows picture_pitch bytes apart, planes H * picture_pitch
+ * apart: a contiguous tensor (n, 4, H, W) is picture_pitch = W * element size, picture_stride = 4 * H * picture_pitch.  The plane order is always R, G, B, A,
+ * whatever the packed order (b64a: the native 16-bit words A, R, G, B; BGRA and BGRa: the bytes B, G, R, A), and the planes always have the top row first: plane row r
+ * of a BGRA picture, whose packed form has the bottom row first, is packed row H - 1 - r; BGRa and b64a keep their order; interlaced pictures keep their frame rows.
+ * _U8 exists for BGRA and BGRa only, _U16 for b64a only: the byte or word as it is.  _F32: (float)w * (1.0f / unit) with the unit of the batch's own word, 255 or
+ * 65535, one IEEE single multiply; _F16: that value rounded to nearest-even to binary16, subnormals kept.  Alpha is a component like the others: the packed byte or
+ * word, no companding, no premultiplication; the constant alpha of a picture whose sample had none arrives as it stands in the packed picture (b64a: 0xffff of 4:2:2,
+ * 0xfff0 of RGB 4:4:4 samples; BGRA / BGRa: the byte the conversion writes).  CFHD_AMD_FRAMES_RGBA_* of cfhd_amd_batch_upload_device_planar invert these rules as
+ * the YUV422 layouts do.  The pitch is >= W * element size; the stride is >= (4 H - 1) * picture_pitch + W * element size.  Written by k_dec_deliver_rgba in place
+ * of k_dec_deliver (kernel_name(batch, 9) answers it while such a layout is set; kernel_ms index 9 times it).
  * Exactly count pictures are written, of every row its row bytes and nothing else: pitch padding, the space between planes and pictures and the pictures behind a short
  * pass are not touched.
  * 0; -1 with the reason in cfhd_amd_last_error(): a pass in flight, an unknown layout, a planar layout on a batch whose output is not RG48, a pointer, stride or pitch
  * that is no multiple of 16, a pitch below the row bytes of the layout, a stride below what one picture occupies; a 4:2:2 plane layout on a batch whose output is not
- * YUY2, 2vuy or YU64, _U8 on a YU64 batch, _U16 on an 8-bit one, a pitch of such a layout that is no multiple of 32. */
+ * YUY2, 2vuy or YU64, _U8 on a YU64 batch, _U16 on an 8-bit one, a pitch of such a layout that is no multiple of 32; RGBA_U8 on a b64a batch, RGBA_U16 on a BGRA or
+ * BGRa one. */
 enum { CFHD_AMD_PICTURES_PACKED = 0, CFHD_AMD_PICTURES_PLANAR_U16 = 1, CFHD_AMD_PICTURES_PLANAR_F16 = 2, CFHD_AMD_PICTURES_PLANAR_F32 = 3 };
 enum { CFHD_AMD_PICTURES_BAYER_U16 = 4, CFHD_AMD_PICTURES_BAYER_F16 = 5, CFHD_AMD_PICTURES_BAYER_F32 = 6 };
 enum { CFHD_AMD_PICTURES_YUV422_U8 = 7, CFHD_AMD_PICTURES_YUV422_U16 = 8, CFHD_AMD_PICTURES_YUV422_F16 = 9, CFHD_AMD_PICTURES_YUV422_F32 = 10 };
+enum { CFHD_AMD_PICTURES_RGBA_U8 = 11, CFHD_AMD_PICTURES_RGBA_U16 = 12, CFHD_AMD_PICTURES_RGBA_F16 = 13, CFHD_AMD_PICTURES_RGBA_F32 = 14 };
 int  cfhd_amd_decode_batch_set_device_pictures(cfhd_amd_decode_batch *batch, void *d_pictures, size_t picture_stride, int picture_pitch, int layout);
 /* Collects the pass: the number of samples that decoded, or < 0 (-1: nothing in flight, -2: device failure).  status (NULL or count entries): status[i] is the CFHD_Error
  * CFHD_DecodeSample returns for sample i on a handle prepared on the first sample; the picture of a sample that failed is zero.  Samples the device parser refuses are
@@ -428,7 +457,7 @@ int  cfhd_amd_decode_batch_wait(cfhd_amd_decode_batch *batch, CFHD_Error *status
 int  cfhd_amd_decode_batch_download_output(cfhd_amd_decode_batch *batch, int i, void *out, int pitch);
 /* HIP-event time (ms) of the kernels of the last pass and their names as a profiler shows them.  which: 0 k_dec_ingest, 1 k_dec_parse, 2 the band decoder (all its
  * kernels), 3 k_dec_lowpass, 4 / 5 / 6 the transform levels in launch order (the last one with the output conversion), 7 k_dec_blank, 9 k_dec_deliver (both kinds of
- * batch; k_dec_deliver_bayer while a BAYER_* layout is set, k_dec_deliver_yuv422 while a YUV422_* one is; 0 ms when the last pass delivered nothing into device memory).  0 / "" otherwise. */
+ * batch; k_dec_deliver_bayer while a BAYER_* layout is set, k_dec_deliver_yuv422 while a YUV422_* one is, k_dec_deliver_rgba while an RGBA_* one is; 0 ms when the last pass delivered nothing into device memory).  0 / "" otherwise. */
 float cfhd_amd_decode_batch_kernel_ms(cfhd_amd_decode_batch *batch, int which);
 const char *cfhd_amd_decode_batch_kernel_name(cfhd_amd_decode_batch *batch, int which);
 int  cfhd_amd_device_count(void);
