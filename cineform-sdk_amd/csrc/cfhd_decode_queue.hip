@@ -6,7 +6,8 @@
 //   (samples H2D: one DMA of a registered blob as it lies, or of the pinned buffer the calling thread packed plain memory into)  ->  k_dec_ingest: every sample into the
 //   decoder's own 256-byte aligned slot, the size table  ->  k_dec_parse with a verdict per sample  ->  the band decoder, k_dec_lowpass  ->  the three transform levels
 //   and the output conversion (DecodeBatch)  ->  k_dec_blank: the pictures of the samples that failed, zeroed  ->  (k_dec_deliver: the pictures into the
-//   device memory cfhd_amd_decode_batch_set_device_pictures named, packed or as planes)  ->  (pictures D2H).
+//   device memory cfhd_amd_decode_batch_set_device_pictures named, packed or as planes; k_dec_deliver_rgb_as_yuv: the RG48 pictures of RGB samples as the YU64
+//   picture the reference decodes such a sample to, every picture with the matrix of its own sample's colour-space tag)  ->  (pictures D2H).
 // The gates are the handle's: create prepares a CFHD_DecodeSample handle on the first sample and decodes that sample once; what the handle refuses, create refuses with
 // the same text.  That handle stays with the batch as the slow path: the samples k_dec_ingest could not place (longer than a slot, a size that is no multiple of 4),
 // those whose scan or colour-space tag differs from the first sample's, and -- when the band decoders' one error word is set after the pass -- every sample the parser
@@ -134,8 +135,18 @@ int allocate(cfhd_amd_decode_batch *b)
 }
 
 // k_dec_deliver over pictures [first, first + count) of the batch's own buffer, queued on the batch's stream: into the caller's device memory, in the layout it asked for.
-int launch_deliver(cfhd_amd_decode_batch *b, int first, int count)
+// (slow_mode: the RGB_AS_YUV_* mode of a run of pictures the handle decoded in wait; -1: the launch of a pass, whose pictures are judged by their verdict words)
+int launch_deliver(cfhd_amd_decode_batch *b, int first, int count, int slow_mode = -1)
 {
+	if (dev::deliver_is_rgb_as_yuv(b->dev_out_layout)) {  // the RG48 pictures of RGB samples as the YU64 picture, packed or as planes (set_device_pictures checked the geometry the kernel assumes)
+		const bool pass = slow_mode < 0;                   // (first = 0: the verdict words are indexed by the picture)
+		dev::k_dec_deliver_rgb_as_yuv<<<dim3(dev::dec_deliver_pieces(b->picture_rows()), (unsigned)count), dev::DEC_DELIVER_THREADS, 0, (hipStream_t)b->stream()>>>(
+			b->device_pictures() + b->picture_bytes() * (size_t)first, b->picture_bytes(), b->picture_rows(), b->picture_width(),
+			b->dev_out + b->dev_out_stride * (size_t)first, b->dev_out_stride, b->dev_out_pitch, b->dev_out_layout, pass ? dev::deliver_rgb_as_yuv_mode(b->st.color_space) : slow_mode,
+			pass ? b->d_verdicts : nullptr, pass ? b->d_verdicts + b->n : nullptr, b->clean_word());
+		HIPCHK(hipGetLastError());
+		return 0;
+	}
 	if (dev::deliver_is_bayer(b->dev_out_layout)) {      // the BYR4 mosaics of a Bayer batch as four planes (set_device_pictures checked the geometry the kernel assumes)
 		const int quad_rows = b->picture_rows() / 2;
 		dev::k_dec_deliver_bayer<<<dim3(dev::dec_deliver_pieces(quad_rows), (unsigned)count), dev::DEC_DELIVER_THREADS, 0, (hipStream_t)b->stream()>>>(
@@ -428,7 +439,9 @@ int cfhd_amd_decode_batch_set_device_pictures(cfhd_amd_decode_batch *b, void *d_
 	const bool yuv422 = dev::deliver_is_yuv422(layout) && b->st.out_kind != PIX_BYR4;
 	// (the RGBA_* layouts exist for the pictures that carry an alpha component -- b64a, BGRA, BGRa --: to every other batch they are unknown)
 	const bool rgba = dev::deliver_is_rgba(layout) && (b->st.out_kind == PIX_B64A || b->st.out_kind == PIX_BGRA || b->st.out_kind == PIX_BGRa);
-	if (!bayer && !yuv422 && !rgba && (layout < CFHD_AMD_PICTURES_PACKED || layout > CFHD_AMD_PICTURES_PLANAR_F32)) { refuse("decode queue: unknown layout of the device pictures"); return -1; }
+	// (the RGB_AS_* layouts exist for RG48 pictures: to every batch with another output they are unknown)
+	const bool rgb_as_yuv = dev::deliver_is_rgb_as_yuv(layout) && b->st.out_kind == PIX_RG48;
+	if (!bayer && !yuv422 && !rgba && !rgb_as_yuv && (layout < CFHD_AMD_PICTURES_PACKED || layout > CFHD_AMD_PICTURES_PLANAR_F32)) { refuse("decode queue: unknown layout of the device pictures"); return -1; }
 	if (yuv422) {
 		const int kind = b->st.out_kind;
 		if (kind != PIX_YUY2 && kind != PIX_2VUY && kind != PIX_YU64) { refuse("decode queue: the 4:2:2 plane layouts serve batches whose output is YUY2, 2vuy or YU64"); return -1; }
@@ -439,7 +452,14 @@ int cfhd_amd_decode_batch_set_device_pictures(cfhd_amd_decode_batch *b, void *d_
 		if (layout == CFHD_AMD_PICTURES_RGBA_U8 && b->st.out_kind == PIX_B64A) { refuse("decode queue: RGBA_U8 serves the 8-bit outputs BGRA and BGRa; a b64a batch delivers RGBA_U16"); return -1; }
 		if (layout == CFHD_AMD_PICTURES_RGBA_U16 && b->st.out_kind != PIX_B64A) { refuse("decode queue: RGBA_U16 serves b64a; a BGRA or BGRa batch delivers RGBA_U8"); return -1; }
 	}
-	const bool planar = !bayer && !yuv422 && !rgba && layout != CFHD_AMD_PICTURES_PACKED;
+	if (rgb_as_yuv) {
+		const int enc = b->st.plan.encoded_format;
+		if (b->groups || b->st.half || (enc != ENC_RGB444 && enc != ENC_RGBA4444)) {
+			refuse("decode queue: the RGB_AS_* layouts serve full-resolution RG48 batches of RGB 4:4:4 and RGBA 4:4:4:4 samples (the YU64 picture of the RG48 one); a 4:2:2 sample decodes to YU64 directly"); return -1;
+		}
+		if (b->picture_width() & 1) { refuse("decode queue: the RGB_AS_* layouts pair the pixels of a row: the width is even"); return -1; }
+	}
+	const bool planar = !bayer && !yuv422 && !rgba && !rgb_as_yuv && layout != CFHD_AMD_PICTURES_PACKED;
 	if (planar && b->st.out_kind != PIX_RG48) { refuse("decode queue: the planar layouts serve batches whose output is RG48"); return -1; }
 	if (((uintptr_t)d_pictures | picture_stride | (size_t)(unsigned)picture_pitch) & 15) { refuse("decode queue: the device pictures' pointer, stride and pitch are multiples of 16"); return -1; }
 	if (yuv422) {
@@ -454,6 +474,29 @@ int cfhd_amd_decode_batch_set_device_pictures(cfhd_amd_decode_batch *b, void *d_
 		if (picture_pitch < luma_row) { refuse("decode queue: the pitch is below the luma row of the 4:2:2 plane layout (width x element size)"); return -1; }
 		if (picture_stride < (size_t)picture_pitch * (size_t)h + (size_t)(picture_pitch / 2) * (2 * (size_t)h - 1) + (size_t)(luma_row / 2)) {
 			refuse("decode queue: the stride is below the three planes of the 4:2:2 layout (H x pitch, then 2 H chroma rows pitch / 2 apart)"); return -1;
+		}
+		b->dev_out = (uint8_t *)d_pictures; b->dev_out_stride = picture_stride; b->dev_out_pitch = picture_pitch; b->dev_out_layout = layout;
+		return 0;
+	}
+	if (rgb_as_yuv) {
+		const bool packed = layout == CFHD_AMD_PICTURES_RGB_AS_YU64;
+		const int w = b->picture_width(), h = b->picture_rows();
+		// what k_dec_deliver_rgb_as_yuv assumes of the batch's own pictures: rows of 6 x width bytes back to back, the pictures on 16-byte boundaries
+		if (b->picture_pitch() != 6 * w || b->picture_bytes() != (size_t)b->picture_pitch() * (size_t)h || (((uintptr_t)b->device_pictures() | b->picture_bytes()) & 15) || b->n > 65535 /* blockIdx.y */) {
+			refuse("decode queue: pictures the RGB-as-YUV deliver kernel does not take"); return -1;
+		}
+		if (packed) {
+			// H rows of 4 x W bytes at the pitch, of which the last needs its row bytes only
+			if (picture_pitch < 4LL * w) { refuse("decode queue: the pitch is below the row of the RGB_AS_YU64 layout (4 x width bytes)"); return -1; }
+			if (picture_stride < (size_t)picture_pitch * (size_t)(h - 1) + 4 * (size_t)w) { refuse("decode queue: the stride is below the rows of the RGB_AS_YU64 layout (H rows a pitch apart)"); return -1; }
+		} else {
+			// the geometry of the YUV422_* layouts: Y at the pitch, Cb and Cr at half of it
+			if (picture_pitch & 31) { refuse("decode queue: the pitch of an RGB_AS_YUV422 layout is a multiple of 32 (the chroma planes' is half of it)"); return -1; }
+			const long long luma_row = (long long)w * dev::deliver_rgb_as_yuv_element_bytes(layout);
+			if (picture_pitch < luma_row) { refuse("decode queue: the pitch is below the luma row of the RGB_AS_YUV422 layout (width x element size)"); return -1; }
+			if (picture_stride < (size_t)picture_pitch * (size_t)h + (size_t)(picture_pitch / 2) * (2 * (size_t)h - 1) + (size_t)(luma_row / 2)) {
+				refuse("decode queue: the stride is below the three planes of the RGB_AS_YUV422 layout (H x pitch, then 2 H chroma rows pitch / 2 apart)"); return -1;
+			}
 		}
 		b->dev_out = (uint8_t *)d_pictures; b->dev_out_stride = picture_stride; b->dev_out_pitch = picture_pitch; b->dev_out_layout = layout;
 		return 0;
@@ -569,6 +612,8 @@ int cfhd_amd_decode_batch_wait(cfhd_amd_decode_batch *b, CFHD_Error *status)
 	std::vector<uint8_t> bytes;
 	int decoded = 0, failure = 0;
 	std::vector<int> slow;                                 // the samples the handle decoded, for k_dec_deliver behind the loop
+	std::vector<int> slow_mode;                            // ... and, for the RGB_AS_* layouts, what each is delivered as: its own sample's matrix, or zeros where the handle refused it
+	const bool rgb_as_yuv = b->dev_out && dev::deliver_is_rgb_as_yuv(b->dev_out_layout);
 	for (int i = count; i < n; i++) b->slow_pictures[i].clear();      // (a short pass: what an earlier pass left behind its count is that pass's picture in HBM again)
 	for (int i = 0; i < count; i++) {
 		uint32_t v = b->h_verdicts[i], mark = b->h_verdicts[n + i];
@@ -607,16 +652,19 @@ int cfhd_amd_decode_batch_wait(cfhd_amd_decode_batch *b, CFHD_Error *status)
 			if (b->dev_out) {
 				if (hipMemcpy(b->device_pictures() + picture_bytes * (size_t)i, b->slow_pictures[i].data(), picture_bytes, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); failure = -2; }
 				slow.push_back(i);
+				int mode = dev::RGB_AS_YUV_ZERO;
+				if (rgb_as_yuv && rc == ERR_OKAY) { ParsedSample own; mode = dev::deliver_rgb_as_yuv_mode(parse_sample(s, size, &own) >= 0 ? own.color_space : 0); }
+				slow_mode.push_back(rgb_as_yuv ? mode : -1);
 			}
 		}
 		if (status) status[i] = rc;
 		decoded += rc == ERR_OKAY;
 	}
-	// one launch per run of neighbouring slow samples (a damaged code stream: one run, the whole pass), then one wait
+	// one launch per run of neighbouring slow samples (a damaged code stream: one run, the whole pass; the RGB_AS_* layouts: neighbours of one mode), then one wait
 	for (size_t k = 0; k < slow.size() && !failure;) {
 		size_t e = k + 1;
-		while (e < slow.size() && slow[e] == slow[e - 1] + 1) e++;
-		if (launch_deliver(b, slow[k], (int)(e - k))) failure = -2;
+		while (e < slow.size() && slow[e] == slow[e - 1] + 1 && slow_mode[e] == slow_mode[k]) e++;
+		if (launch_deliver(b, slow[k], (int)(e - k), slow_mode[k])) failure = -2;
 		k = e;
 	}
 	if (!slow.empty() && !failure && b->wait_stream()) failure = -2;
@@ -656,7 +704,7 @@ float cfhd_amd_decode_batch_kernel_ms(cfhd_amd_decode_batch *b, int which)
 
 const char *cfhd_amd_decode_batch_kernel_name(cfhd_amd_decode_batch *b, int which)
 {
-	if (b && !b->in_flight && which == 9) return b->dev_out && dev::deliver_is_bayer(b->dev_out_layout) ? "k_dec_deliver_bayer" : (b->dev_out && dev::deliver_is_yuv422(b->dev_out_layout) ? "k_dec_deliver_yuv422" : (b->dev_out && dev::deliver_is_rgba(b->dev_out_layout) ? "k_dec_deliver_rgba" : "k_dec_deliver"));
+	if (b && !b->in_flight && which == 9) return b->dev_out && dev::deliver_is_bayer(b->dev_out_layout) ? "k_dec_deliver_bayer" : (b->dev_out && dev::deliver_is_yuv422(b->dev_out_layout) ? "k_dec_deliver_yuv422" : (b->dev_out && dev::deliver_is_rgba(b->dev_out_layout) ? "k_dec_deliver_rgba" : (b->dev_out && dev::deliver_is_rgb_as_yuv(b->dev_out_layout) ? "k_dec_deliver_rgb_as_yuv" : "k_dec_deliver")));
 	if (!b || b->in_flight || which < 0 || which > 7) return "";
 	static const char *const fixed[4] = { "k_dec_ingest", "k_dec_parse", "k_dec_plan+k_dec_index+k_dec_chain+k_dec_tiles", "k_dec_lowpass" };
 	if (which < 4 && !(b->groups && which)) return fixed[which];

@@ -3,7 +3,9 @@
 // pictures they are, at the caller's pitch, or, for RG48, as three planes R, G, B of u16, f16 or f32 elements (a torch tensor N x 3 x H x W) -- and k_dec_deliver_bayer,
 // which takes its place for the BYR4 mosaics of a Bayer batch delivered as four planes, one per position of the 2 x 2 quad (N x 4 x H/2 x W/2), and k_dec_deliver_yuv422,
 // which takes it for the packed 4:2:2 pictures (YUY2, 2vuy, YU64) delivered as a luma plane and two chroma planes of half the width (I422: N x [H x W | 2 x H x W/2]), and
-// k_dec_deliver_rgba, which takes it for the four-component pictures (b64a, BGRA, BGRa) delivered as four planes R, G, B, A, top row first (N x 4 x H x W).
+// k_dec_deliver_rgba, which takes it for the four-component pictures (b64a, BGRA, BGRa) delivered as four planes R, G, B, A, top row first (N x 4 x H x W), and
+// k_dec_deliver_rgb_as_yuv, which takes it for the RG48 pictures of RGB samples delivered as the YU64 picture the reference decodes such a sample to, packed or as
+// Y, Cb, Cr planes.
 #pragma once
 #include <stdint.h>
 #include <stddef.h>
@@ -445,6 +447,147 @@ __global__ void __launch_bounds__(DEC_DELIVER_THREADS) k_dec_deliver_rgba(const 
 			else if (layout == DELIVER_RGBA_F16) deliver_rgba_row_bytes<DELIVER_RGBA_F16>(row, width, aligned, orow, plane, lane);
 			else deliver_rgba_row_bytes<DELIVER_RGBA_F32>(row, width, aligned, orow, plane, lane);
 		}
+	}
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_dec_deliver_rgb_as_yuv: RG48 picture i of the pass -- the decoded picture of an RGB 4:4:4 or RGBA 4:4:4:4 sample, `rows` rows of `width` pixels (an even number)
+// back to back at src + i * src_stride, 6 x width bytes a row -- into dst + i * dst_stride as the YU64 picture the reference decoder gives for the same sample
+// (ReconstructSampleFrameRGB444ToBuffer -> TransformInverseRGB444ToYU64, decoder.c:26874, wavelet.c:4515; the arithmetic is the scalar loop of
+// ConvertPlanarRGB16uToPackedYU64, convert.c:7841-7864, restated):
+//   pixels (2 k, 2 k + 1) of a row form a pair.  With the RG48 words r, g, b as IEEE singles, every product and sum rounded to single on its own (no fused
+//   multiply-add), evaluated as (cr * R + cg * G) + cb * B, every coefficient (float)c * 64.0f, the conversion to int truncating toward zero and >> arithmetic:
+//     Y(x)  = sat16(((int)(yr r + yg g + yb b) >> 6) + 4096)
+//     Cb(k) = sat16(((int)(ur (r0 + r1) + ug (g0 + g1) + ub (b0 + b1)) >> 7) + 32768), Cr(k) the same with the v row; the sums are converted to single once.
+//   4096 is added under both matrices, as the reference adds it; bright pixels saturate under the video-systems one.
+//   The matrix rows (y; u; v) follow bit 2 of the colour-space tag of the picture's own sample (RGB_AS_YUV_CG: the tag absent or the bit clear; RGB_AS_YUV_VS: set).
+// `layout`: DELIVER_RGB_AS_YU64 -- row r at dst_pitch * r, 4 x width bytes, the words Y0 Cr Y1 Cb of every pair -- or DELIVER_RGB_AS_YUV422_U16 / _F16 / _F32: the same
+// values in the geometry of k_dec_deliver_yuv422 (Y, `rows` rows of `width` elements dst_pitch apart, at 0; Cb, `rows` rows of width / 2 elements dst_pitch / 2 apart,
+// behind it; Cr behind that), U16 the word, F32 deliver_unit_f32 of it, F16 deliver_f16_bits of that.  Every row gets its bytes and nothing else.
+// The picture's mode: `mode` (RGB_AS_YUV_CG, _VS, or _ZERO: zeros, 0.0, in place of the picture -- a sample that failed), one for the launch; where `verdicts` is not
+// null -- the launch of a pass, behind k_dec_blank, first picture 0 -- picture i has `mode` if verdicts[i] == clean and marks[i] == 0, k_dec_blank's own condition, and
+// RGB_AS_YUV_ZERO otherwise (black RG48 is not zero in YU64: a blanked picture has to be told from a black one).
+//   A wave owns a row at a time.  A lane holds whole pairs, no lane needs another's words: U16 / F16 16 pixels -- six 16-byte loads of consecutive bytes (96 bytes, 6 KB
+//   a wave), two 16-byte stores of luma, one per chroma plane --, F32 and YU64 8 pixels -- three loads; F32 two stores of luma and one per chroma plane, YU64 two stores
+//   of the packed row: a lane's stores to one row kept to 32 consecutive bytes, as measured for k_dec_deliver_yuv422.  The pairs behind the last whole group go pair by
+//   pair, a lane a pair: three longword loads, and stores no wider than the pair (k_half_packed16's lesson: nothing is written behind the row bytes).  The widths the
+//   encoders give RGB samples are multiples of 8: every row of the batch's buffer starts on a 16-byte boundary (checked where the layout is set); should a gate ever
+//   admit an even width that is no multiple of 8, the rows are longword aligned and the whole picture goes pair by pair.
+// No LDS, no scratch.  Grid (row pieces: dec_deliver_pieces(rows), pictures), DEC_DELIVER_WAVES rows per piece and step.
+// ---------------------------------------------------------------------------------------------
+// (CFHD_AMD_PICTURES_RGB_AS_*)
+enum { DELIVER_RGB_AS_YU64 = 15, DELIVER_RGB_AS_YUV422_U16 = 16, DELIVER_RGB_AS_YUV422_F16 = 17, DELIVER_RGB_AS_YUV422_F32 = 18 };
+enum { RGB_AS_YUV_CG = 0, RGB_AS_YUV_VS = 1, RGB_AS_YUV_ZERO = 2 };
+inline bool deliver_is_rgb_as_yuv(int layout) { return layout >= DELIVER_RGB_AS_YU64 && layout <= DELIVER_RGB_AS_YUV422_F32; }
+inline int deliver_rgb_as_yuv_element_bytes(int layout) { return layout == DELIVER_RGB_AS_YUV422_F32 ? 4 : 2; }
+// the mode of a sample that decoded, by its colour-space tag (0: no tag)
+inline int deliver_rgb_as_yuv_mode(int color_space) { return color_space & 4 ? RGB_AS_YUV_VS : RGB_AS_YUV_CG; }
+template <int LAYOUT> struct deliver_rgb_as_yuv_pixels { static constexpr int value = LAYOUT == DELIVER_RGB_AS_YUV422_U16 || LAYOUT == DELIVER_RGB_AS_YUV422_F16 ? 16 : 8; };
+
+// one product, one sum: rounded to single each, never fused.  (hipcc contracts a * b + c into a fused multiply-add by default, and through __fmul_rn / __fadd_rn too,
+// which are plain operators in its headers: the pragma takes the permission away from the operations of these two functions, wherever they are inlined.  A host
+// compiler for x86-64 without -mfma has no fused instruction to contract into.)
+__host__ __device__ inline float deliver_mul(float a, float b)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+	return a * b;
+}
+__host__ __device__ inline float deliver_add(float a, float b)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+	return a + b;
+}
+struct RgbAsYuvMatrix { float yr, yg, yb, ur, ug, ub, vr, vg, vb; };
+__host__ __device__ inline RgbAsYuvMatrix deliver_rgb_as_yuv_matrix(bool vs)
+{
+	RgbAsYuvMatrix m;
+	m.yr = (vs ? 0.213f : 0.183f) * 64.0f; m.yg = (vs ? 0.715f : 0.614f) * 64.0f; m.yb = (vs ? 0.072f : 0.062f) * 64.0f;
+	m.ur = (vs ? -0.117f : -0.101f) * 64.0f; m.ug = (vs ? -0.394f : -0.338f) * 64.0f; m.ub = (vs ? 0.511f : 0.439f) * 64.0f;
+	m.vr = (vs ? 0.511f : 0.439f) * 64.0f; m.vg = (vs ? -0.464f : -0.399f) * 64.0f; m.vb = (vs ? -0.047f : -0.040f) * 64.0f;
+	return m;
+}
+__host__ __device__ inline uint32_t deliver_sat16(int v) { return (uint32_t)(v < 0 ? 0 : (v > 65535 ? 65535 : v)); }
+__host__ __device__ inline int deliver_rgb_dot(float cr, float cg, float cb, float r, float g, float b) { return (int)deliver_add(deliver_add(deliver_mul(cr, r), deliver_mul(cg, g)), deliver_mul(cb, b)); }
+// one pair of pixels, the three longwords (R0, G0), (B0, R1), (G1, B1): Y0, Y1, Cb, Cr as words
+__host__ __device__ inline void deliver_rgb_as_yuv_pair(const RgbAsYuvMatrix &m, uint32_t d0, uint32_t d1, uint32_t d2, uint32_t &y0, uint32_t &y1, uint32_t &cb, uint32_t &cr)
+{
+	const int r0 = (int)(d0 & 0xffffu), g0 = (int)(d0 >> 16), b0 = (int)(d1 & 0xffffu), r1 = (int)(d1 >> 16), g1 = (int)(d2 & 0xffffu), b1 = (int)(d2 >> 16);
+	y0 = deliver_sat16((deliver_rgb_dot(m.yr, m.yg, m.yb, (float)r0, (float)g0, (float)b0) >> 6) + 4096);
+	y1 = deliver_sat16((deliver_rgb_dot(m.yr, m.yg, m.yb, (float)r1, (float)g1, (float)b1) >> 6) + 4096);
+	const float rs = (float)(r0 + r1), gs = (float)(g0 + g1), bs = (float)(b0 + b1);
+	cb = deliver_sat16((deliver_rgb_dot(m.ur, m.ug, m.ub, rs, gs, bs) >> 7) + 32768);
+	cr = deliver_sat16((deliver_rgb_dot(m.vr, m.vg, m.vb, rs, gs, bs) >> 7) + 32768);
+}
+// N words of one plane row (N: 1 or a multiple of 2) as the elements of LAYOUT at `at`
+template <int LAYOUT, int N> __device__ __forceinline__ void deliver_rgb_as_yuv_store(uint8_t *at, const uint32_t *w)
+{
+	if constexpr (N == 1) {
+		if constexpr (LAYOUT == DELIVER_RGB_AS_YUV422_F32) { const float f = deliver_unit_f32(w[0]); uint32_t d; memcpy(&d, &f, 4); *(uint32_t *)at = d; }
+		else *(uint16_t *)at = (uint16_t)(LAYOUT == DELIVER_RGB_AS_YUV422_F16 ? deliver_f16_bits(deliver_unit_f32(w[0])) : w[0]);
+	} else if constexpr (LAYOUT == DELIVER_RGB_AS_YUV422_F32) {
+		uint32_t d[N];
+		for (int k = 0; k < N; k++) { const float f = deliver_unit_f32(w[k]); memcpy(&d[k], &f, 4); }
+		deliver_store_longwords<N>(at, d);
+	} else {
+		uint32_t d[N / 2];
+		for (int k = 0; k < N / 2; k++)
+			d[k] = LAYOUT == DELIVER_RGB_AS_YUV422_F16 ? (deliver_f16_bits(deliver_unit_f32(w[2 * k])) | (deliver_f16_bits(deliver_unit_f32(w[2 * k + 1])) << 16)) : (w[2 * k] | (w[2 * k + 1] << 16));
+		deliver_store_longwords<N / 2>(at, d);
+	}
+}
+// N pixels (2: one pair, longword loads; 8 or 16: 16-byte loads at `in`, a multiple of 16) of an RG48 row to their places: `y` the packed row (YU64) or the luma row
+template <int LAYOUT, int N> __device__ __forceinline__ void deliver_rgb_as_yuv_pixels_at(const RgbAsYuvMatrix &m, bool zero, const uint8_t *in, uint8_t *y, uint8_t *cb, uint8_t *cr)
+{
+	uint32_t d[3 * N / 2], yy[N], u[N / 2], v[N / 2];
+	if (zero) { for (int k = 0; k < N; k++) yy[k] = 0u; for (int k = 0; k < N / 2; k++) u[k] = v[k] = 0u; }
+	else {
+		if constexpr (N == 2) { d[0] = CFHD_LDG32(in); d[1] = CFHD_LDG32(in + 4); d[2] = CFHD_LDG32(in + 8); }
+		else for (int k = 0; k < 3 * N / 8; k++) { const cfhd_u4 q = CFHD_LDG128(in + 16 * k); d[4 * k] = q.x; d[4 * k + 1] = q.y; d[4 * k + 2] = q.z; d[4 * k + 3] = q.w; }
+		for (int j = 0; j < N / 2; j++) deliver_rgb_as_yuv_pair(m, d[3 * j], d[3 * j + 1], d[3 * j + 2], yy[2 * j], yy[2 * j + 1], u[j], v[j]);
+	}
+	if constexpr (LAYOUT == DELIVER_RGB_AS_YU64) {
+		uint32_t p[N];                                           // (Y0, Cr), (Y1, Cb) of every pair
+		for (int j = 0; j < N / 2; j++) { p[2 * j] = yy[2 * j] | (v[j] << 16); p[2 * j + 1] = yy[2 * j + 1] | (u[j] << 16); }
+		deliver_store_longwords<N>(y, p);
+	} else {
+		deliver_rgb_as_yuv_store<LAYOUT, N>(y, yy); deliver_rgb_as_yuv_store<LAYOUT, N / 2>(cb, u); deliver_rgb_as_yuv_store<LAYOUT, N / 2>(cr, v);
+	}
+}
+// one row of `width` pixels (even)
+template <int LAYOUT> __device__ __forceinline__ void deliver_rgb_as_yuv_row(const RgbAsYuvMatrix &m, bool zero, const uint8_t *row, int width, bool aligned, uint8_t *y, uint8_t *cb, uint8_t *cr, int lane)
+{
+	constexpr int P = deliver_rgb_as_yuv_pixels<LAYOUT>::value;
+	// the bytes a pixel has in the row `y` points at, and a chroma element in its plane row
+	constexpr int E = LAYOUT == DELIVER_RGB_AS_YU64 || LAYOUT == DELIVER_RGB_AS_YUV422_F32 ? 4 : 2, C = LAYOUT == DELIVER_RGB_AS_YUV422_F32 ? 4 : 2;
+	const int groups = aligned ? width / P : 0, pairs = width >> 1;
+	for (int g = lane; g < groups; g += 64) deliver_rgb_as_yuv_pixels_at<LAYOUT, P>(m, zero, row + (size_t)6 * P * g, y + (size_t)P * E * g, cb + (size_t)(P / 2) * C * g, cr + (size_t)(P / 2) * C * g);
+	for (int k = groups * (P / 2) + lane; k < pairs; k += 64) deliver_rgb_as_yuv_pixels_at<LAYOUT, 2>(m, zero, row + (size_t)12 * k, y + (size_t)2 * E * k, cb + (size_t)C * k, cr + (size_t)C * k);
+}
+
+__global__ void __launch_bounds__(DEC_DELIVER_THREADS) k_dec_deliver_rgb_as_yuv(const uint8_t *src, size_t src_stride, int rows, int width, uint8_t *dst, size_t dst_stride, int dst_pitch, int layout, int mode,
+                                                                               const uint32_t *verdicts, const uint32_t *marks, uint32_t clean)
+{
+	const int lane = (int)(threadIdx.x & 63u), wave = wave_uniform((int)(threadIdx.x >> 6));
+	// (the two words through the vector memory path, as everything else this kernel reads: a volatile access is never given to the scalar unit)
+	if (verdicts && !(((const volatile uint32_t *)verdicts)[blockIdx.y] == clean && !((const volatile uint32_t *)marks)[blockIdx.y])) mode = RGB_AS_YUV_ZERO;
+	const bool zero = mode == RGB_AS_YUV_ZERO;
+	const RgbAsYuvMatrix m = deliver_rgb_as_yuv_matrix(mode == RGB_AS_YUV_VS);
+	const uint8_t *pic = src + src_stride * (size_t)blockIdx.y;
+	uint8_t *out = dst + dst_stride * (size_t)blockIdx.y;
+	const int row_bytes = 6 * width, chroma_pitch = dst_pitch >> 1;
+	const bool aligned = !(((uintptr_t)src | src_stride | (size_t)row_bytes) & 15);      // every row of the batch's pictures starts on a 16-byte boundary
+	uint8_t *cb_plane = out + (size_t)dst_pitch * (size_t)rows, *cr_plane = cb_plane + (size_t)chroma_pitch * (size_t)rows;
+	for (int r = (int)blockIdx.x * DEC_DELIVER_WAVES + wave; r < rows; r += (int)gridDim.x * DEC_DELIVER_WAVES) {
+		const uint8_t *row = pic + (size_t)r * row_bytes;
+		uint8_t *y = out + (size_t)r * dst_pitch, *cb = cb_plane + (size_t)r * chroma_pitch, *cr = cr_plane + (size_t)r * chroma_pitch;
+		if (layout == DELIVER_RGB_AS_YU64) deliver_rgb_as_yuv_row<DELIVER_RGB_AS_YU64>(m, zero, row, width, aligned, y, cb, cr, lane);
+		else if (layout == DELIVER_RGB_AS_YUV422_U16) deliver_rgb_as_yuv_row<DELIVER_RGB_AS_YUV422_U16>(m, zero, row, width, aligned, y, cb, cr, lane);
+		else if (layout == DELIVER_RGB_AS_YUV422_F16) deliver_rgb_as_yuv_row<DELIVER_RGB_AS_YUV422_F16>(m, zero, row, width, aligned, y, cb, cr, lane);
+		else deliver_rgb_as_yuv_row<DELIVER_RGB_AS_YUV422_F32>(m, zero, row, width, aligned, y, cb, cr, lane);
 	}
 }
 

@@ -435,16 +435,37 @@ int  cfhd_amd_decode_batch_submit_device(cfhd_amd_decode_batch *batch, const voi
  * 0xfff0 of RGB 4:4:4 samples; BGRA / BGRa: the byte the conversion writes).  CFHD_AMD_FRAMES_RGBA_* of cfhd_amd_batch_upload_device_planar invert these rules as
  * the YUV422 layouts do.  The pitch is >= W * element size; the stride is >= (4 H - 1) * picture_pitch + W * element size.  Written by k_dec_deliver_rgba in place
  * of k_dec_deliver (kernel_name(batch, 9) answers it while such a layout is set; kernel_ms index 9 times it).
+ * CFHD_AMD_PICTURES_RGB_AS_YU64 / _RGB_AS_YUV422_U16 / _F16 / _F32: the YU64 picture of an RGB sample, for the consumer that holds an RGB master and needs 4:2:2 -- served
+ * on a batch made by cfhd_amd_decode_batch_create from an RGB 4:4:4 or RGBA 4:4:4:4 sample with output RG48 at full resolution, whose width is even; every other
+ * batch whose output is RG48 (a 4:2:2 sample -- it decodes to YU64 directly --, a batch of groups, half resolution) is told so, and to every batch with another output
+ * the values are unknown layouts.  (CFHD_PrepareToDecode and cfhd_amd_decode_batch_create keep refusing YU64 of such a sample: the conversion lives in the delivery.)
+ * The values are those the reference decoder writes for the same sample and output YU64, word for word: a pure function of the batch's RG48 picture r, g, b (0 ..
+ * 65535).  Pixels (2 k, 2 k + 1) of a row form a pair; with every product and sum an IEEE single of its own (never fused), evaluated as (cr * R + cg * G) + cb * B,
+ * every coefficient (float)c * 64.0f, the conversion to int truncating toward zero and >> arithmetic:
+ *   Y(x)  = sat16(((int)(yr r + yg g + yb b) >> 6) + 4096)
+ *   Cb(k) = sat16(((int)(ur (r0 + r1) + ug (g0 + g1) + ub (b0 + b1)) >> 7) + 32768); Cr(k) the same with the v row; the sums are converted to single once;
+ * sat16 clamps to 0 .. 65535.  The rows (y; u; v) are (0.183, 0.614, 0.062; -0.101, -0.338, 0.439; 0.439, -0.399, -0.040) for a sample without a colour-space tag
+ * or with bit 2 (value 4) of it clear, and (0.213, 0.715, 0.072; -0.117, -0.394, 0.511; 0.511, -0.464, -0.047) with the bit set; 4096 is added under both, so bright
+ * pixels saturate under the second: the reference's behaviour.  Every picture is converted with the matrix of its own sample's tag; a pass may mix them (a sample whose
+ * tag differs from the first sample's is decoded by the handle inside wait and delivered by a launch of its own there).  The picture of a sample that failed is
+ * zeros (0.0), not the conversion of black.
+ * _RGB_AS_YU64: the packed picture, rows of 4 * W bytes, the words Y0 Cr Y1 Cb; the pitch is a multiple of 16 and >= 4 * W, the stride >= (H - 1) * picture_pitch
+ * + 4 * W.  _RGB_AS_YUV422_U16 / _F16 / _F32: the same words as three planes in exactly the geometry of CFHD_AMD_PICTURES_YUV422_* (Y: H rows of W elements; Cb, Cr:
+ * H rows of W / 2 elements at half the pitch; the pitch a multiple of 32, the stride rule that of the YUV422 layouts), _F32 (float)w * (1.0f / 65535.0f), _F16 that
+ * value rounded to nearest-even to binary16.  Written by k_dec_deliver_rgb_as_yuv in place of k_dec_deliver (kernel_name(batch, 9) answers it while such a layout is
+ * set; kernel_ms index 9 times it).  Host delivery and cfhd_amd_decode_batch_download_output give the RG48 picture beside it, unchanged.
  * Exactly count pictures are written, of every row its row bytes and nothing else: pitch padding, the space between planes and pictures and the pictures behind a short
  * pass are not touched.
  * 0; -1 with the reason in cfhd_amd_last_error(): a pass in flight, an unknown layout, a planar layout on a batch whose output is not RG48, a pointer, stride or pitch
  * that is no multiple of 16, a pitch below the row bytes of the layout, a stride below what one picture occupies; a 4:2:2 plane layout on a batch whose output is not
  * YUY2, 2vuy or YU64, _U8 on a YU64 batch, _U16 on an 8-bit one, a pitch of such a layout that is no multiple of 32; RGBA_U8 on a b64a batch, RGBA_U16 on a BGRA or
- * BGRa one. */
+ * BGRa one; an RGB_AS_* layout on an RG48 batch it does not serve, on an odd width, with a pitch below its row (or, the plane forms, no multiple of 32), with a
+ * stride below its rows or planes. */
 enum { CFHD_AMD_PICTURES_PACKED = 0, CFHD_AMD_PICTURES_PLANAR_U16 = 1, CFHD_AMD_PICTURES_PLANAR_F16 = 2, CFHD_AMD_PICTURES_PLANAR_F32 = 3 };
 enum { CFHD_AMD_PICTURES_BAYER_U16 = 4, CFHD_AMD_PICTURES_BAYER_F16 = 5, CFHD_AMD_PICTURES_BAYER_F32 = 6 };
 enum { CFHD_AMD_PICTURES_YUV422_U8 = 7, CFHD_AMD_PICTURES_YUV422_U16 = 8, CFHD_AMD_PICTURES_YUV422_F16 = 9, CFHD_AMD_PICTURES_YUV422_F32 = 10 };
 enum { CFHD_AMD_PICTURES_RGBA_U8 = 11, CFHD_AMD_PICTURES_RGBA_U16 = 12, CFHD_AMD_PICTURES_RGBA_F16 = 13, CFHD_AMD_PICTURES_RGBA_F32 = 14 };
+enum { CFHD_AMD_PICTURES_RGB_AS_YU64 = 15, CFHD_AMD_PICTURES_RGB_AS_YUV422_U16 = 16, CFHD_AMD_PICTURES_RGB_AS_YUV422_F16 = 17, CFHD_AMD_PICTURES_RGB_AS_YUV422_F32 = 18 };
 int  cfhd_amd_decode_batch_set_device_pictures(cfhd_amd_decode_batch *batch, void *d_pictures, size_t picture_stride, int picture_pitch, int layout);
 /* Collects the pass: the number of samples that decoded, or < 0 (-1: nothing in flight, -2: device failure).  status (NULL or count entries): status[i] is the CFHD_Error
  * CFHD_DecodeSample returns for sample i on a handle prepared on the first sample; the picture of a sample that failed is zero.  Samples the device parser refuses are
@@ -457,7 +478,7 @@ int  cfhd_amd_decode_batch_wait(cfhd_amd_decode_batch *batch, CFHD_Error *status
 int  cfhd_amd_decode_batch_download_output(cfhd_amd_decode_batch *batch, int i, void *out, int pitch);
 /* HIP-event time (ms) of the kernels of the last pass and their names as a profiler shows them.  which: 0 k_dec_ingest, 1 k_dec_parse, 2 the band decoder (all its
  * kernels), 3 k_dec_lowpass, 4 / 5 / 6 the transform levels in launch order (the last one with the output conversion), 7 k_dec_blank, 9 k_dec_deliver (both kinds of
- * batch; k_dec_deliver_bayer while a BAYER_* layout is set, k_dec_deliver_yuv422 while a YUV422_* one is, k_dec_deliver_rgba while an RGBA_* one is; 0 ms when the last pass delivered nothing into device memory).  0 / "" otherwise. */
+ * batch; k_dec_deliver_bayer while a BAYER_* layout is set, k_dec_deliver_yuv422 while a YUV422_* one is, k_dec_deliver_rgba while an RGBA_* one is, k_dec_deliver_rgb_as_yuv while an RGB_AS_* one is; 0 ms when the last pass delivered nothing into device memory).  0 / "" otherwise. */
 float cfhd_amd_decode_batch_kernel_ms(cfhd_amd_decode_batch *batch, int which);
 const char *cfhd_amd_decode_batch_kernel_name(cfhd_amd_decode_batch *batch, int which);
 int  cfhd_amd_device_count(void);
