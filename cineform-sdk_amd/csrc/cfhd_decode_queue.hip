@@ -19,6 +19,12 @@
 // in a small slot behind the group slots (the table names every entry's slot: groups in front, followers behind them)  ->  k_dec_parse_group with a verdict per
 // group and per follower  ->  the band decoder (k_dec_band_two_pass for subband 7 of the groups from 8-bit RGB sources), k_dec_lowpass  ->  GopBatch's inverse
 // stages  ->  k_dec_blank over pairs.  A pair is judged alone: the slow handle forgets its last group in front of every pair it is given.
+//
+// A batch of thumbnails (cfhd_amd_decode_batch_create_thumbnails): the 1/8 x 1/8 DPX0 picture CFHD_GetThumbnail makes of every sample, from the raw lowpass words in
+// its slot.  The front of the same pass and nothing of the decoder: k_dec_ingest  ->  k_dec_parse (by itself: DecParseTables, no pyramid behind its tables)  ->
+// k_dec_thumbnail, which also writes the zeros of the samples without a clean verdict  ->  (k_dec_deliver: the DPX0 words; k_dec_deliver_rgb10: three planes of the 10-bit
+// values)  ->  (pictures D2H).  Such a batch never goes through DecodeBatch::prepare: it owns its slots, tables, verdicts and small pictures and one stream.  The slow
+// path of wait is CFHD_GetThumbnail on the sample's bytes: the samples k_dec_ingest could not place and those the parser does not pass (low byte of the verdict 1 .. 5).
 #include "../../include/cfhd_amd.h"
 #include "cfhd_core.h"
 #include "cfhd_bitstream.h"
@@ -26,6 +32,8 @@
 #include "cfhd_params.h"
 #include "cfhd_ingest_kernels.h"
 #include "cfhd_deliver_kernels.h"
+#include "cfhd_thumbnail_kernels.h"
+#include "cfhd_entropy_gpu.h"
 #include <hip/hip_runtime.h>
 #include <string.h>
 #include <stdio.h>
@@ -59,6 +67,10 @@ struct cfhd_amd_decode_batch {
 	// a batch of two-frame groups: n = 2 ngroups samples, decoded by gdec; group g is table entry g, its follower entry ngroups + g (entry_of)
 	bool groups = false; int ngroups = 0; GopBatch gdec; DecoderGroupState gst;
 	uint8_t *d_slots = nullptr; size_t group_cap = 0; char band_name[96] = "";
+	// a batch of thumbnails: thumb_w x thumb_h DPX0 longwords a picture in d_thumbs, slots of thumb_cap bytes in d_slots, k_dec_parse's own tables, the batch's one stream;
+	// h_thumbs: pinned, allocated by the first pass that delivers to plain host memory (thumbs_staged: this pass does)
+	bool thumbs = false; int thumb_w = 0, thumb_h = 0, thumb_yuv422 = 0; size_t thumb_cap = 0; void *thumb_stream = nullptr;
+	DecParseTables parse; uint8_t *d_thumbs = nullptr, *h_thumbs = nullptr; bool thumbs_staged = false; float parse_ms = 0, thumb_ms = 0;
 	enum { kFollowerCap = 1024 };            // the slot of a P-frame sample (24 bytes as the encoders write it); a longer one is the slow path's
 	CFHD_DecoderRef slow = nullptr;          // the handle create prepared on the first sample: the gates, and the slow path of wait
 	void *scope_stream = nullptr;            // the batch's one stream (StreamScope): released behind the decoder
@@ -92,26 +104,28 @@ struct cfhd_amd_decode_batch {
 	uint32_t clean_word() const { return dev::dec_verdict_word(0, st.progressive_flag, st.color_space); }
 	// sample i of a pass: its table entry, the capacity of its slot; the decoder behind the batch
 	int entry_of(int i) const { return groups ? ((i & 1) ? ngroups + (i >> 1) : (i >> 1)) : i; }
-	size_t cap_of(int i) { return groups ? ((i & 1) ? (size_t)kFollowerCap : group_cap) : dec.entropy().slot_bytes(); }
-	size_t slots_bytes() { return groups ? (size_t)ngroups * (group_cap + kFollowerCap) : dec.entropy().slot_bytes() * (size_t)n; }
-	void *stream() { return groups ? gdec.stream() : dec.stream(); }
-	int wait_stream() { return groups ? gdec.wait() : dec.wait(); }
-	int picture_pitch() const { return groups ? gdec.picture_pitch() : dec.picture_pitch(); }
-	int picture_rows() const { return groups ? gdec.picture_rows() : dec.picture_rows(); }
-	size_t picture_bytes() const { return groups ? gdec.picture_bytes() : dec.picture_bytes(); }
-	uint8_t *device_pictures() const { return groups ? gdec.device_pictures() : dec.device_pictures(); }
+	size_t cap_of(int i) { return thumbs ? thumb_cap : (groups ? ((i & 1) ? (size_t)kFollowerCap : group_cap) : dec.entropy().slot_bytes()); }
+	size_t slots_bytes() { return thumbs ? thumb_cap * (size_t)n : (groups ? (size_t)ngroups * (group_cap + kFollowerCap) : dec.entropy().slot_bytes() * (size_t)n); }
+	void *stream() { return thumbs ? thumb_stream : (groups ? gdec.stream() : dec.stream()); }
+	int wait_stream() { if (thumbs) { if (hipStreamSynchronize((hipStream_t)thumb_stream) != hipSuccess) { (void)hipGetLastError(); return -2; } return 0; } return groups ? gdec.wait() : dec.wait(); }
+	int picture_pitch() const { return thumbs ? 4 * thumb_w : (groups ? gdec.picture_pitch() : dec.picture_pitch()); }
+	int picture_rows() const { return thumbs ? thumb_h : (groups ? gdec.picture_rows() : dec.picture_rows()); }
+	size_t picture_bytes() const { return thumbs ? (size_t)4 * thumb_w * thumb_h : (groups ? gdec.picture_bytes() : dec.picture_bytes()); }
+	uint8_t *device_pictures() const { return thumbs ? d_thumbs : (groups ? gdec.device_pictures() : dec.device_pictures()); }
 	int finish_frame(int i, void *out, int pitch) { return groups ? gdec.finish_frame(i, out, pitch) : dec.finish_frame(i, out, pitch); }
 	int download_frame(int i, void *out, int pitch) { return groups ? gdec.download_frame(i, out, pitch) : dec.download_frame(i, out, pitch); }
 	// (a Bayer plan counts photosite quads: the mosaic is twice as wide)
-	int picture_width() const { const int full = groups ? gst.plan.width : (st.plan.encoded_format == ENC_BAYER ? 2 * st.plan.width : st.plan.width); return (groups ? gst.half : st.half) ? full / 2 : full; }
+	int picture_width() const { if (thumbs) return thumb_w; const int full = groups ? gst.plan.width : (st.plan.encoded_format == ENC_BAYER ? 2 * st.plan.width : st.plan.width); return (groups ? gst.half : st.half) ? full / 2 : full; }
 	~cfhd_amd_decode_batch()
 	{
 		(void)hipSetDevice(device);
 		dec.release(); gdec.release();
 		if (scope_stream) device_stream_release(scope_stream);
+		dec_parse_tables_release(&parse);
+		if (thumb_stream) device_stream_destroy(thumb_stream);
 		for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-		void *dv[] = { d_blob, d_table, d_sizes, d_verdicts, d_slots }; for (void *p : dv) if (p) (void)hipFree(p);
-		void *hv[] = { h_blob, h_table, h_verdicts }; for (void *p : hv) if (p) (void)hipHostFree(p);
+		void *dv[] = { d_blob, d_table, d_sizes, d_verdicts, d_slots, d_thumbs }; for (void *p : dv) if (p) (void)hipFree(p);
+		void *hv[] = { h_blob, h_table, h_verdicts, h_thumbs }; for (void *p : hv) if (p) (void)hipHostFree(p);
 		if (slow) (void)CFHD_CloseDecoder(slow);
 	}
 };
@@ -121,8 +135,8 @@ int allocate(cfhd_amd_decode_batch *b)
 {
 	b->blob_cap = b->slots_bytes() + 32;                 // a pass's samples fit whatever their alignment; a registered span with wider gaps is packed like plain memory
 	b->table_bytes = b->groups ? b->table_dst_at() + 12 * (size_t)b->n : 12 * (size_t)b->n + 4 * ((size_t)b->n + 1);
-	if (b->groups) HIPCHK(hipMalloc((void **)&b->d_slots, b->slots_bytes()));
-	HIPCHK(hipMalloc((void **)&b->d_blob, b->blob_cap));
+	if (b->groups || b->thumbs) HIPCHK(hipMalloc((void **)&b->d_slots, b->slots_bytes()));
+	if (!b->thumbs) HIPCHK(hipMalloc((void **)&b->d_blob, b->blob_cap));      // (a thumbnail batch: by its first submit_host -- samples that lie in HBM never need it)
 	HIPCHK(hipMalloc((void **)&b->d_table, b->table_bytes));
 	HIPCHK(hipHostMalloc((void **)&b->h_table, b->table_bytes, hipHostMallocPortable));
 	HIPCHK(hipMalloc((void **)&b->d_sizes, 4 * (size_t)b->n));
@@ -144,6 +158,13 @@ int launch_deliver(cfhd_amd_decode_batch *b, int first, int count, int slow_mode
 			b->device_pictures() + b->picture_bytes() * (size_t)first, b->picture_bytes(), b->picture_rows(), b->picture_width(),
 			b->dev_out + b->dev_out_stride * (size_t)first, b->dev_out_stride, b->dev_out_pitch, b->dev_out_layout, pass ? dev::deliver_rgb_as_yuv_mode(b->st.color_space) : slow_mode,
 			pass ? b->d_verdicts : nullptr, pass ? b->d_verdicts + b->n : nullptr, b->clean_word());
+		HIPCHK(hipGetLastError());
+		return 0;
+	}
+	if (dev::deliver_is_rgb10(b->dev_out_layout)) {      // the DPX0 thumbnails as three planes R, G, B of the 10-bit values (set_device_pictures checked the geometry)
+		dev::k_dec_deliver_rgb10<<<dim3(dev::dec_deliver_pieces(b->picture_rows()), (unsigned)count), dev::DEC_DELIVER_THREADS, 0, (hipStream_t)b->stream()>>>(
+			b->device_pictures() + b->picture_bytes() * (size_t)first, b->picture_bytes(), b->picture_rows(), b->picture_width(),
+			b->dev_out + b->dev_out_stride * (size_t)first, b->dev_out_stride, b->dev_out_pitch, b->dev_out_layout);
 		HIPCHK(hipGetLastError());
 		return 0;
 	}
@@ -224,12 +245,47 @@ int launch_group_pass(cfhd_amd_decode_batch *b, const uint8_t *blob)
 	return 0;
 }
 
+// The same for a batch of thumbnails: k_dec_ingest, k_dec_parse, k_dec_thumbnail -- which writes the picture or the zeros of every sample of the pass --, the delivery.
+int launch_thumbnail_pass(cfhd_amd_decode_batch *b, const uint8_t *blob)
+{
+	hipStream_t st = (hipStream_t)b->stream();
+	const size_t cap = b->thumb_cap, picture_bytes = b->picture_bytes();
+	uint32_t pieces = 0;
+	for (int i = 0; i < b->count; i++) { b->table_size()[i] = b->sizes[i]; b->table_first()[i] = pieces; pieces += dev::dec_ingest_pieces(b->sizes[i], cap); }
+	b->table_first()[b->count] = pieces;
+	HIPCHK(hipMemcpyAsync(b->d_table, b->h_table, b->table_bytes, hipMemcpyHostToDevice, st));
+	HIPCHK(hipEventRecord(b->ev[0], st));
+	dev::k_dec_ingest<<<pieces ? pieces : 1u, dev::DEC_INGEST_THREADS, 0, st>>>(blob, b->device_table(), b->count, b->d_slots, cap, b->d_sizes, b->d_verdicts + b->n);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(b->ev[1], st));
+	if (dec_parse_launch(b->parse, b->d_slots, cap, b->d_sizes, b->count, b->d_verdicts, st)) return -5;
+	HIPCHK(hipEventRecord(b->ev[2], st));
+	dev::k_dec_thumbnail<<<dim3(dev::dec_thumbnail_pieces(b->thumb_w * b->thumb_h), (unsigned)b->count), dev::DEC_THUMB_THREADS, 0, st>>>(
+		(const dev::DecLowpassJob *)b->parse.d_lowjobs, b->parse.nch, b->d_verdicts, b->d_verdicts + b->n, b->thumb_w, b->thumb_h, b->thumb_yuv422, b->d_thumbs, picture_bytes);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(b->ev[3], st));
+	b->timed = true;
+	if (b->dev_out && launch_pass_deliver(b)) return -5;
+	HIPCHK(hipMemcpyAsync(b->h_verdicts, b->d_verdicts, 8 * (size_t)b->n, hipMemcpyDeviceToHost, st));
+	if (b->host_out) {
+		// contiguous pictures in registered memory: one DMA into them; anything else through the batch's pinned memory, wait copies the rows out
+		const size_t total = picture_bytes * (size_t)b->count;
+		b->thumbs_staged = !(b->host_out_pitch == b->picture_pitch() && b->host_out_stride == picture_bytes && host_buffer_is_registered(b->host_out, total));
+		if (b->thumbs_staged && !b->h_thumbs && hipHostMalloc((void **)&b->h_thumbs, picture_bytes * (size_t)b->n, hipHostMallocPortable) != hipSuccess) {
+			(void)hipGetLastError(); b->h_thumbs = nullptr; device_set_last_error("decode queue: no pinned memory to stage the thumbnails"); return -5;
+		}
+		HIPCHK(hipMemcpyAsync(b->thumbs_staged ? b->h_thumbs : b->host_out, b->d_thumbs, total, hipMemcpyDeviceToHost, st));
+	}
+	return 0;
+}
+
 // Everything of a pass behind the samples' arrival in HBM, queued on the batch's stream: blob + table_src()[i] is sample i.  No host wait.
 int launch_pass(cfhd_amd_decode_batch *b, const uint8_t *blob)
 {
 	(void)hipSetDevice(b->device);
 	hipStream_t st = (hipStream_t)b->stream();
 	if (b->groups) return launch_group_pass(b, blob);
+	if (b->thumbs) return launch_thumbnail_pass(b, blob);
 	const size_t cap = b->dec.entropy().slot_bytes();
 	uint32_t pieces = 0;
 	for (int i = 0; i < b->count; i++) { b->table_size()[i] = b->sizes[i]; b->table_first()[i] = pieces; pieces += dev::dec_ingest_pieces(b->sizes[i], cap); }
@@ -412,6 +468,60 @@ cfhd_amd_decode_batch *cfhd_amd_decode_batch_create_groups(const void *first_gro
 	return b;
 }
 
+// Thumbnails of a batch of intra samples (include/cfhd_amd.h): the front of the decode pass -- k_dec_ingest, k_dec_parse -- and k_dec_thumbnail on the raw lowpass words;
+// every other entry point is shared.  The gates are CFHD_GetThumbnail's on the first sample, the geometry its answer.
+cfhd_amd_decode_batch *cfhd_amd_decode_batch_create_thumbnails(const void *first_sample, size_t first_size, int nsamples)
+{
+	CallerDevice caller_device;
+	if (!first_sample || first_size < 4) { refuse("decode queue: no first sample"); return nullptr; }
+	if (nsamples < 1) { refuse("decode queue: nsamples < 1"); return nullptr; }
+	if (nsamples > 65535) { refuse("decode queue: a thumbnail batch carries its pictures in a grid dimension: nsamples <= 65 535"); return nullptr; }
+	{ const char *e = getenv("CFHD_AMD_ENTROPY"); if (e && strcmp(e, "host") == 0) { refuse("decode queue: CFHD_AMD_ENTROPY=host keeps the entropy stage on the host (the C ABI's arrangement)"); return nullptr; } }
+	const uint8_t *s8 = (const uint8_t *)first_sample;
+	const int first_tag = (int16_t)((s8[0] << 8) | s8[1]), sample_type = (s8[2] << 8) | s8[3];
+	if (first_tag == TAG_SAMPLE && (sample_type == 7 || sample_type == 2 || sample_type == 1)) {
+		refuse("decode queue: thumbnails of two-frame groups (group samples, P-frame samples, sequence headers) are not built; CFHD_GetThumbnail serves intra samples"); return nullptr;
+	}
+	ParsedSample ps;
+	const int parsed = parse_sample(s8, first_size, &ps);
+	if (ps.uncompressed) { refuse("decode queue: a sample of the uncompressed mode (an UNCOMPRESS chunk) has no lowpass bands to make a thumbnail of"); return nullptr; }
+	if (parsed >= 0 && ps.encoded_format == ENC_BAYER) { refuse("decode queue: Bayer thumbnails are not built (the reference makes them by a quarter-resolution decode; CFHD_GetThumbnail answers CFHD_ERROR_BADFORMAT)"); return nullptr; }
+	const size_t w8 = parsed == 0 ? (size_t)(ps.width + 7) / 8 : 0, h8 = parsed == 0 ? (size_t)(ps.height + 7) / 8 : 0;
+	char text[200];
+	if (w8 & 1) { snprintf(text, sizeof(text), "decode queue: the thumbnail of this sample is %d pixels wide: CFHD_GetThumbnail writes even widths only", (int)w8); refuse(text); return nullptr; }
+	cfhd_amd_decode_batch *b = new (std::nothrow) cfhd_amd_decode_batch;
+	if (!b) return nullptr;
+	b->n = nsamples; b->thumbs = true;
+	auto fail = [&](const char *t) { if (t) device_set_last_error(t); delete b; return (cfhd_amd_decode_batch *)nullptr; };
+	if (CFHD_OpenDecoder(&b->slow, nullptr) != ERR_OKAY) return fail("decode queue: no decoder handle");
+	{
+		// CFHD_GetThumbnail's own verdict on the first sample (it checks the lowpass bands against the sample's size before it looks at the buffer)
+		std::vector<uint8_t> scratch(w8 * h8 * 6 <= first_size && w8 * h8 ? w8 * h8 * 4 : 16);
+		size_t rw = 0, rh = 0, rsize = 0;
+		const int rc = CFHD_GetThumbnail(b->slow, (void *)first_sample, first_size, scratch.data(), scratch.size(), 0, &rw, &rh, &rsize);
+		if (rc != ERR_OKAY || rw != w8 || rh != h8) { snprintf(text, sizeof(text), "decode queue: CFHD_GetThumbnail refuses this sample (CFHD_Error %d)", rc); return fail(text); }
+	}
+	// what k_dec_parse checks a sample against: the plan of the sample's geometry (any output of it: no picture is decoded); its lowpass bands are the thumbnail's
+	FramePlan plan;
+	if (!build_frame_plan(&plan, ps.width, ps.display_height ? ps.display_height : ps.height, PIX_RG48, ps.encoded_format)) return fail("decode queue: a geometry the device parser does not take (CFHD_GetThumbnail serves it)");
+	const bool yuv422 = ps.encoded_format == ENC_YUV422;
+	for (int c = 0; c < 3; c++) {
+		const BandDesc &ll = plan.ch[c].band[2][0];
+		if (ll.width != (int)(yuv422 && c ? w8 / 2 : w8) || ll.height != (int)h8) return fail("decode queue: a geometry the device parser does not take (CFHD_GetThumbnail serves it)");
+	}
+	b->thumb_w = (int)w8; b->thumb_h = (int)h8; b->thumb_yuv422 = yuv422;
+	// a slot holds what the handles' device stage takes of such a sample: width x height x bytes per pixel of its 16-bit picture + 64 KB
+	b->thumb_cap = ((size_t)plan.width * plan.height * (yuv422 ? 2 : (ps.encoded_format == ENC_RGB444 ? 6 : 8)) + 65536 + 255) & ~(size_t)255;
+	if (device_init()) return fail(nullptr);
+	b->device = device_current();
+	(void)hipSetDevice(b->device);
+	if (device_stream_create(&b->thumb_stream)) return fail("decode queue: no stream");
+	if (allocate(b) || dec_parse_tables_prepare(plan, nsamples, &b->parse) || hipMalloc((void **)&b->d_thumbs, b->picture_bytes() * (size_t)nsamples) != hipSuccess ||
+	    hipMemset(b->d_thumbs, 0, b->picture_bytes() * (size_t)nsamples) != hipSuccess) { (void)hipGetLastError(); return fail("decode queue: out of device or pinned memory"); }
+	b->slow_pictures.resize((size_t)nsamples);
+	return b;
+}
+
 void cfhd_amd_decode_batch_destroy(cfhd_amd_decode_batch *b)
 {
 	CallerDevice caller_device;
@@ -433,6 +543,20 @@ int cfhd_amd_decode_batch_set_device_pictures(cfhd_amd_decode_batch *b, void *d_
 	if (!b) { refuse("decode queue: no batch"); return -1; }
 	if (b->in_flight) { refuse("decode queue: device pictures are set between passes, not while one is in flight"); return -1; }
 	if (!d_pictures) { b->dev_out = nullptr; return 0; }
+	if (b->thumbs && layout != CFHD_AMD_PICTURES_PACKED) {
+		// (the RGB10_* layouts exist for the DPX0 words of a thumbnail batch alone: to every other batch they are unknown, below)
+		if (layout >= CFHD_AMD_PICTURES_PLANAR_U16 && layout <= CFHD_AMD_PICTURES_RGB_AS_YUV422_F32) {
+			refuse("decode queue: a thumbnail batch delivers its DPX0 words (CFHD_AMD_PICTURES_PACKED) or the planes R, G, B of their 10-bit values (CFHD_AMD_PICTURES_RGB10_U16 / _F16 / _F32)"); return -1;
+		}
+		if (!dev::deliver_is_rgb10(layout)) { refuse("decode queue: unknown layout of the device pictures"); return -1; }
+		if (((uintptr_t)d_pictures | picture_stride | (size_t)(unsigned)picture_pitch) & 15) { refuse("decode queue: the device pictures' pointer, stride and pitch are multiples of 16"); return -1; }
+		// three planes of H rows at the pitch, of which the last row needs its row bytes only
+		const long long plane_row = (long long)b->thumb_w * dev::deliver_rgb10_element_bytes(layout);
+		if (picture_pitch < plane_row) { refuse("decode queue: the pitch is below the plane row of the RGB10 layout (width x element size)"); return -1; }
+		if (picture_stride < (size_t)picture_pitch * (3 * (size_t)b->thumb_h - 1) + (size_t)plane_row) { refuse("decode queue: the stride is below the three planes of the RGB10 layout (3 x H rows a pitch apart)"); return -1; }
+		b->dev_out = (uint8_t *)d_pictures; b->dev_out_stride = picture_stride; b->dev_out_pitch = picture_pitch; b->dev_out_layout = layout;
+		return 0;
+	}
 	// (the BAYER_* layouts exist for the BYR4 mosaics of cfhd_amd_decode_batch_create_bayer's batches alone: to every other batch they are unknown)
 	const bool bayer = dev::deliver_is_bayer(layout) && !b->groups && b->st.out_kind == PIX_BYR4;
 	// (the YUV422_* layouts exist for packed 4:2:2 pictures: to a Bayer batch they are unknown, every other output that is not YUY2, 2vuy or YU64 is told so)
@@ -534,6 +658,7 @@ int cfhd_amd_decode_batch_submit_host(cfhd_amd_decode_batch *b, const void *base
 	if (!b || b->in_flight || !base || !offsets || !sizes || count < 1 || count > b->n || (b->groups && (count & 1))) return -1;
 	if (pictures && (picture_pitch < b->picture_pitch() || picture_stride < (size_t)picture_pitch * (size_t)(b->picture_rows() - 1) + (size_t)b->picture_pitch())) return -1;
 	(void)hipSetDevice(b->device);
+	if (!b->d_blob && hipMalloc((void **)&b->d_blob, b->blob_cap) != hipSuccess) { (void)hipGetLastError(); b->d_blob = nullptr; device_set_last_error("decode queue: no device memory to stage the samples"); return -2; }      // (a thumbnail batch's first pass from host memory)
 	begin_pass(b, offsets, sizes, count);
 	const std::vector<uint32_t> &size = b->sizes;
 	auto placed = [&](int i) { return dev::dec_ingest_pieces(size[i], b->cap_of(i)) != 0; };      // sample i is one k_dec_ingest copies
@@ -582,11 +707,83 @@ int cfhd_amd_decode_batch_submit_device(cfhd_amd_decode_batch *b, const void *d_
 	return 0;
 }
 
+// wait of a thumbnail batch.  Final on the spot: a sample k_dec_ingest placed whose verdict has low byte 0 -- CFHD_ERROR_OKAY, its picture k_dec_thumbnail's (the scan
+// flag and the colour-space tag play no part in a thumbnail).  Every other sample gets its status from CFHD_GetThumbnail on its bytes -- BADSAMPLE where that thumbnail
+// has another geometry than the batch's --, and the host's picture, where there is one, takes its place in the batch's buffer, in the host pictures and, by one more
+// launch of the deliver kernel per run of such neighbours, in the caller's device memory; its place stays zeros otherwise (k_dec_thumbnail wrote them, the pass
+// delivered them).
+static int wait_thumbnails(cfhd_amd_decode_batch *b, CFHD_Error *status)
+{
+	const int n = b->n, count = b->count;
+	auto device_failure = [&](int code) { if (status) for (int i = 0; i < count; i++) status[i] = ERR_INTERNAL; end_pass(b); return code; };
+	if (b->wait_stream()) return device_failure(-2);
+	if (b->timed) {
+		b->timed = false;
+		float *ms[3] = { &b->ingest_ms, &b->parse_ms, &b->thumb_ms };
+		for (int k = 0; k < 3; k++) if (hipEventElapsedTime(ms[k], b->ev[k], b->ev[k + 1]) != hipSuccess) { (void)hipGetLastError(); *ms[k] = 0; }
+		b->deliver_ms = 0;
+		if (b->deliver_timed && hipEventElapsedTime(&b->deliver_ms, b->ev[4], b->ev[5]) != hipSuccess) { (void)hipGetLastError(); b->deliver_ms = 0; }
+		b->deliver_timed = false;
+	}
+	const int pitch = b->picture_pitch(), rows = b->picture_rows(); const size_t picture_bytes = b->picture_bytes();
+	auto to_host = [&](int i, const uint8_t *picture) {
+		for (int r = 0; r < rows; r++) memcpy(b->host_out + b->host_out_stride * (size_t)i + (size_t)r * b->host_out_pitch, picture + (size_t)r * pitch, (size_t)pitch);
+	};
+	if (b->host_out && b->thumbs_staged) parallel_for(count, count > 8 ? 8 : 1, [&](int i) { to_host(i, b->h_thumbs + picture_bytes * (size_t)i); });
+	std::vector<uint8_t> bytes, scratch;
+	std::vector<int> slow;                                 // the samples whose picture the host made, for the deliver kernel behind the loop
+	int decoded = 0, failure = 0;
+	for (int i = count; i < n; i++) b->slow_pictures[i].clear();
+	for (int i = 0; i < count; i++) {
+		b->slow_pictures[i].clear();
+		int rc = ERR_OKAY;
+		if (b->h_verdicts[n + i] || (b->h_verdicts[i] & 0xffu)) {
+			const size_t size = b->full_sizes[i];
+			const uint8_t *s = b->src_host ? b->src_host + b->offsets[i] : nullptr;
+			if (!s) {
+				bytes.resize(size ? size : 1);
+				if (size && hipMemcpy(bytes.data(), b->src_device + b->offsets[i], size, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); failure = -2; }
+				s = bytes.data();
+			}
+			// (the buffer CFHD_GetThumbnail is handed holds the thumbnail of the sample's own geometry, where its lowpass bands can lie inside the sample at all: the
+			// function checks them against the size before it looks at the buffer)
+			size_t need = picture_bytes, rw = 0, rh = 0, rsize = 0;
+			ParsedSample own;
+			if (parse_sample(s, size, &own) == 0) { const size_t w8 = (size_t)(own.width + 7) / 8, h8 = (size_t)(own.height + 7) / 8; if (w8 * h8 * 6 <= size && w8 * h8 * 4 > need) need = w8 * h8 * 4; }
+			scratch.assign(need, 0);
+			rc = failure ? ERR_INTERNAL : CFHD_GetThumbnail(b->slow, (void *)s, size, scratch.data(), need, 0, &rw, &rh, &rsize);
+			if (rc == ERR_OKAY && (rw != (size_t)b->thumb_w || rh != (size_t)b->thumb_h)) rc = ERR_BADSAMPLE;
+			b->slow_pictures[i].assign(picture_bytes, 0);
+			if (rc == ERR_OKAY) memcpy(b->slow_pictures[i].data(), scratch.data(), picture_bytes);
+			if (b->host_out) to_host(i, b->slow_pictures[i].data());
+			(void)hipSetDevice(b->device);
+			// (a synchronous copy on the null stream; the batch's stream is idle here, and the launch below is queued behind the copy's return)
+			if (rc == ERR_OKAY) {
+				if (hipMemcpy(b->d_thumbs + picture_bytes * (size_t)i, b->slow_pictures[i].data(), picture_bytes, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); failure = -2; }
+				if (b->dev_out) slow.push_back(i);
+			}
+		}
+		if (status) status[i] = rc;
+		decoded += rc == ERR_OKAY;
+	}
+	for (size_t k = 0; k < slow.size() && !failure;) {
+		size_t e = k + 1;
+		while (e < slow.size() && slow[e] == slow[e - 1] + 1) e++;
+		if (launch_deliver(b, slow[k], (int)(e - k))) failure = -2;
+		k = e;
+	}
+	if (!slow.empty() && !failure && b->wait_stream()) failure = -2;
+	b->steps++;
+	end_pass(b);
+	return failure ? failure : decoded;
+}
+
 int cfhd_amd_decode_batch_wait(cfhd_amd_decode_batch *b, CFHD_Error *status)
 {
 	CallerDevice caller_device;
 	if (!b || !b->in_flight) return -1;
 	(void)hipSetDevice(b->device);
+	if (b->thumbs) return wait_thumbnails(b, status);
 	const int n = b->n, count = b->count;
 	auto device_failure = [&](int code) { if (status) for (int i = 0; i < count; i++) status[i] = ERR_INTERNAL; end_pass(b); return code; };
 	if (b->wait_stream()) return device_failure(-2);
@@ -682,6 +879,11 @@ int cfhd_amd_decode_batch_download_output(cfhd_amd_decode_batch *b, int i, void 
 		for (int r = 0; r < rows; r++) memcpy((uint8_t *)out + (size_t)r * pitch, b->slow_pictures[i].data() + (size_t)r * row_bytes, (size_t)row_bytes);
 		return 0;
 	}
+	if (b->thumbs) {                                       // the DPX0 words out of the batch's own buffer
+		(void)hipSetDevice(b->device);
+		if (hipMemcpy2DAsync(out, (size_t)pitch, b->d_thumbs + b->picture_bytes() * (size_t)i, (size_t)row_bytes, (size_t)row_bytes, (size_t)rows, hipMemcpyDeviceToHost, (hipStream_t)b->stream()) != hipSuccess) { (void)hipGetLastError(); return -2; }
+		return b->wait_stream();
+	}
 	if (b->download_frame(i, out, pitch) || b->wait_stream()) return -2;
 	return b->finish_frame(i, out, pitch);
 }
@@ -692,6 +894,8 @@ int cfhd_amd_decode_batch_download_output(cfhd_amd_decode_batch *b, int i, void 
 float cfhd_amd_decode_batch_kernel_ms(cfhd_amd_decode_batch *b, int which)
 {
 	if (b && !b->in_flight && which == 9) return b->deliver_ms;
+	// a batch of thumbnails: 0 k_dec_ingest, 1 k_dec_parse, 6 k_dec_thumbnail (the place of the last level), nothing else
+	if (b && !b->in_flight && b->thumbs) return which == 0 ? b->ingest_ms : (which == 1 ? b->parse_ms : (which == 6 ? b->thumb_ms : 0));
 	if (!b || b->in_flight || which < 0 || which > (b->groups ? 8 : 7)) return 0;
 	if (which == 0) return b->ingest_ms;
 	if (which == 7) return b->blank_ms;
@@ -704,6 +908,7 @@ float cfhd_amd_decode_batch_kernel_ms(cfhd_amd_decode_batch *b, int which)
 
 const char *cfhd_amd_decode_batch_kernel_name(cfhd_amd_decode_batch *b, int which)
 {
+	if (b && !b->in_flight && b->thumbs) return which == 0 ? "k_dec_ingest" : (which == 1 ? "k_dec_parse" : (which == 6 ? "k_dec_thumbnail" : (which == 9 && b->dev_out ? (dev::deliver_is_rgb10(b->dev_out_layout) ? "k_dec_deliver_rgb10" : "k_dec_deliver") : "")));
 	if (b && !b->in_flight && which == 9) return b->dev_out && dev::deliver_is_bayer(b->dev_out_layout) ? "k_dec_deliver_bayer" : (b->dev_out && dev::deliver_is_yuv422(b->dev_out_layout) ? "k_dec_deliver_yuv422" : (b->dev_out && dev::deliver_is_rgba(b->dev_out_layout) ? "k_dec_deliver_rgba" : (b->dev_out && dev::deliver_is_rgb_as_yuv(b->dev_out_layout) ? "k_dec_deliver_rgb_as_yuv" : "k_dec_deliver")));
 	if (!b || b->in_flight || which < 0 || which > 7) return "";
 	static const char *const fixed[4] = { "k_dec_ingest", "k_dec_parse", "k_dec_plan+k_dec_index+k_dec_chain+k_dec_tiles", "k_dec_lowpass" };

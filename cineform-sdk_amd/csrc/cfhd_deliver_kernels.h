@@ -5,7 +5,7 @@
 // which takes it for the packed 4:2:2 pictures (YUY2, 2vuy, YU64) delivered as a luma plane and two chroma planes of half the width (I422: N x [H x W | 2 x H x W/2]), and
 // k_dec_deliver_rgba, which takes it for the four-component pictures (b64a, BGRA, BGRa) delivered as four planes R, G, B, A, top row first (N x 4 x H x W), and
 // k_dec_deliver_rgb_as_yuv, which takes it for the RG48 pictures of RGB samples delivered as the YU64 picture the reference decodes such a sample to, packed or as
-// Y, Cb, Cr planes.
+// Y, Cb, Cr planes, and k_dec_deliver_rgb10, which takes it for the DPX0 longwords of a thumbnail batch delivered as three planes R, G, B of their 10-bit values.
 #pragma once
 #include <stdint.h>
 #include <stddef.h>
@@ -588,6 +588,76 @@ __global__ void __launch_bounds__(DEC_DELIVER_THREADS) k_dec_deliver_rgb_as_yuv(
 		else if (layout == DELIVER_RGB_AS_YUV422_U16) deliver_rgb_as_yuv_row<DELIVER_RGB_AS_YUV422_U16>(m, zero, row, width, aligned, y, cb, cr, lane);
 		else if (layout == DELIVER_RGB_AS_YUV422_F16) deliver_rgb_as_yuv_row<DELIVER_RGB_AS_YUV422_F16>(m, zero, row, width, aligned, y, cb, cr, lane);
 		else deliver_rgb_as_yuv_row<DELIVER_RGB_AS_YUV422_F32>(m, zero, row, width, aligned, y, cb, cr, lane);
+	}
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_dec_deliver_rgb10: picture i of the pass -- `rows` rows of `width` DPX0 longwords (big-endian, r << 22 | g << 12 | b << 2: the thumbnails of
+// cfhd_amd_decode_batch_create_thumbnails) back to back at src + i * src_stride -- into dst + i * dst_stride as three planes R, G, B of `rows` rows of `width` elements,
+// rows dst_pitch apart, planes rows x dst_pitch apart (a torch tensor N x 3 x H x W).  Every plane row gets its bytes and nothing else.  `layout`: DELIVER_RGB10_U16 (the
+// 10-bit value as it is, 0 .. 1023), _F32 (deliver_unit_f32_of<1023>), _F16 (deliver_f16_bits of that): the rules of the other plane layouts with the unit of the
+// picture's own word.
+//   A wave owns a row at a time.  Where the row starts on a 16-byte boundary (always when 4 x width and src_stride are multiples of 16; every second row, or none, of
+//   the others: decided per row, wave-uniform) a lane takes 8 pixels: two 16-byte loads -- a wave reads 2 KB of the row without a gap --, the bytes swapped and the
+//   three fields separated in registers, one 16-byte store per plane for u16 / f16, two for f32.  The pixels behind the last whole group of eight, and every pixel of
+//   a row that starts elsewhere (on a longword boundary: src, src_stride and 4 x width are multiples of 4), go element by element: a 4-byte load, three 2- or 4-byte
+//   stores.  Nothing ties the kernel to thumbnails: width, rows and the source stride are arguments.
+// No LDS, no scratch.  Grid (row pieces: dec_deliver_pieces(rows), pictures), DEC_DELIVER_WAVES rows per piece and step.
+// ---------------------------------------------------------------------------------------------
+enum { DELIVER_RGB10_U16 = 19, DELIVER_RGB10_F16 = 20, DELIVER_RGB10_F32 = 21 };      // (CFHD_AMD_PICTURES_RGB10_*)
+inline bool deliver_is_rgb10(int layout) { return layout >= DELIVER_RGB10_U16 && layout <= DELIVER_RGB10_F32; }
+inline int deliver_rgb10_element_bytes(int layout) { return layout == DELIVER_RGB10_F32 ? 4 : 2; }
+// the DPX0 longword as it was loaded, in the machine's order
+__device__ __forceinline__ uint32_t deliver_rgb10_word(uint32_t l) { return byte_perm(0u, l, 0x00010203u); }
+// eight 10-bit values of one plane (at: a multiple of 16)
+template <int LAYOUT> __device__ __forceinline__ void deliver_rgb10_store(uint8_t *at, const uint32_t *v)
+{
+	if constexpr (LAYOUT == DELIVER_RGB10_U16) store_u32x4_global(at, v[0] | (v[1] << 16), v[2] | (v[3] << 16), v[4] | (v[5] << 16), v[6] | (v[7] << 16));
+	else {
+		float f[8];
+		for (int k = 0; k < 8; k++) f[k] = deliver_unit_f32_of<1023>(v[k]);
+		deliver_store_floats<LAYOUT == DELIVER_RGB10_F32 ? DELIVER_YUV422_F32 : DELIVER_YUV422_F16, 8>(at, f);
+	}
+}
+template <int LAYOUT> __device__ __forceinline__ void deliver_rgb10_element(uint8_t *plane_row, int x, uint32_t v)
+{
+	if constexpr (LAYOUT == DELIVER_RGB10_U16) ((uint16_t *)plane_row)[x] = (uint16_t)v;
+	else if constexpr (LAYOUT == DELIVER_RGB10_F16) ((uint16_t *)plane_row)[x] = (uint16_t)deliver_f16_bits(deliver_unit_f32_of<1023>(v));
+	else ((float *)plane_row)[x] = deliver_unit_f32_of<1023>(v);
+}
+template <int LAYOUT> __device__ __forceinline__ void deliver_rgb10_row(const uint8_t *row, int width, uint8_t *orow, size_t plane, int lane)
+{
+	constexpr int E = LAYOUT == DELIVER_RGB10_F32 ? 4 : 2;
+	const int groups = ((uintptr_t)row & 15) ? 0 : width >> 3;
+	for (int g = lane; g < groups; g += 64) {
+		const cfhd_u4 a = CFHD_LDG128(row + 32 * (size_t)g), b = CFHD_LDG128(row + 32 * (size_t)g + 16);
+		const uint32_t w[8] = { deliver_rgb10_word(a.x), deliver_rgb10_word(a.y), deliver_rgb10_word(a.z), deliver_rgb10_word(a.w),
+		                        deliver_rgb10_word(b.x), deliver_rgb10_word(b.y), deliver_rgb10_word(b.z), deliver_rgb10_word(b.w) };
+		uint32_t r[8], gr[8], bl[8];
+		for (int k = 0; k < 8; k++) { r[k] = w[k] >> 22; gr[k] = (w[k] >> 12) & 0x3ffu; bl[k] = (w[k] >> 2) & 0x3ffu; }
+		uint8_t *at = orow + (size_t)g * 8 * E;
+		deliver_rgb10_store<LAYOUT>(at, r); deliver_rgb10_store<LAYOUT>(at + plane, gr); deliver_rgb10_store<LAYOUT>(at + 2 * plane, bl);
+	}
+	for (int x = 8 * groups + lane; x < width; x += 64) {
+		const uint32_t w = deliver_rgb10_word(CFHD_LDG32(row + 4 * (size_t)x));
+		deliver_rgb10_element<LAYOUT>(orow, x, w >> 22);
+		deliver_rgb10_element<LAYOUT>(orow + plane, x, (w >> 12) & 0x3ffu);
+		deliver_rgb10_element<LAYOUT>(orow + 2 * plane, x, (w >> 2) & 0x3ffu);
+	}
+}
+
+__global__ void __launch_bounds__(DEC_DELIVER_THREADS) k_dec_deliver_rgb10(const uint8_t *src, size_t src_stride, int rows, int width, uint8_t *dst, size_t dst_stride, int dst_pitch, int layout)
+{
+	const int lane = (int)(threadIdx.x & 63u), wave = wave_uniform((int)(threadIdx.x >> 6));
+	const uint8_t *pic = src + src_stride * (size_t)blockIdx.y;
+	uint8_t *out = dst + dst_stride * (size_t)blockIdx.y;
+	const size_t plane = (size_t)dst_pitch * (size_t)rows;
+	for (int r = (int)blockIdx.x * DEC_DELIVER_WAVES + wave; r < rows; r += (int)gridDim.x * DEC_DELIVER_WAVES) {
+		const uint8_t *row = pic + (size_t)r * 4 * (size_t)width;
+		uint8_t *orow = out + (size_t)r * dst_pitch;
+		if (layout == DELIVER_RGB10_U16) deliver_rgb10_row<DELIVER_RGB10_U16>(row, width, orow, plane, lane);
+		else if (layout == DELIVER_RGB10_F16) deliver_rgb10_row<DELIVER_RGB10_F16>(row, width, orow, plane, lane);
+		else deliver_rgb10_row<DELIVER_RGB10_F32>(row, width, orow, plane, lane);
 	}
 }
 

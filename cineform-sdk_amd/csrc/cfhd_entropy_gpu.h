@@ -255,4 +255,17 @@ private:
 	void *ev_[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; bool timed_ = false;      // [0] parser begins, [1] parser ends, [2] band decoder begins, [3] ends, [4] lowpass ends, [5] in front of k_dec_band_two_pass (which ends at [3])
 };
 
+// k_dec_parse by itself, for a caller that wants the parser's verdicts and its DecLowpassJobs and follows none of the band pointers (the thumbnail batches of the
+// decode queue, cfhd_decode_queue.hip): the plan and job tables the kernel writes into, for n samples of `plan`'s geometry, with no coefficient pyramid, no chunk
+// index and no decoder tables behind them.  The kernel runs as it stands: it fills band jobs nobody reads and computes destination pointers from a null base.
+// Interlaced and progressive samples both pass (the table of difference jobs is always there).
+struct DecParseTables {
+	void *d_plan = nullptr, *d_bandjobs = nullptr, *d_lowjobs = nullptr /* dev::DecLowpassJob [n * nch]: sample f, channel c at f * nch + c */, *d_diffjobs = nullptr;
+	int *d_errors = nullptr; int n = 0, nch = 0;
+};
+int dec_parse_tables_prepare(const FramePlan &plan, int n, DecParseTables *t);      // on the current device; 0, or a hipError_t
+void dec_parse_tables_release(DecParseTables *t);
+// queued on `stream`: samples 0 .. count-1 (count <= n) in slots slot_stride apart (both multiples of 256), sizes and verdicts [count] in device memory
+int dec_parse_launch(const DecParseTables &t, const uint8_t *d_slots, size_t slot_stride, const uint32_t *d_sizes, int count, uint32_t *d_verdicts, void *stream);
+
 } // namespace cfhd

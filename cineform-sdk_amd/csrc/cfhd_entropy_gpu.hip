@@ -935,4 +935,40 @@ float GpuGroupBatchEntropyDecoder::kernel_ms(int k)
 	return ms;
 }
 
+// ---- k_dec_parse by itself (cfhd_entropy_gpu.h DecParseTables)
+int dec_parse_tables_prepare(const FramePlan &plan, int n, DecParseTables *t)
+{
+	dec_parse_tables_release(t);
+	if (n < 1) return -1;
+	dev::DecPlan dp;
+	dec_build_plan(plan, plan.pixel_kind, &dp);
+	t->n = n; t->nch = plan.num_channels;
+	const size_t lows = (size_t)n * plan.num_channels;
+	HIPCHK(hipMalloc(&t->d_plan, sizeof(dp)));
+	HIPCHK(hipMemcpy(t->d_plan, &dp, sizeof(dp), hipMemcpyHostToDevice));
+	HIPCHK(hipMalloc(&t->d_bandjobs, lows * 9 * sizeof(dev::DecBandJob)));
+	HIPCHK(hipMalloc(&t->d_lowjobs, lows * sizeof(dev::DecLowpassJob)));
+	HIPCHK(hipMalloc(&t->d_diffjobs, lows * sizeof(dev::DecDiffJob)));
+	HIPCHK(hipMalloc((void **)&t->d_errors, sizeof(int)));
+	HIPCHK(hipMemset(t->d_lowjobs, 0, lows * sizeof(dev::DecLowpassJob)));
+	HIPCHK(hipMemset(t->d_errors, 0, sizeof(int)));
+	return 0;
+}
+
+void dec_parse_tables_release(DecParseTables *t)
+{
+	void *dv[] = { t->d_plan, t->d_bandjobs, t->d_lowjobs, t->d_diffjobs, t->d_errors };
+	for (void *p : dv) if (p) (void)hipFree(p);
+	*t = DecParseTables();
+}
+
+int dec_parse_launch(const DecParseTables &t, const uint8_t *d_slots, size_t slot_stride, const uint32_t *d_sizes, int count, uint32_t *d_verdicts, void *stream)
+{
+	if (!t.d_plan || !d_slots || !d_sizes || !d_verdicts || count < 1 || count > t.n || ((uintptr_t)d_slots & 255) || (slot_stride & 255)) return -1;
+	dev::k_dec_parse<<<count, dev::DEC_PARSE_THREADS, 0, (hipStream_t)stream>>>(d_slots, slot_stride, d_sizes, count, (const dev::DecPlan *)t.d_plan, nullptr, 0,
+		(dev::DecBandJob *)t.d_bandjobs, (dev::DecLowpassJob *)t.d_lowjobs, t.d_errors, (dev::DecDiffJob *)t.d_diffjobs, nullptr, d_verdicts);
+	HIPCHK(hipGetLastError());
+	return 0;
+}
+
 } // namespace cfhd

@@ -16,6 +16,7 @@
 #pragma once
 #include <stdint.h>
 #include <cfhd_gfx950.h>
+#include "cfhd_lowpass_job.h"
 
 // Timing probes of round 3 (kernels that stop early or skip their stores: they write INVALID samples) exist only in builds made with -DCFHD_AMD_PROBES
 // (tools/gpu_probe.sh); the shipped library compiles them out.
@@ -1078,7 +1079,7 @@ struct DecBandJob {
 // The difference-coded band of one channel of an interlaced frame, after its code words were decoded: peak values (if any) and running sums.
 struct DecDiffJob { int16_t *band; int width, height, pitch; const uint8_t *peaks; uint32_t peak_bytes; int level; };
 
-struct DecLowpassJob { const uint8_t *src; int16_t *dst; int width, height, pitch, bias; };
+// (struct DecLowpassJob: cfhd_lowpass_job.h, shared with k_dec_thumbnail)
 
 __global__ void __launch_bounds__(DEC_THREADS) k_dec_bands(const DecBandJob *jobs, int njobs, const DecTables *T, int *errors)
 {

@@ -372,6 +372,28 @@ cfhd_amd_decode_batch *cfhd_amd_decode_batch_create_groups(const void *first_gro
  * NULL, with the reason in cfhd_amd_last_error(): a first sample that is not a Bayer intra sample; an output other than BYR4; half or quarter resolution;
  * CFHD_AMD_ENTROPY=host; nsamples < 1 or 4 x nsamples > 65 535; whatever CFHD_PrepareToDecode or CFHD_DecodeSample refuses for that sample. */
 cfhd_amd_decode_batch *cfhd_amd_decode_batch_create_bayer(const void *first_sample, size_t first_size, uint32_t output_format, int decoded_resolution, int nsamples);
+/* Thumbnails of a batch of samples: the 1/8 x 1/8 picture CFHD_GetThumbnail makes of each, straight from the raw level-3 lowpass words of the sample -- no entropy
+ * decoder and no inverse transform run.  Prepares from one complete intra sample of encoded format 4:2:2, RGB 4:4:4 or RGBA 4:4:4:4, progressive or interlaced (a
+ * batch serves both scans).  The output is fixed to what CFHD_GetThumbnail writes: W8 x H8 pixels, one big-endian longword a pixel, r << 22 | g << 12 | b << 2 ("DPX0"),
+ * W8 = (width + 7) / 8 and H8 = (height + 7) / 8 of the first sample's header.  Every other entry point is shared and keeps its meaning:
+ * cfhd_amd_decode_batch_geometry answers W8, H8 and row_bytes = 4 x W8; submit_host, submit_device, wait, download_output, set_device_pictures and destroy work as for
+ * any batch, one pass per batch at a time, several batches in flight.  A pass is k_dec_ingest, k_dec_parse and k_dec_thumbnail on the batch's one stream, then the
+ * delivery; no host wait inside.  Every picture equals CFHD_GetThumbnail's byte for byte.
+ * Device memory: the sample slots (width x height x bytes per pixel of the sample's 16-bit picture + 64 KB each: about 4 MB for 1080p 4:2:2), the parser's tables,
+ * the verdicts and the small pictures (4 x W8 x H8 bytes each); as much as the slots again once submit_host has been used (the samples' way in).  No coefficient
+ * pyramid, no full-size picture and no chunk index: a decode batch of the same samples holds about 30 MB a sample.
+ * status[i] of wait is what CFHD_GetThumbnail returns for sample i on any decoder handle, with one addition: a sample whose thumbnail would not have the batch's
+ * W8 x H8 gets CFHD_ERROR_BADSAMPLE.  The picture of a sample whose status is not CFHD_ERROR_OKAY is zeros -- in the batch's buffer, in host delivery and in the caller's
+ * device memory.  Samples the device stage places and whose tag stream the device parser passes are final on the GPU, whatever their scan flag and colour-space tag
+ * (a thumbnail depends on neither); the others -- longer than a slot, a size that is no multiple of 4, anything the parser does not pass, such as an RGB 4:4:4 sample
+ * of the same geometry in a 4:2:2 batch -- get status and picture from CFHD_GetThumbnail on their bytes inside wait.
+ * cfhd_amd_decode_batch_set_device_pictures takes CFHD_AMD_PICTURES_PACKED -- the DPX0 words as they are -- and CFHD_AMD_PICTURES_RGB10_U16 / _F16 / _F32 (below); every
+ * other layout is refused.  cfhd_amd_decode_batch_kernel_ms / _kernel_name: 0 k_dec_ingest, 1 k_dec_parse, 6 k_dec_thumbnail (the place of the last level), 9 the
+ * deliver kernel while a layout is set; 0 / "" for every other index.
+ * NULL, with the reason in cfhd_amd_last_error(): no first sample; nsamples < 1 or > 65 535 (the pictures are a grid dimension); group samples, P-frame samples and
+ * sequence headers; Bayer samples (the reference makes their thumbnail by a quarter-resolution decode; CFHD_GetThumbnail answers CFHD_ERROR_BADFORMAT); a sample with
+ * an UNCOMPRESS chunk; a first sample CFHD_GetThumbnail refuses; an odd W8 (CFHD_GetThumbnail writes even widths only); CFHD_AMD_ENTROPY=host. */
+cfhd_amd_decode_batch *cfhd_amd_decode_batch_create_thumbnails(const void *first_sample, size_t first_size, int nsamples);
 /* Waits for a pass in flight, then frees the batch. */
 void cfhd_amd_decode_batch_destroy(cfhd_amd_decode_batch *batch);
 /* One decoded picture: width x height pixels in rows of row_bytes bytes (any of the three may be NULL).  0, or -1. */
@@ -454,18 +476,25 @@ int  cfhd_amd_decode_batch_submit_device(cfhd_amd_decode_batch *batch, const voi
  * H rows of W / 2 elements at half the pitch; the pitch a multiple of 32, the stride rule that of the YUV422 layouts), _F32 (float)w * (1.0f / 65535.0f), _F16 that
  * value rounded to nearest-even to binary16.  Written by k_dec_deliver_rgb_as_yuv in place of k_dec_deliver (kernel_name(batch, 9) answers it while such a layout is
  * set; kernel_ms index 9 times it).  Host delivery and cfhd_amd_decode_batch_download_output give the RG48 picture beside it, unchanged.
+ * CFHD_AMD_PICTURES_RGB10_U16 / _F16 / _F32: a batch made by cfhd_amd_decode_batch_create_thumbnails only (to every other batch the values are unknown layouts; on such
+ * a batch every layout but these and PACKED is refused).  The picture of W8 x H8 DPX0 words is three planes, R, then G, then B, each H8 rows of W8 elements, rows
+ * picture_pitch bytes apart, planes H8 * picture_pitch apart: a contiguous tensor (n, 3, H8, W8) is picture_pitch = W8 * element size, picture_stride = 3 * H8 *
+ * picture_pitch.  _U16: the 10-bit value as it is, 0 .. 1023; _F32: (float)v * (1.0f / 1023.0f), one IEEE single multiply; _F16: that value rounded to nearest-even to
+ * binary16.  The pitch is >= W8 * element size; the stride is >= (3 H8 - 1) * picture_pitch + W8 * element size.  Written by k_dec_deliver_rgb10 in place of
+ * k_dec_deliver (kernel_name(batch, 9) answers it while such a layout is set; kernel_ms index 9 times it).
  * Exactly count pictures are written, of every row its row bytes and nothing else: pitch padding, the space between planes and pictures and the pictures behind a short
  * pass are not touched.
  * 0; -1 with the reason in cfhd_amd_last_error(): a pass in flight, an unknown layout, a planar layout on a batch whose output is not RG48, a pointer, stride or pitch
  * that is no multiple of 16, a pitch below the row bytes of the layout, a stride below what one picture occupies; a 4:2:2 plane layout on a batch whose output is not
  * YUY2, 2vuy or YU64, _U8 on a YU64 batch, _U16 on an 8-bit one, a pitch of such a layout that is no multiple of 32; RGBA_U8 on a b64a batch, RGBA_U16 on a BGRA or
  * BGRa one; an RGB_AS_* layout on an RG48 batch it does not serve, on an odd width, with a pitch below its row (or, the plane forms, no multiple of 32), with a
- * stride below its rows or planes. */
+ * stride below its rows or planes; on a thumbnail batch any layout but PACKED and RGB10_*, an RGB10 pitch below its plane row, a stride below its three planes. */
 enum { CFHD_AMD_PICTURES_PACKED = 0, CFHD_AMD_PICTURES_PLANAR_U16 = 1, CFHD_AMD_PICTURES_PLANAR_F16 = 2, CFHD_AMD_PICTURES_PLANAR_F32 = 3 };
 enum { CFHD_AMD_PICTURES_BAYER_U16 = 4, CFHD_AMD_PICTURES_BAYER_F16 = 5, CFHD_AMD_PICTURES_BAYER_F32 = 6 };
 enum { CFHD_AMD_PICTURES_YUV422_U8 = 7, CFHD_AMD_PICTURES_YUV422_U16 = 8, CFHD_AMD_PICTURES_YUV422_F16 = 9, CFHD_AMD_PICTURES_YUV422_F32 = 10 };
 enum { CFHD_AMD_PICTURES_RGBA_U8 = 11, CFHD_AMD_PICTURES_RGBA_U16 = 12, CFHD_AMD_PICTURES_RGBA_F16 = 13, CFHD_AMD_PICTURES_RGBA_F32 = 14 };
 enum { CFHD_AMD_PICTURES_RGB_AS_YU64 = 15, CFHD_AMD_PICTURES_RGB_AS_YUV422_U16 = 16, CFHD_AMD_PICTURES_RGB_AS_YUV422_F16 = 17, CFHD_AMD_PICTURES_RGB_AS_YUV422_F32 = 18 };
+enum { CFHD_AMD_PICTURES_RGB10_U16 = 19, CFHD_AMD_PICTURES_RGB10_F16 = 20, CFHD_AMD_PICTURES_RGB10_F32 = 21 };
 int  cfhd_amd_decode_batch_set_device_pictures(cfhd_amd_decode_batch *batch, void *d_pictures, size_t picture_stride, int picture_pitch, int layout);
 /* Collects the pass: the number of samples that decoded, or < 0 (-1: nothing in flight, -2: device failure).  status (NULL or count entries): status[i] is the CFHD_Error
  * CFHD_DecodeSample returns for sample i on a handle prepared on the first sample; the picture of a sample that failed is zero.  Samples the device parser refuses are
@@ -478,7 +507,7 @@ int  cfhd_amd_decode_batch_wait(cfhd_amd_decode_batch *batch, CFHD_Error *status
 int  cfhd_amd_decode_batch_download_output(cfhd_amd_decode_batch *batch, int i, void *out, int pitch);
 /* HIP-event time (ms) of the kernels of the last pass and their names as a profiler shows them.  which: 0 k_dec_ingest, 1 k_dec_parse, 2 the band decoder (all its
  * kernels), 3 k_dec_lowpass, 4 / 5 / 6 the transform levels in launch order (the last one with the output conversion), 7 k_dec_blank, 9 k_dec_deliver (both kinds of
- * batch; k_dec_deliver_bayer while a BAYER_* layout is set, k_dec_deliver_yuv422 while a YUV422_* one is, k_dec_deliver_rgba while an RGBA_* one is, k_dec_deliver_rgb_as_yuv while an RGB_AS_* one is; 0 ms when the last pass delivered nothing into device memory).  0 / "" otherwise. */
+ * batch; k_dec_deliver_bayer while a BAYER_* layout is set, k_dec_deliver_yuv422 while a YUV422_* one is, k_dec_deliver_rgba while an RGBA_* one is, k_dec_deliver_rgb_as_yuv while an RGB_AS_* one is; a thumbnail batch: see cfhd_amd_decode_batch_create_thumbnails; 0 ms when the last pass delivered nothing into device memory).  0 / "" otherwise. */
 float cfhd_amd_decode_batch_kernel_ms(cfhd_amd_decode_batch *batch, int which);
 const char *cfhd_amd_decode_batch_kernel_name(cfhd_amd_decode_batch *batch, int which);
 int  cfhd_amd_device_count(void);
