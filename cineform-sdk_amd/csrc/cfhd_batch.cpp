@@ -53,6 +53,7 @@ struct cfhd_amd_batch {
 	// (the decoder's stream waits for the encoder's events), wait fetches the sizes, queues the copy of the samples and waits for both streams.  The other arrangements
 	// (host hand-off, host entropy, several chunks) have host work in the middle of a pass: those run the blocking pass on a thread of their own.
 	std::thread worker; bool in_flight = false, queued = false; long long pending = -1;
+	bool counted = false;              // the pass in flight is one of its device's passes in flight (cfhd_device.h device_pass_begin; pass_counted below)
 	// cfhd_amd_batch_submit_host: the pass in flight takes its frames from / leaves its pictures in the caller's memory
 	const uint8_t *host_in = nullptr; size_t host_in_stride = 0; int host_in_pitch = 0;
 	uint8_t *host_out = nullptr; size_t host_out_stride = 0; int host_out_pitch = 0;
@@ -99,6 +100,27 @@ template <typename F> void parallel_for(int n, int nthreads, F f)
 	for (auto &th : pool) th.join();
 }
 double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// The frame queue's pass joins (submit, in front of its first launch) / leaves (wait, or a submit that fails) the passes in flight on its device: launches of this and
+// of other queues size their persistent kernels by that count (GpuEntropyDecoder::launch_dx).  The batch's own decoders are told that their pass is in it.
+// (The device is the encoder's: a batch prepares its encoder and its decoder on one device, the one launch_dx reads the count of.  Group batches count too,
+// though their own band decoder has no persistent kernels: they are passes that want room beside an intra batch's.)
+void pass_counted(cfhd_amd_batch *b, bool on)
+{
+	if (b->counted == on) return;
+	const int device = b->gop ? b->genc->device() : b->chunks[0]->enc.device();
+	if (on) device_pass_begin(device); else device_pass_end(device);
+	for (auto &c : b->chunks) c->dec.entropy().set_pass_counted(on);
+	b->counted = on;
+}
+// a submit: counted from here on; every return that does not keep() the pass -- a launch that failed -- takes it out of the count again
+struct CountedSubmit {
+	cfhd_amd_batch *b; bool kept = false;
+	explicit CountedSubmit(cfhd_amd_batch *batch) : b(batch) { pass_counted(b, true); }
+	~CountedSubmit() { if (!kept) pass_counted(b, false); }
+	int keep(bool queued) { kept = true; b->in_flight = true; b->queued = queued; return 0; }
+	CountedSubmit(const CountedSubmit &) = delete;
+};
 
 // ---- streams with rate feedback (cfhd_amd_batch_create_stream, tables that move)
 bool same_tables(const FramePlan &a, const FramePlan &b)      // (tables, not states: two states can give the same divisors)
@@ -891,6 +913,7 @@ int cfhd_amd_batch_submit(cfhd_amd_batch *b)
 	CallerDevice caller_device;
 	if (!b || b->in_flight) return -1;
 	b->pending = -1;
+	CountedSubmit pass(b);
 	// CFHD_AMD_QUEUE=thread: (A/B) the blocking pass on a thread of its own for the default arrangement too, as in round 4.  (Also measured: the launches of a queued
 	// pass -- 2-3 ms of host time with the serialising of 512 sample headers -- on a short-lived thread instead of the caller's: no difference on any line, profiles/r05_q_*.)
 	static const bool threaded = [] { const char *e = getenv("CFHD_AMD_QUEUE"); return e && strcmp(e, "thread") == 0; }();
@@ -898,8 +921,7 @@ int cfhd_amd_batch_submit(cfhd_amd_batch *b)
 		b->genc->entropy().set_speculative_download(true);
 		const int rc = gop_launch(b);                      // the whole pass is on the batch's streams when this returns; nothing waits
 		if (rc) { gop_drain(b); b->genc->entropy().set_speculative_download(false); return rc; }
-		b->in_flight = true; b->queued = true;
-		return 0;
+		return pass.keep(true);
 	}
 	if (b->gpu_entropy && b->device_handoff && b->chunks.size() == 1 && !threaded) {
 		b->chunks[0]->enc.entropy().set_speculative_download(true);
@@ -909,10 +931,9 @@ int cfhd_amd_batch_submit(cfhd_amd_batch *b)
 			b->chunks[0]->enc.entropy().set_speculative_download(false);
 			return rc;
 		}
-		b->in_flight = true; b->queued = true;
-		return 0;
+		return pass.keep(true);
 	}
-	b->in_flight = true; b->queued = false;
+	pass.keep(false);
 	b->worker = std::thread([b] { b->pending = cfhd_amd_batch_roundtrip_locked(b); });
 	return 0;
 }
@@ -930,18 +951,17 @@ int cfhd_amd_batch_submit_host(cfhd_amd_batch *b, const void *frames, size_t fra
 	b->pending = -1;
 	b->host_in = (const uint8_t *)frames; b->host_in_stride = frame_stride; b->host_in_pitch = pitch;
 	b->host_out = (uint8_t *)pictures; b->host_out_stride = picture_stride; b->host_out_pitch = picture_pitch;
+	CountedSubmit pass(b);
 	if (b->gop) {
 		b->genc->entropy().set_speculative_download(true);
 		const int rc = gop_launch(b);
 		if (rc) { b->host_in = nullptr; b->host_out = nullptr; gop_drain(b); b->genc->entropy().set_speculative_download(false); return rc; }
-		b->in_flight = true; b->queued = true;
-		return 0;
+		return pass.keep(true);
 	}
 	b->chunks[0]->enc.entropy().set_speculative_download(true);
 	const int rc = batch_launch(b);
 	if (rc) { b->host_in = nullptr; b->host_out = nullptr; (void)b->chunks[0]->enc.wait(); if (b->decode) (void)b->chunks[0]->dec.wait(); b->chunks[0]->enc.entropy().set_speculative_download(false); return rc; }
-	b->in_flight = true; b->queued = true;
-	return 0;
+	return pass.keep(true);
 }
 
 long long cfhd_amd_batch_wait(cfhd_amd_batch *b)
@@ -958,6 +978,7 @@ long long cfhd_amd_batch_wait(cfhd_amd_batch *b)
 		b->host_in = nullptr; b->host_out = nullptr;
 	}
 	else b->worker.join();
+	pass_counted(b, false);
 	b->in_flight = false; b->queued = false;
 	return b->pending;
 }

@@ -84,6 +84,7 @@ struct cfhd_amd_decode_batch {
 	uint8_t *dev_out = nullptr; size_t dev_out_stride = 0; int dev_out_pitch = 0, dev_out_layout = 0;
 	// the pass in flight
 	bool in_flight = false; int count = 0; uint32_t steps = 0;
+	bool counted = false;                                          // ... is one of the device's passes in flight (cfhd_device.h device_pass_begin: begin_pass to end_pass)
 	const uint8_t *src_host = nullptr, *src_device = nullptr;      // where sample i's bytes are for the slow path: src + offsets[i]
 	std::vector<unsigned long long> offsets; std::vector<uint32_t> sizes;      // sizes: as k_dec_ingest sees them (a sample beyond 4 GB: 0xffffffff, no multiple of 4 -- the slow path's)
 	std::vector<size_t> full_sizes;
@@ -316,8 +317,14 @@ void begin_pass(cfhd_amd_decode_batch *b, const size_t *offsets, const size_t *s
 	b->offsets.assign(offsets, offsets + count); b->full_sizes.assign(sizes, sizes + count);
 	b->sizes.resize((size_t)count);
 	for (int i = 0; i < count; i++) b->sizes[i] = sizes[i] > 0xfffffffeu ? 0xffffffffu : (uint32_t)sizes[i];
+	// in front of the pass's first launch: the pass counts among the device's passes in flight until end_pass -- collected, or failed in submit
+	if (!b->counted) { device_pass_begin(b->device); b->counted = true; b->dec.entropy().set_pass_counted(true); }
 }
-void end_pass(cfhd_amd_decode_batch *b) { b->in_flight = false; b->src_host = b->src_device = nullptr; b->host_out = nullptr; }
+void end_pass(cfhd_amd_decode_batch *b)
+{
+	if (b->counted) { device_pass_end(b->device); b->counted = false; b->dec.entropy().set_pass_counted(false); }
+	b->in_flight = false; b->src_host = b->src_device = nullptr; b->host_out = nullptr;
+}
 bool refuse(const char *text) { device_set_last_error(text); return false; }
 
 // A batch of intra samples: cfhd_amd_decode_batch_create's, and -- bayer -- cfhd_amd_decode_batch_create_bayer's (the same gates and the same pass; the Bayer batch

@@ -23,6 +23,12 @@ int device_current();              // the device device_init() puts this thread 
 // `stream` from now on waits for the last stage_order_done of that stage on `device`; stage_order_done: the work `stream` holds now is that stage's latest.
 int stage_order_wait(int device, int stage, void *stream);
 int stage_order_done(int device, int stage, void *stream);
+// Passes in flight on a device: a queue raises the count when it queues a pass (cfhd_amd_batch_submit and its variants, the decode queue's submits) and lowers it
+// when the pass is collected or fails; the synchronous entry points never touch it.  Read on the host when a pass is queued, by launches that claim less of the chip
+// while other passes wait for room beside them (GpuEntropyDecoder::launch_dx).  A hint, never a correctness input: nothing orders a reader against a writer.
+void device_pass_begin(int device);
+void device_pass_end(int device);
+int device_passes_in_flight(int device);
 // The HIP device the calling thread had current when it entered the library, put back when it leaves: a handle that was dealt another GPU (unit_device)
 // must not leave the application's thread on that GPU -- its own HIP / PyTorch work would land there.  Every public entry point that can select a device holds one.
 int device_caller_save();          // the caller's current device, -1 when there is none to restore

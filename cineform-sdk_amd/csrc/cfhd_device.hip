@@ -288,7 +288,7 @@ int device_select(int dev)
 int device_current() { return t_device >= 0 ? t_device : g_device; }
 
 namespace {
-struct StageOrder { std::mutex m; hipEvent_t ev[2] = { nullptr, nullptr }; bool recorded[2] = { false, false }; };
+struct StageOrder { std::mutex m; hipEvent_t ev[2] = { nullptr, nullptr }; bool recorded[2] = { false, false }; std::atomic<int> passes{0}; /* device_pass_begin / _end */ };
 StageOrder *stage_order_of(int device)
 {
 	static std::mutex m; static std::vector<StageOrder *> all;       // (never freed: events of a device live as long as the process)
@@ -318,6 +318,10 @@ int stage_order_done(int device, int stage, void *stream)
 	o->recorded[stage] = true;
 	return 0;
 }
+// Passes in flight (cfhd_device.h): one counter per device, beside the device's stage order.
+void device_pass_begin(int device) { if (StageOrder *o = stage_order_of(device)) o->passes.fetch_add(1); }
+void device_pass_end(int device) { if (StageOrder *o = stage_order_of(device)) o->passes.fetch_sub(1); }
+int device_passes_in_flight(int device) { StageOrder *o = stage_order_of(device); return o ? o->passes.load() : 0; }
 int device_caller_save() { int d = -1; if (hipGetDevice(&d) != hipSuccess) { (void)hipGetLastError(); return -1; } return d; }
 void device_caller_restore(int dev) { if (dev >= 0) { int now = -1; if (hipGetDevice(&now) == hipSuccess && now != dev) (void)hipSetDevice(dev); } }
 

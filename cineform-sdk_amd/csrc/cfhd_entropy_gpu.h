@@ -138,6 +138,9 @@ public:
 	uint8_t *sample_slots() const { return d_samples_; }
 	size_t slot_bytes() const { return cap_; }
 	void set_verdicts(uint32_t *d_verdicts) { d_verdicts_ = d_verdicts; }
+	// The owner's pass is one of the device's passes in flight (cfhd_device.h device_pass_begin) from now on / no longer: launch() takes the shared grids of
+	// k_dec_index / k_dec_tiles when passes other than its own are in flight on the device, the solo grids otherwise.
+	void set_pass_counted(bool counted) { pass_counted_ = counted; }
 	int launch();                        // async: (H2D samples, job tables | k_dec_parse), the band decoder (k_dec_index .. k_dec_tiles by default) + k_dec_lowpass
 	int check();                         // after the stream was synchronised: 0 when every band decoded cleanly
 	float kernel_ms(int k);              // last launch(): 0 k_dec_parse (device-resident samples only), 1 band decoder (all its kernels), 2 k_dec_lowpass, 3 k_dec_plan + k_dec_index, 4 k_dec_chain + k_dec_tile_index, 5 k_dec_tiles
@@ -171,8 +174,11 @@ private:
 	void *d_tile_start_ = nullptr, *d_stats_ = nullptr, *d_repair_ = nullptr, *d_alts_ = nullptr, *d_reindex_ = nullptr, *d_alt_entries_ = nullptr; uint32_t alt_slots_ = 0;
 	void *d_idx_tables_ = nullptr, *d_entries_ = nullptr, *d_recs_ = nullptr, *d_chunk_base_ = nullptr, *d_chunk_job_ = nullptr, *d_sums_ = nullptr, *d_counters_ = nullptr;
 	uint32_t max_chunks_ = 0, *h_counters_ = nullptr; void *h_chunk_job_ = nullptr;
-	int grid_index_ = 0, grid_tiles_ = 0;
-	int device_ = 0;                       // the GPU prepare() ran on: every launch selects it for the calling thread
+	// grids of the persistent kernels k_dec_index (k_dec_reindex follows it) and k_dec_tiles: [0] solo -- every workgroup slot of every CU, the shortest launch when
+	// nothing else wants the chip --, [1] shared -- fewer workgroups per CU, so that workgroups of other passes find LDS and registers beside them
+	int grid_index_[2] = {0, 0}, grid_tiles_[2] = {0, 0};
+	bool pass_counted_ = false;
+	int device_ = 0;                      // the GPU prepare() ran on: every launch selects it for the calling thread
 	// what one launch() decodes: jobs written by k_dec_parse or flattened from the host's tables, the frames taking part, the band and lowpass jobs, and the chunks
 	// (host tables: their number; device jobs: the bound, the device numbers them)
 	struct Pass { bool device_jobs; int frames, band_jobs, lowpass_jobs; uint32_t chunks; };

@@ -11,8 +11,11 @@ namespace cfhd {
 
 int device_init();
 int device_current();
+int device_passes_in_flight(int device);      // (cfhd_device.h)
 namespace { int g_fail(hipError_t e, const char *what) { fprintf(stderr, "[cfhd_amd] %s: %s\n", what, hipGetErrorString(e)); return (int)e ? (int)e : -1; } }
 #define HIPCHK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return g_fail(_e, #expr); } while (0)
+// workgroups per CU of k_dec_index / k_dec_tiles beside other passes in flight (GpuEntropyDecoder::prepare; alone: 5 and 3, all that fit)
+enum { kDxSharedIndexPerCu = 2, kDxSharedTilesPerCu = 2 };
 
 struct GpuEntropyEncoder::Host { EntHostJobs jobs; std::vector<EntHoleGeom> geom; dev::EntFrameJob *frames = nullptr; /* pinned: async copies must not stall the host */ };
 
@@ -410,10 +413,18 @@ int GpuEntropyDecoder::prepare(const FramePlan &plan, int nframes, int16_t *d_co
 		int cus = 256;
 		(void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_current());
 		// workgroups that fit a CU at once: k_dec_index 31 KB of LDS each, k_dec_tiles its tables (22.5 KB) + the image of a tile
-		grid_index_ = cus * 5; grid_tiles_ = cus * (int)((160 * 1024) / (sizeof(uint2) * (1 << dev::DX_KM) + sizeof(uint32_t) * (dev::DX_LONG11_MAX + dev::DX_TILE_WORDS)));
-		if (const char *e = getenv("CFHD_AMD_DX_GRID_TILES")) if (atoi(e) > 0) grid_tiles_ = atoi(e);      // (sweeps: tools/dx_tile_sweep.sh)
-		if (grid_index_ < 1) grid_index_ = 1;
-		if (grid_tiles_ < 1) grid_tiles_ = 1;
+		grid_index_[0] = cus * 5; grid_tiles_[0] = cus * (int)((160 * 1024) / (sizeof(uint2) * (1 << dev::DX_KM) + sizeof(uint32_t) * (dev::DX_LONG11_MAX + dev::DX_TILE_WORDS)));
+		// The shared shapes, for launches beside other passes in flight (launch_dx): both kernels wait on LDS latency rather than on instruction issue, and resident
+		// for a whole launch with every slot taken they leave the VALU-bound kernels of the other passes no LDS to start in.  Measured under four passes in flight
+		// (profiles/dx_shared_grids_ab.txt).  CFHD_AMD_DX_SHARED=0: the solo shapes for every launch.
+		grid_index_[1] = cus * kDxSharedIndexPerCu; grid_tiles_[1] = cus * kDxSharedTilesPerCu;
+		if (grid_index_[1] > grid_index_[0]) grid_index_[1] = grid_index_[0];
+		if (grid_tiles_[1] > grid_tiles_[0]) grid_tiles_[1] = grid_tiles_[0];
+		if (const char *e = getenv("CFHD_AMD_DX_SHARED")) if (atoi(e) == 0) { grid_index_[1] = grid_index_[0]; grid_tiles_[1] = grid_tiles_[0]; }
+		// one shape for every launch (sweeps: tools/dx_index_sweep.sh, tools/dx_tile_sweep.sh; tests: a workgroup that decodes chunk after chunk, tile after tile)
+		if (const char *e = getenv("CFHD_AMD_DX_GRID_INDEX")) if (atoi(e) > 0) grid_index_[0] = grid_index_[1] = atoi(e);
+		if (const char *e = getenv("CFHD_AMD_DX_GRID_TILES")) if (atoi(e) > 0) grid_tiles_[0] = grid_tiles_[1] = atoi(e);
+		for (int k = 0; k < 2; k++) { if (grid_index_[k] < 1) grid_index_[k] = 1; if (grid_tiles_[k] < 1) grid_tiles_[k] = 1; }
 	}
 	HIPCHK(hipMalloc(&d_plan_, sizeof(dp)));
 	HIPCHK(hipMemcpy(d_plan_, &dp, sizeof(dp), hipMemcpyHostToDevice));
@@ -594,7 +605,10 @@ int GpuEntropyDecoder::launch_dx(const Pass &p)
 	}
 	HIPCHK(hipEventRecord((hipEvent_t)ev_[7], st));         // (k_dec_index is timed by itself: kernel_ms(3); the plan in front of it: kernel_ms(6))
 	// grid-stride kernels: as many workgroups as the chip holds at once, fewer when there is less work (k_dec_tiles: a workgroup per tile)
-	int g1 = grid_index_, g3 = grid_tiles_;
+	// (the shared shapes when passes other than this decoder's own are in flight on the device: a hint read here, on the host, while the pass is queued.  device_
+	// is the device the owner counts its pass on: a batch prepares its encoder and its decoder on one device)
+	const int shape = device_passes_in_flight(device_) - (pass_counted_ ? 1 : 0) > 0 ? 1 : 0;
+	int g1 = grid_index_[shape], g3 = grid_tiles_[shape];
 	if ((uint32_t)g1 * dev::DX_WAVES > p.chunks) g1 = (int)((p.chunks + dev::DX_WAVES - 1) / dev::DX_WAVES);
 	if ((uint32_t)g3 > tp.total) g3 = (int)tp.total;
 	if (g1 < 1) g1 = 1;

@@ -1,6 +1,8 @@
 #!/bin/bash
 # On the GPU box: rebuild the entropy driver with different register budgets of k_dec_index (memo entries per lane, waves per SIMD asked of the
 # compiler, workgroups per CU in the grid) and time the bench's decoder kernels.  usage: tools/dx_index_sweep.sh  (gpurun_out/dx_index_sweep.log)
+# CFHD_AMD_DX_GRID_INDEX (like CFHD_AMD_DX_GRID_TILES) forces one grid for every launch, alone or beside other passes; the library's own rule -- fewer workgroups
+# per CU beside other passes in flight, CFHD_AMD_DX_SHARED=0 to turn it off -- and the sweep that chose its shapes: DESIGN.md 5.1, profiles/dx_shared_grids_ab.txt.
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
 for cfg in "3 5 5" "2 5 5" "6 5 5" "3 5 6" "2 6 6"; do

@@ -1,6 +1,8 @@
 #!/bin/bash
 # On the GPU box: rebuild the entropy driver with different workgroup shapes of k_dec_tiles (coefficients per tile, threads, workgroups per CU in the
 # grid) and time the bench's decoder kernels.  usage: tools/dx_tile_sweep.sh  (writes gpurun_out/dx_tile_sweep.log)
+# CFHD_AMD_DX_GRID_TILES (like CFHD_AMD_DX_GRID_INDEX) forces one grid for every launch, alone or beside other passes; the library's own rule -- fewer workgroups
+# per CU beside other passes in flight, CFHD_AMD_DX_SHARED=0 to turn it off -- and the sweep that chose its shapes: DESIGN.md 5.1, profiles/dx_shared_grids_ab.txt.
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
 IFS=";" read -ra LIST <<< "${CFGS:-2048 512 2;2048 640 2;2048 384 3;2048 576 2}"; unset IFS
